@@ -2,6 +2,12 @@
 """bench.py -- throughput of one LSTM-NADE train step on synthetic 5-track piano-rolls (BASELINE.json `metric`).
 
     python bench.py --gpus N --steps K --warmup W [--workload tgt|c2|c1x5|tiny|c3|c4] [--precision fp16|bf16|fp32] [--rho 0.03]
+                    [--dump-outputs DIR] [--full]
+
+A plain run measures the headline figure only: set-up, W warm-up steps, the K timed steps, then ONE JSON line with the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed step, ...).  `--dump-outputs DIR` writes what the
+last timed step computed (loss, parameters after the step, gradient of the step) as DIR/<name>.npy; the inputs depend on the arguments
+only, so two builds can be compared output for output.  Everything else (below) is measured with `--full` only.
 
 Default workload = the north-star shape TGT [1024,256,88,5] (BASELINE.json `north_star`; C2 = configs[1] is `--workload c2`), default
 precision = fp16: the mode for which tests/test_gpu_realdims.py asserts BASELINE.json's 1e-4 on loss, per-row NLL and conditionals at
@@ -10,7 +16,10 @@ xGMI); every rank trains its own [B,T,88,5] batch (weak scaling), ONE all-reduce
 WORLD_SIZE and with --gpus N > 1, this process only LAUNCHES the N ranks (torch.distributed.run in a child process, before anything touches
 the GPU) and relays rank 0's line.
 
-Rank 0 prints ONE JSON line: the contract fields plus
+Rank 0 prints ONE JSON line: the contract fields plus, with --full,
+  ms_per_step_median  the median of K more replays, each between two HIP events;
+  breakdown_ms  HIP events around every C-ABI call of a few eager steps after the timed region;
+  hbm_traffic   the HBM-side bytes per step of the committed counter recording next to SURVEY.md 8(d)'s algorithmic bytes;
   roofline      dominant entry point of the step (HIP events around every C-ABI call) against the MFMA / HBM peak, its counters from the
                 committed rocprofv3 passes (mfma_busy, hbm_gbs, traffic), and roofline.step: per PHASE (LSTM + Dense | NADE scan) the measured
                 time, T_min and frac under two accountings -- `dense` = SURVEY.md 8(d)'s counts (every sigmoid of the reference formulation)
@@ -25,7 +34,7 @@ Rank 0 prints ONE JSON line: the contract fields plus
   cpu_baseline  the oracle's torch-CPU port of the reference formulation on the host cores (N = 1 only): median of 3 steps at C2 [256,128,88,5],
                 preparation (batch, dropout uniforms, conversions) outside the timed region and reported separately.
 `--workload c3|c4` (BASELINE configs[2] / [3]: jamming 5 x LSTM-RBM CD-10, composer DBNEncoder -> LSTM-MultiNADE) time the mode classes'
-captured train step at the reference's layer widths and print the same contract fields.
+captured train step at the reference's layer widths and print the same contract fields (with --full also breakdown_ms and roofline).
 """
 import argparse
 import json
@@ -65,9 +74,14 @@ def parse_args(argv=None):
     ap.add_argument("--workload", default="tgt", choices=sorted(WORKLOADS))
     ap.add_argument("--precision", default="fp16", choices=["fp16", "bf16", "fp32"])
     ap.add_argument("--rho", type=float, default=0.03)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sampling", action="store_true", help="skip the sampling-scan measurement (rank 0, after the timed region)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the rho = 0.5, ragged, bf16, fp32 and strong-scaling legs")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline step: median step, per-call breakdown, roofline, the extra legs, the "
+                         "sampling scan and the CPU baseline (a plain run times the headline step only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, parameters, gradient) as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-sampling", action="store_true", help="(--full) skip the sampling-scan measurement (rank 0, after the timed region)")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the rho = 0.5, ragged, bf16, fp32 and strong-scaling legs")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying a captured hipGraph")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo to rehearse N > 1 without RCCL)")
     ap.add_argument("--collective-only", action="store_true",
@@ -116,6 +130,23 @@ def ragged_lengths(B, T, seed=24):
     """lengths ~ U{T/2..T}, seed 24."""
     import numpy as np
     return np.random.Generator(np.random.PCG64(seed)).integers(T // 2, T + 1, size=B).astype(np.int32)
+
+
+DUMP_CAP = 1 << 22       # elements per dumped array (16 MB in float32); a larger array is written as a fixed sample of its elements
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array flattened and written as float32 DIR/<name>.npy.  An array of more than DUMP_CAP elements is written as
+    its elements at sorted(numpy default_rng(0).choice(n, DUMP_CAP, replace=False)): the same positions in every run and every build."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().reshape(-1)
+        if t.numel() > DUMP_CAP:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_CAP, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
 
 
 def cpu_baseline(P, M, rho=0.03, reps=3):
@@ -582,32 +613,41 @@ def main(argv=None):
         sec, loss = time_region(step_fn, a.steps)
         skipped = sum(int(g.store.skipped) for g in model._generators if getattr(g, "store", None) is not None and g.store.theta is not None)
         model.check(tolerate_overflow=True)          # (f16: a skipped step is the dynamic loss scale at work; it is reported below)
-        _lib.TIMING = {}
-        nb = min(a.steps, 3)
-        for _ in range(nb):
-            model.train_step(x, None, opt)
-        torch.cuda.synchronize()
-        timing, _lib.TIMING = _lib.TIMING, None
+        if a.dump_outputs and rank == 0:
+            stores = model._all_stores()
+            dump_outputs(a.dump_outputs, {"loss": loss, "params": torch.cat([st.theta for st in stores]),
+                                          "grads": torch.cat([st.grad for st in stores])})
+        out = {
+            "metric": "piano-roll timesteps/sec (train step), " + ("5 x LSTM-RBM CD-10 (jamming)" if w["mode"] == "jamming" else "DBNEncoder -> LSTM-MultiNADE (composer)"),
+            "value": world * B * T / sec, "unit": "timesteps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": sec * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE[a.precision], "data": "synthetic",
+            "config": {"workload": w["name"], "global_batch": world * B, "per_gpu_batch": B, "seq_len": T, "pitches": P, "tracks": M, "rho": a.rho,
+                       "parallelism": f"dp{world}"},
+            "launch": launch, "loss": float(loss), "optimizer_steps_skipped": skipped, "dp": dp_info}
+        if a.full:
+            _lib.TIMING = {}
+            nb = min(a.steps, 3)
+            for _ in range(nb):
+                model.train_step(x, None, opt)
+            torch.cuda.synchronize()
+            timing, _lib.TIMING = _lib.TIMING, None
+            if rank == 0:
+                per = {k: sum(e0.elapsed_time(e1) for e0, e1 in v) / nb for k, v in timing.items()}
+                calls = {k: len(v) // nb for k, v in timing.items()}
+                top = sorted(per.items(), key=lambda kv: -kv[1])
+                out["breakdown_ms"] = {k: round(v, 3) for k, v in top}
+                out["roofline"] = mode_roofline(w, a.precision, per, calls, B * T, sec)
         if rank == 0:
-            per = {k: sum(e0.elapsed_time(e1) for e0, e1 in v) / nb for k, v in timing.items()}
-            calls = {k: len(v) // nb for k, v in timing.items()}
-            top = sorted(per.items(), key=lambda kv: -kv[1])
-            print(json.dumps({
-                "metric": "piano-roll timesteps/sec (train step), " + ("5 x LSTM-RBM CD-10 (jamming)" if w["mode"] == "jamming" else "DBNEncoder -> LSTM-MultiNADE (composer)"),
-                "value": world * B * T / sec, "unit": "timesteps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": sec * 1e3,
-                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE[a.precision], "data": "synthetic",
-                "config": {"workload": w["name"], "global_batch": world * B, "per_gpu_batch": B, "seq_len": T, "pitches": P, "tracks": M, "rho": a.rho,
-                           "parallelism": f"dp{world}"},
-                "launch": launch, "loss": float(loss), "optimizer_steps_skipped": skipped, "dp": dp_info, "breakdown_ms": {k: round(v, 3) for k, v in top},
-                "roofline": mode_roofline(w, a.precision, per, calls, B * T, sec)}), flush=True)
+            print(json.dumps(out), flush=True)
         if multi:
             dist.barrier()
             dist.destroy_process_group()
         return 0
 
-    def timed_steps(precision, rho, batch, steps, warmup, keep=False, lengths=None):
+    def timed_steps(precision, rho, batch, steps, warmup, keep=False, lengths=None, median=False, dump=None):
         """`steps` optimiser steps of a fresh generator on a resident synthetic batch: W eager warm-up steps, capture, K replays
-        bracketed by barrier + synchronize, MAX over ranks.  Returns (seconds per step, loss, kept objects or None, launch mode)."""
+        bracketed by barrier + synchronize, MAX over ranks.  Returns (seconds per step, loss, kept objects or None, launch mode).
+        median: `steps` more replays for timed_steps.median_ms; dump: the directory rank 0 writes the last timed step's outputs to."""
         gen = RnnNade(D, HN, UNITS, keep_prob=0.9, precision=precision, seed=23, device=dev)
         gen.row0 = rank * batch                               # RNG streams keyed by the GLOBAL sequence index
         x = torch.from_numpy(synth(batch, T, P, M, 23 + rank, rho)).to(dev)
@@ -627,7 +667,9 @@ def main(argv=None):
                 torch.cuda.synchronize()
         sec, loss = time_region(step_fn, steps)
         gen._stack.check()              # a persistent launch that gave up on a bounded spin would have produced garbage: fail loudly
-        if keep:
+        if dump and rank == 0:
+            dump_outputs(dump, {"loss": loss, "params": gen.store.theta, "grads": gen.store.grad})
+        if median:
             # SURVEY 8(d) asks for the MEDIAN step: `steps` more replays, each between two HIP events (the contract's value stays the mean of
             # the bracketed region above)
             evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
@@ -645,8 +687,34 @@ def main(argv=None):
         return res
 
     # ---- the timed region: K steps of the named workload, weak scaling -------------------------------------------------------
-    sec, loss, kept, launch = timed_steps(a.precision, a.rho, B, a.steps, a.warmup, keep=True)
+    sec, loss, kept, launch = timed_steps(a.precision, a.rho, B, a.steps, a.warmup, keep=True, median=a.full, dump=a.dump_outputs)
     gen, x, opt = kept
+
+    def headline():
+        return {
+            "metric": "piano-roll timesteps/sec (train step), 5-track LSTM-NADE", "value": world * B * T / sec,
+            "unit": "timesteps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": sec * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE[a.precision],
+            "data": "synthetic",
+            "config": {"workload": w["name"], "global_batch": world * B, "per_gpu_batch": B, "seq_len": T, "pitches": P, "tracks": M, "rho": a.rho,
+                       "nade_hidden": HN, "lstm_units": UNITS, "keep_prob": 0.9, "optimizer": "TF-Adam lr 0.01 eps 1e-4 clip 5.0",
+                       "parallelism": f"dp{world}"},
+            "launch": launch, "loss": loss, "optimizer_steps_skipped": int(gen.store.skipped), "loss_scale_multiplier": float(gen.store.ls_dyn[0]), "dp": dp_info,
+            "parity": {"mode": a.precision,
+                       "gate": ("tests/test_gpu_realdims.py: loss, per-row NLL <= 1e-4 relative, conditionals <= 1e-4 absolute vs the float64 oracle at D=440, "
+                                "Hn=256, [512,256], rho in {0.03, 0.5}, persistent kernels asserted ON") if a.precision in ("fp16", "fp32") else
+                               ("bf16 operands (8 significant bits): loss 6e-6, per-row NLL 1.2e-4, conditionals 3e-4 abs, gradients 2e-3..4.5e-3 vs the "
+                                "float64 oracle (tests/test_gpu_realdims.py, printed bounds)")}}
+
+    if not a.full:                    # a plain run: the headline figure only
+        if rank == 0:
+            print(f"# loss {loss:.4f}  step {sec * 1e3:.2f} ms", file=sys.stderr)
+            print(json.dumps(headline()), flush=True)
+        if multi:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
+
     nnz_row = float(x.sum()) / (B * T)            # active visibles per row, counted on the device (a prefix of them are targets: T-1 of T steps)
     # per-entry-point HIP-event breakdown: the same steps launched eagerly right after the timed region (events cannot be recorded
     # inside a graph replay); every C-ABI call is bracketed by events on the stream it launches on
@@ -771,25 +839,13 @@ def main(argv=None):
     survey_bytes = N * D + 2.0 * 2 * N * 6 * (R1 + R2) + 2.0 * 4 * N * (HN + D) + 4.0 * N * D + 7 * 4 * N_PARAMS
     traffic_step = step_traffic(a.workload, a.precision, survey_bytes)
 
-    out = {
-        "metric": "piano-roll timesteps/sec (train step), 5-track LSTM-NADE", "value": world * B * T / sec,
-        "unit": "timesteps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": sec * 1e3,
+    out = headline()
+    out.update({
         "ms_per_step_median": getattr(timed_steps, "median_ms", None),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE[a.precision],
-        "data": "synthetic",
-        "config": {"workload": w["name"], "global_batch": world * B, "per_gpu_batch": B, "seq_len": T, "pitches": P, "tracks": M, "rho": a.rho,
-                   "nade_hidden": HN, "lstm_units": UNITS, "keep_prob": 0.9, "optimizer": "TF-Adam lr 0.01 eps 1e-4 clip 5.0",
-                   "parallelism": f"dp{world}"},
-        "launch": launch, "loss": loss, "optimizer_steps_skipped": int(gen.store.skipped), "loss_scale_multiplier": float(gen.store.ls_dyn[0]), "dp": dp_info,
-        "parity": {"mode": a.precision,
-                   "gate": ("tests/test_gpu_realdims.py: loss, per-row NLL <= 1e-4 relative, conditionals <= 1e-4 absolute vs the float64 oracle at D=440, "
-                            "Hn=256, [512,256], rho in {0.03, 0.5}, persistent kernels asserted ON") if a.precision in ("fp16", "fp32") else
-                           ("bf16 operands (8 significant bits): loss 6e-6, per-row NLL 1.2e-4, conditionals 3e-4 abs, gradients 2e-3..4.5e-3 vs the "
-                            "float64 oracle (tests/test_gpu_realdims.py, printed bounds)")},
         "roofline": roof,
         "hbm_traffic": traffic_step,
         "breakdown_ms": {k: round(v[0], 3) for k, v in top},
-    }
+    })
     out.update(extras)
     if not a.no_sampling:
         out["sampling"] = sampling_scan(gen, P, M)

@@ -1,4 +1,4 @@
-"""Summarise two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of `python3 bench.py --no-cpu-baseline --no-graph --steps 3 --warmup 1`
+"""Summarise two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of `python3 bench.py --full --no-cpu-baseline --no-graph --steps 3 --warmup 1`
 into per-kernel HBM-side bytes per launch (MI355X_MICROARCH.md, HBM section: bytes = counter * 1024; FETCH_SIZE doubled on gfx950).
 Usage: python profiles/pmc_traffic.py <dir of the FETCH_SIZE pass> <dir of the WRITE_SIZE pass> <out.json> [workload label] [steps recorded]
 [sources sha16 (profiles/tools/source_hash.py)]"""
@@ -38,7 +38,7 @@ def main():
         wb = write.get(name, [0.0, 0])[0] * 1024.0
         out["kernels"][name] = {"calls": calls, "fetch_size_bytes_raw": fb / calls, "fetch_bytes_x2_corrected": 2 * fb / calls,
                                 "write_bytes": wb / calls, "hbm_side_bytes_per_launch": (2 * fb + wb) / calls}
-    # optimiser steps the passes really contain (bench.py runs a few eager steps for its per-call timing besides --steps / --warmup): one
+    # optimiser steps the passes really contain (bench.py --full runs a few eager steps for its per-call timing besides --steps / --warmup): one
     # clip_adam_kernel launch per step
     for name, k in out["kernels"].items():
         if name.startswith("clip_adam_kernel"):

@@ -1,4 +1,4 @@
-"""Summarise one rocprofv3 --pmc pass of SQ / GRBM counters over `python3 bench.py --no-cpu-baseline --no-sampling --no-graph --steps 3
+"""Summarise one rocprofv3 --pmc pass of SQ / GRBM counters over `python3 bench.py --full --no-cpu-baseline --no-sampling --no-graph --steps 3
 --warmup 1` into per-kernel averages per launch and two derived ratios:
   mfma_busy_frac = SQ_VALU_MFMA_BUSY_CYCLES / (4 SIMDs x 256 CUs x GRBM_GUI_ACTIVE / 8)   (MI355X_MICROARCH.md: the counter is in
                    cycles, 32 per v_mfma_f32_32x32x16_bf16, summed over the chip's SIMDs; GRBM_GUI_ACTIVE comes back summed over the 8

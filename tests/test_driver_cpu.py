@@ -78,10 +78,27 @@ def test_bench_cli_contract():
     tree = ast.parse(src)
     flags = {a.value for n in ast.walk(tree) if isinstance(n, ast.Call) and getattr(n.func, "attr", "") == "add_argument"
              for a in n.args if isinstance(a, ast.Constant)}
-    assert {"--gpus", "--steps", "--warmup"} <= flags
+    assert {"--gpus", "--steps", "--warmup", "--full", "--dump-outputs"} <= flags
     for key in ('"metric"', '"value"', '"unit"', '"n_gpus"', '"steps"', '"warmup"', '"ms_per_step"', '"higher_is_better"', '"scaling"',
                 '"vs_baseline"', '"dtype"', '"data"', '"config"', '"roofline"', '"cpu_baseline"'):
         assert key in src, key
+
+
+def test_bench_dump_outputs_float32_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: every array as float32 DIR/<name>.npy; one larger than DUMP_CAP elements as the same fixed sample in every run."""
+    import numpy as np
+    import torch
+    import bench
+    big = torch.arange(bench.DUMP_CAP + 12345, dtype=torch.float64)
+    arrays = {"loss": torch.tensor([2.5]), "params": torch.arange(1000, dtype=torch.float32).reshape(10, 100), "grads": big}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in arrays}
+    assert all(v.dtype == np.float32 and v.ndim == 1 for v in got.values())
+    assert got["loss"].tolist() == [2.5] and np.array_equal(got["params"], np.arange(1000, dtype=np.float32))
+    g = got["grads"]
+    assert g.size == bench.DUMP_CAP and np.all(np.diff(g) > 0) and np.all(g == np.round(g)) and g[0] >= 0 and g[-1] < big.numel()
+    assert np.array_equal(g, np.load(str(tmp_path / "b" / "grads.npy")))
 
 
 def test_pack_epoch_dates_the_repacked_sampling_weights():
