@@ -43,9 +43,9 @@ enum { MNN_STREAM_DROPOUT = 0, MNN_STREAM_NADE = 1, MNN_STREAM_RBM_H = 2, MNN_ST
 
 /* ABI version of THIS header: bumped whenever a signature or a descriptor struct changes.  mnn_version() returns the value the library
  * was built with; a loader must compare the two before its first call (multinn_amd/_lib.py load() does) -- a library built for another
- * version reads garbage arguments without any diagnosis otherwise.  121 (round 6): + mnn_gemm_tn_rows.  120 (round 6): mnn_step_increment gained `ls_dyn`, `ls_good`, `grow_after` (dynamic f16 loss scale).  119 (round 6): mnn_det_dense_job gained `Wp`, + mnn_det_dense_pack / _pack_bytes.  118 (round 6): mnn_det_lstm_job gained `Wp`, + mnn_det_lstm_pack / _pack_bytes, mnn_generate_scan_workspace_bytes gained `n_in`.  117 (round 6): + mnn_lstm_cluster_bwd_ok, + mnn_ragged_index / mnn_rows_gather16 / mnn_rows_scatter_f32, `n_rows_dev` on the gated NADE forwards and mnn_nade_logprob_bwd, `inv` / `hdr` on mnn_pianoroll_shift_timemajor_t, + mnn_lstm_resident_{fwd,bwd}_multi / mnn_lstm_cluster_{fwd,bwd}_multi / _bwd_multi_ok, `unsafe` on mnn_nade_logprob_fwd_gated, `unsafe` on mnn_nade_logprob_bwd.  116: + mnn_lstm_cluster_ok / _fwd / _bwd.  115: mnn_step_increment gained `sumsq`, `clip_norm`.  114: + mnn_lstm_resident_ok / _fwd / _bwd.  113: mnn_pianoroll_shift_timemajor_t gained `count`.  112: + mnn_generate_scan.  111: mnn_rbm_free_energy gained `p_h`.  110: mnn_clip_adam_step gained `skipped`; the dtype arguments of
+ * version reads garbage arguments without any diagnosis otherwise.  122: conditional sampling -- a trailing `given` on mnn_nade_sample and mnn_generate_scan, mnn_nade_sample_job gained `given`.  121 (round 6): + mnn_gemm_tn_rows.  120 (round 6): mnn_step_increment gained `ls_dyn`, `ls_good`, `grow_after` (dynamic f16 loss scale).  119 (round 6): mnn_det_dense_job gained `Wp`, + mnn_det_dense_pack / _pack_bytes.  118 (round 6): mnn_det_lstm_job gained `Wp`, + mnn_det_lstm_pack / _pack_bytes, mnn_generate_scan_workspace_bytes gained `n_in`.  117 (round 6): + mnn_lstm_cluster_bwd_ok, + mnn_ragged_index / mnn_rows_gather16 / mnn_rows_scatter_f32, `n_rows_dev` on the gated NADE forwards and mnn_nade_logprob_bwd, `inv` / `hdr` on mnn_pianoroll_shift_timemajor_t, + mnn_lstm_resident_{fwd,bwd}_multi / mnn_lstm_cluster_{fwd,bwd}_multi / _bwd_multi_ok, `unsafe` on mnn_nade_logprob_fwd_gated, `unsafe` on mnn_nade_logprob_bwd.  116: + mnn_lstm_cluster_ok / _fwd / _bwd.  115: mnn_step_increment gained `sumsq`, `clip_norm`.  114: + mnn_lstm_resident_ok / _fwd / _bwd.  113: mnn_pianoroll_shift_timemajor_t gained `count`.  112: + mnn_generate_scan.  111: mnn_rbm_free_energy gained `p_h`.  110: mnn_clip_adam_step gained `skipped`; the dtype arguments of
  * mnn_pianoroll_shift_timemajor_t / mnn_grad_rows_fanout and the `f16` descriptor fields of round 3 are part of it. */
-#define MNN_ABI_VERSION 121
+#define MNN_ABI_VERSION 122
 int mnn_version(void);
 const char* mnn_last_error(void);
 
@@ -356,6 +356,8 @@ int mnn_nade_logprob_fwd_mfma_f32(mnn_stream_t s, int tracks, int N, int D, int 
  * mnn_nade_sample (nade.py:231-308): deterministic-order kernel, Bernoulli u < sigmoid(l/T);
  *   u = Philox(stream 1, row = row0+n, sub, elem = m*D+i); temperature <= 0 -> threshold 0.5.
  *   D <= 1536 (a row's logits, b_dec and draws are parked in LDS during the scan); Hn <= 256.
+ *   given (NULL allowed): u8 codes with the strides of `samples` -- 0 / 1 clamps the visible to that value (it is not drawn, its uniform is
+ *   left unused, its value moves the NADE's state like a draw), 255 leaves it free.  nll is that of the emitted vector, clamped visibles included.
  * ------------------------------------------------------------------------------------------ */
 int mnn_nade_logprob_fwd(mnn_stream_t s, int tracks, int N, int D, int Hn, const uint8_t* v, long v_track_stride,
                          const float* bias, int ld_bias, const float* w_enc, const float* w_dec, const float* row_weight,
@@ -369,7 +371,7 @@ int mnn_nade_logprob_bwd(mnn_stream_t s, int tracks, int N, int D, int Hn, const
                                               instantiations are launched, one leaves at once.  NULL: the direct form */);
 int mnn_nade_sample(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
                     const float* w_dec, float temperature, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
-                    long s_track_stride, int s_row_stride, int s_elem_stride, float* nll);
+                    long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given);
 /* mnn_nade_sample for SEVERAL single-NADE generators in ONE launch (multinn_feedback.py:196: every per-track generator's sample_single in a
  * step of the feedback scan).  `jobs`: HOST array of 1..8 descriptors (passed to the kernel by value): the generator's Dense output matrix
  * bias [N, ld_bias] (b_enc at column 0, b_dec at column Hn), its weights [D, Hn], its Philox seed and where its samples go
@@ -379,6 +381,7 @@ typedef struct {
     const float* w_enc; const float* w_dec;
     uint64_t seed;
     uint8_t* samples; float* nll;            /* nll [N] or NULL */
+    const uint8_t* given;                    /* NULL or codes [N, D] with the strides of samples (see mnn_nade_sample) */
 } mnn_nade_sample_job;
 int mnn_nade_sample_multi(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, float temperature,
                           uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride);
@@ -527,14 +530,15 @@ int mnn_dense_det(mnn_stream_t s, int B, int njobs, const mnn_det_dense_job* job
  * one host loop (nothing synchronised: capturable into a hipGraph).  layers: HOST array of the stack's master weights (TF layout); Dense W
  * [units_last, n_out], n_out = tracks * (Hn + D) (b_enc blocks, then b_dec blocks); n_in = tracks * D (a sample is the next input).
  * samples u8 [B, num_steps, tracks * D] (feature m D + i for one NADE, i tracks + m for several: rnn_multinade.py:313-314).  Same bits as the
- * single-step entry points; workspace: mnn_generate_scan_workspace_bytes(), 256-byte aligned, caller-owned. */
+ * single-step entry points; workspace: mnn_generate_scan_workspace_bytes(), 256-byte aligned, caller-owned.  given (NULL allowed): codes u8
+ * [B, num_steps, n_in] in the layout of samples (mnn_nade_sample's `given`); clamped values are what the next LSTM step reads. */
 #define MNN_SCAN_MAX_LAYERS 8
 typedef struct { const float* W; const float* bias; int units; } mnn_scan_lstm_layer;
 size_t mnn_generate_scan_workspace_bytes(int B, int n_in, int n_layers, const mnn_scan_lstm_layer* layers, int n_out);
 int mnn_generate_scan(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
                       const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D, int Hn,
                       const float* w_enc, const float* w_dec, float temperature, uint64_t seed, uint32_t row0, uint8_t* samples,
-                      void* workspace, size_t workspace_bytes);
+                      void* workspace, size_t workspace_bytes, const uint8_t* given);
 
 /* ------------------------------------------------------------------------------------------
  * Data-parallel exchange (the gradients of utils/training.py:151-177 as ONE flat f32 buffer): RCCL over xGMI, one

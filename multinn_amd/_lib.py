@@ -9,7 +9,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MULTINN_HIP_LIB", os.path.join(HERE, "libmultinn_hip.so"))   # override: A/B builds of the same ABI
 
-ABI_VERSION = 121          # == MNN_ABI_VERSION of include/multinn_hip.h; load() refuses a library built for another one
+ABI_VERSION = 122          # == MNN_ABI_VERSION of include/multinn_hip.h; load() refuses a library built for another one
 F32, BF16, U8, F16 = 0, 1, 2, 3
 GEMM_ACCUMULATE, GEMM_ATOMIC, GEMM_A_KBLOCK32 = 1, 2, 8
 
@@ -41,7 +41,7 @@ SIGNATURES = {
     "mnn_dropout_bwd": (_i, [_p, _p, _p, _i, _i, _i, _f, _u64, _p, _u32, _i, _i, _i]),
     "mnn_nade_logprob_fwd": (_i, [_p, _i, _i, _i, _i, _p, _l, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
     "mnn_nade_logprob_bwd": (_i, [_p, _i, _i, _i, _i, _p, _l, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "mnn_nade_sample": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p, _f, _u64, _u32, _u32, _p, _l, _i, _i, _p]),
+    "mnn_nade_sample": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p, _f, _u64, _u32, _u32, _p, _l, _i, _i, _p, _p]),
     "mnn_rbm_workspace_bytes": (_sz, [_i, _i]),
     "mnn_rbm_gibbs": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _u64, _u32, _p, _u32, _p, _p, _p]),
     "mnn_rbm_gibbs_stepped": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _u64, _u32, _p, _u32, _p, _p, _p, _p]),
@@ -63,7 +63,7 @@ SIGNATURES = {
     "mnn_det_lstm_pack": (_i, [_p, _p, _i, _i, _p]),
     "mnn_det_dense_pack_bytes": (_sz, [_i, _i]),
     "mnn_det_dense_pack": (_i, [_p, _p, _i, _i, _i, _p]),
-    "mnn_generate_scan": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _f, _u64, _u32, _p, _p, _sz]),
+    "mnn_generate_scan": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _f, _u64, _u32, _p, _p, _sz, _p]),
     "mnn_comm_unique_id": (_i, [_p]),
     "mnn_comm_init": (_i, [C.POINTER(_p), _i, _i, _p]),
     "mnn_allreduce_flat": (_i, [_p, _p, _p, _l]),
@@ -78,7 +78,7 @@ class DetLstmJob(C.Structure):
 
 class NadeSampleJob(C.Structure):
     """mnn_nade_sample_job (include/multinn_hip.h)."""
-    _fields_ = [("bias", _p), ("ld_bias", _i), ("w_enc", _p), ("w_dec", _p), ("seed", _u64), ("samples", _p), ("nll", _p)]
+    _fields_ = [("bias", _p), ("ld_bias", _i), ("w_enc", _p), ("w_dec", _p), ("seed", _u64), ("samples", _p), ("nll", _p), ("given", _p)]
 
 
 class ScanLstmLayer(C.Structure):

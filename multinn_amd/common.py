@@ -51,7 +51,8 @@ class ScanGraphs:
     A scan is `num_steps` x {sample, LSTM step, Dense}: a dozen small launches per generated step, ~0.5 ms of host time
     against ~0.1 ms of device time when launched eagerly.  The whole scan -- intro pass, weight packing and every
     step, each with its own RNG counter baked into its node -- is captured once per (shape, num_steps, seed) and
-    replayed; inputs are copied into the captured buffer, the result is a copy of the captured output.
+    replayed; inputs are copied into the captured buffer, the result is a copy of the captured output.  A conditioned scan takes its codes
+    (given_codes) as a second static input, copied in the same way: the caller's key records only whether there are any.
     MULTINN_GENERATE_GRAPH=0 keeps the eager loop."""
 
     def __init__(self, max_entries=4):
@@ -63,32 +64,83 @@ class ScanGraphs:
     def enabled(x):
         return x.is_cuda and os.environ.get("MULTINN_GENERATE_GRAPH", "1") != "0" and not torch.cuda.is_current_stream_capturing()
 
-    def run(self, key, x, scan, warm, after_capture):
+    def run(self, key, x, scan, warm, after_capture, extra=None):
         """scan(static_x) -> output tensor (captured); warm(static_x): a short eager run that creates parameters and
-        workspaces before the capture; after_capture(): drop host-side caches that now point into the graph's pool."""
+        workspaces before the capture; after_capture(): drop host-side caches that now point into the graph's pool.
+        extra (optional, e.g. the codes of a conditioned scan): a second input, then scan(static_x, static_extra) and
+        warm(static_x, static_extra)."""
         ent = self._cache.get(key)
         if ent is None:
             static_x = x.clone()
+            static_e = None if extra is None else extra.clone()
+            args = (static_x,) if extra is None else (static_x, static_e)
             cur = torch.cuda.current_stream()
             side = torch.cuda.Stream()
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                warm(static_x)
+                warm(*args)
             cur.wait_stream(side)
             g = torch.cuda.CUDAGraph()
             with graph_capture(g, capture_error_mode="thread_local"):
-                out = scan(static_x)
+                out = scan(*args)
             after_capture()
-            ent = (g, static_x, out)
+            ent = (g, static_x, out, static_e)
             self._cache[key] = ent
             while len(self._cache) > self._max:
                 self._cache.popitem(last=False)
         else:
             self._cache.move_to_end(key)
-        g, static_x, out = ent
+        g, static_x, out, static_e = ent
         static_x.copy_(x)
+        if static_e is not None:
+            static_e.copy_(extra)
         g.replay()
         return out.clone()
+
+
+# --------------------------------------------------------------------------------------------
+# Conditional generation.  A visible of a sampling scan is given a code: 0 or 1 clamps it to that value (it is not drawn; its value is fed
+# forward exactly like a draw), 255 leaves it free (ops.nade_sample / generate_scan: `given`).
+GIVEN_FREE = 255
+
+
+def _check_mask(given_shape, given_mask):
+    if given_mask.dtype != torch.bool:
+        raise ValueError(f"given_mask must be bool, got {given_mask.dtype}")
+    try:
+        ok = torch.broadcast_shapes(tuple(given_mask.shape), tuple(given_shape)) == tuple(given_shape)
+    except RuntimeError:
+        ok = False
+    if not ok:
+        raise ValueError(f"given_mask of shape {tuple(given_mask.shape)} does not broadcast to {tuple(given_shape)} ([M], [P, M] or [B, steps, P, M])")
+
+
+def given_codes(given, given_mask=None, shape=None):
+    """(given, given_mask) -> the scan's tri-state codes, u8 [B, num_steps, P, M] on given's device (no value is read back to the host).
+    given: u8 [B, num_steps, P, M], any nonzero value is a note on; given_mask: bool broadcastable to it ([M]: whole tracks, [P, M]: pitch
+    ranges, the full shape: any cells), None = every cell is given.  shape (optional): the shape the caller expects.  Cells under the mask
+    get 0 / 1, the others GIVEN_FREE.  `.reshape(B, steps, P * M)` is both the joint order p M + m and the MultiNADE order i tracks + m."""
+    if given.dtype != torch.uint8 or given.dim() != 4:
+        raise ValueError(f"given must be u8 [B, num_steps, P, M], got {given.dtype} {tuple(given.shape)}")
+    if shape is not None and tuple(given.shape) != tuple(shape):
+        raise ValueError(f"given has shape {tuple(given.shape)}, expected {tuple(shape)}")
+    on = (given != 0).to(torch.uint8)
+    if given_mask is None:
+        return on.contiguous()
+    _check_mask(given.shape, given_mask)
+    free = torch.full((), GIVEN_FREE, dtype=torch.uint8, device=given.device)
+    return torch.where(given_mask.to(given.device), on, free).contiguous()
+
+
+def given_tracks(given_mask, shape):
+    """Host summary of a mask over [B, num_steps, P, M]: (whole, some) -- per track, whether every cell / any cell of it is given."""
+    M = shape[-1]
+    if given_mask is None:
+        return [True] * M, [True] * M
+    _check_mask(shape, given_mask)
+    m = given_mask.detach().to("cpu")
+    per = m.reshape(-1, M) if m.dim() > 0 and m.shape[-1] == M else m.reshape(-1, 1).expand(-1, M)     # (broadcast axes repeat what they hold)
+    return [bool(v) for v in per.all(0)], [bool(v) for v in per.any(0)]
 
 
 # --------------------------------------------------------------------------------------------

@@ -412,6 +412,8 @@ extern "C" int mnn_dense_det(mnn_stream_t s, int B, int njobs, const mnn_det_den
 // the sample -> Dense }.  Everything is enqueued on the caller's stream from this one host loop (4 launches per generated step for a
 // two-layer stack; nothing is synchronised), so the call is capturable into a hipGraph like any other entry point; states ping-pong in the
 // caller's workspace.  Bits: exactly those of the single-step entry points above (oracle/det.py rnn_nade_generate restates the scan).
+// given (optional, laid out like samples): step st's codes go to its sample call; the LSTM step reads the sample buffer, so clamped values
+// feed forward by themselves.
 // ------------------------------------------------------------------------------------------------------------------------------------
 static size_t scan_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -429,7 +431,7 @@ extern "C" size_t mnn_generate_scan_workspace_bytes(int B, int n_in, int n_layer
 extern "C" int mnn_generate_scan(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
                                  const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
                                  int Hn, const float* w_enc, const float* w_dec, float temperature, uint64_t seed, uint32_t row0,
-                                 uint8_t* samples, void* workspace, size_t workspace_bytes) {
+                                 uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given) {
     MNN_REQUIRE(B > 0 && n_intro > 0 && num_steps >= 0 && intro && n_in > 0 && n_layers > 0 && n_layers <= MNN_SCAN_MAX_LAYERS && layers,
                 "mnn_generate_scan: B, n_intro > 0, 1..%d layers", MNN_SCAN_MAX_LAYERS);
     MNN_REQUIRE(dense_W && tracks > 0 && D > 0 && Hn > 0 && n_out == tracks * (Hn + D) && n_in == tracks * D && w_enc && w_dec && samples,
@@ -503,7 +505,7 @@ extern "C" int mnn_generate_scan(mnn_stream_t s, int B, int n_intro, int num_ste
     for (int st = 0; st < num_steps; ++st) {
         uint8_t* smp = samples + (size_t)st * n_in;            // samples[:, st, :]; feature m D + i (one NADE) or i tracks + m (rnn_multinade.py:313-314)
         rc = mnn_nade_sample(s, tracks, B, D, Hn, out, ld_out, w_enc, w_dec, temperature, seed, row0, (uint32_t)st, smp,
-                             tracks > 1 ? 1 : D, row_stride, tracks > 1 ? tracks : 1, nullptr);
+                             tracks > 1 ? 1 : D, row_stride, tracks > 1 ? tracks : 1, nullptr, given ? given + (size_t)st * n_in : nullptr);
         if (rc != MNN_OK) return rc;
         rc = stack_step(smp, row_stride);
         if (rc != MNN_OK) return rc;

@@ -728,15 +728,20 @@ struct SampleJob {
     const float* w_enc; const float* w_dec;                  // [D, Hn] of this track
     uint64_t seed; uint32_t elem0;                           // Philox key; element index of visible 0 (m D inside a MultiNADE, 0 otherwise)
     uint8_t* samples; float* nll;                            // samples[row * s_row_stride + i * s_elem_stride]; nll [N] or NULL
+    const uint8_t* given;                                    // NULL or indexed like samples: 0 / 1 = the visible is clamped to that value, 255 = drawn
 };
 #define SAMPLE_MAX_JOBS 8
 struct SampleJobs { SampleJob job[SAMPLE_MAX_JOBS]; };
 
 // TMODE: 0 = threshold draws (temperature None / <= 0), 1 = temperature 1, 2 = any other temperature.  FULL: Hn == 256, no lane is idle.
-template <int TMODE, bool FULL, bool SPEC>
+// GIVEN: conditional sampling -- a visible whose code in job.given is 0 / 1 is not drawn, its value is written and fed forward like a draw
+// (its uniform is left unused: every free visible reads the uniform of the unconditioned scan); logits are parked as before, so nll is that of
+// the emitted vector.
+template <int TMODE, bool FULL, bool SPEC, bool GIVEN>
 __global__ void __launch_bounds__(256)
 nade_sample_kernel(SampleJobs J, int N, int D, int Hn, float temperature, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char nade_sample_smem[];       // per wave: logit / log term [Dp] f32, b_dec [Dp] f32, draws [Dp] u8, 256 uniforms
+    // per wave: logit / log term [Dp] f32, b_dec [Dp] f32, draws [Dp] u8, 256 uniforms (, GIVEN: the row's codes [Dp] u8)
+    extern __shared__ __attribute__((aligned(16))) unsigned char nade_sample_smem[];
     // blockIdx.y = job: a track of one MultiNADE (mnn_nade_sample) or one of several generators sampled together (mnn_nade_sample_multi)
     const SampleJob& jb = J.job[blockIdx.y];
     const float* __restrict__ bias = jb.bias;
@@ -752,6 +757,7 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, float temperature, uint32
     float* sbd = reinterpret_cast<float*>(nade_sample_smem) + (size_t)(4 + wv) * Dp;
     unsigned char* son = nade_sample_smem + (size_t)32 * Dp + (size_t)wv * Dp;
     float* su = reinterpret_cast<float*>(nade_sample_smem + (size_t)36 * Dp) + wv * 256;    // uniforms of Philox blocks b0 .. b0 + 63
+    unsigned char* sg = nade_sample_smem + (size_t)36 * Dp + 4096 + (size_t)wv * Dp;
     const float* __restrict__ we = jb.w_enc;
     const float* __restrict__ wd = jb.w_dec;
     const float* __restrict__ bd = bias + (size_t)row * ld_bias + jb.dec_off;
@@ -777,6 +783,10 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, float temperature, uint32
         }
     };
     for (int i = lane; i < D; i += 64) sbd[i] = bd[i];      // the row's b_dec: one coalesced pass into LDS, a broadcast read per visible
+    if (GIVEN) {                                            // the row's codes likewise (a job without them: every visible is drawn)
+        const uint8_t* __restrict__ gv = jb.given;
+        for (int i = lane; i < D; i += 64) sg[i] = gv != nullptr ? gv[(size_t)row * s_row_stride + (size_t)i * s_elem_stride] : (uint8_t)255;
+    }
 #pragma unroll
     for (int k = 0; k < RING; ++k) {
         fetch(k, k);
@@ -817,8 +827,11 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, float temperature, uint32
                 // no dependence on the sigmoid / draw chain below and fills its issue slots (a draw of 1 recomputes it)
                 const float spec = SPEC ? dot((k + 1) % RING) : 0.f;
                 const float l = sbd[i] + acc;
+                const int code = GIVEN ? __builtin_amdgcn_readfirstlane((int)sg[i]) : 255;     // (the same byte in every lane: a uniform branch)
                 bool on;
-                if (TMODE != 0) {
+                if (GIVEN && code != 255) {                 // clamped: the given value moves a / h like a draw (and the speculation holds as for one)
+                    on = code != 0;
+                } else if (TMODE != 0) {
                     on = draw_below(u_cur, TMODE == 1 ? l : l / temperature);
                 } else {
                     on = prob_at_least_half(l);              // nade.py:278-279
@@ -880,13 +893,15 @@ extern "C" int mnn_sch_trace_read(long long* host) { return hipMemcpyFromSymbol(
 #else
 #define SCH_TR(k, c) do { } while (0)
 #endif
-template <int TMODE, bool FULL, int G>
+// GIVEN: as nade_sample_kernel.  A clamped lane's `on` is its code; the tie ballot counts free lanes only, and the first 1 of a pass -- given or
+// drawn -- moves the state.
+template <int TMODE, bool FULL, int G, bool GIVEN>
 __global__ void __launch_bounds__(64)
 nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, float temperature, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
     constexpr int NB = sch_nb(G);
     constexpr int KSH = G == 16 ? 2 : 3;                      // lane l decides visible l >> KSH of the chunk
     constexpr int WAITN = (NB - 2) * 2 * G;                   // copies that may still be in flight when a chunk is needed: the NB - 2 chunks behind it
-    // ring [NB][w_dec | w_enc][G][256] f32 (64 KB) | logit / log term [Dp] f32 | b_dec [Dp] f32 | 256 uniforms | draws [Dp] u8
+    // ring [NB][w_dec | w_enc][G][256] f32 (64 KB) | logit / log term [Dp] f32 | b_dec [Dp] f32 | 256 uniforms | draws [Dp] u8 (| GIVEN: codes [Dp] u8)
     extern __shared__ __attribute__((aligned(16))) unsigned char nade_sample_smem[];
     float* ring = reinterpret_cast<float*>(nade_sample_smem);
     const int Dp = (D + 3) & ~3;
@@ -894,6 +909,7 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, float temperature, 
     float* sbd = sp + Dp;
     float* su = sbd + Dp;
     unsigned char* son = reinterpret_cast<unsigned char*>(su + 256);
+    unsigned char* sg = son + Dp;
     const SampleJob& jb = J.job[blockIdx.y];
     const float* __restrict__ bias = jb.bias;
     const int ld_bias = jb.ld_bias;
@@ -947,6 +963,10 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, float temperature, 
         h[q] = det_sigmoid(a[q]);
     }
     for (int i = lane; i < D; i += 64) sbd[i] = bd[i];
+    if (GIVEN) {
+        const uint8_t* __restrict__ gv = jb.given;
+        for (int i = lane; i < D; i += 64) sg[i] = gv != nullptr ? gv[(size_t)row * s_row_stride + (size_t)i * s_elem_stride] : (uint8_t)255;
+    }
     const uint32_t e0 = jb.elem0;
     uint32_t b0 = e0 >> 2;
     auto refill = [&]() {                                    // (an LDS write waits for every copy in flight -- the compiler cannot tell them apart: once per ~31 chunks)
@@ -964,7 +984,7 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, float temperature, 
     // what a chunk's passes read besides h: its eight w_dec rows -- visibles (2 p, 2 p + 1) side by side, one packed FMA serves both --, the lane's
     // b_dec and uniform.  (Measured and dropped: fetching them one chunk AHEAD, under the previous chunk's passes -- 47.0 vs 46.5 us per call: a lone
     // wave spends ~10 cycles per instruction of this chain whatever flies beside it.)
-    struct ChunkIn { nade_f32x2 w[G / 2][4]; float bdv, u; };
+    struct ChunkIn { nade_f32x2 w[G / 2][4]; float bdv, u; int code; };
     auto fetch_in = [&](int slot, int c, ChunkIn& ci) {
         const int i0 = c * G;
         // (Hn == 256, D % 8 != 0: the last chunk was copied from row D - 8 on -- visible i0 + k sits rsh rows further down; rows past D are never decided)
@@ -979,6 +999,7 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, float temperature, 
             }
         const int ivc = min(i0 + kq, D - 1);
         ci.bdv = sbd[ivc];
+        ci.code = GIVEN ? (int)sg[ivc] : 255;
         ci.u = 0.f;
         if (TMODE != 0) {
             const uint32_t e_last = e0 + (uint32_t)min(i0 + G - 1, D - 1);
@@ -1055,20 +1076,22 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, float temperature, 
                     if (sfrom == 0) { asm volatile("" ::"v"(l)); SCH_TR(5, c); }
 #endif
                     const bool open = mine && kq >= sfrom;   // lanes whose visible is still undecided
+                    const bool drawn = !GIVEN || ci.code == 255;     // (a clamped lane takes its code below, whatever its comparison says)
                     bool on;
                     if (TMODE != 0) {                        // u < det_sigmoid(l / T), settled by the hardware sigmoid unless within 1e-4 of a tie (draw_below)
                         const float xa = TMODE == 1 ? l : l / temperature;
                         const float r = sig_approx(xa);
                         const float d = u - r;
                         const bool tie = !(fabsf(d) > 1e-4f * r + 1e-30f);
-                        if (__builtin_amdgcn_ballot_w64(tie && open) == 0ull) on = d < 0.f;
+                        if (__builtin_amdgcn_ballot_w64(tie && open && drawn) == 0ull) on = d < 0.f;
                         else on = u < det_sigmoid(xa);
                     } else {                                 // nade.py:278-279
                         const float d = sig_approx(l) - 0.5f;
                         const bool tie = !(fabsf(d) > 1e-4f);
-                        if (__builtin_amdgcn_ballot_w64(tie && open) == 0ull) on = d > 0.f;
+                        if (__builtin_amdgcn_ballot_w64(tie && open && drawn) == 0ull) on = d > 0.f;
                         else on = det_sigmoid(l) >= 0.5f;
                     }
+                    if (GIVEN && !drawn) on = ci.code != 0;
                     const uint64_t m = __builtin_amdgcn_ballot_w64(on && open) & (G == 16 ? 0x1111111111111111ull : 0x0101010101010101ull);
                     const int f = m != 0ull ? (int)(__builtin_ctzll(m) >> KSH) : G;     // the first draw of 1 (uniform)
 #ifdef SCH_TRACE
@@ -1113,26 +1136,31 @@ static hipError_t sample_chunk_raise_lds() {                 // the ring + a row
     bool& raised = mnn_dev_flag(raised_);
     if (raised) return hipSuccess;
     hipError_t e = hipSuccess;
-#define RAISE(TM, FU) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&nade_sample_chunk_kernel<TM, FU, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); \
-                      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&nade_sample_chunk_kernel<TM, FU, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)
+#define RAISE1(TM, FU, GV) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&nade_sample_chunk_kernel<TM, FU, 8, GV>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); \
+                           if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&nade_sample_chunk_kernel<TM, FU, 16, GV>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)
+#define RAISE(TM, FU) RAISE1(TM, FU, false); RAISE1(TM, FU, true)
     RAISE(0, true); RAISE(1, true); RAISE(2, true); RAISE(0, false); RAISE(1, false); RAISE(2, false);
 #undef RAISE
+#undef RAISE1
     raised = e == hipSuccess;
     return e;
 }
 
-static int launch_sample(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, float temperature, uint32_t row0, uint32_t sub,
-                         long s_row_stride, int s_elem_stride) {
+// GV: some job carries codes (SampleJob.given) -- the GIVEN instantiations; without any, the launch is the unconditioned one
+template <bool GV>
+static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, float temperature, uint32_t row0, uint32_t sub,
+                           long s_row_stride, int s_elem_stride) {
     const int tmode = temperature > 0.f ? (temperature == 1.0f ? 1 : 2) : 0;
     bool chunked = Hn % 4 == 0 && Hn >= 4 && getenv("MNN_SAMPLE_NO_CHUNK") == nullptr;      // (read per call: tests compare the two forms)
     for (int j = 0; j < njobs && chunked; ++j) chunked = (((uintptr_t)J.job[j].w_enc | (uintptr_t)J.job[j].w_dec) & 15) == 0;
+    const size_t gbytes = GV ? (size_t)((D + 3) & ~3) : 0;   // the row's codes
     if (chunked) {                                           // eight visibles per pass, one wave per row
         // sixteen visibles per pass while every row has a CU of its own (96 KB of ring: one workgroup per CU); eight with more rows than that
         const int g = (long)N * njobs <= 256 && !getenv("MNN_SAMPLE_G8") ? 16 : 8;
-        const size_t ldc = (size_t)sch_nb(g) * 2 * g * 1024 + (size_t)9 * ((D + 3) & ~3) + 1024;       // <= 96 KB + 13.5 KB + 1 KB (D <= 1536)
+        const size_t ldc = (size_t)sch_nb(g) * 2 * g * 1024 + (size_t)9 * ((D + 3) & ~3) + 1024 + gbytes;     // <= 96 KB + 15 KB + 1 KB (D <= 1536)
         MNN_HIP(sample_chunk_raise_lds());
-#define SMC(TM, FU) do { if (g == 16) hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 16>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride); \
-                         else hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 8>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride); } while (0)
+#define SMC(TM, FU) do { if (g == 16) hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 16, GV>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride); \
+                         else hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 8, GV>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride); } while (0)
         if (Hn == 256) { if (tmode == 0) SMC(0, true); else if (tmode == 1) SMC(1, true); else SMC(2, true); }
         else { if (tmode == 0) SMC(0, false); else if (tmode == 1) SMC(1, false); else SMC(2, false); }
 #undef SMC
@@ -1140,8 +1168,8 @@ static int launch_sample(hipStream_t st, const SampleJobs& J, int njobs, int N, 
         return MNN_OK;
     }
     dim3 grid(cdiv(N, 4), njobs);
-    const size_t lds = (size_t)36 * ((D + 3) & ~3) + 4096;   // 4 waves x ((2 f32 + u8) per visible + 256 uniforms)
-#define SMP(TM, FU, SP) hipLaunchKernelGGL((nade_sample_kernel<TM, FU, SP>), grid, dim3(256), lds, st, J, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride)
+    const size_t lds = (size_t)36 * ((D + 3) & ~3) + 4096 + 4 * gbytes;     // 4 waves x ((2 f32 + u8 (+ u8 code)) per visible + 256 uniforms): <= 64 KB
+#define SMP(TM, FU, SP) hipLaunchKernelGGL((nade_sample_kernel<TM, FU, SP, GV>), grid, dim3(256), lds, st, J, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride)
     if (Hn == 256 && tmode == 1) { if (getenv("MNN_SAMPLE_NO_SPEC")) SMP(1, true, false); else SMP(1, true, true); }
     else if (Hn == 256) { if (tmode == 0) SMP(0, true, false); else SMP(2, true, false); }
     else { if (tmode == 0) SMP(0, false, false); else if (tmode == 1) SMP(1, false, false); else SMP(2, false, false); }
@@ -1150,9 +1178,17 @@ static int launch_sample(hipStream_t st, const SampleJobs& J, int njobs, int N, 
     return MNN_OK;
 }
 
+static int launch_sample(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, float temperature, uint32_t row0, uint32_t sub,
+                         long s_row_stride, int s_elem_stride) {
+    bool given = false;
+    for (int j = 0; j < njobs; ++j) given = given || J.job[j].given != nullptr;
+    return given ? launch_sample_t<true>(st, J, njobs, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride)
+                 : launch_sample_t<false>(st, J, njobs, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride);
+}
+
 extern "C" int mnn_nade_sample(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
                                const float* w_dec, float temperature, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
-                               long s_track_stride, int s_row_stride, int s_elem_stride, float* nll) {
+                               long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given) {
     MNN_REQUIRE(tracks > 0 && N > 0 && D > 0 && Hn > 0 && Hn <= 256, "mnn_nade_sample: need tracks,N,D>0 and 0<Hn<=256 (Hn=%d)", Hn);
     MNN_REQUIRE(bias && w_enc && w_dec && samples, "mnn_nade_sample: null pointer");
     MNN_REQUIRE(ld_bias >= tracks * (Hn + D), "mnn_nade_sample: ld_bias too small");
@@ -1164,7 +1200,8 @@ extern "C" int mnn_nade_sample(mnn_stream_t s, int tracks, int N, int D, int Hn,
         for (int j = 0; j < nj; ++j) {
             const int m = m0 + j;
             J.job[j] = SampleJob{bias, ld_bias, m * Hn, tracks * Hn + m * D, w_enc + (size_t)m * D * Hn, w_dec + (size_t)m * D * Hn, seed,
-                                 (uint32_t)(m * D), samples + (size_t)m * s_track_stride, nll ? nll + (size_t)m * N : nullptr};
+                                 (uint32_t)(m * D), samples + (size_t)m * s_track_stride, nll ? nll + (size_t)m * N : nullptr,
+                                 given ? given + (size_t)m * s_track_stride : nullptr};
         }
         const int rc = launch_sample((hipStream_t)s, J, nj, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride);
         if (rc != MNN_OK) return rc;
@@ -1184,7 +1221,7 @@ extern "C" int mnn_nade_sample_multi(mnn_stream_t s, int njobs, const mnn_nade_s
     for (int j = 0; j < njobs; ++j) {
         const mnn_nade_sample_job& q = jobs[j];
         MNN_REQUIRE(q.bias && q.w_enc && q.w_dec && q.samples && q.ld_bias >= Hn + D, "mnn_nade_sample_multi: job %d: null pointer or ld_bias < Hn + D", j);
-        J.job[j] = SampleJob{q.bias, q.ld_bias, 0, Hn, q.w_enc, q.w_dec, q.seed, 0u, q.samples, q.nll};
+        J.job[j] = SampleJob{q.bias, q.ld_bias, 0, Hn, q.w_enc, q.w_dec, q.seed, 0u, q.samples, q.nll, q.given};
     }
     return launch_sample((hipStream_t)s, J, njobs, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride);
 }

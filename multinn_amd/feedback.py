@@ -7,7 +7,7 @@ import torch
 
 from . import ops
 from .common import Model, RNN, ParamStore
-from .generators import LstmStack, RnnEstimator, _compute_dtype, det_steps
+from .generators import LstmStack, RnnEstimator, RnnNade, _compute_dtype, det_steps
 
 
 class FeedbackRnn(Model):
@@ -197,15 +197,18 @@ class FeedbackRnnSampler:
         self.num_tracks = len(generators)
         self.concurrent = True       # the M generators of a step run on M streams (parallel branches of the captured scan)
 
-    def generate(self, x_u8, num_steps):
+    def generate(self, x_u8, num_steps, given=None):
         """x_u8 [B,Ti,P,M] intro piano-rolls -> samples u8 [B,num_steps,P,M].  One hipGraph replay per call on the
-        device (common.ScanGraphs): the M generators and the feedback module step inside the same captured scan."""
+        device (common.ScanGraphs): the M generators and the feedback module step inside the same captured scan.
+        given (optional): codes u8 [B, num_steps, P, M] (common.given_codes), see generate_encoded."""
         from .common import ScanGraphs
         if not ScanGraphs.enabled(x_u8):
-            return self._generate_scan(x_u8, num_steps)
+            return self._generate_scan(x_u8, num_steps, given)
         if getattr(self, "_scan_graphs", None) is None:
             self._scan_graphs = ScanGraphs()
         key = (tuple(x_u8.shape), int(num_steps), tuple((g.seed, g.row0) for g in self.generators))
+        if given is not None:
+            key = key + ("given",)
 
         def stale():
             for g in self.generators:
@@ -213,11 +216,15 @@ class FeedbackRnnSampler:
             if hasattr(self.feedback, "_packed_step"):
                 self.feedback._packed_step = -1
 
-        def scan(sx):
+        def scan(sx, sg=None):
             stale()                                    # pack inside the graph: a replay always sees the current weights
-            return self._generate_scan(sx, num_steps)
+            return self._generate_scan(sx, num_steps, sg)
 
-        return self._scan_graphs.run(key, x_u8, scan, lambda sx: self._generate_scan(sx, min(int(num_steps), 2)), stale)
+        def warm(sx, sg=None):
+            n = min(int(num_steps), 2)
+            return self._generate_scan(sx, n, None if sg is None else sg[:, :n].contiguous())
+
+        return self._scan_graphs.run(key, x_u8, scan, warm, stale, extra=given)
 
     def _group_dense(self, hs, rnn_states):
         """The M generators' Dense layers on their top outputs in one launch -> their RnnEstimatorStateTuples."""
@@ -225,16 +232,18 @@ class FeedbackRnnSampler:
         ops.dense_det(list(jobs))
         return [g._state_from_dense(o, tuple(st)) for g, o, st in zip(self.generators, outs, rnn_states)]
 
-    def _generate_scan(self, x_u8, num_steps):
+    def _generate_scan(self, x_u8, num_steps, given=None):
         B, Ti, P, M = x_u8.shape
         assert M == self.num_tracks
         enc = torch.cat([torch.zeros((B, 1, P, M), device=x_u8.device, dtype=torch.uint8), x_u8], 1)      # multi_encoder_nn.py:73-76
-        return self.generate_encoded([enc[..., i] for i in range(M)], num_steps)
+        return self.generate_encoded([enc[..., i] for i in range(M)], num_steps, given)
 
-    def generate_encoded(self, enc_tracks, num_steps):
+    def generate_encoded(self, enc_tracks, num_steps, given=None):
         """The scan on per-track ENCODED inputs (multinn_feedback.py:120-173 between the encoders): enc_tracks = M x u8
         [B, Ti+1, E] (zero first step included) -> sampled codes u8 [B, num_steps, E, M]; the caller decodes them through
-        its encoders (identity for PassEncoder)."""
+        its encoders (identity for PassEncoder).  given (optional): codes u8 [B, num_steps, E, M] (common.given_codes).  NADE
+        generators clamp inside their sampling kernels; an RBM generator's track is pasted over its sample before the feedback step
+        (whole tracks only: the mode classes refuse partial masks on RBM generators)."""
         M = self.num_tracks
         enc_tracks = [e.contiguous() for e in enc_tracks]            # (views of a [B, T, P, M] roll have inner stride M)
         B, _, P = enc_tracks[0].shape
@@ -263,6 +272,10 @@ class FeedbackRnnSampler:
             for i, g in enumerate(self.generators):
                 states.append(g.steps(torch.cat([enc_tracks[i].float(), x_fb], -1)))                # multinn_feedback.py:143-149
         out = torch.empty((B, num_steps, P, M), device=dev, dtype=torch.uint8)
+        if given is not None:
+            if given.dtype != torch.uint8 or tuple(given.shape) != (B, int(num_steps), P, M):
+                raise ValueError(f"given must be u8 [{B}, {int(num_steps)}, {P}, {M}], got {given.dtype} {tuple(given.shape)}")
+            given = given.contiguous()                      # (the strides of out: its [:, s, :, i] views are the sample views')
         # Inside a step the tracks are independent: generator i's {sample | LSTM step, Dense} run on stream i, joined on
         # the main stream around the feedback step.  Their single steps take the launch-per-step LSTM kernels: persistent launches
         # spin on their own workgroups and must not share the device with one another (LstmStack.persist_single_step).
@@ -277,7 +290,8 @@ class FeedbackRnnSampler:
             for s in range(num_steps):                                                              # _feedback_recurrence (175-218)
                 views = [out[:, s, :, i] for i in range(M)]                                          # u8 [B, P] views of track i (element stride M)
                 ops.nade_sample_multi([dict(bias=states[i].dense, w_enc=g.store["nade/w_enc"][0], w_dec=g.store["nade/w_dec"][0], seed=g.seed,
-                                            samples=views[i]) for i, g in enumerate(gs)], P, Hn, 1.0, gs[0].row0, s)
+                                            samples=views[i], given=None if given is None else given[:, s, :, i])
+                                       for i, g in enumerate(gs)], P, Hn, 1.0, gs[0].row0, s)
                 st = out[:, s].reshape(B, P * M)                                                     # [B, P*M] view, feature p*M+m
                 fb, fb_state = self.feedback.single(st if fb_strided else st.contiguous(), fb_state)
                 res = det_steps([g._stack for g in gs], views, [list(s_.rnn_state) for s_ in states], [fb] * M)
@@ -302,7 +316,14 @@ class FeedbackRnnSampler:
                     with on(i):
                         g._gen_step = s
                         g._last_dense = states[i].dense
-                        smp, _ = g.sample_single(None, states[i])
+                        gi = None if given is None else given[:, s, :, i]
+                        if gi is None:
+                            smp, _ = g.sample_single(None, states[i])
+                        elif isinstance(g, RnnNade):
+                            smp, _ = g.sample_single(None, states[i], given=gi.contiguous())
+                        else:                               # a wholly given track pasted over the RBM's sample
+                            smp, _ = g.sample_single(None, states[i])
+                            smp = torch.where(gi != 255, gi, smp)
                     samples.append(smp)
                 if par:
                     for ln in lanes:

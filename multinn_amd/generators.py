@@ -760,7 +760,7 @@ class Generator(Model):
         return self._outputs
 
     @abc.abstractmethod
-    def generate(self, x, num_steps):
+    def generate(self, x, num_steps, given=None):
         ...
 
     def pretrain(self, optimizer, lr, run_optimizer=True):
@@ -883,7 +883,7 @@ class RnnEstimator(Generator):
             return self._det_state(h, st)
         return self._get_state(inputs, initial_state=initial_state, last_outputs=True)
 
-    def _scan_in_one_call(self, x, num_steps):
+    def _scan_in_one_call(self, x, num_steps, given=None):
         return None                         # estimators without a one-call scan (RnnRBM) step through sample_single / single_step
 
     def _det_single_step(self, inputs, initial_state, x2=None):
@@ -970,30 +970,43 @@ class RnnEstimator(Generator):
         return buf
 
     # -- sampling -------------------------------------------------------------------------------
-    def generate(self, x, num_steps):
+    def generate(self, x, num_steps, given=None):
         """rnn_estimator.py:271-298: intro pass, then num_steps x {sample_single, single_step}.
         x [B,Ti,Din]; returns samples u8 [B,num_steps,num_output].  On the device the whole scan is ONE hipGraph
-        replay (captured per shape / num_steps / seed, see common.ScanGraphs); same kernels, same RNG counters, same bits."""
+        replay (captured per shape / num_steps / seed, see common.ScanGraphs); same kernels, same RNG counters, same bits.
+        given (optional): codes u8 [B, num_steps, num_output] in the generator's feature order (common.given_codes): a clamped visible is
+        emitted as given and fed forward like a draw, every free one is drawn from the uniform it draws unconditioned."""
+        if given is not None:
+            n_out = getattr(self, "_num_output", self.num_dims)
+            if given.dtype != torch.uint8 or tuple(given.shape) != (x.shape[0], int(num_steps), n_out):
+                raise ValueError(f"given must be u8 [{x.shape[0]}, {int(num_steps)}, {n_out}], got {given.dtype} {tuple(given.shape)}")
+            given = given.contiguous()
         if not ScanGraphs.enabled(x):
-            return self._generate_scan(x, num_steps)
+            return self._generate_scan(x, num_steps, given)
         if getattr(self, "_scan_graphs", None) is None:
             self._scan_graphs = ScanGraphs()
         key = (tuple(x.shape), x.dtype, int(num_steps), self.seed, self.row0)
+        if given is not None:
+            key = key + ("given",)                     # a new given of the same shape replays the same graph
 
-        def scan(sx):
+        def scan(sx, sg=None):
             self._packed_step = -1                     # pack inside the graph: a replay always sees the current weights
-            return self._generate_scan(sx, num_steps)
+            return self._generate_scan(sx, num_steps, sg)
 
         def after():
             self._packed_step = -1                     # the packed copies now live in the graph's pool
 
-        return self._scan_graphs.run(key, x, scan, lambda sx: self._generate_scan(sx, min(int(num_steps), 2)), after)
+        def warm(sx, sg=None):
+            n = min(int(num_steps), 2)
+            return self._generate_scan(sx, n, None if sg is None else sg[:, :n].contiguous())
 
-    def _generate_scan(self, x, num_steps):
+        return self._scan_graphs.run(key, x, scan, warm, after, extra=given)
+
+    def _generate_scan(self, x, num_steps, given=None):
         self._materialize(x.shape[-1])
         self._rnn.build_cell(False)
         if self.det_sampling:
-            whole = self._scan_in_one_call(x, num_steps)        # LSTM-(Multi)NADE on a byte piano-roll: mnn_generate_scan runs the whole scan
+            whole = self._scan_in_one_call(x, num_steps, given)     # LSTM-(Multi)NADE on a byte piano-roll: mnn_generate_scan runs the whole scan
             if whole is not None:
                 return whole
             state = self.steps(x)
@@ -1004,7 +1017,10 @@ class RnnEstimator(Generator):
         out = []
         for s in range(num_steps):
             self._gen_step = s
-            samples, _ = self.sample_single(intro, state)
+            if given is None:
+                samples, _ = self.sample_single(intro, state)
+            else:
+                samples, _ = self.sample_single(intro, state, given=given[:, s].contiguous())
             state = self.single_step(samples, state)
             intro = samples
             out.append(samples)
@@ -1509,15 +1525,16 @@ class RnnNade(RnnEstimator):
             out = self._dense(y.view(T * B, -1))[flat_index(lengths, B, T, inputs.device)]
         return self._state_from_dense(out, tuple((c.clone(), h.clone()) for c, h in final))
 
-    def _scan_in_one_call(self, x, num_steps):
+    def _scan_in_one_call(self, x, num_steps, given=None):
         """rnn_estimator.py:271-298 through ONE C-ABI call (mnn_generate_scan: intro pass + num_steps x {NADE sample, LSTM step, Dense} enqueued
-        by the library's own host loop) when the inputs are the byte piano-roll itself; the same kernels and bits as the step-by-step path."""
+        by the library's own host loop) when the inputs are the byte piano-roll itself; the same kernels and bits as the step-by-step path.
+        given: the scan's codes u8 [B, num_steps, num_output] (generate)."""
         if x.dtype != torch.uint8 or x.shape[-1] != self.num_tracks * self.num_dims or int(num_steps) < 1:
             return None
         pre = self._rnn.prefix
         layers = [(self.store[f"{pre}/cell_{l}/kernel"], self.store[f"{pre}/cell_{l}/bias"]) for l in range(len(self._rnn.num_units))]
         return ops.generate_scan(x.contiguous(), num_steps, layers, self.store["dense/kernel"], self._det_fc_bias(), self.num_tracks, self.num_dims,
-                                 self.num_hidden[-1], self.store["nade/w_enc"], self.store["nade/w_dec"], 1.0, self.seed, self.row0)
+                                 self.num_hidden[-1], self.store["nade/w_enc"], self.store["nade/w_dec"], 1.0, self.seed, self.row0, given=given)
 
     def _det_fc_bias(self):
         if not self.internal_bias:
@@ -1553,15 +1570,16 @@ class RnnNade(RnnEstimator):
         state = self._get_state(inputs, lengths=lengths)
         return self._nade.log_prob(targets_flat, state.b_enc, state.b_dec)
 
-    def sample_single(self, inputs, state, temperature=1.0):
-        """rnn_nade.py:304-318 / rnn_multinade.py:295-317: returns (sample u8 [B,num_output], nll)."""
+    def sample_single(self, inputs, state, temperature=1.0, given=None):
+        """rnn_nade.py:304-318 / rnn_multinade.py:295-317: returns (sample u8 [B,num_output], nll).  given (optional): codes u8
+        [B, num_output] (ops.nade_sample): clamped visibles are emitted as given, nll is that of the emitted vector."""
         M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
         out = state.dense if getattr(state, "dense", None) is not None else self._last_dense
         Bn = out.shape[0]
         smp = torch.empty((Bn, M * D), device=out.device, dtype=torch.uint8)
         nll = torch.empty((M, Bn), device=out.device)
         ops.nade_sample(out, self.store["nade/w_enc"], self.store["nade/w_dec"], M, D, Hn, temperature, self.seed, self.row0,
-                        getattr(self, "_gen_step", 0), smp, track_minor=(M > 1), nll=nll)
+                        getattr(self, "_gen_step", 0), smp, track_minor=(M > 1), nll=nll, given=given)
         return smp, (nll[0] if M == 1 else [nll[m] for m in range(M)])
 
 
@@ -1822,6 +1840,12 @@ class RnnRBM(RnnEstimator):
         out = self._biases(h.contiguous())
         Hn, D = self.num_hidden[-1], self.num_dims
         return RnnEstimatorStateTuple(out[:, :Hn], out[:, Hn:Hn + D], tuple(new))
+
+    def generate(self, x, num_steps, given=None):
+        """RnnEstimator.generate; a clamped cell in `given` would need a clamped Gibbs chain, which this generator does not have."""
+        if given is not None and bool((given != 255).any()):
+            raise NotImplementedError("conditional generation with an RBM generator (a clamped Gibbs chain) is not implemented")
+        return super().generate(x, num_steps)
 
     def sample_single(self, inputs, state):
         """rnn_rbm.py:283-297 with k = rbm.k (R1): returns (sample u8, cond_prob)."""

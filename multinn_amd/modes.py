@@ -23,7 +23,7 @@ import os
 
 import torch
 
-from .common import Model, graph_capture
+from .common import Model, graph_capture, given_codes, given_tracks
 from .encoders import PassEncoder, DBNEncoder
 from .generators import RnnNade, RnnRBM, RnnMultiNADE
 from . import ops
@@ -216,11 +216,40 @@ class MultINNCore(Model):
     metrics_upd = property(lambda self: (self._ensure_global_metrics(), self._metrics_upd)[1])
 
     # -- sampling -------------------------------------------------------------------------------
-    def sampler(self, num_beats):
-        """multinn_core.py:324-341: number of model time steps in `num_beats` beats, then generate()."""
+    def sampler(self, num_beats, given=None, given_mask=None):
+        """multinn_core.py:324-341: number of model time steps in `num_beats` beats, then generate() (given / given_mask: see generate)."""
         d = self._config["data"]
         pitch_span = d["pitch_range"]["highest"] - d["pitch_range"]["lowest"]
-        return self.generate(num_beats * d["beat_resolution"] * pitch_span // self._num_dims)
+        num_steps = num_beats * d["beat_resolution"] * pitch_span // self._num_dims
+        if given is None and given_mask is None:
+            return self.generate(num_steps)
+        return self.generate(num_steps, given=given, given_mask=given_mask)
+
+    # Conditional generation (generate(num_steps, given, given_mask)): given u8 [B, num_steps, P, M] (nonzero = note on), given_mask bool
+    # broadcastable to it -- [M] whole tracks (accompaniment), [P, M] pitch ranges, the full shape any cells (infilling); None = every cell.
+    # The result equals given wherever the mask is true; the other cells are ancestral samples with the given values fed forward.
+    def _given(self, num_steps, given, given_mask):
+        """Host checks, then the codes: None without `given`, else (codes u8 [B, num_steps, P, M] on the device, whole, some) -- per
+        track whether every / any cell of it is given.  Refuses what this build cannot condition on before any device work."""
+        if given is None:
+            if given_mask is not None:
+                raise ValueError("given_mask without given")
+            return None
+        if self._encoder_type != "Pass":
+            raise NotImplementedError("conditional generation through DBN encoders (in code space) is not implemented: use Pass encoders")
+        if not torch.is_tensor(given) or given.dtype != torch.uint8 or given.dim() != 4:
+            raise ValueError("given must be a u8 tensor [B, num_steps, P, M]")
+        B = given.shape[0] if self._x is None else self._x.shape[0]
+        shape = (B, int(num_steps), self.num_dims, self.num_tracks)
+        if tuple(given.shape) != shape:
+            raise ValueError(f"given has shape {tuple(given.shape)}, expected {shape}")
+        whole, some = given_tracks(given_mask, shape)
+        self._refuse_given(whole, some)
+        dev = self._x.device if self._x is not None else given.device
+        return given_codes(given.to(dev), given_mask, shape), whole, some
+
+    def _refuse_given(self, whole, some):
+        """NotImplementedError for a mask this mode's generators cannot honour (RnnRBM: only tracks it does not sample)."""
 
     def evaluator(self):
         """multinn_core.py:343-362: musical metrics of the fed batch reshaped into bars `[B, bars, 4*beat_resolution, pitch_span, M]`."""
@@ -534,11 +563,22 @@ class MultINNJoint(MultINNCore):
             metrics[k] = metrics[k] / self.num_tracks
         return metrics, metrics_upd, summaries
 
-    def generate(self, num_steps):
-        """multinn_joint.py:188-215 -> u8 `[B, num_steps, P, M]`."""
+    def _refuse_given(self, whole, some):
+        if isinstance(self._generator, RnnRBM) and any(some):
+            raise NotImplementedError("joint mode with an RBM generator cannot condition on given notes (that needs a clamped Gibbs chain)")
+
+    def generate(self, num_steps, given=None, given_mask=None):
+        """multinn_joint.py:188-215 -> u8 `[B, num_steps, P, M]`.  given / given_mask: conditional generation (MultINNCore._given).  The
+        one NADE orders the visibles of a step p M + m: a free visible is conditioned on the clamped visibles ordered BEFORE it only (the
+        ones after it are fed forward to the later visibles and steps) -- what a NADE offers without importance sampling."""
+        cond = self._given(num_steps, given, given_mask)
         if self._x_encoded is None:
             MultINNCore._build_all(self, "generate")
-        samples_h = self._generator.generate(self._x_encoded, num_steps)
+        if cond is None:
+            samples_h = self._generator.generate(self._x_encoded, num_steps)
+        else:
+            codes = cond[0]
+            samples_h = self._generator.generate(self._x_encoded, num_steps, given=codes.reshape(codes.shape[0], num_steps, -1))
         _, samples = self._encoder.decode(samples_h)
         return samples.reshape(-1, num_steps, self.num_dims, self.num_tracks).to(torch.uint8)
 
@@ -680,13 +720,26 @@ class MultINNJamming(MultIEncoderNN):
     def _decode_generator_outputs(self):
         return self._decode_tracks(self._x_hidden)
 
-    def generate(self, num_steps):
-        """multinn_jamming.py:101-133 -> u8 `[B, num_steps, P, M]`."""
+    def _refuse_given(self, whole, some):
+        for i, g in enumerate(self.generators):
+            if isinstance(g, RnnRBM) and some[i] and not whole[i]:
+                raise NotImplementedError(f"track {i}: an RBM generator takes whole given tracks only (a partial mask needs a clamped Gibbs chain)")
+
+    def generate(self, num_steps, given=None, given_mask=None):
+        """multinn_jamming.py:101-133 -> u8 `[B, num_steps, P, M]`.  given / given_mask (MultINNCore._given): the generators are independent --
+        a wholly given track is not sampled at all, a partly given one is clamped inside its NADE generator's scan."""
+        cond = self._given(num_steps, given, given_mask)
         if self._x_encoded is None:
             MultINNCore._build_all(self, "generate")
         music = []
         for i in range(self.num_tracks):
-            samples_h = self.generators[i].generate(self._x_encoded[i], num_steps)
+            if cond is not None and cond[1][i]:
+                music.append(cond[0][..., i].contiguous())
+                continue
+            if cond is not None and cond[2][i]:
+                samples_h = self.generators[i].generate(self._x_encoded[i], num_steps, given=cond[0][..., i].contiguous())
+            else:
+                samples_h = self.generators[i].generate(self._x_encoded[i], num_steps)
             music.append(self.encoders[i].decode(samples_h)[1].to(torch.uint8))
         return torch.stack(music, dim=3)
 
@@ -775,11 +828,17 @@ class MultINNComposer(MultIEncoderNN):
     def _decode_generator_outputs(self):
         return self._decode_tracks(self._x_hidden)
 
-    def generate(self, num_steps):
-        """multinn_composer.py:114-151 -> u8 `[B, num_steps, P, M]`."""
+    def generate(self, num_steps, given=None, given_mask=None):
+        """multinn_composer.py:114-151 -> u8 `[B, num_steps, P, M]`.  given / given_mask (MultINNCore._given): the tracks of a step are
+        conditionally independent given the history, so clamping whole tracks conditions the others exactly."""
+        cond = self._given(num_steps, given, given_mask)
         if self._x_encoded is None:
             MultINNCore._build_all(self, "generate")
-        samples_h = self._generator.generate(self._x_encoded_stack, num_steps)
+        if cond is None:
+            samples_h = self._generator.generate(self._x_encoded_stack, num_steps)
+        else:
+            codes = cond[0]                                         # [B, steps, P, M] -> feature p M + m: the MultiNADE's i tracks + m
+            samples_h = self._generator.generate(self._x_encoded_stack, num_steps, given=codes.reshape(codes.shape[0], num_steps, -1))
         samples_h = samples_h.reshape(samples_h.shape[0], num_steps, self._num_dims_generator, self.num_tracks).unbind(-1)
         music = [self.encoders[i].decode(samples_h[i].contiguous())[1].to(torch.uint8) for i in range(self.num_tracks)]
         return torch.stack(music, dim=3)
@@ -848,9 +907,11 @@ class MultINNFeedback(MultINNJamming):
         inputs = torch.cat([self._x_encoded[i].float(), self._x_feedback], dim=-1)               # multinn_feedback.py:85-91
         return inputs[:, :-1], self._x_encoded[i][:, 1:]
 
-    def generate(self, num_steps):
-        """multinn_feedback.py:120-173 -> u8 `[B, num_steps, P, M]`: one joint scan over the M generators and the feedback module."""
+    def generate(self, num_steps, given=None, given_mask=None):
+        """multinn_feedback.py:120-173 -> u8 `[B, num_steps, P, M]`: one joint scan over the M generators and the feedback module.
+        given / given_mask (MultINNCore._given): NADE generators clamp inside the scan, RBM generators take whole given tracks only."""
         from .feedback import FeedbackRnnSampler
+        cond = self._given(num_steps, given, given_mask)
         if self._x_encoded is None:
             self._inputs = self._build_inputs()
             self._build_encoders("eval")
@@ -860,7 +921,10 @@ class MultINNFeedback(MultINNJamming):
         if getattr(self, "_sampler", None) is None:
             self._sampler = FeedbackRnnSampler(self.generators, self._feedback_layer)
         if self._encoder_type == "Pass":
-            samples_h = self._sampler.generate(self._x, num_steps)                                # whole scan = one hipGraph replay
+            if cond is None:
+                samples_h = self._sampler.generate(self._x, num_steps)                            # whole scan = one hipGraph replay
+            else:
+                samples_h = self._sampler.generate(self._x, num_steps, given=cond[0])
         else:
             samples_h = self._sampler.generate_encoded([e.to(torch.uint8) for e in self._x_encoded], num_steps)
         music = [self.encoders[i].decode(samples_h[..., i].contiguous())[1].to(torch.uint8) for i in range(self.num_tracks)]

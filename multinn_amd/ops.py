@@ -619,8 +619,10 @@ def nade_logprob_bwd(v, bias, w_enc, w_dec, tracks, D, Hn, a_final, d_bias, d_w_
          _ptr(a_final), _ptr(d_bias), _ptr(d_w_enc), _ptr(d_w_dec), _ptr(n_rows_dev), _ptr(unsafe))
 
 
-def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub, samples, track_minor=False, nll=None):
-    """samples u8 [N, tracks*D]; feature index m*D+i (track_minor False) or i*tracks+m (True, rnn_multinade.py:313-314)."""
+def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub, samples, track_minor=False, nll=None, given=None):
+    """samples u8 [N, tracks*D]; feature index m*D+i (track_minor False) or i*tracks+m (True, rnn_multinade.py:313-314).
+    given (optional): codes u8 [N, tracks*D] in the layout of samples -- 0 / 1 clamp the visible to that value, 255 leaves it to the draw
+    (common.given_codes)."""
     N = bias.shape[0]
     _req(bias.dtype == torch.float32 and bias.dim() == 2 and bias.stride(1) == 1 and bias.shape[1] >= tracks * (Hn + D), "sample: bias")
     _req(samples.dtype == torch.uint8 and samples.shape == (N, tracks * D) and samples.is_contiguous(), "sample: samples u8 [N,tracks*D]")
@@ -628,15 +630,18 @@ def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub,
         _req(w.dtype == torch.float32 and w.is_contiguous() and w.numel() == tracks * D * Hn, "sample: weights")
     if nll is not None:
         _req(nll.dtype == torch.float32 and nll.numel() == tracks * N, "sample: nll")
+    if given is not None:
+        _req(given.dtype == torch.uint8 and tuple(given.shape) == (N, tracks * D) and given.is_contiguous() and given.device == samples.device,
+             "sample: given u8 [N, tracks*D], contiguous")
     ts, es = (1, tracks) if track_minor else (D, 1)
     call("mnn_nade_sample", _stream(), tracks, N, D, Hn, _ptr(bias), bias.stride(0), _ptr(w_enc), _ptr(w_dec),
-         float(-1.0 if temperature is None else temperature), int(seed), int(row0), int(sub), _ptr(samples), ts, tracks * D, es, _ptr(nll))
+         float(-1.0 if temperature is None else temperature), int(seed), int(row0), int(sub), _ptr(samples), ts, tracks * D, es, _ptr(nll), _ptr(given))
 
 
 def nade_sample_multi(jobs, D, Hn, temperature, row0, sub):
     """mnn_nade_sample for up to 8 single-NADE generators in ONE launch.  job = dict(bias f32 [N, >= Hn + D] (the generator's Dense output),
     w_enc / w_dec f32 [D, Hn], seed, samples = a u8 [N, D] VIEW (any strides, the same for every job: e.g. out[:, s, :, m] of a
-    [B, steps, P, M] piano-roll), nll f32 [N] or None)."""
+    [B, steps, P, M] piano-roll), nll f32 [N] or None, given = None or a u8 [N, D] view of codes with the strides of samples)."""
     _req(1 <= len(jobs) <= 8, "nade_sample_multi: 1..8 jobs")
     arr = (_lib.NadeSampleJob * len(jobs))()
     N = jobs[0]["bias"].shape[0]
@@ -648,7 +653,11 @@ def nade_sample_multi(jobs, D, Hn, temperature, row0, sub):
         for w in (j["w_enc"], j["w_dec"]):
             _req(w.dtype == torch.float32 and w.is_contiguous() and w.numel() == D * Hn, "sample_multi: weights f32 [D, Hn]")
         _req(nll is None or (nll.dtype == torch.float32 and nll.is_contiguous() and nll.numel() == N), "sample_multi: nll f32 [N]")
+        gv = j.get("given")
+        _req(gv is None or (gv.dtype == torch.uint8 and tuple(gv.shape) == (N, D) and gv.stride() == (rs, es) and gv.device == smp.device),
+             "sample_multi: given u8 [N, D] with the strides of samples")
         a.bias, a.ld_bias, a.w_enc, a.w_dec, a.seed, a.samples, a.nll = _ptr(b), b.stride(0), _ptr(j["w_enc"]), _ptr(j["w_dec"]), int(j["seed"]), _ptr(smp), _ptr(nll)
+        a.given = _ptr(gv)
     call("mnn_nade_sample_multi", _stream(), len(jobs), arr, N, D, Hn, float(-1.0 if temperature is None else temperature), int(row0), int(sub), rs, es)
 
 
@@ -952,9 +961,10 @@ def det_dense_pack(W, out=None):
     return out
 
 
-def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0):
+def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, given=None):
     """mnn_generate_scan: the whole sampling scan of an LSTM-(Multi)NADE generator in one call.  intro u8 [B, Ti, tracks * D]; layers = [(W, bias)]
-    f32 master weights; returns samples u8 [B, num_steps, tracks * D]."""
+    f32 master weights; returns samples u8 [B, num_steps, tracks * D].  given (optional): codes u8 [B, num_steps, tracks * D] in the layout of
+    the samples (see nade_sample)."""
     _req(intro.dtype == torch.uint8 and intro.dim() == 3 and intro.is_contiguous() and intro.shape[2] == tracks * D, "generate_scan: intro u8 [B, Ti, tracks * D]")
     B, Ti, n_in = intro.shape
     n_out = tracks * (Hn + D)
@@ -970,11 +980,14 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
     _req(dense_bias is None or (dense_bias.dtype == torch.float32 and dense_bias.is_contiguous() and dense_bias.numel() == n_out), "generate_scan: Dense bias")
     for w in (w_enc, w_dec):
         _req(w.dtype == torch.float32 and w.is_contiguous() and w.numel() == tracks * D * Hn, "generate_scan: NADE weights f32 [tracks, D, Hn]")
+    if given is not None:
+        _req(given.dtype == torch.uint8 and tuple(given.shape) == (B, int(num_steps), n_in) and given.is_contiguous() and given.device == intro.device,
+             "generate_scan: given u8 [B, num_steps, tracks * D], contiguous")
     need = int(_lib.load().mnn_generate_scan_workspace_bytes(B, n_in, len(layers), arr, n_out))
     ws = torch.empty(need + 256, dtype=torch.uint8, device=intro.device)
     off = (-ws.data_ptr()) % 256
     samples = torch.empty((B, int(num_steps), n_in), dtype=torch.uint8, device=intro.device)
     call("mnn_generate_scan", _stream(), B, Ti, int(num_steps), _ptr(intro), n_in, len(layers), arr, _ptr(dense_W), _ptr(dense_bias), n_out, tracks, D, Hn,
          _ptr(w_enc), _ptr(w_dec), float(-1.0 if temperature is None else temperature), int(seed), int(row0), _ptr(samples),
-         C.c_void_p(ws.data_ptr() + off), need)
+         C.c_void_p(ws.data_ptr() + off), need, _ptr(given))
     return samples                          # (the workspace returns to the allocator in stream order: later users are behind the scan)
