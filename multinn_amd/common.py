@@ -31,18 +31,73 @@ def default_device():
 # --------------------------------------------------------------------------------------------
 @contextlib.contextmanager
 def graph_capture(g, **kw):
-    """`with torch.cuda.graph(g, **kw)` with the cyclic garbage collector switched off for the duration of the capture.  torch collects once
-    when the capture begins; a collection that starts DURING it runs finalisers of whatever cyclic garbage the captured Python code has left
-    behind (dead generators with their own graphs, streams, pools) in the middle of the capture -- one full GPU test run of round 6 died that
-    way ("Fatal Python error: Aborted", "Garbage-collecting", inside a captured sampling scan).  Reference-counted frees are unaffected."""
-    with torch.cuda.graph(g, **kw):
-        was = gc.isenabled()
-        gc.disable()
-        try:
+    """`with torch.cuda.graph(g, **kw)` with the cyclic garbage collector switched off from before the capture begins until after it ends.  A
+    collection that starts DURING a capture runs finalisers of whatever cyclic garbage is left (dead generators with their own graphs, streams,
+    pools) in the middle of it -- one full GPU test run of round 6 died that way ("Fatal Python error: Aborted", "Garbage-collecting", inside a
+    captured sampling scan).  Reference-counted frees are unaffected, and so is an explicit gc.collect() (torch.cuda.graph's, when it is
+    configured to collect as the capture begins)."""
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(g, **kw):
             yield
-        finally:
-            if was:
-                gc.enable()
+    finally:
+        if was:
+            gc.enable()
+
+
+def _warm_up(fn, n=1):
+    """fn() n times on a side stream, then the current stream waits for it: whatever a capture needs (parameters, workspaces, persistent-kernel
+    attributes) exists before it, and none of the warm-up's work is pending on the stream about to be captured."""
+    cur = torch.cuda.current_stream()
+    side = torch.cuda.Stream()
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        for _ in range(int(n)):
+            fn()
+    cur.wait_stream(side)
+
+
+def capture_train_step(feed, step, warmup, models, stores, split=False, fwd_bwd=None, opt=None, error_mode="global"):
+    """The captured optimiser step of every graphed_* train entry: `warmup` eager step()s on a side stream, then hipGraph(s) of the step.
+    Returns run(*a, **kw) -> loss: feed(*a, **kw) copies new inputs into the static ones, then the replay.  One rank: ONE graph of step()
+    (capture_error_mode=error_mode).  split (data parallel): a graph of fwd_bwd() -> loss and one of opt() (clip + Adam, no all-reduce) in its
+    pool (run.opt_graph); each replay all-reduces the flat gradients eagerly between them, so nothing of RCCL is captured (thread_local: the
+    process group's watchdog thread may touch the runtime while this thread captures).  The 16-bit packed weights of `models` are marked
+    stale before the capture (the graph packs them itself, whatever ran before) and after it (the packed copies live in the graph's pool).
+    stores() (asked after the warm-up, which may create some): the ParamStores whose host mirror store.step follows the device counter.
+    run holds no model: one cached on its model (driver._captured_step) would make it cyclic garbage (graph_capture)."""
+    from .training import allreduce_flat, setup_cabi_comm
+    if split:
+        setup_cabi_comm()               # MULTINN_COMM=capi: the communicator exists before anything is captured
+    _warm_up(step, warmup)
+    for m in models:
+        m._packed_step = -1
+    graph, opt_graph = torch.cuda.CUDAGraph(), None
+    with graph_capture(graph, capture_error_mode="thread_local" if split else error_mode):
+        loss = fwd_bwd() if split else step()
+    if split:
+        opt_graph = torch.cuda.CUDAGraph()
+        with graph_capture(opt_graph, pool=graph.pool(), capture_error_mode="thread_local"):
+            opt()
+    for m in models:
+        m._packed_step = -1
+    mirror = list(stores())
+    for st in mirror:
+        st.step -= 1                    # the capture executed nothing (host mirror of store.step_dev)
+
+    def run(*a, **kw):
+        feed(*a, **kw)
+        graph.replay()
+        if opt_graph is not None:
+            for st in mirror:
+                allreduce_flat(st.grad)
+            opt_graph.replay()
+        for st in mirror:
+            st.step += 1
+        return loss
+    run.graph, run.opt_graph = graph, opt_graph
+    return run
 
 
 class ScanGraphs:
@@ -74,12 +129,7 @@ class ScanGraphs:
             static_x = x.clone()
             static_e = None if extra is None else extra.clone()
             args = (static_x,) if extra is None else (static_x, static_e)
-            cur = torch.cuda.current_stream()
-            side = torch.cuda.Stream()
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                warm(*args)
-            cur.wait_stream(side)
+            _warm_up(lambda: warm(*args))
             g = torch.cuda.CUDAGraph()
             with graph_capture(g, capture_error_mode="thread_local"):
                 out = scan(*args)

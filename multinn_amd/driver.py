@@ -133,31 +133,18 @@ def train_epoch(generator, X, lengths, ids, batch_size, piece_size, optimizer, l
 
 def _captured_step(generator, xb, optimizer, lr, max_graphs=8, lengths=None):
     """An eager optimiser step is host-bound (C2 shape: 7.2 ms eager, 2.85 ms as a hipGraph replay), so windows of a shape that keeps
-    coming back -- batch_size x piece_size, i.e. nearly all of an epoch -- run as replays of RnnNade.graphed_train_step.
+    coming back -- batch_size x piece_size, i.e. nearly all of an epoch -- run as replays of the model's graphed_train_step (RnnNade,
+    MultINNCore), for the windows its `capturable(shape, ragged)` accepts.
     A shape is captured at its SECOND occurrence (the first one runs eagerly and creates every workspace; capturing executes nothing,
-    so the trajectory is the eager one), keyed by optimiser and learning rate (both are baked into the graph).  Only for the paths the
-    captured step is tested on: the two-layer persistent recurrence and the row-parallel (CU-resident / cluster) one.
-    RAGGED windows (lengths given) are captured too where the generator runs them compacted (16-bit RnnNade: every row count lives on the
-    device, so ONE graph per window shape serves any lengths -- the reference's data is ragged, train.py:165-173); they get their own graph
-    beside the full-length one of the same shape, which skips the compaction passes.  MULTINN_TRAIN_GRAPH=0 keeps every step eager."""
+    so the trajectory is the eager one), keyed by optimiser and learning rate (both are baked into the graph).
+    RAGGED windows (lengths given) get their own graph beside the full-length one of the same shape, which skips the compaction passes:
+    ONE graph per window shape serves any lengths (the reference's data is ragged, train.py:165-173).  MULTINN_TRAIN_GRAPH=0 keeps every
+    step eager."""
     import os
-    if os.environ.get("MULTINN_TRAIN_GRAPH", "1") == "0" or not xb.is_cuda or not hasattr(generator, "graphed_train_step"):
-        return None
     ragged = lengths is not None
-    if getattr(generator, "_mode", None) in ("joint", "jamming", "composer") and hasattr(generator, "generators"):
-        # a mode class (multinn_amd.modes): its own captured step -- encoders, every generator, the joint clipped step -- full-length or ragged
-        # (MultINNCore.graphed_train_step keeps every row count of a ragged window on the device)
-        from .training import dp_active
-        if dp_active() or any(getattr(g, "store", None) is None or g.store.theta is None for g in generator.generators):
-            return None
-    else:
-        stack = getattr(generator, "_stack", None)
-        if stack is None or getattr(stack, "packed", None) is None or not (stack._persist(xb.shape[0], xb.shape[1]) or stack._rowpar(xb.shape[0], xb.shape[1])):
-            return None
-        if ragged:
-            from . import ops as _ops
-            if not (getattr(generator, "ragged_compact", False) and getattr(generator, "dtype", None) in _ops.H16 and getattr(generator, "num_tracks", 0) == 1):
-                return None
+    if os.environ.get("MULTINN_TRAIN_GRAPH", "1") == "0" or not xb.is_cuda or not hasattr(generator, "capturable") \
+            or not generator.capturable(tuple(xb.shape), ragged):
+        return None
     key = (tuple(xb.shape), id(optimizer), lr, "ragged" if ragged else "full")
     graphs = generator.__dict__.setdefault("_step_graphs", {})
     if key in graphs:
@@ -191,13 +178,10 @@ def evaluate(generator, X, lengths, batch_size, piece_size, device=None):
 
 def check_recurrences(model):
     """Raise if any persistent-recurrence launch of the model's LSTM stacks timed out on a bounded spin since the last check (its sticky
-    status word: LstmStack.check / MultINNCore.check; synchronises the device).  The launches of lstm_persist.hip / lstm_rowpar.hip need
+    status word: LstmStack.check / MultINNCore.check; synchronises the device).  The persistent and row-parallel recurrence launches need
     their whole grid resident at once; one that could not become resident returns garbage and only sets that word."""
     if hasattr(model, "check"):
-        try:
-            model.check(tolerate_overflow=True)          # the training loop: f16 overflows are answered by the dynamic loss scale (a warning)
-        except TypeError:
-            model.check()
+        model.check(tolerate_overflow=True)          # the training loop: f16 overflows are answered by the dynamic loss scale (a warning)
     elif getattr(model, "_stack", None) is not None:
         model._stack.check()
 

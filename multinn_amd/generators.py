@@ -19,7 +19,7 @@ import weakref
 import torch
 
 from . import ops
-from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, glorot_uniform, zeros_init, default_device, graph_capture
+from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, glorot_uniform, zeros_init, default_device, capture_train_step
 from .training import compute_gradients, world, dp_active, AdamOptimizer
 
 _RnnEstimatorStateTuple = collections.namedtuple("RnnEstimatorStateTuple", ("b_enc", "b_dec", "rnn_state"))
@@ -918,46 +918,32 @@ class RnnEstimator(Generator):
         mode; RnnNade.graphed_train_step is the fused piano-roll form).  Eagerly such a step is host-bound (RnnRBM at [256,128,88]:
         kernels 4 ms, wall 14 ms).  Returns run(x=None, y=None) -> loss.  Step-dependent values (dropout seed, Gibbs seed, Adam step)
         are read from store.step_dev on the device; under data parallelism the gradient all-reduce stays an eager call between two
-        graphs.  Full-length batches only."""
-        from .training import allreduce_flat
+        graphs (common.capture_train_step).  Full-length batches only."""
         sx, sy = x.clone(), y.clone()
-        cur = torch.cuda.current_stream()
-        side = torch.cuda.Stream()
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self.build(sx, sy, None, True, "train")
-                self.train(optimizer, lr)
-        cur.wait_stream(side)
-        multi = dp_active()
-        g_fb, g_opt = torch.cuda.CUDAGraph(), None
-        with graph_capture(g_fb, capture_error_mode="thread_local"):
-            self.build(sx, sy, None, True, "train")
-            if multi:
-                self.backward()
-            else:
-                self.train(optimizer, lr)
-            loss = self._loss
-        if multi:
-            g_opt = torch.cuda.CUDAGraph()
-            with graph_capture(g_opt, pool=g_fb.pool(), capture_error_mode="thread_local"):
-                self._grad_sumsq = compute_gradients(optimizer, self.store, self.clip_norm, lr, reduce=False)
-        self._packed_step = -1
-        self.store.step -= 1            # the captured step has not executed (host mirror of store.step_dev)
 
-        def run(x=None, y=None):
+        def feed(x=None, y=None):
             if x is not None:
                 sx.copy_(x)
             if y is not None:
                 sy.copy_(y)
-            g_fb.replay()
-            if g_opt is not None:
-                allreduce_flat(self.store.grad)
-                g_opt.replay()
-            self.store.step += 1
-            return loss
-        run.graph = g_fb
-        return run
+        return self._capture_step(feed, lambda: self.build(sx, sy, None, True, "train"), optimizer, lr, warmup, error_mode="thread_local")
+
+    def _capture_step(self, feed, forward, optimizer, lr, warmup, **kw):
+        """common.capture_train_step of this generator's step: forward() (a train-mode build) + train, or under data parallelism
+        forward() + backward | clip + Adam."""
+        def step():
+            forward()
+            self.train(optimizer, lr)
+            return self._loss
+
+        def fwd_bwd():
+            forward()
+            self.backward()
+            return self._loss
+
+        def opt():
+            self._grad_sumsq = compute_gradients(optimizer, self.store, self.clip_norm, lr, reduce=False)
+        return capture_train_step(feed, step, warmup, [self], lambda: [self.store], split=dp_active(), fwd_bwd=fwd_bwd, opt=opt, **kw)
 
     def _step_input(self, B, device):
         """[B, ld0] staging row block of single_step: the zero padding beyond the input width is written once, every step converts its
@@ -1406,6 +1392,16 @@ class RnnNade(RnnEstimator):
         self.train(optimizer, lr)
         return self._loss
 
+    def capturable(self, shape, ragged):
+        """Whether windows of this shape (full-length, or ragged) may train as replays of graphed_train_step (driver._captured_step): only the
+        paths the captured step is tested on -- the two-layer persistent recurrence and the row-parallel (CU-resident / cluster) one; ragged
+        windows where they run compacted (16-bit, one track: every row count lives on the device, so one graph serves any lengths)."""
+        B, T = shape[0], shape[1]
+        stack = getattr(self, "_stack", None)
+        if stack is None or stack.packed is None or not (stack._persist(B, T) or stack._rowpar(B, T)):
+            return False
+        return not ragged or (self.ragged_compact and self.dtype in ops.H16 and self.num_tracks == 1)
+
     def graphed_train_step(self, x_u8, optimizer, lr=None, warmup=2, lengths=None):
         """Capture one whole optimiser step (plumbing, packing, forward, backward, clip, Adam: ~300 launches) into
         hipGraphs and return ``run(x=None, lengths=None) -> loss``: the T-step recurrences are launch-bound on the host otherwise.
@@ -1417,8 +1413,6 @@ class RnnNade(RnnEstimator):
         the valid-row count, 1 / n_valid and the f16 loss scale are computed from it ON THE DEVICE inside the graph (ops.ragged_index), so one
         capture serves every later ``run(x, lengths)``.  16-bit modes only (the compacted path); under data parallelism the total row count of
         all ranks is all-reduced eagerly in front of the replay."""
-        from .training import allreduce_flat, setup_cabi_comm
-        setup_cabi_comm()               # MULTINN_COMM=capi: the communicator exists before anything is captured
         static_x = x_u8.clone()
         ragged = lengths is not None
         if ragged and not (self.dtype in ops.H16 and self.ragged_compact):
@@ -1434,35 +1428,7 @@ class RnnNade(RnnEstimator):
                 static_ntot.copy_(static_len.clamp(0, T).sum().float().reshape(1))
                 torch.distributed.all_reduce(static_ntot)
 
-        set_total()
-        cur = torch.cuda.current_stream()
-        side = torch.cuda.Stream()
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self.build_pianoroll(static_x, static_len, is_train=True, mode="train", n_total_dev=static_ntot)
-                self.train(optimizer, lr)
-        cur.wait_stream(side)
-        self._packed_step = -1          # the captured step packs the weights itself, whatever ran before (warmup = 0: a caller's own steps)
-        g_fb, g_opt = torch.cuda.CUDAGraph(), None
-        if not multi:
-            with graph_capture(g_fb):
-                self.build_pianoroll(static_x, static_len, is_train=True, mode="train")
-                self.train(optimizer, lr)
-                loss = self._loss
-        else:
-            # thread_local: the process group's watchdog thread may touch the runtime while this thread captures
-            with graph_capture(g_fb, capture_error_mode="thread_local"):
-                self.build_pianoroll(static_x, static_len, is_train=True, mode="train", n_total_dev=static_ntot)
-                self.backward()
-                loss = self._loss
-            g_opt = torch.cuda.CUDAGraph()
-            with graph_capture(g_opt, pool=g_fb.pool(), capture_error_mode="thread_local"):
-                self._grad_sumsq = compute_gradients(optimizer, self.store, self.clip_norm, lr, reduce=False)
-            self._packed_step = -1
-        self.store.step -= 1            # the captured step has not executed (host mirror of store.step_dev)
-
-        def run(x=None, lengths=None):
+        def feed(x=None, lengths=None):
             if x is not None:
                 static_x.copy_(x)
             if lengths is not None:
@@ -1470,13 +1436,10 @@ class RnnNade(RnnEstimator):
                     raise ValueError("this step was captured for full-length windows: capture it with lengths= to feed ragged ones")
                 static_len.copy_(lengths.to(device=dev, dtype=torch.int32))
                 set_total()
-            g_fb.replay()
-            if g_opt is not None:
-                allreduce_flat(self.store.grad)
-                g_opt.replay()
-            self.store.step += 1
-            return loss
-        run.graph = g_fb
+
+        set_total()
+        run = self._capture_step(feed, lambda: self.build_pianoroll(static_x, static_len, is_train=True, mode="train", n_total_dev=static_ntot),
+                                 optimizer, lr, warmup)
         run.ragged = ragged
         return run
 

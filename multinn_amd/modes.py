@@ -23,7 +23,7 @@ import os
 
 import torch
 
-from .common import Model, graph_capture, given_codes, given_tracks
+from .common import Model, capture_train_step, given_codes, given_tracks
 from .encoders import PassEncoder, DBNEncoder
 from .generators import RnnNade, RnnRBM, RnnMultiNADE
 from . import ops
@@ -453,37 +453,27 @@ class MultINNCore(Model):
         if ragged:
             for g in self._generators:
                 g.ragged_on_device = True
-        cur, side = torch.cuda.current_stream(), torch.cuda.Stream()
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            # warm-up steps are REAL optimiser steps: variables, persistent-kernel attributes and workspaces must exist before the capture.
-            # warmup = 0 is for a caller that has just run this very step eagerly (driver._captured_step: the capture then executes nothing)
-            for _ in range(int(warmup)):
-                self.train_step(sx, sl, optimizer, lr)
-        cur.wait_stream(side)
-        for g in self._generators:
-            g._packed_step = -1
-        graph = torch.cuda.CUDAGraph()
-        with graph_capture(graph):
-            loss = self.train_step(sx, sl, optimizer, lr)
-        stores = self._all_stores()
-        for st in stores:
-            st.step -= 1                                # the captured step has not executed (host mirror of step_dev)
 
-        def run(x=None, lengths=None):
+        def feed(x=None, lengths=None):
             if x is not None:
                 sx.copy_(x)
             if lengths is not None:
                 if not ragged:
                     raise ValueError("this step was captured for full-length windows: capture it with lengths= to feed ragged ones")
                 sl.copy_(lengths.to(device=sx.device, dtype=torch.int32))
-            graph.replay()
-            for st in stores:
-                st.step += 1
-            return loss
-        run.graph = graph
+
+        # warm-up steps are REAL optimiser steps: variables, persistent-kernel attributes and workspaces must exist before the capture.
+        # warmup = 0 is for a caller that has just run this very step eagerly (driver._captured_step: the capture then executes nothing)
+        run = capture_train_step(feed, lambda: self.train_step(sx, sl, optimizer, lr), warmup, self._generators, self._all_stores)
         run.ragged = ragged
         return run
+
+    def capturable(self, shape, ragged):
+        """Whether the driver may train windows of this shape as replays of graphed_train_step (driver._captured_step), full-length or ragged:
+        the modes whose captured step is tested (joint, jamming, composer), on one rank, once every generator's variables exist."""
+        from .training import dp_active
+        return self._mode in ("joint", "jamming", "composer") and not dp_active() and \
+            all(getattr(g, "store", None) is not None and g.store.theta is not None for g in self._generators)
 
     def build_pianoroll(self, x, lengths=None, is_train=False, mode="eval"):
         """The driver's evaluation entry (same name as RnnNade.build_pianoroll)."""

@@ -188,6 +188,7 @@ def test_two_graph_step_replays_at_full_size(monkeypatch):
     for _ in range(2):                                  # as bench.py does: eager steps on the main stream first
         g.train_step(x, None, opt)
     run = g.graphed_train_step(x, opt, warmup=1)
+    assert run.opt_graph is not None                    # the two-graph form is the one under test
     losses = []
     for _ in range(5):
         losses.append(float(run()))

@@ -744,6 +744,41 @@ def test_driver_epoch_replays_captured_steps(monkeypatch):
     assert torch.allclose(gg.store.theta, ge.store.theta, atol=5e-3)
 
 
+def test_captured_generator_is_freed_by_reference_count():
+    """A generator the driver has captured a train step for (cached in its own __dict__) and that has run a captured sampling scan is freed
+    by reference counting alone: nothing cyclic runs through its captured step or scan.  Cyclic garbage waits for the collector, which may
+    then run the finalisers of dead graphs, streams and pools in the middle of another capture (common.graph_capture)."""
+    import gc
+    import weakref
+    from multinn_amd import RnnNade, AdamOptimizer
+    from multinn_amd.driver import _captured_step
+    B, T, lr = 32, 12, 0.01
+    x = dev(make_batch(B, T, 8, 2, 7, rho=0.2))
+    gen = RnnNade(16, 16, [128, 128], keep_prob=0.9, precision="bf16", seed=3)
+    gen._materialize(16)
+    opt = AdamOptimizer(lr)
+    gen.train_step(x, None, opt, lr)                            # the driver's eager steps: the first packs the weights, ...
+    assert gen._stack._persist(B, T)                            # the persistent recurrence is the captured path
+    assert _captured_step(gen, x, opt, lr) is None              # ... the shape's first occurrence stays eager, ...
+    gen.train_step(x, None, opt, lr)
+    run = _captured_step(gen, x, opt, lr)                       # ... its second one is captured
+    assert run is not None
+    assert np.isfinite(float(run(x)))
+    out = gen.generate(x.reshape(B, T, 16)[:, :3].contiguous(), 2)
+    assert out.shape == (B, 2, 16)
+    gen.check()
+    ref = weakref.ref(gen)
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        del gen, run, out
+        alive = ref()
+        assert alive is None, [type(r).__name__ for r in gc.get_referrers(alive)]
+    finally:
+        if was:
+            gc.enable()
+
+
 def test_save_load_roundtrip(tmp_path):
     from multinn_amd import RnnNade, AdamOptimizer
     x = make_batch(4, 4, 4, 2, 3)
@@ -992,6 +1027,7 @@ def test_two_graph_data_parallel_step_matches_eager(monkeypatch):
     b.store.theta.copy_(a.store.theta)
     opt = AdamOptimizer(0.01)
     run = b.graphed_train_step(dev(x), opt, warmup=2)
+    assert run.opt_graph is not None                            # the two-graph form is the one under test
     assert b._stack._persist(32)                                # the persistent recurrence is the path under test
     la = [float(a.train_step(dev(x), None, opt)) for _ in range(7)]
     lb = [float(run()) for _ in range(5)]
