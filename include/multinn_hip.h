@@ -43,9 +43,9 @@ enum { MNN_STREAM_DROPOUT = 0, MNN_STREAM_NADE = 1, MNN_STREAM_RBM_H = 2, MNN_ST
 
 /* ABI version of THIS header: bumped whenever a signature or a descriptor struct changes.  mnn_version() returns the value the library
  * was built with; a loader must compare the two before its first call (multinn_amd/_lib.py load() does) -- a library built for another
- * version reads garbage arguments without any diagnosis otherwise.  122: conditional sampling -- a trailing `given` on mnn_nade_sample and mnn_generate_scan, mnn_nade_sample_job gained `given`.  121 (round 6): + mnn_gemm_tn_rows.  120 (round 6): mnn_step_increment gained `ls_dyn`, `ls_good`, `grow_after` (dynamic f16 loss scale).  119 (round 6): mnn_det_dense_job gained `Wp`, + mnn_det_dense_pack / _pack_bytes.  118 (round 6): mnn_det_lstm_job gained `Wp`, + mnn_det_lstm_pack / _pack_bytes, mnn_generate_scan_workspace_bytes gained `n_in`.  117 (round 6): + mnn_lstm_cluster_bwd_ok, + mnn_ragged_index / mnn_rows_gather16 / mnn_rows_scatter_f32, `n_rows_dev` on the gated NADE forwards and mnn_nade_logprob_bwd, `inv` / `hdr` on mnn_pianoroll_shift_timemajor_t, + mnn_lstm_resident_{fwd,bwd}_multi / mnn_lstm_cluster_{fwd,bwd}_multi / _bwd_multi_ok, `unsafe` on mnn_nade_logprob_fwd_gated, `unsafe` on mnn_nade_logprob_bwd.  116: + mnn_lstm_cluster_ok / _fwd / _bwd.  115: mnn_step_increment gained `sumsq`, `clip_norm`.  114: + mnn_lstm_resident_ok / _fwd / _bwd.  113: mnn_pianoroll_shift_timemajor_t gained `count`.  112: + mnn_generate_scan.  111: mnn_rbm_free_energy gained `p_h`.  110: mnn_clip_adam_step gained `skipped`; the dtype arguments of
+ * version reads garbage arguments without any diagnosis otherwise.  123: the clamped Gibbs chain -- mnn_rbm_gibbs gained a trailing `given`, `ld_given`.  122: conditional sampling -- a trailing `given` on mnn_nade_sample and mnn_generate_scan, mnn_nade_sample_job gained `given`.  121 (round 6): + mnn_gemm_tn_rows.  120 (round 6): mnn_step_increment gained `ls_dyn`, `ls_good`, `grow_after` (dynamic f16 loss scale).  119 (round 6): mnn_det_dense_job gained `Wp`, + mnn_det_dense_pack / _pack_bytes.  118 (round 6): mnn_det_lstm_job gained `Wp`, + mnn_det_lstm_pack / _pack_bytes, mnn_generate_scan_workspace_bytes gained `n_in`.  117 (round 6): + mnn_lstm_cluster_bwd_ok, + mnn_ragged_index / mnn_rows_gather16 / mnn_rows_scatter_f32, `n_rows_dev` on the gated NADE forwards and mnn_nade_logprob_bwd, `inv` / `hdr` on mnn_pianoroll_shift_timemajor_t, + mnn_lstm_resident_{fwd,bwd}_multi / mnn_lstm_cluster_{fwd,bwd}_multi / _bwd_multi_ok, `unsafe` on mnn_nade_logprob_fwd_gated, `unsafe` on mnn_nade_logprob_bwd.  116: + mnn_lstm_cluster_ok / _fwd / _bwd.  115: mnn_step_increment gained `sumsq`, `clip_norm`.  114: + mnn_lstm_resident_ok / _fwd / _bwd.  113: mnn_pianoroll_shift_timemajor_t gained `count`.  112: + mnn_generate_scan.  111: mnn_rbm_free_energy gained `p_h`.  110: mnn_clip_adam_step gained `skipped`; the dtype arguments of
  * mnn_pianoroll_shift_timemajor_t / mnn_grad_rows_fanout and the `f16` descriptor fields of round 3 are part of it. */
-#define MNN_ABI_VERSION 122
+#define MNN_ABI_VERSION 123
 int mnn_version(void);
 const char* mnn_last_error(void);
 
@@ -391,6 +391,11 @@ int mnn_nade_sample_multi(mnn_stream_t s, int njobs, const mnn_nade_sample_job* 
  * bv likewise.  Deterministic summation order (ascending index) for bit-exact sampling.
  * mnn_rbm_gibbs (rbm.py:192-231): k steps from v0 u8 [N,D]; p_v f32 [N,D], v_out u8 [N,D];
  *   uniforms Philox(stream 2/3, row = row_ids ? row_ids[n] : row0+n, sub = sub0+it, elem = j / d).
+ *   given (NULL allowed = unconditioned, the same kernels and bits as before): u8 codes [N, ld_given] (ld_given >= D; a step slice
+ *   given[:, s] of a [B, steps, D] block is read in place), 0 / 1 clamp the visible to that value, 255 leaves it free -- the clamped chain:
+ *   it starts from v0 with every clamped cell replaced by its code; every hidden phase is unchanged; in every visible phase a free cell draws
+ *   from exactly the uniform it draws unconditioned and a clamped cell keeps its code (its uniform is not consumed, no other counter moves).
+ *   v_out equals the code at clamped cells; p_v is sigmoid(logit) at every cell, clamped ones included; k = 0 returns the clamped v0 twice.
  * mnn_rbm_hidden (rbm.py:148-167,337-353): p_h f32 [N,Hn]; h u8 [N,Hn] sampled with `stream`
  *   (either may be NULL).  mnn_rbm_visible (rbm.py:169-190,355-373) likewise.
  * mnn_rbm_free_energy (rbm.py:256-258, per-row, R4): F f32 [N].
@@ -399,10 +404,10 @@ int mnn_nade_sample_multi(mnn_stream_t s, int njobs, const mnn_nade_sample_job* 
 size_t mnn_rbm_workspace_bytes(int D, int Hn);
 int mnn_rbm_gibbs(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
                   const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0,
-                  float* p_v, uint8_t* v_out, void* workspace);
+                  float* p_v, uint8_t* v_out, void* workspace, const uint8_t* given, int ld_given);
 /* The same chain with the step counter of the optimiser read ON THE DEVICE: effective seed = seed + *seed_step (NULL: seed).  A launch
  * captured in a hipGraph then draws new uniforms at every replay, like the dropout masks (mnn_dropout_mask's step pointer); the
- * reference re-runs its random ops at every sess.run (rbm.py:222-226). */
+ * reference re-runs its random ops at every sess.run (rbm.py:222-226).  Unconditioned (training's CD-k chain). */
 int mnn_rbm_gibbs_stepped(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
                   const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0,
                   float* p_v, uint8_t* v_out, void* workspace, const int* seed_step);

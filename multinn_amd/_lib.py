@@ -9,7 +9,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MULTINN_HIP_LIB", os.path.join(HERE, "libmultinn_hip.so"))   # override: A/B builds of the same ABI
 
-ABI_VERSION = 122          # == MNN_ABI_VERSION of include/multinn_hip.h; load() refuses a library built for another one
+ABI_VERSION = 123          # == MNN_ABI_VERSION of include/multinn_hip.h; load() refuses a library built for another one
 F32, BF16, U8, F16 = 0, 1, 2, 3
 GEMM_ACCUMULATE, GEMM_ATOMIC, GEMM_A_KBLOCK32 = 1, 2, 8
 
@@ -43,7 +43,7 @@ SIGNATURES = {
     "mnn_nade_logprob_bwd": (_i, [_p, _i, _i, _i, _i, _p, _l, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "mnn_nade_sample": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p, _f, _u64, _u32, _u32, _p, _l, _i, _i, _p, _p]),
     "mnn_rbm_workspace_bytes": (_sz, [_i, _i]),
-    "mnn_rbm_gibbs": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _u64, _u32, _p, _u32, _p, _p, _p]),
+    "mnn_rbm_gibbs": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _u64, _u32, _p, _u32, _p, _p, _p, _p, _i]),
     "mnn_rbm_gibbs_stepped": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _u64, _u32, _p, _u32, _p, _p, _p, _p]),
     "mnn_rbm_hidden": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _i, _i, _u64, _u32, _u32, _p, _p]),
     "mnn_rbm_visible": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _i, _i, _u64, _u32, _u32, _p, _p, _p]),
@@ -150,6 +150,11 @@ _lib = None
 
 class MnnError(RuntimeError):
     pass
+
+
+class MnnUnsupported(MnnError, NotImplementedError):
+    """A request this build has no path for (e.g. conditional generation of a model that does not live on a ROCm device): caught by both
+    `except MnnError` and `except NotImplementedError`."""
 
 
 def load():

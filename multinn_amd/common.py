@@ -553,15 +553,17 @@ class RBM(Model):
         ops.rbm_visible(hh.contiguous(), self.W, bv, stream, self.seed if seed is None else seed, row0, sub, p, v)
         return p, v
 
-    def sample(self, v, bh=None, bv=None, k=None, seed=None, row0=0, row_ids=None, sub0=0):
-        """rbm.py:192-231; k=None -> self.k (R1).  Returns (p_v, v_sample u8)."""
+    def sample(self, v, bh=None, bv=None, k=None, seed=None, row0=0, row_ids=None, sub0=0, given=None):
+        """rbm.py:192-231; k=None -> self.k (R1).  Returns (p_v, v_sample u8).  given (optional): codes u8 [N, D] (ops.rbm_gibbs) -- the
+        clamped chain: v_sample equals the code at every clamped visible, the free ones are sampled conditioned on all of them."""
         k = self._k if k is None else k
         bh = bh if bh is not None else self.bh
         bv = bv if bv is not None else self.bv
         N, D = v.shape
         p_v = torch.empty((N, D), device=v.device)
         v_s = torch.empty((N, D), device=v.device, dtype=torch.uint8)
-        ops.rbm_gibbs(v.to(torch.uint8).contiguous(), self.W, bh, bv, k, self.seed if seed is None else seed, row0, row_ids, sub0, p_v, v_s)
+        ops.rbm_gibbs(v.to(torch.uint8).contiguous(), self.W, bh, bv, k, self.seed if seed is None else seed, row0, row_ids, sub0, p_v, v_s,
+                      given=given)
         return p_v, v_s
 
     def free_energy(self, v, bh=None, bv=None):

@@ -61,19 +61,47 @@ __device__ __forceinline__ void rbm_load_rows(const TV* __restrict__ src, int N,
 
 // ----------------------------------------------------------------------------------------------
 // k-step Gibbs chain (rbm.py:192-231)
+//
+// GIVEN (the clamped chain of conditional sampling; every form below has one): `given` u8 [N, ld_given], 0 / 1 clamp the visible to that
+// value, 255 leaves it free.  The chain starts from v0 with the clamped cells replaced by their codes; every hidden phase is today's; in every
+// visible phase a clamped cell keeps its code and leaves its uniform unused, a free cell draws from the uniform it draws unconditioned (the
+// counters are per cell: nothing shifts).  p_v is sigmoid(logit) at every cell, clamped ones included.
 // ----------------------------------------------------------------------------------------------
+#define RBM_GIVEN_FREE 255
+
+// The codes of a clamped chain, from the trailing kernel arguments (const uint8_t* given, int ld_given).  The free chain's kernels are the
+// instantiations with NO trailing arguments: their parameter lists -- and with them the kernarg offsets of the implicit arguments they read
+// (blockDim) -- are the ones they always had, and GIVEN = false removes every clamp at compile time.
+struct GibbsCodes {
+    const uint8_t* p = nullptr;
+    int ld = 0;
+    __device__ GibbsCodes() {}
+    __device__ GibbsCodes(const uint8_t* p_, int ld_) : p(p_), ld(ld_) {}
+};
+
+template <typename... Codes>
 __global__ void __launch_bounds__(256)
 rbm_gibbs_kernel(int N, int D, int Hn, int k, const uint8_t* __restrict__ v0, const float* __restrict__ W, const float* __restrict__ Wt,
                  const float* __restrict__ bh, int ld_bh, const float* __restrict__ bv, int ld_bv, uint64_t seed, uint32_t row0,
                  const uint32_t* __restrict__ row_ids, uint32_t sub0, float* __restrict__ p_v, uint8_t* __restrict__ v_out,
-                 const int* __restrict__ seed_step) {
+                 const int* __restrict__ seed_step, Codes... codes) {
+    constexpr bool GIVEN = sizeof...(Codes) != 0;
+    const GibbsCodes gc(codes...);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (seed_step != nullptr) seed += (uint64_t)(int64_t)*seed_step;      // step counter on the device: a captured launch draws anew every replay
     const int Dp = (D + 3) & ~3, Hp = (Hn + 3) & ~3;
     float* vs = smem;                 // [RBM_R][Dp]
     float* hs = smem + RBM_R * Dp;    // [RBM_R][Hp]
+    uint8_t* cs = reinterpret_cast<uint8_t*>(hs + RBM_R * Hp);      // GIVEN: the rows' codes [RBM_R][Dp]
     const int n0 = blockIdx.x * RBM_R;
     rbm_load_rows<uint8_t>(v0, N, n0, D, Dp, vs);
+    if (GIVEN)                        // the same cells per thread as rbm_load_rows: no barrier in between
+        for (int e = threadIdx.x; e < RBM_R * Dp; e += blockDim.x) {
+            const int r = e / Dp, d = e % Dp, n = n0 + r;
+            const uint8_t c = (n < N && d < D) ? gc.p[(size_t)n * gc.ld + d] : (uint8_t)RBM_GIVEN_FREE;
+            cs[e] = c;
+            if (c != RBM_GIVEN_FREE) vs[e] = (float)c;
+        }
     for (int e = threadIdx.x; e < RBM_R * Hp; e += blockDim.x) hs[e] = 0.f;
     __syncthreads();
     if (k == 0) {                     // tf.while_loop with zero iterations returns (v, v)
@@ -100,8 +128,13 @@ rbm_gibbs_kernel(int N, int D, int Hn, int k, const uint8_t* __restrict__ v0, co
             const int n = n0 + r;
             if (n >= N) return;
             const float p = det_sigmoid(z);
-            const float u = philox_uniform1(seed, MNN_STREAM_RBM_V, rbm_rowid(row_ids, row0, n), sub0 + (uint32_t)it, (uint32_t)d);
-            const float s = u < p ? 1.f : 0.f;
+            float s;
+            if (GIVEN && cs[r * Dp + d] != RBM_GIVEN_FREE) {
+                s = (float)cs[r * Dp + d];
+            } else {
+                const float u = philox_uniform1(seed, MNN_STREAM_RBM_V, rbm_rowid(row_ids, row0, n), sub0 + (uint32_t)it, (uint32_t)d);
+                s = u < p ? 1.f : 0.f;
+            }
             vs[r * Dp + d] = s;
             if (last) {
                 if (p_v) p_v[(size_t)n * D + d] = p;
@@ -148,11 +181,13 @@ __device__ __forceinline__ void rbm_phase_lds(const float* __restrict__ in_s, in
     for (int r = 0; r < RG; ++r) fn(g * RG + r, r, o, acc[r]);
 }
 
-template <int R, int RGH, int RGV>        // rows per thread in the hidden / visible phase (R / RG row groups of n_out threads each)
+template <int R, int RGH, int RGV, typename... Codes>        // rows per thread in the hidden / visible phase (R / RG row groups of n_out threads each)
 __global__ void __launch_bounds__(256)
 rbm_gibbs_lds_kernel(int N, int D, int Hn, int k, const uint8_t* __restrict__ v0, const float* __restrict__ W, const float* __restrict__ bh,
                      int ld_bh, const float* __restrict__ bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* __restrict__ row_ids,
-                     uint32_t sub0, float* __restrict__ p_v, uint8_t* __restrict__ v_out, const int* __restrict__ seed_step) {
+                     uint32_t sub0, float* __restrict__ p_v, uint8_t* __restrict__ v_out, const int* __restrict__ seed_step, Codes... codes) {
+    constexpr bool GIVEN = sizeof...(Codes) != 0;
+    const GibbsCodes gc(codes...);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (seed_step != nullptr) seed += (uint64_t)(int64_t)*seed_step;
     const int Dp = (D + 3) & ~3, Hp = (Hn + 3) & ~3, ldw = Hn + 1;
@@ -165,11 +200,15 @@ rbm_gibbs_lds_kernel(int N, int D, int Hn, int k, const uint8_t* __restrict__ v0
     for (int e = threadIdx.x; e < R * Dp; e += blockDim.x) {
         const int r = e / Dp, kx = e % Dp, n = n0 + r;
         vs[e] = (n < N && kx < D) ? (float)v0[(size_t)n * D + kx] : 0.f;
+        if (GIVEN && n < N && kx < D) {
+            const uint8_t c = gc.p[(size_t)n * gc.ld + kx];
+            if (c != RBM_GIVEN_FREE) vs[e] = (float)c;
+        }
     }
     for (int e = threadIdx.x; e < R * Hp; e += blockDim.x) hs[e] = 0.f;
-    // this thread's biases and row ids: constant over the chain
+    // this thread's biases, row ids (and GIVEN: codes of its visible cells): constant over the chain
     float bhr[RGH], bvr[RGV];
-    uint32_t idh[RGH], idv[RGV];
+    uint32_t idh[RGH], idv[RGV], cvr[RGV];
     {
         const int g = threadIdx.x / Hn, o = threadIdx.x - g * Hn;
 #pragma unroll
@@ -186,6 +225,7 @@ rbm_gibbs_lds_kernel(int N, int D, int Hn, int k, const uint8_t* __restrict__ v0
             const int n = min(n0 + min(g * RGV + r, R - 1), N - 1);
             bvr[r] = bv[(size_t)n * ld_bv + min(o, D - 1)];
             idv[r] = rbm_rowid(row_ids, row0, n);
+            if (GIVEN) cvr[r] = gc.p[(size_t)n * gc.ld + min(o, D - 1)];
         }
     }
     __syncthreads();
@@ -212,8 +252,13 @@ rbm_gibbs_lds_kernel(int N, int D, int Hn, int k, const uint8_t* __restrict__ v0
             const int n = n0 + r;
             if (n >= N) return;
             const float p = det_sigmoid(acc + bvr[rl]);
-            const float u = philox_uniform1(seed, MNN_STREAM_RBM_V, idv[rl], sub0 + (uint32_t)it, (uint32_t)d);
-            const float sv = u < p ? 1.f : 0.f;
+            float sv;
+            if (GIVEN && cvr[rl] != RBM_GIVEN_FREE) {        // clamped: no Philox evaluation
+                sv = (float)cvr[rl];
+            } else {
+                const float u = philox_uniform1(seed, MNN_STREAM_RBM_V, idv[rl], sub0 + (uint32_t)it, (uint32_t)d);
+                sv = u < p ? 1.f : 0.f;
+            }
             vs[r * Dp + d] = sv;
             if (last) {
                 if (p_v) p_v[(size_t)n * D + d] = p;
@@ -229,24 +274,42 @@ static size_t rbm_lds_resident_bytes(int R, int D, int Hn) {
 }
 
 // Launch the resident-W form when it applies (both phases fit 256 threads, W fits LDS); false: the caller streams.
-template <int R, int RGH, int RGV>
+template <int R, int RGH, int RGV, bool GIVEN>
 static bool launch_gibbs_lds(hipStream_t st, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh, const float* bv,
                              int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v, uint8_t* v_out,
-                             const int* seed_step) {
+                             const int* seed_step, const uint8_t* given, int ld_given) {
     const size_t lds = rbm_lds_resident_bytes(R, D, Hn);
+    const void* fn = GIVEN ? reinterpret_cast<const void*>(&rbm_gibbs_lds_kernel<R, RGH, RGV, const uint8_t*, int>)
+                           : reinterpret_cast<const void*>(&rbm_gibbs_lds_kernel<R, RGH, RGV>);
     static bool raised_[64];                           // per instantiation and device: dynamic LDS above 64 KB has to be asked for once
     bool& raised = mnn_dev_flag(raised_);
     if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rbm_gibbs_lds_kernel<R, RGH, RGV>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess) {
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
             (void)hipGetLastError();
             return false;
         }
         raised = true;
     }
-    hipLaunchKernelGGL((rbm_gibbs_lds_kernel<R, RGH, RGV>), dim3(cdiv(N, R)), dim3(256), lds, st, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed,
-                       row0, row_ids, sub0, p_v, v_out, seed_step);
+    if constexpr (GIVEN)
+        hipLaunchKernelGGL((rbm_gibbs_lds_kernel<R, RGH, RGV, const uint8_t*, int>), dim3(cdiv(N, R)), dim3(256), lds, st, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv,
+                           seed, row0, row_ids, sub0, p_v, v_out, seed_step, given, ld_given);
+    else
+        hipLaunchKernelGGL((rbm_gibbs_lds_kernel<R, RGH, RGV>), dim3(cdiv(N, R)), dim3(256), lds, st, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed,
+                           row0, row_ids, sub0, p_v, v_out, seed_step);
     return true;
+}
+
+// the instantiation for this shape: rows per thread by how many row groups of n_out threads fit 256
+template <bool GIVEN>
+static bool try_gibbs_lds(hipStream_t st, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh, const float* bv,
+                          int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v, uint8_t* v_out,
+                          const int* seed_step, const uint8_t* given, int ld_given) {
+    const int gh = 256 / Hn, gv = 256 / D;          // row groups available in the hidden / visible phase
+#define TRY(R, RGH, RGV) (rbm_lds_resident_bytes(R, D, Hn) <= 158 * 1024 && \
+                          launch_gibbs_lds<R, RGH, RGV, GIVEN>(st, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, \
+                                                               seed_step, given, ld_given))
+    return gv >= 2 ? (gh >= 2 ? TRY(2, 1, 1) : TRY(2, 2, 1)) : (gh >= 2 ? TRY(2, 1, 2) : TRY(2, 2, 2));
+#undef TRY
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -289,7 +352,25 @@ __device__ __forceinline__ void gm_chain(const float* __restrict__ Ws, int ldw, 
     for (int s = 0; s < K / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[(size_t)s * astep], (float)sp[2 * s], acc, 0, 0, 0);
 }
 
-__global__ void __launch_bounds__(512) rbm_gibbs_mfma_kernel(GibbsMfmaArgs A) {
+// GIVEN helpers of the matrix-core chain: the codes of cells d0 .. d0 + 3 of one row packed into a word (cells past D repeat D - 1: never used),
+// and whether any of the four is free
+__device__ __forceinline__ uint32_t gm_code_quad(const uint8_t* __restrict__ given, int ld_given, int row, int d0, int D) {
+    uint32_t q = 0u;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) q |= (uint32_t)given[(size_t)row * ld_given + min(d0 + e, D - 1)] << (8 * e);
+    return q;
+}
+__device__ __forceinline__ bool gm_any_free(uint32_t q) {
+    return (q & 0xffu) == 0xffu || (q & 0xff00u) == 0xff00u || (q & 0xff0000u) == 0xff0000u || (q & 0xff000000u) == 0xff000000u;
+}
+
+// GIVEN: the codes clamp the byte states at load and after each visible quad; a lane's codes of its first-pass visible job stay in registers
+// (four packed words next to bvr: no LDS, so the given form fits wherever the free one does); a quad whose four cells are all clamped skips its
+// Philox block
+template <typename... Codes>
+__global__ void __launch_bounds__(512) rbm_gibbs_mfma_kernel(GibbsMfmaArgs A, Codes... codes) {
+    constexpr bool GIVEN = sizeof...(Codes) != 0;
+    const GibbsCodes gc(codes...);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     uint64_t seed = A.seed;
     if (A.seed_step != nullptr) seed += (uint64_t)(int64_t)*A.seed_step;
@@ -306,10 +387,18 @@ __global__ void __launch_bounds__(512) rbm_gibbs_mfma_kernel(GibbsMfmaArgs A) {
     {   // v0 rows: thread t -> row t >> 3, eight lanes walk its bytes, sixteen loads in flight (unconditional, clamped)
         const int rr = threadIdx.x >> 3, sub = threadIdx.x & 7, n = n0 + rr;
         const uint8_t* __restrict__ src = A.v0 + (size_t)min(n, N - 1) * D;
+        const uint8_t* __restrict__ gsrc = GIVEN ? gc.p + (size_t)min(n, N - 1) * gc.ld : nullptr;
         for (int kb = sub; kb < pv; kb += 128) {
             uint8_t v[16];
 #pragma unroll
             for (int q = 0; q < 16; ++q) v[q] = src[min(kb + 8 * q, D - 1)];
+            if (GIVEN) {
+                uint8_t c[16];
+#pragma unroll
+                for (int q = 0; q < 16; ++q) c[q] = gsrc[min(kb + 8 * q, D - 1)];
+#pragma unroll
+                for (int q = 0; q < 16; ++q) v[q] = c[q] != RBM_GIVEN_FREE ? c[q] : v[q];
+            }
 #pragma unroll
             for (int q = 0; q < 16; ++q)
                 if (kb + 8 * q < pv) vs[rr * pv + kb + 8 * q] = (n < N && kb + 8 * q < D) ? v[q] : (uint8_t)0;
@@ -326,6 +415,7 @@ __global__ void __launch_bounds__(512) rbm_gibbs_mfma_kernel(GibbsMfmaArgs A) {
     // the biases of this wave's first-pass jobs stay in registers over the chain (they do not change between Gibbs iterations; loaded inside
     // the epilogue, every accumulator quad waited for its own L2 round trip in every iteration)
     float bhr[2][16], bvr[16];
+    uint32_t cvr[4];                                          // GIVEN: the codes of the first-pass visible job, one quad per word
 #pragma unroll
     for (int q = 0; q < 2; ++q)
 #pragma unroll
@@ -338,6 +428,9 @@ __global__ void __launch_bounds__(512) rbm_gibbs_mfma_kernel(GibbsMfmaArgs A) {
         const int row = min(n0 + 32 * rt + r, N - 1);
 #pragma unroll
         for (int e = 0; e < 16; ++e) bvr[e] = A.bv[(size_t)row * A.ld_bv + min(32 * dt + (e & 3) + 8 * (e >> 2) + 4 * hh, D - 1)];
+        if (GIVEN)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) cvr[g4] = gm_code_quad(gc.p, gc.ld, row, 32 * dt + 8 * g4 + 4 * hh, D);
     }
     __syncthreads();
     if (A.k == 0) {
@@ -405,13 +498,16 @@ __global__ void __launch_bounds__(512) rbm_gibbs_mfma_kernel(GibbsMfmaArgs A) {
                 const int d0 = 32 * dt + 8 * g4 + 4 * hh;
                 if (d0 >= D) continue;
                 float u[4];
-                philox_uniform4(seed, MNN_STREAM_RBM_V, idv, A.sub0 + (uint32_t)it, (uint32_t)(d0 >> 2), u);
+                uint32_t cq = 0xffffffffu;
+                if (GIVEN) cq = job < 8 ? cvr[g4] : gm_code_quad(gc.p, gc.ld, min(row, N - 1), d0, D);
+                if (!GIVEN || gm_any_free(cq)) philox_uniform4(seed, MNN_STREAM_RBM_V, idv, A.sub0 + (uint32_t)it, (uint32_t)(d0 >> 2), u);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int d = d0 + e;
                     if (d >= D) continue;
                     const float p = det_sigmoid(acc[4 * g4 + e] + (job < 8 ? bvr[4 * g4 + e] : A.bv[(size_t)min(row, N - 1) * A.ld_bv + d]));
-                    const uint8_t sv = u[e] < p ? 1 : 0;
+                    const uint8_t c = (uint8_t)(cq >> (8 * e));
+                    const uint8_t sv = GIVEN && c != RBM_GIVEN_FREE ? c : (u[e] < p ? 1 : 0);
                     vs[(32 * rt + r) * pv + d] = sv;
                     if (last && row < N) {
                         if (A.p_v) A.p_v[(size_t)row * D + d] = p;
@@ -434,25 +530,26 @@ extern "C" int mnn_transpose(mnn_stream_t s, const void* in, int in_dtype, int R
 
 static size_t rbm_lds_bytes(int D, int Hn) { return (size_t)RBM_R * (((D + 3) & ~3) + ((Hn + 3) & ~3)) * sizeof(float); }
 
-extern "C" int mnn_rbm_gibbs_stepped(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
-                                     const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v,
-                                     uint8_t* v_out, void* workspace, const int* seed_step) {
+// The dispatch of both entry points: the same form for a shape whether or not `given` is set (the clamped forms need no LDS beyond the free
+// ones' except the streaming kernel's codes, which no threshold looks at)
+static int rbm_gibbs_launch(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
+                            const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v,
+                            uint8_t* v_out, void* workspace, const int* seed_step, const uint8_t* given, int ld_given) {
     MNN_REQUIRE(N > 0 && D > 0 && Hn > 0 && k >= 0, "mnn_rbm_gibbs: bad sizes N=%d D=%d Hn=%d k=%d", N, D, Hn, k);
     MNN_REQUIRE(v0 && W && bh && bv && workspace, "mnn_rbm_gibbs: null pointer");
     MNN_REQUIRE((ld_bh == 0 || ld_bh >= Hn) && (ld_bv == 0 || ld_bv >= D), "mnn_rbm_gibbs: bad bias leading dimension");
-    MNN_REQUIRE(rbm_lds_bytes(D, Hn) <= 160 * 1024, "mnn_rbm_gibbs: D+Hn too large for LDS");
+    MNN_REQUIRE(given == nullptr || ld_given >= D, "mnn_rbm_gibbs: ld_given=%d < D=%d", ld_given, D);
+    const size_t codes_lds = given != nullptr ? (size_t)RBM_R * ((D + 3) & ~3) : 0;
+    MNN_REQUIRE(rbm_lds_bytes(D, Hn) + codes_lds <= 160 * 1024, "mnn_rbm_gibbs: D+Hn too large for LDS");
+    hipStream_t st = (hipStream_t)s;
     if (N < 2048 && Hn <= 256 && D <= 256 && getenv("MNN_RBM_STREAM_W") == nullptr) {
         // sampling-sized batches: W resident in LDS, two rows per workgroup (one workgroup per CU: at training sizes -- 32 768 rows --
         // the streaming kernel's eight rows per workgroup and several workgroups per CU win, 1.5 vs 2.5 ms; round 3: also with the workgroup
         // walking over its row groups so that W is loaded once, 4.9 ms -- two rows per pass are two dependent fma chains per thread at one
         // wave per SIMD: latency-bound); rows per thread by how many row groups of n_out threads fit 256
-        hipStream_t st = (hipStream_t)s;
-        const int gh = 256 / Hn, gv = 256 / D;          // row groups available in the hidden / visible phase
-        bool done = false;
-#define TRY(R, RGH, RGV) (rbm_lds_resident_bytes(R, D, Hn) <= 158 * 1024 && \
-                          launch_gibbs_lds<R, RGH, RGV>(st, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, seed_step))
-        done = gv >= 2 ? (gh >= 2 ? TRY(2, 1, 1) : TRY(2, 2, 1)) : (gh >= 2 ? TRY(2, 1, 2) : TRY(2, 2, 2));
-#undef TRY
+        const bool done = given != nullptr
+                              ? try_gibbs_lds<true>(st, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, seed_step, given, ld_given)
+                              : try_gibbs_lds<false>(st, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, seed_step, nullptr, 0);
         if (done) {
             MNN_LAUNCH_CHECK();
             return MNN_OK;
@@ -463,26 +560,40 @@ extern "C" int mnn_rbm_gibbs_stepped(mnn_stream_t s, int N, int D, int Hn, int k
         static bool raised_[64];
         bool& raised = mnn_dev_flag(raised_);
         if (!raised) {
-            MNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rbm_gibbs_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            MNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rbm_gibbs_mfma_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            MNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rbm_gibbs_mfma_kernel<const uint8_t*, int>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             raised = true;
         }
         GibbsMfmaArgs a{N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, seed_step};
-        hipLaunchKernelGGL(rbm_gibbs_mfma_kernel, dim3(cdiv(N, GM_ROWS)), dim3(512), gibbs_mfma_lds_bytes(D, Hn), (hipStream_t)s, a);
+        if (given != nullptr)
+            hipLaunchKernelGGL((rbm_gibbs_mfma_kernel<const uint8_t*, int>), dim3(cdiv(N, GM_ROWS)), dim3(512), gibbs_mfma_lds_bytes(D, Hn), st, a, given, ld_given);
+        else
+            hipLaunchKernelGGL(rbm_gibbs_mfma_kernel<>, dim3(cdiv(N, GM_ROWS)), dim3(512), gibbs_mfma_lds_bytes(D, Hn), st, a);
         MNN_LAUNCH_CHECK();
         return MNN_OK;
     }
     int rc = mnn_transpose(s, W, MNN_F32, D, Hn, Hn, workspace, MNN_F32, D);
     if (rc != MNN_OK) return rc;
-    hipLaunchKernelGGL(rbm_gibbs_kernel, dim3(cdiv(N, RBM_R)), dim3(256), rbm_lds_bytes(D, Hn), (hipStream_t)s, N, D, Hn, k, v0, W,
-                       (const float*)workspace, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, seed_step);
+    if (given != nullptr)
+        hipLaunchKernelGGL((rbm_gibbs_kernel<const uint8_t*, int>), dim3(cdiv(N, RBM_R)), dim3(256), rbm_lds_bytes(D, Hn) + codes_lds, st, N, D, Hn, k, v0, W,
+                           (const float*)workspace, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, seed_step, given, ld_given);
+    else
+        hipLaunchKernelGGL(rbm_gibbs_kernel<>, dim3(cdiv(N, RBM_R)), dim3(256), rbm_lds_bytes(D, Hn), st, N, D, Hn, k, v0, W,
+                           (const float*)workspace, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, seed_step);
     MNN_LAUNCH_CHECK();
     return MNN_OK;
 }
 
+extern "C" int mnn_rbm_gibbs_stepped(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
+                                     const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v,
+                                     uint8_t* v_out, void* workspace, const int* seed_step) {
+    return rbm_gibbs_launch(s, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, workspace, seed_step, nullptr, 0);
+}
+
 extern "C" int mnn_rbm_gibbs(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
                              const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v,
-                             uint8_t* v_out, void* workspace) {
-    return mnn_rbm_gibbs_stepped(s, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, workspace, nullptr);
+                             uint8_t* v_out, void* workspace, const uint8_t* given, int ld_given) {
+    return rbm_gibbs_launch(s, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, workspace, nullptr, given, ld_given);
 }
 
 // ----------------------------------------------------------------------------------------------

@@ -1006,7 +1006,7 @@ class RnnEstimator(Generator):
             if given is None:
                 samples, _ = self.sample_single(intro, state)
             else:
-                samples, _ = self.sample_single(intro, state, given=given[:, s].contiguous())
+                samples, _ = self.sample_single(intro, state, given=given[:, s])
             state = self.single_step(samples, state)
             intro = samples
             out.append(samples)
@@ -1542,7 +1542,7 @@ class RnnNade(RnnEstimator):
         smp = torch.empty((Bn, M * D), device=out.device, dtype=torch.uint8)
         nll = torch.empty((M, Bn), device=out.device)
         ops.nade_sample(out, self.store["nade/w_enc"], self.store["nade/w_dec"], M, D, Hn, temperature, self.seed, self.row0,
-                        getattr(self, "_gen_step", 0), smp, track_minor=(M > 1), nll=nll, given=given)
+                        getattr(self, "_gen_step", 0), smp, track_minor=(M > 1), nll=nll, given=None if given is None else given.contiguous())
         return smp, (nll[0] if M == 1 else [nll[m] for m in range(M)])
 
 
@@ -1804,16 +1804,12 @@ class RnnRBM(RnnEstimator):
         Hn, D = self.num_hidden[-1], self.num_dims
         return RnnEstimatorStateTuple(out[:, :Hn], out[:, Hn:Hn + D], tuple(new))
 
-    def generate(self, x, num_steps, given=None):
-        """RnnEstimator.generate; a clamped cell in `given` would need a clamped Gibbs chain, which this generator does not have."""
-        if given is not None and bool((given != 255).any()):
-            raise NotImplementedError("conditional generation with an RBM generator (a clamped Gibbs chain) is not implemented")
-        return super().generate(x, num_steps)
-
-    def sample_single(self, inputs, state):
-        """rnn_rbm.py:283-297 with k = rbm.k (R1): returns (sample u8, cond_prob)."""
+    def sample_single(self, inputs, state, given=None):
+        """rnn_rbm.py:283-297 with k = rbm.k (R1): returns (sample u8, cond_prob).  given (optional): codes u8 [B, D] (a step slice of
+        generate's [B, num_steps, D] is read in place): the clamped Gibbs chain -- clamped visibles are emitted as given, every free one is
+        sampled conditioned on all of them (RBM.sample); cond_prob is sigmoid(logit) at every visible."""
         p_v, v = self._rbm.sample(inputs[:, :self.num_dims], state.b_enc, state.b_dec, self._k, self.seed, self.row0, None,
-                                  getattr(self, "_gen_step", 0) * max(self._k, 1))
+                                  getattr(self, "_gen_step", 0) * max(self._k, 1), given=given)
         return v, p_v
 
     def pretrain(self, optimizer, lr, run_optimizer=True):

@@ -27,6 +27,7 @@ from .common import Model, capture_train_step, given_codes, given_tracks
 from .encoders import PassEncoder, DBNEncoder
 from .generators import RnnNade, RnnRBM, RnnMultiNADE
 from . import ops
+from ._lib import MnnUnsupported
 from .training import compute_gradients_multi, world
 
 
@@ -245,11 +246,14 @@ class MultINNCore(Model):
             raise ValueError(f"given has shape {tuple(given.shape)}, expected {shape}")
         whole, some = given_tracks(given_mask, shape)
         self._refuse_given(whole, some)
+        if self.device is not None and torch.device(self.device).type != "cuda":
+            raise MnnUnsupported(f"conditional generation runs in the HIP sampling kernels: this model lives on {self.device}, not a ROCm device")
         dev = self._x.device if self._x is not None else given.device
         return given_codes(given.to(dev), given_mask, shape), whole, some
 
     def _refuse_given(self, whole, some):
-        """NotImplementedError for a mask this mode's generators cannot honour (RnnRBM: only tracks it does not sample)."""
+        """NotImplementedError for a mask this mode's generators cannot honour (every generator of the joint, composer and jamming modes
+        clamps inside its sampling kernels; see MultINNFeedback)."""
 
     def evaluator(self):
         """multinn_core.py:343-362: musical metrics of the fed batch reshaped into bars `[B, bars, 4*beat_resolution, pitch_span, M]`."""
@@ -553,14 +557,11 @@ class MultINNJoint(MultINNCore):
             metrics[k] = metrics[k] / self.num_tracks
         return metrics, metrics_upd, summaries
 
-    def _refuse_given(self, whole, some):
-        if isinstance(self._generator, RnnRBM) and any(some):
-            raise NotImplementedError("joint mode with an RBM generator cannot condition on given notes (that needs a clamped Gibbs chain)")
-
     def generate(self, num_steps, given=None, given_mask=None):
-        """multinn_joint.py:188-215 -> u8 `[B, num_steps, P, M]`.  given / given_mask: conditional generation (MultINNCore._given).  The
-        one NADE orders the visibles of a step p M + m: a free visible is conditioned on the clamped visibles ordered BEFORE it only (the
-        ones after it are fed forward to the later visibles and steps) -- what a NADE offers without importance sampling."""
+        """multinn_joint.py:188-215 -> u8 `[B, num_steps, P, M]`.  given / given_mask: conditional generation (MultINNCore._given), codes in
+        p M + m order.  The one NADE orders the visibles of a step p M + m: a free visible is conditioned on the clamped visibles ordered
+        BEFORE it only (the ones after it are fed forward to the later visibles and steps) -- what a NADE offers without importance sampling.
+        An RBM generator runs the clamped Gibbs chain: every free visible is conditioned on ALL clamped ones, in any position."""
         cond = self._given(num_steps, given, given_mask)
         if self._x_encoded is None:
             MultINNCore._build_all(self, "generate")
@@ -710,14 +711,10 @@ class MultINNJamming(MultIEncoderNN):
     def _decode_generator_outputs(self):
         return self._decode_tracks(self._x_hidden)
 
-    def _refuse_given(self, whole, some):
-        for i, g in enumerate(self.generators):
-            if isinstance(g, RnnRBM) and some[i] and not whole[i]:
-                raise NotImplementedError(f"track {i}: an RBM generator takes whole given tracks only (a partial mask needs a clamped Gibbs chain)")
-
     def generate(self, num_steps, given=None, given_mask=None):
         """multinn_jamming.py:101-133 -> u8 `[B, num_steps, P, M]`.  given / given_mask (MultINNCore._given): the generators are independent --
-        a wholly given track is not sampled at all, a partly given one is clamped inside its NADE generator's scan."""
+        a wholly given track is not sampled at all, a partly given one is clamped inside its generator's scan (the NADE sampling kernels, or
+        an RBM generator's clamped Gibbs chain)."""
         cond = self._given(num_steps, given, given_mask)
         if self._x_encoded is None:
             MultINNCore._build_all(self, "generate")
@@ -896,6 +893,12 @@ class MultINNFeedback(MultINNJamming):
     def _generator_io(self, i):
         inputs = torch.cat([self._x_encoded[i].float(), self._x_feedback], dim=-1)               # multinn_feedback.py:85-91
         return inputs[:, :-1], self._x_encoded[i][:, 1:]
+
+    def _refuse_given(self, whole, some):
+        """The feedback scan pastes an RBM generator's given track (feedback.FeedbackRnnSampler): whole tracks only."""
+        for i, g in enumerate(self.generators):
+            if isinstance(g, RnnRBM) and some[i] and not whole[i]:
+                raise NotImplementedError(f"track {i}: in feedback mode an RBM generator takes whole given tracks only (no clamped chain in the feedback scan)")
 
     def generate(self, num_steps, given=None, given_mask=None):
         """multinn_feedback.py:120-173 -> u8 `[B, num_steps, P, M]`: one joint scan over the M generators and the feedback module.

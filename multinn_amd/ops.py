@@ -671,8 +671,10 @@ def rbm_workspace(D, Hn, device):
     return torch.empty(_lib.load().mnn_rbm_workspace_bytes(D, Hn), dtype=torch.uint8, device=device)
 
 
-def rbm_gibbs(v0, W, bh, bv, k, seed, row0=0, row_ids=None, sub0=0, p_v=None, v_out=None, seed_step=None):
-    """seed_step (int32 device scalar, optional): added to `seed` on the device (graph-replay safe step-dependent draws)."""
+def rbm_gibbs(v0, W, bh, bv, k, seed, row0=0, row_ids=None, sub0=0, p_v=None, v_out=None, seed_step=None, given=None):
+    """seed_step (int32 device scalar, optional): added to `seed` on the device (graph-replay safe step-dependent draws).
+    given (optional): codes u8 [N, D] (row stride >= D: a step slice given[:, s] of a [B, steps, D] block is read in place) -- 0 / 1 clamp
+    the visible to that value through the whole chain, 255 leaves it free (common.given_codes); not with seed_step (training's chain)."""
     N, D = v0.shape
     Hn = W.shape[1]
     _req(v0.dtype == torch.uint8 and v0.is_contiguous(), "gibbs: v0 u8 [N,D]")
@@ -684,6 +686,10 @@ def rbm_gibbs(v0, W, bh, bv, k, seed, row0=0, row_ids=None, sub0=0, p_v=None, v_
         _req(v_out.dtype == torch.uint8 and v_out.shape == (N, D) and v_out.is_contiguous(), "gibbs: v_out u8 [N,D]")
     if row_ids is not None:
         _req(row_ids.dtype == torch.int32 and row_ids.numel() == N, "gibbs: row_ids int32 [N]")
+    if given is not None:
+        _req(given.dtype == torch.uint8 and given.dim() == 2 and tuple(given.shape) == (N, D) and given.stride(1) == 1
+             and (given.stride(0) >= D or N == 1) and given.device == v0.device, "gibbs: given u8 [N, D], unit column stride, row stride >= D")
+        _req(seed_step is None, "gibbs: given with seed_step (the stepped chain is training's, unconditioned)")
     ws = rbm_workspace(D, Hn, v0.device)
     if seed_step is not None:
         _req(seed_step.dtype == torch.int32 and seed_step.numel() == 1, "gibbs: seed_step int32 [1]")
@@ -691,7 +697,7 @@ def rbm_gibbs(v0, W, bh, bv, k, seed, row0=0, row_ids=None, sub0=0, p_v=None, v_
              int(row0), _ptr(row_ids), int(sub0), _ptr(p_v), _ptr(v_out), _ptr(ws), _ptr(seed_step))
         return
     call("mnn_rbm_gibbs", _stream(), N, D, Hn, int(k), _ptr(v0), _ptr(W), _ptr(bh), _ldb(bh, Hn), _ptr(bv), _ldb(bv, D), int(seed), int(row0),
-         _ptr(row_ids), int(sub0), _ptr(p_v), _ptr(v_out), _ptr(ws))
+         _ptr(row_ids), int(sub0), _ptr(p_v), _ptr(v_out), _ptr(ws), _ptr(given), 0 if given is None else (given.stride(0) if N > 1 else D))
 
 
 def rbm_hidden(v, W, bh, stream_id, seed, row0, sub, p_h=None, h=None):
