@@ -43,9 +43,9 @@ enum { MNN_STREAM_DROPOUT = 0, MNN_STREAM_NADE = 1, MNN_STREAM_RBM_H = 2, MNN_ST
 
 /* ABI version of THIS header: bumped whenever a signature or a descriptor struct changes.  mnn_version() returns the value the library
  * was built with; a loader must compare the two before its first call (multinn_amd/_lib.py load() does) -- a library built for another
- * version reads garbage arguments without any diagnosis otherwise.  123: the clamped Gibbs chain -- mnn_rbm_gibbs gained a trailing `given`, `ld_given`.  122: conditional sampling -- a trailing `given` on mnn_nade_sample and mnn_generate_scan, mnn_nade_sample_job gained `given`.  121 (round 6): + mnn_gemm_tn_rows.  120 (round 6): mnn_step_increment gained `ls_dyn`, `ls_good`, `grow_after` (dynamic f16 loss scale).  119 (round 6): mnn_det_dense_job gained `Wp`, + mnn_det_dense_pack / _pack_bytes.  118 (round 6): mnn_det_lstm_job gained `Wp`, + mnn_det_lstm_pack / _pack_bytes, mnn_generate_scan_workspace_bytes gained `n_in`.  117 (round 6): + mnn_lstm_cluster_bwd_ok, + mnn_ragged_index / mnn_rows_gather16 / mnn_rows_scatter_f32, `n_rows_dev` on the gated NADE forwards and mnn_nade_logprob_bwd, `inv` / `hdr` on mnn_pianoroll_shift_timemajor_t, + mnn_lstm_resident_{fwd,bwd}_multi / mnn_lstm_cluster_{fwd,bwd}_multi / _bwd_multi_ok, `unsafe` on mnn_nade_logprob_fwd_gated, `unsafe` on mnn_nade_logprob_bwd.  116: + mnn_lstm_cluster_ok / _fwd / _bwd.  115: mnn_step_increment gained `sumsq`, `clip_norm`.  114: + mnn_lstm_resident_ok / _fwd / _bwd.  113: mnn_pianoroll_shift_timemajor_t gained `count`.  112: + mnn_generate_scan.  111: mnn_rbm_free_energy gained `p_h`.  110: mnn_clip_adam_step gained `skipped`; the dtype arguments of
+ * version reads garbage arguments without any diagnosis otherwise.  124: + mnn_rbm_ais / mnn_rbm_ais_workspace_bytes (AIS estimate of an RBM's log partition function).  123: the clamped Gibbs chain -- mnn_rbm_gibbs gained a trailing `given`, `ld_given`.  122: conditional sampling -- a trailing `given` on mnn_nade_sample and mnn_generate_scan, mnn_nade_sample_job gained `given`.  121 (round 6): + mnn_gemm_tn_rows.  120 (round 6): mnn_step_increment gained `ls_dyn`, `ls_good`, `grow_after` (dynamic f16 loss scale).  119 (round 6): mnn_det_dense_job gained `Wp`, + mnn_det_dense_pack / _pack_bytes.  118 (round 6): mnn_det_lstm_job gained `Wp`, + mnn_det_lstm_pack / _pack_bytes, mnn_generate_scan_workspace_bytes gained `n_in`.  117 (round 6): + mnn_lstm_cluster_bwd_ok, + mnn_ragged_index / mnn_rows_gather16 / mnn_rows_scatter_f32, `n_rows_dev` on the gated NADE forwards and mnn_nade_logprob_bwd, `inv` / `hdr` on mnn_pianoroll_shift_timemajor_t, + mnn_lstm_resident_{fwd,bwd}_multi / mnn_lstm_cluster_{fwd,bwd}_multi / _bwd_multi_ok, `unsafe` on mnn_nade_logprob_fwd_gated, `unsafe` on mnn_nade_logprob_bwd.  116: + mnn_lstm_cluster_ok / _fwd / _bwd.  115: mnn_step_increment gained `sumsq`, `clip_norm`.  114: + mnn_lstm_resident_ok / _fwd / _bwd.  113: mnn_pianoroll_shift_timemajor_t gained `count`.  112: + mnn_generate_scan.  111: mnn_rbm_free_energy gained `p_h`.  110: mnn_clip_adam_step gained `skipped`; the dtype arguments of
  * mnn_pianoroll_shift_timemajor_t / mnn_grad_rows_fanout and the `f16` descriptor fields of round 3 are part of it. */
-#define MNN_ABI_VERSION 123
+#define MNN_ABI_VERSION 124
 int mnn_version(void);
 const char* mnn_last_error(void);
 
@@ -432,6 +432,24 @@ int mnn_rbm_visible_bias_init(mnn_stream_t s, int D, const float* colsum, float 
  * ACCUMULATING weight-gradient products v_s^T pos + v^T neg.  v / v_s u8 [N,D]; sv / ss = sigmoid(bh + v W), sigmoid(bh + v_s W) f32 [N,Hn]. */
 int mnn_rbm_cd_rows(mnn_stream_t s, int N, int D, int Hn, int ld, const uint8_t* v, const uint8_t* v_s, const float* sv, const float* ss,
                     const float* row_weight, float scale, float* d_out, float* pos, float* neg);
+
+/* Annealed importance sampling of log Z per bias row (Neal 2001; Salakhutdinov & Murray 2008; DESIGN.md section 4 "AIS estimator").
+ * W f32 [D,Hn]; bh f32 [N or 1, Hn] (ld_bh = 0 broadcasts one row), bv likewise; betas f32 DEVICE [n_betas], 0 = b_0 <= ... <= b_{L-1} = 1
+ * (the ladder's values are checked by the caller: ops.rbm_ais).  S = n_chains independent chains per row through the whole ladder:
+ *   v ~ Bernoulli(sigmoid(bv)); for k = 1 .. L-1: log w += F_{b_{k-1}}(v) - F_{b_k}(v), F_b(v) = -bv.v - sum_j softplus(bh_j + b (vW)_j);
+ *   if k < L-1 one Gibbs transition at b_k (h ~ sigmoid(bh + b_k vW), v ~ sigmoid(bv + b_k hW^T)).
+ *   log_z[n] = log Z_0 + logsumexp_c(log w_c) - log S, log Z_0 = sum_d softplus(bv_d) + sum_j softplus(bh_j).  E[Z^] = Z, so log Z^ is
+ *   biased LOW (an NLL built from it is optimistic).
+ * Uniforms: Philox stream 6 (hidden phases) / 7 (base draw, visible phases), row = row_ids ? row_ids[n] : row0 + n, sub = c L + k (k = 0:
+ * the base draw), elem = j / d.  Pre-activations: ascending fmaf chain from 0, then fmaf(b, s, bias), det_sigmoid, u < p -- at b = 1 the
+ * transition of mnn_rbm_gibbs bit for bit.  Requires n_chains >= 1, n_betas >= 2, n_chains * n_betas < 2^32.
+ * Outputs: log_z f32 [N]; log_w f32 [N, S] (optional); v_out u8 [N, S, D] the chains' final states (optional); stats f32 [N, 2] (optional):
+ * the effective sample size (sum w)^2 / sum w^2 and the standard error of log_z (delta method on the mean of w).  workspace:
+ * mnn_rbm_ais_workspace_bytes.  A chain's log w depends on its own counters only (not on S, N, or the rows launched with it). */
+size_t mnn_rbm_ais_workspace_bytes(int N, int D, int Hn, int n_chains, int n_betas);
+int mnn_rbm_ais(mnn_stream_t s, int N, int D, int Hn, int n_chains, int n_betas, const float* betas, const float* W, const float* bh, int ld_bh,
+                const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, float* log_z, float* log_w, uint8_t* v_out,
+                float* stats, void* workspace);
 
 /* dz = dy * y * (1 - y) over n f32 words (dz may alias dy): backward of the sigmoid Dense layers of the feedback module (dnn.py:60-76). */
 int mnn_sigmoid_grad_f32(mnn_stream_t s, long n, const float* dy, const float* y, float* dz);

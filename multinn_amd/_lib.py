@@ -9,7 +9,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MULTINN_HIP_LIB", os.path.join(HERE, "libmultinn_hip.so"))   # override: A/B builds of the same ABI
 
-ABI_VERSION = 123          # == MNN_ABI_VERSION of include/multinn_hip.h; load() refuses a library built for another one
+ABI_VERSION = 124          # == MNN_ABI_VERSION of include/multinn_hip.h; load() refuses a library built for another one
 F32, BF16, U8, F16 = 0, 1, 2, 3
 GEMM_ACCUMULATE, GEMM_ATOMIC, GEMM_A_KBLOCK32 = 1, 2, 8
 
@@ -140,6 +140,8 @@ SIGNATURES["mnn_log_loss_rows"] = (_i, [_p, _p, _p, _i, _i, _i, _p])
 SIGNATURES["mnn_rbm_cd_bias_delta"] = (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _f, _p, _p])
 SIGNATURES["mnn_rbm_visible_bias_init"] = (_i, [_p, _i, _p, _f, _p])
 SIGNATURES["mnn_sigmoid_grad_f32"] = (_i, [_p, _l, _p, _p, _p])
+SIGNATURES["mnn_rbm_ais_workspace_bytes"] = (_sz, [_i, _i, _i, _i, _i])
+SIGNATURES["mnn_rbm_ais"] = (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _u64, _u32, _p, _p, _p, _p, _p, _p])
 SIGNATURES["mnn_rbm_cd_rows"] = (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p])
 SIGNATURES["mnn_probe_sigmoid"] = (_i, [_p, _i, _i, _p])
 SIGNATURES["mnn_axpby_f32"] = (_i, [_p, _l, _f, _p, _f, _p, _p])

@@ -497,6 +497,13 @@ class NADE(Model):
 
 
 # --------------------------------------------------------------------------------------------
+def ais_ladder(num_betas, device):
+    """The default AIS ladder: num_betas uniformly spaced values from 0 to 1 (f32; the end points exact).  Untuned: pass betas= to override."""
+    if num_betas < 2:
+        raise ValueError("the AIS ladder needs at least two values (0 and 1)")
+    return (torch.arange(num_betas, dtype=torch.float64) / (num_betas - 1)).to(torch.float32).to(device)
+
+
 class RBM(Model):
     """models/common/rbm.py."""
 
@@ -565,6 +572,17 @@ class RBM(Model):
         ops.rbm_gibbs(v.to(torch.uint8).contiguous(), self.W, bh, bv, k, self.seed if seed is None else seed, row0, row_ids, sub0, p_v, v_s,
                       given=given)
         return p_v, v_s
+
+    def log_partition(self, bh=None, bv=None, num_chains=64, num_betas=1000, betas=None, seed=None, row0=0, row_ids=None, stats=None):
+        """log Z of each bias row by annealed importance sampling (ops.rbm_ais; DESIGN.md section 4 "AIS estimator") -> log Z^ f32 [N].
+        bh / bv: [N or 1, Hn] / [N or 1, D] rows (default: this RBM's own biases).  betas: the ladder (0 = b_0 <= ... <= b_{L-1} = 1);
+        default ais_ladder(num_betas), uniform -- nobody has tuned or measured it.  Z^ is unbiased for Z, so log Z^ is biased LOW.
+        stats (optional f32 [N, 2]) receives (effective sample size, standard error of log Z^)."""
+        bh = bh if bh is not None else self.bh
+        bv = bv if bv is not None else self.bv
+        dev = self.W.device
+        betas = ais_ladder(num_betas, dev) if betas is None else torch.as_tensor(betas, dtype=torch.float32).to(dev).contiguous()
+        return ops.rbm_ais(self.W, bh, bv, betas, num_chains, self.seed if seed is None else seed, row0, row_ids, stats=stats)
 
     def free_energy(self, v, bh=None, bv=None):
         bh = bh if bh is not None else self.bh

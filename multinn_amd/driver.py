@@ -157,9 +157,14 @@ def _captured_step(generator, xb, optimizer, lr, max_graphs=8, lengths=None):
     return graphs[key]
 
 
-def evaluate(generator, X, lengths, batch_size, piece_size, device=None):
-    """utils/training.py:180-213 collect_metrics: mean generator NLL per valid row over all windows."""
+def evaluate(generator, X, lengths, batch_size, piece_size, device=None, nll="loss", ais=None):
+    """utils/training.py:180-213 collect_metrics: mean generator NLL per valid row over all windows.
+    nll="loss" (default): the training loss (an RBM generator's is the CD cost, a difference of free energies, not a likelihood).
+    nll="ais": the model's estimate_nll(x, lengths, **ais) -- exact for NADE generators, annealed importance sampling for RBM generators
+    (biased low), summed over a mode's generators."""
     import torch
+    if nll not in ("loss", "ais"):
+        raise ValueError(f"nll must be 'loss' or 'ais', got {nll!r}")
     tot, cnt = 0.0, 0
     ids = np.arange(X.shape[0])
     for w in iter_windows(ids, lengths, X.shape[1], batch_size, piece_size):
@@ -168,6 +173,11 @@ def evaluate(generator, X, lengths, batch_size, piece_size, device=None):
         song_ids, j, max_len, len_batch = w
         xb = torch.from_numpy(np.ascontiguousarray(X[song_ids, j:j + max_len])).to(device or "cuda")
         full = bool((len_batch == max_len).all())
+        if nll == "ais":
+            n = int(len_batch.sum())
+            tot += generator.estimate_nll(xb, None if full else torch.from_numpy(len_batch).to(xb.device), **(ais or {})).mean * n
+            cnt += n
+            continue
         generator.build_pianoroll(xb, None if full else torch.from_numpy(len_batch).to(xb.device), is_train=False, mode="eval")
         n = int(len_batch.sum())
         loss = generator.generator_loss() if hasattr(generator, "generator_loss") else generator.metrics["batch/loss"]

@@ -21,6 +21,7 @@ import torch
 from . import ops
 from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, glorot_uniform, zeros_init, default_device, capture_train_step
 from .training import compute_gradients, world, dp_active, AdamOptimizer
+from ._lib import MnnUnsupported
 
 _RnnEstimatorStateTuple = collections.namedtuple("RnnEstimatorStateTuple", ("b_enc", "b_dec", "rnn_state"))
 
@@ -54,6 +55,52 @@ def flat_index(lengths, B, T, device):
         return (t * B + b).reshape(-1)
     m = t < lengths.to(device)[:, None]
     return (t * B + b)[m]
+
+
+class NllEstimate:
+    """Negative log-likelihood of a built batch, per valid row in API order (b-major, then t; like RnnRBM.cost).
+    nll [n] f32; log_z / free_energy [n] (AIS estimators; None where the NLL is exact); mean: mean NLL per valid row; stderr: standard error
+    of `mean` (0 when exact; AIS: sqrt(sum of the rows' squared standard errors) / n, the rows' chains being independent); ess: the smallest
+    effective sample size over the rows (inf when exact).  An AIS estimate is biased LOW (E[Z^] = Z, so E[log Z^] <= log Z): optimistic."""
+
+    def __init__(self, nll, log_z=None, free_energy=None, row_stderr=None, row_ess=None):
+        self.nll, self.log_z, self.free_energy = nll, log_z, free_energy
+        self.row_stderr, self.row_ess = row_stderr, row_ess
+        n = max(int(nll.numel()), 1)
+        self.mean = float(nll.double().sum()) / n
+        self.stderr = 0.0 if row_stderr is None else float(row_stderr.double().pow(2).sum().sqrt()) / n
+        self.ess = math.inf if row_ess is None or row_ess.numel() == 0 else float(row_ess.min())
+
+    @staticmethod
+    def total(parts):
+        """The joint NLL of several models of the same rows (a mode's generators): row NLLs, log Z^ and free energies add, squared standard
+        errors add, the smallest ESS is kept."""
+        if len(parts) == 1:
+            return parts[0]
+        nll = sum(p.nll for p in parts)
+        ai = [p for p in parts if p.log_z is not None]
+        log_z = sum(p.log_z for p in ai) if ai else None
+        fe = sum(p.free_energy for p in ai) if ai else None
+        se = torch.stack([p.row_stderr for p in ai]).pow(2).sum(0).sqrt() if ai else None
+        ess = torch.stack([p.row_ess for p in ai]).min(0).values if ai else None
+        return NllEstimate(nll, log_z, fe, se, ess)
+
+
+def refuse_host_model(device, what):
+    """MnnUnsupported (an MnnError and a NotImplementedError) for a model that does not live on a ROCm device: raised before any device work."""
+    if device is not None and torch.device(device).type != "cuda":
+        raise MnnUnsupported(f"{what} runs in HIP kernels: this model lives on {device}, not a ROCm device")
+
+
+def shifted_sequences(x):
+    """x [B, T, F] (or [B, T, P, M]: feature p * M + m) -> (inputs, targets): one all-zero step in front, inputs = x[:, :-1] (multinn_joint.py:83-89)."""
+    if x.dim() == 4:
+        x = x.reshape(x.shape[0], x.shape[1], -1)
+    if x.dim() != 3:
+        raise ValueError(f"x must be [B, T, F] or [B, T, P, M], got {tuple(x.shape)}")
+    x = x if x.dtype == torch.uint8 else (x != 0).to(torch.uint8)
+    inputs = torch.cat([torch.zeros_like(x[:, :1]), x[:, :-1]], 1)
+    return inputs.contiguous(), x.contiguous()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -945,6 +992,16 @@ class RnnEstimator(Generator):
             self._grad_sumsq = compute_gradients(optimizer, self.store, self.clip_norm, lr, reduce=False)
         return capture_train_step(feed, step, warmup, [self], lambda: [self.store], split=dp_active(), fwd_bwd=fwd_bwd, opt=opt, **kw)
 
+    def estimate_nll(self, x, lengths=None, num_chains=64, num_betas=1000, betas=None, seed=None):
+        """NLL of every step of x [B, T, F] (or [B, T, P, M]) given the steps before it: builds in eval mode (keep_prob 1) on inputs = x
+        shifted by one all-zero step, targets = x, and returns an NllEstimate over the valid rows.  RnnNade: exact (the AIS arguments are
+        ignored).  RnnRBM: AIS (see RnnRBM._nll_rows_built)."""
+        refuse_host_model(self.store.device, "estimate_nll")
+        dev = self.store.device if self.store.device is not None else default_device()
+        inputs, targets = shifted_sequences(x.to(dev))
+        self.build(inputs, targets, lengths, is_train=False, mode="eval")
+        return self._nll_rows_built(num_chains=num_chains, num_betas=num_betas, betas=betas, seed=seed)
+
     def _step_input(self, B, device):
         """[B, ld0] staging row block of single_step: the zero padding beyond the input width is written once, every step converts its
         input into the prefix (the step's GEMM has read the previous contents by then: same stream)."""
@@ -1308,6 +1365,11 @@ class RnnNade(RnnEstimator):
     def log_probs(self):
         r = [self._nll_tm[m][self._idx()] for m in range(self.num_tracks)]
         return r[0] if self.num_tracks == 1 else r
+
+    def _nll_rows_built(self, **ais):
+        """The exact NLL rows of the last build (API order, valid rows), summed over the NADE tracks: an NllEstimate with stderr 0."""
+        idx = self._idx()
+        return NllEstimate(sum(self._nll_tm[m][idx] for m in range(self.num_tracks)))
 
     @property
     def cond_probs(self):
@@ -1677,6 +1739,30 @@ class RnnRBM(RnnEstimator):
 
     def build_metrics(self, targets, predictions, cond_probs=None, log_probs=None):
         return self._rbm.build_metrics(targets, predictions, cond_probs, log_probs)
+
+    def _nll_rows_built(self, num_chains=64, num_betas=1000, betas=None, seed=None):
+        """AIS NLL of the last build's valid rows (API order):  -log p(v_t | v_<t) = F_t(v_t) + log Z_t with the row's CONDITIONAL biases
+        bh_t, bv_t (the distribution sample() draws from, whatever bias_mode trained) and log Z_t estimated by RBM.log_partition -- the
+        chains keyed by the global row ids of build (t * 65536 + row0 + b), seed default self.seed.  Biased low: see NllEstimate."""
+        cx = self._ctx
+        B, T = cx["B"], cx["T"]
+        D, Hn = self.num_dims, self.num_hidden[-1]
+        out, dev = cx["out"], cx["out"].device
+        idx = self._idx()
+        rows = (torch.arange(T, device=dev)[:, None] * 65536 + (self.row0 + torch.arange(B, device=dev))[None, :]).reshape(-1)
+        bh = out[:, :Hn][idx].contiguous()
+        bv = out[:, Hn:Hn + D][idx].contiguous()
+        n = bh.shape[0]
+        if n == 0:
+            e = torch.zeros(0, device=dev)
+            return NllEstimate(e, e, e, e, e)
+        stats = torch.empty((n, 2), device=dev)
+        log_z = self._rbm.log_partition(bh, bv, num_chains, num_betas, betas, self.seed if seed is None else seed,
+                                        row_ids=rows[idx].to(torch.int32).contiguous(), stats=stats)
+        F = torch.empty(n, device=dev)
+        ops.rbm_free_energy(cx["tgt"][idx].contiguous(), self._rbm.W, bh, bv, F)
+        return NllEstimate(F + log_z, log_z, F, stats[:, 1], stats[:, 0])
+
 
     def backward(self):
         return drive(self._backward_co())
