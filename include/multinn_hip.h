@@ -236,7 +236,7 @@ int mnn_lstm2_persist_bwd(mnn_stream_t s, int T, int B, const mnn_lstm_bwd_layer
  * mnn_gemm_tn with a bf16 C) [T,B,4u] including the bias (mnn_lstm_rows_gate_minor); L->gates points at BF16 [T,B,4u]
  * (gate-minor; half the bytes of the other forms' f32 copy: the saved activations only feed products that are rounded to bf16 anyway, and
  * only mnn_lstm_rowpar_bwd reads them); with a keep mask (L->mask, L->y) the layer's output is y and L->h receives ONLY its last timestep
- * (the final state) -- the rows of h[0 .. T-2] are left untouched; L->wx_t / bias_p unused, no initial state (h0 = c0 = NULL: a window starts from the zero state, train.py:165-173); backward -- L->dh_ext f32 [T,B,u]
+ * (the final state) -- the rows of h[0 .. T-2] are left untouched; L->wx_t / bias_p unused, no initial state in the row-parallel form itself (h0 = c0 = NULL; the resident and cluster forms below take one); backward -- L->dh_ext f32 [T,B,u]
  * required (the gradient wrt the layer's output; with L->mask it is taken wrt the DROPPED output and dh_ext / keep_prob * mask is applied
  * here), L->dz_T (optional) receives dz bf16 [T,B,4u] row-major in the gate-interleaved column order (the A operand of the input-gradient
  * GEMM against wx_p), L->dzT_t / db_p as in the persistent form, L->workspace / wx_p / dz unused.  B must be a multiple of 32.
@@ -253,18 +253,28 @@ int mnn_lstm_rowpar_bwd(mnn_stream_t s, int T, int B, const mnn_lstm_bwd_layer* 
  * one quarter in LDS), so a timestep hands nothing between workgroups -- no flags, no exchange area, no workspace, no co-residency
  * requirement (any grid size runs).  Same layer descriptors, inputs, outputs and layouts as mnn_lstm_rowpar_fwd (16-bit gate-minor xproj
  * REQUIRED: L->xproj_bf16 != 0; the saved gates, hT and yT come together or not at all); units must be 256 and B a multiple of 4
- * (mnn_lstm_resident_ok); every tensor of the call below 2 GB (buffer descriptors). */
+ * (mnn_lstm_resident_ok); every tensor of the call below 2 GB (buffer descriptors).
+ * Initial state (optional): L->h0 (the layer's 16-bit type, [B, u]) and L->c0 (f32 [B, u]), both given or both NULL (the zero state).  With them
+ * step 0 multiplies h0 and the cell state starts at c0; columns [0, B) of hT stay the caller's (h0^T, as for mnn_lstm_seq_fwd).  All-zero arrays
+ * give the bits of the NULL launch. */
 int mnn_lstm_resident_ok(int B, int units);
 int mnn_lstm_resident_fwd(mnn_stream_t s, int T, int B, const mnn_lstm_fwd_layer* L, float keep_prob);
 /* ... and its backward: descriptor, outputs and layouts of mnn_lstm_rowpar_bwd (dh_ext required; dz_T, dzT_t / ld_t (0 = K-blocked), db_p optional;
  * workspace / wx_p / dz unused).  The saved gates must be the 16-bit gate-minor copy written by mnn_lstm_resident_fwd / mnn_lstm_rowpar_fwd. */
 int mnn_lstm_resident_bwd(mnn_stream_t s, int T, int B, const mnn_lstm_bwd_layer* L, float keep_prob);
+/* ... with an initial state: L->c0 (f32 [B, u], optional; accepted by every resident / cluster backward entry) is c[-1] of step 0's gate backward.
+ * The _state entries launch the same kernels and add ONE output beside the descriptor: dc0 f32 [B, u] (NULL allowed) receives the gradient wrt
+ * c0, d_c[0] . f[0]; mnn_lstm_resident_bwd is the call with dc0 = NULL.  The gradient wrt h0 is NOT formed here: it is dz[0] . Wh^T, one
+ * [B, 4u] x [4u, u] product (mnn_gemm_tn) over the 16-bit dz[0] this launch has written into L->dz_T. */
+int mnn_lstm_resident_bwd_state(mnn_stream_t s, int T, int B, const mnn_lstm_bwd_layer* L, float keep_prob, float* dc0);
 /* Cluster form of the CU-resident recurrence for ONE 512-unit layer (multinn_amd/csrc/lstm_cluster.hip; rnn.py:104-145 as above): eight
  * workgroups -- one per CU, on one XCD -- share 32 batch rows for the whole sequence; each keeps the recurrent weights of 64 units in its waves'
  * registers and the members exchange h[t] (backward: dz[t]) through a two-deep area in their XCD's L2 (progress flags, bounded spins, the sticky
  * status word of mnn_lstm_rowpar_status).  Same layer descriptors, inputs, outputs, layouts AND workspace as mnn_lstm_rowpar_fwd / _bwd with a
  * 16-bit gate-minor xproj (the caller may use either form on the same buffers).  units == 512, B a multiple of 256 with B / 4 <= the device's
  * CUs (mnn_lstm_cluster_ok; the whole grid must be resident at once: never next to another persistent launch); every tensor below 2 GB. */
+/* Initial state (optional): L->h0 / L->c0 as for mnn_lstm_resident_fwd -- every member reads the cluster's 32 rows of h0 itself before the loop
+ * (nothing is exchanged for step 0; the protocol of the steps >= 1 is unchanged). */
 int mnn_lstm_cluster_ok(int B, int units);
 int mnn_lstm_cluster_fwd(mnn_stream_t s, int T, int B, const mnn_lstm_fwd_layer* L, float keep_prob, void* workspace);
 /* ... and its backward: descriptor, outputs and layouts of mnn_lstm_rowpar_bwd (dh_ext required; dz_T, dzT_t / ld_t (0 = K-blocked), db_p optional;
@@ -276,6 +286,8 @@ int mnn_lstm_cluster_fwd(mnn_stream_t s, int T, int B, const mnn_lstm_fwd_layer*
  * that nevertheless finds a cluster off one XCD gives up (status word) instead of computing on stale lines. */
 int mnn_lstm_cluster_bwd_ok(int B, int units);
 int mnn_lstm_cluster_bwd(mnn_stream_t s, int T, int B, const mnn_lstm_bwd_layer* L, float keep_prob, void* workspace);
+/* ... with an initial state: L->c0 and the extra output dc0 exactly as for mnn_lstm_resident_bwd_state (dh0 likewise formed by the caller). */
+int mnn_lstm_cluster_bwd_state(mnn_stream_t s, int T, int B, const mnn_lstm_bwd_layer* L, float keep_prob, void* workspace, float* dc0);
 /* Several INDEPENDENT layers of one shape in one launch: the M per-track generators of the jamming mode (multinn_jamming.py:40-68,213-221 trains
  * them on one loss; each has its own LSTM).  L: array of njobs (1..8) descriptors sharing T, B, units, keep_prob, precision, dropout and save
  * mode; every job keeps its own tensors and -- cluster form -- its own workspace.  The CU-resident and cluster recurrences own row groups for
@@ -287,6 +299,11 @@ int mnn_lstm_resident_bwd_multi(mnn_stream_t s, int T, int B, int njobs, const m
 int mnn_lstm_cluster_fwd_multi(mnn_stream_t s, int T, int B, int njobs, const mnn_lstm_fwd_layer* L, float keep_prob, void* const* workspaces);
 int mnn_lstm_cluster_bwd_multi(mnn_stream_t s, int T, int B, int njobs, const mnn_lstm_bwd_layer* L, float keep_prob, void* const* workspaces);
 int mnn_lstm_cluster_bwd_multi_ok(int B, int units, int njobs);
+/* Every job carries its own initial state in its descriptor (jobs with and without one may share a launch: the test is per workgroup).  The
+ * _state_multi entries take dc0 as an array of njobs pointers (the array or any entry may be NULL); the _multi entries above are dc0 = NULL. */
+int mnn_lstm_resident_bwd_state_multi(mnn_stream_t s, int T, int B, int njobs, const mnn_lstm_bwd_layer* L, float keep_prob, float* const* dc0);
+int mnn_lstm_cluster_bwd_state_multi(mnn_stream_t s, int T, int B, int njobs, const mnn_lstm_bwd_layer* L, float keep_prob, void* const* workspaces,
+                                     float* const* dc0);
 int mnn_dropout_mask(mnn_stream_t s, uint8_t* mask, int T, int B, int units, float keep_prob, uint64_t seed, const int32_t* step_dev,
                      uint32_t row0, int layer);
 
@@ -562,6 +579,13 @@ int mnn_generate_scan(mnn_stream_t s, int B, int n_intro, int num_steps, const u
                       const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D, int Hn,
                       const float* w_enc, const float* w_dec, float temperature, uint64_t seed, uint32_t row0, uint8_t* samples,
                       void* workspace, size_t workspace_bytes, const uint8_t* given);
+/* ... started from an initial state (a learned one: rnn.py:139-143, 166-172): c0 / h0 are arrays of n_layers device pointers, each f32 [B, u] of
+ * that layer (both NULL: mnn_generate_scan).  They are INPUTS of the scan -- the host layer tiles c0 and tanh(c0) over the batch once, on the
+ * device -- handed to the intro pass's first step as c_prev / h_prev; everything else, bits included, is mnn_generate_scan. */
+int mnn_generate_scan_state(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                            const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D, int Hn,
+                            const float* w_enc, const float* w_dec, float temperature, uint64_t seed, uint32_t row0, uint8_t* samples,
+                            void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0, const float* const* h0);
 
 /* ------------------------------------------------------------------------------------------
  * Data-parallel exchange (the gradients of utils/training.py:151-177 as ONE flat f32 buffer): RCCL over xGMI, one

@@ -64,6 +64,8 @@ SIGNATURES = {
     "mnn_det_dense_pack_bytes": (_sz, [_i, _i]),
     "mnn_det_dense_pack": (_i, [_p, _p, _i, _i, _i, _p]),
     "mnn_generate_scan": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _f, _u64, _u32, _p, _p, _sz, _p]),
+    "mnn_generate_scan_state": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _f, _u64, _u32, _p, _p, _sz, _p,
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "mnn_comm_unique_id": (_i, [_p]),
     "mnn_comm_init": (_i, [C.POINTER(_p), _i, _i, _p]),
     "mnn_allreduce_flat": (_i, [_p, _p, _p, _l]),
@@ -126,6 +128,10 @@ SIGNATURES["mnn_lstm_cluster_fwd_multi"] = (_i, [_p, _i, _i, _i, C.POINTER(LstmF
 SIGNATURES["mnn_lstm_cluster_bwd_multi"] = (_i, [_p, _i, _i, _i, C.POINTER(LstmBwdLayer), _f, C.POINTER(C.c_void_p)])
 SIGNATURES["mnn_lstm_cluster_fwd"] = (_i, [_p, _i, _i, C.POINTER(LstmFwdLayer), _f, _p])
 SIGNATURES["mnn_lstm_cluster_bwd"] = (_i, [_p, _i, _i, C.POINTER(LstmBwdLayer), _f, _p])
+SIGNATURES["mnn_lstm_resident_bwd_state"] = (_i, [_p, _i, _i, C.POINTER(LstmBwdLayer), _f, _p])
+SIGNATURES["mnn_lstm_cluster_bwd_state"] = (_i, [_p, _i, _i, C.POINTER(LstmBwdLayer), _f, _p, _p])
+SIGNATURES["mnn_lstm_resident_bwd_state_multi"] = (_i, [_p, _i, _i, _i, C.POINTER(LstmBwdLayer), _f, C.POINTER(C.c_void_p)])
+SIGNATURES["mnn_lstm_cluster_bwd_state_multi"] = (_i, [_p, _i, _i, _i, C.POINTER(LstmBwdLayer), _f, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)])
 SIGNATURES["mnn_nade_mfma_ok"] = (_i, [_i])
 SIGNATURES["mnn_nade_logprob_fwd_mfma"] = (_i, [_p, _i, _i, _i, _i, _p, _l, _p, _i, _p, _p, _p, _p, _p, _p, _p])
 SIGNATURES["mnn_density_gate"] = (_i, [_p, _p, _l, _l, _p, _p])

@@ -382,27 +382,35 @@ class RNN(Model):
         super().__init__(name=name)
         if isinstance(num_units, int):
             num_units = [num_units]
-        if attn_length or learn_zero_state:
-            raise NotImplementedError("attn_length / learn_zero_state are not on the hot path (rnn.py:127-145)")
+        if attn_length:
+            raise NotImplementedError("attn_length (the AttentionCellWrapper of rnn.py:127-129) is not built: no caller of the reference sets it")
         for u in num_units:
             if u % 32:
                 raise ValueError("LSTM units must be a multiple of 32 (gate-interleaved MFMA layout)")
         self._num_units = list(num_units)
         self._keep_prob = keep_prob
+        self._learn_zero_state = bool(learn_zero_state)
+        self._tanh_c0 = {}
         self._is_train = False
 
+    learn_zero_state = property(lambda self: self._learn_zero_state)
     num_units = property(lambda self: self._num_units)
     num_layers = property(lambda self: len(self._num_units))
     keep_prob = property(lambda self: self._keep_prob)
 
     def declare(self, store, n_in, gen, prefix="rnn"):
-        """Kernel [in+u, 4u] glorot-uniform, bias zeros (LSTMBlockCell defaults)."""
+        """Kernel [in+u, 4u] glorot-uniform, bias zeros (LSTMBlockCell defaults).  learn_zero_state: per layer a trainable c0 [1, u],
+        zeros, behind ALL cell kernels / biases (rnn.py:139-143, 214-217) -- zeros_init draws nothing, so every other weight is the one a
+        model without the flag gets from the same seed."""
         self.n_in = n_in
         self.prefix = prefix
         for l, u in enumerate(self._num_units):
             store.declare(f"{prefix}/cell_{l}/kernel", (n_in + u, 4 * u), glorot_uniform(gen, n_in + u, 4 * u))
             store.declare(f"{prefix}/cell_{l}/bias", (4 * u,), zeros_init)
             n_in = u
+        if self._learn_zero_state:
+            for l, u in enumerate(self._num_units):
+                store.declare(f"{prefix}/cell_{l}/c0", (1, u), zeros_init)
         self.store = store
 
     def layer_inputs(self):
@@ -419,10 +427,35 @@ class RNN(Model):
         return [], [], None
 
     def zero_state(self, batch_size, dtype=torch.float32):
-        """rnn.py:155-176: tuple of (c, h) per layer."""
+        """rnn.py:155-176: tuple of (c, h) per layer.  learn_zero_state: (c0, tanh(c0)) tiled over the batch, computed on the device from the
+        CURRENT value of the variables (no host read: a captured step follows c0 as the optimiser moves it)."""
         dev = self.store.theta.device
+        if self._learn_zero_state:
+            out = []
+            for l, u in enumerate(self._num_units):
+                c0 = self.store[f"{self.prefix}/cell_{l}/c0"]
+                th = torch.tanh(c0)
+                self._tanh_c0[l] = th                   # kept for zero_state_grad of the same step (the tanh' factor)
+                out.append((c0.expand(batch_size, u).contiguous(), th.to(dtype).expand(batch_size, u).contiguous()))
+            return tuple(out)
         return tuple((torch.zeros((batch_size, u), device=dev), torch.zeros((batch_size, u), device=dev, dtype=dtype))
                      for u in self._num_units)
+
+    def zero_state_grad(self, dstate):
+        """Chain rule of zero_state: dstate [(dc0, dh0) f32 [B, u]] per layer (LstmStack.backward(need_dstate=True)) ->
+        g(c0_l) += sum_b dc0_l[b] + (1 - tanh(c0_l)^2) * sum_b dh0_l[b], added into the store's gradient view (every row of a window is valid
+        at t = 0; loss scale, grad_scale and row weights are already in dstate)."""
+        for l, ds in enumerate(dstate):
+            if ds is None:                              # (a layer that ran without a state: LstmStack.backward)
+                continue
+            dc0, dh0 = ds
+            g = self.store.gviews[f"{self.prefix}/cell_{l}/c0"].view(-1)
+            ops.bias_grad(dc0, g, accumulate=True)
+            sh = torch.empty_like(g)
+            ops.bias_grad(dh0, sh)
+            th = self._tanh_c0.pop(l, None)             # tanh(c0) of this step's zero_state
+            th = torch.tanh(self.store[f"{self.prefix}/cell_{l}/c0"]).view(-1) if th is None else th.view(-1)
+            g.addcmul_(sh, 1.0 - th * th)
 
     def __call__(self, inputs, state, *args, **kwargs):
         if not self._is_built:

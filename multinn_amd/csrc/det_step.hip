@@ -428,10 +428,13 @@ extern "C" size_t mnn_generate_scan_workspace_bytes(int B, int n_in, int n_layer
     return bytes;
 }
 
-extern "C" int mnn_generate_scan(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
-                                 const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
-                                 int Hn, const float* w_enc, const float* w_dec, float temperature, uint64_t seed, uint32_t row0,
-                                 uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given) {
+// c0 / h0 (mnn_generate_scan_state; both NULL: the zero state): per layer an f32 [B, u] array, the state the intro pass starts from -- inputs of
+// the scan (the host layer tiles a learned c0 and tanh(c0) once, on the device), handed to the first step's jobs as h_prev / c_prev.
+static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                              const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
+                              int Hn, const float* w_enc, const float* w_dec, float temperature, uint64_t seed, uint32_t row0,
+                              uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0,
+                              const float* const* h0) {
     MNN_REQUIRE(B > 0 && n_intro > 0 && num_steps >= 0 && intro && n_in > 0 && n_layers > 0 && n_layers <= MNN_SCAN_MAX_LAYERS && layers,
                 "mnn_generate_scan: B, n_intro > 0, 1..%d layers", MNN_SCAN_MAX_LAYERS);
     MNN_REQUIRE(dense_W && tracks > 0 && D > 0 && Hn > 0 && n_out == tracks * (Hn + D) && n_in == tracks * D && w_enc && w_dec && samples,
@@ -477,8 +480,8 @@ extern "C" int mnn_generate_scan(mnn_stream_t s, int B, int n_intro, int num_ste
             const int u = layers[l].units;
             if (l == 0) { jb.x = x; jb.x_dtype = MNN_U8; jb.n_x = n_in; jb.ld_x = ld_x; jb.es_x = 1; }
             else { jb.x = hbuf[l - 1][nxt]; jb.x_dtype = MNN_F32; jb.n_x = layers[l - 1].units; jb.ld_x = layers[l - 1].units; jb.es_x = 1; }
-            jb.h_prev = have_state ? hbuf[l][cur] : nullptr;
-            jb.c_prev = have_state ? cbuf[l][cur] : nullptr;
+            jb.h_prev = have_state ? hbuf[l][cur] : (h0 ? h0[l] : nullptr);
+            jb.c_prev = have_state ? cbuf[l][cur] : (c0 ? c0[l] : nullptr);
             jb.W = layers[l].W; jb.Wp = wpack[l]; jb.bias = layers[l].bias; jb.c_out = cbuf[l][nxt]; jb.h_out = hbuf[l][nxt]; jb.units = u;
             const int rc = mnn_lstm_step_det(s, B, 1, &jb);
             if (rc != MNN_OK) return rc;
@@ -513,4 +516,25 @@ extern "C" int mnn_generate_scan(mnn_stream_t s, int B, int n_intro, int num_ste
         if (rc != MNN_OK) return rc;
     }
     return MNN_OK;
+}
+
+extern "C" int mnn_generate_scan(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                 const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
+                                 int Hn, const float* w_enc, const float* w_dec, float temperature, uint64_t seed, uint32_t row0,
+                                 uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given) {
+    return generate_scan_impl(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc, w_dec, temperature,
+                              seed, row0, samples, workspace, workspace_bytes, given, nullptr, nullptr);
+}
+extern "C" int mnn_generate_scan_state(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                       const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
+                                       int Hn, const float* w_enc, const float* w_dec, float temperature, uint64_t seed, uint32_t row0,
+                                       uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0,
+                                       const float* const* h0) {
+    MNN_REQUIRE((c0 == nullptr) == (h0 == nullptr), "mnn_generate_scan_state: c0 and h0 come together (arrays of n_layers pointers) or not at all");
+    if (c0 != nullptr) {
+        MNN_REQUIRE(n_layers > 0 && n_layers <= MNN_SCAN_MAX_LAYERS, "mnn_generate_scan_state: 1..%d layers", MNN_SCAN_MAX_LAYERS);
+        for (int l = 0; l < n_layers; ++l) MNN_REQUIRE(c0[l] && h0[l], "mnn_generate_scan_state: layer %d has no initial state", l);
+    }
+    return generate_scan_impl(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc, w_dec, temperature,
+                              seed, row0, samples, workspace, workspace_bytes, given, c0, h0);
 }

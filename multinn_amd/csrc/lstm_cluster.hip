@@ -109,6 +109,7 @@ __device__ __forceinline__ void cl_dma4(const void* g, const void* l) {
 struct ClFwdArgs {
     const h16_t* xproj; const h16_t* wh_t; h16_t* gates; float* c; h16_t* h; h16_t* y; const uint8_t* mask;
     h16_t* hT; int ld_hT; h16_t* yT; int ld_yT;
+    const h16_t* h0; const float* c0;      // initial state [B, u] (both or neither; NULL: the zero state)
     char* xchg; unsigned* sync;
     int T, B, ncl, allow_local; float kp;
 };
@@ -180,7 +181,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 #pragma unroll
             for (int s = 0; s < 32; ++s) asm volatile("" : "+a"(wr[j][s]));
     }
-    for (int i = tid; i < G::HB / 4; i += 256) reinterpret_cast<unsigned*>(smem + G::OFF_H)[i] = 0u;       // h[-1] = 0 (state buffer 0)
+    // h[-1] in state buffer 0: the zero state, or the cluster's 32 rows of the caller's h0 -- an INPUT, so every member reads it itself: nothing
+    // is exchanged for step 0, no flag, and the protocol of the steps >= 1 does not move.  (A uniform pointer test outside the time loop.)
+    if (A.h0 != nullptr) {
+        const unsigned* h0w = reinterpret_cast<const unsigned*>(A.h0 + (size_t)row0 * U);
+        for (int i = tid; i < G::HB / 4; i += 256) {
+            const int r = i / (G::PH / 4), cw = i - r * (G::PH / 4);
+            reinterpret_cast<unsigned*>(smem + G::OFF_H)[i] = cw < U / 2 ? h0w[r * (U / 2) + cw] : 0u;
+        }
+    } else {
+        for (int i = tid; i < G::HB / 4; i += 256) reinterpret_cast<unsigned*>(smem + G::OFF_H)[i] = 0u;
+    }
 
     // ---- staging of a step's xproj rows (32 x 512 bytes) and keep bytes (32 x 64) a step ahead: wave w moves row pairs 4w..4w+3 / rows 8w..8w+7 ----
     const char* xsrc = reinterpret_cast<const char*>(A.xproj) + ((size_t)(row0 + hf) * U + 64 * mem) * 8 + (lane & 31) * 16;
@@ -228,6 +239,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     float creg[8];
 #pragma unroll
     for (int p = 0; p < 8; ++p) creg[p] = 0.f;
+    if (A.c0 != nullptr) {                          // c[-1] of this lane's (row, unit) pairs (the ownership of `pointwise`: p = 4 j + q)
+#pragma unroll
+        for (int p = 0; p < 8; ++p) creg[p] = A.c0[(size_t)(row0 + row) * U + ub + 8 * (p >> 2) + 2 * (p & 3) + hf];
+        // consumed HERE: the loads are waited for in the prologue, not by a wait the compiler would put in front of the first pointwise of
+        // every step (where it would also wait for the step's staging requests)
+#pragma unroll
+        for (int p = 0; p < 8; ++p) asm volatile("" : "+v"(creg[p]));
+    }
     constexpr int PFB = 4;                          // state fragments requested ahead of their MFMAs
     CL_TR_DECL;
     for (int t = 0; t < T; ++t) {
@@ -371,6 +390,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 struct ClBwdArgs {
     const float* dh_ext; const h16_t* wh_p; const h16_t* gates; const float* c; const uint8_t* mask;
     h16_t* dzc; h16_t* dzT; int ld_t; float* db_p;
+    const float* c0; float* dc0;           // initial cell state [B, u] (NULL: zero) and its gradient d_c[0] . f[0] (NULL: not wanted)
     char* xchg; unsigned* sync;
     int T, B, ncl, allow_local; float kp;
 };
@@ -550,7 +570,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
                 const float dv = __uint_as_float(dq[a][r]);
                 pe[a][r] = DROP ? dv * ikp * (float)((mq[a] >> (8 * r)) & 0xffu) : dv;
                 const float tc = fast_tanh(cnext[a][r]);
-                const float cprev = t > 0 ? __uint_as_float(cq[a][r]) : 0.f;
+                const float cprev = t > 0 ? __uint_as_float(cq[a][r]) : 0.f;    // (step 0 with an initial cell state: completed behind the loop)
                 pA[a][r] = go * (1.f - tc * tc);
                 pK[a][0][r] = gg * gi * (1.f - gi);
                 pK[a][1][r] = gi * (1.f - gg * gg);
@@ -628,6 +648,46 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         CL_BARRIER();
         CL_TR(6);
         CL_TR_FLUSH(1, kk);
+    }
+    // gradient wrt the initial cell state: d_c[0] . f[0], what the loop left in dcreg.  (Stored HERE, directly behind the loop, and through a
+    // buffer resource: placed behind the epilogue below, the fp16 instantiations' loop lost its one-by-one waits for the eight partial-sum
+    // loads (vmcnt 15 .. 8 became 15, 14, 13, 9, 8) and the launch 1.5 % -- the order of these two blocks is measured, not taste.)
+    if (A.dc0 != nullptr) {
+        const __amdgpu_buffer_rsrc_t rs_d0 = __builtin_amdgcn_make_buffer_rsrc((void*)A.dc0, 0, (int)min(us * 4, (size_t)0x7fffffff), 0x00020000);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            u32x4_t v;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = __float_as_uint(dcreg[a][r]);
+            __builtin_amdgcn_raw_buffer_store_b128(v, rs_d0, (vo_e + 8 * a) * 4, (unsigned)((size_t)row0 * U) * 4, 0);
+        }
+    }
+    // ---- initial cell state: the loop is the loop of a launch without one (it took c[-1] = 0).  c[-1] enters step 0 in ONE place, the forget
+    // gate's dz = d_c . c[-1] . f (1 - f) = dcreg . c[-1] . (1 - f): completed here, once per launch, in the tile the loop has just left.
+    // Nothing of it is exchanged: dz[0] feeds no further step ----
+    __builtin_amdgcn_sched_barrier(0);
+    if (A.c0 != nullptr) {
+        const __amdgpu_buffer_rsrc_t rs_c0 = __builtin_amdgcn_make_buffer_rsrc((void*)A.c0, 0, (int)min(us * 4, (size_t)0x7fffffff), 0x00020000);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const u32x4_t c0q = __builtin_amdgcn_raw_buffer_load_b128(rs_c0, (vo_e + 8 * a) * 4, (unsigned)((size_t)row0 * U) * 4, 0);
+            // (step 0's gates are fetched again here rather than taken from the final request's registers: nothing of the loop's operand
+            // registers is then live behind the loop)
+            const u32x4_t ga = __builtin_amdgcn_raw_buffer_load_b128(rs_g, (vo_e + 8 * a) * 8, (unsigned)((size_t)row0 * U) * 8, 0);
+            const u32x4_t gb = __builtin_amdgcn_raw_buffer_load_b128(rs_g, (vo_e + 8 * a) * 8 + 16, (unsigned)((size_t)row0 * U) * 8, 0);
+            h16_t zf[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const unsigned g23 = r < 2 ? ga[2 * r + 1] : gb[2 * r - 3];
+                zf[r] = F::cvt(dcreg[a][r] * __uint_as_float(c0q[r]) * (1.f - F::lo(g23)));
+                dbv[a][2][r] += F::f32(zf[r]);
+            }
+            u32x2_t v;
+            v[0] = (unsigned)zf[0] | ((unsigned)zf[1] << 16);
+            v[1] = (unsigned)zf[2] | ((unsigned)zf[3] << 16);
+            *reinterpret_cast<u32x2_t*>(smem + G::OFF_Z + (T & 1) * G::ZB + row * G::PZ + (gate_perm_col(2, u0 + 8 * a) - 256 * mem) * 2) = v;
+        }
+        CL_BARRIER();
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -771,7 +831,7 @@ static int cl_fwd_fill(const mnn_lstm_fwd_layer* L, int T, int B, float keep_pro
     MNN_REQUIRE(cl_shape_ok(B, L->units), "mnn_lstm_cluster_fwd: units must be 512, B a multiple of 256 and B / 4 at most the device's CUs (B=%d u=%d)", B, L->units);
     MNN_REQUIRE(L->xproj && L->wh_t && L->c && L->h, "mnn_lstm_cluster_fwd: null pointer");
     MNN_REQUIRE(L->xproj_bf16 != 0, "mnn_lstm_cluster_fwd: the input projection must be in the layer's 16-bit type (gate-minor, bias included)");
-    MNN_REQUIRE(L->h0 == nullptr && L->c0 == nullptr, "mnn_lstm_cluster_fwd: an initial state is not supported by this form (zero state per window)");
+    MNN_REQUIRE((L->h0 == nullptr) == (L->c0 == nullptr), "mnn_lstm_cluster_fwd: an initial state is h0 (the layer's 16-bit type) AND c0 (f32), both [B, u], or neither");
     MNN_REQUIRE(L->hT == nullptr || (L->ld_hT >= T * B && (L->ld_hT & 7) == 0), "mnn_lstm_cluster_fwd: ld_hT too small / not a multiple of 8");
     MNN_REQUIRE(L->yT == nullptr || (L->ld_yT >= T * B && (L->ld_yT & 7) == 0), "mnn_lstm_cluster_fwd: ld_yT too small / not a multiple of 8");
     MNN_REQUIRE((L->mask == nullptr) == (keep_prob >= 1.0f) && (L->mask == nullptr || L->y != nullptr),
@@ -782,6 +842,7 @@ static int cl_fwd_fill(const mnn_lstm_fwd_layer* L, int T, int B, float keep_pro
                 "mnn_lstm_cluster_fwd: a tensor of this call exceeds the 2 GB a buffer descriptor addresses");
     a.xproj = (const h16_t*)L->xproj; a.wh_t = (const h16_t*)L->wh_t; a.gates = (h16_t*)L->gates; a.c = L->c; a.h = (h16_t*)L->h; a.y = (h16_t*)L->y;
     a.mask = L->mask; a.hT = (h16_t*)L->hT; a.ld_hT = L->ld_hT; a.yT = (h16_t*)L->yT; a.ld_yT = L->ld_yT;
+    a.h0 = (const h16_t*)L->h0; a.c0 = L->c0;
     size_t sync_bytes = 0, xoff = 0;
     mnn_rp_workspace_layout(B / 32, 512, &sync_bytes, &xoff);
     a.sync = (unsigned*)workspace; a.xchg = (char*)workspace + xoff;
@@ -812,38 +873,41 @@ extern "C" int mnn_lstm_cluster_fwd(mnn_stream_t s, int T, int B, const mnn_lstm
     return mnn_lstm_cluster_fwd_multi(s, T, B, 1, L, keep_prob, &workspace);
 }
 
-static int cl_bwd_fill(const mnn_lstm_bwd_layer* L, int T, int B, float keep_prob, void* workspace, ClBwdArgs& a) {
-    MNN_REQUIRE(L && workspace && T > 0 && B > 0 && keep_prob > 0.f, "mnn_lstm_cluster_bwd: bad arguments");
-    MNN_REQUIRE(((size_t)workspace & 255) == 0, "mnn_lstm_cluster_bwd: workspace must be 256-byte aligned");
-    MNN_REQUIRE(cl_shape_ok(B, L->units), "mnn_lstm_cluster_bwd: units must be 512, B a multiple of 256 and B / 4 at most the device's CUs (B=%d u=%d)", B, L->units);
-    MNN_REQUIRE(L->dh_ext && L->wh_p && L->gates && L->c, "mnn_lstm_cluster_bwd: null pointer");
-    MNN_REQUIRE(L->c0 == nullptr && L->dz == nullptr, "mnn_lstm_cluster_bwd: no initial state / f32 dz output in this form");
+static int cl_bwd_fill(const mnn_lstm_bwd_layer* L, int T, int B, float keep_prob, void* workspace, float* dc0, ClBwdArgs& a) {
+    MNN_REQUIRE(L && workspace && T > 0 && B > 0 && keep_prob > 0.f, "mnn_lstm_cluster_bwd[_state]: bad arguments");
+    MNN_REQUIRE(((size_t)workspace & 255) == 0, "mnn_lstm_cluster_bwd[_state]: workspace must be 256-byte aligned");
+    MNN_REQUIRE(cl_shape_ok(B, L->units), "mnn_lstm_cluster_bwd[_state]: units must be 512, B a multiple of 256 and B / 4 at most the device's CUs (B=%d u=%d)", B, L->units);
+    MNN_REQUIRE(L->dh_ext && L->wh_p && L->gates && L->c, "mnn_lstm_cluster_bwd[_state]: null pointer");
+    MNN_REQUIRE(L->dz == nullptr, "mnn_lstm_cluster_bwd[_state]: no f32 dz output in this form");
     MNN_REQUIRE(L->dzT_t == nullptr || L->ld_t == 0 || (L->ld_t >= T * B && (L->ld_t & 7) == 0),
-                "mnn_lstm_cluster_bwd: ld_t too small / not a multiple of 8 (0 = the K-blocked layout [T*B/32][4u][32])");
+                "mnn_lstm_cluster_bwd[_state]: ld_t too small / not a multiple of 8 (0 = the K-blocked layout [T*B/32][4u][32])");
     MNN_REQUIRE((size_t)T * B * 512 * 8 < ((size_t)1 << 31) && (size_t)2048 * (size_t)L->ld_t * 2 < ((size_t)1 << 31),
-                "mnn_lstm_cluster_bwd: a tensor of this call exceeds the 2 GB a buffer descriptor addresses");
-    MNN_REQUIRE((L->mask == nullptr) == (keep_prob >= 1.0f), "mnn_lstm_cluster_bwd: a keep mask goes with keep_prob < 1 and only with it (the forward's rule)");
-    MNN_REQUIRE(T >= 4, "mnn_lstm_cluster_bwd: T >= 4 (the two exchange buffers of a cluster take the room of four timesteps of the row-parallel workspace)");
+                "mnn_lstm_cluster_bwd[_state]: a tensor of this call exceeds the 2 GB a buffer descriptor addresses");
+    MNN_REQUIRE((L->mask == nullptr) == (keep_prob >= 1.0f), "mnn_lstm_cluster_bwd[_state]: a keep mask goes with keep_prob < 1 and only with it (the forward's rule)");
+    MNN_REQUIRE(T >= 4, "mnn_lstm_cluster_bwd[_state]: T >= 4 (the two exchange buffers of a cluster take the room of four timesteps of the row-parallel workspace)");
     a.dh_ext = L->dh_ext; a.wh_p = (const h16_t*)L->wh_p; a.gates = (const h16_t*)L->gates; a.c = L->c; a.mask = keep_prob < 1.0f ? L->mask : nullptr;
     a.dzc = (h16_t*)L->dz_T; a.dzT = (h16_t*)L->dzT_t; a.ld_t = L->ld_t; a.db_p = L->db_p;
+    a.c0 = L->c0; a.dc0 = dc0;
     size_t sync_bytes = 0, xoff = 0;
     mnn_rp_workspace_layout(B / 32, 512, &sync_bytes, &xoff);
     a.sync = (unsigned*)workspace; a.xchg = (char*)workspace + xoff;
     a.T = T; a.B = B; a.ncl = B / 32; a.kp = keep_prob; a.allow_local = getenv("MNN_PERSIST_NO_LOCAL") == nullptr;
     return MNN_OK;
 }
-extern "C" int mnn_lstm_cluster_bwd_multi(mnn_stream_t s, int T, int B, int njobs, const mnn_lstm_bwd_layer* L, float keep_prob, void* const* workspaces) {
+// dc0: NULL, or one pointer per job (each f32 [B, u] or NULL)
+extern "C" int mnn_lstm_cluster_bwd_state_multi(mnn_stream_t s, int T, int B, int njobs, const mnn_lstm_bwd_layer* L, float keep_prob, void* const* workspaces,
+                                                float* const* dc0) {
     hipStream_t st = (hipStream_t)s;
-    MNN_REQUIRE(L && workspaces && njobs >= 1 && njobs <= CL_MAX_JOBS, "mnn_lstm_cluster_bwd_multi: 1..%d jobs", CL_MAX_JOBS);
+    MNN_REQUIRE(L && workspaces && njobs >= 1 && njobs <= CL_MAX_JOBS, "mnn_lstm_cluster_bwd[_state]_multi: 1..%d jobs", CL_MAX_JOBS);
     ClBwdJobs j{};
     j.njobs = njobs;
     for (int i = 0; i < njobs; ++i) {
-        if (int rc = cl_bwd_fill(L + i, T, B, keep_prob, workspaces[i], j.job[i])) return rc;
+        if (int rc = cl_bwd_fill(L + i, T, B, keep_prob, workspaces[i], dc0 ? dc0[i] : nullptr, j.job[i])) return rc;
         MNN_REQUIRE((L[i].f16 != 0) == (L[0].f16 != 0) && (j.job[i].mask != nullptr) == (j.job[0].mask != nullptr),
-                    "mnn_lstm_cluster_bwd_multi: the jobs must share precision and dropout mode");
-        for (int k = 0; k < i; ++k) MNN_REQUIRE(workspaces[k] != workspaces[i], "mnn_lstm_cluster_bwd_multi: every job needs its own workspace");
+                    "mnn_lstm_cluster_bwd[_state]_multi: the jobs must share precision and dropout mode");
+        for (int k = 0; k < i; ++k) MNN_REQUIRE(workspaces[k] != workspaces[i], "mnn_lstm_cluster_bwd[_state]_multi: every job needs its own workspace");
     }
-    MNN_REQUIRE(((njobs * (B / 32)) & 7) == 0, "mnn_lstm_cluster_bwd_multi: the grid's clusters must be a multiple of 8");
+    MNN_REQUIRE(((njobs * (B / 32)) & 7) == 0, "mnn_lstm_cluster_bwd[_state]_multi: the grid's clusters must be a multiple of 8");
     MNN_HIP(cl_prepare());
     for (int i = 0; i < njobs; ++i)
         if (int rc = mnn_rp_reset_launch(st, workspaces[i], B / 32, 512)) return rc;
@@ -851,6 +915,12 @@ extern "C" int mnn_lstm_cluster_bwd_multi(mnn_stream_t s, int T, int B, int njob
     MNN_LAUNCH_CHECK();
     return MNN_OK;
 }
+extern "C" int mnn_lstm_cluster_bwd_multi(mnn_stream_t s, int T, int B, int njobs, const mnn_lstm_bwd_layer* L, float keep_prob, void* const* workspaces) {
+    return mnn_lstm_cluster_bwd_state_multi(s, T, B, njobs, L, keep_prob, workspaces, nullptr);
+}
+extern "C" int mnn_lstm_cluster_bwd_state(mnn_stream_t s, int T, int B, const mnn_lstm_bwd_layer* L, float keep_prob, void* workspace, float* dc0) {
+    return mnn_lstm_cluster_bwd_state_multi(s, T, B, 1, L, keep_prob, &workspace, &dc0);
+}
 extern "C" int mnn_lstm_cluster_bwd(mnn_stream_t s, int T, int B, const mnn_lstm_bwd_layer* L, float keep_prob, void* workspace) {
-    return mnn_lstm_cluster_bwd_multi(s, T, B, 1, L, keep_prob, &workspace);
+    return mnn_lstm_cluster_bwd_state_multi(s, T, B, 1, L, keep_prob, &workspace, nullptr);
 }

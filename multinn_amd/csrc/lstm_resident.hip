@@ -38,6 +38,7 @@ extern "C" int mnn_lstm_resident_trace(void* out) {
 struct ResFwdArgs {
     const h16_t* xproj; const h16_t* wh_t; h16_t* gates; float* c; h16_t* h; h16_t* y; const uint8_t* mask;
     h16_t* hT; int ld_hT; h16_t* yT; int ld_yT;
+    const h16_t* h0; const float* c0;      // initial state [B, u] (both or neither; NULL: the zero state)
     int T, B; float kp;
 };
 // Several independent layers of the same shape in ONE launch (mnn_lstm_resident_fwd_multi: the per-track generators of the jamming mode,
@@ -122,8 +123,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 #pragma unroll
             for (int s = 0; s < 4; ++s) asm volatile("" : "+a"(wr[tl][s]));
     }
-    // zero state: h[-1] = 0 in the first state buffer
-    for (int i = tid; i < 4 * G::PH / 4; i += 256) reinterpret_cast<unsigned*>(smem + G::OFF_H)[i] = 0u;
+    // h[-1] in the first state buffer: the caller's h0 rows, or the zero state.  A run-time property of the launch (uniform pointer test,
+    // outside the time loop): behind the barrier in front of step 0 nothing differs
+    if (A.h0 != nullptr) {
+        const unsigned* h0w = reinterpret_cast<const unsigned*>(A.h0 + (size_t)row0 * U);
+        for (int i = tid; i < 4 * G::PH / 4; i += 256) {
+            const int r = i / (G::PH / 4), cw = i - r * (G::PH / 4);
+            reinterpret_cast<unsigned*>(smem + G::OFF_H)[i] = cw < U / 2 ? h0w[r * (U / 2) + cw] : 0u;
+        }
+    } else {
+        for (int i = tid; i < 4 * G::PH / 4; i += 256) reinterpret_cast<unsigned*>(smem + G::OFF_H)[i] = 0u;
+    }
 
     // ---- staging of a step's xproj rows (4 x 8u bytes) and keep bytes (4 x u) a step ahead, global -> LDS without registers: wave w moves row w ----
     const char* xsrc = reinterpret_cast<const char*>(A.xproj) + ((size_t)(row0 + w) * U) * 8 + lane * 16;
@@ -202,6 +212,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     float creg[G::NG];
 #pragma unroll
     for (int q = 0; q < G::NG; ++q) creg[q] = 0.f;
+    if (A.c0 != nullptr) {                          // c[-1] of this lane's (row, unit) pairs (the ownership of `pointwise`)
+#pragma unroll
+        for (int q = 0; q < G::NG; ++q) creg[q] = A.c0[(size_t)(row0 + row) * U + G::UW * w + 16 * q + 4 * bank + g4];
+        // consumed HERE: the loads are waited for in the prologue, not by a wait the compiler would put in front of the first pointwise of
+        // every step (where it would also wait for the step's LDS-DMA)
+#pragma unroll
+        for (int q = 0; q < G::NG; ++q) asm volatile("" : "+v"(creg[q]));
+    }
     const uint4* wl = reinterpret_cast<const uint4*>(smem + G::OFF_W) + (size_t)w * G::WPW * 64 + lane;
     // order of the k-steps inside a group: the two LDS-resident ones sit two register k-steps apart, so that the four fragment registers
     // of the first can be re-requested for the second while 8 MFMAs run
@@ -323,6 +341,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 struct ResBwdArgs {
     const float* dh_ext; const h16_t* wh_p; const h16_t* gates; const float* c; const uint8_t* mask;
     h16_t* dzc; h16_t* dzT; int ld_t; float* db_p;
+    const float* c0; float* dc0;           // initial cell state [B, u] (NULL: zero) and its gradient d_c[0] . f[0] (NULL: not wanted)
     int T, B; float kp;
 };
 struct ResBwdJobs { ResBwdArgs job[RES_MAX_JOBS]; int njobs; };
@@ -482,6 +501,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             }
         }
         RES_TR(1);
+        // (nothing of the pointwise above this line: with the loop's registers live behind the loop -- the initial-state epilogue -- the
+        // scheduler otherwise pulls the gate arithmetic, and its wait for the step's operands, into the MFMA stream: + 8 % on the launch)
+        __builtin_amdgcn_sched_barrier(0);
         // ---- pointwise: bank b keeps tile b; register r = unit u0 + r ----
         float dhr[4];
 #pragma unroll
@@ -499,7 +521,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             const float tc = fast_tanh(cnext[r]);
             const float d_o = dh * tc;
             const float d_c = dh * go * (1.f - tc * tc) + dcreg[r];
-            const float cprev = t > 0 ? __uint_as_float(cq[r]) : 0.f;
+            const float cprev = t > 0 ? __uint_as_float(cq[r]) : 0.f;              // (step 0 with an initial cell state: completed behind the loop)
             const float dzv[4] = {d_c * gg * gi * (1.f - gi), d_c * gi * (1.f - gg * gg), d_c * cprev * gf * (1.f - gf), d_o * go * (1.f - go)};
             dcreg[r] = d_c * gf;
             cnext[r] = cprev;
@@ -522,10 +544,36 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         RES_TR(3);
         RES_TR_FLUSH(1, kk);
     }
+    // ---- initial cell state: the loop is the loop of a launch without one (it took c[-1] = 0; a select of the c[t-1] resource inside the step
+    // was measured: it re-ordered the pointwise of the fp16 / dropout kernel, + 9 %).  c[-1] enters step 0 in ONE place, the forget gate's
+    // dz = d_c . c[-1] . f (1 - f) = dcreg . c[-1] . (1 - f): completed here, once per launch, in the tile the loop has just left (the final
+    // clamped request has brought step 0's gates back) ----
+    const bool has0 = A.c0 != nullptr;
+    if (has0) {
+        const u32x4_t c0q = *reinterpret_cast<const u32x4_t*>(A.c0 + (size_t)(row0 + row) * U + u0);
+        h16_t zf[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const unsigned g23 = r < 2 ? gq0[2 * r + 1] : gq1[2 * r - 3];
+            zf[r] = F::cvt(dcreg[r] * __uint_as_float(c0q[r]) * (1.f - F::lo(g23)));
+            dbv[2][r] += F::f32(zf[r]);
+        }
+        u32x2_t v;
+        v[0] = (unsigned)zf[0] | ((unsigned)zf[1] << 16);
+        v[1] = (unsigned)zf[2] | ((unsigned)zf[3] << 16);
+        *reinterpret_cast<u32x2_t*>(smem + G::OFF_Z + (T & 1) * 4 * G::PZ + row * G::PZ + gate_perm_col(2, u0) * 2) = v;
+        RES_BARRIER();
+    }
     emit_read(T & 1, 0);
     emit_store(0, 0);
     emit_read(T & 1, 1);
     emit_store(0, 1);
+    if (A.dc0 != nullptr) {                             // gradient wrt the initial cell state: d_c[0] . f[0], what the loop left in dcreg
+        u32x4_t v;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = __float_as_uint(dcreg[r]);
+        *reinterpret_cast<u32x4_t*>(A.dc0 + (size_t)(row0 + row) * U + u0) = v;
+    }
     if (A.db_p != nullptr) {                            // bias gradient: sums over this workgroup's four rows and all steps
 #pragma unroll
         for (int g = 0; g < 4; ++g)
@@ -582,7 +630,7 @@ static int res_fwd_fill(const mnn_lstm_fwd_layer* L, int T, int B, float keep_pr
     MNN_REQUIRE(res_shape_ok(B, L->units), "mnn_lstm_resident_fwd: units must be 256 and B a multiple of 4 (B=%d u=%d)", B, L->units);
     MNN_REQUIRE(L->xproj && L->wh_t && L->c && L->h, "mnn_lstm_resident_fwd: null pointer");
     MNN_REQUIRE(L->xproj_bf16 != 0, "mnn_lstm_resident_fwd: the input projection must be in the layer's 16-bit type (gate-minor, bias included)");
-    MNN_REQUIRE(L->h0 == nullptr && L->c0 == nullptr, "mnn_lstm_resident_fwd: an initial state is not supported by this form (zero state per window)");
+    MNN_REQUIRE((L->h0 == nullptr) == (L->c0 == nullptr), "mnn_lstm_resident_fwd: an initial state is h0 (the layer's 16-bit type) AND c0 (f32), both [B, u], or neither");
     MNN_REQUIRE(L->hT == nullptr || (L->ld_hT >= T * B && (L->ld_hT & 3) == 0), "mnn_lstm_resident_fwd: ld_hT too small / not a multiple of 4");
     MNN_REQUIRE(L->yT == nullptr || (L->ld_yT >= T * B && (L->ld_yT & 3) == 0), "mnn_lstm_resident_fwd: ld_yT too small / not a multiple of 4");
     MNN_REQUIRE((L->mask == nullptr) == (keep_prob >= 1.0f) && (L->mask == nullptr || L->y != nullptr),
@@ -593,6 +641,7 @@ static int res_fwd_fill(const mnn_lstm_fwd_layer* L, int T, int B, float keep_pr
                 "mnn_lstm_resident_fwd: a tensor of this call exceeds the 2 GB a buffer descriptor addresses");
     a.xproj = (const h16_t*)L->xproj; a.wh_t = (const h16_t*)L->wh_t; a.gates = (h16_t*)L->gates; a.c = L->c; a.h = (h16_t*)L->h; a.y = (h16_t*)L->y;
     a.mask = L->mask; a.hT = (h16_t*)L->hT; a.ld_hT = L->ld_hT; a.yT = (h16_t*)L->yT; a.ld_yT = L->ld_yT;
+    a.h0 = (const h16_t*)L->h0; a.c0 = L->c0;
     a.T = T; a.B = B; a.kp = keep_prob;
     return MNN_OK;
 }
@@ -616,36 +665,44 @@ extern "C" int mnn_lstm_resident_fwd(mnn_stream_t s, int T, int B, const mnn_lst
     return mnn_lstm_resident_fwd_multi(s, T, B, 1, L, keep_prob);
 }
 
-static int res_bwd_fill(const mnn_lstm_bwd_layer* L, int T, int B, float keep_prob, ResBwdArgs& a) {
-    MNN_REQUIRE(L && T > 0 && B > 0 && keep_prob > 0.f, "mnn_lstm_resident_bwd: bad arguments");
-    MNN_REQUIRE(res_shape_ok(B, L->units), "mnn_lstm_resident_bwd: units must be 256 and B a multiple of 4 (B=%d u=%d)", B, L->units);
-    MNN_REQUIRE(L->dh_ext && L->wh_p && L->gates && L->c, "mnn_lstm_resident_bwd: null pointer");
-    MNN_REQUIRE(L->c0 == nullptr && L->dz == nullptr, "mnn_lstm_resident_bwd: no initial state / f32 dz output in this form");
+static int res_bwd_fill(const mnn_lstm_bwd_layer* L, int T, int B, float keep_prob, float* dc0, ResBwdArgs& a) {
+    MNN_REQUIRE(L && T > 0 && B > 0 && keep_prob > 0.f, "mnn_lstm_resident_bwd[_state]: bad arguments");
+    MNN_REQUIRE(res_shape_ok(B, L->units), "mnn_lstm_resident_bwd[_state]: units must be 256 and B a multiple of 4 (B=%d u=%d)", B, L->units);
+    MNN_REQUIRE(L->dh_ext && L->wh_p && L->gates && L->c, "mnn_lstm_resident_bwd[_state]: null pointer");
+    MNN_REQUIRE(L->dz == nullptr, "mnn_lstm_resident_bwd[_state]: no f32 dz output in this form");
     MNN_REQUIRE(L->dzT_t == nullptr || (L->ld_t == 0 ? (B & 31) == 0 : (L->ld_t >= T * B && (L->ld_t & 3) == 0)),
-                "mnn_lstm_resident_bwd: ld_t too small / not a multiple of 4 (0 = the K-blocked layout [T*B/32][4u][32], B a multiple of 32)");
+                "mnn_lstm_resident_bwd[_state]: ld_t too small / not a multiple of 4 (0 = the K-blocked layout [T*B/32][4u][32], B a multiple of 32)");
     MNN_REQUIRE((size_t)T * B * 256 * 8 < ((size_t)1 << 31) && (size_t)1024 * (size_t)L->ld_t * 2 < ((size_t)1 << 31),
-                "mnn_lstm_resident_bwd: a tensor of this call exceeds the 2 GB a buffer descriptor addresses");
-    MNN_REQUIRE((L->mask == nullptr) == (keep_prob >= 1.0f), "mnn_lstm_resident_bwd: a keep mask goes with keep_prob < 1 and only with it (the forward's rule)");
+                "mnn_lstm_resident_bwd[_state]: a tensor of this call exceeds the 2 GB a buffer descriptor addresses");
+    MNN_REQUIRE((L->mask == nullptr) == (keep_prob >= 1.0f), "mnn_lstm_resident_bwd[_state]: a keep mask goes with keep_prob < 1 and only with it (the forward's rule)");
     a.dh_ext = L->dh_ext; a.wh_p = (const h16_t*)L->wh_p; a.gates = (const h16_t*)L->gates; a.c = L->c; a.mask = keep_prob < 1.0f ? L->mask : nullptr;
     a.dzc = (h16_t*)L->dz_T; a.dzT = (h16_t*)L->dzT_t; a.ld_t = L->ld_t; a.db_p = L->db_p;
+    a.c0 = L->c0; a.dc0 = dc0;
     a.T = T; a.B = B; a.kp = keep_prob;
     return MNN_OK;
 }
-extern "C" int mnn_lstm_resident_bwd_multi(mnn_stream_t s, int T, int B, int njobs, const mnn_lstm_bwd_layer* L, float keep_prob) {
+// dc0: NULL, or one pointer per job (each f32 [B, u] or NULL)
+extern "C" int mnn_lstm_resident_bwd_state_multi(mnn_stream_t s, int T, int B, int njobs, const mnn_lstm_bwd_layer* L, float keep_prob, float* const* dc0) {
     hipStream_t st = (hipStream_t)s;
-    MNN_REQUIRE(L && njobs >= 1 && njobs <= RES_MAX_JOBS, "mnn_lstm_resident_bwd_multi: 1..%d jobs", RES_MAX_JOBS);
+    MNN_REQUIRE(L && njobs >= 1 && njobs <= RES_MAX_JOBS, "mnn_lstm_resident_bwd[_state]_multi: 1..%d jobs", RES_MAX_JOBS);
     ResBwdJobs j{};
     j.njobs = njobs;
     for (int i = 0; i < njobs; ++i) {
-        if (int rc = res_bwd_fill(L + i, T, B, keep_prob, j.job[i])) return rc;
+        if (int rc = res_bwd_fill(L + i, T, B, keep_prob, dc0 ? dc0[i] : nullptr, j.job[i])) return rc;
         MNN_REQUIRE((L[i].f16 != 0) == (L[0].f16 != 0) && (j.job[i].mask != nullptr) == (j.job[0].mask != nullptr),
-                    "mnn_lstm_resident_bwd_multi: the jobs must share precision and dropout mode");
+                    "mnn_lstm_resident_bwd[_state]_multi: the jobs must share precision and dropout mode");
     }
     MNN_HIP(res_prepare());
     hipLaunchKernelGGL(res_bwd_kernel(L->f16 != 0, j.job[0].mask != nullptr), dim3(njobs * (B / 4)), dim3(256), ResBwdGeom<256>::LDS, st, j);
     MNN_LAUNCH_CHECK();
     return MNN_OK;
 }
+extern "C" int mnn_lstm_resident_bwd_multi(mnn_stream_t s, int T, int B, int njobs, const mnn_lstm_bwd_layer* L, float keep_prob) {
+    return mnn_lstm_resident_bwd_state_multi(s, T, B, njobs, L, keep_prob, nullptr);
+}
+extern "C" int mnn_lstm_resident_bwd_state(mnn_stream_t s, int T, int B, const mnn_lstm_bwd_layer* L, float keep_prob, float* dc0) {
+    return mnn_lstm_resident_bwd_state_multi(s, T, B, 1, L, keep_prob, &dc0);
+}
 extern "C" int mnn_lstm_resident_bwd(mnn_stream_t s, int T, int B, const mnn_lstm_bwd_layer* L, float keep_prob) {
-    return mnn_lstm_resident_bwd_multi(s, T, B, 1, L, keep_prob);
+    return mnn_lstm_resident_bwd_state_multi(s, T, B, 1, L, keep_prob, nullptr);
 }

@@ -278,7 +278,8 @@ def build_generator(params, P, M, precision="bf16", seed=23):
         raise ValueError("build_generator is the joint / PassEncoder shortcut: use build_model(config, params) for the other modes")
     g = params["generator"]
     cls = {"NADE": RnnNade, "RBM": RnnRBM}[g["type"]]
-    return cls(P * M, g["num_hidden"], g["num_hidden_rnn"], keep_prob=params.get("keep_prob", 0.9), precision=precision, seed=seed)
+    return cls(P * M, g["num_hidden"], g["num_hidden_rnn"], keep_prob=params.get("keep_prob", 0.9), precision=precision, seed=seed,
+               learn_zero_state=bool(g.get("learn_zero_state", False)))
 
 
 def build_model(config, params, precision="bf16", seed=None, device=None):

@@ -111,10 +111,12 @@ def shifted_sequences(x):
 # turns the M requests of a rendezvous into ONE launch where the library has a multi-job form (ops.lstm_recurrence_multi: the CU-resident and
 # cluster recurrences own their rows for the whole sequence, so independent layers simply share a grid); everything between two rendezvous
 # (GEMMs, Gibbs chains, ...) is issued per generator, in generator order, on the same stream.
+# A backward request of the resident / cluster form may carry a seventh element: dc0 f32 [B, u], the output for the gradient wrt the layer's
+# initial cell state (a stack that started from a state: LstmStack.backward(need_dstate=True)).
 _SINGLE = {"resident_fwd": lambda T, B, d, kp, ws: ops.lstm_resident_fwd(T, B, d, kp),
-           "resident_bwd": lambda T, B, d, kp, ws: ops.lstm_resident_bwd(T, B, d, kp),
+           "resident_bwd": lambda T, B, d, kp, ws, dc0=None: ops.lstm_resident_bwd(T, B, d, kp, dc0),
            "cluster_fwd": lambda T, B, d, kp, ws: ops.lstm_cluster_fwd(T, B, d, kp, ws),
-           "cluster_bwd": lambda T, B, d, kp, ws: ops.lstm_cluster_bwd(T, B, d, kp, ws),
+           "cluster_bwd": lambda T, B, d, kp, ws, dc0=None: ops.lstm_cluster_bwd(T, B, d, kp, ws, dc0),
            "rowpar_fwd": lambda T, B, d, kp, ws: ops.lstm_rowpar_fwd(T, B, d, kp, ws),
            "rowpar_bwd": lambda T, B, d, kp, ws: ops.lstm_rowpar_bwd(T, B, d, kp, ws)}
 
@@ -147,7 +149,7 @@ def drive_group(cos):
     while any(alive):
         if not all(alive):
             raise RuntimeError("drive_group: the grouped generators did not ask for the same sequence of recurrences")
-        kind, T, B, _, kp, _ = reqs[0]
+        kind, T, B, kp = reqs[0][0], reqs[0][1], reqs[0][2], reqs[0][4]
         same = all(r[0] == kind and r[1] == T and r[2] == B and r[4] == kp and r[3].units == reqs[0][3].units for r in reqs)
         multi = same and n > 1 and kind.split("_")[0] in ("resident", "cluster")
         if multi and kind == "cluster_bwd" and not ops.lstm_cluster_bwd_multi_ok(B, reqs[0][3].units, n):
@@ -155,7 +157,8 @@ def drive_group(cos):
         if multi and kind.startswith("cluster") and (n * (B // 32)) % 8 != 0:
             multi = False
         if multi:
-            ops.lstm_recurrence_multi(kind, T, B, [r[3] for r in reqs], kp, [r[5] for r in reqs] if kind.startswith("cluster") else None)
+            ops.lstm_recurrence_multi(kind, T, B, [r[3] for r in reqs], kp, [r[5] for r in reqs] if kind.startswith("cluster") else None,
+                                      [r[6] if len(r) > 6 else None for r in reqs])
         else:
             for r in reqs:
                 _SINGLE[r[0]](*r[1:])
@@ -300,6 +303,15 @@ class LstmStack:
             return False
         return all("wx_gm" in p and ops.lstm_rowpar_ok(B, p["u"]) for p in self.packed)
 
+    def _rowpar_state0(self, B, T=2):
+        """The row-parallel path for a stack that starts from an initial state: of its three recurrences only the CU-resident and the cluster
+        form take one (and return its gradient), so every layer's forward AND backward must be theirs -- answered on the host, before the
+        forward (the saved gates of this family and of the launch-per-timestep kernels differ).  Otherwise such a stack takes the
+        launch-per-timestep path."""
+        if not self._rowpar(B, T):
+            return False
+        return all(self._resident(l, B, T) or (self._cluster(l, B, T) and self._cluster_bwd(l, B, T)) for l in range(len(self.packed)))
+
     def _rp_workspace(self, l, T, B, dev):
         if not hasattr(self, "_rpws"):
             self._rpws = {}
@@ -326,12 +338,14 @@ class LstmStack:
         self._cat0 = (torch.zeros if Np != T * B else torch.empty)(self._cat_shape(0, Np), device=dev, dtype=self.dtype)
         return self._cat0[:self.packed[0]["ld"]]
 
-    def _forward_rowpar(self, x_tm, keep_prob, seed, row0, save, step_dev):
-        return drive(self._forward_rowpar_co(x_tm, keep_prob, seed, row0, save, step_dev))
+    def _forward_rowpar(self, x_tm, keep_prob, seed, row0, save, step_dev, state0=None):
+        return drive(self._forward_rowpar_co(x_tm, keep_prob, seed, row0, save, step_dev, state0))
 
-    def _forward_rowpar_co(self, x_tm, keep_prob, seed, row0, save, step_dev):
+    def _forward_rowpar_co(self, x_tm, keep_prob, seed, row0, save, step_dev, state0=None):
         """Layer by layer: gate-minor input projection (one GEMM over all T*B rows), then the layer's whole recurrence in one launch -- YIELDED
-        to the driver (drive / drive_group above), which issues it alone or together with the same layer of other stacks."""
+        to the driver (drive / drive_group above), which issues it alone or together with the same layer of other stacks.
+        state0 ([(c0 f32, h0) [B, u]] per layer; only where _rowpar_state0 holds): h0 rounded to the compute type and c0 go into the layer's
+        descriptor, h0^T into columns [0, B) of h^T -- which puts the t = 0 term into dWh through the weight-gradient GEMM."""
         T, B, _ = x_tm.shape
         dev, N = x_tm.device, T * B
         Np = ops.round_up(N, 64)
@@ -363,33 +377,45 @@ class LstmStack:
             hT = yT = None
             if save:
                 hT = cats[l][p["ld"]:] if cats[l] is not None else torch.empty((u, Np), device=dev, dtype=self.dtype)
-                hT[:, :B].zero_()                      # h_{-1} = 0; columns [B, T*B) are written by the launch
                 if Np != N:
                     hT[:, N:].zero_()
                 nxt = cats[l + 1] if l + 1 < len(self.packed) else None
                 yT = nxt[:u] if nxt is not None else zalloc((u, Np), device=dev, dtype=self.dtype)
-            d = ops.lstm2_fwd_layer(xproj, p["wh_t"], None, None, gates, c, h, hT, y, mask, yT=yT, gates_dtype=self.dtype,
+            h0 = c0 = None
+            if state0 is not None:
+                c0, h0 = state0[l][0].float().contiguous(), state0[l][1].to(self.dtype).contiguous()
+            if save:                                    # columns [0, B) of h^T = h_{-1}^T (zero, or h0^T); columns [B, T*B) are written by the launch
+                if h0 is not None:
+                    ops.transpose(h0, hT[:, :B])
+                else:
+                    hT[:, :B].zero_()
+            d = ops.lstm2_fwd_layer(xproj, p["wh_t"], h0, c0, gates, c, h, hT, y, mask, yT=yT, gates_dtype=self.dtype,
                                     xproj_dtype=self.rowpar_xproj_dtype)
             if self._resident(l, B, T):
                 yield ("resident_fwd", T, B, d, keep_prob, None)
             elif self._cluster(l, B, T):
                 yield ("cluster_fwd", T, B, d, keep_prob, self._rp_workspace(l, T, B, dev))
             else:
+                if h0 is not None:
+                    raise RuntimeError("LstmStack: the row-parallel recurrence takes no initial state (_rowpar_state0 answers this before the forward)")
                 yield ("rowpar_fwd", T, B, d, keep_prob, self._rp_workspace(l, T, B, dev))
             out = y if y is not None else h
             if save:
-                ctx.append(dict(inp=inp, gates=gates, c=c, h=h, c0=None, h0=None, hT=hT, mask=mask, yT=yT,
+                ctx.append(dict(inp=inp, gates=gates, c=c, h=h, c0=c0, h0=h0, hT=hT, mask=mask, yT=yT,
                                 inT=ctx[l - 1]["yT"] if l > 0 else None, persist=True, rowpar=True, catT=cats[l]))
             final.append((c[-1], h[-1]))
             inp = out
         return inp, ctx, final
 
-    def _backward_rowpar(self, dy, ctx, keep_prob, need_dx=False):
-        return drive(self._backward_rowpar_co(dy, ctx, keep_prob, need_dx))
+    def _backward_rowpar(self, dy, ctx, keep_prob, need_dx=False, need_dstate=False):
+        return drive(self._backward_rowpar_co(dy, ctx, keep_prob, need_dx, need_dstate))
 
-    def _backward_rowpar_co(self, dy, ctx, keep_prob, need_dx=False):
+    def _backward_rowpar_co(self, dy, ctx, keep_prob, need_dx=False, need_dstate=False):
         """Top layer first: the layer's whole backward recurrence in one launch (dropout backward of its output folded in; yielded to the
-        driver like the forward's), then the gradient wrt its input as one GEMM (dz row-major x Wx), which is the next layer's dh_ext."""
+        driver like the forward's), then the gradient wrt its input as one GEMM (dz row-major x Wx), which is the next layer's dh_ext.
+        need_dstate (a stack that started from a state): returns (dx, [(dc0, dh0) f32 [B, u]] per layer).  dc0 comes out of the launch
+        (d_c . f of step 0); dh0 = dz[0] . Wh^T is one small GEMM over the 16-bit dz[0] the launch has written -- the operands the in-kernel
+        contraction of every other step sees."""
         T, B, _ = dy.shape
         dev, N = dy.device, T * B
         Np = ops.round_up(N, 64)
@@ -404,24 +430,42 @@ class LstmStack:
             # backward chain, and the GEMM only changes its LDS-DMA source addresses
             kb = self.kblock_wgrads and cx.get("catT") is not None and Np == N and N % 64 == 0
             dzT = torch.empty((N // 32, 4 * u, 32), device=dev, dtype=self.dtype) if kb else zalloc((4 * u, Np), device=dev, dtype=self.dtype)
+            want0 = need_dstate and cx.get("c0") is not None
             dzc = torch.empty((T, B, 4 * u), device=dev, dtype=self.dtype) if (l > 0 or (kb and need_dx)) else None
             db_p = self._accum(l, dev)[2]
-            e = ops.lstm2_bwd_layer(dh.view(T, B, u), p["wh_p"], cx["gates"], cx["c"], None, dzc, ops.lstm_seq_bwd_workspace(B, u, dev), dzT, db_p,
+            e = ops.lstm2_bwd_layer(dh.view(T, B, u), p["wh_p"], cx["gates"], cx["c"], cx.get("c0"), dzc, ops.lstm_seq_bwd_workspace(B, u, dev), dzT, db_p,
                                     cx["mask"] if keep_prob < 1.0 else None, gates_dtype=self.dtype)
+            dc0 = torch.empty((B, u), device=dev) if want0 else None
+            tail = (dc0,) if want0 else ()
             if self._resident(l, B, T):
-                yield ("resident_bwd", T, B, e, keep_prob, None)
+                yield ("resident_bwd", T, B, e, keep_prob, None) + tail
             elif self._cluster_bwd(l, B, T):
-                yield ("cluster_bwd", T, B, e, keep_prob, self._rp_workspace(l, T, B, dev))
+                yield ("cluster_bwd", T, B, e, keep_prob, self._rp_workspace(l, T, B, dev)) + tail
             else:
+                if cx.get("c0") is not None:
+                    raise RuntimeError("LstmStack: the row-parallel backward takes no initial state (_rowpar_state0 answers this before the forward)")
                 yield ("rowpar_bwd", T, B, e, keep_prob, self._rp_workspace(l, T, B, dev))
-            st[l] = dict(dzT=dzT, dzc=dzc, db_p=db_p)
+            st[l] = dict(dzT=dzT, dzc=dzc, db_p=db_p, dc0=dc0)
+            if want0:
+                # dz[0] row-major [B, 4u]: the first slab of the launch's row-major dz where this layer writes one, else read back out of dz^T
+                # (step 0 is its first B columns / B / 32 K-blocks: 1 MB, not worth a [T, B, 4u] output of its own -- 1 GB at the bench shape)
+                if dzc is not None:
+                    dz0 = dzc[0]
+                elif kb:
+                    dz0 = dzT[:B // 32].permute(0, 2, 1).reshape(B, 4 * u)
+                else:
+                    dz0 = dzT[:, :B].t().contiguous()
+                st[l]["dh0"] = ops.gemm_tn(dz0, p["wh_p"], torch.empty((B, u), device=dev))
             if l > 0:
                 dh = torch.empty((N, p["n_in"]), device=dev)
                 ops.gemm_tn(dzc.view(N, 4 * u), p["wx_p"], dh)
         if getattr(self, "keep_debug", False):
             self._dbg_dzT = [s_["dzT"] for s_ in st]
         keep = [self._weight_grads(l, ctx[l], st[l]["dzT"], st[l]["db_p"], T, B, dz=st[l]["dzc"]) for l in range(len(self.packed) - 1, -1, -1)]
-        return self._input_grad(st[0]["dzT"], T, B, dz=st[0]["dzc"]) if need_dx else None
+        dx = self._input_grad(st[0]["dzT"], T, B, dz=st[0]["dzc"]) if need_dx else None
+        if need_dstate:
+            return dx, [(s_["dc0"], s_["dh0"]) if s_["dc0"] is not None else None for s_ in st]
+        return dx
 
     def _workspace(self, T, B, dev):
         """Flags + exchange area of the persistent launches, one per (T, B) (kept alive: captured graphs point at it)."""
@@ -442,21 +486,26 @@ class LstmStack:
     def _chunks(T, step):
         return [(t0, min(T, t0 + step)) for t0 in range(0, T, step)]
 
-    def forward_co(self, x_tm, keep_prob=1.0, seed=0, row0=0, save=True, state0=None, step_dev=None):
+    def forward_co(self, x_tm, keep_prob=1.0, seed=0, row0=0, save=True, state0=None, step_dev=None, state_grad=False):
         """`forward` as a generator function for drive / drive_group: the row-parallel path yields its recurrence launches, every other path
         runs at once."""
         T, B, _ = x_tm.shape
         if self._rowpar(B, T, state0):
             return (yield from self._forward_rowpar_co(x_tm, keep_prob, seed, row0, save, step_dev))
-        return self.forward(x_tm, keep_prob, seed, row0, save, state0, step_dev)
+        if state0 is not None and T > 1 and self._rowpar_state0(B, T):
+            return (yield from self._forward_rowpar_co(x_tm, keep_prob, seed, row0, save, step_dev, state0))
+        return self.forward(x_tm, keep_prob, seed, row0, save, state0, step_dev, state_grad)
 
-    def backward_co(self, dy, ctx, keep_prob=1.0, seed=0, row0=0, need_dx=False, step_dev=None):
+    def backward_co(self, dy, ctx, keep_prob=1.0, seed=0, row0=0, need_dx=False, step_dev=None, need_dstate=False):
         if ctx and ctx[0].get("rowpar"):
-            return (yield from self._backward_rowpar_co(dy, ctx, keep_prob, need_dx))
-        return self.backward(dy, ctx, keep_prob, seed, row0, need_dx, step_dev)
+            return (yield from self._backward_rowpar_co(dy, ctx, keep_prob, need_dx, need_dstate))
+        return self.backward(dy, ctx, keep_prob, seed, row0, need_dx, step_dev, need_dstate)
 
-    def forward(self, x_tm, keep_prob=1.0, seed=0, row0=0, save=True, state0=None, step_dev=None):
+    def forward(self, x_tm, keep_prob=1.0, seed=0, row0=0, save=True, state0=None, step_dev=None, state_grad=False):
         """x_tm [T,B,ld0] compute dtype.  Returns (y [T,B,u_last], ctx, final_state[(c,h)...]).
+        state0: [(c0 f32, h0) [B, u]] per layer.  state_grad: the backward will be asked for the gradient wrt state0 (need_dstate): where the
+        resident / cluster recurrences do not cover the stack, the launch-per-timestep kernels run (the two-layer persistent form has a
+        state input but no state gradient).
 
         The T-step recurrences are latency-bound chains, so the layers run as a WAVEFRONT: layer l works on
         time chunk c on its own HIP stream while layer l-1 is already on chunk c+1 (events order the chunks)."""
@@ -465,7 +514,9 @@ class LstmStack:
         L = len(self.packed)
         if self._rowpar(B, T, state0):
             return self._forward_rowpar(x_tm, keep_prob, seed, row0, save, step_dev)
-        persist = self._persist(B, T)
+        if state0 is not None and T > 1 and self._rowpar_state0(B, T):
+            return self._forward_rowpar(x_tm, keep_prob, seed, row0, save, step_dev, state0)
+        persist = self._persist(B, T) and not (state_grad and state0 is not None and save)
         bufs = []
         for l, p in enumerate(self.packed):
             u = p["u"]
@@ -617,12 +668,13 @@ class LstmStack:
                             torch.zeros(4 * p["u"], device=dev))
         return self._acc[l]
 
-    def backward(self, dy, ctx, keep_prob=1.0, seed=0, row0=0, need_dx=False, step_dev=None):
+    def backward(self, dy, ctx, keep_prob=1.0, seed=0, row0=0, need_dx=False, step_dev=None, need_dstate=False):
         """dy f32 [T,B,u_last]: gradient wrt the (dropped) top output.  Accumulates the kernel / bias gradients
         into the store's flat gradient buffer.  Same wavefront as forward, top layer first, chunks descending;
-        each layer's weight-gradient GEMMs then run on that layer's stream."""
+        each layer's weight-gradient GEMMs then run on that layer's stream.
+        need_dstate: returns (dx, [(dc0, dh0) f32 [B, u]] per layer), the gradient wrt the forward's state0 (None for a layer without one)."""
         if ctx and ctx[0].get("rowpar"):
-            return self._backward_rowpar(dy, ctx, keep_prob, need_dx)
+            return self._backward_rowpar(dy, ctx, keep_prob, need_dx, need_dstate)
         T, B, _ = dy.shape
         dev = dy.device
         L = len(self.packed)
@@ -635,6 +687,8 @@ class LstmStack:
         dyl = [None] * L
         dyl[L - 1] = dy.view(T, B, -1)
         persist = bool(ctx[0].get("persist"))       # the layout of the saved gates is the forward's choice
+        if need_dstate and persist and ctx[0].get("c0") is not None:
+            raise RuntimeError("LstmStack.backward(need_dstate=True): the two-layer persistent form has no state gradient; run the forward with state_grad=True")
         st = []
         Np = ops.round_up(T * B, 64)
         for l, p in enumerate(self.packed):
@@ -646,6 +700,8 @@ class LstmStack:
                            db_p=self._accum(l, dev)[2],
                            dh=torch.empty((T, B, u), device=dev) if (keep_prob < 1.0 and not (persist and ctx[l].get("mask") is not None)) else None,
                            ws=ops.lstm_seq_bwd_workspace(B, u, dev)))
+            if need_dstate and ctx[l].get("c0") is not None:
+                st[-1]["dh0"], st[-1]["dc0"] = torch.empty((B, u), device=dev), torch.empty((B, u), device=dev)
             if l < L - 1 and not persist:
                 dyl[l] = torch.empty((T, B, u), device=dev)
         lane_of = lambda l: lanes[L - 1 - l] if piped else main          # the top layer leads, on the current stream
@@ -679,8 +735,8 @@ class LstmStack:
                         dh = s_["dh"]
                     else:
                         dh = dyl[l]
-                    ops.lstm_seq_bwd(dh, p["wh_p"], cx["gates"], cx["c"], cx["c0"], s_["dz"], s_["dzc"], None, None, t0, t1, s_["ws"],
-                                     s_["dzT"], s_["db_p"])
+                    ops.lstm_seq_bwd(dh, p["wh_p"], cx["gates"], cx["c"], cx["c0"], s_["dz"], s_["dzc"], s_.get("dh0") if t0 == 0 else None,
+                                     s_.get("dc0") if t0 == 0 else None, t0, t1, s_["ws"], s_["dzT"], s_["db_p"])
                     if l > 0:
                         ops.gemm_tn(s_["dzc"][t0:t1].view((t1 - t0) * B, -1), p["wx_p"], dyl[l - 1][t0:t1].view((t1 - t0) * B, -1))
                         if piped:
@@ -694,7 +750,10 @@ class LstmStack:
                 keep.append(self._weight_grads(l, ctx[l], st[l]["dzT"], st[l]["db_p"], T, B))
         for s in lanes[1:]:
             main.wait_stream(s)
-        return self._input_grad(st[0]["dzT"], T, B) if need_dx else None
+        dx = self._input_grad(st[0]["dzT"], T, B) if need_dx else None
+        if need_dstate:
+            return dx, [(s_["dc0"], s_["dh0"]) if "dc0" in s_ else None for s_ in st]
+        return dx
 
     def _input_grad(self, dzT0, T, B, dz=None):
         """Gradient wrt the stack's inputs, f32 [T,B,n_in] = dz_0 . Wx_0^T (only the feedback modes consume it: the feedback vector is part of
@@ -827,8 +886,9 @@ class RnnEstimator(Generator):
     """models/generators/rnn_estimator.py:39-323."""
 
     def __init__(self, num_dims, num_hidden, num_hidden_rnn, keep_prob=1.0, internal_bias=True, name="rnn-rbm", track_name="all",
-                 num_inputs=None, precision="bf16", seed=23, device=None, clip_norm=5.0):
+                 num_inputs=None, precision="bf16", seed=23, device=None, clip_norm=5.0, learn_zero_state=False):
         super().__init__(num_dims, num_hidden, num_hidden_rnn, keep_prob, internal_bias, name, track_name)
+        self.learn_zero_state = bool(learn_zero_state)  # rnn.py:139-143: every window / intro pass starts from a trained (c0, tanh c0) instead of zeros
         self.dtype = _compute_dtype(precision)
         self.seed, self.clip_norm = seed, clip_norm
         self.row0 = 0                     # global index of this rank's first sequence (data parallel)
@@ -846,7 +906,7 @@ class RnnEstimator(Generator):
 
     # -- construction ---------------------------------------------------------------------------
     def _init_rnn(self):
-        self._rnn = RNN(num_units=self.num_hidden_rnn, keep_prob=self.keep_prob)
+        self._rnn = RNN(num_units=self.num_hidden_rnn, keep_prob=self.keep_prob, learn_zero_state=self.learn_zero_state)
 
     @abc.abstractmethod
     def _init_estimator(self):
@@ -866,6 +926,25 @@ class RnnEstimator(Generator):
 
     def _get_rnn_zero_state(self, batch_size):
         return self._rnn.zero_state(batch_size, self.dtype)
+
+    def _state0(self, B, dtype=None):
+        """Initial LSTM state of a window / an intro pass: None (the kernels' zero state) or, with learn_zero_state, [(c0, tanh c0)] tiled over
+        the B rows -- formed on the device at every call, so a captured step follows c0 as the optimiser moves it."""
+        if not self.learn_zero_state:
+            return None
+        return list(self._rnn.zero_state(B, self.dtype if dtype is None else dtype))
+
+    def _lstm_backward_co(self, dy, cx):
+        """The stack's backward of a built window (cx: the build's context) -- and, with learn_zero_state, the chain rule of zero_state into
+        the c0 gradients, in front of _unscale like every other gradient."""
+        T, B = cx["T"], cx["B"]
+        need = self.learn_zero_state
+        r = yield from self._stack.backward_co(dy.view(T, B, -1), cx["lstm"], cx["kp"], self.seed, self.row0, need_dx=self.need_dx,
+                                               step_dev=self.store.step_dev, need_dstate=need)
+        if need:
+            r, dstate = r
+            self._rnn.zero_state_grad(dstate)
+        return r
 
     def _ensure_packed(self):
         if self._packed_step != self.store.step or self._stack.packed is None:
@@ -923,7 +1002,7 @@ class RnnEstimator(Generator):
             if inputs.dim() == 2:
                 inputs = inputs[:, None, :]
             x = inputs if inputs.dtype in (torch.uint8, torch.float32) else inputs.float()
-            st = None if initial_state is None else [(c, h) for c, h in initial_state.rnn_state]
+            st = self._state0(x.shape[0], torch.float32) if initial_state is None else [(c, h) for c, h in initial_state.rnn_state]
             h = None
             for t in range(x.shape[1]):
                 h, st = self._stack.det_step(x[:, t], st)
@@ -1285,7 +1364,8 @@ class RnnNade(RnnEstimator):
         N, dev = T * B, x_tm.device
         self._ensure_packed()
         kp = self._rnn.effective_keep_prob()
-        y, ctx, _ = yield from self._stack.forward_co(x_tm, kp, self.seed, self.row0, save=train, step_dev=self.store.step_dev)
+        y, ctx, _ = yield from self._stack.forward_co(x_tm, kp, self.seed, self.row0, save=train, state0=self._state0(B),
+                                                      step_dev=self.store.step_dev, state_grad=train)
         if ctx and x_tmT is not None:
             ctx[0]["inT"] = x_tmT
         nrows = None
@@ -1444,8 +1524,7 @@ class RnnNade(RnnEstimator):
         if compact is not None:                                     # back into time-major order for the LSTM backward (padding rows: 0)
             dy_c, dy = dy, torch.empty((N, R), device=dev)
             ops.rows_scatter_f32(dy_c, compact["inv"], compact["hdr"], dy)
-        self._dx = yield from self._stack.backward_co(dy.view(T, B, R), cx["lstm"], cx["kp"], cx["seed"], self.row0, need_dx=self.need_dx,
-                                                      step_dev=self.store.step_dev)
+        self._dx = yield from self._lstm_backward_co(dy, cx)
         self._unscale(cx.get("ls", 1.0))
 
     def train_step(self, x_u8, lengths, optimizer, lr=None):
@@ -1462,6 +1541,8 @@ class RnnNade(RnnEstimator):
         stack = getattr(self, "_stack", None)
         if stack is None or stack.packed is None or not (stack._persist(B, T) or stack._rowpar(B, T)):
             return False
+        if self.learn_zero_state and not stack._rowpar_state0(B, T):
+            return False                    # a learned start off the resident / cluster kernels trains on the launch-per-timestep path, eagerly
         return not ragged or (self.ragged_compact and self.dtype in ops.H16 and self.num_tracks == 1)
 
     def graphed_train_step(self, x_u8, optimizer, lr=None, warmup=2, lengths=None):
@@ -1542,7 +1623,7 @@ class RnnNade(RnnEstimator):
             inputs = inputs[:, None, :]
         B, T, _ = inputs.shape
         x_tm = self._to_time_major_inputs(inputs)
-        st0 = [(c, h) for c, h in initial_state.rnn_state] if initial_state is not None else None
+        st0 = [(c, h) for c, h in initial_state.rnn_state] if initial_state is not None else self._state0(B)
         y, _, final = self._stack.forward(x_tm, self._rnn.effective_keep_prob(), self.seed, self.row0, save=False, state0=st0)
         if last_outputs:
             out = self._dense(y[-1].contiguous())
@@ -1559,7 +1640,8 @@ class RnnNade(RnnEstimator):
         pre = self._rnn.prefix
         layers = [(self.store[f"{pre}/cell_{l}/kernel"], self.store[f"{pre}/cell_{l}/bias"]) for l in range(len(self._rnn.num_units))]
         return ops.generate_scan(x.contiguous(), num_steps, layers, self.store["dense/kernel"], self._det_fc_bias(), self.num_tracks, self.num_dims,
-                                 self.num_hidden[-1], self.store["nade/w_enc"], self.store["nade/w_dec"], 1.0, self.seed, self.row0, given=given)
+                                 self.num_hidden[-1], self.store["nade/w_enc"], self.store["nade/w_dec"], 1.0, self.seed, self.row0, given=given,
+                                 state0=self._state0(x.shape[0], torch.float32))      # (learn_zero_state: tiled on the device here, an input array of the scan)
 
     def _det_fc_bias(self):
         if not self.internal_bias:
@@ -1686,7 +1768,8 @@ class RnnRBM(RnnEstimator):
             rw = self._row_weight(lengths, B, T, dev)
             kp = self._rnn.effective_keep_prob()
             seed = self.seed + self.store.step
-            yy, ctx, _ = yield from self._stack.forward_co(x_tm, kp, self.seed, self.row0, save=(mode == "train"), step_dev=self.store.step_dev)
+            yy, ctx, _ = yield from self._stack.forward_co(x_tm, kp, self.seed, self.row0, save=(mode == "train"), state0=self._state0(B),
+                                                           step_dev=self.store.step_dev, state_grad=(mode == "train"))
             out = self._biases(yy.view(N, -1))
             bh_t, bv_t = out[:, :Hn], out[:, Hn:Hn + D]
             # global flat row ids keep the Gibbs uniforms independent of the data-parallel split
@@ -1844,8 +1927,7 @@ class RnnRBM(RnnEstimator):
         ops.gemm_tn(yT, doT[Hn:Hn + D], g["Wuv"], accumulate=True, split_k=LstmStack._split_k(R, D, Np8))
         dy = torch.empty((N, R), device=dev)
         ops.gemm_tn(do_c, self._wu_p, dy)
-        self._dx = yield from self._stack.backward_co(dy.view(T, B, R), cx["lstm"], cx["kp"], self.seed, self.row0, need_dx=self.need_dx,
-                                                      step_dev=self.store.step_dev)
+        self._dx = yield from self._lstm_backward_co(dy, cx)
         self._unscale(ls)
 
     def zero_state(self, batch_size):
@@ -1862,7 +1944,7 @@ class RnnRBM(RnnEstimator):
             inputs = inputs[:, None, :]
         B, T, _ = inputs.shape
         x_tm = self._to_time_major_inputs(inputs)
-        st0 = [(c, h) for c, h in initial_state.rnn_state] if initial_state is not None else None
+        st0 = [(c, h) for c, h in initial_state.rnn_state] if initial_state is not None else self._state0(B)
         y, _, final = self._stack.forward(x_tm, self._rnn.effective_keep_prob(), self.seed, self.row0, save=False, state0=st0)
         out = self._biases(y[-1].contiguous()) if last_outputs else self._biases(y.view(T * B, -1))[flat_index(lengths, B, T, inputs.device)]
         Hn, D = self.num_hidden[-1], self.num_dims

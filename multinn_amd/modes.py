@@ -126,7 +126,9 @@ class MultINNCore(Model):
         return {} if self._encoder_type == "Pass" else dict(seed=self.seed + 1000 + i, device=self.device)
 
     def _generator_kwargs(self, i=0):
-        return dict(precision=self.precision, seed=self.seed + i, device=self.device, clip_norm=self.clip_norm)
+        # params["generator"]["learn_zero_state"] (rnn.py:18-24): every generator starts its windows / intro passes from a trained state
+        return dict(precision=self.precision, seed=self.seed + i, device=self.device, clip_norm=self.clip_norm,
+                    learn_zero_state=bool(self._params["generator"].get("learn_zero_state", False)))
 
     @abc.abstractmethod
     def _init_encoders(self, encoder_class):
@@ -492,8 +494,12 @@ class MultINNCore(Model):
         """Whether the driver may train windows of this shape as replays of graphed_train_step (driver._captured_step), full-length or ragged:
         the modes whose captured step is tested (joint, jamming, composer), on one rank, once every generator's variables exist."""
         from .training import dp_active
-        return self._mode in ("joint", "jamming", "composer") and not dp_active() and \
-            all(getattr(g, "store", None) is not None and g.store.theta is not None for g in self._generators)
+        if not (self._mode in ("joint", "jamming", "composer") and not dp_active() and
+                all(getattr(g, "store", None) is not None and g.store.theta is not None for g in self._generators)):
+            return False
+        # a learned initial state off the resident / cluster kernels trains on the launch-per-timestep path, eagerly (RnnNade.capturable)
+        return all(not getattr(g, "learn_zero_state", False) or
+                   (g._stack.packed is not None and g._stack._rowpar_state0(shape[0], shape[1])) for g in self._generators)
 
     def build_pianoroll(self, x, lengths=None, is_train=False, mode="eval"):
         """The driver's evaluation entry (same name as RnnNade.build_pianoroll)."""
@@ -857,6 +863,10 @@ class MultINNFeedback(MultINNJamming):
     """multinn_feedback.py: jamming + a Dense feedback module over the stacked encodings of the step."""
 
     def __init__(self, config, params, name="MultINN-feedback", **kw):
+        if params["generator"].get("learn_zero_state", False):
+            # the feedback scans and the FeedbackRnn LSTM start from the zero state: refused here, before any device work
+            raise MnnUnsupported("generator.learn_zero_state is not supported by the feedback / feedback-rnn modes (their sampling scans and "
+                                 "the feedback LSTM start from the zero state); use the joint, jamming or composer mode")
         super().__init__(config, params, name=name, **kw)
         self._mode = "feedback"
         self._feedback_module = True

@@ -420,9 +420,18 @@ def lstm_resident_fwd(T, B, L, keep_prob):
     call("mnn_lstm_resident_fwd", _stream(), T, B, C.byref(L), float(keep_prob))
 
 
-def lstm_resident_bwd(T, B, L, keep_prob):
-    """L: descriptor of lstm2_bwd_layer, as for lstm_rowpar_bwd; no workspace."""
-    call("mnn_lstm_resident_bwd", _stream(), T, B, C.byref(L), float(keep_prob))
+def _dc0_ok(dc0, B, units):
+    _req(dc0.shape == (B, units) and dc0.dtype == torch.float32 and dc0.is_contiguous(), "lstm bwd: dc0 f32 [B,u]")
+
+
+def lstm_resident_bwd(T, B, L, keep_prob, dc0=None):
+    """L: descriptor of lstm2_bwd_layer, as for lstm_rowpar_bwd (its c0, when given, is the initial cell state); no workspace.
+    dc0 (optional f32 [B,u]) receives the gradient wrt the initial cell state."""
+    if dc0 is None:
+        call("mnn_lstm_resident_bwd", _stream(), T, B, C.byref(L), float(keep_prob))
+    else:
+        _dc0_ok(dc0, B, L.units)
+        call("mnn_lstm_resident_bwd_state", _stream(), T, B, C.byref(L), float(keep_prob), _ptr(dc0))
 
 
 def lstm_cluster_ok(B, units):
@@ -436,22 +445,35 @@ def lstm_cluster_bwd_ok(B, units):
     return bool(_lib.load().mnn_lstm_cluster_bwd_ok(int(B), int(units)))
 
 
-def lstm_recurrence_multi(kind, T, B, descs, keep_prob, wss=None):
+def lstm_recurrence_multi(kind, T, B, descs, keep_prob, wss=None, dc0s=None):
     """One launch for several independent layers of one shape (the per-track generators of the jamming mode).  kind: 'resident_fwd' |
     'resident_bwd' | 'cluster_fwd' | 'cluster_bwd'; descs: the layers' descriptors (lstm2_fwd_layer / lstm2_bwd_layer); wss: cluster forms: one
-    lstm_rowpar_workspace per job."""
+    lstm_rowpar_workspace per job; dc0s (backward kinds): per job an f32 [B,u] tensor for the gradient wrt the initial cell state, or None."""
     n = len(descs)
     _req(1 <= n <= 8, "lstm_recurrence_multi: 1..8 jobs")
     fwd = kind.endswith("fwd")
     arr = ((_lib.LstmFwdLayer if fwd else _lib.LstmBwdLayer) * n)(*descs)
+    dptr = None
+    if dc0s is not None and any(d is not None for d in dc0s):
+        _req(not fwd and len(dc0s) == n, "lstm_recurrence_multi: dc0s goes with a backward kind, one entry per job")
+        for d, L in zip(dc0s, descs):
+            if d is not None:
+                _dc0_ok(d, B, L.units)
+        dptr = (C.c_void_p * n)(*[_p0(d) for d in dc0s])
     if kind.startswith("resident"):
-        call("mnn_lstm_resident_%s_multi" % ("fwd" if fwd else "bwd"), _stream(), T, B, n, arr, float(keep_prob))
+        if dptr is not None:
+            call("mnn_lstm_resident_bwd_state_multi", _stream(), T, B, n, arr, float(keep_prob), dptr)
+        else:
+            call("mnn_lstm_resident_%s_multi" % ("fwd" if fwd else "bwd"), _stream(), T, B, n, arr, float(keep_prob))
     else:
         _req(wss is not None and len(wss) == n, "lstm_recurrence_multi: one workspace per job")
         for ws, d in zip(wss, descs):
             _rp_ws_ok(ws, T, B, d.units)
         ptrs = (C.c_void_p * n)(*[ws.data_ptr() for ws in wss])
-        call("mnn_lstm_cluster_%s_multi" % ("fwd" if fwd else "bwd"), _stream(), T, B, n, arr, float(keep_prob), ptrs)
+        if dptr is not None:
+            call("mnn_lstm_cluster_bwd_state_multi", _stream(), T, B, n, arr, float(keep_prob), ptrs, dptr)
+        else:
+            call("mnn_lstm_cluster_%s_multi" % ("fwd" if fwd else "bwd"), _stream(), T, B, n, arr, float(keep_prob), ptrs)
     return arr            # (keeps the by-value copies alive until the call has returned)
 
 
@@ -465,10 +487,15 @@ def lstm_cluster_fwd(T, B, L, keep_prob, ws):
     call("mnn_lstm_cluster_fwd", _stream(), T, B, C.byref(L), float(keep_prob), _ptr(ws))
 
 
-def lstm_cluster_bwd(T, B, L, keep_prob, ws):
-    """L: descriptor of lstm2_bwd_layer, as for lstm_rowpar_bwd; ws: the tensor of lstm_rowpar_workspace(T, B, 512); T >= 4."""
+def lstm_cluster_bwd(T, B, L, keep_prob, ws, dc0=None):
+    """L: descriptor of lstm2_bwd_layer, as for lstm_rowpar_bwd (its c0, when given, is the initial cell state); ws: the tensor of
+    lstm_rowpar_workspace(T, B, 512); T >= 4.  dc0 (optional f32 [B,u]) receives the gradient wrt the initial cell state."""
     _rp_ws_ok(ws, T, B, L.units)
-    call("mnn_lstm_cluster_bwd", _stream(), T, B, C.byref(L), float(keep_prob), _ptr(ws))
+    if dc0 is None:
+        call("mnn_lstm_cluster_bwd", _stream(), T, B, C.byref(L), float(keep_prob), _ptr(ws))
+    else:
+        _dc0_ok(dc0, B, L.units)
+        call("mnn_lstm_cluster_bwd_state", _stream(), T, B, C.byref(L), float(keep_prob), _ptr(ws), _ptr(dc0))
 
 
 def lstm_rowpar_check(ws):
@@ -1010,10 +1037,10 @@ def det_dense_pack(W, out=None):
     return out
 
 
-def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, given=None):
+def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, given=None, state0=None):
     """mnn_generate_scan: the whole sampling scan of an LSTM-(Multi)NADE generator in one call.  intro u8 [B, Ti, tracks * D]; layers = [(W, bias)]
     f32 master weights; returns samples u8 [B, num_steps, tracks * D].  given (optional): codes u8 [B, num_steps, tracks * D] in the layout of
-    the samples (see nade_sample)."""
+    the samples (see nade_sample).  state0 (optional, mnn_generate_scan_state): [(c0, h0) f32 [B, u]] per layer, the state the intro pass starts from."""
     _req(intro.dtype == torch.uint8 and intro.dim() == 3 and intro.is_contiguous() and intro.shape[2] == tracks * D, "generate_scan: intro u8 [B, Ti, tracks * D]")
     B, Ti, n_in = intro.shape
     n_out = tracks * (Hn + D)
@@ -1036,7 +1063,18 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
     ws = torch.empty(need + 256, dtype=torch.uint8, device=intro.device)
     off = (-ws.data_ptr()) % 256
     samples = torch.empty((B, int(num_steps), n_in), dtype=torch.uint8, device=intro.device)
-    call("mnn_generate_scan", _stream(), B, Ti, int(num_steps), _ptr(intro), n_in, len(layers), arr, _ptr(dense_W), _ptr(dense_bias), n_out, tracks, D, Hn,
-         _ptr(w_enc), _ptr(w_dec), float(-1.0 if temperature is None else temperature), int(seed), int(row0), _ptr(samples),
-         C.c_void_p(ws.data_ptr() + off), need, _ptr(given))
+    args = (_stream(), B, Ti, int(num_steps), _ptr(intro), n_in, len(layers), arr, _ptr(dense_W), _ptr(dense_bias), n_out, tracks, D, Hn,
+            _ptr(w_enc), _ptr(w_dec), float(-1.0 if temperature is None else temperature), int(seed), int(row0), _ptr(samples),
+            C.c_void_p(ws.data_ptr() + off), need, _ptr(given))
+    if state0 is None:
+        call("mnn_generate_scan", *args)
+    else:
+        _req(len(state0) == len(layers), "generate_scan: one (c0, h0) per layer")
+        for (c0, h0), a in zip(state0, arr):
+            for t in (c0, h0):
+                _req(t.dtype == torch.float32 and tuple(t.shape) == (B, a.units) and t.is_contiguous() and t.device == intro.device,
+                     "generate_scan: state0 entries f32 [B, u], contiguous")
+        cp = (C.c_void_p * len(layers))(*[c0.data_ptr() for c0, _ in state0])
+        hp = (C.c_void_p * len(layers))(*[h0.data_ptr() for _, h0 in state0])
+        call("mnn_generate_scan_state", *args, cp, hp)
     return samples                          # (the workspace returns to the allocator in stream order: later users are behind the scan)
