@@ -435,6 +435,39 @@ int mnn_rbm_visible(mnn_stream_t s, int N, int D, int Hn, const void* h, int h_d
                     void* workspace);
 int mnn_rbm_free_energy(mnn_stream_t s, int N, int D, int Hn, const uint8_t* v, const float* W, const float* bh, int ld_bh,
                         const float* bv, int ld_bv, float* F, float* p_h /* optional f32 [N, Hn]: sigmoid(v W + bh), = -dF/dz, for the backward pass */);
+/* Grouped launches: the chains / free energies of 1..8 RBMs of one shape (the per-track RBMs of a composer-mode LSTM-RBM) in ONE launch,
+ * the grid gaining a job dimension.  The job tables are host arrays, copied by value into the kernel arguments.
+ * mnn_rbm_gibbs_multi: per job W [D,Hn], bh / bv (pointers into one shared Dense-output block: rows of ld_bh / ld_bv floats, 0 = one
+ *   broadcast row), seed, v0, p_v (optional), v_out (optional), given (optional: set on every job or on none).  Cell (n, d) of v0 / p_v /
+ *   v_out lies at n * row_stride + d * elem_stride elements (elem_stride = M addresses track m of a composer-layout row, feature d * M + m,
+ *   in place; elem_stride = 1 with row_stride = D are contiguous planes), of the codes at n * given_row_stride + d * elem_stride.
+ *   seed_step (NULL allowed) is mnn_rbm_gibbs_stepped's: effective seed = job seed + *seed_step.  Forms and dispatch are mnn_rbm_gibbs's
+ *   (W resident in LDS with two rows per workgroup below 2048 rows, the matrix-core chain above, the streaming chain where neither fits).
+ *   INVARIANT: every job's p_v / v_out equal, bit for bit, what mnn_rbm_gibbs (mnn_rbm_gibbs_stepped with seed_step) returns for that job
+ *   alone on contiguous copies.  workspace: njobs * mnn_rbm_workspace_bytes(D, Hn).
+ * mnn_rbm_free_energy_multi: per job v u8 [N,D], W, bh, bv, F f32 [N], p_h (optional f32 [N,Hn]); the values of mnn_rbm_free_energy. */
+typedef struct {
+    const float* W;
+    const float* bh;
+    const float* bv;
+    uint64_t seed;
+    const uint8_t* v0;
+    float* p_v;
+    uint8_t* v_out;
+    const uint8_t* given;
+} mnn_rbm_gibbs_job;
+int mnn_rbm_gibbs_multi(mnn_stream_t s, int njobs, const mnn_rbm_gibbs_job* jobs, int N, int D, int Hn, int k, int ld_bh, int ld_bv,
+                        uint32_t row0, const uint32_t* row_ids, uint32_t sub0, const int* seed_step, long row_stride, int elem_stride,
+                        long given_row_stride, void* workspace);
+typedef struct {
+    const uint8_t* v;
+    const float* W;
+    const float* bh;
+    const float* bv;
+    float* F;
+    float* p_h;
+} mnn_rbm_free_energy_job;
+int mnn_rbm_free_energy_multi(mnn_stream_t s, int njobs, const mnn_rbm_free_energy_job* jobs, int N, int D, int Hn, int ld_bh, int ld_bv);
 /* CD-k bias deltas (rbm.py:318-327): dbv[d] += scale * sum_n (v - p_v)[n,d], dbh[j] += scale * sum_n (h - p_h)[n,j] (f32 atomics: zero
  * the outputs first).  The weight delta is two mnn_gemm_tn products combined by mnn_axpby_f32, which is also the `assign_add` of
  * rbm.py:329-333: out[i] = a*x[i] + b*y[i] (out may alias x or y; y may be NULL when b == 0).  Under data parallelism the flat

@@ -3,13 +3,13 @@
 Host API mirrors ilya16/MultINN's Encoder/Generator plugin classes; compute is hand-written HIP
 behind the C ABI in include/multinn_hip.h (libmultinn_hip.so).  No CPU fallback.
 """
-__all__ = ["RnnNade", "RnnMultiNADE", "RnnRBM", "PassEncoder", "DBNEncoder", "NADE", "RBM", "RNN", "DBN",
+__all__ = ["RnnNade", "RnnMultiNADE", "RnnMultiRBM", "RnnRBM", "PassEncoder", "DBNEncoder", "NADE", "RBM", "RNN", "DBN",
            "AdamOptimizer", "GradientDescentOptimizer", "MultINN", "MultINNJoint", "MultINNComposer", "MultINNJamming",
            "MultINNFeedback", "MultINNFeedbackRnn"]
 
 
 def __getattr__(name):
-    if name in ("RnnNade", "RnnMultiNADE", "RnnRBM", "RnnEstimatorStateTuple", "Generator", "RnnEstimator"):
+    if name in ("RnnNade", "RnnMultiNADE", "RnnMultiRBM", "RnnRBM", "RnnEstimatorStateTuple", "Generator", "RnnEstimator"):
         from . import generators
         return getattr(generators, name)
     if name in ("PassEncoder", "DBNEncoder", "Encoder"):

@@ -83,6 +83,16 @@ class NadeSampleJob(C.Structure):
     _fields_ = [("bias", _p), ("ld_bias", _i), ("w_enc", _p), ("w_dec", _p), ("seed", _u64), ("samples", _p), ("nll", _p), ("given", _p)]
 
 
+class RbmGibbsJob(C.Structure):
+    """mnn_rbm_gibbs_job (include/multinn_hip.h)."""
+    _fields_ = [("W", _p), ("bh", _p), ("bv", _p), ("seed", _u64), ("v0", _p), ("p_v", _p), ("v_out", _p), ("given", _p)]
+
+
+class RbmFreeEnergyJob(C.Structure):
+    """mnn_rbm_free_energy_job (include/multinn_hip.h)."""
+    _fields_ = [("v", _p), ("W", _p), ("bh", _p), ("bv", _p), ("F", _p), ("p_h", _p)]
+
+
 class ScanLstmLayer(C.Structure):
     """mnn_scan_lstm_layer (include/multinn_hip.h)."""
     _fields_ = [("W", _p), ("bias", _p), ("units", _i)]
@@ -148,6 +158,8 @@ SIGNATURES["mnn_rbm_visible_bias_init"] = (_i, [_p, _i, _p, _f, _p])
 SIGNATURES["mnn_sigmoid_grad_f32"] = (_i, [_p, _l, _p, _p, _p])
 SIGNATURES["mnn_rbm_ais_workspace_bytes"] = (_sz, [_i, _i, _i, _i, _i])
 SIGNATURES["mnn_rbm_ais"] = (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _u64, _u32, _p, _p, _p, _p, _p, _p])
+SIGNATURES["mnn_rbm_gibbs_multi"] = (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _u32, _p, _u32, _p, _l, _i, _l, _p])
+SIGNATURES["mnn_rbm_free_energy_multi"] = (_i, [_p, _i, _p, _i, _i, _i, _i, _i])
 SIGNATURES["mnn_rbm_cd_rows"] = (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p])
 SIGNATURES["mnn_probe_sigmoid"] = (_i, [_p, _i, _i, _p])
 SIGNATURES["mnn_axpby_f32"] = (_i, [_p, _l, _f, _p, _f, _p, _p])

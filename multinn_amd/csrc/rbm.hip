@@ -6,58 +6,7 @@
 // copy serves the visible half-step), each thread accumulates RBM_R rows of one output unit.
 // Summation order is ascending input index with one fma per term, and the sigmoid uses IEEE ops
 // only, so Bernoulli draws are bit-identical to oracle/det_ref.c.
-#include "common.h"
-
-#define RBM_R 8
-
-__device__ __forceinline__ uint32_t rbm_rowid(const uint32_t* __restrict__ row_ids, uint32_t row0, int n) {
-    return row_ids != nullptr ? row_ids[n] : row0 + (uint32_t)n;
-}
-
-// out-unit phase: for each output unit `o` (strided over threads) and each of the block's rows
-//   z[r] = sum_{k asc} in[r][k] * Wk[k*ldw + o]  + bias[row r][o]
-// in_s: LDS [RBM_R][Kpad] f32 (Kpad multiple of 4, zero padded).  Calls fn(r, o, z).
-// The bias rows bias[(n0 + r) * ld_bias + o] (ld_bias = 0: one shared row) are REQUESTED in front of the K loop and added behind it; the
-// weights come 16 k at a time, unconditionally (k clamped: the inputs are zero past K, so the clamped weight contributes fma(0, w, acc) = acc
-// exactly -- same ascending fma chain, bit for bit).  Round 3: with `k < K ? load : 0` per weight and the bias loaded inside the per-row
-// callback every load was waited for on its own (s_waitcnt vmcnt(0) per element: 4 + 8 memory round trips per 4 k).
-template <typename F>
-__device__ __forceinline__ void rbm_phase(const float* __restrict__ in_s, int Kpad, int K, const float* __restrict__ Wk, int ldw, int n_out,
-                                          const float* __restrict__ bias, int ld_bias, int n0, int N, F&& fn) {
-    for (int o = threadIdx.x; o < n_out; o += blockDim.x) {
-        float acc[RBM_R], bb[RBM_R];
-#pragma unroll
-        for (int r = 0; r < RBM_R; ++r) { acc[r] = 0.f; bb[r] = bias[(size_t)min(n0 + r, N - 1) * ld_bias + o]; }
-        for (int k0 = 0; k0 < K; k0 += 16) {
-            float w[16];
-#pragma unroll
-            for (int kk = 0; kk < 16; ++kk) w[kk] = Wk[(size_t)min(k0 + kk, K - 1) * ldw + o];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (k0 + 4 * q < K) {                       // block-uniform; Kpad covers the quad
-#pragma unroll
-                    for (int r = 0; r < RBM_R; ++r) {
-                        const float4 x = *reinterpret_cast<const float4*>(in_s + r * Kpad + k0 + 4 * q);
-                        acc[r] = fmaf(x.x, w[4 * q + 0], acc[r]);
-                        acc[r] = fmaf(x.y, w[4 * q + 1], acc[r]);
-                        acc[r] = fmaf(x.z, w[4 * q + 2], acc[r]);
-                        acc[r] = fmaf(x.w, w[4 * q + 3], acc[r]);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < RBM_R; ++r) fn(r, o, acc[r] + bb[r]);
-    }
-}
-
-template <typename TV>
-__device__ __forceinline__ void rbm_load_rows(const TV* __restrict__ src, int N, int n0, int K, int Kpad, float* __restrict__ dst_s) {
-    for (int e = threadIdx.x; e < RBM_R * Kpad; e += blockDim.x) {
-        const int r = e / Kpad, k = e % Kpad, n = n0 + r;
-        dst_s[e] = (n < N && k < K) ? (float)src[(size_t)n * K + k] : 0.f;
-    }
-}
+#include "rbm_chain.h"      // the chain / free-energy bodies (shared with the grouped launches of rbm_multi.hip), RBM_R, rbm_phase, the matrix-core helpers
 
 // ----------------------------------------------------------------------------------------------
 // k-step Gibbs chain (rbm.py:192-231)
@@ -67,7 +16,6 @@ __device__ __forceinline__ void rbm_load_rows(const TV* __restrict__ src, int N,
 // visible phase a clamped cell keeps its code and leaves its uniform unused, a free cell draws from the uniform it draws unconditioned (the
 // counters are per cell: nothing shifts).  p_v is sigmoid(logit) at every cell, clamped ones included.
 // ----------------------------------------------------------------------------------------------
-#define RBM_GIVEN_FREE 255
 
 // The codes of a clamped chain, from the trailing kernel arguments (const uint8_t* given, int ld_given).  The free chain's kernels are the
 // instantiations with NO trailing arguments: their parameter lists -- and with them the kernarg offsets of the implicit arguments they read
@@ -89,60 +37,8 @@ rbm_gibbs_kernel(int N, int D, int Hn, int k, const uint8_t* __restrict__ v0, co
     const GibbsCodes gc(codes...);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (seed_step != nullptr) seed += (uint64_t)(int64_t)*seed_step;      // step counter on the device: a captured launch draws anew every replay
-    const int Dp = (D + 3) & ~3, Hp = (Hn + 3) & ~3;
-    float* vs = smem;                 // [RBM_R][Dp]
-    float* hs = smem + RBM_R * Dp;    // [RBM_R][Hp]
-    uint8_t* cs = reinterpret_cast<uint8_t*>(hs + RBM_R * Hp);      // GIVEN: the rows' codes [RBM_R][Dp]
-    const int n0 = blockIdx.x * RBM_R;
-    rbm_load_rows<uint8_t>(v0, N, n0, D, Dp, vs);
-    if (GIVEN)                        // the same cells per thread as rbm_load_rows: no barrier in between
-        for (int e = threadIdx.x; e < RBM_R * Dp; e += blockDim.x) {
-            const int r = e / Dp, d = e % Dp, n = n0 + r;
-            const uint8_t c = (n < N && d < D) ? gc.p[(size_t)n * gc.ld + d] : (uint8_t)RBM_GIVEN_FREE;
-            cs[e] = c;
-            if (c != RBM_GIVEN_FREE) vs[e] = (float)c;
-        }
-    for (int e = threadIdx.x; e < RBM_R * Hp; e += blockDim.x) hs[e] = 0.f;
-    __syncthreads();
-    if (k == 0) {                     // tf.while_loop with zero iterations returns (v, v)
-        for (int e = threadIdx.x; e < RBM_R * D; e += blockDim.x) {
-            const int r = e / D, d = e % D, n = n0 + r;
-            if (n < N) {
-                if (p_v) p_v[(size_t)n * D + d] = vs[r * Dp + d];
-                if (v_out) v_out[(size_t)n * D + d] = (uint8_t)vs[r * Dp + d];
-            }
-        }
-        return;
-    }
-    for (int it = 0; it < k; ++it) {
-        rbm_phase(vs, Dp, D, W, Hn, Hn, bh, ld_bh, n0, N, [&](int r, int j, float z) {
-            const int n = n0 + r;
-            if (n >= N) return;
-            const float p = det_sigmoid(z);
-            const float u = philox_uniform1(seed, MNN_STREAM_RBM_H, rbm_rowid(row_ids, row0, n), sub0 + (uint32_t)it, (uint32_t)j);
-            hs[r * Hp + j] = u < p ? 1.f : 0.f;
-        });
-        __syncthreads();
-        const bool last = it == k - 1;
-        rbm_phase(hs, Hp, Hn, Wt, D, D, bv, ld_bv, n0, N, [&](int r, int d, float z) {
-            const int n = n0 + r;
-            if (n >= N) return;
-            const float p = det_sigmoid(z);
-            float s;
-            if (GIVEN && cs[r * Dp + d] != RBM_GIVEN_FREE) {
-                s = (float)cs[r * Dp + d];
-            } else {
-                const float u = philox_uniform1(seed, MNN_STREAM_RBM_V, rbm_rowid(row_ids, row0, n), sub0 + (uint32_t)it, (uint32_t)d);
-                s = u < p ? 1.f : 0.f;
-            }
-            vs[r * Dp + d] = s;
-            if (last) {
-                if (p_v) p_v[(size_t)n * D + d] = p;
-                if (v_out) v_out[(size_t)n * D + d] = (uint8_t)s;
-            }
-        });
-        __syncthreads();
-    }
+    const GibbsView a{N, D, Hn, k, v0, W, Wt, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, gc.p, gc.ld, 0, 1};
+    rbm_gibbs_stream_body<GIVEN, false>(a, blockIdx.x * RBM_R, smem);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -154,33 +50,6 @@ rbm_gibbs_kernel(int N, int D, int Hn, int k, const uint8_t* __restrict__ v0, co
 // spare threads (visible phase at D = 88: two row groups).  Biases stay in registers over the chain.  Arithmetic and order are
 // the streaming kernel's: ascending-index fma chain from 0, + bias, det_sigmoid, Philox draw -- bit-identical draws.
 // ----------------------------------------------------------------------------------------------
-template <int R, int RG, typename F>      // RG rows per thread; thread t -> (row group t / n_out, output t % n_out)
-__device__ __forceinline__ void rbm_phase_lds(const float* __restrict__ in_s, int Kpad, int K, const float* __restrict__ Ws, int w_k_stride,
-                                              int w_o_stride, int n_out, F&& fn) {
-    const int g = threadIdx.x / n_out, o = threadIdx.x - g * n_out;
-    if (g >= R / RG) return;
-    const float* __restrict__ wp = Ws + (size_t)o * w_o_stride;
-    const float* __restrict__ xp = in_s + (size_t)g * RG * Kpad;
-    float acc[RG];
-#pragma unroll
-    for (int r = 0; r < RG; ++r) acc[r] = 0.f;
-    for (int k0 = 0; k0 < K; k0 += 4) {
-        float w[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) w[kk] = wp[(size_t)min(k0 + kk, K - 1) * w_k_stride];     // beyond K the input is the zero padding
-#pragma unroll
-        for (int r = 0; r < RG; ++r) {
-            const float4 x = *reinterpret_cast<const float4*>(xp + r * Kpad + k0);
-            acc[r] = fmaf(x.x, w[0], acc[r]);
-            acc[r] = fmaf(x.y, w[1], acc[r]);
-            acc[r] = fmaf(x.z, w[2], acc[r]);
-            acc[r] = fmaf(x.w, w[3], acc[r]);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < RG; ++r) fn(g * RG + r, r, o, acc[r]);
-}
-
 template <int R, int RGH, int RGV, typename... Codes>        // rows per thread in the hidden / visible phase (R / RG row groups of n_out threads each)
 __global__ void __launch_bounds__(256)
 rbm_gibbs_lds_kernel(int N, int D, int Hn, int k, const uint8_t* __restrict__ v0, const float* __restrict__ W, const float* __restrict__ bh,
@@ -190,87 +59,8 @@ rbm_gibbs_lds_kernel(int N, int D, int Hn, int k, const uint8_t* __restrict__ v0
     const GibbsCodes gc(codes...);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (seed_step != nullptr) seed += (uint64_t)(int64_t)*seed_step;
-    const int Dp = (D + 3) & ~3, Hp = (Hn + 3) & ~3, ldw = Hn + 1;
-    float* vs = smem;                 // [R][Dp]
-    float* hs = vs + R * Dp;          // [R][Hp]
-    float* Ws = hs + R * Hp;          // [D][ldw]
-    const int n0 = blockIdx.x * R;
-    for (int d = threadIdx.x >> 6; d < D; d += 4)            // one wave per row of W: coalesced, no index division
-        for (int j = threadIdx.x & 63; j < Hn; j += 64) Ws[d * ldw + j] = W[(size_t)d * Hn + j];
-    for (int e = threadIdx.x; e < R * Dp; e += blockDim.x) {
-        const int r = e / Dp, kx = e % Dp, n = n0 + r;
-        vs[e] = (n < N && kx < D) ? (float)v0[(size_t)n * D + kx] : 0.f;
-        if (GIVEN && n < N && kx < D) {
-            const uint8_t c = gc.p[(size_t)n * gc.ld + kx];
-            if (c != RBM_GIVEN_FREE) vs[e] = (float)c;
-        }
-    }
-    for (int e = threadIdx.x; e < R * Hp; e += blockDim.x) hs[e] = 0.f;
-    // this thread's biases, row ids (and GIVEN: codes of its visible cells): constant over the chain
-    float bhr[RGH], bvr[RGV];
-    uint32_t idh[RGH], idv[RGV], cvr[RGV];
-    {
-        const int g = threadIdx.x / Hn, o = threadIdx.x - g * Hn;
-#pragma unroll
-        for (int r = 0; r < RGH; ++r) {
-            const int n = min(n0 + g * RGH + r, N - 1);
-            bhr[r] = bh[(size_t)n * ld_bh + min(o, Hn - 1)];
-            idh[r] = rbm_rowid(row_ids, row0, n);
-        }
-    }
-    {
-        const int g = threadIdx.x / D, o = threadIdx.x - g * D;
-#pragma unroll
-        for (int r = 0; r < RGV; ++r) {
-            const int n = min(n0 + min(g * RGV + r, R - 1), N - 1);
-            bvr[r] = bv[(size_t)n * ld_bv + min(o, D - 1)];
-            idv[r] = rbm_rowid(row_ids, row0, n);
-            if (GIVEN) cvr[r] = gc.p[(size_t)n * gc.ld + min(o, D - 1)];
-        }
-    }
-    __syncthreads();
-    if (k == 0) {                     // tf.while_loop with zero iterations returns (v, v)
-        for (int e = threadIdx.x; e < R * D; e += blockDim.x) {
-            const int r = e / D, d = e % D, n = n0 + r;
-            if (n < N) {
-                if (p_v) p_v[(size_t)n * D + d] = vs[r * Dp + d];
-                if (v_out) v_out[(size_t)n * D + d] = (uint8_t)vs[r * Dp + d];
-            }
-        }
-        return;
-    }
-    for (int it = 0; it < k; ++it) {
-        rbm_phase_lds<R, RGH>(vs, Dp, D, Ws, ldw, 1, Hn, [&](int r, int rl, int j, float acc) {
-            if (n0 + r >= N) return;
-            const float p = det_sigmoid(acc + bhr[rl]);
-            const float u = philox_uniform1(seed, MNN_STREAM_RBM_H, idh[rl], sub0 + (uint32_t)it, (uint32_t)j);
-            hs[r * Hp + j] = u < p ? 1.f : 0.f;
-        });
-        __syncthreads();
-        const bool last = it == k - 1;
-        rbm_phase_lds<R, RGV>(hs, Hp, Hn, Ws, 1, ldw, D, [&](int r, int rl, int d, float acc) {
-            const int n = n0 + r;
-            if (n >= N) return;
-            const float p = det_sigmoid(acc + bvr[rl]);
-            float sv;
-            if (GIVEN && cvr[rl] != RBM_GIVEN_FREE) {        // clamped: no Philox evaluation
-                sv = (float)cvr[rl];
-            } else {
-                const float u = philox_uniform1(seed, MNN_STREAM_RBM_V, idv[rl], sub0 + (uint32_t)it, (uint32_t)d);
-                sv = u < p ? 1.f : 0.f;
-            }
-            vs[r * Dp + d] = sv;
-            if (last) {
-                if (p_v) p_v[(size_t)n * D + d] = p;
-                if (v_out) v_out[(size_t)n * D + d] = (uint8_t)sv;
-            }
-        });
-        __syncthreads();
-    }
-}
-
-static size_t rbm_lds_resident_bytes(int R, int D, int Hn) {
-    return ((size_t)R * (((D + 3) & ~3) + ((Hn + 3) & ~3)) + (size_t)D * (Hn + 1)) * sizeof(float);
+    const GibbsView a{N, D, Hn, k, v0, W, nullptr, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, gc.p, gc.ld, 0, 1};
+    rbm_gibbs_lds_body<R, RGH, RGV, GIVEN, false>(a, blockIdx.x * R, smem);
 }
 
 // Launch the resident-W form when it applies (both phases fit 256 threads, W fits LDS); false: the caller streams.
@@ -325,48 +115,12 @@ static bool try_gibbs_lds(hipStream_t st, int N, int D, int Hn, int k, const uin
 // evaluation.  Hidden phase: 2 row tiles x (Hn / 32) unit tiles, two unit tiles per wave share the state operand; visible phase:
 // 2 x ceil(D / 32) jobs on the first waves (one K = Hn chain per output: it cannot be split without changing the summation order).
 // ----------------------------------------------------------------------------------------------
-typedef float gm_f32x16 __attribute__((ext_vector_type(16)));
-#define GM_ROWS 64
-
 struct GibbsMfmaArgs {
     int N, D, Hn, k;
     const uint8_t* v0; const float* W; const float* bh; int ld_bh; const float* bv; int ld_bv;
     uint64_t seed; uint32_t row0; const uint32_t* row_ids; uint32_t sub0; float* p_v; uint8_t* v_out; const int* seed_step;
 };
 
-// pitch (bytes) of a byte-state row of `n` cells: covers n rounded up to even (the k pairs of the MFMA), a whole number of words, and an ODD
-// number of words (rows land in distinct banks)
-static __host__ __device__ __forceinline__ int gm_pitch(int n) { int w = (n + 1 + 3) / 4; return 4 * (w | 1); }
-
-// one output tile (32 units x 32 rows) of a phase: K ascending in pairs; A = W (unit, k) from LDS, B = the rows' byte states
-// (Reading the operands of eight k-pairs ahead of their MFMAs -- what the single-wave det-step kernels need -- was measured SLOWER here, 2.78 ->
-// 3.19 ms per jamming step: with two waves per SIMD the other wave's MFMA fills the LDS wait, and the batches cost 60 more registers.)
-template <bool VIS>
-__device__ __forceinline__ void gm_chain(const float* __restrict__ Ws, int ldw, const uint8_t* __restrict__ st, int pitch, int K, int unit,
-                                         int lane, gm_f32x16& acc) {
-    const int r = lane & 31, hh = lane >> 5;
-    const uint8_t* sp = st + r * pitch + hh;
-    // hidden phase: A[i = hidden j][k = d] = W[d][j] (walks down a column); visible phase: A[i = visible d][k = j] = W[d][j] (walks a row)
-    const float* ap = VIS ? Ws + (size_t)unit * ldw + hh : Ws + (size_t)hh * ldw + unit;
-    const int astep = VIS ? 2 : 2 * ldw;
-    for (int s = 0; s < K / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[(size_t)s * astep], (float)sp[2 * s], acc, 0, 0, 0);
-}
-
-// GIVEN helpers of the matrix-core chain: the codes of cells d0 .. d0 + 3 of one row packed into a word (cells past D repeat D - 1: never used),
-// and whether any of the four is free
-__device__ __forceinline__ uint32_t gm_code_quad(const uint8_t* __restrict__ given, int ld_given, int row, int d0, int D) {
-    uint32_t q = 0u;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) q |= (uint32_t)given[(size_t)row * ld_given + min(d0 + e, D - 1)] << (8 * e);
-    return q;
-}
-__device__ __forceinline__ bool gm_any_free(uint32_t q) {
-    return (q & 0xffu) == 0xffu || (q & 0xff00u) == 0xff00u || (q & 0xff0000u) == 0xff0000u || (q & 0xff000000u) == 0xff000000u;
-}
-
-// GIVEN: the codes clamp the byte states at load and after each visible quad; a lane's codes of its first-pass visible job stay in registers
-// (four packed words next to bvr: no LDS, so the given form fits wherever the free one does); a quad whose four cells are all clamped skips its
-// Philox block
 template <typename... Codes>
 __global__ void __launch_bounds__(512) rbm_gibbs_mfma_kernel(GibbsMfmaArgs A, Codes... codes) {
     constexpr bool GIVEN = sizeof...(Codes) != 0;
@@ -374,161 +128,13 @@ __global__ void __launch_bounds__(512) rbm_gibbs_mfma_kernel(GibbsMfmaArgs A, Co
     extern __shared__ __attribute__((aligned(16))) float smem[];
     uint64_t seed = A.seed;
     if (A.seed_step != nullptr) seed += (uint64_t)(int64_t)*A.seed_step;
-    const int N = A.N, D = A.D, Hn = A.Hn, ldw = Hn + 1;
-    const int De = (D + 1) & ~1, He = (Hn + 1) & ~1;          // K of the two phases (even; the states are zero past D / Hn)
-    const int pv = gm_pitch(D), ph = gm_pitch(Hn);
-    float* Ws = smem;                                         // [De][ldw] (row D, if any, repeats row D - 1: its inputs are zero)
-    uint8_t* vs = reinterpret_cast<uint8_t*>(Ws + (size_t)De * ldw);      // [64][pv]
-    uint8_t* hs = vs + GM_ROWS * pv;                                        // [64][ph]
-    const int n0 = blockIdx.x * GM_ROWS;
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (int d = w; d < De; d += 8)                          // one wave per row of W: coalesced
-        for (int j = lane; j < ldw; j += 64) Ws[d * ldw + j] = j < Hn ? A.W[(size_t)min(d, D - 1) * Hn + j] : 0.f;
-    {   // v0 rows: thread t -> row t >> 3, eight lanes walk its bytes, sixteen loads in flight (unconditional, clamped)
-        const int rr = threadIdx.x >> 3, sub = threadIdx.x & 7, n = n0 + rr;
-        const uint8_t* __restrict__ src = A.v0 + (size_t)min(n, N - 1) * D;
-        const uint8_t* __restrict__ gsrc = GIVEN ? gc.p + (size_t)min(n, N - 1) * gc.ld : nullptr;
-        for (int kb = sub; kb < pv; kb += 128) {
-            uint8_t v[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = src[min(kb + 8 * q, D - 1)];
-            if (GIVEN) {
-                uint8_t c[16];
-#pragma unroll
-                for (int q = 0; q < 16; ++q) c[q] = gsrc[min(kb + 8 * q, D - 1)];
-#pragma unroll
-                for (int q = 0; q < 16; ++q) v[q] = c[q] != RBM_GIVEN_FREE ? c[q] : v[q];
-            }
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                if (kb + 8 * q < pv) vs[rr * pv + kb + 8 * q] = (n < N && kb + 8 * q < D) ? v[q] : (uint8_t)0;
-        }
-    }
-    for (int e = threadIdx.x; e < GM_ROWS * ph; e += 512) hs[e] = 0;
-    const int r = lane & 31, hh = lane >> 5;
-    // jobs: hidden -- row tile w >> 2, unit tiles 2 (w & 3) + 8 q ... (two per pass, all Hn / 32 covered in ceil(Hn / 256) passes);
-    //       visible -- job id w (+ 8 per pass) = row tile * ndt + unit tile
-    const int nht = (Hn + 31) / 32, ndt = (D + 31) / 32;
-    const int rt_h = w >> 2;
-    const int row_h = n0 + 32 * rt_h + r;                     // the batch row of this lane's accumulator column (hidden jobs)
-    const uint32_t id_h = rbm_rowid(A.row_ids, A.row0, min(row_h, N - 1));
-    // the biases of this wave's first-pass jobs stay in registers over the chain (they do not change between Gibbs iterations; loaded inside
-    // the epilogue, every accumulator quad waited for its own L2 round trip in every iteration)
-    float bhr[2][16], bvr[16];
-    uint32_t cvr[4];                                          // GIVEN: the codes of the first-pass visible job, one quad per word
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int j = min(32 * (2 * (w & 3) + q) + (e & 3) + 8 * (e >> 2) + 4 * hh, Hn - 1);
-            bhr[q][e] = A.bh[(size_t)min(row_h, N - 1) * A.ld_bh + j];
-        }
-    {
-        const int job = min(w, 2 * ndt - 1), rt = job / ndt, dt = job - rt * ndt;
-        const int row = min(n0 + 32 * rt + r, N - 1);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) bvr[e] = A.bv[(size_t)row * A.ld_bv + min(32 * dt + (e & 3) + 8 * (e >> 2) + 4 * hh, D - 1)];
-        if (GIVEN)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) cvr[g4] = gm_code_quad(gc.p, gc.ld, row, 32 * dt + 8 * g4 + 4 * hh, D);
-    }
-    __syncthreads();
-    if (A.k == 0) {
-        for (int e = threadIdx.x; e < GM_ROWS * D; e += 512) {
-            const int rr = e / D, d = e - rr * D, n = n0 + rr;
-            if (n < N) {
-                if (A.p_v) A.p_v[(size_t)n * D + d] = (float)vs[rr * pv + d];
-                if (A.v_out) A.v_out[(size_t)n * D + d] = vs[rr * pv + d];
-            }
-        }
-        return;
-    }
-    for (int it = 0; it < A.k; ++it) {
-        // ---- hidden phase ----
-        for (int jt0 = 2 * (w & 3); jt0 < nht; jt0 += 8) {
-            gm_f32x16 acc[2];
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[q][e] = 0.f;
-            const uint8_t* sp = vs + (32 * rt_h + r) * pv + hh;
-            const int u0 = min(32 * jt0 + r, Hn - 1), u1 = min(32 * (jt0 + 1) + r, Hn - 1);
-            const float* a0 = Ws + (size_t)hh * ldw + u0;
-            const float* a1 = Ws + (size_t)hh * ldw + u1;
-            const bool two = jt0 + 1 < nht;
-            for (int s = 0; s < De / 2; ++s) {                // the two unit tiles share the state operand
-                const float b = (float)sp[2 * s];
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[(size_t)s * 2 * ldw], b, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[(size_t)s * 2 * ldw], b, acc[1], 0, 0, 0);      // (a lone last tile repeats column Hn - 1: discarded)
-            }
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                if (q == 1 && !two) break;
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    const int j0 = 32 * (jt0 + q) + 8 * g4 + 4 * hh;          // four consecutive hidden units: one Philox block
-                    if (j0 >= Hn) continue;
-                    float u[4];
-                    philox_uniform4(seed, MNN_STREAM_RBM_H, id_h, A.sub0 + (uint32_t)it, (uint32_t)(j0 >> 2), u);
-                    uint32_t pk = 0u;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int j = min(j0 + e, Hn - 1);
-                        const float bb = jt0 < 8 ? bhr[q][4 * g4 + e] : A.bh[(size_t)min(row_h, N - 1) * A.ld_bh + j];
-                        const float p = det_sigmoid(acc[q][4 * g4 + e] + bb);
-                        pk |= (u[e] < p && j0 + e < Hn ? 1u : 0u) << (8 * e);
-                    }
-                    *reinterpret_cast<uint32_t*>(hs + (32 * rt_h + r) * ph + j0) = pk;     // j0 % 4 == 0, ph % 4 == 0
-                }
-            }
-        }
-        __syncthreads();
-        // ---- visible phase ----
-        const bool last = it == A.k - 1;
-        for (int job = w; job < 2 * ndt; job += 8) {
-            const int rt = job / ndt, dt = job - rt * ndt;
-            gm_f32x16 acc;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-            gm_chain<true>(Ws, ldw, hs + 32 * rt * ph, ph, He, min(32 * dt + r, D - 1), lane, acc);
-            const int row = n0 + 32 * rt + r;
-            const uint32_t idv = rbm_rowid(A.row_ids, A.row0, min(row, N - 1));
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int d0 = 32 * dt + 8 * g4 + 4 * hh;
-                if (d0 >= D) continue;
-                float u[4];
-                uint32_t cq = 0xffffffffu;
-                if (GIVEN) cq = job < 8 ? cvr[g4] : gm_code_quad(gc.p, gc.ld, min(row, N - 1), d0, D);
-                if (!GIVEN || gm_any_free(cq)) philox_uniform4(seed, MNN_STREAM_RBM_V, idv, A.sub0 + (uint32_t)it, (uint32_t)(d0 >> 2), u);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int d = d0 + e;
-                    if (d >= D) continue;
-                    const float p = det_sigmoid(acc[4 * g4 + e] + (job < 8 ? bvr[4 * g4 + e] : A.bv[(size_t)min(row, N - 1) * A.ld_bv + d]));
-                    const uint8_t c = (uint8_t)(cq >> (8 * e));
-                    const uint8_t sv = GIVEN && c != RBM_GIVEN_FREE ? c : (u[e] < p ? 1 : 0);
-                    vs[(32 * rt + r) * pv + d] = sv;
-                    if (last && row < N) {
-                        if (A.p_v) A.p_v[(size_t)row * D + d] = p;
-                        if (A.v_out) A.v_out[(size_t)row * D + d] = sv;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-static size_t gibbs_mfma_lds_bytes(int D, int Hn) {
-    return (size_t)((D + 1) & ~1) * (Hn + 1) * sizeof(float) + (size_t)GM_ROWS * (gm_pitch(D) + gm_pitch(Hn));
+    const GibbsView a{A.N, A.D, A.Hn, A.k, A.v0, A.W, nullptr, A.bh, A.ld_bh, A.bv, A.ld_bv, seed, A.row0, A.row_ids, A.sub0, A.p_v, A.v_out, gc.p, gc.ld, 0, 1};
+    rbm_gibbs_mfma_body<GIVEN, false>(a, blockIdx.x * GM_ROWS, smem);
 }
 
 extern "C" size_t mnn_rbm_workspace_bytes(int D, int Hn) { return (size_t)D * Hn * sizeof(float); }
 
 extern "C" int mnn_transpose(mnn_stream_t s, const void* in, int in_dtype, int R, int C, int ld_in, void* out, int out_dtype, int ld_out);
-
-static size_t rbm_lds_bytes(int D, int Hn) { return (size_t)RBM_R * (((D + 3) & ~3) + ((Hn + 3) & ~3)) * sizeof(float); }
 
 // The dispatch of both entry points: the same form for a shape whether or not `given` is set (the clamped forms need no LDS beyond the free
 // ones' except the streaming kernel's codes, which no threshold looks at)
@@ -761,45 +367,13 @@ extern "C" int mnn_rbm_visible(mnn_stream_t s, int N, int D, int Hn, const void*
 // ----------------------------------------------------------------------------------------------
 // free energy, per row (rbm.py:256-258; R4):  F[n] = -sum_j softplus((vW)_j + bh[n,j]) - v.bv[n]
 // ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ float softplus_f(float z) { return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z))); }
 
 __global__ void __launch_bounds__(256)
 rbm_free_energy_kernel(int N, int D, int Hn, const uint8_t* __restrict__ v, const float* __restrict__ W, const float* __restrict__ bh, int ld_bh,
                        const float* __restrict__ bv, int ld_bv, float* __restrict__ F, float* __restrict__ p_h) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ float fsum[RBM_R];
-    const int Dp = (D + 3) & ~3;
-    const int n0 = blockIdx.x * RBM_R;
-    rbm_load_rows<uint8_t>(v, N, n0, D, Dp, smem);
-    if (threadIdx.x < RBM_R) fsum[threadIdx.x] = 0.f;
-    __syncthreads();
-    float part[RBM_R];
-#pragma unroll
-    for (int r = 0; r < RBM_R; ++r) part[r] = 0.f;
-    rbm_phase(smem, Dp, D, W, Hn, Hn, bh, ld_bh, n0, N, [&](int r, int j, float z) {
-        const int n = n0 + r;
-        if (n < N) {
-            part[r] -= softplus_f(z);
-            // d F / d z = -sigmoid(z): the backward pass's hidden activations, from the pre-activation this pass has anyway (the same
-            // det_sigmoid as mnn_rbm_hidden, so the gradient keeps its bits; saves that pass re-reading v and W and re-forming z)
-            if (p_h != nullptr) p_h[(size_t)n * Hn + j] = det_sigmoid(z);
-        }
-    });
-    for (int d = threadIdx.x; d < D; d += blockDim.x)
-#pragma unroll
-        for (int r = 0; r < RBM_R; ++r) {
-            const int n = n0 + r;
-            if (n < N) part[r] -= smem[r * Dp + d] * bv[(size_t)n * ld_bv + d];
-        }
-#pragma unroll
-    for (int r = 0; r < RBM_R; ++r) {
-        float x = part[r];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-        if ((threadIdx.x & 63) == 0) atomicAdd(&fsum[r], x);
-    }
-    __syncthreads();
-    if (threadIdx.x < RBM_R && n0 + threadIdx.x < N) F[n0 + threadIdx.x] = fsum[threadIdx.x];
+    __shared__ float fsum[4 * RBM_R];
+    rbm_free_energy_body(N, D, Hn, v, W, bh, ld_bh, bv, ld_bv, F, p_h, blockIdx.x * RBM_R, smem, fsum);
 }
 
 extern "C" int mnn_rbm_free_energy(mnn_stream_t s, int N, int D, int Hn, const uint8_t* v, const float* W, const float* bh, int ld_bh,

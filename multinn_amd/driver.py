@@ -277,6 +277,9 @@ def build_generator(params, P, M, precision="bf16", seed=23):
     if params.get("mode", "joint") != "joint" or (params.get("encoder") or {}).get("type", "Pass") != "Pass":
         raise ValueError("build_generator is the joint / PassEncoder shortcut: use build_model(config, params) for the other modes")
     g = params["generator"]
+    if g["type"] == "MultiRBM":
+        raise ValueError("generator type `MultiRBM` is the composer mode's (one shared LSTM, one RBM per track): use build_model(config, params) "
+                         "with mode: composer")
     cls = {"NADE": RnnNade, "RBM": RnnRBM}[g["type"]]
     return cls(P * M, g["num_hidden"], g["num_hidden_rnn"], keep_prob=params.get("keep_prob", 0.9), precision=precision, seed=seed,
                learn_zero_state=bool(g.get("learn_zero_state", False)))

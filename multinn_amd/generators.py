@@ -1947,8 +1947,12 @@ class RnnRBM(RnnEstimator):
         st0 = [(c, h) for c, h in initial_state.rnn_state] if initial_state is not None else self._state0(B)
         y, _, final = self._stack.forward(x_tm, self._rnn.effective_keep_prob(), self.seed, self.row0, save=False, state0=st0)
         out = self._biases(y[-1].contiguous()) if last_outputs else self._biases(y.view(T * B, -1))[flat_index(lengths, B, T, inputs.device)]
+        return self._state_from_out(out, tuple((c.clone(), h.clone()) for c, h in final))
+
+    def _state_from_out(self, out, rnn_state):
+        """The estimator state of a Dense output [B, ld] = [bh_t | bv_t] (views)."""
         Hn, D = self.num_hidden[-1], self.num_dims
-        return RnnEstimatorStateTuple(out[:, :Hn], out[:, Hn:Hn + D], tuple((c.clone(), h.clone()) for c, h in final))
+        return RnnEstimatorStateTuple(out[:, :Hn], out[:, Hn:Hn + D], rnn_state)
 
     def _det_state(self, h, rnn_state):
         """rnn_rbm.py:240-259 in the deterministic arithmetic: bh_t = rbm.bh + h . Wuh, bv_t = rbm.bv + h . Wuv (two jobs, one launch)."""
@@ -1968,9 +1972,7 @@ class RnnRBM(RnnEstimator):
         x = self._step_input(inputs.shape[0], inputs.device)
         ops.convert2d(inputs.contiguous(), x[:, :inputs.shape[1]])
         h, new = self._stack.single_step(x, [(c, hh) for c, hh in initial_state.rnn_state])
-        out = self._biases(h.contiguous())
-        Hn, D = self.num_hidden[-1], self.num_dims
-        return RnnEstimatorStateTuple(out[:, :Hn], out[:, Hn:Hn + D], tuple(new))
+        return self._state_from_out(self._biases(h.contiguous()), tuple(new))
 
     def sample_single(self, inputs, state, given=None):
         """rnn_rbm.py:283-297 with k = rbm.k (R1): returns (sample u8, cond_prob).  given (optional): codes u8 [B, D] (a step slice of
@@ -2000,4 +2002,305 @@ class RnnRBM(RnnEstimator):
         # pretrain() call, not after it, or the first update's visible-bias delta is overwritten
         init_ops, update_ops, self._cd_gradients = self._rbm.train(flat.contiguous(), lr, seed=self.seed + self.store.step, row0=self.row0 * T)
         self._packed_step = -1                          # rbm.bh / rbm.bv feed the packed bias row
+        return init_ops, update_ops, self.metrics, self.metrics_upd, self.summaries
+
+
+# ------------------------------------------------------------------------------------------------
+class RnnMultiRBM(RnnRBM):
+    """A shared-LSTM multi-track LSTM-RBM: one LSTM, one Dense (Wuh | Wuv), ``len(tracks)`` RBMs -- the structure of rnn_multinade.py with
+    the estimator of rnn_rbm.py (the reference stops at multinn_composer.py:44-45; it has no such model).
+
+    Inputs / targets are [B, T, M * D] in composer layout (feature d * M + m).  The Dense output of a step is
+    [bh_0 .. bh_{M-1} | bv_0 .. bv_{M-1}] (track-major blocks: RnnNade._build_biases' split order); track m runs a CD-k chain with seed
+    ``seed + m`` from its slice of the inputs, cost_m = F_m(target_m) - F_m(v_s,m).  The optimised loss, and `free_energy` /
+    `log_likelihood`, are the MEAN over the tracks of the per-track row-weighted values (rnn_multinade.py:199-203).  The M chains of a step
+    -- training's and every sampling step's -- are ONE grouped launch (ops.rbm_gibbs_multi), the free energies one per chain end
+    (ops.rbm_free_energy_multi)."""
+
+    def __init__(self, num_dims, num_hidden, num_hidden_rnn, tracks, keep_prob=1.0, internal_bias=True, k=10, name="rnn-multirbm",
+                 bias_mode="conditional", **kw):
+        self._tracks = list(tracks)
+        if not 1 <= len(self._tracks) <= ops.RBM_MULTI_MAX_JOBS:
+            raise ValueError(f"RnnMultiRBM takes 1..{ops.RBM_MULTI_MAX_JOBS} tracks (one grouped launch), got {len(self._tracks)}")
+        super().__init__(num_dims, num_hidden, num_hidden_rnn, keep_prob, internal_bias, k, name, "all", bias_mode, **kw)
+        self._num_output = self.num_tracks * self.num_dims
+        self._det_bias = None
+
+    tracks = property(lambda self: self._tracks)
+    num_tracks = property(lambda self: len(self._tracks))
+
+    def _init_estimator(self):
+        self._rbms = [RBM(self.num_dims, self.num_hidden[-1], k=self._k, name=f"rbm_{m}") for m in range(self.num_tracks)]
+        self._rbm = self._rbms[0]
+
+    def _declare(self, num_inputs):
+        """Variable order rbm_m [W, bv, bh] for every track, rnn, [Wuh, Wuv]; the columns of Wuh / Wuv are track-major."""
+        M, D, Hn, R = self.num_tracks, self.num_dims, self.num_hidden[-1], self.num_hidden_rnn[-1]
+        for m, r in enumerate(self._rbms):
+            r.declare(self.store, self._gen, prefix=f"rbm_{m}")
+        self._rnn.declare(self.store, num_inputs, self._gen)
+        self.store.declare("Wuh", (R, M * Hn), glorot_uniform(self._gen, R, M * Hn))
+        self.store.declare("Wuv", (R, M * D), glorot_uniform(self._gen, R, M * D))
+        self.n_out = M * (Hn + D)
+        self.ldo = ops.round_up(self.n_out, 64)
+
+    def _internal_biases(self):
+        """[bh_0 .. bh_{M-1}] and [bv_0 .. bv_{M-1}] as two flat vectors, in the Dense output's column order."""
+        return torch.cat([r.bh.view(-1) for r in self._rbms]), torch.cat([r.bv.view(-1) for r in self._rbms])
+
+    def _pack_estimator(self):
+        dev = self.store.theta.device
+        R = self.num_hidden_rnn[-1]
+        wu = torch.cat([self.store["Wuh"], self.store["Wuv"]], 1).contiguous()          # [R, M Hn + M D]
+        self._wu_t = torch.empty((self.n_out, R), device=dev, dtype=self.dtype)
+        ops.transpose(wu, self._wu_t)
+        self._wu_p = torch.zeros((R, self.ldo), device=dev, dtype=self.dtype)
+        ops.convert2d(wu, self._wu_p[:, :self.n_out])
+        self._bias_cat = torch.cat(self._internal_biases()).contiguous() if self.internal_bias else torch.zeros(self.n_out, device=dev)
+
+    def _split(self, out):
+        """The per-track bias blocks of a Dense output [N, ld]: views, one leading dimension."""
+        M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
+        return ([out[:, m * Hn:(m + 1) * Hn] for m in range(M)], [out[:, M * Hn + m * D:M * Hn + (m + 1) * D] for m in range(M)])
+
+    def _planes(self, x, B, T):
+        """[B, T, D * M] composer layout -> u8 [M, T * B, D]: every track's rows as a contiguous time-major plane."""
+        M, D = self.num_tracks, self.num_dims
+        return x[:, :, :D * M].to(torch.uint8).reshape(B, T, D, M).permute(3, 1, 0, 2).contiguous().view(M, T * B, D)
+
+    def _build_co(self, x=None, y=None, lengths=None, is_train=None, mode="eval"):
+        Generator.build(self, x, y, lengths, is_train, mode)
+        self._materialize(x.shape[-1] if x is not None else self._num_inputs)
+        self._rnn.build_cell(is_train)
+        if mode in ("train", "eval"):
+            B, T, _ = x.shape
+            M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
+            N, dev = B * T, x.device
+            self._ensure_packed()
+            x_tm = self._to_time_major_inputs(x)
+            v0, tgt = self._planes(x, B, T), self._planes(y, B, T)                   # every chain starts from its track of the inputs
+            rw = self._row_weight(lengths, B, T, dev)
+            kp = self._rnn.effective_keep_prob()
+            seed = self.seed + self.store.step
+            yy, ctx, _ = yield from self._stack.forward_co(x_tm, kp, self.seed, self.row0, save=(mode == "train"), state0=self._state0(B),
+                                                           step_dev=self.store.step_dev, state_grad=(mode == "train"))
+            out = self._biases(yy.view(N, -1))
+            bh_t, bv_t = self._split(out)
+            rows = (torch.arange(T, device=dev)[:, None] * 65536 + (self.row0 + torch.arange(B, device=dev))[None, :]).reshape(-1).int()
+            p_v = torch.empty((M, N, D), device=dev)
+            v_s = torch.empty((M, N, D), device=dev, dtype=torch.uint8)
+            W = [r.W for r in self._rbms]
+            # the M chains in one launch; seed + m + step, the step read on the device (RnnRBM._build_co)
+            ops.rbm_gibbs_multi([dict(v0=v0[m], W=W[m], bh=bh_t[m], bv=bv_t[m], seed=self.seed + m, p_v=p_v[m], v_out=v_s[m]) for m in range(M)],
+                                self._k, 0, rows, 0, seed_step=self.store.step_dev)
+            if self.bias_mode == "conditional":
+                bh_u, bv_u = bh_t, bv_t
+            else:
+                bh_u, bv_u = [r.bh for r in self._rbms], [r.bv for r in self._rbms]
+            Fv = torch.empty((M, N), device=dev); Fs = torch.empty((M, N), device=dev)
+            sv = torch.empty((M, N, Hn), device=dev) if mode == "train" else None
+            ss = torch.empty((M, N, Hn), device=dev) if mode == "train" else None
+            ops.rbm_free_energy_multi([dict(v=tgt[m], W=W[m], bh=bh_u[m], bv=bv_u[m], F=Fv[m], p_h=None if sv is None else sv[m]) for m in range(M)])
+            ops.rbm_free_energy_multi([dict(v=v_s[m], W=W[m], bh=bh_u[m], bv=bv_u[m], F=Fs[m], p_h=None if ss is None else ss[m]) for m in range(M)])
+            cost = Fv - Fs
+            rwm = (rw / M).repeat(M)                                                     # mean over the tracks of the row-weighted sums
+            loss = torch.zeros(1, device=dev)
+            ops.weighted_sum(cost.view(-1), rwm, loss)
+            self._ctx = dict(y=yy, lstm=ctx, out=out, tgt=tgt, v_s=v_s, rw=rw, kp=kp, seed=seed, B=B, T=T, n_valid=self._n_valid,
+                             ls_dev=self._ls_dev if self._n_valid is None else None, sv=sv, ss=ss)
+            self._cost_tm, self._F_tm, self._pv_tm, self._vs_tm, self._loss = cost, Fv, p_v, v_s, loss
+            self._lengths, self._flat_idx = lengths, None
+            self._recon_tm = torch.empty((M, N), device=dev)
+            ops.log_loss_rows(tgt.view(M * N, D), p_v.view(M * N, D), self._recon_tm.view(-1))
+            fe, ll = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
+            ops.weighted_sum(Fv.view(-1), rwm, fe)
+            ops.weighted_sum(self._recon_tm.view(-1), rwm, ll)
+            self._metrics = {"batch/loss": loss, "free_energy": fe, "log_likelihood": ll}
+            self._metrics_upd = []
+        self._is_built = True
+
+    def _per_track(self, t, cast=None):
+        idx = self._idx()
+        return [t[m][idx] if cast is None else t[m][idx].to(cast) for m in range(self.num_tracks)]
+
+    cond_probs = property(lambda self: self._per_track(self._pv_tm))
+    _outputs = property(lambda self: self._per_track(self._vs_tm, torch.float32))
+    free_energy = property(lambda self: self._per_track(self._F_tm))
+    cost = property(lambda self: self._per_track(self._cost_tm))
+    reconstruction_cost = property(lambda self: self._per_track(self._recon_tm))
+
+    def _nll_rows_built(self, num_chains=64, num_betas=1000, betas=None, seed=None):
+        """AIS NLL of the last build's valid rows: the SUM over the tracks of F_m(target_m) + log Z^_m on the row's conditional biases
+        (the tracks of a step are independent given the history), each track estimated as RnnRBM._nll_rows_built does with seed + m."""
+        cx = self._ctx
+        B, T = cx["B"], cx["T"]
+        bh_t, bv_t = self._split(cx["out"])
+        dev = cx["out"].device
+        idx = self._idx()
+        rows = (torch.arange(T, device=dev)[:, None] * 65536 + (self.row0 + torch.arange(B, device=dev))[None, :]).reshape(-1)
+        ids = rows[idx].to(torch.int32).contiguous()
+        n = ids.numel()
+        if n == 0:
+            e = torch.zeros(0, device=dev)
+            return NllEstimate(e, e, e, e, e)
+        s0 = self.seed if seed is None else seed
+        parts = []
+        for m, r in enumerate(self._rbms):
+            bh, bv = bh_t[m][idx].contiguous(), bv_t[m][idx].contiguous()
+            stats = torch.empty((n, 2), device=dev)
+            log_z = r.log_partition(bh, bv, num_chains, num_betas, betas, s0 + m, row_ids=ids, stats=stats)
+            F = torch.empty(n, device=dev)
+            ops.rbm_free_energy(cx["tgt"][m][idx].contiguous(), r.W, bh, bv, F)
+            parts.append(NllEstimate(F + log_z, log_z, F, stats[:, 1], stats[:, 0]))
+        return NllEstimate.total(parts)
+
+    def _backward_co(self):
+        cx = self._ctx
+        M, D, Hn, R = self.num_tracks, self.num_dims, self.num_hidden[-1], self.num_hidden_rnn[-1]
+        B, T = cx["B"], cx["T"]
+        N, dev = B * T, cx["out"].device
+        g = self.store.gviews
+        self.store.grad.zero_()
+        sv, ss = cx.get("sv"), cx.get("ss")
+        if sv is None:
+            raise RuntimeError("build(..., mode='train') must run before train()")
+        # row weights, scale and the f16 loss scale (static x dynamic) exactly as RnnRBM._backward_co; the 1 / M of the mean over the tracks
+        # rides on the scale
+        dyn = self.store.ls_dyn if self.dtype == torch.float16 else None
+        gs = self.grad_scale / M
+        if cx["n_valid"] is None:
+            lsd = cx.get("ls_dev")
+            if lsd is not None and dyn is not None:
+                lsd = lsd * dyn[0:1]
+            rw, scale = (cx["rw"] if lsd is None else cx["rw"] * lsd), gs
+            ls = 1.0 if lsd is None else 1.0 / lsd
+        else:
+            ls = self._stack.loss_scale(cx["n_valid"])
+            if dyn is not None:
+                rw, scale = cx["rw"] * dyn[0:1], gs * ls
+                ls = dyn[1:2] * (1.0 / ls)
+            else:
+                rw, scale = cx["rw"], gs * ls
+        # per track the rows of RnnRBM's gradient block [Hn | D], moved into the track's column blocks of the one Dense-shaped d_out
+        d_out = torch.zeros((N, self.ldo), device=dev)
+        d_m = torch.empty((N, Hn + D), device=dev)
+        pos = torch.empty((M, N, Hn), device=dev); neg = torch.empty((M, N, Hn), device=dev)
+        h16 = self._stack.h16
+        Np = ops.round_up(N, 64 if h16 else 4)
+        def tr(xm, rows):
+            o = (torch.zeros if Np != N else torch.empty)((rows, Np), device=dev, dtype=self.dtype if h16 else torch.float32)
+            return ops.transpose(xm, o)
+        sk = int(max(1, min(256 // (-(-D // 128) * -(-Hn // 128)), Np // 256)))
+        dbh, dbv = self._split(d_out)
+        for m, r in enumerate(self._rbms):
+            ops.rbm_cd_rows(cx["tgt"][m], cx["v_s"][m], sv[m], ss[m], rw, scale, d_m, pos[m], neg[m])
+            dbh[m].copy_(d_m[:, :Hn]); dbv[m].copy_(d_m[:, Hn:])
+            gW = g[f"{r.prefix}/W"]                                                      # dW_m = v_s,m^T pos_m + target_m^T neg_m
+            ops.gemm_tn(tr(cx["v_s"][m], D), tr(pos[m], Hn), gW, accumulate=True, split_k=sk)
+            ops.gemm_tn(tr(cx["tgt"][m], D), tr(neg[m], Hn), gW, accumulate=True, split_k=sk)
+        def bias_grads(col):                                                             # col(lo, hi) -> the column sums [lo, hi) of d_out, accumulated by the callee
+            for m, r in enumerate(self._rbms):
+                col(m * Hn, (m + 1) * Hn, g[f"{r.prefix}/bh"].view(-1))
+                col(M * Hn + m * D, M * Hn + (m + 1) * D, g[f"{r.prefix}/bv"].view(-1))
+        if self.bias_mode != "conditional":
+            bias_grads(lambda lo, hi, gv: ops.bias_grad(d_out[:, lo:hi], gv, accumulate=True))
+            self._dx = None
+            self._unscale(ls)
+            return                                   # as RnnRBM: no gradient reaches the LSTM / Wuh / Wuv
+        Np8 = ops.round_up(N, 64)
+        zalloc = torch.zeros if Np8 != N else torch.empty
+        yT = cx["lstm"][-1].get("yT") if cx["lstm"] else None
+        if yT is None:
+            yT = zalloc((R, Np8), device=dev, dtype=self.dtype)
+            ops.transpose(cx["y"].view(N, R), yT)
+        doT = zalloc((self.n_out, Np8), device=dev, dtype=self.dtype)
+        if self.dtype == torch.float32:
+            if self.internal_bias:
+                bias_grads(lambda lo, hi, gv: ops.bias_grad(d_out[:, lo:hi], gv, accumulate=True))
+            ops.transpose(d_out[:, :self.n_out], doT)
+            do_c = d_out
+        else:
+            do_c = torch.empty((N, self.ldo), device=dev, dtype=self.dtype)
+            colsum = torch.zeros(self.n_out, device=dev)
+            ops.grad_rows_fanout(d_out, self.n_out, do_c, doT, colsum)
+            if self.internal_bias:
+                bias_grads(lambda lo, hi, gv: ops.axpby(1.0, colsum[lo:hi], 1.0, gv, gv))
+        # one accumulating product per variable, over all tracks' blocks
+        ops.gemm_tn(yT, doT[:M * Hn], g["Wuh"], accumulate=True, split_k=LstmStack._split_k(R, M * Hn, Np8))
+        ops.gemm_tn(yT, doT[M * Hn:self.n_out], g["Wuv"], accumulate=True, split_k=LstmStack._split_k(R, M * D, Np8))
+        dy = torch.empty((N, R), device=dev)
+        ops.gemm_tn(do_c, self._wu_p, dy)
+        self._dx = yield from self._lstm_backward_co(dy, cx)
+        self._unscale(ls)
+
+    # -- states and sampling --------------------------------------------------------------------
+    def zero_state(self, batch_size):
+        self._materialize(self._num_inputs)
+        dev = self.store.theta.device
+        z = lambda n: torch.zeros((batch_size, n), device=dev)
+        return RnnEstimatorStateTuple([z(self.num_hidden[-1]) for _ in self._tracks], [z(self.num_dims) for _ in self._tracks],
+                                      self._get_rnn_zero_state(batch_size))
+
+    def _state_from_out(self, out, rnn_state):
+        """Per-track lists of bias blocks (RnnRBM._get_state / single_step form their states through this)."""
+        be, bd = self._split(out)
+        return RnnEstimatorStateTuple(be, bd, rnn_state)
+
+    def _det_state(self, h, rnn_state):
+        """The Dense of a sampling step in the deterministic arithmetic: [bh_0 ..] = [rbm_m.bh] + h . Wuh, [bv_0 ..] = [rbm_m.bv] + h . Wuv
+        (two jobs, one launch; inside a scan the concatenated internal biases are formed once)."""
+        M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
+        out = torch.empty((h.shape[0], self.ldo), device=h.device)
+        ib = self._det_bias
+        if self.internal_bias and (ib is None or ib is True):
+            cat = self._internal_biases()
+            if ib is True:
+                self._det_bias = cat
+            ib = cat
+        bh, bv = ib if self.internal_bias else (None, None)
+        ops.dense_det([dict(x=h, W=self.store["Wuh"], bias=bh, out=out[:, :M * Hn]),
+                       dict(x=h, W=self.store["Wuv"], bias=bv, out=out[:, M * Hn:self.n_out])])
+        return self._state_from_out(out, tuple(rnn_state))
+
+    def _generate_scan(self, x, num_steps, given=None):
+        self._det_bias = True              # the first Dense of this scan forms the internal bias vectors, the later ones reuse them
+        try:
+            return super()._generate_scan(x, num_steps, given)
+        finally:
+            self._det_bias = None
+
+    def sample_single(self, inputs, state, given=None):
+        """The M chains of a sampling step in ONE grouped launch: the previous row is read, and the new one written, in composer layout in
+        place (element stride M), track m with seed + m.  Returns (sample u8 [B, M * D], cond_prob f32 [B, M * D]).  given (optional):
+        codes u8 [B, M * D] in the same layout (a step slice of generate's block is read in place): every track runs the clamped chain."""
+        M, D = self.num_tracks, self.num_dims
+        v0 = inputs[:, :M * D]
+        v0 = (v0 if v0.dtype == torch.uint8 else v0.to(torch.uint8)).contiguous()
+        Bn = v0.shape[0]
+        smp = torch.empty((Bn, M * D), device=v0.device, dtype=torch.uint8)
+        p_v = torch.empty((Bn, M * D), device=v0.device)
+        jobs = [dict(v0=v0[:, m::M], W=r.W, bh=state.b_enc[m], bv=state.b_dec[m], seed=self.seed + m, p_v=p_v[:, m::M], v_out=smp[:, m::M],
+                     given=None if given is None else given[:, m::M]) for m, r in enumerate(self._rbms)]
+        ops.rbm_gibbs_multi(jobs, self._k, self.row0, None, getattr(self, "_gen_step", 0) * max(self._k, 1))
+        return smp, p_v
+
+    def pretrain(self, optimizer, lr, run_optimizer=True):
+        """One CD-k update of every track's RBM on its track of the flattened inputs (RBM.train; RnnRBM.pretrain per track, seed + m)."""
+        x = self._inputs
+        B, T, _ = x.shape
+        M, D = self.num_tracks, self.num_dims
+        xt = x.to(torch.uint8)[:, :, :D * M].reshape(B * T, D, M)
+        keep = None
+        if self._lengths is not None:
+            keep = (torch.arange(T, device=x.device)[None, :] < self._lengths.to(x.device)[:, None]).reshape(-1)
+        self._materialize(x.shape[-1])
+        init_ops, update_ops, self._cd_gradients = [], [], []
+        for m, r in enumerate(self._rbms):
+            flat = xt[:, :, m] if keep is None else xt[:, :, m][keep]
+            if not run_optimizer:
+                init_ops += r.visible_bias_init_ops(flat.contiguous())
+                continue
+            io, uo, gr = r.train(flat.contiguous(), lr, seed=self.seed + m + self.store.step, row0=self.row0 * T)
+            init_ops += io; update_ops += uo; self._cd_gradients.append(gr)
+        self._packed_step = -1
         return init_ops, update_ops, self.metrics, self.metrics_upd, self.summaries

@@ -6,6 +6,7 @@ outputs are decoded back, how the per-track losses are combined and optimised, a
     MultINNJoint        multinn_joint.py:41-215       one encoder over P*M features, one generator            (C1, C2, TGT)
     MultINNJamming      multinn_jamming.py:31-250     M per-track encoders, M independent generators           (C3)
     MultINNComposer     multinn_composer.py:33-204    M per-track encoders, ONE RnnMultiNADE over the stack    (C4)
+                                                      (generator type `MultiRBM`: ONE RnnMultiRBM, which the reference lacks)
     MultINNFeedback     multinn_feedback.py:46-218    jamming + Dense feedback module
     MultINNFeedbackRnn  multinn_feedback_rnn.py:30-79 jamming + recurrent feedback module                      (C5)
     MultINN             multinn.py:24-53              facade choosing one of them by `params['mode']`
@@ -25,7 +26,7 @@ import torch
 
 from .common import Model, capture_train_step, given_codes, given_tracks
 from .encoders import PassEncoder, DBNEncoder
-from .generators import RnnNade, RnnRBM, RnnMultiNADE
+from .generators import RnnNade, RnnRBM, RnnMultiNADE, RnnMultiRBM
 from . import ops
 from ._lib import MnnUnsupported
 from .training import compute_gradients_multi, world
@@ -97,8 +98,14 @@ class MultINNCore(Model):
             generator_class = RnnRBM
         elif self._generator_type == "NADE":
             generator_class = RnnNade
+        elif self._generator_type == "MultiRBM":
+            # the shared-LSTM multi-track LSTM-RBM (generators.RnnMultiRBM) is a composer-mode model: one generator over the stacked tracks
+            if not isinstance(self, MultINNComposer):
+                raise ValueError("Incorrect generator type: `MultiRBM` (one shared LSTM, one RBM per track) is built by the `composer` mode "
+                                 "only; the other modes take `RBM` or `NADE`")
+            generator_class = RnnMultiRBM
         else:
-            raise ValueError("Incorrect generator type, supported types are `RBM`, and `NADE`")
+            raise ValueError("Incorrect generator type, supported types are `RBM`, and `NADE` (and `MultiRBM` in composer mode)")
         num_dims = config["data"]["pitch_range"]["highest"] - config["data"]["pitch_range"]["lowest"]
         self._num_dims = num_dims * config["training"]["num_pixels"]
         self._tracks = list(config["data"]["instruments"])
@@ -811,7 +818,8 @@ class MultINNJamming(MultIEncoderNN):
 
 
 class MultINNComposer(MultIEncoderNN):
-    """multinn_composer.py: per-track encoders, ONE generator with a shared LSTM and one NADE per track."""
+    """multinn_composer.py: per-track encoders, ONE generator with a shared LSTM and one NADE per track -- or, with generator type
+    `MultiRBM`, one RBM per track (generators.RnnMultiRBM).  The type `RBM` keeps the reference's refusal."""
 
     def __init__(self, config, params, name="MultINN-composer", **kw):
         super().__init__(config, params, name=name, **kw)
@@ -819,7 +827,14 @@ class MultINNComposer(MultIEncoderNN):
 
     def _init_generators(self, generator_class):
         if self.generator_type == "RBM":
-            raise NotImplementedError("MultiRNNRBM is not implemented yet :(")                 # multinn_composer.py:44-45
+            raise NotImplementedError("MultiRNNRBM is not implemented yet :( -- the generator type `RBM` keeps the reference's refusal in "
+                                      "composer mode; the shared-LSTM multi-track LSTM-RBM is the type `MultiRBM`")   # multinn_composer.py:44-45
+        if self.generator_type == "MultiRBM":
+            generators = [RnnMultiRBM(num_dims=self._num_dims_generator, num_hidden=self._params["generator"]["num_hidden"],
+                                      num_hidden_rnn=self._params["generator"]["num_hidden_rnn"], tracks=self.tracks, keep_prob=self.keep_prob,
+                                      k=self._params["generator"].get("k", 10), **self._generator_kwargs())]
+            self._generator = generators[0]
+            return generators
         generators = [RnnMultiNADE(num_dims=self._num_dims_generator, num_hidden=self._params["generator"]["num_hidden"],
                                    num_hidden_rnn=self._params["generator"]["num_hidden_rnn"], tracks=self.tracks,
                                    keep_prob=self.keep_prob, **self._generator_kwargs())]       # multinn_composer.py:49-57

@@ -807,6 +807,90 @@ def rbm_free_energy(v, W, bh, bv, F, p_h=None):
     return F
 
 
+RBM_MULTI_MAX_JOBS = 8
+
+
+def _multi_bias_ld(jobs, key, n, N, what):
+    """The jobs' bias blocks share one leading dimension: all broadcast rows (0) or rows of one stride (slices of one Dense-output block)."""
+    lds = set()
+    for j in jobs:
+        b = j[key]
+        _req(torch.is_tensor(b) and b.dim() == 2 and b.shape[0] in (1, N), f"{what}: {key} rows must be 1 or N")
+        lds.add(_ldb(b, n))
+    _req(len(lds) == 1, f"{what}: the jobs' {key} must share one leading dimension")
+    return lds.pop()
+
+
+def rbm_gibbs_multi(jobs, k, row0=0, row_ids=None, sub0=0, seed_step=None):
+    """ops.rbm_gibbs for 1..8 RBMs of one shape in ONE launch (mnn_rbm_gibbs_multi).  job = dict(v0 = a u8 [N, D] VIEW (any row / column
+    strides, the same for every job: e.g. x[:, m::M] of a composer-layout [N, D * M] block, or a contiguous plane), W f32 [D, Hn], bh / bv
+    f32 [N or 1, >= Hn / D] (slices of one block: one leading dimension), seed, p_v f32 [N, D] / v_out u8 [N, D] views or None (the element
+    strides of v0), given = None or a u8 [N, D] view of codes with v0's column stride (set on every job or on none; not with seed_step)).
+    Per job the results are bit for bit those of ops.rbm_gibbs on contiguous copies."""
+    _req(isinstance(jobs, (list, tuple)) and 1 <= len(jobs) <= RBM_MULTI_MAX_JOBS, f"gibbs_multi: 1..{RBM_MULTI_MAX_JOBS} jobs")
+    v0 = jobs[0]["v0"]
+    _req(torch.is_tensor(v0) and v0.dim() == 2, "gibbs_multi: v0 u8 [N, D] views")
+    N, D = v0.shape
+    W0 = jobs[0]["W"]
+    _req(torch.is_tensor(W0) and W0.dim() == 2 and W0.shape[0] == D, "gibbs_multi: W f32 [D, Hn]")
+    Hn = W0.shape[1]
+    rs, es = v0.stride()
+    _req(es >= 1 and (N == 1 or rs >= (D - 1) * es + 1), "gibbs_multi: v0 needs a positive column stride and rows that do not overlap")
+    has_given = jobs[0].get("given") is not None
+    rs_g = jobs[0]["given"].stride(0) if has_given else 0
+    _req(not (has_given and seed_step is not None), "gibbs_multi: given with seed_step (the stepped chain is training's, unconditioned)")
+    for j in jobs:
+        v, W = j["v0"], j["W"]
+        _req(torch.is_tensor(v) and v.dtype == torch.uint8 and tuple(v.shape) == (N, D) and v.stride() == (rs, es) and v.device == v0.device,
+             "gibbs_multi: v0 u8 [N, D] views of equal shape and strides")
+        _req(torch.is_tensor(W) and W.dtype == torch.float32 and tuple(W.shape) == (D, Hn) and W.is_contiguous(), "gibbs_multi: W f32 [D, Hn], one shape for every job")
+        for t, dt, what in ((j.get("p_v"), torch.float32, "p_v f32"), (j.get("v_out"), torch.uint8, "v_out u8")):
+            _req(t is None or (t.dtype == dt and tuple(t.shape) == (N, D) and t.stride() == (rs, es)), f"gibbs_multi: {what} [N, D] with the strides of v0")
+        g = j.get("given")
+        _req((g is not None) == has_given, "gibbs_multi: given on every job or on none")
+        _req(g is None or (g.dtype == torch.uint8 and tuple(g.shape) == (N, D) and g.stride(1) == es and g.stride(0) == rs_g
+                           and (N == 1 or rs_g >= (D - 1) * es + 1) and g.device == v0.device),
+             "gibbs_multi: given u8 [N, D] views with v0's column stride and one row stride")
+    ld_bh = _multi_bias_ld(jobs, "bh", Hn, N, "gibbs_multi")
+    ld_bv = _multi_bias_ld(jobs, "bv", D, N, "gibbs_multi")
+    if row_ids is not None:
+        _req(row_ids.dtype == torch.int32 and row_ids.numel() == N, "gibbs_multi: row_ids int32 [N]")
+    if seed_step is not None:
+        _req(seed_step.dtype == torch.int32 and seed_step.numel() == 1, "gibbs_multi: seed_step int32 [1]")
+    arr = (_lib.RbmGibbsJob * len(jobs))()
+    for a, j in zip(arr, jobs):
+        a.W, a.bh, a.bv, a.seed, a.v0 = _ptr(j["W"]), _ptr(j["bh"]), _ptr(j["bv"]), int(j["seed"]), _ptr(j["v0"])
+        a.p_v, a.v_out, a.given = _ptr(j.get("p_v")), _ptr(j.get("v_out")), _ptr(j.get("given"))
+    ws = torch.empty(len(jobs) * _lib.load().mnn_rbm_workspace_bytes(D, Hn), dtype=torch.uint8, device=v0.device)
+    call("mnn_rbm_gibbs_multi", _stream(), len(jobs), arr, N, D, Hn, int(k), ld_bh, ld_bv, int(row0), _ptr(row_ids), int(sub0), _ptr(seed_step),
+         rs if N > 1 else max(rs, (D - 1) * es + 1), es, rs_g if N > 1 else max(rs_g, (D - 1) * es + 1), _ptr(ws))
+
+
+def rbm_free_energy_multi(jobs):
+    """ops.rbm_free_energy for 1..8 RBMs of one shape in ONE launch (mnn_rbm_free_energy_multi).  job = dict(v u8 [N, D], W f32 [D, Hn],
+    bh / bv f32 [N or 1, .] (one leading dimension over the jobs), F f32 [N], p_h = None or f32 [N, Hn])."""
+    _req(isinstance(jobs, (list, tuple)) and 1 <= len(jobs) <= RBM_MULTI_MAX_JOBS, f"free_energy_multi: 1..{RBM_MULTI_MAX_JOBS} jobs")
+    v0 = jobs[0]["v"]
+    _req(torch.is_tensor(v0) and v0.dim() == 2, "free_energy_multi: v u8 [N, D]")
+    N, D = v0.shape
+    W0 = jobs[0]["W"]
+    _req(torch.is_tensor(W0) and W0.dim() == 2 and W0.shape[0] == D, "free_energy_multi: W f32 [D, Hn]")
+    Hn = W0.shape[1]
+    for j in jobs:
+        v, W, F, p_h = j["v"], j["W"], j["F"], j.get("p_h")
+        _req(torch.is_tensor(v) and v.dtype == torch.uint8 and tuple(v.shape) == (N, D) and v.is_contiguous() and v.device == v0.device,
+             "free_energy_multi: v u8 [N, D], one shape for every job")
+        _req(torch.is_tensor(W) and W.dtype == torch.float32 and tuple(W.shape) == (D, Hn) and W.is_contiguous(), "free_energy_multi: W f32 [D, Hn], one shape for every job")
+        _req(torch.is_tensor(F) and F.dtype == torch.float32 and F.numel() == N and F.is_contiguous(), "free_energy_multi: F f32 [N]")
+        _req(p_h is None or (p_h.dtype == torch.float32 and p_h.is_contiguous() and tuple(p_h.shape) == (N, Hn)), "free_energy_multi: p_h f32 [N, Hn]")
+    ld_bh = _multi_bias_ld(jobs, "bh", Hn, N, "free_energy_multi")
+    ld_bv = _multi_bias_ld(jobs, "bv", D, N, "free_energy_multi")
+    arr = (_lib.RbmFreeEnergyJob * len(jobs))()
+    for a, j in zip(arr, jobs):
+        a.v, a.W, a.bh, a.bv, a.F, a.p_h = _ptr(j["v"]), _ptr(j["W"]), _ptr(j["bh"]), _ptr(j["bv"]), _ptr(j["F"]), _ptr(j.get("p_h"))
+    call("mnn_rbm_free_energy_multi", _stream(), len(jobs), arr, N, D, Hn, ld_bh, ld_bv)
+
+
 def rbm_cd_bias_delta(v, p_v, h, p_h, scale, dbv, dbh):
     """dbv += scale * colsum(v - p_v), dbh += scale * colsum(h - p_h) (rbm.py:318-327); v/h u8, p_* f32, outputs f32 (zeroed by the caller)."""
     N, D = v.shape
