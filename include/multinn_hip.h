@@ -389,6 +389,21 @@ int mnn_nade_logprob_bwd(mnn_stream_t s, int tracks, int N, int D, int Hn, const
 int mnn_nade_sample(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
                     const float* w_dec, float temperature, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
                     long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given);
+/* Sampling temperatures of the NADE entry points that end in _temps (added without a version bump; the entry points that take one float are
+ * wrappers: temperature <= 0 is n = 0, any other is n = 1).  n = 0: threshold draws, p >= 0.5.  n >= 1: n positive finite temperatures (at
+ * most MNN_TEMPS_MAX); visible i is drawn as u < sigmoid(logit_i / T) while nll and probabilities stay the model's own.  n = 1: T = t[0]
+ * everywhere.  n > 1 with by_visible = 0: T = t[track] (mnn_nade_sample_temps, mnn_generate_scan_temps: n = tracks) or t[job]
+ * (mnn_nade_sample_multi_temps: n = njobs).  n > 1 with by_visible = 1: T = t[i % n] for visible i of every track / job -- a NADE over
+ * visibles ordered p * M + m with one temperature per track m.  A launch whose temperatures are all 1 runs the kernels of temperature 1. */
+#define MNN_TEMPS_MAX 8
+typedef struct {
+    int n;
+    int by_visible;
+    float t[MNN_TEMPS_MAX];
+} mnn_temps;
+int mnn_nade_sample_temps(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
+                          const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
+                          long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given);
 /* mnn_nade_sample for SEVERAL single-NADE generators in ONE launch (multinn_feedback.py:196: every per-track generator's sample_single in a
  * step of the feedback scan).  `jobs`: HOST array of 1..8 descriptors (passed to the kernel by value): the generator's Dense output matrix
  * bias [N, ld_bias] (b_enc at column 0, b_dec at column Hn), its weights [D, Hn], its Philox seed and where its samples go
@@ -402,6 +417,8 @@ typedef struct {
 } mnn_nade_sample_job;
 int mnn_nade_sample_multi(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, float temperature,
                           uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride);
+int mnn_nade_sample_multi_temps(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, const mnn_temps* temps,
+                                uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride);
 
 /* ------------------------------------------------------------------------------------------
  * RBM (models/common/rbm.py).  W f32 [D,Hn]; bh f32 [N or 1, Hn] (ld_bh = 0 broadcasts one row);
@@ -422,6 +439,12 @@ size_t mnn_rbm_workspace_bytes(int D, int Hn);
 int mnn_rbm_gibbs(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
                   const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0,
                   float* p_v, uint8_t* v_out, void* workspace, const uint8_t* given, int ld_given);
+/* mnn_rbm_gibbs at a sampling temperature (positive, finite): the chain of the RBM with energy E / T -- every hidden and visible conditional is
+ * sigmoid(z / T), z the pre-activation with its bias; uniforms, counters and clamps are mnn_rbm_gibbs's, p_v is the tempered probability the
+ * last visible phase drew from.  temperature == 1 IS mnn_rbm_gibbs (which calls this): the same kernels, launches and bits. */
+int mnn_rbm_gibbs_temp(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
+                       const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0,
+                       float* p_v, uint8_t* v_out, void* workspace, const uint8_t* given, int ld_given, float temperature);
 /* The same chain with the step counter of the optimiser read ON THE DEVICE: effective seed = seed + *seed_step (NULL: seed).  A launch
  * captured in a hipGraph then draws new uniforms at every replay, like the dropout masks (mnn_dropout_mask's step pointer); the
  * reference re-runs its random ops at every sess.run (rbm.py:222-226).  Unconditioned (training's CD-k chain). */
@@ -459,6 +482,11 @@ typedef struct {
 int mnn_rbm_gibbs_multi(mnn_stream_t s, int njobs, const mnn_rbm_gibbs_job* jobs, int N, int D, int Hn, int k, int ld_bh, int ld_bv,
                         uint32_t row0, const uint32_t* row_ids, uint32_t sub0, const int* seed_step, long row_stride, int elem_stride,
                         long given_row_stride, void* workspace);
+/* mnn_rbm_gibbs_multi with one temperature per job (temps: HOST array of njobs positive finite floats, or NULL = all 1 = mnn_rbm_gibbs_multi,
+ * which calls this).  Job j equals mnn_rbm_gibbs_temp at temps[j] on contiguous copies, bit for bit. */
+int mnn_rbm_gibbs_multi_temps(mnn_stream_t s, int njobs, const mnn_rbm_gibbs_job* jobs, int N, int D, int Hn, int k, int ld_bh, int ld_bv,
+                              uint32_t row0, const uint32_t* row_ids, uint32_t sub0, const int* seed_step, long row_stride, int elem_stride,
+                              long given_row_stride, void* workspace, const float* temps);
 typedef struct {
     const uint8_t* v;
     const float* W;
@@ -618,6 +646,12 @@ int mnn_generate_scan(mnn_stream_t s, int B, int n_intro, int num_steps, const u
 int mnn_generate_scan_state(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
                             const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D, int Hn,
                             const float* w_enc, const float* w_dec, float temperature, uint64_t seed, uint32_t row0, uint8_t* samples,
+                            void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0, const float* const* h0);
+/* ... with a temperature table (mnn_temps: n = 1, one per track of a MultiNADE, or -- by_visible -- by visible index of the one NADE) in place of
+ * the float, and the optional initial state (c0 / h0 both NULL: the zero state).  The two entry points above are wrappers over this one. */
+int mnn_generate_scan_temps(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                            const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D, int Hn,
+                            const float* w_enc, const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint8_t* samples,
                             void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0, const float* const* h0);
 
 /* ------------------------------------------------------------------------------------------

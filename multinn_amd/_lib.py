@@ -83,6 +83,11 @@ class NadeSampleJob(C.Structure):
     _fields_ = [("bias", _p), ("ld_bias", _i), ("w_enc", _p), ("w_dec", _p), ("seed", _u64), ("samples", _p), ("nll", _p), ("given", _p)]
 
 
+class Temps(C.Structure):
+    """mnn_temps (include/multinn_hip.h)."""
+    _fields_ = [("n", _i), ("by_visible", _i), ("t", _f * 8)]
+
+
 class RbmGibbsJob(C.Structure):
     """mnn_rbm_gibbs_job (include/multinn_hip.h)."""
     _fields_ = [("W", _p), ("bh", _p), ("bv", _p), ("seed", _u64), ("v0", _p), ("p_v", _p), ("v_out", _p), ("given", _p)]
@@ -164,6 +169,14 @@ SIGNATURES["mnn_rbm_cd_rows"] = (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f
 SIGNATURES["mnn_probe_sigmoid"] = (_i, [_p, _i, _i, _p])
 SIGNATURES["mnn_axpby_f32"] = (_i, [_p, _l, _f, _p, _f, _p, _p])
 SIGNATURES["mnn_dropout_mask"] = (_i, [_p, _p, _i, _i, _i, _f, _u64, _p, _u32, _i])
+# sampling temperatures (additions without a version bump): the float of the entry points they wrap becomes a table / gains a temperature
+SIGNATURES["mnn_nade_sample_temps"] = (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _u64, _u32, _u32, _p, _l, _i, _i, _p, _p])
+SIGNATURES["mnn_nade_sample_multi_temps"] = (_i, [_p, _i, _p, _i, _i, _i, _p, _u32, _u32, _l, _i])
+SIGNATURES["mnn_generate_scan_temps"] = (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _u64, _u32, _p, _p, _sz, _p,
+                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)])
+SIGNATURES["mnn_rbm_gibbs_temp"] = (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _u64, _u32, _p, _u32, _p, _p, _p, _p, _i, _f])
+SIGNATURES["mnn_rbm_gibbs_multi_temps"] = (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _u32, _p, _u32, _p, _l, _i, _l, _p, C.POINTER(C.c_float)])
+TEMPS_MAX = 8              # MNN_TEMPS_MAX
 
 _lib = None
 

@@ -194,6 +194,53 @@ def given_tracks(given_mask, shape):
 
 
 # --------------------------------------------------------------------------------------------
+# Sampling temperature.  A NADE generator draws visible i as u < sigmoid(logit_i / T) (its nll / probabilities stay the model's own); an RBM
+# generator runs the Gibbs chain of exp(-E / T), every conditional sigmoid(z / T).  T is one number or one per track.
+MAX_TEMPERATURE_TRACKS = 8
+
+
+def sampling_temperature(temperature, num_tracks=None, allow_none=True, allow_sequence=True, what="temperature"):
+    """The one normalisation of a `temperature` argument, on the host, before any device work.  Returns None (threshold decoding, p >= 0.5:
+    NADE generators only -- allow_none), a float, or a tuple of num_tracks floats.  Accepted: a positive finite number; a sequence of
+    num_tracks of them (at most MAX_TEMPERATURE_TRACKS; not where allow_sequence is False -- the hidden units of a joint RBM belong to no
+    track); None.  A sequence of equal values IS the scalar, so 1.0 and (1.0, ..., 1.0) are both the float 1.0: the kernels, bits and
+    captured scans of a call without the argument.  Anything else raises ValueError."""
+    import math
+    import numbers
+    if temperature is None:
+        if not allow_none:
+            raise ValueError(f"{what}=None (threshold decoding) exists for NADE generators only: an RBM has no threshold mode")
+        return None
+
+    def one(t):
+        if isinstance(t, bool) or not isinstance(t, numbers.Real) or not math.isfinite(t) or not t > 0:
+            raise ValueError(f"{what} must be a positive finite number, got {t!r}")
+        return float(t)
+
+    if torch.is_tensor(temperature):
+        temperature = temperature.detach().to("cpu").tolist()
+    if isinstance(temperature, numbers.Real):
+        return one(temperature)
+    try:
+        seq = list(temperature)
+    except TypeError:
+        raise ValueError(f"{what} must be a positive finite number or a sequence of them, got {temperature!r}") from None
+    if not allow_sequence:
+        raise ValueError(f"{what} per track does not exist here (a joint RBM's hidden units belong to no track): pass one number")
+    if len(seq) > MAX_TEMPERATURE_TRACKS:
+        raise ValueError(f"{what}: at most {MAX_TEMPERATURE_TRACKS} tracks, got {len(seq)} values")
+    if num_tracks is None or len(seq) != int(num_tracks):
+        raise ValueError(f"{what}: a sequence needs one value per track ({num_tracks}), got {len(seq)}")
+    seq = tuple(one(t) for t in seq)
+    return seq[0] if all(t == seq[0] for t in seq) else seq
+
+
+def temperature_key(temperature):
+    """What a scan-graph key gains from a (normalised) temperature: nothing at 1.0 -- the key, and the captured scan, of a call without one."""
+    return () if temperature == 1.0 else (("temperature", temperature),)
+
+
+# --------------------------------------------------------------------------------------------
 class ParamStore:
     """Flat f32 parameter / gradient / Adam-slot buffers with named views."""
 
@@ -593,9 +640,11 @@ class RBM(Model):
         ops.rbm_visible(hh.contiguous(), self.W, bv, stream, self.seed if seed is None else seed, row0, sub, p, v)
         return p, v
 
-    def sample(self, v, bh=None, bv=None, k=None, seed=None, row0=0, row_ids=None, sub0=0, given=None):
+    def sample(self, v, bh=None, bv=None, k=None, seed=None, row0=0, row_ids=None, sub0=0, given=None, temperature=1.0):
         """rbm.py:192-231; k=None -> self.k (R1).  Returns (p_v, v_sample u8).  given (optional): codes u8 [N, D] (ops.rbm_gibbs) -- the
-        clamped chain: v_sample equals the code at every clamped visible, the free ones are sampled conditioned on all of them."""
+        clamped chain: v_sample equals the code at every clamped visible, the free ones are sampled conditioned on all of them.
+        temperature: the chain of exp(-E / T); p_v is then the tempered probability."""
+        temperature = sampling_temperature(temperature, allow_none=False, allow_sequence=False)
         k = self._k if k is None else k
         bh = bh if bh is not None else self.bh
         bv = bv if bv is not None else self.bv
@@ -603,7 +652,7 @@ class RBM(Model):
         p_v = torch.empty((N, D), device=v.device)
         v_s = torch.empty((N, D), device=v.device, dtype=torch.uint8)
         ops.rbm_gibbs(v.to(torch.uint8).contiguous(), self.W, bh, bv, k, self.seed if seed is None else seed, row0, row_ids, sub0, p_v, v_s,
-                      given=given)
+                      given=given, temperature=temperature)
         return p_v, v_s
 
     def log_partition(self, bh=None, bv=None, num_chains=64, num_betas=1000, betas=None, seed=None, row0=0, row_ids=None, stats=None):

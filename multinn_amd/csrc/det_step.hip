@@ -432,9 +432,10 @@ extern "C" size_t mnn_generate_scan_workspace_bytes(int B, int n_in, int n_layer
 // the scan (the host layer tiles a learned c0 and tanh(c0) once, on the device), handed to the first step's jobs as h_prev / c_prev.
 static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
                               const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
-                              int Hn, const float* w_enc, const float* w_dec, float temperature, uint64_t seed, uint32_t row0,
+                              int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0,
                               uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0,
                               const float* const* h0) {
+    MNN_REQUIRE(temps, "mnn_generate_scan: null temps");     // (its contents: mnn_nade_sample_temps, before anything is enqueued when num_steps > 0)
     MNN_REQUIRE(B > 0 && n_intro > 0 && num_steps >= 0 && intro && n_in > 0 && n_layers > 0 && n_layers <= MNN_SCAN_MAX_LAYERS && layers,
                 "mnn_generate_scan: B, n_intro > 0, 1..%d layers", MNN_SCAN_MAX_LAYERS);
     MNN_REQUIRE(dense_W && tracks > 0 && D > 0 && Hn > 0 && n_out == tracks * (Hn + D) && n_in == tracks * D && w_enc && w_dec && samples,
@@ -507,7 +508,7 @@ static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps,
     const int row_stride = num_steps * n_in;
     for (int st = 0; st < num_steps; ++st) {
         uint8_t* smp = samples + (size_t)st * n_in;            // samples[:, st, :]; feature m D + i (one NADE) or i tracks + m (rnn_multinade.py:313-314)
-        rc = mnn_nade_sample(s, tracks, B, D, Hn, out, ld_out, w_enc, w_dec, temperature, seed, row0, (uint32_t)st, smp,
+        rc = mnn_nade_sample_temps(s, tracks, B, D, Hn, out, ld_out, w_enc, w_dec, temps, seed, row0, (uint32_t)st, smp,
                              tracks > 1 ? 1 : D, row_stride, tracks > 1 ? tracks : 1, nullptr, given ? given + (size_t)st * n_in : nullptr);
         if (rc != MNN_OK) return rc;
         rc = stack_step(smp, row_stride);
@@ -518,16 +519,10 @@ static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps,
     return MNN_OK;
 }
 
-extern "C" int mnn_generate_scan(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
-                                 const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
-                                 int Hn, const float* w_enc, const float* w_dec, float temperature, uint64_t seed, uint32_t row0,
-                                 uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given) {
-    return generate_scan_impl(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc, w_dec, temperature,
-                              seed, row0, samples, workspace, workspace_bytes, given, nullptr, nullptr);
-}
-extern "C" int mnn_generate_scan_state(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+// the scan with a temperature table (mnn_temps: per track of a MultiNADE, or per visible index of the one NADE) and the optional initial state
+extern "C" int mnn_generate_scan_temps(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
                                        const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
-                                       int Hn, const float* w_enc, const float* w_dec, float temperature, uint64_t seed, uint32_t row0,
+                                       int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0,
                                        uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0,
                                        const float* const* h0) {
     MNN_REQUIRE((c0 == nullptr) == (h0 == nullptr), "mnn_generate_scan_state: c0 and h0 come together (arrays of n_layers pointers) or not at all");
@@ -535,6 +530,30 @@ extern "C" int mnn_generate_scan_state(mnn_stream_t s, int B, int n_intro, int n
         MNN_REQUIRE(n_layers > 0 && n_layers <= MNN_SCAN_MAX_LAYERS, "mnn_generate_scan_state: 1..%d layers", MNN_SCAN_MAX_LAYERS);
         for (int l = 0; l < n_layers; ++l) MNN_REQUIRE(c0[l] && h0[l], "mnn_generate_scan_state: layer %d has no initial state", l);
     }
-    return generate_scan_impl(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc, w_dec, temperature,
+    return generate_scan_impl(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc, w_dec, temps,
                               seed, row0, samples, workspace, workspace_bytes, given, c0, h0);
+}
+static mnn_temps scan_temps_of_scalar(float temperature) {   // <= 0: threshold draws
+    mnn_temps t;
+    memset(&t, 0, sizeof(t));
+    if (temperature > 0.f) { t.n = 1; t.t[0] = temperature; }
+    return t;
+}
+
+extern "C" int mnn_generate_scan(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                 const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
+                                 int Hn, const float* w_enc, const float* w_dec, float temperature, uint64_t seed, uint32_t row0,
+                                 uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given) {
+    const mnn_temps t = scan_temps_of_scalar(temperature);
+    return mnn_generate_scan_temps(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc, w_dec, &t,
+                                   seed, row0, samples, workspace, workspace_bytes, given, nullptr, nullptr);
+}
+extern "C" int mnn_generate_scan_state(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                       const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
+                                       int Hn, const float* w_enc, const float* w_dec, float temperature, uint64_t seed, uint32_t row0,
+                                       uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0,
+                                       const float* const* h0) {
+    const mnn_temps t = scan_temps_of_scalar(temperature);
+    return mnn_generate_scan_temps(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc, w_dec, &t,
+                                   seed, row0, samples, workspace, workspace_bytes, given, c0, h0);
 }

@@ -732,15 +732,28 @@ struct SampleJob {
 };
 #define SAMPLE_MAX_JOBS 8
 struct SampleJobs { SampleJob job[SAMPLE_MAX_JOBS]; };
+// The temperatures of a launch (TMODE 2 only; the other modes never read it).  by_visible == 0: job j (blockIdx.y) draws at t[j] -- the launcher
+// fills all eight entries, a scalar eight times; by_visible == 1: visible i of every job draws at t[i % n] (the joint NADE orders its visibles
+// p M + m: one temperature per track).
+struct SampleTemps { float t[SAMPLE_MAX_JOBS]; int n; int by_visible; };
+// the table parked in LDS (eight floats at `stt`): every lane selects its entry with constant indices -- the by-value argument stays in scalar
+// registers -- and the scan then reads the entry of a running index, a broadcast (kernel below) or per-lane (chunk kernel) LDS read
+__device__ __forceinline__ void sample_temps_park(const SampleTemps& TT, int lane, float* stt) {
+    float tv = TT.t[0];
+#pragma unroll
+    for (int k = 1; k < SAMPLE_MAX_JOBS; ++k) tv = (lane & (SAMPLE_MAX_JOBS - 1)) == k ? TT.t[k] : tv;
+    if (lane < SAMPLE_MAX_JOBS) stt[lane] = tv;
+}
 
-// TMODE: 0 = threshold draws (temperature None / <= 0), 1 = temperature 1, 2 = any other temperature.  FULL: Hn == 256, no lane is idle.
+// TMODE: 0 = threshold draws (temperature None / <= 0), 1 = temperature 1, 2 = any other temperature: the table TT, per job or per visible.
+// FULL: Hn == 256, no lane is idle.
 // GIVEN: conditional sampling -- a visible whose code in job.given is 0 / 1 is not drawn, its value is written and fed forward like a draw
 // (its uniform is left unused: every free visible reads the uniform of the unconditioned scan); logits are parked as before, so nll is that of
 // the emitted vector.
 template <int TMODE, bool FULL, bool SPEC, bool GIVEN>
 __global__ void __launch_bounds__(256)
-nade_sample_kernel(SampleJobs J, int N, int D, int Hn, float temperature, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
-    // per wave: logit / log term [Dp] f32, b_dec [Dp] f32, draws [Dp] u8, 256 uniforms (, GIVEN: the row's codes [Dp] u8)
+nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
+    // per wave: logit / log term [Dp] f32, b_dec [Dp] f32, draws [Dp] u8, 256 uniforms (, GIVEN: the row's codes [Dp] u8) (, TMODE 2: 8 temperatures)
     extern __shared__ __attribute__((aligned(16))) unsigned char nade_sample_smem[];
     // blockIdx.y = job: a track of one MultiNADE (mnn_nade_sample) or one of several generators sampled together (mnn_nade_sample_multi)
     const SampleJob& jb = J.job[blockIdx.y];
@@ -758,6 +771,8 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, float temperature, uint32
     unsigned char* son = nade_sample_smem + (size_t)32 * Dp + (size_t)wv * Dp;
     float* su = reinterpret_cast<float*>(nade_sample_smem + (size_t)36 * Dp) + wv * 256;    // uniforms of Philox blocks b0 .. b0 + 63
     unsigned char* sg = nade_sample_smem + (size_t)36 * Dp + 4096 + (size_t)wv * Dp;
+    // TMODE 2: the temperatures, behind the codes; one copy for the four waves, each writes the same eight values before it reads them
+    float* stt = reinterpret_cast<float*>(nade_sample_smem + (size_t)36 * Dp + 4096 + (GIVEN ? (size_t)4 * Dp : 0));
     const float* __restrict__ we = jb.w_enc;
     const float* __restrict__ wd = jb.w_dec;
     const float* __restrict__ bd = bias + (size_t)row * ld_bias + jb.dec_off;
@@ -800,6 +815,14 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, float temperature, uint32
         *reinterpret_cast<float4*>(su + 4 * lane) = make_float4(u4[0], u4[1], u4[2], u4[3]);
     };
     if (TMODE != 0) refill();
+    // TMODE 2: the temperature of visible i is stt[tix]; tix = i % n carried along (never a division per visible), or the job for good
+    int tix = 0;
+    float t_cur = 1.0f;
+    if (TMODE == 2) {
+        sample_temps_park(TT, lane, stt);
+        tix = TT.by_visible ? 0 : (int)blockIdx.y;
+        t_cur = stt[tix];
+    }
     auto dot = [&](int k) {                                 // sum_j h_j w_dec[visible of ring slot k][j], the contract's order
         float acc = 0.f;
 #pragma unroll
@@ -832,7 +855,7 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, float temperature, uint32
                 if (GIVEN && code != 255) {                 // clamped: the given value moves a / h like a draw (and the speculation holds as for one)
                     on = code != 0;
                 } else if (TMODE != 0) {
-                    on = draw_below(u_cur, TMODE == 1 ? l : l / temperature);
+                    on = draw_below(u_cur, TMODE == 1 ? l : l / t_cur);
                 } else {
                     on = prob_at_least_half(l);              // nade.py:278-279
                 }
@@ -849,6 +872,10 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, float temperature, uint32
                 sp[i] = l;                                  // every lane holds the same logit and draw: one merged LDS write each;
                 son[i] = on ? 1 : 0;                        // p = det_sigmoid(logit) is evaluated after the scan, 64 visibles at a time
                 if (TMODE != 0) u_cur = uniform_of(i + 1);
+                if (TMODE == 2 && TT.by_visible) {          // uniform; fetched one visible ahead like the uniform
+                    tix = tix + 1 == TT.n ? 0 : tix + 1;
+                    t_cur = stt[tix];
+                }
             }
             __builtin_amdgcn_sched_barrier(0);
             fetch(k, i + RING);
@@ -897,11 +924,12 @@ extern "C" int mnn_sch_trace_read(long long* host) { return hipMemcpyFromSymbol(
 // drawn -- moves the state.
 template <int TMODE, bool FULL, int G, bool GIVEN>
 __global__ void __launch_bounds__(64)
-nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, float temperature, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
+nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
     constexpr int NB = sch_nb(G);
     constexpr int KSH = G == 16 ? 2 : 3;                      // lane l decides visible l >> KSH of the chunk
     constexpr int WAITN = (NB - 2) * 2 * G;                   // copies that may still be in flight when a chunk is needed: the NB - 2 chunks behind it
     // ring [NB][w_dec | w_enc][G][256] f32 (64 KB) | logit / log term [Dp] f32 | b_dec [Dp] f32 | 256 uniforms | draws [Dp] u8 (| GIVEN: codes [Dp] u8)
+    // (| TMODE 2: 8 temperatures)
     extern __shared__ __attribute__((aligned(16))) unsigned char nade_sample_smem[];
     float* ring = reinterpret_cast<float*>(nade_sample_smem);
     const int Dp = (D + 3) & ~3;
@@ -910,6 +938,7 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, float temperature, 
     float* su = sbd + Dp;
     unsigned char* son = reinterpret_cast<unsigned char*>(su + 256);
     unsigned char* sg = son + Dp;
+    float* stt = reinterpret_cast<float*>(sg + (GIVEN ? Dp : 0));
     const SampleJob& jb = J.job[blockIdx.y];
     const float* __restrict__ bias = jb.bias;
     const int ld_bias = jb.ld_bias;
@@ -975,16 +1004,24 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, float temperature, 
         *reinterpret_cast<float4*>(su + 4 * lane) = make_float4(u4[0], u4[1], u4[2], u4[3]);
     };
     if (TMODE != 0) refill();
+    if (TMODE == 2) sample_temps_park(TT, lane, stt);        // (an LDS write: ahead of every copy, like the uniforms)
     asm volatile("" ::"v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(h[3]));     // the initial states are evaluated HERE: behind the copies they would wait for all 64 of them
     __builtin_amdgcn_sched_barrier(0);                       // the loads above are older than every DMA: the counted waits below cover them
 #pragma unroll
     for (int b = 0; b < NB - 1; ++b) stage(b, b);            // NB - 1 chunks ahead: the last slot is refilled while its successor is evaluated (below)
     const int kq = lane >> KSH;                              // the visible of the chunk this lane decides
     const int nchunks = (D + G - 1) / G;
+    // TMODE 2: this lane's visible of chunk c is c G + kq; its temperature is stt[(c G + kq) % n], the index carried from chunk to chunk (one
+    // division per kernel, none per chunk), or stt[job]
+    int tix = 0, tstep = 0;
+    if (TMODE == 2) {
+        tix = TT.by_visible ? kq % TT.n : (int)blockIdx.y;
+        tstep = TT.by_visible ? G % TT.n : 0;
+    }
     // what a chunk's passes read besides h: its eight w_dec rows -- visibles (2 p, 2 p + 1) side by side, one packed FMA serves both --, the lane's
     // b_dec and uniform.  (Measured and dropped: fetching them one chunk AHEAD, under the previous chunk's passes -- 47.0 vs 46.5 us per call: a lone
     // wave spends ~10 cycles per instruction of this chain whatever flies beside it.)
-    struct ChunkIn { nade_f32x2 w[G / 2][4]; float bdv, u; int code; };
+    struct ChunkIn { nade_f32x2 w[G / 2][4]; float bdv, u, t; int code; };
     auto fetch_in = [&](int slot, int c, ChunkIn& ci) {
         const int i0 = c * G;
         // (Hn == 256, D % 8 != 0: the last chunk was copied from row D - 8 on -- visible i0 + k sits rsh rows further down; rows past D are never decided)
@@ -1001,6 +1038,12 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, float temperature, 
         ci.bdv = sbd[ivc];
         ci.code = GIVEN ? (int)sg[ivc] : 255;
         ci.u = 0.f;
+        ci.t = 1.0f;
+        if (TMODE == 2) {                                    // called once per chunk, in order
+            ci.t = stt[tix];
+            tix += tstep;
+            if (tix >= TT.n) tix -= TT.n;
+        }
         if (TMODE != 0) {
             const uint32_t e_last = e0 + (uint32_t)min(i0 + G - 1, D - 1);
             if ((e_last >> 2) >= b0 + 64u) {                 // uniform: the window of 64 Philox blocks restarts at this chunk's first element
@@ -1079,7 +1122,7 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, float temperature, 
                     const bool drawn = !GIVEN || ci.code == 255;     // (a clamped lane takes its code below, whatever its comparison says)
                     bool on;
                     if (TMODE != 0) {                        // u < det_sigmoid(l / T), settled by the hardware sigmoid unless within 1e-4 of a tie (draw_below)
-                        const float xa = TMODE == 1 ? l : l / temperature;
+                        const float xa = TMODE == 1 ? l : l / ci.t;
                         const float r = sig_approx(xa);
                         const float d = u - r;
                         const bool tie = !(fabsf(d) > 1e-4f * r + 1e-30f);
@@ -1147,20 +1190,21 @@ static hipError_t sample_chunk_raise_lds() {                 // the ring + a row
 }
 
 // GV: some job carries codes (SampleJob.given) -- the GIVEN instantiations; without any, the launch is the unconditioned one
+// tmode / TT: launch_sample's reading of the caller's mnn_temps (TT is read by the TMODE 2 instantiations only)
 template <bool GV>
-static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, float temperature, uint32_t row0, uint32_t sub,
+static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, int tmode, const SampleTemps& TT, uint32_t row0, uint32_t sub,
                            long s_row_stride, int s_elem_stride) {
-    const int tmode = temperature > 0.f ? (temperature == 1.0f ? 1 : 2) : 0;
     bool chunked = Hn % 4 == 0 && Hn >= 4 && getenv("MNN_SAMPLE_NO_CHUNK") == nullptr;      // (read per call: tests compare the two forms)
     for (int j = 0; j < njobs && chunked; ++j) chunked = (((uintptr_t)J.job[j].w_enc | (uintptr_t)J.job[j].w_dec) & 15) == 0;
     const size_t gbytes = GV ? (size_t)((D + 3) & ~3) : 0;   // the row's codes
+    const size_t tbytes = tmode == 2 ? SAMPLE_MAX_JOBS * sizeof(float) : 0;     // the temperatures
     if (chunked) {                                           // eight visibles per pass, one wave per row
         // sixteen visibles per pass while every row has a CU of its own (96 KB of ring: one workgroup per CU); eight with more rows than that
         const int g = (long)N * njobs <= 256 && !getenv("MNN_SAMPLE_G8") ? 16 : 8;
-        const size_t ldc = (size_t)sch_nb(g) * 2 * g * 1024 + (size_t)9 * ((D + 3) & ~3) + 1024 + gbytes;     // <= 96 KB + 15 KB + 1 KB (D <= 1536)
+        const size_t ldc = (size_t)sch_nb(g) * 2 * g * 1024 + (size_t)9 * ((D + 3) & ~3) + 1024 + gbytes + tbytes;     // <= 96 KB + 15 KB + 1 KB (D <= 1536)
         MNN_HIP(sample_chunk_raise_lds());
-#define SMC(TM, FU) do { if (g == 16) hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 16, GV>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride); \
-                         else hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 8, GV>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride); } while (0)
+#define SMC(TM, FU) do { if (g == 16) hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 16, GV>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride); \
+                         else hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 8, GV>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride); } while (0)
         if (Hn == 256) { if (tmode == 0) SMC(0, true); else if (tmode == 1) SMC(1, true); else SMC(2, true); }
         else { if (tmode == 0) SMC(0, false); else if (tmode == 1) SMC(1, false); else SMC(2, false); }
 #undef SMC
@@ -1168,8 +1212,8 @@ static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N
         return MNN_OK;
     }
     dim3 grid(cdiv(N, 4), njobs);
-    const size_t lds = (size_t)36 * ((D + 3) & ~3) + 4096 + 4 * gbytes;     // 4 waves x ((2 f32 + u8 (+ u8 code)) per visible + 256 uniforms): <= 64 KB
-#define SMP(TM, FU, SP) hipLaunchKernelGGL((nade_sample_kernel<TM, FU, SP, GV>), grid, dim3(256), lds, st, J, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride)
+    const size_t lds = (size_t)36 * ((D + 3) & ~3) + 4096 + 4 * gbytes + tbytes;     // 4 waves x ((2 f32 + u8 (+ u8 code)) per visible + 256 uniforms): <= 64 KB
+#define SMP(TM, FU, SP) hipLaunchKernelGGL((nade_sample_kernel<TM, FU, SP, GV>), grid, dim3(256), lds, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride)
     if (Hn == 256 && tmode == 1) { if (getenv("MNN_SAMPLE_NO_SPEC")) SMP(1, true, false); else SMP(1, true, true); }
     else if (Hn == 256) { if (tmode == 0) SMP(0, true, false); else SMP(2, true, false); }
     else { if (tmode == 0) SMP(0, false, false); else if (tmode == 1) SMP(1, false, false); else SMP(2, false, false); }
@@ -1178,21 +1222,53 @@ static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N
     return MNN_OK;
 }
 
-static int launch_sample(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, float temperature, uint32_t row0, uint32_t sub,
-                         long s_row_stride, int s_elem_stride) {
+// temps (validated by sample_temps_ok): n == 0 -> threshold draws; every temperature this launch uses equal to 1 -> the TMODE 1 kernels, the
+// ones a launch without temperatures always ran; anything else -> TMODE 2 with the table.  track0: the first job's index into a per-job table
+// (mnn_nade_sample walks a MultiNADE's tracks eight at a time).
+static int launch_sample(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, const mnn_temps& temps, int track0, uint32_t row0,
+                         uint32_t sub, long s_row_stride, int s_elem_stride) {
     bool given = false;
     for (int j = 0; j < njobs; ++j) given = given || J.job[j].given != nullptr;
-    return given ? launch_sample_t<true>(st, J, njobs, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride)
-                 : launch_sample_t<false>(st, J, njobs, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride);
+    SampleTemps TT;
+    memset(&TT, 0, sizeof(TT));
+    int tmode = 0;
+    if (temps.n > 0) {
+        tmode = 1;
+        if (temps.by_visible && temps.n > 1) {
+            TT.n = temps.n; TT.by_visible = 1;
+            for (int e = 0; e < temps.n; ++e) TT.t[e] = temps.t[e];
+            for (int e = 0; e < temps.n && e < D; ++e) if (temps.t[e] != 1.0f) tmode = 2;
+        } else {
+            TT.n = SAMPLE_MAX_JOBS; TT.by_visible = 0;
+            for (int j = 0; j < SAMPLE_MAX_JOBS; ++j) TT.t[j] = temps.n == 1 ? temps.t[0] : (track0 + j < temps.n ? temps.t[track0 + j] : 1.0f);
+            for (int j = 0; j < njobs; ++j) if (TT.t[j] != 1.0f) tmode = 2;
+        }
+    }
+    return given ? launch_sample_t<true>(st, J, njobs, N, D, Hn, tmode, TT, row0, sub, s_row_stride, s_elem_stride)
+                 : launch_sample_t<false>(st, J, njobs, N, D, Hn, tmode, TT, row0, sub, s_row_stride, s_elem_stride);
 }
 
-extern "C" int mnn_nade_sample(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
-                               const float* w_dec, float temperature, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
-                               long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given) {
+// n == 0 (threshold draws), or 1..8 positive finite temperatures; a per-job table (by_visible == 0) has one entry or one per job
+static bool sample_temps_ok(const mnn_temps* t, int njobs) {
+    if (t == nullptr || t->n < 0 || t->n > MNN_TEMPS_MAX) return false;
+    for (int e = 0; e < t->n; ++e) if (!(t->t[e] > 0.f) || !(t->t[e] <= 3.0e38f)) return false;
+    return t->n <= 1 || t->by_visible != 0 || t->n == njobs;
+}
+static mnn_temps temps_of_scalar(float temperature) {        // the float of the entry points without a table: <= 0 is the threshold mode
+    mnn_temps t;
+    memset(&t, 0, sizeof(t));
+    if (temperature > 0.f) { t.n = 1; t.t[0] = temperature; }
+    return t;
+}
+
+extern "C" int mnn_nade_sample_temps(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
+                                     const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
+                                     long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given) {
     MNN_REQUIRE(tracks > 0 && N > 0 && D > 0 && Hn > 0 && Hn <= 256, "mnn_nade_sample: need tracks,N,D>0 and 0<Hn<=256 (Hn=%d)", Hn);
     MNN_REQUIRE(bias && w_enc && w_dec && samples, "mnn_nade_sample: null pointer");
     MNN_REQUIRE(ld_bias >= tracks * (Hn + D), "mnn_nade_sample: ld_bias too small");
     MNN_REQUIRE(D <= 1536, "mnn_nade_sample: D <= 1536 (logits, b_dec and draws of a row are parked in LDS, 36 B per visible and wave; D=%d)", D);
+    MNN_REQUIRE(sample_temps_ok(temps, tracks), "mnn_nade_sample: temps: 0..%d positive finite temperatures, per track one or `tracks` of them", MNN_TEMPS_MAX);
     for (int m0 = 0; m0 < tracks; m0 += SAMPLE_MAX_JOBS) {            // the tracks of a MultiNADE: up to eight per launch
         SampleJobs J;
         memset(&J, 0, sizeof(J));
@@ -1203,19 +1279,28 @@ extern "C" int mnn_nade_sample(mnn_stream_t s, int tracks, int N, int D, int Hn,
                                  (uint32_t)(m * D), samples + (size_t)m * s_track_stride, nll ? nll + (size_t)m * N : nullptr,
                                  given ? given + (size_t)m * s_track_stride : nullptr};
         }
-        const int rc = launch_sample((hipStream_t)s, J, nj, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride);
+        const int rc = launch_sample((hipStream_t)s, J, nj, N, D, Hn, *temps, m0, row0, sub, s_row_stride, s_elem_stride);
         if (rc != MNN_OK) return rc;
     }
     return MNN_OK;
 }
 
+extern "C" int mnn_nade_sample(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
+                               const float* w_dec, float temperature, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
+                               long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given) {
+    const mnn_temps t = temps_of_scalar(temperature);
+    return mnn_nade_sample_temps(s, tracks, N, D, Hn, bias, ld_bias, w_enc, w_dec, &t, seed, row0, sub, samples, s_track_stride, s_row_stride,
+                                 s_elem_stride, nll, given);
+}
+
 // The same scan for SEVERAL single-NADE generators in one launch (the M per-track generators of a feedback-scan step,
 // multinn_feedback.py:196: `generators[i].sample_single` for every track): job j has its own Dense output matrix, weights, seed and output
-// pointer; rows, widths, temperature, the RNG row / sub counters and the output strides are shared.
-extern "C" int mnn_nade_sample_multi(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, float temperature,
-                                     uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
+// pointer -- and, with a table of njobs entries, its own temperature; rows, widths, the RNG row / sub counters and the output strides are shared.
+extern "C" int mnn_nade_sample_multi_temps(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, const mnn_temps* temps,
+                                           uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
     MNN_REQUIRE(njobs > 0 && njobs <= SAMPLE_MAX_JOBS && jobs && N > 0 && D > 0 && Hn > 0 && Hn <= 256 && D <= 1536,
                 "mnn_nade_sample_multi: 1..%d jobs, N, D > 0, 0 < Hn <= 256, D <= 1536", SAMPLE_MAX_JOBS);
+    MNN_REQUIRE(sample_temps_ok(temps, njobs), "mnn_nade_sample_multi: temps: 0..%d positive finite temperatures, per job one or `njobs` of them", MNN_TEMPS_MAX);
     SampleJobs J;
     memset(&J, 0, sizeof(J));
     for (int j = 0; j < njobs; ++j) {
@@ -1223,5 +1308,11 @@ extern "C" int mnn_nade_sample_multi(mnn_stream_t s, int njobs, const mnn_nade_s
         MNN_REQUIRE(q.bias && q.w_enc && q.w_dec && q.samples && q.ld_bias >= Hn + D, "mnn_nade_sample_multi: job %d: null pointer or ld_bias < Hn + D", j);
         J.job[j] = SampleJob{q.bias, q.ld_bias, 0, Hn, q.w_enc, q.w_dec, q.seed, 0u, q.samples, q.nll, q.given};
     }
-    return launch_sample((hipStream_t)s, J, njobs, N, D, Hn, temperature, row0, sub, s_row_stride, s_elem_stride);
+    return launch_sample((hipStream_t)s, J, njobs, N, D, Hn, *temps, 0, row0, sub, s_row_stride, s_elem_stride);
+}
+
+extern "C" int mnn_nade_sample_multi(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, float temperature,
+                                     uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
+    const mnn_temps t = temps_of_scalar(temperature);
+    return mnn_nade_sample_multi_temps(s, njobs, jobs, N, D, Hn, &t, row0, sub, s_row_stride, s_elem_stride);
 }

@@ -190,6 +190,103 @@ static int rbm_gibbs_launch(mnn_stream_t s, int N, int D, int Hn, int k, const u
     return MNN_OK;
 }
 
+// ----------------------------------------------------------------------------------------------
+// The TEMPERED chain (sampling at a temperature other than 1: generation only, training's stepped chain has none).  Kernels of their own --
+// the three forms above with TEMPERED = true, one by-value argument block for all of them -- so that the untempered kernels, their argument
+// lists and their code are the ones they always were.  Dispatch: the thresholds of rbm_gibbs_launch.
+// ----------------------------------------------------------------------------------------------
+struct GibbsTempArgs {
+    int N, D, Hn, k;
+    const uint8_t* v0; const float* W; const float* Wt; const float* bh; int ld_bh; const float* bv; int ld_bv;
+    uint64_t seed; uint32_t row0; const uint32_t* row_ids; uint32_t sub0; float* p_v; uint8_t* v_out;
+    const uint8_t* given; int ld_given; float temp;
+};
+__device__ __forceinline__ GibbsView gibbs_temp_view(const GibbsTempArgs& A) {
+    return GibbsView{A.N, A.D, A.Hn, A.k, A.v0, A.W, A.Wt, A.bh, A.ld_bh, A.bv, A.ld_bv, A.seed, A.row0, A.row_ids, A.sub0, A.p_v, A.v_out,
+                     A.given, A.ld_given, 0, 1, A.temp};
+}
+template <bool GIVEN>
+__global__ void __launch_bounds__(256) rbm_gibbs_temp_stream_kernel(GibbsTempArgs A) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    rbm_gibbs_stream_body<GIVEN, false, true>(gibbs_temp_view(A), blockIdx.x * RBM_R, smem);
+}
+template <int R, int RGH, int RGV, bool GIVEN>
+__global__ void __launch_bounds__(256) rbm_gibbs_temp_lds_kernel(GibbsTempArgs A) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    rbm_gibbs_lds_body<R, RGH, RGV, GIVEN, false, true>(gibbs_temp_view(A), blockIdx.x * R, smem);
+}
+template <bool GIVEN>
+__global__ void __launch_bounds__(512) rbm_gibbs_temp_mfma_kernel(GibbsTempArgs A) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    rbm_gibbs_mfma_body<GIVEN, false, true>(gibbs_temp_view(A), blockIdx.x * GM_ROWS, smem);
+}
+
+template <typename K>
+static bool gibbs_temp_raise(K kernel, bool (&flags)[64]) {   // dynamic LDS above 64 KB: once per instantiation and device
+    bool& raised = mnn_dev_flag(flags);
+    if (!raised) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        raised = true;
+    }
+    return true;
+}
+template <int R, int RGH, int RGV, bool GIVEN>
+static bool launch_gibbs_temp_lds(hipStream_t st, const GibbsTempArgs& A) {
+    static bool raised_[64];
+    if (rbm_lds_resident_bytes(R, A.D, A.Hn) > 158 * 1024 || !gibbs_temp_raise(&rbm_gibbs_temp_lds_kernel<R, RGH, RGV, GIVEN>, raised_)) return false;
+    hipLaunchKernelGGL((rbm_gibbs_temp_lds_kernel<R, RGH, RGV, GIVEN>), dim3(cdiv(A.N, R)), dim3(256), rbm_lds_resident_bytes(R, A.D, A.Hn), st, A);
+    return true;
+}
+template <bool GIVEN>
+static int rbm_gibbs_temp_launch_t(mnn_stream_t s, GibbsTempArgs& A, void* workspace) {
+    const int N = A.N, D = A.D, Hn = A.Hn;
+    const size_t codes_lds = GIVEN ? (size_t)RBM_R * ((D + 3) & ~3) : 0;
+    hipStream_t st = (hipStream_t)s;
+    if (N < 2048 && Hn <= 256 && D <= 256 && getenv("MNN_RBM_STREAM_W") == nullptr) {
+        const int gh = 256 / Hn, gv = 256 / D;
+        const bool done = gv >= 2 ? (gh >= 2 ? launch_gibbs_temp_lds<2, 1, 1, GIVEN>(st, A) : launch_gibbs_temp_lds<2, 2, 1, GIVEN>(st, A))
+                                  : (gh >= 2 ? launch_gibbs_temp_lds<2, 1, 2, GIVEN>(st, A) : launch_gibbs_temp_lds<2, 2, 2, GIVEN>(st, A));
+        if (done) {
+            MNN_LAUNCH_CHECK();
+            return MNN_OK;
+        }
+    }
+    if (gibbs_mfma_lds_bytes(D, Hn) <= 158 * 1024 && getenv("MNN_RBM_NO_MFMA") == nullptr) {
+        static bool raised_[64];
+        MNN_REQUIRE(gibbs_temp_raise(&rbm_gibbs_temp_mfma_kernel<GIVEN>, raised_), "mnn_rbm_gibbs_temp: cannot raise the dynamic LDS limit");
+        hipLaunchKernelGGL(rbm_gibbs_temp_mfma_kernel<GIVEN>, dim3(cdiv(N, GM_ROWS)), dim3(512), gibbs_mfma_lds_bytes(D, Hn), st, A);
+        MNN_LAUNCH_CHECK();
+        return MNN_OK;
+    }
+    int rc = mnn_transpose(s, A.W, MNN_F32, D, Hn, Hn, workspace, MNN_F32, D);
+    if (rc != MNN_OK) return rc;
+    A.Wt = (const float*)workspace;
+    static bool raised_s_[64];
+    MNN_REQUIRE(gibbs_temp_raise(&rbm_gibbs_temp_stream_kernel<GIVEN>, raised_s_), "mnn_rbm_gibbs_temp: cannot raise the dynamic LDS limit");
+    hipLaunchKernelGGL(rbm_gibbs_temp_stream_kernel<GIVEN>, dim3(cdiv(N, RBM_R)), dim3(256), rbm_lds_bytes(D, Hn) + codes_lds, st, A);
+    MNN_LAUNCH_CHECK();
+    return MNN_OK;
+}
+
+extern "C" int mnn_rbm_gibbs_temp(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
+                                  const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v,
+                                  uint8_t* v_out, void* workspace, const uint8_t* given, int ld_given, float temperature) {
+    MNN_REQUIRE(temperature > 0.f && temperature <= 3.0e38f, "mnn_rbm_gibbs_temp: the temperature is a positive finite number (%g)", (double)temperature);
+    if (temperature == 1.0f)          // the untempered kernels, bit for bit and launch for launch
+        return rbm_gibbs_launch(s, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, workspace, nullptr, given, ld_given);
+    MNN_REQUIRE(N > 0 && D > 0 && Hn > 0 && k >= 0, "mnn_rbm_gibbs: bad sizes N=%d D=%d Hn=%d k=%d", N, D, Hn, k);
+    MNN_REQUIRE(v0 && W && bh && bv && workspace, "mnn_rbm_gibbs: null pointer");
+    MNN_REQUIRE((ld_bh == 0 || ld_bh >= Hn) && (ld_bv == 0 || ld_bv >= D), "mnn_rbm_gibbs: bad bias leading dimension");
+    MNN_REQUIRE(given == nullptr || ld_given >= D, "mnn_rbm_gibbs: ld_given=%d < D=%d", ld_given, D);
+    const size_t codes_lds = given != nullptr ? (size_t)RBM_R * ((D + 3) & ~3) : 0;
+    MNN_REQUIRE(rbm_lds_bytes(D, Hn) + codes_lds <= 160 * 1024, "mnn_rbm_gibbs: D+Hn too large for LDS");
+    GibbsTempArgs A{N, D, Hn, k, v0, W, nullptr, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, given, ld_given, temperature};
+    return given != nullptr ? rbm_gibbs_temp_launch_t<true>(s, A, workspace) : rbm_gibbs_temp_launch_t<false>(s, A, workspace);
+}
+
 extern "C" int mnn_rbm_gibbs_stepped(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
                                      const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v,
                                      uint8_t* v_out, void* workspace, const int* seed_step) {
@@ -199,7 +296,7 @@ extern "C" int mnn_rbm_gibbs_stepped(mnn_stream_t s, int N, int D, int Hn, int k
 extern "C" int mnn_rbm_gibbs(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
                              const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v,
                              uint8_t* v_out, void* workspace, const uint8_t* given, int ld_given) {
-    return rbm_gibbs_launch(s, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, workspace, nullptr, given, ld_given);
+    return mnn_rbm_gibbs_temp(s, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, workspace, given, ld_given, 1.0f);
 }
 
 // ----------------------------------------------------------------------------------------------

@@ -69,7 +69,15 @@ struct GibbsView {
     uint64_t seed; uint32_t row0; const uint32_t* row_ids; uint32_t sub0; float* p_v; uint8_t* v_out;
     const uint8_t* given; long ld_given;      // GIVEN only
     long rs; int es;                          // STRIDED only
+    float temp;                               // TEMPERED only: the chain samples exp(-E / temp)
 };
+// TEMPERED (a template flag of the three chain bodies, false = the code they always were): every conditional of the chain, hidden and visible,
+// is det_sigmoid(z / temp) with z the pre-activation including its bias -- the Gibbs chain of the RBM with energy E / temp.  A division, as in the
+// NADE scan: by a power of two it is exact, so that chain is bit for bit the untempered one on parameters scaled by 1 / temp.  Uniforms, counters
+// and clamps are untouched; p_v is the tempered probability the last visible phase drew from.
+template <bool TEMPERED> __device__ __forceinline__ float gv_sigmoid(const GibbsView& a, float z) {
+    return det_sigmoid(TEMPERED ? z / a.temp : z);
+}
 template <bool STRIDED> __device__ __forceinline__ size_t gv_cell(const GibbsView& a, int n, int d) {
     return STRIDED ? (size_t)n * a.rs + (size_t)d * a.es : (size_t)n * a.D + d;
 }
@@ -142,7 +150,7 @@ __device__ __forceinline__ uint32_t gv_code_quad(const GibbsView& a, int row, in
 // STREAMING form: one 256-thread workgroup owns RBM_R rows for the whole chain, W (and its transposed copy Wt) come from L2.
 // smem: f32 [RBM_R][Dp] | f32 [RBM_R][Hp] | GIVEN: u8 [RBM_R][Dp]
 // ----------------------------------------------------------------------------------------------
-template <bool GIVEN, bool STRIDED>
+template <bool GIVEN, bool STRIDED, bool TEMPERED = false>
 __device__ __forceinline__ void rbm_gibbs_stream_body(const GibbsView& a, const int n0, float* __restrict__ smem) {
     const int N = a.N, D = a.D, Hn = a.Hn, k = a.k;
     const uint64_t seed = a.seed;
@@ -181,7 +189,7 @@ __device__ __forceinline__ void rbm_gibbs_stream_body(const GibbsView& a, const 
         rbm_phase(vs, Dp, D, a.W, Hn, Hn, a.bh, a.ld_bh, n0, N, [&](int r, int j, float z) {
             const int n = n0 + r;
             if (n >= N) return;
-            const float p = det_sigmoid(z);
+            const float p = gv_sigmoid<TEMPERED>(a, z);
             const float u = philox_uniform1(seed, MNN_STREAM_RBM_H, rbm_rowid(a.row_ids, a.row0, n), a.sub0 + (uint32_t)it, (uint32_t)j);
             hs[r * Hp + j] = u < p ? 1.f : 0.f;
         });
@@ -190,7 +198,7 @@ __device__ __forceinline__ void rbm_gibbs_stream_body(const GibbsView& a, const 
         rbm_phase(hs, Hp, Hn, a.Wt, D, D, a.bv, a.ld_bv, n0, N, [&](int r, int d, float z) {
             const int n = n0 + r;
             if (n >= N) return;
-            const float p = det_sigmoid(z);
+            const float p = gv_sigmoid<TEMPERED>(a, z);
             float s;
             if (GIVEN && cs[r * Dp + d] != RBM_GIVEN_FREE) {
                 s = (float)cs[r * Dp + d];
@@ -211,7 +219,7 @@ __device__ __forceinline__ void rbm_gibbs_stream_body(const GibbsView& a, const 
 // ----------------------------------------------------------------------------------------------
 // W RESIDENT IN LDS, R rows per workgroup (sampling batches): see rbm.hip.  smem: f32 [R][Dp] | [R][Hp] | [D][Hn + 1]
 // ----------------------------------------------------------------------------------------------
-template <int R, int RGH, int RGV, bool GIVEN, bool STRIDED>        // rows per thread in the hidden / visible phase (R / RG row groups of n_out threads each)
+template <int R, int RGH, int RGV, bool GIVEN, bool STRIDED, bool TEMPERED = false>        // rows per thread in the hidden / visible phase (R / RG row groups of n_out threads each)
 __device__ __forceinline__ void rbm_gibbs_lds_body(const GibbsView& a, const int n0, float* __restrict__ smem) {
     const int N = a.N, D = a.D, Hn = a.Hn, k = a.k;
     const uint64_t seed = a.seed;
@@ -268,7 +276,7 @@ __device__ __forceinline__ void rbm_gibbs_lds_body(const GibbsView& a, const int
     for (int it = 0; it < k; ++it) {
         rbm_phase_lds<R, RGH>(vs, Dp, D, Ws, ldw, 1, Hn, [&](int r, int rl, int j, float acc) {
             if (n0 + r >= N) return;
-            const float p = det_sigmoid(acc + bhr[rl]);
+            const float p = gv_sigmoid<TEMPERED>(a, acc + bhr[rl]);
             const float u = philox_uniform1(seed, MNN_STREAM_RBM_H, idh[rl], sub0 + (uint32_t)it, (uint32_t)j);
             hs[r * Hp + j] = u < p ? 1.f : 0.f;
         });
@@ -277,7 +285,7 @@ __device__ __forceinline__ void rbm_gibbs_lds_body(const GibbsView& a, const int
         rbm_phase_lds<R, RGV>(hs, Hp, Hn, Ws, 1, ldw, D, [&](int r, int rl, int d, float acc) {
             const int n = n0 + r;
             if (n >= N) return;
-            const float p = det_sigmoid(acc + bvr[rl]);
+            const float p = gv_sigmoid<TEMPERED>(a, acc + bvr[rl]);
             float sv;
             if (GIVEN && cvr[rl] != RBM_GIVEN_FREE) {        // clamped: no Philox evaluation
                 sv = (float)cvr[rl];
@@ -306,7 +314,7 @@ static inline size_t rbm_lds_resident_bytes(int R, int D, int Hn) {
 // (four packed words next to bvr: no LDS, so the given form fits wherever the free one does); a quad whose four cells are all clamped skips its
 // Philox block
 // ----------------------------------------------------------------------------------------------
-template <bool GIVEN, bool STRIDED>
+template <bool GIVEN, bool STRIDED, bool TEMPERED = false>
 __device__ __forceinline__ void rbm_gibbs_mfma_body(const GibbsView& A, const int n0, float* __restrict__ smem) {
     const uint64_t seed = A.seed;
     const int N = A.N, D = A.D, Hn = A.Hn, ldw = Hn + 1;
@@ -410,7 +418,7 @@ __device__ __forceinline__ void rbm_gibbs_mfma_body(const GibbsView& A, const in
                     for (int e = 0; e < 4; ++e) {
                         const int j = min(j0 + e, Hn - 1);
                         const float bb = jt0 < 8 ? bhr[q][4 * g4 + e] : A.bh[(size_t)min(row_h, N - 1) * A.ld_bh + j];
-                        const float p = det_sigmoid(acc[q][4 * g4 + e] + bb);
+                        const float p = gv_sigmoid<TEMPERED>(A, acc[q][4 * g4 + e] + bb);
                         pk |= (u[e] < p && j0 + e < Hn ? 1u : 0u) << (8 * e);
                     }
                     *reinterpret_cast<uint32_t*>(hs + (32 * rt_h + r) * ph + j0) = pk;     // j0 % 4 == 0, ph % 4 == 0
@@ -440,7 +448,7 @@ __device__ __forceinline__ void rbm_gibbs_mfma_body(const GibbsView& A, const in
                 for (int e = 0; e < 4; ++e) {
                     const int d = d0 + e;
                     if (d >= D) continue;
-                    const float p = det_sigmoid(acc[4 * g4 + e] + (job < 8 ? bvr[4 * g4 + e] : A.bv[(size_t)min(row, N - 1) * A.ld_bv + d]));
+                    const float p = gv_sigmoid<TEMPERED>(A, acc[4 * g4 + e] + (job < 8 ? bvr[4 * g4 + e] : A.bv[(size_t)min(row, N - 1) * A.ld_bv + d]));
                     const uint8_t c = (uint8_t)(cq >> (8 * e));
                     const uint8_t sv = GIVEN && c != RBM_GIVEN_FREE ? c : (u[e] < p ? 1 : 0);
                     vs[(32 * rt + r) * pv + d] = sv;

@@ -30,6 +30,15 @@ __device__ __forceinline__ GibbsView gibbs_multi_view(const GibbsMultiArgs& A) {
                      j.given, A.rs_given, A.rs, A.es};
 }
 
+// a grouped launch with temperatures: the same table with one temperature per job behind it.  The kernels that take it are the TEMPERED
+// instantiations; a launch whose temperatures are all 1 never comes here (the kernels and the argument block below it are unchanged)
+struct GibbsMultiTempArgs { GibbsMultiArgs A; float temp[RBM_MULTI_MAX_JOBS]; };
+__device__ __forceinline__ GibbsView gibbs_multi_view(const GibbsMultiTempArgs& T) {
+    GibbsView v = gibbs_multi_view(T.A);
+    v.temp = T.temp[blockIdx.y];
+    return v;
+}
+
 template <int R, int RGH, int RGV, bool GIVEN>
 __global__ void __launch_bounds__(256) rbm_gibbs_multi_lds_kernel(GibbsMultiArgs A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -48,6 +57,22 @@ __global__ void __launch_bounds__(256) rbm_gibbs_multi_stream_kernel(GibbsMultiA
     rbm_gibbs_stream_body<GIVEN, true>(gibbs_multi_view(A), blockIdx.x * RBM_R, smem);
 }
 
+template <int R, int RGH, int RGV, bool GIVEN>
+__global__ void __launch_bounds__(256) rbm_gibbs_multi_temp_lds_kernel(GibbsMultiTempArgs T) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    rbm_gibbs_lds_body<R, RGH, RGV, GIVEN, true, true>(gibbs_multi_view(T), blockIdx.x * R, smem);
+}
+template <bool GIVEN>
+__global__ void __launch_bounds__(512) rbm_gibbs_multi_temp_mfma_kernel(GibbsMultiTempArgs T) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    rbm_gibbs_mfma_body<GIVEN, true, true>(gibbs_multi_view(T), blockIdx.x * GM_ROWS, smem);
+}
+template <bool GIVEN>
+__global__ void __launch_bounds__(256) rbm_gibbs_multi_temp_stream_kernel(GibbsMultiTempArgs T) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    rbm_gibbs_stream_body<GIVEN, true, true>(gibbs_multi_view(T), blockIdx.x * RBM_R, smem);
+}
+
 // dynamic LDS above 64 KB has to be asked for once per kernel and device
 static bool raise_lds(const void* fn, bool (&flags)[64]) {
     bool& raised = mnn_dev_flag(flags);
@@ -61,28 +86,37 @@ static bool raise_lds(const void* fn, bool (&flags)[64]) {
     return true;
 }
 
+// T == nullptr: the untempered kernels; otherwise the TEMPERED ones with T's temperatures
 template <int R, int RGH, int RGV, bool GIVEN>
-static bool launch_multi_lds(hipStream_t st, const GibbsMultiArgs& A, int njobs) {
-    static bool raised_[64];
+static bool launch_multi_lds(hipStream_t st, const GibbsMultiArgs& A, int njobs, const GibbsMultiTempArgs* T) {
+    static bool raised_[64], raised_t_[64];
+    const dim3 grid(cdiv(A.N, R), njobs);
+    const size_t lds = rbm_lds_resident_bytes(R, A.D, A.Hn);
+    if (T != nullptr) {
+        if (!raise_lds(reinterpret_cast<const void*>(&rbm_gibbs_multi_temp_lds_kernel<R, RGH, RGV, GIVEN>), raised_t_)) return false;
+        hipLaunchKernelGGL((rbm_gibbs_multi_temp_lds_kernel<R, RGH, RGV, GIVEN>), grid, dim3(256), lds, st, *T);
+        return true;
+    }
     if (!raise_lds(reinterpret_cast<const void*>(&rbm_gibbs_multi_lds_kernel<R, RGH, RGV, GIVEN>), raised_)) return false;
-    hipLaunchKernelGGL((rbm_gibbs_multi_lds_kernel<R, RGH, RGV, GIVEN>), dim3(cdiv(A.N, R), njobs), dim3(256), rbm_lds_resident_bytes(R, A.D, A.Hn), st, A);
+    hipLaunchKernelGGL((rbm_gibbs_multi_lds_kernel<R, RGH, RGV, GIVEN>), grid, dim3(256), lds, st, A);
     return true;
 }
 
 // the instantiation for this shape: the choice of rbm.hip's try_gibbs_lds
 template <bool GIVEN>
-static bool try_multi_lds(hipStream_t st, const GibbsMultiArgs& A, int njobs) {
+static bool try_multi_lds(hipStream_t st, const GibbsMultiArgs& A, int njobs, const GibbsMultiTempArgs* T) {
     const int gh = 256 / A.Hn, gv = 256 / A.D;
     if (rbm_lds_resident_bytes(2, A.D, A.Hn) > 158 * 1024) return false;
-    return gv >= 2 ? (gh >= 2 ? launch_multi_lds<2, 1, 1, GIVEN>(st, A, njobs) : launch_multi_lds<2, 2, 1, GIVEN>(st, A, njobs))
-                   : (gh >= 2 ? launch_multi_lds<2, 1, 2, GIVEN>(st, A, njobs) : launch_multi_lds<2, 2, 2, GIVEN>(st, A, njobs));
+    return gv >= 2 ? (gh >= 2 ? launch_multi_lds<2, 1, 1, GIVEN>(st, A, njobs, T) : launch_multi_lds<2, 2, 1, GIVEN>(st, A, njobs, T))
+                   : (gh >= 2 ? launch_multi_lds<2, 1, 2, GIVEN>(st, A, njobs, T) : launch_multi_lds<2, 2, 2, GIVEN>(st, A, njobs, T));
 }
 
 extern "C" int mnn_transpose(mnn_stream_t s, const void* in, int in_dtype, int R, int C, int ld_in, void* out, int out_dtype, int ld_out);
 
-extern "C" int mnn_rbm_gibbs_multi(mnn_stream_t s, int njobs, const mnn_rbm_gibbs_job* jobs, int N, int D, int Hn, int k, int ld_bh, int ld_bv,
-                                   uint32_t row0, const uint32_t* row_ids, uint32_t sub0, const int* seed_step, long row_stride, int elem_stride,
-                                   long given_row_stride, void* workspace) {
+// temps: NULL (every job at temperature 1) or njobs positive finite temperatures; all of them 1 is NULL
+extern "C" int mnn_rbm_gibbs_multi_temps(mnn_stream_t s, int njobs, const mnn_rbm_gibbs_job* jobs, int N, int D, int Hn, int k, int ld_bh, int ld_bv,
+                                         uint32_t row0, const uint32_t* row_ids, uint32_t sub0, const int* seed_step, long row_stride, int elem_stride,
+                                         long given_row_stride, void* workspace, const float* temps) {
     MNN_REQUIRE(njobs > 0 && njobs <= RBM_MULTI_MAX_JOBS && jobs, "mnn_rbm_gibbs_multi: 1..%d jobs", RBM_MULTI_MAX_JOBS);
     MNN_REQUIRE(N > 0 && D > 0 && Hn > 0 && k >= 0, "mnn_rbm_gibbs_multi: bad sizes N=%d D=%d Hn=%d k=%d", N, D, Hn, k);
     MNN_REQUIRE((ld_bh == 0 || ld_bh >= Hn) && (ld_bv == 0 || ld_bv >= D), "mnn_rbm_gibbs_multi: bad bias leading dimension");
@@ -102,27 +136,42 @@ extern "C" int mnn_rbm_gibbs_multi(mnn_stream_t s, int njobs, const mnn_rbm_gibb
     A.N = N; A.D = D; A.Hn = Hn; A.k = k; A.ld_bh = ld_bh; A.ld_bv = ld_bv;
     A.row0 = row0; A.row_ids = row_ids; A.sub0 = sub0; A.seed_step = seed_step;
     A.rs = row_stride; A.rs_given = given_row_stride; A.es = elem_stride;
+    bool tempered = false;
+    GibbsMultiTempArgs TA;
+    memset(&TA, 0, sizeof(TA));
+    for (int j = 0; j < njobs && temps != nullptr; ++j) {
+        MNN_REQUIRE(temps[j] > 0.f && temps[j] <= 3.0e38f, "mnn_rbm_gibbs_multi_temps: job %d: the temperature is a positive finite number (%g)", j, (double)temps[j]);
+        TA.temp[j] = temps[j];
+        tempered = tempered || temps[j] != 1.0f;
+    }
+    const GibbsMultiTempArgs* T = tempered ? &TA : nullptr;      // (the streaming form completes A -- and TA.A -- below)
+    TA.A = A;
     const size_t codes_lds = given ? (size_t)RBM_R * ((D + 3) & ~3) : 0;
     MNN_REQUIRE(rbm_lds_bytes(D, Hn) + codes_lds <= 160 * 1024, "mnn_rbm_gibbs_multi: D+Hn too large for LDS");
     hipStream_t st = (hipStream_t)s;
     // the dispatch of mnn_rbm_gibbs, with a job dimension on the grid
     if (N < 2048 && Hn <= 256 && D <= 256 && getenv("MNN_RBM_STREAM_W") == nullptr) {
         // sampling-sized batches: W resident in LDS, two rows per workgroup, every workgroup loads its job's W
-        if (given ? try_multi_lds<true>(st, A, njobs) : try_multi_lds<false>(st, A, njobs)) {
+        if (given ? try_multi_lds<true>(st, A, njobs, T) : try_multi_lds<false>(st, A, njobs, T)) {
             MNN_LAUNCH_CHECK();
             return MNN_OK;
         }
     }
     if (gibbs_mfma_lds_bytes(D, Hn) <= 158 * 1024 && getenv("MNN_RBM_NO_MFMA") == nullptr) {
         // training batches: the chains on the f32 matrix cores, 64 rows per workgroup
-        static bool raised_[64], raised_g_[64];
-        const void* fn = given ? reinterpret_cast<const void*>(&rbm_gibbs_multi_mfma_kernel<true>) : reinterpret_cast<const void*>(&rbm_gibbs_multi_mfma_kernel<false>);
-        bool& raised = given ? mnn_dev_flag(raised_g_) : mnn_dev_flag(raised_);
+        static bool raised_[64], raised_g_[64], raised_t_[64], raised_tg_[64];
+        const void* fn = tempered ? (given ? reinterpret_cast<const void*>(&rbm_gibbs_multi_temp_mfma_kernel<true>) : reinterpret_cast<const void*>(&rbm_gibbs_multi_temp_mfma_kernel<false>))
+                                  : (given ? reinterpret_cast<const void*>(&rbm_gibbs_multi_mfma_kernel<true>) : reinterpret_cast<const void*>(&rbm_gibbs_multi_mfma_kernel<false>));
+        bool& raised = tempered ? (given ? mnn_dev_flag(raised_tg_) : mnn_dev_flag(raised_t_)) : (given ? mnn_dev_flag(raised_g_) : mnn_dev_flag(raised_));
         if (!raised) {
             MNN_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             raised = true;
         }
-        if (given)
+        if (tempered && given)
+            hipLaunchKernelGGL(rbm_gibbs_multi_temp_mfma_kernel<true>, dim3(cdiv(N, GM_ROWS), njobs), dim3(512), gibbs_mfma_lds_bytes(D, Hn), st, TA);
+        else if (tempered)
+            hipLaunchKernelGGL(rbm_gibbs_multi_temp_mfma_kernel<false>, dim3(cdiv(N, GM_ROWS), njobs), dim3(512), gibbs_mfma_lds_bytes(D, Hn), st, TA);
+        else if (given)
             hipLaunchKernelGGL(rbm_gibbs_multi_mfma_kernel<true>, dim3(cdiv(N, GM_ROWS), njobs), dim3(512), gibbs_mfma_lds_bytes(D, Hn), st, A);
         else
             hipLaunchKernelGGL(rbm_gibbs_multi_mfma_kernel<false>, dim3(cdiv(N, GM_ROWS), njobs), dim3(512), gibbs_mfma_lds_bytes(D, Hn), st, A);
@@ -136,12 +185,24 @@ extern "C" int mnn_rbm_gibbs_multi(mnn_stream_t s, int njobs, const mnn_rbm_gibb
         if (rc != MNN_OK) return rc;
         A.job[j].Wt = wt;
     }
-    if (given)
+    TA.A = A;
+    if (tempered && given)
+        hipLaunchKernelGGL(rbm_gibbs_multi_temp_stream_kernel<true>, dim3(cdiv(N, RBM_R), njobs), dim3(256), rbm_lds_bytes(D, Hn) + codes_lds, st, TA);
+    else if (tempered)
+        hipLaunchKernelGGL(rbm_gibbs_multi_temp_stream_kernel<false>, dim3(cdiv(N, RBM_R), njobs), dim3(256), rbm_lds_bytes(D, Hn), st, TA);
+    else if (given)
         hipLaunchKernelGGL(rbm_gibbs_multi_stream_kernel<true>, dim3(cdiv(N, RBM_R), njobs), dim3(256), rbm_lds_bytes(D, Hn) + codes_lds, st, A);
     else
         hipLaunchKernelGGL(rbm_gibbs_multi_stream_kernel<false>, dim3(cdiv(N, RBM_R), njobs), dim3(256), rbm_lds_bytes(D, Hn), st, A);
     MNN_LAUNCH_CHECK();
     return MNN_OK;
+}
+
+extern "C" int mnn_rbm_gibbs_multi(mnn_stream_t s, int njobs, const mnn_rbm_gibbs_job* jobs, int N, int D, int Hn, int k, int ld_bh, int ld_bv,
+                                   uint32_t row0, const uint32_t* row_ids, uint32_t sub0, const int* seed_step, long row_stride, int elem_stride,
+                                   long given_row_stride, void* workspace) {
+    return mnn_rbm_gibbs_multi_temps(s, njobs, jobs, N, D, Hn, k, ld_bh, ld_bv, row0, row_ids, sub0, seed_step, row_stride, elem_stride,
+                                     given_row_stride, workspace, nullptr);
 }
 
 // ----------------------------------------------------------------------------------------------

@@ -197,18 +197,26 @@ class FeedbackRnnSampler:
         self.num_tracks = len(generators)
         self.concurrent = True       # the M generators of a step run on M streams (parallel branches of the captured scan)
 
-    def generate(self, x_u8, num_steps, given=None):
+    def _temperature(self, temperature):
+        """One temperature or one per generator (common.sampling_temperature); None only where every generator is a NADE."""
+        from .common import sampling_temperature
+        return sampling_temperature(temperature, self.num_tracks, allow_none=all(isinstance(g, RnnNade) for g in self.generators))
+
+    def generate(self, x_u8, num_steps, given=None, temperature=1.0):
         """x_u8 [B,Ti,P,M] intro piano-rolls -> samples u8 [B,num_steps,P,M].  One hipGraph replay per call on the
         device (common.ScanGraphs): the M generators and the feedback module step inside the same captured scan.
-        given (optional): codes u8 [B, num_steps, P, M] (common.given_codes), see generate_encoded."""
-        from .common import ScanGraphs
+        given (optional): codes u8 [B, num_steps, P, M] (common.given_codes), see generate_encoded.
+        temperature: one for all generators or generator m's own, temperature[m]; 1.0 is the call (and the captured scan) without it."""
+        from .common import ScanGraphs, temperature_key
+        temperature = self._temperature(temperature)
         if not ScanGraphs.enabled(x_u8):
-            return self._generate_scan(x_u8, num_steps, given)
+            return self._generate_scan(x_u8, num_steps, given, temperature)
         if getattr(self, "_scan_graphs", None) is None:
             self._scan_graphs = ScanGraphs()
         key = (tuple(x_u8.shape), int(num_steps), tuple((g.seed, g.row0) for g in self.generators))
         if given is not None:
             key = key + ("given",)
+        key = key + temperature_key(temperature)
 
         def stale():
             for g in self.generators:
@@ -218,11 +226,11 @@ class FeedbackRnnSampler:
 
         def scan(sx, sg=None):
             stale()                                    # pack inside the graph: a replay always sees the current weights
-            return self._generate_scan(sx, num_steps, sg)
+            return self._generate_scan(sx, num_steps, sg, temperature)
 
         def warm(sx, sg=None):
             n = min(int(num_steps), 2)
-            return self._generate_scan(sx, n, None if sg is None else sg[:, :n].contiguous())
+            return self._generate_scan(sx, n, None if sg is None else sg[:, :n].contiguous(), temperature)
 
         return self._scan_graphs.run(key, x_u8, scan, warm, stale, extra=given)
 
@@ -232,19 +240,22 @@ class FeedbackRnnSampler:
         ops.dense_det(list(jobs))
         return [g._state_from_dense(o, tuple(st)) for g, o, st in zip(self.generators, outs, rnn_states)]
 
-    def _generate_scan(self, x_u8, num_steps, given=None):
+    def _generate_scan(self, x_u8, num_steps, given=None, temperature=1.0):
         B, Ti, P, M = x_u8.shape
         assert M == self.num_tracks
         enc = torch.cat([torch.zeros((B, 1, P, M), device=x_u8.device, dtype=torch.uint8), x_u8], 1)      # multi_encoder_nn.py:73-76
-        return self.generate_encoded([enc[..., i] for i in range(M)], num_steps, given)
+        return self.generate_encoded([enc[..., i] for i in range(M)], num_steps, given, temperature)
 
-    def generate_encoded(self, enc_tracks, num_steps, given=None):
+    def generate_encoded(self, enc_tracks, num_steps, given=None, temperature=1.0):
         """The scan on per-track ENCODED inputs (multinn_feedback.py:120-173 between the encoders): enc_tracks = M x u8
         [B, Ti+1, E] (zero first step included) -> sampled codes u8 [B, num_steps, E, M]; the caller decodes them through
         its encoders (identity for PassEncoder).  given (optional): codes u8 [B, num_steps, E, M] (common.given_codes).  NADE
         generators clamp inside their sampling kernels; an RBM generator's track is pasted over its sample before the feedback step
-        (whole tracks only: the mode classes refuse partial masks on RBM generators)."""
+        (whole tracks only: the mode classes refuse partial masks on RBM generators).  temperature: as generate; it acts on the generators'
+        samples of the codes."""
         M = self.num_tracks
+        temperature = self._temperature(temperature)
+        temps = list(temperature) if isinstance(temperature, tuple) else [temperature] * M          # generator i samples at temps[i]
         enc_tracks = [e.contiguous() for e in enc_tracks]            # (views of a [B, T, P, M] roll have inner stride M)
         B, _, P = enc_tracks[0].shape
         dev = enc_tracks[0].device
@@ -291,7 +302,7 @@ class FeedbackRnnSampler:
                 views = [out[:, s, :, i] for i in range(M)]                                          # u8 [B, P] views of track i (element stride M)
                 ops.nade_sample_multi([dict(bias=states[i].dense, w_enc=g.store["nade/w_enc"][0], w_dec=g.store["nade/w_dec"][0], seed=g.seed,
                                             samples=views[i], given=None if given is None else given[:, s, :, i])
-                                       for i, g in enumerate(gs)], P, Hn, 1.0, gs[0].row0, s)
+                                       for i, g in enumerate(gs)], P, Hn, temperature, gs[0].row0, s)
                 st = out[:, s].reshape(B, P * M)                                                     # [B, P*M] view, feature p*M+m
                 fb, fb_state = self.feedback.single(st if fb_strided else st.contiguous(), fb_state)
                 res = det_steps([g._stack for g in gs], views, [list(s_.rnn_state) for s_ in states], [fb] * M)
@@ -317,12 +328,13 @@ class FeedbackRnnSampler:
                         g._gen_step = s
                         g._last_dense = states[i].dense
                         gi = None if given is None else given[:, s, :, i]
+                        kw = {} if temps[i] == 1.0 else dict(temperature=temps[i])
                         if gi is None:
-                            smp, _ = g.sample_single(None, states[i])
+                            smp, _ = g.sample_single(None, states[i], **kw)
                         elif isinstance(g, RnnNade):
-                            smp, _ = g.sample_single(None, states[i], given=gi.contiguous())
+                            smp, _ = g.sample_single(None, states[i], given=gi.contiguous(), **kw)
                         else:                               # a wholly given track pasted over the RBM's sample
-                            smp, _ = g.sample_single(None, states[i])
+                            smp, _ = g.sample_single(None, states[i], **kw)
                             smp = torch.where(gi != 255, gi, smp)
                     samples.append(smp)
                 if par:

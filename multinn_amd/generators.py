@@ -19,7 +19,7 @@ import weakref
 import torch
 
 from . import ops
-from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, glorot_uniform, zeros_init, default_device, capture_train_step
+from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, sampling_temperature, temperature_key, glorot_uniform, zeros_init, default_device, capture_train_step
 from .training import compute_gradients, world, dp_active, AdamOptimizer
 from ._lib import MnnUnsupported
 
@@ -866,7 +866,7 @@ class Generator(Model):
         return self._outputs
 
     @abc.abstractmethod
-    def generate(self, x, num_steps, given=None):
+    def generate(self, x, num_steps, given=None, temperature=1.0):
         ...
 
     def pretrain(self, optimizer, lr, run_optimizer=True):
@@ -1009,7 +1009,12 @@ class RnnEstimator(Generator):
             return self._det_state(h, st)
         return self._get_state(inputs, initial_state=initial_state, last_outputs=True)
 
-    def _scan_in_one_call(self, x, num_steps, given=None):
+    def _temperature(self, temperature):
+        """generate's `temperature`, normalised (common.sampling_temperature): NADE estimators take None and one value per track (of a
+        MultiNADE, or by visible index for the one NADE of joint mode), RBM estimators a positive number (per track: RnnMultiRBM)."""
+        raise NotImplementedError
+
+    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0):
         return None                         # estimators without a one-call scan (RnnRBM) step through sample_single / single_step
 
     def _det_single_step(self, inputs, initial_state, x2=None):
@@ -1092,8 +1097,10 @@ class RnnEstimator(Generator):
         return buf
 
     # -- sampling -------------------------------------------------------------------------------
-    def generate(self, x, num_steps, given=None):
+    def generate(self, x, num_steps, given=None, temperature=1.0):
         """rnn_estimator.py:271-298: intro pass, then num_steps x {sample_single, single_step}.
+        temperature: a positive float, one per track where the estimator has tracks, or (NADE estimators) None for threshold decoding --
+        common.sampling_temperature.  1.0 is the call without it: the same kernels, bits and captured scan.
         x [B,Ti,Din]; returns samples u8 [B,num_steps,num_output].  On the device the whole scan is ONE hipGraph
         replay (captured per shape / num_steps / seed, see common.ScanGraphs); same kernels, same RNG counters, same bits.
         given (optional): codes u8 [B, num_steps, num_output] in the generator's feature order (common.given_codes): a clamped visible is
@@ -1103,32 +1110,34 @@ class RnnEstimator(Generator):
             if given.dtype != torch.uint8 or tuple(given.shape) != (x.shape[0], int(num_steps), n_out):
                 raise ValueError(f"given must be u8 [{x.shape[0]}, {int(num_steps)}, {n_out}], got {given.dtype} {tuple(given.shape)}")
             given = given.contiguous()
+        temperature = self._temperature(temperature)
         if not ScanGraphs.enabled(x):
-            return self._generate_scan(x, num_steps, given)
+            return self._generate_scan(x, num_steps, given, temperature)
         if getattr(self, "_scan_graphs", None) is None:
             self._scan_graphs = ScanGraphs()
         key = (tuple(x.shape), x.dtype, int(num_steps), self.seed, self.row0)
         if given is not None:
             key = key + ("given",)                     # a new given of the same shape replays the same graph
+        key = key + temperature_key(temperature)       # (baked into the captured launches; nothing at 1.0: the scan captured without it)
 
         def scan(sx, sg=None):
             self._packed_step = -1                     # pack inside the graph: a replay always sees the current weights
-            return self._generate_scan(sx, num_steps, sg)
+            return self._generate_scan(sx, num_steps, sg, temperature)
 
         def after():
             self._packed_step = -1                     # the packed copies now live in the graph's pool
 
         def warm(sx, sg=None):
             n = min(int(num_steps), 2)
-            return self._generate_scan(sx, n, None if sg is None else sg[:, :n].contiguous())
+            return self._generate_scan(sx, n, None if sg is None else sg[:, :n].contiguous(), temperature)
 
         return self._scan_graphs.run(key, x, scan, warm, after, extra=given)
 
-    def _generate_scan(self, x, num_steps, given=None):
+    def _generate_scan(self, x, num_steps, given=None, temperature=1.0):
         self._materialize(x.shape[-1])
         self._rnn.build_cell(False)
         if self.det_sampling:
-            whole = self._scan_in_one_call(x, num_steps, given)     # LSTM-(Multi)NADE on a byte piano-roll: mnn_generate_scan runs the whole scan
+            whole = self._scan_in_one_call(x, num_steps, given, temperature)     # LSTM-(Multi)NADE on a byte piano-roll: mnn_generate_scan runs the whole scan
             if whole is not None:
                 return whole
             state = self.steps(x)
@@ -1139,10 +1148,10 @@ class RnnEstimator(Generator):
         out = []
         for s in range(num_steps):
             self._gen_step = s
-            if given is None:
-                samples, _ = self.sample_single(intro, state)
-            else:
-                samples, _ = self.sample_single(intro, state, given=given[:, s])
+            kw = {} if temperature == 1.0 else dict(temperature=temperature)
+            if given is not None:
+                kw["given"] = given[:, s]
+            samples, _ = self.sample_single(intro, state, **kw)
             state = self.single_step(samples, state)
             intro = samples
             out.append(samples)
@@ -1631,7 +1640,17 @@ class RnnNade(RnnEstimator):
             out = self._dense(y.view(T * B, -1))[flat_index(lengths, B, T, inputs.device)]
         return self._state_from_dense(out, tuple((c.clone(), h.clone()) for c, h in final))
 
-    def _scan_in_one_call(self, x, num_steps, given=None):
+    def _temperature(self, temperature):
+        if self.num_tracks > 1:                        # a MultiNADE: one NADE, one temperature per track
+            return sampling_temperature(temperature, self.num_tracks)
+        # one NADE: a sequence of n values (n divides the visibles) gives visible i the temperature [i % n] -- the tracks of joint mode,
+        # whose NADE orders its visibles p M + m (the mode has checked n == M)
+        n = None
+        if hasattr(temperature, "__len__") and len(temperature) > 0 and self.num_dims % len(temperature) == 0:
+            n = len(temperature)
+        return sampling_temperature(temperature, n, what="temperature (one NADE: a sequence whose length divides its visibles)")
+
+    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0):
         """rnn_estimator.py:271-298 through ONE C-ABI call (mnn_generate_scan: intro pass + num_steps x {NADE sample, LSTM step, Dense} enqueued
         by the library's own host loop) when the inputs are the byte piano-roll itself; the same kernels and bits as the step-by-step path.
         given: the scan's codes u8 [B, num_steps, num_output] (generate)."""
@@ -1640,8 +1659,8 @@ class RnnNade(RnnEstimator):
         pre = self._rnn.prefix
         layers = [(self.store[f"{pre}/cell_{l}/kernel"], self.store[f"{pre}/cell_{l}/bias"]) for l in range(len(self._rnn.num_units))]
         return ops.generate_scan(x.contiguous(), num_steps, layers, self.store["dense/kernel"], self._det_fc_bias(), self.num_tracks, self.num_dims,
-                                 self.num_hidden[-1], self.store["nade/w_enc"], self.store["nade/w_dec"], 1.0, self.seed, self.row0, given=given,
-                                 state0=self._state0(x.shape[0], torch.float32))      # (learn_zero_state: tiled on the device here, an input array of the scan)
+                                 self.num_hidden[-1], self.store["nade/w_enc"], self.store["nade/w_dec"], temperature, self.seed, self.row0, given=given,
+                                 state0=self._state0(x.shape[0], torch.float32), by_visible=self.num_tracks == 1)      # (learn_zero_state: tiled on the device here, an input array of the scan)
 
     def _det_fc_bias(self):
         if not self.internal_bias:
@@ -1679,14 +1698,17 @@ class RnnNade(RnnEstimator):
 
     def sample_single(self, inputs, state, temperature=1.0, given=None):
         """rnn_nade.py:304-318 / rnn_multinade.py:295-317: returns (sample u8 [B,num_output], nll).  given (optional): codes u8
-        [B, num_output] (ops.nade_sample): clamped visibles are emitted as given, nll is that of the emitted vector."""
+        [B, num_output] (ops.nade_sample): clamped visibles are emitted as given, nll is that of the emitted vector.
+        temperature: a float, None (threshold draws), or a sequence -- per track of a MultiNADE, by visible index modulo its length for
+        the one NADE; the returned nll stays the model's own."""
         M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
         out = state.dense if getattr(state, "dense", None) is not None else self._last_dense
         Bn = out.shape[0]
         smp = torch.empty((Bn, M * D), device=out.device, dtype=torch.uint8)
         nll = torch.empty((M, Bn), device=out.device)
         ops.nade_sample(out, self.store["nade/w_enc"], self.store["nade/w_dec"], M, D, Hn, temperature, self.seed, self.row0,
-                        getattr(self, "_gen_step", 0), smp, track_minor=(M > 1), nll=nll, given=None if given is None else given.contiguous())
+                        getattr(self, "_gen_step", 0), smp, track_minor=(M > 1), nll=nll, given=None if given is None else given.contiguous(),
+                        by_visible=M == 1)
         return smp, (nll[0] if M == 1 else [nll[m] for m in range(M)])
 
 
@@ -1974,12 +1996,16 @@ class RnnRBM(RnnEstimator):
         h, new = self._stack.single_step(x, [(c, hh) for c, hh in initial_state.rnn_state])
         return self._state_from_out(self._biases(h.contiguous()), tuple(new))
 
-    def sample_single(self, inputs, state, given=None):
-        """rnn_rbm.py:283-297 with k = rbm.k (R1): returns (sample u8, cond_prob).  given (optional): codes u8 [B, D] (a step slice of
+    def _temperature(self, temperature):
+        return sampling_temperature(temperature, allow_none=False, allow_sequence=False)
+
+    def sample_single(self, inputs, state, given=None, temperature=1.0):
+        """rnn_rbm.py:283-297 with k = rbm.k (R1): returns (sample u8, cond_prob).  temperature: the chain of exp(-E / T), cond_prob the
+        tempered probability.  given (optional): codes u8 [B, D] (a step slice of
         generate's [B, num_steps, D] is read in place): the clamped Gibbs chain -- clamped visibles are emitted as given, every free one is
         sampled conditioned on all of them (RBM.sample); cond_prob is sigmoid(logit) at every visible."""
         p_v, v = self._rbm.sample(inputs[:, :self.num_dims], state.b_enc, state.b_dec, self._k, self.seed, self.row0, None,
-                                  getattr(self, "_gen_step", 0) * max(self._k, 1), given=given)
+                                  getattr(self, "_gen_step", 0) * max(self._k, 1), given=given, temperature=temperature)
         return v, p_v
 
     def pretrain(self, optimizer, lr, run_optimizer=True):
@@ -2262,15 +2288,18 @@ class RnnMultiRBM(RnnRBM):
                        dict(x=h, W=self.store["Wuv"], bias=bv, out=out[:, M * Hn:self.n_out])])
         return self._state_from_out(out, tuple(rnn_state))
 
-    def _generate_scan(self, x, num_steps, given=None):
+    def _temperature(self, temperature):
+        return sampling_temperature(temperature, self.num_tracks, allow_none=False)
+
+    def _generate_scan(self, x, num_steps, given=None, temperature=1.0):
         self._det_bias = True              # the first Dense of this scan forms the internal bias vectors, the later ones reuse them
         try:
-            return super()._generate_scan(x, num_steps, given)
+            return super()._generate_scan(x, num_steps, given, temperature)
         finally:
             self._det_bias = None
 
-    def sample_single(self, inputs, state, given=None):
-        """The M chains of a sampling step in ONE grouped launch: the previous row is read, and the new one written, in composer layout in
+    def sample_single(self, inputs, state, given=None, temperature=1.0):
+        """The M chains of a sampling step in ONE grouped launch (temperature: one for all, or track m's chain at temperature[m]): the previous row is read, and the new one written, in composer layout in
         place (element stride M), track m with seed + m.  Returns (sample u8 [B, M * D], cond_prob f32 [B, M * D]).  given (optional):
         codes u8 [B, M * D] in the same layout (a step slice of generate's block is read in place): every track runs the clamped chain."""
         M, D = self.num_tracks, self.num_dims
@@ -2281,7 +2310,7 @@ class RnnMultiRBM(RnnRBM):
         p_v = torch.empty((Bn, M * D), device=v0.device)
         jobs = [dict(v0=v0[:, m::M], W=r.W, bh=state.b_enc[m], bv=state.b_dec[m], seed=self.seed + m, p_v=p_v[:, m::M], v_out=smp[:, m::M],
                      given=None if given is None else given[:, m::M]) for m, r in enumerate(self._rbms)]
-        ops.rbm_gibbs_multi(jobs, self._k, self.row0, None, getattr(self, "_gen_step", 0) * max(self._k, 1))
+        ops.rbm_gibbs_multi(jobs, self._k, self.row0, None, getattr(self, "_gen_step", 0) * max(self._k, 1), temperature=temperature)
         return smp, p_v
 
     def pretrain(self, optimizer, lr, run_optimizer=True):

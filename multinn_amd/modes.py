@@ -24,7 +24,7 @@ import os
 
 import torch
 
-from .common import Model, capture_train_step, given_codes, given_tracks
+from .common import Model, capture_train_step, given_codes, given_tracks, sampling_temperature
 from .encoders import PassEncoder, DBNEncoder
 from .generators import RnnNade, RnnRBM, RnnMultiNADE, RnnMultiRBM
 from . import ops
@@ -226,14 +226,28 @@ class MultINNCore(Model):
     metrics_upd = property(lambda self: (self._ensure_global_metrics(), self._metrics_upd)[1])
 
     # -- sampling -------------------------------------------------------------------------------
-    def sampler(self, num_beats, given=None, given_mask=None):
-        """multinn_core.py:324-341: number of model time steps in `num_beats` beats, then generate() (given / given_mask: see generate)."""
+    def sampler(self, num_beats, given=None, given_mask=None, temperature=1.0):
+        """multinn_core.py:324-341: number of model time steps in `num_beats` beats, then generate() (given / given_mask / temperature: see
+        generate)."""
         d = self._config["data"]
         pitch_span = d["pitch_range"]["highest"] - d["pitch_range"]["lowest"]
         num_steps = num_beats * d["beat_resolution"] * pitch_span // self._num_dims
+        kw = {} if isinstance(temperature, (int, float)) and temperature == 1.0 else dict(temperature=temperature)
         if given is None and given_mask is None:
-            return self.generate(num_steps)
-        return self.generate(num_steps, given=given, given_mask=given_mask)
+            return self.generate(num_steps, **kw)
+        return self.generate(num_steps, given=given, given_mask=given_mask, **kw)
+
+    # Sampling temperature (generate(..., temperature)): one positive number, or one per track -- the drums hotter than the bass.  NADE
+    # generators draw u < sigmoid(logit / T) and also take None (threshold decoding); RBM generators run the chain of exp(-E / T).  With
+    # encoders the temperature acts on the generator's samples of the CODES; the encoders are untouched.  It combines with conditioning: a
+    # clamped cell stays as given at any temperature.  1.0 (or all ones) is the call without it, down to the captured scan that is replayed.
+    _temperature_per_track = True
+
+    def _temperature(self, temperature):
+        """Normalised on the host before any device work (common.sampling_temperature): ValueError for a value that is not positive and
+        finite, a sequence of the wrong length or of more than 8 tracks, None with RBM generators, a sequence where no per-track exists."""
+        rbm = self._generator_type in ("RBM", "MultiRBM")
+        return sampling_temperature(temperature, self.num_tracks, allow_none=not rbm, allow_sequence=self._temperature_per_track)
 
     # Conditional generation (generate(num_steps, given, given_mask)): given u8 [B, num_steps, P, M] (nonzero = note on), given_mask bool
     # broadcastable to it -- [M] whole tracks (accompaniment), [P, M] pitch ranges, the full shape any cells (infilling); None = every cell.
@@ -586,19 +600,28 @@ class MultINNJoint(MultINNCore):
             metrics[k] = metrics[k] / self.num_tracks
         return metrics, metrics_upd, summaries
 
-    def generate(self, num_steps, given=None, given_mask=None):
-        """multinn_joint.py:188-215 -> u8 `[B, num_steps, P, M]`.  given / given_mask: conditional generation (MultINNCore._given), codes in
+    def _temperature(self, temperature):
+        # per track: the one NADE over the raw piano-roll orders its visibles p M + m, so visible i is track i % M.  The hidden units of a
+        # joint RBM -- and the codes of a joint encoder -- belong to no track: one number there.
+        rbm = self._generator_type == "RBM"
+        return sampling_temperature(temperature, self.num_tracks, allow_none=not rbm, allow_sequence=not rbm and self._encoder_type == "Pass")
+
+    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0):
+        """multinn_joint.py:188-215 -> u8 `[B, num_steps, P, M]`.  temperature: MultINNCore._temperature; a sequence tempers each conditional
+        of the NADE by its track.  given / given_mask: conditional generation (MultINNCore._given), codes in
         p M + m order.  The one NADE orders the visibles of a step p M + m: a free visible is conditioned on the clamped visibles ordered
         BEFORE it only (the ones after it are fed forward to the later visibles and steps) -- what a NADE offers without importance sampling.
         An RBM generator runs the clamped Gibbs chain: every free visible is conditioned on ALL clamped ones, in any position."""
+        temperature = self._temperature(temperature)
+        kw = {} if temperature == 1.0 else dict(temperature=temperature)
         cond = self._given(num_steps, given, given_mask)
         if self._x_encoded is None:
             MultINNCore._build_all(self, "generate")
         if cond is None:
-            samples_h = self._generator.generate(self._x_encoded, num_steps)
+            samples_h = self._generator.generate(self._x_encoded, num_steps, **kw)
         else:
             codes = cond[0]
-            samples_h = self._generator.generate(self._x_encoded, num_steps, given=codes.reshape(codes.shape[0], num_steps, -1))
+            samples_h = self._generator.generate(self._x_encoded, num_steps, given=codes.reshape(codes.shape[0], num_steps, -1), **kw)
         _, samples = self._encoder.decode(samples_h)
         return samples.reshape(-1, num_steps, self.num_dims, self.num_tracks).to(torch.uint8)
 
@@ -740,22 +763,25 @@ class MultINNJamming(MultIEncoderNN):
     def _decode_generator_outputs(self):
         return self._decode_tracks(self._x_hidden)
 
-    def generate(self, num_steps, given=None, given_mask=None):
-        """multinn_jamming.py:101-133 -> u8 `[B, num_steps, P, M]`.  given / given_mask (MultINNCore._given): the generators are independent --
+    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0):
+        """multinn_jamming.py:101-133 -> u8 `[B, num_steps, P, M]`.  temperature (MultINNCore._temperature): generator m samples at its own.  given / given_mask (MultINNCore._given): the generators are independent --
         a wholly given track is not sampled at all, a partly given one is clamped inside its generator's scan (the NADE sampling kernels, or
         an RBM generator's clamped Gibbs chain)."""
+        temperature = self._temperature(temperature)
+        temps = list(temperature) if isinstance(temperature, tuple) else [temperature] * self.num_tracks
         cond = self._given(num_steps, given, given_mask)
         if self._x_encoded is None:
             MultINNCore._build_all(self, "generate")
         music = []
         for i in range(self.num_tracks):
+            kw = {} if temps[i] == 1.0 else dict(temperature=temps[i])
             if cond is not None and cond[1][i]:
                 music.append(cond[0][..., i].contiguous())
                 continue
             if cond is not None and cond[2][i]:
-                samples_h = self.generators[i].generate(self._x_encoded[i], num_steps, given=cond[0][..., i].contiguous())
+                samples_h = self.generators[i].generate(self._x_encoded[i], num_steps, given=cond[0][..., i].contiguous(), **kw)
             else:
-                samples_h = self.generators[i].generate(self._x_encoded[i], num_steps)
+                samples_h = self.generators[i].generate(self._x_encoded[i], num_steps, **kw)
             music.append(self.encoders[i].decode(samples_h)[1].to(torch.uint8))
         return torch.stack(music, dim=3)
 
@@ -852,17 +878,20 @@ class MultINNComposer(MultIEncoderNN):
     def _decode_generator_outputs(self):
         return self._decode_tracks(self._x_hidden)
 
-    def generate(self, num_steps, given=None, given_mask=None):
-        """multinn_composer.py:114-151 -> u8 `[B, num_steps, P, M]`.  given / given_mask (MultINNCore._given): the tracks of a step are
+    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0):
+        """multinn_composer.py:114-151 -> u8 `[B, num_steps, P, M]`.  temperature (MultINNCore._temperature): track m's NADE scan or Gibbs
+        chain runs at its own.  given / given_mask (MultINNCore._given): the tracks of a step are
         conditionally independent given the history, so clamping whole tracks conditions the others exactly."""
+        temperature = self._temperature(temperature)
+        kw = {} if temperature == 1.0 else dict(temperature=temperature)
         cond = self._given(num_steps, given, given_mask)
         if self._x_encoded is None:
             MultINNCore._build_all(self, "generate")
         if cond is None:
-            samples_h = self._generator.generate(self._x_encoded_stack, num_steps)
+            samples_h = self._generator.generate(self._x_encoded_stack, num_steps, **kw)
         else:
             codes = cond[0]                                         # [B, steps, P, M] -> feature p M + m: the MultiNADE's i tracks + m
-            samples_h = self._generator.generate(self._x_encoded_stack, num_steps, given=codes.reshape(codes.shape[0], num_steps, -1))
+            samples_h = self._generator.generate(self._x_encoded_stack, num_steps, given=codes.reshape(codes.shape[0], num_steps, -1), **kw)
         samples_h = samples_h.reshape(samples_h.shape[0], num_steps, self._num_dims_generator, self.num_tracks).unbind(-1)
         music = [self.encoders[i].decode(samples_h[i].contiguous())[1].to(torch.uint8) for i in range(self.num_tracks)]
         return torch.stack(music, dim=3)
@@ -941,10 +970,13 @@ class MultINNFeedback(MultINNJamming):
             if isinstance(g, RnnRBM) and some[i] and not whole[i]:
                 raise NotImplementedError(f"track {i}: in feedback mode an RBM generator takes whole given tracks only (no clamped chain in the feedback scan)")
 
-    def generate(self, num_steps, given=None, given_mask=None):
+    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0):
         """multinn_feedback.py:120-173 -> u8 `[B, num_steps, P, M]`: one joint scan over the M generators and the feedback module.
+        temperature (MultINNCore._temperature): generator m samples at its own inside the scan.
         given / given_mask (MultINNCore._given): NADE generators clamp inside the scan, RBM generators take whole given tracks only."""
         from .feedback import FeedbackRnnSampler
+        temperature = self._temperature(temperature)
+        kw = {} if temperature == 1.0 else dict(temperature=temperature)
         cond = self._given(num_steps, given, given_mask)
         if self._x_encoded is None:
             self._inputs = self._build_inputs()
@@ -956,11 +988,11 @@ class MultINNFeedback(MultINNJamming):
             self._sampler = FeedbackRnnSampler(self.generators, self._feedback_layer)
         if self._encoder_type == "Pass":
             if cond is None:
-                samples_h = self._sampler.generate(self._x, num_steps)                            # whole scan = one hipGraph replay
+                samples_h = self._sampler.generate(self._x, num_steps, **kw)                      # whole scan = one hipGraph replay
             else:
-                samples_h = self._sampler.generate(self._x, num_steps, given=cond[0])
+                samples_h = self._sampler.generate(self._x, num_steps, given=cond[0], **kw)
         else:
-            samples_h = self._sampler.generate_encoded([e.to(torch.uint8) for e in self._x_encoded], num_steps)
+            samples_h = self._sampler.generate_encoded([e.to(torch.uint8) for e in self._x_encoded], num_steps, **kw)
         music = [self.encoders[i].decode(samples_h[..., i].contiguous())[1].to(torch.uint8) for i in range(self.num_tracks)]
         return torch.stack(music, dim=3)
 

@@ -5,6 +5,7 @@ a kernel), extracts raw device pointers and the current HIP stream, and calls th
 There is no CPU path: tensors must be on a ROCm device.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -646,8 +647,27 @@ def nade_logprob_bwd(v, bias, w_enc, w_dec, tracks, D, Hn, a_final, d_bias, d_w_
          _ptr(a_final), _ptr(d_bias), _ptr(d_w_enc), _ptr(d_w_dec), _ptr(n_rows_dev), _ptr(unsafe))
 
 
-def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub, samples, track_minor=False, nll=None, given=None):
+def _temps(temperature, n_per_job, by_visible, what):
+    """None (a float, or None: the entry point that takes one float serves it, as it always did) or the mnn_temps of a SEQUENCE of
+    temperatures: one per track / job (n_per_job of them), or -- by_visible -- visible i draws at temperature[i % len(temperature)]."""
+    if temperature is None or isinstance(temperature, (int, float)):
+        return None
+    t = tuple(float(x) for x in temperature)
+    _req(1 <= len(t) <= _lib.TEMPS_MAX and all(math.isfinite(x) and x > 0.0 for x in t),
+         f"{what}: 1..{_lib.TEMPS_MAX} positive finite temperatures")
+    _req(by_visible or len(t) in (1, n_per_job), f"{what}: one temperature, or one per track / job ({n_per_job})")
+    st = _lib.Temps()
+    st.n, st.by_visible = len(t), 1 if by_visible else 0
+    for i, x in enumerate(t):
+        st.t[i] = x
+    return st
+
+
+def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub, samples, track_minor=False, nll=None, given=None,
+                by_visible=False):
     """samples u8 [N, tracks*D]; feature index m*D+i (track_minor False) or i*tracks+m (True, rnn_multinade.py:313-314).
+    temperature: a float, None (threshold draws) or a sequence -- one temperature per track, or with by_visible the temperature of visible
+    i is temperature[i % len] (a joint NADE over visibles p * M + m: one per track m).  nll stays the model's own at any temperature.
     given (optional): codes u8 [N, tracks*D] in the layout of samples -- 0 / 1 clamp the visible to that value, 255 leaves it to the draw
     (common.given_codes)."""
     N = bias.shape[0]
@@ -661,6 +681,11 @@ def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub,
         _req(given.dtype == torch.uint8 and tuple(given.shape) == (N, tracks * D) and given.is_contiguous() and given.device == samples.device,
              "sample: given u8 [N, tracks*D], contiguous")
     ts, es = (1, tracks) if track_minor else (D, 1)
+    tt = _temps(temperature, tracks, by_visible, "sample")
+    if tt is not None:
+        call("mnn_nade_sample_temps", _stream(), tracks, N, D, Hn, _ptr(bias), bias.stride(0), _ptr(w_enc), _ptr(w_dec), C.byref(tt), int(seed),
+             int(row0), int(sub), _ptr(samples), ts, tracks * D, es, _ptr(nll), _ptr(given))
+        return
     call("mnn_nade_sample", _stream(), tracks, N, D, Hn, _ptr(bias), bias.stride(0), _ptr(w_enc), _ptr(w_dec),
          float(-1.0 if temperature is None else temperature), int(seed), int(row0), int(sub), _ptr(samples), ts, tracks * D, es, _ptr(nll), _ptr(given))
 
@@ -668,7 +693,8 @@ def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub,
 def nade_sample_multi(jobs, D, Hn, temperature, row0, sub):
     """mnn_nade_sample for up to 8 single-NADE generators in ONE launch.  job = dict(bias f32 [N, >= Hn + D] (the generator's Dense output),
     w_enc / w_dec f32 [D, Hn], seed, samples = a u8 [N, D] VIEW (any strides, the same for every job: e.g. out[:, s, :, m] of a
-    [B, steps, P, M] piano-roll), nll f32 [N] or None, given = None or a u8 [N, D] view of codes with the strides of samples)."""
+    [B, steps, P, M] piano-roll), nll f32 [N] or None, given = None or a u8 [N, D] view of codes with the strides of samples).
+    temperature: a float, None, or a sequence with one temperature per job."""
     _req(1 <= len(jobs) <= 8, "nade_sample_multi: 1..8 jobs")
     arr = (_lib.NadeSampleJob * len(jobs))()
     N = jobs[0]["bias"].shape[0]
@@ -685,6 +711,10 @@ def nade_sample_multi(jobs, D, Hn, temperature, row0, sub):
              "sample_multi: given u8 [N, D] with the strides of samples")
         a.bias, a.ld_bias, a.w_enc, a.w_dec, a.seed, a.samples, a.nll = _ptr(b), b.stride(0), _ptr(j["w_enc"]), _ptr(j["w_dec"]), int(j["seed"]), _ptr(smp), _ptr(nll)
         a.given = _ptr(gv)
+    tt = _temps(temperature, len(jobs), False, "sample_multi")
+    if tt is not None:
+        call("mnn_nade_sample_multi_temps", _stream(), len(jobs), arr, N, D, Hn, C.byref(tt), int(row0), int(sub), rs, es)
+        return
     call("mnn_nade_sample_multi", _stream(), len(jobs), arr, N, D, Hn, float(-1.0 if temperature is None else temperature), int(row0), int(sub), rs, es)
 
 
@@ -698,8 +728,15 @@ def rbm_workspace(D, Hn, device):
     return torch.empty(_lib.load().mnn_rbm_workspace_bytes(D, Hn), dtype=torch.uint8, device=device)
 
 
-def rbm_gibbs(v0, W, bh, bv, k, seed, row0=0, row_ids=None, sub0=0, p_v=None, v_out=None, seed_step=None, given=None):
-    """seed_step (int32 device scalar, optional): added to `seed` on the device (graph-replay safe step-dependent draws).
+def _rbm_temperature(t, what):
+    _req(isinstance(t, (int, float)) and math.isfinite(t) and t > 0.0, f"{what}: the temperature of an RBM chain is a positive finite number")
+    return float(t)
+
+
+def rbm_gibbs(v0, W, bh, bv, k, seed, row0=0, row_ids=None, sub0=0, p_v=None, v_out=None, seed_step=None, given=None, temperature=1.0):
+    """temperature (a positive float; not with seed_step): the chain of the RBM with energy E / T -- every conditional is sigmoid(z / T), p_v
+    the tempered probability; 1.0 is the untempered chain, kernels and bits.
+    seed_step (int32 device scalar, optional): added to `seed` on the device (graph-replay safe step-dependent draws).
     given (optional): codes u8 [N, D] (row stride >= D: a step slice given[:, s] of a [B, steps, D] block is read in place) -- 0 / 1 clamp
     the visible to that value through the whole chain, 255 leaves it free (common.given_codes); not with seed_step (training's chain)."""
     N, D = v0.shape
@@ -717,14 +754,21 @@ def rbm_gibbs(v0, W, bh, bv, k, seed, row0=0, row_ids=None, sub0=0, p_v=None, v_
         _req(given.dtype == torch.uint8 and given.dim() == 2 and tuple(given.shape) == (N, D) and given.stride(1) == 1
              and (given.stride(0) >= D or N == 1) and given.device == v0.device, "gibbs: given u8 [N, D], unit column stride, row stride >= D")
         _req(seed_step is None, "gibbs: given with seed_step (the stepped chain is training's, unconditioned)")
+    temperature = _rbm_temperature(temperature, "gibbs")
+    _req(temperature == 1.0 or seed_step is None, "gibbs: a temperature with seed_step (the stepped chain is training's, untempered)")
     ws = rbm_workspace(D, Hn, v0.device)
     if seed_step is not None:
         _req(seed_step.dtype == torch.int32 and seed_step.numel() == 1, "gibbs: seed_step int32 [1]")
         call("mnn_rbm_gibbs_stepped", _stream(), N, D, Hn, int(k), _ptr(v0), _ptr(W), _ptr(bh), _ldb(bh, Hn), _ptr(bv), _ldb(bv, D), int(seed),
              int(row0), _ptr(row_ids), int(sub0), _ptr(p_v), _ptr(v_out), _ptr(ws), _ptr(seed_step))
         return
+    ld_given = 0 if given is None else (given.stride(0) if N > 1 else D)
+    if temperature != 1.0:
+        call("mnn_rbm_gibbs_temp", _stream(), N, D, Hn, int(k), _ptr(v0), _ptr(W), _ptr(bh), _ldb(bh, Hn), _ptr(bv), _ldb(bv, D), int(seed), int(row0),
+             _ptr(row_ids), int(sub0), _ptr(p_v), _ptr(v_out), _ptr(ws), _ptr(given), ld_given, temperature)
+        return
     call("mnn_rbm_gibbs", _stream(), N, D, Hn, int(k), _ptr(v0), _ptr(W), _ptr(bh), _ldb(bh, Hn), _ptr(bv), _ldb(bv, D), int(seed), int(row0),
-         _ptr(row_ids), int(sub0), _ptr(p_v), _ptr(v_out), _ptr(ws), _ptr(given), 0 if given is None else (given.stride(0) if N > 1 else D))
+         _ptr(row_ids), int(sub0), _ptr(p_v), _ptr(v_out), _ptr(ws), _ptr(given), ld_given)
 
 
 def _check_ladder(betas):
@@ -821,13 +865,21 @@ def _multi_bias_ld(jobs, key, n, N, what):
     return lds.pop()
 
 
-def rbm_gibbs_multi(jobs, k, row0=0, row_ids=None, sub0=0, seed_step=None):
+def rbm_gibbs_multi(jobs, k, row0=0, row_ids=None, sub0=0, seed_step=None, temperature=1.0):
     """ops.rbm_gibbs for 1..8 RBMs of one shape in ONE launch (mnn_rbm_gibbs_multi).  job = dict(v0 = a u8 [N, D] VIEW (any row / column
     strides, the same for every job: e.g. x[:, m::M] of a composer-layout [N, D * M] block, or a contiguous plane), W f32 [D, Hn], bh / bv
     f32 [N or 1, >= Hn / D] (slices of one block: one leading dimension), seed, p_v f32 [N, D] / v_out u8 [N, D] views or None (the element
     strides of v0), given = None or a u8 [N, D] view of codes with v0's column stride (set on every job or on none; not with seed_step)).
-    Per job the results are bit for bit those of ops.rbm_gibbs on contiguous copies."""
+    temperature: a positive float or one per job (not with seed_step); all of them 1 is the untempered launch.
+    Per job the results are bit for bit those of ops.rbm_gibbs (at the job's temperature) on contiguous copies."""
     _req(isinstance(jobs, (list, tuple)) and 1 <= len(jobs) <= RBM_MULTI_MAX_JOBS, f"gibbs_multi: 1..{RBM_MULTI_MAX_JOBS} jobs")
+    if isinstance(temperature, (int, float)):
+        temperature = (temperature,) * len(jobs)
+    _req(isinstance(temperature, (list, tuple)), "gibbs_multi: the temperature is a positive finite number, or one per job")
+    temps = tuple(_rbm_temperature(t, "gibbs_multi") for t in temperature)
+    _req(len(temps) == len(jobs), "gibbs_multi: one temperature, or one per job")
+    tempered = any(t != 1.0 for t in temps)
+    _req(not (tempered and seed_step is not None), "gibbs_multi: a temperature with seed_step (the stepped chain is training's, untempered)")
     v0 = jobs[0]["v0"]
     _req(torch.is_tensor(v0) and v0.dim() == 2, "gibbs_multi: v0 u8 [N, D] views")
     N, D = v0.shape
@@ -862,8 +914,12 @@ def rbm_gibbs_multi(jobs, k, row0=0, row_ids=None, sub0=0, seed_step=None):
         a.W, a.bh, a.bv, a.seed, a.v0 = _ptr(j["W"]), _ptr(j["bh"]), _ptr(j["bv"]), int(j["seed"]), _ptr(j["v0"])
         a.p_v, a.v_out, a.given = _ptr(j.get("p_v")), _ptr(j.get("v_out")), _ptr(j.get("given"))
     ws = torch.empty(len(jobs) * _lib.load().mnn_rbm_workspace_bytes(D, Hn), dtype=torch.uint8, device=v0.device)
-    call("mnn_rbm_gibbs_multi", _stream(), len(jobs), arr, N, D, Hn, int(k), ld_bh, ld_bv, int(row0), _ptr(row_ids), int(sub0), _ptr(seed_step),
-         rs if N > 1 else max(rs, (D - 1) * es + 1), es, rs_g if N > 1 else max(rs_g, (D - 1) * es + 1), _ptr(ws))
+    tail = (rs if N > 1 else max(rs, (D - 1) * es + 1), es, rs_g if N > 1 else max(rs_g, (D - 1) * es + 1), _ptr(ws))
+    if tempered:
+        call("mnn_rbm_gibbs_multi_temps", _stream(), len(jobs), arr, N, D, Hn, int(k), ld_bh, ld_bv, int(row0), _ptr(row_ids), int(sub0),
+             _ptr(seed_step), *tail, (C.c_float * len(jobs))(*temps))
+        return
+    call("mnn_rbm_gibbs_multi", _stream(), len(jobs), arr, N, D, Hn, int(k), ld_bh, ld_bv, int(row0), _ptr(row_ids), int(sub0), _ptr(seed_step), *tail)
 
 
 def rbm_free_energy_multi(jobs):
@@ -1121,10 +1177,11 @@ def det_dense_pack(W, out=None):
     return out
 
 
-def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, given=None, state0=None):
+def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, given=None, state0=None,
+                  by_visible=False):
     """mnn_generate_scan: the whole sampling scan of an LSTM-(Multi)NADE generator in one call.  intro u8 [B, Ti, tracks * D]; layers = [(W, bias)]
     f32 master weights; returns samples u8 [B, num_steps, tracks * D].  given (optional): codes u8 [B, num_steps, tracks * D] in the layout of
-    the samples (see nade_sample).  state0 (optional, mnn_generate_scan_state): [(c0, h0) f32 [B, u]] per layer, the state the intro pass starts from."""
+    the samples (see nade_sample).  temperature: a float, None, or a sequence (per track, or by visible index: nade_sample).  state0 (optional, mnn_generate_scan_state): [(c0, h0) f32 [B, u]] per layer, the state the intro pass starts from."""
     _req(intro.dtype == torch.uint8 and intro.dim() == 3 and intro.is_contiguous() and intro.shape[2] == tracks * D, "generate_scan: intro u8 [B, Ti, tracks * D]")
     B, Ti, n_in = intro.shape
     n_out = tracks * (Hn + D)
@@ -1143,16 +1200,16 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
     if given is not None:
         _req(given.dtype == torch.uint8 and tuple(given.shape) == (B, int(num_steps), n_in) and given.is_contiguous() and given.device == intro.device,
              "generate_scan: given u8 [B, num_steps, tracks * D], contiguous")
+    tt = _temps(temperature, tracks, by_visible, "generate_scan")
     need = int(_lib.load().mnn_generate_scan_workspace_bytes(B, n_in, len(layers), arr, n_out))
     ws = torch.empty(need + 256, dtype=torch.uint8, device=intro.device)
     off = (-ws.data_ptr()) % 256
     samples = torch.empty((B, int(num_steps), n_in), dtype=torch.uint8, device=intro.device)
     args = (_stream(), B, Ti, int(num_steps), _ptr(intro), n_in, len(layers), arr, _ptr(dense_W), _ptr(dense_bias), n_out, tracks, D, Hn,
-            _ptr(w_enc), _ptr(w_dec), float(-1.0 if temperature is None else temperature), int(seed), int(row0), _ptr(samples),
-            C.c_void_p(ws.data_ptr() + off), need, _ptr(given))
-    if state0 is None:
-        call("mnn_generate_scan", *args)
-    else:
+            _ptr(w_enc), _ptr(w_dec), 1.0 if tt is not None else float(-1.0 if temperature is None else temperature), int(seed), int(row0),
+            _ptr(samples), C.c_void_p(ws.data_ptr() + off), need, _ptr(given))        # (args[16]: the float, replaced by the table where there is one)
+    cp = hp = None
+    if state0 is not None:
         _req(len(state0) == len(layers), "generate_scan: one (c0, h0) per layer")
         for (c0, h0), a in zip(state0, arr):
             for t in (c0, h0):
@@ -1160,5 +1217,10 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
                      "generate_scan: state0 entries f32 [B, u], contiguous")
         cp = (C.c_void_p * len(layers))(*[c0.data_ptr() for c0, _ in state0])
         hp = (C.c_void_p * len(layers))(*[h0.data_ptr() for _, h0 in state0])
+    if tt is not None:              # a temperature table: the one entry point that takes it, with or without an initial state
+        call("mnn_generate_scan_temps", *args[:16], C.byref(tt), *args[17:], cp, hp)
+    elif state0 is None:
+        call("mnn_generate_scan", *args)
+    else:
         call("mnn_generate_scan_state", *args, cp, hp)
     return samples                          # (the workspace returns to the allocator in stream order: later users are behind the scan)
