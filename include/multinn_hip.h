@@ -68,8 +68,10 @@ int mnn_gemm_tn(mnn_stream_t s, int dtype, int M, int N, int K, const void* A, i
                 void* C, int ldc, int c_dtype, const float* bias, int flags, int split_k);
 /* The same product on a COMPACTED ragged batch (mnn_ragged_index: valid rows first): m_rows_dev / k_rows_dev (device words, either may be NULL)
  * say how many rows of A (= of C) / how much of the K dimension carry data.  A hint the large-tile 16-bit kernels act on -- row tiles past
- * the count leave without writing (their C rows are never read), the K loop stops at the count (zeros lie behind it) -- and every other kernel
- * ignores: the result on the valid rows is the same either way. */
+ * the count leave without writing (their C rows are never read), the K loop stops at the 64-deep tile that holds the count (zeros lie behind
+ * it) -- and every other kernel ignores: the result on the valid rows is the same either way.  That includes *k_rows_dev == 0: C (+)= bias,
+ * or zeros, on the valid rows.  "Valid rows" are those below *m_rows_dev; the rest of the 256-row tile that holds the count is written too
+ * (from the zero rows of A: bias), rows behind that tile may or may not be. */
 int mnn_gemm_tn_rows(mnn_stream_t s, int dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
                      void* C, int ldc, int c_dtype, const float* bias, int flags, int split_k, const int* m_rows_dev, const int* k_rows_dev);
 

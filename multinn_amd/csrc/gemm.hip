@@ -523,7 +523,10 @@ gemm_tn_glds256_kernel(const bf16_t* __restrict__ A, int lda, const bf16_t* __re
     const int nkt = k_rows_dev != nullptr ? min(K / BK, (*k_rows_dev + BK - 1) / BK) : K / BK;
     const int per = (nkt + split_k - 1) / split_k;
     const int kt0 = z * per, kt1 = min(nkt, kt0 + per);
-    if (kt0 >= kt1) return;
+    // An empty slice leaves -- except slice 0 of a product whose hinted K extent is 0 tiles and whose C is not only added to: it still owes C
+    // the value every other kernel gives for an all-zero K range (bias, or zeros), so it runs its epilogue on zero accumulators and stages
+    // nothing.  (Adding into C without a bias is a no-op: the weight gradients of an empty window leave here as before.)
+    if (kt0 >= kt1 && (nkt > 0 || z != 0 || (bias == nullptr && (flags & (MNN_GEMM_ACCUMULATE | MNN_GEMM_ATOMIC))))) return;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave >> 2, wn = wave & 3;
     const int r = lane & 31, h = lane >> 5;
@@ -543,7 +546,7 @@ gemm_tn_glds256_kernel(const bf16_t* __restrict__ A, int lda, const bf16_t* __re
         slotB.stage(kt * BK, smem256 + (buf * 2 + 1) * TILE, wave);
     };
     GM_T0();
-    stage(0, kt0);
+    if (kt0 < kt1) stage(0, kt0);                           // (uniform; false only for the zero-extent K hint above)
     __syncthreads();                                        // hipcc drains vmcnt(0) before the barrier
     GM_T(1);
     int cur = 0;

@@ -57,7 +57,8 @@ def gemm_tn(A, B, C_out, bias=None, accumulate=False, split_k=1, a_kblock=False,
     """C[M,N] (+)= A[M,K] . B[N,K]^T (+bias).  A,B same dtype (f32/bf16/f16), K-contiguous views.  a_kblock: A is
     given K-blocked, a contiguous [K/32, rows >= M, 32] tensor (element (m, k) at [k // 32, m, k % 32]), 16-bit, K % 64 == 0.
     m_rows / k_rows (int32 device words, compacted ragged batches): how many rows of A / how much of K carry data -- a hint the large-tile
-    kernels use to skip the padding (mnn_gemm_tn_rows); rows of C past m_rows are then left unwritten."""
+    kernels use to skip the padding (mnn_gemm_tn_rows); A / both operands must be zero behind the count.  Rows of C past the 256-row tile
+    that holds m_rows may then be left unwritten; k_rows = 0 gives C (+)= bias (or zeros), like all-zero operands do."""
     _rowmajor(B, "gemm B"); _rowmajor(C_out, "gemm C")
     _req(A.dtype == B.dtype and A.dtype in (torch.float32,) + H16, "gemm: A/B must both be f32, bf16 or f16")
     if a_kblock:

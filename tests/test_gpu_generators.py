@@ -167,6 +167,60 @@ def test_ragged_window_compacted_rows_equal_the_padded_path(precision, Hn, units
     assert float((ga - gb).abs().max()) <= 2e-4 * float(gb.abs().max()), float((ga - gb).abs().max()) / float(gb.abs().max())
 
 
+def test_ragged_window_where_the_hinted_gemms_dispatch():
+    """One ragged train step at the smallest row count at which ALL THREE hinted Dense GEMMs of the compacted path reach the kernel that
+    acts on the hints (the 256 x 256 tile of mnn_gemm_tn_rows): the real widths (D = 440, Hn = 256, LSTM [512, 256], fp16) at B = 1024,
+    T = 64 = 65536 rows -- LstmStack._split_k(256, 696, 65536) is 64 only from there (the weight gradient's k_rows), the forward (m_rows,
+    from ~16 k rows) and dy (m_rows, from ~49 k rows) are above their thresholds too.  The windows of the test above stop at 1536 rows, where
+    every hinted call falls through to kernels that ignore the hint.
+    Three runs on the same weights, seed and batch: (1) compact with the hints (the default), (2) compact with `ragged_gemm_rows = False`,
+    (3) padded (`ragged_compact = False`), compared pairwise (1)/(2) and (1)/(3) at the bounds of the test above: loss 1e-6 relative, NLL
+    rows and conditionals 1e-6, gradients 2e-4 * max|g|.  (1) and (2) run the same kernels on the same valid rows except that (1) skips row
+    tiles / K tiles of padding: the m_rows hint must not change a valid row, so their `log_probs` are BIT-equal; their gradients differ
+    only through the split-K slicing of dense/kernel that the k_rows count changes (and the order of the split-K atomics everywhere).
+    Before run (1) NaN-filled f32 blocks of the shapes of the hinted GEMMs' outputs are allocated and freed, so that the caching allocator
+    hands their `torch.empty` outputs back poisoned: a read of a skipped row tile then shows as a NaN.  Best effort -- the allocator is
+    free to serve those requests from other blocks.
+    No float64 oracle here: at 65 k rows the CPU reference takes minutes; the padded path is oracle-checked at these widths in
+    tests/test_gpu_realdims.py."""
+    from multinn_amd import RnnNade
+    from multinn_amd.generators import LstmStack
+    P, M, Hn, units, B, T = 88, 5, 256, [512, 256], 1024, 64
+    D, N = P * M, B * T
+    x = dev(make_batch(B, T, P, M, 11, rho=0.03))
+    rng = np.random.default_rng(5)
+    ln = rng.integers(1, T + 1, B).astype(np.int32)
+    ln[B // 2:] = np.minimum(ln[B // 2:], T // 2)
+    ln[0] = T
+    res = []
+    for hints, compact in ((True, True), (False, True), (True, False)):
+        gen = RnnNade(D, Hn, units, keep_prob=0.9, precision="fp16", seed=23)
+        gen._materialize(D)
+        gen.ragged_gemm_rows, gen.ragged_compact = hints, compact
+        if hints and compact:
+            assert LstmStack._split_k(units[-1], gen.n_out, N) == 64 and LstmStack._split_k(units[-1], gen.n_out, N - 64) < 64
+            poison = [torch.full(s, float("nan"), device=DEV) for s in ((N, gen.ldo), (N, gen.ldo), (N, units[-1]), (N, units[-1]))]
+            del poison
+        gen.build_pianoroll(x, dev(ln), is_train=True, mode="train")
+        assert (gen._ctx.get("compact") is not None) == compact
+        loss, nll, cp = float(gen.metrics["batch/loss"]), gen.log_probs.clone(), gen.cond_probs.clone()
+        gen.backward()
+        gen.check()
+        res.append((loss, nll, cp, gen.store.grad.clone()))
+        del gen
+    la, na, ca, ga = res[0]
+    assert na.shape == (int(ln.sum()),) and bool(torch.isfinite(ga).all()) and bool(torch.isfinite(na).all())
+    for what, (lb, nb_, cb, gb) in zip(("compact without the hints", "padded"), res[1:]):
+        assert nb_.shape == na.shape and cb.shape == ca.shape and bool(torch.isfinite(gb).all()), what
+        gerr = float((ga - gb).abs().max()) / float(gb.abs().max())
+        print(f"\n[ragged 65 k rows, hints vs {what}] loss {abs(la - lb) / abs(lb):.2e}  NLL rows {float((na - nb_).abs().max()) / float(nb_.abs().max()):.2e}  "
+              f"conditionals {float((ca - cb).abs().max()):.2e}  gradients {gerr:.2e}")
+        assert abs(la - lb) < 1e-6 * abs(lb), what
+        assert float((na - nb_).abs().max()) <= 1e-6 * float(nb_.abs().max()) and float((ca - cb).abs().max()) <= 1e-6, what
+        assert gerr <= 2e-4, (what, gerr)
+    assert torch.equal(na, res[1][1]), "the m_rows hint changed a valid row of the Dense forward"
+
+
 def test_ragged_window_through_build_compacts_multinade_rows():
     """`build(x, y, lengths)` of a generator that trains on encoder outputs (composer mode: RnnMultiNADE, one NADE per track on one Dense
     output) runs Dense + NADE on the valid rows only, like `build_pianoroll` does for the joint mode: against the padded path

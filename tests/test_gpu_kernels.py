@@ -117,6 +117,190 @@ def test_gemm_tn_a_kblock(ops, M, N, K, split_k, rows, dt):
         assert torch.equal(C[:M], C2) or float((C[:M] - C2).abs().max()) < 1e-6 * scale
 
 
+# ------------------------------------------------------------------------------------------------
+# mnn_gemm_tn_rows: the m_rows / k_rows hints of a compacted ragged batch.  Only the 256 x 256 tile acts on them, and it is dispatched only for
+# large problems (launch_gemm: K % 64 == 0, M >= 256, N >= 192, cdiv(M, 256) * cdiv(N, 256) * split_k >= 192, K / 64 / split_k >= 4, or a
+# K-blocked A), so the shapes below are the smallest of each kind that reach it.  Reference: the float64 product of the same 16-bit operands
+# on the device; bound: this kernel family's own, 2e-5 * max|ref| * max(1, K // 1024) for an f32 C (test_gemm_tn_step_shapes).
+def _hint_operands(M, N, K, dt, marker_col):
+    tdt = torch.float16 if dt == "f16" else torch.bfloat16
+    g = torch.Generator(device=DEV).manual_seed(M + N + K)
+    A = (torch.randn((M, K), device=DEV, generator=g) * 0.5).to(tdt)
+    B = (torch.randn((N, K), device=DEV, generator=g) * 0.5).to(tdt)
+    B[min(3, N - 1)] = 0
+    B[min(3, N - 1), marker_col] = 1.0          # asymmetric marker (test_gemm_tn): C[:, 3] = A[:, marker_col] -- a transposed or shifted C write shows
+    bias = torch.randn(N, device=DEV, generator=g)
+    return A, B, bias
+
+
+def _word(n):
+    return torch.tensor([n], device=DEV, dtype=torch.int32)
+
+
+def _ceil_to(n, m):
+    return -(-n // m) * m
+
+
+def _zero_behind(X, k):
+    X = X.clone()
+    X[:, k:] = 0
+    return X
+
+
+def _kblocked(A):
+    M, K = A.shape
+    return A.view(M, K // 32, 32).permute(1, 0, 2).contiguous()
+
+
+def _check_m_hint(C, M, N, m, full, brow, K, what):
+    """C [M + 1, ldc] was filled with 7.0 and then written by a product hinted with m_rows = m whose A has zero rows from m on.
+    full: float64 reference of the un-truncated product (+ bias), brow: what a zero row of A gives (bias or 0)."""
+    lo, hi = min(m, M), min(M, _ceil_to(m, 256))
+    if hi > 0:
+        tol = 2e-5 * max(float(full[:lo].abs().max()) if lo else 0.0, float(brow.abs().max()), 1e-30) * max(1, K // 1024)
+        if lo:
+            err = float((C[:lo, :N] - full[:lo]).abs().max())
+            assert err < tol, (what, m, "rows below the count", err, tol)                              # (a)
+        if hi > lo:
+            err = float((C[lo:hi, :N] - brow).abs().max())
+            assert err < tol, (what, m, "rows of the tile that straddles the count", err, tol)         # (b)
+    assert bool((C[M] == 7.0).all()) and bool((C[:, N:] == 7.0).all()), (what, m, "guard row / pad columns written")     # (c)
+    assert bool((C[hi:M] == 7.0).all()), (what, m, "row tiles past the count were written: the hinted 256 x 256 kernel did not run")     # (d)
+
+
+@pytest.mark.parametrize("M,N,K,ldc,has_bias", [(16384, 696, 256, 704, True), (16400, 2048, 448, 2056, True), (49152, 256, 704, 264, False)])
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+def test_gemm_tn_rows_hint_m_rows(ops, M, N, K, ldc, has_bias, dt):
+    """m_rows on the three shapes of the ragged step that dispatch the 256 x 256 tile (Dense forward with its N edge inside the last column
+    tile; an M that is no multiple of 256, f32 C so that the weight-resident kernel does not take it; the dy product), counts at every edge
+    of a row tile and beyond M.  A has zero rows from the count on, as ops.rows_gather16 leaves it.  Rows below the count and the rest of
+    the tile that straddles it (the NADE workgroup there reads them) equal the float64 product; the guard row and the pad columns of ldc
+    keep their sentinel.  (d) EVERY ROW TILE PAST THE COUNT STILL HOLDS THE SENTINEL: that is the witness that the hinted kernel ran at all.
+    It pins the implementation on purpose -- if the dispatch thresholds of launch_gemm move and another kernel takes one of these shapes,
+    it writes all of C, this assertion fails, and the shapes have to be chosen anew so that the hint stays under test."""
+    A, B, bias = _hint_operands(M, N, K, dt, K // 2)
+    full = A.double() @ B.double().T
+    brow = torch.zeros(N, device=DEV, dtype=torch.float64)
+    if has_bias:
+        full += bias.double()
+        brow = bias.double()
+    for m in (0, 1, 255, 256, 257, 8191, M - 1, M, M + 1000):
+        Am = A.clone()
+        Am[m:] = 0
+        C = torch.full((M + 1, ldc), 7.0, device=DEV)
+        ops.gemm_tn(Am, B, C[:M, :N], bias=bias if has_bias else None, m_rows=_word(m))
+        _check_m_hint(C, M, N, m, full, brow, K, (M, N, K, dt))
+
+
+@pytest.mark.parametrize("M,N,K,split_k,kblock", [(256, 704, 65536, 64, False), (256, 704, 65536, 65, False), (2048, 960, 16384, 8, False),
+                                                  (2048, 960, 16384, 8, True)])
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+def test_gemm_tn_rows_hint_k_rows(ops, M, N, K, split_k, kblock, dt):
+    """k_rows with accumulate=True into a random C0 (how the Dense weight gradient uses it): the slice mapping z = id % split_k (64 slices),
+    the XCD-contiguous mapping (65 slices), a square-ish problem, and the K-blocked A, which receives the hint too.
+    Contract variant, every count: both operands are zero from the count on, so C must equal C0 + the (truncated = full) float64 product;
+    count 0 leaves C bit-equal to C0.  The error bound scales with the depth actually summed, min(k, K) // 1024 -- never wider than the
+    family's K // 1024.
+    Witness variant, one count that is no multiple of 64: the operands hold zeros in [k, ceil64(k)) and finite random values from
+    ceil64(k) on.  The result must equal the product over the first ceil64(k) columns, NOT the full product: that proves the K loop
+    stopped at the hinted tile.  It pins the implementation on purpose (a kernel that ignores the hint is within the header's contract
+    but fails here): if another kernel takes these shapes, choose shapes that dispatch the hinted one again."""
+    A, B, _ = _hint_operands(M, N, K, dt, 0)
+    g = torch.Generator(device=DEV).manual_seed(7)
+    C0 = torch.randn((M, N), device=DEV, generator=g)
+
+    def run(Ak, Bk, k):
+        C = torch.full((M + 1, N), 7.0, device=DEV)
+        C[:M] = C0
+        ops.gemm_tn(_kblocked(Ak) if kblock else Ak, Bk, C[:M], accumulate=True, split_k=split_k, a_kblock=kblock, k_rows=_word(k))
+        assert bool((C[M] == 7.0).all())
+        return C[:M]
+
+    def ref_to(Ak, Bk, depth):
+        return C0.double() + Ak[:, :depth].double() @ Bk[:, :depth].double().T
+
+    for k in (0, 1, 63, 64, 65, 4097, 40000, K - 1, K, K + 5000):
+        Ak, Bk = _zero_behind(A, k), _zero_behind(B, k)
+        C = run(Ak, Bk, k)
+        if k == 0:
+            assert torch.equal(C, C0), "k_rows = 0 with accumulate must leave C alone"
+            continue
+        ref = ref_to(Ak, Bk, min(k, K))
+        err, tol = float((C - ref).abs().max()), 2e-5 * float(ref.abs().max()) * max(1, min(k, K) // 1024)
+        assert err < tol, (k, err, tol)
+    k = 4097
+    kc = _ceil_to(k, 64)
+    Aw, Bw = A.clone(), B.clone()
+    Aw[:, k:kc] = 0
+    Bw[:, k:kc] = 0
+    C = run(Aw, Bw, k)
+    ref, ref_full = ref_to(Aw, Bw, kc), ref_to(Aw, Bw, K)
+    tol = 2e-5 * float(ref.abs().max()) * max(1, kc // 1024)
+    assert float((ref_full - ref).abs().max()) > 1e3 * tol            # (the operands behind the count do tell the two products apart)
+    err = float((C - ref).abs().max())
+    assert err < tol, ("the K loop did not stop at the hinted tile: the 256 x 256 kernel did not run, or ignores k_rows", err, tol)
+
+
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+def test_gemm_tn_rows_hint_both(ops, dt):
+    """m_rows = 5000 and k_rows = 200 on one product (f32 C, bias, no accumulate): the assertions of the m_rows test, on operands that are
+    zero behind both counts."""
+    M, N, K, ldc, m, k = 16384, 704, 512, 712, 5000, 200
+    A, B, bias = _hint_operands(M, N, K, dt, 100)
+    A, B = _zero_behind(A, k), _zero_behind(B, k)
+    full = A.double() @ B.double().T + bias.double()
+    A[m:] = 0
+    C = torch.full((M + 1, ldc), 7.0, device=DEV)
+    ops.gemm_tn(A, B, C[:M, :N], bias=bias, m_rows=_word(m), k_rows=_word(k))
+    _check_m_hint(C, M, N, m, full, bias.double(), K, (M, N, K, dt))
+
+
+@pytest.mark.parametrize("split_k", [1, 2])
+@pytest.mark.parametrize("has_bias", [True, False])
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+def test_gemm_tn_rows_hint_k_rows_zero_without_accumulate(ops, split_k, has_bias, dt):
+    """k_rows = 0 on a product that does NOT accumulate, at a shape where the hinted kernel runs (one slice, and split-K): C is the bias (or
+    zero), which is what every kernel that ignores the hint gives for all-zero operands and what include/multinn_hip.h promises.  (The
+    hinted kernel used to leave before its epilogue: C unwritten with one slice, zero without the bias under split-K.)  Second launch: the
+    same with finite operands behind the count -- still exactly the bias, because the K loop reads nothing; this one pins the
+    implementation, like the witnesses above."""
+    M, N, K, ldc = 16384, 704, 512, 712
+    A, B, bias = _hint_operands(M, N, K, dt, 0)
+    want = (bias if has_bias else torch.zeros(N, device=DEV)).expand(M, N)
+    for Ak, Bk in ((torch.zeros_like(A), torch.zeros_like(B)), (A, B)):
+        C = torch.full((M + 1, ldc), 7.0, device=DEV)
+        ops.gemm_tn(Ak, Bk, C[:M, :N], bias=bias if has_bias else None, split_k=split_k, k_rows=_word(0))
+        assert torch.equal(C[:M, :N], want)
+        assert bool((C[M] == 7.0).all()) and bool((C[:, N:] == 7.0).all())
+
+
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+def test_gemm_tn_rows_hint_fall_through(ops, dt):
+    """Shapes below the dispatch threshold of the 256 x 256 tile: the other kernels ignore the hints, write all of C, and give the un-hinted
+    call's result bit for bit ((1536, 696, 256) is the largest ragged window of tests/test_gpu_generators.py before the 65 k-row one)."""
+    M, N, K, ldc, m = 1536, 696, 256, 704, 700
+    A, B, bias = _hint_operands(M, N, K, dt, K // 2)
+    A[m:] = 0
+    Ch, Cu = torch.full((M + 1, ldc), 7.0, device=DEV), torch.full((M + 1, ldc), 7.0, device=DEV)
+    ops.gemm_tn(A, B, Ch[:M, :N], bias=bias, m_rows=_word(m))
+    ops.gemm_tn(A, B, Cu[:M, :N], bias=bias)
+    assert torch.equal(Ch, Cu) and bool((Ch[m:M, :N] == bias).all())
+    ref = A.double() @ B.double().T + bias.double()
+    assert float((Ch[:M, :N] - ref).abs().max()) < 2e-5 * float(ref.abs().max())
+    assert bool((Ch[M] == 7.0).all()) and bool((Ch[:, N:] == 7.0).all())
+    # k_rows, one slice (split-K sums its slices with atomics in no fixed order: nothing to compare bit for bit there)
+    M, N, K, k = 512, 704, 4096, 1000
+    A, B, _ = _hint_operands(M, N, K, dt, 0)
+    A, B = _zero_behind(A, k), _zero_behind(B, k)
+    C0 = torch.randn((M, N), device=DEV, generator=torch.Generator(device=DEV).manual_seed(7))
+    Ch, Cu = C0.clone(), C0.clone()
+    ops.gemm_tn(A, B, Ch, accumulate=True, k_rows=_word(k))
+    ops.gemm_tn(A, B, Cu, accumulate=True)
+    assert torch.equal(Ch, Cu)
+    ref = C0.double() + A.double() @ B.double().T
+    assert float((Ch - ref).abs().max()) < 2e-5 * float(ref.abs().max()) * max(1, k // 1024)
+
+
 def test_gemm_strided_views_and_errors(ops):
     R = np.random.default_rng(0)
     A = dev(R.standard_normal((50, 96)).astype(np.float32))

@@ -119,6 +119,56 @@ def test_c3_jamming_generators_in_lockstep_equal_one_after_the_other():
         assert a.shape == (int(ln.sum()),) and float((a - b).abs().max()) < 2e-3 * float(b.abs().max())
 
 
+def test_c3_jamming_lockstep_real_widths_vs_oracle():
+    """test_c3_jamming_real_widths on the form the C3 benchmark runs: the five generators in LOCKSTEP (`group_generators = True`, B = 256:
+    one `_multi` launch of the cluster / CU-resident recurrence per layer and direction for all tracks) against the float64 oracle, at
+    the file's own fp16 bounds.  The lockstep test above compares this form only with the sequential one, at cosine > 0.98 on gradients; the
+    oracle test above runs B = 16 on the persistent recurrence.  T = 4 is the shortest window the lockstep path takes (MultINNJamming._grouped
+    needs T >= 4 and B % 256 == 0; at T = 3 the build falls back to one generator after the other, which the assertion on the path below
+    refuses): the float64 oracle of five tracks at CD-10 is dominated by its Philox uniforms and grows with the rows (~7 s at T = 4,
+    ~11 s at T = 6), so the window stays at the shortest one."""
+    from multinn_amd import MultINN, AdamOptimizer
+    precision, B, T, k = "fp16", 256, 4, 10
+    x = TM.batch(B, T, P, M, 9, rho=0.05)
+    m = MultINN(TM.config(P, TM.TRACKS5), TM.params("jamming", gen="RBM", Hn=HN, units=UNITS), mode="jamming", precision=precision)
+    m.group_generators = True
+    m.build(TM.dev(x), lengths=None, is_train=True, mode="train")
+    ps = [G.init_rnn_rbm(50 + i, P, P, HN, UNITS, np.float64) for i in range(M)]
+    for i, g in enumerate(m.generators):
+        ps[i]['bh'] += 0.05 * i
+        ps[i]['bv'] += np.log(0.05 / 0.95)
+        TM.load_rbm_params(g, ps[i])
+    m.build(TM.dev(x), lengths=None, is_train=True, mode="train")
+    assert m._built_grouped and all(g._ctx["lstm"][0].get("rowpar") for g in m.generators), "the lockstep `_multi` launches must be the form under test"
+    tracks = G.per_track_inputs(x)
+    rows = np.array([t * 65536 + b for b in range(B) for t in range(T)])
+    grads, losses, worst = [], [], {"free_energy": 0.0, "loss": 0.0, "agree": 1.0}
+    for i, g in enumerate(m.generators):
+        inp, tgt = tracks[i][:, :-1].astype(np.float64), tracks[i][:, 1:].astype(np.float64)
+        du = G.dropout_uniforms(g.seed, B, T, UNITS)
+        fw = G.rnn_rbm_forward(inp, tgt, None, ps[i], k, seed=g.seed, keep_prob=0.9, drop_u=du, row_ids=rows)
+        vs = g._outputs.cpu().numpy()
+        worst["agree"] = min(worst["agree"], float((vs == fw['v_sample']).all(1).mean()))
+        fw['v_sample'] = vs.astype(np.float64)              # the device's own chain ends: costs and gradients on identical samples
+        cost, F = orbm.free_energy_cost(fw['tgt'], fw['v_sample'], ps[i]['W'], fw['bh_t'], fw['bv_t'])
+        worst["free_energy"] = max(worst["free_energy"], TM.rel(g.free_energy.cpu().numpy(), F))
+        worst["loss"] = max(worst["loss"], abs(float(g.metrics["batch/loss"]) - cost.mean()) / max(1.0, abs(cost.mean())))
+        losses.append(cost.mean())
+        grads.append(G.rnn_rbm_backward(fw, ps[i]))
+    _, _, metrics, _, _ = m.train_generators(AdamOptimizer(0.01), 0.01)
+    m.check()
+    gerr = 0.0
+    for i, g in enumerate(m.generators):
+        for name, ref in zip(g.store.names(), TM.rbm_grad_list(grads[i])):
+            gerr = max(gerr, TM.rel(g.store.gviews[name].cpu().numpy().reshape(ref.shape), ref / M))
+    print(f"\n[C3 lockstep {precision}, B = {B}] free energy {worst['free_energy']:.2e}  loss {worst['loss']:.2e}  rows whose Gibbs chain end equals the "
+          f"float64 chain's {worst['agree']:.3f}  gradients {gerr:.2e}")
+    assert worst["agree"] >= 0.99, worst
+    assert worst["free_energy"] < FWD_TOL[precision] and worst["loss"] < FWD_TOL[precision]
+    assert abs(float(metrics["batch/loss"]) - np.mean(losses)) < FWD_TOL[precision] * max(1.0, abs(np.mean(losses)))
+    assert gerr < GRAD_TOL[precision]
+
+
 @pytest.mark.parametrize("precision", ["fp32", "fp16", "bf16"])
 def test_c4_composer_real_widths(precision):
     from multinn_amd import MultINN, AdamOptimizer
