@@ -1,302 +1,56 @@
-// RBM CD-k Gibbs chain, half-steps and free energy for gfx950.
+// RBM CD-k Gibbs chain (single launches), half-steps and free energy for gfx950.
 // Reference: /root/reference/multinn/models/common/rbm.py:148-263, 337-387.
 //
-// One 256-thread block owns RBM_R rows for the whole chain: the visible and hidden states of those
-// rows live in LDS (as f32 0/1), W is streamed from L2 (coalesced over the output unit; a transposed
-// copy serves the visible half-step), each thread accumulates RBM_R rows of one output unit.
+// The chain itself -- bodies, kernels and the dispatch between its three forms -- is rbm_chain.h, shared with the grouped launches of
+// rbm_multi.hip; this file holds the entry points of the single chain, which fill a one-job argument block and call that dispatch.
 // Summation order is ascending input index with one fma per term, and the sigmoid uses IEEE ops
 // only, so Bernoulli draws are bit-identical to oracle/det_ref.c.
-#include "rbm_chain.h"      // the chain / free-energy bodies (shared with the grouped launches of rbm_multi.hip), RBM_R, rbm_phase, the matrix-core helpers
+#include "rbm_chain.h"      // the chain, RBM_R, rbm_phase, the matrix-core helpers
 
 // ----------------------------------------------------------------------------------------------
 // k-step Gibbs chain (rbm.py:192-231)
 //
-// GIVEN (the clamped chain of conditional sampling; every form below has one): `given` u8 [N, ld_given], 0 / 1 clamp the visible to that
+// GIVEN (the clamped chain of conditional sampling; every form has one): `given` u8 [N, ld_given], 0 / 1 clamp the visible to that
 // value, 255 leaves it free.  The chain starts from v0 with the clamped cells replaced by their codes; every hidden phase is today's; in every
 // visible phase a clamped cell keeps its code and leaves its uniform unused, a free cell draws from the uniform it draws unconditioned (the
 // counters are per cell: nothing shifts).  p_v is sigmoid(logit) at every cell, clamped ones included.
+// TEMPERED (sampling at a temperature other than 1: generation only, training's stepped chain has none): see GibbsView.  A temperature of
+// exactly 1 is the untempered kernels, bit for bit and launch for launch.
 // ----------------------------------------------------------------------------------------------
-
-// The codes of a clamped chain, from the trailing kernel arguments (const uint8_t* given, int ld_given).  The free chain's kernels are the
-// instantiations with NO trailing arguments: their parameter lists -- and with them the kernarg offsets of the implicit arguments they read
-// (blockDim) -- are the ones they always had, and GIVEN = false removes every clamp at compile time.
-struct GibbsCodes {
-    const uint8_t* p = nullptr;
-    int ld = 0;
-    __device__ GibbsCodes() {}
-    __device__ GibbsCodes(const uint8_t* p_, int ld_) : p(p_), ld(ld_) {}
-};
-
-template <typename... Codes>
-__global__ void __launch_bounds__(256)
-rbm_gibbs_kernel(int N, int D, int Hn, int k, const uint8_t* __restrict__ v0, const float* __restrict__ W, const float* __restrict__ Wt,
-                 const float* __restrict__ bh, int ld_bh, const float* __restrict__ bv, int ld_bv, uint64_t seed, uint32_t row0,
-                 const uint32_t* __restrict__ row_ids, uint32_t sub0, float* __restrict__ p_v, uint8_t* __restrict__ v_out,
-                 const int* __restrict__ seed_step, Codes... codes) {
-    constexpr bool GIVEN = sizeof...(Codes) != 0;
-    const GibbsCodes gc(codes...);
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    if (seed_step != nullptr) seed += (uint64_t)(int64_t)*seed_step;      // step counter on the device: a captured launch draws anew every replay
-    const GibbsView a{N, D, Hn, k, v0, W, Wt, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, gc.p, gc.ld, 0, 1};
-    rbm_gibbs_stream_body<GIVEN, false>(a, blockIdx.x * RBM_R, smem);
-}
-
-// ----------------------------------------------------------------------------------------------
-// The same chain with W RESIDENT IN LDS (D (Hn + 1) floats fit: D = 88, Hn = 256 is 90 KB).  The streaming kernel above fetches every
-// W row from L2 inside the k loop, twice per Gibbs iteration, and waits for it: 33 us per iteration whatever the row count.  Here W is
-// read once per workgroup; the row stride Hn + 1 makes both walks conflict-free (hidden phase: consecutive threads, consecutive
-// columns; visible phase: thread d walks row d, bank (d + k) mod 32), so no transposed copy either.  R = 2 rows per workgroup (many
-// short workgroups; used below 2048 rows, see mnn_rbm_gibbs); a phase with fewer outputs than threads splits the rows over the
-// spare threads (visible phase at D = 88: two row groups).  Biases stay in registers over the chain.  Arithmetic and order are
-// the streaming kernel's: ascending-index fma chain from 0, + bias, det_sigmoid, Philox draw -- bit-identical draws.
-// ----------------------------------------------------------------------------------------------
-template <int R, int RGH, int RGV, typename... Codes>        // rows per thread in the hidden / visible phase (R / RG row groups of n_out threads each)
-__global__ void __launch_bounds__(256)
-rbm_gibbs_lds_kernel(int N, int D, int Hn, int k, const uint8_t* __restrict__ v0, const float* __restrict__ W, const float* __restrict__ bh,
-                     int ld_bh, const float* __restrict__ bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* __restrict__ row_ids,
-                     uint32_t sub0, float* __restrict__ p_v, uint8_t* __restrict__ v_out, const int* __restrict__ seed_step, Codes... codes) {
-    constexpr bool GIVEN = sizeof...(Codes) != 0;
-    const GibbsCodes gc(codes...);
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    if (seed_step != nullptr) seed += (uint64_t)(int64_t)*seed_step;
-    const GibbsView a{N, D, Hn, k, v0, W, nullptr, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, gc.p, gc.ld, 0, 1};
-    rbm_gibbs_lds_body<R, RGH, RGV, GIVEN, false>(a, blockIdx.x * R, smem);
-}
-
-// Launch the resident-W form when it applies (both phases fit 256 threads, W fits LDS); false: the caller streams.
-template <int R, int RGH, int RGV, bool GIVEN>
-static bool launch_gibbs_lds(hipStream_t st, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh, const float* bv,
-                             int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v, uint8_t* v_out,
-                             const int* seed_step, const uint8_t* given, int ld_given) {
-    const size_t lds = rbm_lds_resident_bytes(R, D, Hn);
-    const void* fn = GIVEN ? reinterpret_cast<const void*>(&rbm_gibbs_lds_kernel<R, RGH, RGV, const uint8_t*, int>)
-                           : reinterpret_cast<const void*>(&rbm_gibbs_lds_kernel<R, RGH, RGV>);
-    static bool raised_[64];                           // per instantiation and device: dynamic LDS above 64 KB has to be asked for once
-    bool& raised = mnn_dev_flag(raised_);
-    if (!raised) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        raised = true;
-    }
-    if constexpr (GIVEN)
-        hipLaunchKernelGGL((rbm_gibbs_lds_kernel<R, RGH, RGV, const uint8_t*, int>), dim3(cdiv(N, R)), dim3(256), lds, st, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv,
-                           seed, row0, row_ids, sub0, p_v, v_out, seed_step, given, ld_given);
-    else
-        hipLaunchKernelGGL((rbm_gibbs_lds_kernel<R, RGH, RGV>), dim3(cdiv(N, R)), dim3(256), lds, st, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed,
-                           row0, row_ids, sub0, p_v, v_out, seed_step);
-    return true;
-}
-
-// the instantiation for this shape: rows per thread by how many row groups of n_out threads fit 256
-template <bool GIVEN>
-static bool try_gibbs_lds(hipStream_t st, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh, const float* bv,
-                          int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v, uint8_t* v_out,
-                          const int* seed_step, const uint8_t* given, int ld_given) {
-    const int gh = 256 / Hn, gv = 256 / D;          // row groups available in the hidden / visible phase
-#define TRY(R, RGH, RGV) (rbm_lds_resident_bytes(R, D, Hn) <= 158 * 1024 && \
-                          launch_gibbs_lds<R, RGH, RGV, GIVEN>(st, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, \
-                                                               seed_step, given, ld_given))
-    return gv >= 2 ? (gh >= 2 ? TRY(2, 1, 1) : TRY(2, 2, 1)) : (gh >= 2 ? TRY(2, 1, 2) : TRY(2, 2, 2));
-#undef TRY
-}
-
-// ----------------------------------------------------------------------------------------------
-// The chain on the MATRIX CORES, bit for bit the same draws (training batches, N >= 2048 rows).  v_mfma_f32_32x32x2_f32 computes
-// D = fma(a_k1, b_k1, fma(a_k0, b_k0, C)) with one IEEE rounding per product-add (cdna_hip_programming.md, "FP32-input MFMA"): a run of
-// such instructions over ascending k IS the ascending-index fmaf chain of the vector kernels above, so the logits -- and with them every
-// Bernoulli draw -- are identical, at the matrix pipe's rate instead of one fma per lane and term (the vector form reaches 22 TFLOP/s of the
-// 157 f32 peak: its inner loop is LDS reads and address arithmetic).  Layout: a workgroup (8 waves) owns 64 rows for the whole chain; W sits
-// in LDS once (f32 [D][Hn + 1]); the binary v / h states sit in LDS as BYTES (row pitch = an odd number of words: the B-operand reads of the
-// 32 rows of a tile hit 32 banks).  The product is formed TRANSPOSED, C[out unit][row] = sum_k W(k, unit) state[row][k] (A = the weights,
-// B = the states): a lane then holds four CONSECUTIVE output units of one row per accumulator quad = exactly the four uniforms of one
-// Philox block (element >> 2 is the block counter), so every Philox evaluation is used in full -- the vector kernels draw one element per
-// evaluation.  Hidden phase: 2 row tiles x (Hn / 32) unit tiles, two unit tiles per wave share the state operand; visible phase:
-// 2 x ceil(D / 32) jobs on the first waves (one K = Hn chain per output: it cannot be split without changing the summation order).
-// ----------------------------------------------------------------------------------------------
-struct GibbsMfmaArgs {
-    int N, D, Hn, k;
-    const uint8_t* v0; const float* W; const float* bh; int ld_bh; const float* bv; int ld_bv;
-    uint64_t seed; uint32_t row0; const uint32_t* row_ids; uint32_t sub0; float* p_v; uint8_t* v_out; const int* seed_step;
-};
-
-template <typename... Codes>
-__global__ void __launch_bounds__(512) rbm_gibbs_mfma_kernel(GibbsMfmaArgs A, Codes... codes) {
-    constexpr bool GIVEN = sizeof...(Codes) != 0;
-    const GibbsCodes gc(codes...);
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    uint64_t seed = A.seed;
-    if (A.seed_step != nullptr) seed += (uint64_t)(int64_t)*A.seed_step;
-    const GibbsView a{A.N, A.D, A.Hn, A.k, A.v0, A.W, nullptr, A.bh, A.ld_bh, A.bv, A.ld_bv, seed, A.row0, A.row_ids, A.sub0, A.p_v, A.v_out, gc.p, gc.ld, 0, 1};
-    rbm_gibbs_mfma_body<GIVEN, false>(a, blockIdx.x * GM_ROWS, smem);
-}
-
 extern "C" size_t mnn_rbm_workspace_bytes(int D, int Hn) { return (size_t)D * Hn * sizeof(float); }
 
-extern "C" int mnn_transpose(mnn_stream_t s, const void* in, int in_dtype, int R, int C, int ld_in, void* out, int out_dtype, int ld_out);
-
-// The dispatch of both entry points: the same form for a shape whether or not `given` is set (the clamped forms need no LDS beyond the free
-// ones' except the streaming kernel's codes, which no threshold looks at)
-static int rbm_gibbs_launch(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
-                            const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v,
-                            uint8_t* v_out, void* workspace, const int* seed_step, const uint8_t* given, int ld_given) {
-    MNN_REQUIRE(N > 0 && D > 0 && Hn > 0 && k >= 0, "mnn_rbm_gibbs: bad sizes N=%d D=%d Hn=%d k=%d", N, D, Hn, k);
-    MNN_REQUIRE(v0 && W && bh && bv && workspace, "mnn_rbm_gibbs: null pointer");
-    MNN_REQUIRE((ld_bh == 0 || ld_bh >= Hn) && (ld_bv == 0 || ld_bv >= D), "mnn_rbm_gibbs: bad bias leading dimension");
-    MNN_REQUIRE(given == nullptr || ld_given >= D, "mnn_rbm_gibbs: ld_given=%d < D=%d", ld_given, D);
-    const size_t codes_lds = given != nullptr ? (size_t)RBM_R * ((D + 3) & ~3) : 0;
-    MNN_REQUIRE(rbm_lds_bytes(D, Hn) + codes_lds <= 160 * 1024, "mnn_rbm_gibbs: D+Hn too large for LDS");
-    hipStream_t st = (hipStream_t)s;
-    if (N < 2048 && Hn <= 256 && D <= 256 && getenv("MNN_RBM_STREAM_W") == nullptr) {
-        // sampling-sized batches: W resident in LDS, two rows per workgroup (one workgroup per CU: at training sizes -- 32 768 rows --
-        // the streaming kernel's eight rows per workgroup and several workgroups per CU win, 1.5 vs 2.5 ms; round 3: also with the workgroup
-        // walking over its row groups so that W is loaded once, 4.9 ms -- two rows per pass are two dependent fma chains per thread at one
-        // wave per SIMD: latency-bound); rows per thread by how many row groups of n_out threads fit 256
-        const bool done = given != nullptr
-                              ? try_gibbs_lds<true>(st, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, seed_step, given, ld_given)
-                              : try_gibbs_lds<false>(st, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, seed_step, nullptr, 0);
-        if (done) {
-            MNN_LAUNCH_CHECK();
-            return MNN_OK;
-        }
+static int gibbs_single(const char* who, mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
+                        const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v, uint8_t* v_out,
+                        void* workspace, const int* seed_step, const uint8_t* given, int ld_given, float temperature) {
+    MNN_REQUIRE(temperature > 0.f && temperature <= 3.0e38f, "%s: the temperature is a positive finite number (%g)", who, (double)temperature);
+    MNN_REQUIRE(given == nullptr || ld_given >= D, "%s: ld_given=%d < D=%d", who, ld_given, D);
+    if (temperature != 1.0f) {
+        GibbsArgs<true> A{N, D, Hn, k, v0, W, nullptr, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, given, ld_given, temperature, seed_step};
+        return rbm_gibbs_dispatch(who, s, A, workspace);
     }
-    if (gibbs_mfma_lds_bytes(D, Hn) <= 158 * 1024 && getenv("MNN_RBM_NO_MFMA") == nullptr) {
-        // training batches: the chain on the f32 matrix cores (same draws: see rbm_gibbs_mfma_kernel)
-        static bool raised_[64];
-        bool& raised = mnn_dev_flag(raised_);
-        if (!raised) {
-            MNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rbm_gibbs_mfma_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            MNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rbm_gibbs_mfma_kernel<const uint8_t*, int>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            raised = true;
-        }
-        GibbsMfmaArgs a{N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, seed_step};
-        if (given != nullptr)
-            hipLaunchKernelGGL((rbm_gibbs_mfma_kernel<const uint8_t*, int>), dim3(cdiv(N, GM_ROWS)), dim3(512), gibbs_mfma_lds_bytes(D, Hn), st, a, given, ld_given);
-        else
-            hipLaunchKernelGGL(rbm_gibbs_mfma_kernel<>, dim3(cdiv(N, GM_ROWS)), dim3(512), gibbs_mfma_lds_bytes(D, Hn), st, a);
-        MNN_LAUNCH_CHECK();
-        return MNN_OK;
-    }
-    int rc = mnn_transpose(s, W, MNN_F32, D, Hn, Hn, workspace, MNN_F32, D);
-    if (rc != MNN_OK) return rc;
-    if (given != nullptr)
-        hipLaunchKernelGGL((rbm_gibbs_kernel<const uint8_t*, int>), dim3(cdiv(N, RBM_R)), dim3(256), rbm_lds_bytes(D, Hn) + codes_lds, st, N, D, Hn, k, v0, W,
-                           (const float*)workspace, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, seed_step, given, ld_given);
-    else
-        hipLaunchKernelGGL(rbm_gibbs_kernel<>, dim3(cdiv(N, RBM_R)), dim3(256), rbm_lds_bytes(D, Hn), st, N, D, Hn, k, v0, W,
-                           (const float*)workspace, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, seed_step);
-    MNN_LAUNCH_CHECK();
-    return MNN_OK;
-}
-
-// ----------------------------------------------------------------------------------------------
-// The TEMPERED chain (sampling at a temperature other than 1: generation only, training's stepped chain has none).  Kernels of their own --
-// the three forms above with TEMPERED = true, one by-value argument block for all of them -- so that the untempered kernels, their argument
-// lists and their code are the ones they always were.  Dispatch: the thresholds of rbm_gibbs_launch.
-// ----------------------------------------------------------------------------------------------
-struct GibbsTempArgs {
-    int N, D, Hn, k;
-    const uint8_t* v0; const float* W; const float* Wt; const float* bh; int ld_bh; const float* bv; int ld_bv;
-    uint64_t seed; uint32_t row0; const uint32_t* row_ids; uint32_t sub0; float* p_v; uint8_t* v_out;
-    const uint8_t* given; int ld_given; float temp;
-};
-__device__ __forceinline__ GibbsView gibbs_temp_view(const GibbsTempArgs& A) {
-    return GibbsView{A.N, A.D, A.Hn, A.k, A.v0, A.W, A.Wt, A.bh, A.ld_bh, A.bv, A.ld_bv, A.seed, A.row0, A.row_ids, A.sub0, A.p_v, A.v_out,
-                     A.given, A.ld_given, 0, 1, A.temp};
-}
-template <bool GIVEN>
-__global__ void __launch_bounds__(256) rbm_gibbs_temp_stream_kernel(GibbsTempArgs A) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    rbm_gibbs_stream_body<GIVEN, false, true>(gibbs_temp_view(A), blockIdx.x * RBM_R, smem);
-}
-template <int R, int RGH, int RGV, bool GIVEN>
-__global__ void __launch_bounds__(256) rbm_gibbs_temp_lds_kernel(GibbsTempArgs A) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    rbm_gibbs_lds_body<R, RGH, RGV, GIVEN, false, true>(gibbs_temp_view(A), blockIdx.x * R, smem);
-}
-template <bool GIVEN>
-__global__ void __launch_bounds__(512) rbm_gibbs_temp_mfma_kernel(GibbsTempArgs A) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    rbm_gibbs_mfma_body<GIVEN, false, true>(gibbs_temp_view(A), blockIdx.x * GM_ROWS, smem);
-}
-
-template <typename K>
-static bool gibbs_temp_raise(K kernel, bool (&flags)[64]) {   // dynamic LDS above 64 KB: once per instantiation and device
-    bool& raised = mnn_dev_flag(flags);
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        raised = true;
-    }
-    return true;
-}
-template <int R, int RGH, int RGV, bool GIVEN>
-static bool launch_gibbs_temp_lds(hipStream_t st, const GibbsTempArgs& A) {
-    static bool raised_[64];
-    if (rbm_lds_resident_bytes(R, A.D, A.Hn) > 158 * 1024 || !gibbs_temp_raise(&rbm_gibbs_temp_lds_kernel<R, RGH, RGV, GIVEN>, raised_)) return false;
-    hipLaunchKernelGGL((rbm_gibbs_temp_lds_kernel<R, RGH, RGV, GIVEN>), dim3(cdiv(A.N, R)), dim3(256), rbm_lds_resident_bytes(R, A.D, A.Hn), st, A);
-    return true;
-}
-template <bool GIVEN>
-static int rbm_gibbs_temp_launch_t(mnn_stream_t s, GibbsTempArgs& A, void* workspace) {
-    const int N = A.N, D = A.D, Hn = A.Hn;
-    const size_t codes_lds = GIVEN ? (size_t)RBM_R * ((D + 3) & ~3) : 0;
-    hipStream_t st = (hipStream_t)s;
-    if (N < 2048 && Hn <= 256 && D <= 256 && getenv("MNN_RBM_STREAM_W") == nullptr) {
-        const int gh = 256 / Hn, gv = 256 / D;
-        const bool done = gv >= 2 ? (gh >= 2 ? launch_gibbs_temp_lds<2, 1, 1, GIVEN>(st, A) : launch_gibbs_temp_lds<2, 2, 1, GIVEN>(st, A))
-                                  : (gh >= 2 ? launch_gibbs_temp_lds<2, 1, 2, GIVEN>(st, A) : launch_gibbs_temp_lds<2, 2, 2, GIVEN>(st, A));
-        if (done) {
-            MNN_LAUNCH_CHECK();
-            return MNN_OK;
-        }
-    }
-    if (gibbs_mfma_lds_bytes(D, Hn) <= 158 * 1024 && getenv("MNN_RBM_NO_MFMA") == nullptr) {
-        static bool raised_[64];
-        MNN_REQUIRE(gibbs_temp_raise(&rbm_gibbs_temp_mfma_kernel<GIVEN>, raised_), "mnn_rbm_gibbs_temp: cannot raise the dynamic LDS limit");
-        hipLaunchKernelGGL(rbm_gibbs_temp_mfma_kernel<GIVEN>, dim3(cdiv(N, GM_ROWS)), dim3(512), gibbs_mfma_lds_bytes(D, Hn), st, A);
-        MNN_LAUNCH_CHECK();
-        return MNN_OK;
-    }
-    int rc = mnn_transpose(s, A.W, MNN_F32, D, Hn, Hn, workspace, MNN_F32, D);
-    if (rc != MNN_OK) return rc;
-    A.Wt = (const float*)workspace;
-    static bool raised_s_[64];
-    MNN_REQUIRE(gibbs_temp_raise(&rbm_gibbs_temp_stream_kernel<GIVEN>, raised_s_), "mnn_rbm_gibbs_temp: cannot raise the dynamic LDS limit");
-    hipLaunchKernelGGL(rbm_gibbs_temp_stream_kernel<GIVEN>, dim3(cdiv(N, RBM_R)), dim3(256), rbm_lds_bytes(D, Hn) + codes_lds, st, A);
-    MNN_LAUNCH_CHECK();
-    return MNN_OK;
+    GibbsArgs<false> A{N, D, Hn, k, v0, W, nullptr, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, given, ld_given, 1.0f, seed_step};
+    return rbm_gibbs_dispatch(who, s, A, workspace);
 }
 
 extern "C" int mnn_rbm_gibbs_temp(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
                                   const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v,
                                   uint8_t* v_out, void* workspace, const uint8_t* given, int ld_given, float temperature) {
-    MNN_REQUIRE(temperature > 0.f && temperature <= 3.0e38f, "mnn_rbm_gibbs_temp: the temperature is a positive finite number (%g)", (double)temperature);
-    if (temperature == 1.0f)          // the untempered kernels, bit for bit and launch for launch
-        return rbm_gibbs_launch(s, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, workspace, nullptr, given, ld_given);
-    MNN_REQUIRE(N > 0 && D > 0 && Hn > 0 && k >= 0, "mnn_rbm_gibbs: bad sizes N=%d D=%d Hn=%d k=%d", N, D, Hn, k);
-    MNN_REQUIRE(v0 && W && bh && bv && workspace, "mnn_rbm_gibbs: null pointer");
-    MNN_REQUIRE((ld_bh == 0 || ld_bh >= Hn) && (ld_bv == 0 || ld_bv >= D), "mnn_rbm_gibbs: bad bias leading dimension");
-    MNN_REQUIRE(given == nullptr || ld_given >= D, "mnn_rbm_gibbs: ld_given=%d < D=%d", ld_given, D);
-    const size_t codes_lds = given != nullptr ? (size_t)RBM_R * ((D + 3) & ~3) : 0;
-    MNN_REQUIRE(rbm_lds_bytes(D, Hn) + codes_lds <= 160 * 1024, "mnn_rbm_gibbs: D+Hn too large for LDS");
-    GibbsTempArgs A{N, D, Hn, k, v0, W, nullptr, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, given, ld_given, temperature};
-    return given != nullptr ? rbm_gibbs_temp_launch_t<true>(s, A, workspace) : rbm_gibbs_temp_launch_t<false>(s, A, workspace);
+    return gibbs_single("mnn_rbm_gibbs_temp", s, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, workspace, nullptr, given,
+                        ld_given, temperature);
 }
 
 extern "C" int mnn_rbm_gibbs_stepped(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
                                      const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v,
                                      uint8_t* v_out, void* workspace, const int* seed_step) {
-    return rbm_gibbs_launch(s, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, workspace, seed_step, nullptr, 0);
+    return gibbs_single("mnn_rbm_gibbs_stepped", s, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, workspace, seed_step,
+                        nullptr, 0, 1.0f);
 }
 
 extern "C" int mnn_rbm_gibbs(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
                              const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v,
                              uint8_t* v_out, void* workspace, const uint8_t* given, int ld_given) {
-    return mnn_rbm_gibbs_temp(s, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, workspace, given, ld_given, 1.0f);
+    return gibbs_single("mnn_rbm_gibbs", s, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, workspace, nullptr, given,
+                        ld_given, 1.0f);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -323,7 +77,7 @@ rbm_half_kernel(int N, int K, int n_out, const TV* __restrict__ in, const float*
     });
 }
 
-// The half-step on the f32 matrix cores (same ascending fmaf chain per output: see rbm_gibbs_mfma_kernel): 64 rows per workgroup, the rows'
+// The half-step on the f32 matrix cores (same ascending fmaf chain per output: see rbm_gibbs_mfma_body): 64 rows per workgroup, the rows'
 // inputs in LDS as f32 [64][odd pitch], Wk [K][n_out] in LDS, C[out unit][row] tiles of 32 x 32 spread over the 8 waves; a lane's accumulator
 // quad = four consecutive outputs of one row = one Philox block.  From 2048 rows on (DBN encode / decode of a training batch, dbn.py:136-180,
 // and the free-energy gradient's hidden passes).
@@ -465,22 +219,11 @@ extern "C" int mnn_rbm_visible(mnn_stream_t s, int N, int D, int Hn, const void*
 // free energy, per row (rbm.py:256-258; R4):  F[n] = -sum_j softplus((vW)_j + bh[n,j]) - v.bv[n]
 // ----------------------------------------------------------------------------------------------
 
-__global__ void __launch_bounds__(256)
-rbm_free_energy_kernel(int N, int D, int Hn, const uint8_t* __restrict__ v, const float* __restrict__ W, const float* __restrict__ bh, int ld_bh,
-                       const float* __restrict__ bv, int ld_bv, float* __restrict__ F, float* __restrict__ p_h) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ float fsum[4 * RBM_R];
-    rbm_free_energy_body(N, D, Hn, v, W, bh, ld_bh, bv, ld_bv, F, p_h, blockIdx.x * RBM_R, smem, fsum);
-}
-
+// (a one-job call of the grouped launch: one kernel, rbm_free_energy_multi_kernel, serves both)
 extern "C" int mnn_rbm_free_energy(mnn_stream_t s, int N, int D, int Hn, const uint8_t* v, const float* W, const float* bh, int ld_bh,
                                    const float* bv, int ld_bv, float* F, float* p_h) {
-    MNN_REQUIRE(N > 0 && D > 0 && Hn > 0 && v && W && bh && bv && F, "mnn_rbm_free_energy: bad arguments");
-    MNN_REQUIRE((ld_bh == 0 || ld_bh >= Hn) && (ld_bv == 0 || ld_bv >= D), "mnn_rbm_free_energy: bad bias leading dimension");
-    const size_t lds = (size_t)RBM_R * ((D + 3) & ~3) * sizeof(float);
-    hipLaunchKernelGGL(rbm_free_energy_kernel, dim3(cdiv(N, RBM_R)), dim3(256), lds, (hipStream_t)s, N, D, Hn, v, W, bh, ld_bh, bv, ld_bv, F, p_h);
-    MNN_LAUNCH_CHECK();
-    return MNN_OK;
+    const mnn_rbm_free_energy_job job{v, W, bh, bv, F, p_h};
+    return mnn_rbm_free_energy_multi(s, 1, &job, N, D, Hn, ld_bh, ld_bv);
 }
 
 // ----------------------------------------------------------------------------------------------

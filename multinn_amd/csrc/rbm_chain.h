@@ -1,10 +1,15 @@
-// The Gibbs chain and free-energy bodies shared by the single launches (rbm.hip) and the grouped launches (rbm_multi.hip).
+// The Gibbs chain of the RBMs, whole: the chain bodies, the argument block of their kernels, the three kernel templates and the ONE host
+// dispatch that every entry point -- single (rbm.hip) or grouped (rbm_multi.hip), free or clamped, tempered or not -- goes through.  Also the
+// free-energy body.
 //
 // Every body is one templated device function over a GibbsView -- the per-job argument block: a kernel builds the view of ITS job (the one
 // job of mnn_rbm_gibbs, or job blockIdx.y of mnn_rbm_gibbs_multi) and calls the body with its first row.  STRIDED = false is the layout the
 // single launches always had (v0 / p_v / v_out contiguous [N, D]); STRIDED = true addresses cell (n, d) of v0 / p_v / v_out at
 // n * rs + d * es and of the codes at n * ld_given + d * es (es = M: track m of a composer-layout row [D, M], read and written in place).
 // The arithmetic does not depend on the addressing, so a grouped job is bit for bit its single launch.
+//
+// A translation unit instantiates the kernels of the argument blocks its entry points fill, and no others: rbm.hip the single-job blocks,
+// rbm_multi.hip the job tables -- (LDS 4 + matrix cores 1 + streaming 1) x GIVEN x TEMPERED = 24 kernels each.
 #pragma once
 #include "common.h"
 
@@ -59,7 +64,7 @@ __device__ __forceinline__ void rbm_load_rows(const TV* __restrict__ src, int N,
     }
 }
 
-// codes of the clamped chain (u8 per visible): 0 / 1 hold the visible at that value, RBM_GIVEN_FREE leaves it to the chain (see rbm.hip)
+// codes of the clamped chain (u8 per visible): 0 / 1 hold the visible at that value, RBM_GIVEN_FREE leaves it to the chain
 #define RBM_GIVEN_FREE 255
 
 // per-job argument block of the chain bodies
@@ -147,7 +152,9 @@ __device__ __forceinline__ uint32_t gv_code_quad(const GibbsView& a, int row, in
 }
 
 // ----------------------------------------------------------------------------------------------
-// STREAMING form: one 256-thread workgroup owns RBM_R rows for the whole chain, W (and its transposed copy Wt) come from L2.
+// STREAMING form: one 256-thread workgroup owns RBM_R rows for the whole chain: their visible and hidden states live in LDS (as f32 0/1), W
+// is streamed from L2 (coalesced over the output unit; a transposed copy Wt serves the visible phase), each thread accumulates RBM_R rows of
+// one output unit.
 // smem: f32 [RBM_R][Dp] | f32 [RBM_R][Hp] | GIVEN: u8 [RBM_R][Dp]
 // ----------------------------------------------------------------------------------------------
 template <bool GIVEN, bool STRIDED, bool TEMPERED = false>
@@ -217,7 +224,14 @@ __device__ __forceinline__ void rbm_gibbs_stream_body(const GibbsView& a, const 
 }
 
 // ----------------------------------------------------------------------------------------------
-// W RESIDENT IN LDS, R rows per workgroup (sampling batches): see rbm.hip.  smem: f32 [R][Dp] | [R][Hp] | [D][Hn + 1]
+// The same chain with W RESIDENT IN LDS (D (Hn + 1) floats fit: D = 88, Hn = 256 is 90 KB).  The streaming form above fetches every
+// W row from L2 inside the k loop, twice per Gibbs iteration, and waits for it: 33 us per iteration whatever the row count.  Here W is
+// read once per workgroup; the row stride Hn + 1 makes both walks conflict-free (hidden phase: consecutive threads, consecutive
+// columns; visible phase: thread d walks row d, bank (d + k) mod 32), so no transposed copy either.  R = 2 rows per workgroup (many
+// short workgroups; used below 2048 rows, see rbm_gibbs_forms); a phase with fewer outputs than threads splits the rows over the
+// spare threads (visible phase at D = 88: two row groups).  Biases stay in registers over the chain.  Arithmetic and order are
+// the streaming form's: ascending-index fma chain from 0, + bias, det_sigmoid, Philox draw -- bit-identical draws.
+// smem: f32 [R][Dp] | [R][Hp] | [D][Hn + 1]
 // ----------------------------------------------------------------------------------------------
 template <int R, int RGH, int RGV, bool GIVEN, bool STRIDED, bool TEMPERED = false>        // rows per thread in the hidden / visible phase (R / RG row groups of n_out threads each)
 __device__ __forceinline__ void rbm_gibbs_lds_body(const GibbsView& a, const int n0, float* __restrict__ smem) {
@@ -308,7 +322,17 @@ static inline size_t rbm_lds_resident_bytes(int R, int D, int Hn) {
 }
 
 // ----------------------------------------------------------------------------------------------
-// The chain on the MATRIX CORES (training batches): see rbm.hip.  A 512-thread workgroup owns GM_ROWS rows.
+// The chain on the MATRIX CORES, bit for bit the same draws (training batches, N >= 2048 rows).  v_mfma_f32_32x32x2_f32 computes
+// D = fma(a_k1, b_k1, fma(a_k0, b_k0, C)) with one IEEE rounding per product-add (cdna_hip_programming.md, "FP32-input MFMA"): a run of
+// such instructions over ascending k IS the ascending-index fmaf chain of the vector forms above, so the logits -- and with them every
+// Bernoulli draw -- are identical, at the matrix pipe's rate instead of one fma per lane and term (the vector form reaches 22 TFLOP/s of the
+// 157 f32 peak: its inner loop is LDS reads and address arithmetic).  Layout: a workgroup (8 waves) owns GM_ROWS = 64 rows for the whole chain;
+// W sits in LDS once (f32 [D][Hn + 1]); the binary v / h states sit in LDS as BYTES (row pitch = an odd number of words: the B-operand reads
+// of the 32 rows of a tile hit 32 banks).  The product is formed TRANSPOSED, C[out unit][row] = sum_k W(k, unit) state[row][k] (A = the weights,
+// B = the states): a lane then holds four CONSECUTIVE output units of one row per accumulator quad = exactly the four uniforms of one
+// Philox block (element >> 2 is the block counter), so every Philox evaluation is used in full -- the vector forms draw one element per
+// evaluation.  Hidden phase: 2 row tiles x (Hn / 32) unit tiles, two unit tiles per wave share the state operand; visible phase:
+// 2 x ceil(D / 32) jobs on the first waves (one K = Hn chain per output: it cannot be split without changing the summation order).
 // smem: f32 [De][Hn + 1] | u8 [64][pv] | u8 [64][ph]
 // GIVEN: the codes clamp the byte states at load and after each visible quad; a lane's codes of its first-pass visible job stay in registers
 // (four packed words next to bvr: no LDS, so the given form fits wherever the free one does); a quad whose four cells are all clamped skips its
@@ -467,6 +491,150 @@ static inline size_t gibbs_mfma_lds_bytes(int D, int Hn) {
     return (size_t)((D + 1) & ~1) * (Hn + 1) * sizeof(float) + (size_t)GM_ROWS * (gm_pitch(D) + gm_pitch(Hn));
 }
 static inline size_t rbm_lds_bytes(int D, int Hn) { return (size_t)RBM_R * (((D + 3) & ~3) + ((Hn + 3) & ~3)) * sizeof(float); }
+
+// ----------------------------------------------------------------------------------------------
+// The argument blocks of the chain kernels, passed by value.  Two shapes: the one job of mnn_rbm_gibbs / _stepped / _temp, contiguous [N, D]
+// (STRIDED = false: the bodies keep their n * D + d addressing, the view does not read blockIdx.y), and a table of up to RBM_MULTI_MAX_JOBS
+// jobs, job = blockIdx.y, STRIDED.  `given` (null: the free chain), `temp` and `seed_step` (null: none) are plain fields; whether a kernel
+// reads the first two is its GIVEN / TEMPERED.  For the dispatch both give view() on the device and, on the host, jobs(), weights(j),
+// set_wt(j, .) (the streaming form's transposed copy), has_given() and complete(j).
+// ----------------------------------------------------------------------------------------------
+#define RBM_MULTI_MAX_JOBS 8
+
+// the single-job block
+template <bool TEMPERED_>
+struct GibbsArgs {
+    static constexpr bool STRIDED = false, TEMPERED = TEMPERED_;
+    int N, D, Hn, k;
+    const uint8_t* v0; const float* W; const float* Wt; const float* bh; int ld_bh; const float* bv; int ld_bv;
+    uint64_t seed; uint32_t row0; const uint32_t* row_ids; uint32_t sub0; float* p_v; uint8_t* v_out;
+    const uint8_t* given; int ld_given; float temp; const int* seed_step;
+    __device__ __forceinline__ GibbsView view() const {
+        uint64_t sd = seed;
+        if (seed_step != nullptr) sd += (uint64_t)(int64_t)*seed_step;      // step counter on the device: a captured launch draws anew every replay
+        return GibbsView{N, D, Hn, k, v0, W, Wt, bh, ld_bh, bv, ld_bv, sd, row0, row_ids, sub0, p_v, v_out, given, ld_given, 0, 1, temp};
+    }
+    int jobs() const { return 1; }
+    const float* weights(int) const { return W; }
+    void set_wt(int, const float* wt) { Wt = wt; }
+    bool has_given() const { return given != nullptr; }
+    bool complete(int) const { return v0 && W && bh && bv; }
+};
+
+// the job-table block
+struct GibbsJob {
+    const float* W; const float* Wt; const float* bh; const float* bv; uint64_t seed;
+    const uint8_t* v0; float* p_v; uint8_t* v_out; const uint8_t* given;
+};
+template <bool TEMPERED_>
+struct GibbsTableArgs {
+    static constexpr bool STRIDED = true, TEMPERED = TEMPERED_;
+    GibbsJob job[RBM_MULTI_MAX_JOBS];
+    int N, D, Hn, k, ld_bh, ld_bv;
+    uint32_t row0; const uint32_t* row_ids; uint32_t sub0; const int* seed_step;
+    long rs, rs_given; int es, njobs;
+    float temp[RBM_MULTI_MAX_JOBS];          // read by the TEMPERED kernels only
+    __device__ __forceinline__ GibbsView view() const {
+        const GibbsJob& j = job[blockIdx.y];
+        uint64_t seed = j.seed;
+        if (seed_step != nullptr) seed += (uint64_t)(int64_t)*seed_step;
+        return GibbsView{N, D, Hn, k, j.v0, j.W, j.Wt, j.bh, ld_bh, j.bv, ld_bv, seed, row0, row_ids, sub0, j.p_v, j.v_out, j.given, rs_given, rs, es,
+                         temp[blockIdx.y]};
+    }
+    int jobs() const { return njobs; }
+    const float* weights(int j) const { return job[j].W; }
+    void set_wt(int j, const float* wt) { job[j].Wt = wt; }
+    bool has_given() const { return job[0].given != nullptr; }
+    bool complete(int j) const { return job[j].v0 && job[j].W && job[j].bh && job[j].bv && (job[j].given != nullptr) == has_given(); }
+};
+
+// The three forms.  Grid: x = row block, y = job.
+template <typename Args, bool GIVEN>
+__global__ void __launch_bounds__(256) rbm_gibbs_stream_kernel(Args A) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    rbm_gibbs_stream_body<GIVEN, Args::STRIDED, Args::TEMPERED>(A.view(), blockIdx.x * RBM_R, smem);
+}
+template <typename Args, bool GIVEN, int R, int RGH, int RGV>
+__global__ void __launch_bounds__(256) rbm_gibbs_lds_kernel(Args A) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    rbm_gibbs_lds_body<R, RGH, RGV, GIVEN, Args::STRIDED, Args::TEMPERED>(A.view(), blockIdx.x * R, smem);
+}
+template <typename Args, bool GIVEN>
+__global__ void __launch_bounds__(512) rbm_gibbs_mfma_kernel(Args A) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    rbm_gibbs_mfma_body<GIVEN, Args::STRIDED, Args::TEMPERED>(A.view(), blockIdx.x * GM_ROWS, smem);
+}
+
+extern "C" int mnn_transpose(mnn_stream_t s, const void* in, int in_dtype, int R, int C, int ld_in, void* out, int out_dtype, int ld_out);
+
+// Launch KERNEL over (ceil(N / rows), jobs) workgroups.  Dynamic LDS above 64 KB has to be asked for once per instantiation and device; false
+// (nothing launched) when that is refused.
+template <auto KERNEL, typename Args>
+static bool gibbs_launch(hipStream_t st, const Args& A, int rows, int threads, size_t lds) {
+    static bool raised_[64];
+    bool& raised = mnn_dev_flag(raised_);
+    if (!raised) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        raised = true;
+    }
+    hipLaunchKernelGGL(KERNEL, dim3(cdiv(A.N, rows), A.jobs()), dim3(threads), lds, st, A);
+    return true;
+}
+
+// The choice of the form: the same one for a shape whether the launch is single or grouped, clamped or tempered (the clamped forms need no
+// LDS beyond the free ones' except the streaming kernel's codes, which no threshold looks at).
+template <bool GIVEN, typename Args>
+static int rbm_gibbs_forms(const char* who, mnn_stream_t s, Args& A, void* workspace) {
+    const int N = A.N, D = A.D, Hn = A.Hn;
+    const size_t codes_lds = GIVEN ? (size_t)RBM_R * ((D + 3) & ~3) : 0;
+    MNN_REQUIRE(rbm_lds_bytes(D, Hn) + codes_lds <= 160 * 1024, "%s: D+Hn too large for LDS", who);
+    hipStream_t st = (hipStream_t)s;
+    if (N < 2048 && Hn <= 256 && D <= 256 && rbm_lds_resident_bytes(2, D, Hn) <= 158 * 1024 && getenv("MNN_RBM_STREAM_W") == nullptr) {
+        // sampling-sized batches: W resident in LDS, two rows per workgroup (one workgroup per CU: at training sizes -- 32 768 rows --
+        // the streaming kernel's eight rows per workgroup and several workgroups per CU win, 1.5 vs 2.5 ms; round 3: also with the workgroup
+        // walking over its row groups so that W is loaded once, 4.9 ms -- two rows per pass are two dependent fma chains per thread at one
+        // wave per SIMD: latency-bound); rows per thread by how many row groups of n_out threads fit 256
+        const int gh = 256 / Hn, gv = 256 / D;          // row groups available in the hidden / visible phase
+        const size_t lds = rbm_lds_resident_bytes(2, D, Hn);
+#define GIBBS_LDS(RGH, RGV) gibbs_launch<&rbm_gibbs_lds_kernel<Args, GIVEN, 2, RGH, RGV>>(st, A, 2, 256, lds)
+        const bool done = gv >= 2 ? (gh >= 2 ? GIBBS_LDS(1, 1) : GIBBS_LDS(2, 1)) : (gh >= 2 ? GIBBS_LDS(1, 2) : GIBBS_LDS(2, 2));
+#undef GIBBS_LDS
+        if (done) {
+            MNN_LAUNCH_CHECK();
+            return MNN_OK;
+        }
+    }
+    if (gibbs_mfma_lds_bytes(D, Hn) <= 158 * 1024 && getenv("MNN_RBM_NO_MFMA") == nullptr) {
+        // training batches: the chain on the f32 matrix cores, 64 rows per workgroup (same draws: see rbm_gibbs_mfma_body)
+        MNN_REQUIRE((gibbs_launch<&rbm_gibbs_mfma_kernel<Args, GIVEN>>(st, A, GM_ROWS, 512, gibbs_mfma_lds_bytes(D, Hn))), "%s: cannot raise the dynamic LDS limit", who);
+        MNN_LAUNCH_CHECK();
+        return MNN_OK;
+    }
+    // neither fits: the streaming chain, W and a transposed copy per job from L2
+    for (int j = 0; j < A.jobs(); ++j) {
+        float* wt = (float*)workspace + (size_t)j * D * Hn;
+        int rc = mnn_transpose(s, A.weights(j), MNN_F32, D, Hn, Hn, wt, MNN_F32, D);
+        if (rc != MNN_OK) return rc;
+        A.set_wt(j, wt);
+    }
+    MNN_REQUIRE((gibbs_launch<&rbm_gibbs_stream_kernel<Args, GIVEN>>(st, A, RBM_R, 256, rbm_lds_bytes(D, Hn) + codes_lds)), "%s: cannot raise the dynamic LDS limit", who);
+    MNN_LAUNCH_CHECK();
+    return MNN_OK;
+}
+
+// What every entry point requires of a filled block, then the launch.  `who`: the entry point, for the messages.
+template <typename Args>
+static int rbm_gibbs_dispatch(const char* who, mnn_stream_t s, Args& A, void* workspace) {
+    MNN_REQUIRE(A.N > 0 && A.D > 0 && A.Hn > 0 && A.k >= 0, "%s: bad sizes N=%d D=%d Hn=%d k=%d", who, A.N, A.D, A.Hn, A.k);
+    MNN_REQUIRE((A.ld_bh == 0 || A.ld_bh >= A.Hn) && (A.ld_bv == 0 || A.ld_bv >= A.D), "%s: bad bias leading dimension", who);
+    MNN_REQUIRE(workspace, "%s: null workspace", who);
+    for (int j = 0; j < A.jobs(); ++j)
+        MNN_REQUIRE(A.complete(j), "%s: job %d: null pointer, or `given` set on some jobs only", who, j);
+    return A.has_given() ? rbm_gibbs_forms<true>(who, s, A, workspace) : rbm_gibbs_forms<false>(who, s, A, workspace);
+}
 
 // ----------------------------------------------------------------------------------------------
 // free energy, per row (rbm.py:256-258; R4):  F[n] = -sum_j softplus((vW)_j + bh[n,j]) - v.bv[n]

@@ -53,7 +53,8 @@ def test_matrix_core_chain_kernels_use_no_scratch_and_read_operands_ahead(tmp_pa
     per SIMD: nothing else hides an LDS wait) come in runs -- a rolled loop with one LDS read + wait in front of every MFMA would show up as
     single MFMAs separated by `s_waitcnt lgkmcnt(0)`.  (The Gibbs / half-step kernels run two waves per SIMD and keep the rolled loop: measured.)"""
     from multinn_amd import build
-    for fn, names, min_run in (("det_step.hip", ("lstm_step_det_kernel", "dense_det_kernel"), 8), ("rbm.hip", ("rbm_gibbs_mfma_kernel", "rbm_half_mfma_kernel"), 1)):
+    for fn, names, min_run in (("det_step.hip", ("lstm_step_det_kernel", "dense_det_kernel"), 8), ("rbm.hip", ("rbm_gibbs_mfma_kernel", "rbm_half_mfma_kernel"), 1),
+                               ("rbm_multi.hip", ("rbm_gibbs_mfma_kernel",), 1)):
         out = str(tmp_path / (fn + ".s"))
         subprocess.check_call([HIPCC] + build.flags_for(fn) + ["-S", "--cuda-device-only", os.path.join(build.CSRC, fn), "-o", out], stderr=subprocess.DEVNULL)
         text = open(out).read()

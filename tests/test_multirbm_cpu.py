@@ -93,16 +93,18 @@ def test_grouped_kernels_use_no_scratch_and_the_matrix_cores(tmp_path):
     text = open(out).read()
     sizes = {m.group(1): int(m.group(2))
              for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", text)}
-    for nm, count in (("rbm_gibbs_multi_lds_kernel", 8), ("rbm_gibbs_multi_mfma_kernel", 2), ("rbm_gibbs_multi_stream_kernel", 2),
-                      ("rbm_free_energy_multi_kernel", 1)):
+    # the three chain kernel templates of rbm_chain.h over the job-table block: (4 LDS + 1 matrix-core + 1 streaming) x given x tempered
+    for nm, count in (("rbm_gibbs_lds_kernel", 16), ("rbm_gibbs_mfma_kernel", 4), ("rbm_gibbs_stream_kernel", 4), ("rbm_free_energy_multi_kernel", 1)):
         hit = {k: v for k, v in sizes.items() if nm in k}
         assert len(hit) == count and all(v == 0 for v in hit.values()), (nm, hit)
+    chain = [k for k in sizes if "rbm_gibbs_" in k]
+    assert len(chain) == 24 and all("GibbsTableArgs" in k for k in chain), chain      # and no single-job kernel: those are rbm.hip's
     seen = 0
     for body in re.split(r"\n(?=_Z\w+:)", text):
-        if re.match(r"_Z\w*rbm_gibbs_multi_mfma_kernel", body):
+        if re.match(r"_Z\w*rbm_gibbs_mfma_kernel", body):
             seen += 1
             assert "v_mfma_f32_32x32x2_f32" in body and "scratch_" not in body, body[:70]
-    assert seen == 2
+    assert seen == 4
 
 
 def _job(N=6, D=5, Hn=4, **kw):
