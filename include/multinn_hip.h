@@ -43,7 +43,7 @@ enum { MNN_STREAM_DROPOUT = 0, MNN_STREAM_NADE = 1, MNN_STREAM_RBM_H = 2, MNN_ST
 
 /* ABI version of THIS header: bumped whenever a signature or a descriptor struct changes.  mnn_version() returns the value the library
  * was built with; a loader must compare the two before its first call (multinn_amd/_lib.py load() does) -- a library built for another
- * version reads garbage arguments without any diagnosis otherwise.  124: + mnn_rbm_ais / mnn_rbm_ais_workspace_bytes (AIS estimate of an RBM's log partition function).  123: the clamped Gibbs chain -- mnn_rbm_gibbs gained a trailing `given`, `ld_given`.  122: conditional sampling -- a trailing `given` on mnn_nade_sample and mnn_generate_scan, mnn_nade_sample_job gained `given`.  121 (round 6): + mnn_gemm_tn_rows.  120 (round 6): mnn_step_increment gained `ls_dyn`, `ls_good`, `grow_after` (dynamic f16 loss scale).  119 (round 6): mnn_det_dense_job gained `Wp`, + mnn_det_dense_pack / _pack_bytes.  118 (round 6): mnn_det_lstm_job gained `Wp`, + mnn_det_lstm_pack / _pack_bytes, mnn_generate_scan_workspace_bytes gained `n_in`.  117 (round 6): + mnn_lstm_cluster_bwd_ok, + mnn_ragged_index / mnn_rows_gather16 / mnn_rows_scatter_f32, `n_rows_dev` on the gated NADE forwards and mnn_nade_logprob_bwd, `inv` / `hdr` on mnn_pianoroll_shift_timemajor_t, + mnn_lstm_resident_{fwd,bwd}_multi / mnn_lstm_cluster_{fwd,bwd}_multi / _bwd_multi_ok, `unsafe` on mnn_nade_logprob_fwd_gated, `unsafe` on mnn_nade_logprob_bwd.  116: + mnn_lstm_cluster_ok / _fwd / _bwd.  115: mnn_step_increment gained `sumsq`, `clip_norm`.  114: + mnn_lstm_resident_ok / _fwd / _bwd.  113: mnn_pianoroll_shift_timemajor_t gained `count`.  112: + mnn_generate_scan.  111: mnn_rbm_free_energy gained `p_h`.  110: mnn_clip_adam_step gained `skipped`; the dtype arguments of
+ * version reads garbage arguments without any diagnosis otherwise.  124: + mnn_rbm_ais / mnn_rbm_ais_workspace_bytes (AIS estimate of an RBM's log partition function); mnn_rbm_raise (its reverse run) joined later as a new symbol, without a bump.  123: the clamped Gibbs chain -- mnn_rbm_gibbs gained a trailing `given`, `ld_given`.  122: conditional sampling -- a trailing `given` on mnn_nade_sample and mnn_generate_scan, mnn_nade_sample_job gained `given`.  121 (round 6): + mnn_gemm_tn_rows.  120 (round 6): mnn_step_increment gained `ls_dyn`, `ls_good`, `grow_after` (dynamic f16 loss scale).  119 (round 6): mnn_det_dense_job gained `Wp`, + mnn_det_dense_pack / _pack_bytes.  118 (round 6): mnn_det_lstm_job gained `Wp`, + mnn_det_lstm_pack / _pack_bytes, mnn_generate_scan_workspace_bytes gained `n_in`.  117 (round 6): + mnn_lstm_cluster_bwd_ok, + mnn_ragged_index / mnn_rows_gather16 / mnn_rows_scatter_f32, `n_rows_dev` on the gated NADE forwards and mnn_nade_logprob_bwd, `inv` / `hdr` on mnn_pianoroll_shift_timemajor_t, + mnn_lstm_resident_{fwd,bwd}_multi / mnn_lstm_cluster_{fwd,bwd}_multi / _bwd_multi_ok, `unsafe` on mnn_nade_logprob_fwd_gated, `unsafe` on mnn_nade_logprob_bwd.  116: + mnn_lstm_cluster_ok / _fwd / _bwd.  115: mnn_step_increment gained `sumsq`, `clip_norm`.  114: + mnn_lstm_resident_ok / _fwd / _bwd.  113: mnn_pianoroll_shift_timemajor_t gained `count`.  112: + mnn_generate_scan.  111: mnn_rbm_free_energy gained `p_h`.  110: mnn_clip_adam_step gained `skipped`; the dtype arguments of
  * mnn_pianoroll_shift_timemajor_t / mnn_grad_rows_fanout and the `f16` descriptor fields of round 3 are part of it. */
 #define MNN_ABI_VERSION 124
 int mnn_version(void);
@@ -530,6 +530,19 @@ size_t mnn_rbm_ais_workspace_bytes(int N, int D, int Hn, int n_chains, int n_bet
 int mnn_rbm_ais(mnn_stream_t s, int N, int D, int Hn, int n_chains, int n_betas, const float* betas, const float* W, const float* bh, int ld_bh,
                 const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, float* log_z, float* log_w, uint8_t* v_out,
                 float* stats, void* workspace);
+
+/* Reverse annealed importance sampling (RAISE: Burda, Grosse & Salakhutdinov 2015; DESIGN.md section 4 "Reverse AIS"): the ladder of mnn_rbm_ais
+ * run downwards from a data vector.  Operands, counters, arithmetic, requirements, outputs and workspace (mnn_rbm_ais_workspace_bytes) are
+ * those of mnn_rbm_ais; v u8 [N, D] (non-null) holds the rows' data vectors, and every one of a row's S chains starts there:
+ *   x = v; for k = L-1 .. 0: s = xW; if k < L-1: log w += F_{b_{k+1}}(x) - F_{b_k}(x); if k > 0 one Gibbs transition at b_k
+ *   (h ~ sigmoid(bh + b_k s), x ~ sigmoid(bv + b_k hW^T)).  L hidden and L - 1 visible contractions.
+ *   log_z[n] = log Z_0 - (logsumexp_c(log w_c) - log S): the mean weight estimates the annealing model's probability of v over p_0, so its
+ *   log is biased the other way from mnn_rbm_ais's -- HIGH in expectation over data drawn from the model, not a bound per row.
+ * Uniforms: Philox stream 8 (hidden phases) / 9 (visible phases), row and sub = c L + k as in mnn_rbm_ais: no uniform is shared with the
+ * forward chains of the same seed.  log_w holds log w_c; stats = (ESS of w, standard error of log_z) by mnn_rbm_ais's formulas. */
+int mnn_rbm_raise(mnn_stream_t s, int N, int D, int Hn, int n_chains, int n_betas, const float* betas, const float* W, const float* bh, int ld_bh,
+                  const float* bv, int ld_bv, const uint8_t* v, uint64_t seed, uint32_t row0, const uint32_t* row_ids, float* log_z, float* log_w,
+                  uint8_t* v_out, float* stats, void* workspace);
 
 /* dz = dy * y * (1 - y) over n f32 words (dz may alias dy): backward of the sigmoid Dense layers of the feedback module (dnn.py:60-76). */
 int mnn_sigmoid_grad_f32(mnn_stream_t s, long n, const float* dy, const float* y, float* dz);

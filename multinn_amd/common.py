@@ -666,6 +666,19 @@ class RBM(Model):
         betas = ais_ladder(num_betas, dev) if betas is None else torch.as_tensor(betas, dtype=torch.float32).to(dev).contiguous()
         return ops.rbm_ais(self.W, bh, bv, betas, num_chains, self.seed if seed is None else seed, row0, row_ids, stats=stats)
 
+    def log_partition_reverse(self, v, bh=None, bv=None, num_chains=64, num_betas=1000, betas=None, seed=None, row0=0, row_ids=None, stats=None):
+        """log Z of each bias row by REVERSE annealed importance sampling from the row's data vector v [N, D] (ops.rbm_raise; DESIGN.md
+        section 4 "Reverse AIS") -> log Z^_rev f32 [N].  Arguments as log_partition, the same ladder.  1 / Z^_rev is unbiased for the annealing
+        model's likelihood ratio of v, so log Z^_rev is biased the other way from log_partition's: HIGH in expectation over data drawn from
+        the model.  With a long enough ladder the two bracket log Z and their gap says whether it was long enough; for an arbitrary v on a
+        short ladder log Z^_rev can fall below the truth -- it is not a bound per row."""
+        bh = bh if bh is not None else self.bh
+        bv = bv if bv is not None else self.bv
+        dev = self.W.device
+        betas = ais_ladder(num_betas, dev) if betas is None else torch.as_tensor(betas, dtype=torch.float32).to(dev).contiguous()
+        return ops.rbm_raise(self.W, bh, bv, v.to(torch.uint8).contiguous(), betas, num_chains, self.seed if seed is None else seed, row0, row_ids,
+                             stats=stats)
+
     def free_energy(self, v, bh=None, bv=None):
         bh = bh if bh is not None else self.bh
         bv = bv if bv is not None else self.bv

@@ -19,10 +19,21 @@
 // difference of the two softplus values.  Each lane
 // adds its float increments into a double accumulator over the whole ladder; a chain's lanes are combined in a fixed order at the end, so a
 // chain's log w depends on nothing but its own counters (not on S, N or the row's position in the launch).
+//
+// Reverse AIS (RAISE: Burda, Grosse & Salakhutdinov 2015; mnn_rbm_raise, DESIGN.md §4 "Reverse AIS") runs the same ladder backwards from a
+// data vector: the REVERSE instantiation of the two chain bodies below.
+//   chain c: x = the row's data vector
+//            for k = L-1 .. 0:  s = x W;  if k < L-1: log w_c += F_{b_{k+1}}(x) - F_{b_k}(x)
+//                               if k > 0: h ~ sigmoid(bh + b_k s)            (stream 8, sub c L + k)
+//                                         x ~ sigmoid(bv + b_k h W^T)        (stream 9, sub c L + k)
+//   log Z^_rev = log Z_0 - (logsumexp_c(log w_c) - log S).
+// It is the forward step with the rungs taken downwards: the draw's sigmoid sits at the LOWER b of the increment's pair, so with z = bh_j +
+// b_k s_j the term is softplus(z) - softplus(z - dl) with dl = (b_k - b_{k+1}) s_j: ais_increment as it stands, and dl = 0 on the first pass
+// (an increment of exactly 0).  L hidden and L - 1 visible contractions against the forward run's L - 1 and L - 2.
 #include "common.h"
 
-#define AIS_STREAM_H 6u
-#define AIS_STREAM_V 7u
+// Philox streams of the hidden / visible draws: the reverse chains are reported beside the forward ones from one seed and share no uniform
+template <bool REVERSE> struct AisStreams { static constexpr uint32_t H = REVERSE ? 8u : 6u, V = REVERSE ? 9u : 7u; };
 
 __device__ __forceinline__ uint32_t ais_rowid(const uint32_t* __restrict__ row_ids, uint32_t row0, int n) {
     return row_ids != nullptr ? row_ids[n] : row0 + (uint32_t)n;
@@ -44,6 +55,7 @@ struct AisArgs {
     uint64_t seed; uint32_t row0; const uint32_t* row_ids;
     double* lw;                 // [N, S] per-chain log weights (workspace)
     uint8_t* v_out;             // optional [N, S, D] final states
+    const uint8_t* v_data;      // reverse only: [N, D] the rows' data vectors, where every chain of a row starts
 };
 
 // ----------------------------------------------------------------------------------------------
@@ -57,7 +69,8 @@ typedef float ais_f32x16 __attribute__((ext_vector_type(16)));
 
 static __host__ __device__ __forceinline__ int ais_pitch(int n) { int w = (n + 1 + 3) / 4; return 4 * (w | 1); }
 
-__global__ void __launch_bounds__(512) rbm_ais_mfma_kernel(AisArgs A) {
+template <bool REVERSE> __device__ __forceinline__ void ais_mfma_chains(const AisArgs& A) {
+    constexpr uint32_t STREAM_H = AisStreams<REVERSE>::H, STREAM_V = AisStreams<REVERSE>::V;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int N = A.N, D = A.D, Hn = A.Hn, S = A.S, L = A.L, ldw = Hn + 1;
     const int De = (D + 1) & ~1, He = (Hn + 1) & ~1;
@@ -77,16 +90,23 @@ __global__ void __launch_bounds__(512) rbm_ais_mfma_kernel(AisArgs A) {
         for (int j = lane; j < ldw; j += 64) Ws[d * ldw + j] = j < Hn ? A.W[(size_t)min(d, D - 1) * Hn + j] : 0.f;
     for (int e = threadIdx.x; e < AIS_CHAINS * (pv + ph) / 4; e += 512) reinterpret_cast<uint32_t*>(vs)[e] = 0u;
     __syncthreads();
-    // base draw: v ~ Bernoulli(det_sigmoid(bv)), stream 7, sub c L; thread -> (chain, quad of four visibles)
-    const int nq = (D + 3) / 4;
-    for (int e = threadIdx.x; e < AIS_CHAINS * nq; e += 512) {
-        const int lc = e / nq, q = e - lc * nq;
-        float u[4];
-        philox_uniform4(A.seed, AIS_STREAM_V, id, (uint32_t)(c0 + lc) * (uint32_t)L, (uint32_t)q, u);
+    if constexpr (REVERSE) {
+        // every chain starts at the row's data vector: wave -> chains, lane -> visibles
+        const uint8_t* __restrict__ x0 = A.v_data + (size_t)n * D;
+        for (int lc = w; lc < AIS_CHAINS; lc += 8)
+            for (int d = lane; d < D; d += 64) vs[lc * pv + d] = x0[d] ? 1 : 0;
+    } else {
+        // base draw: v ~ Bernoulli(det_sigmoid(bv)), stream 7, sub c L; thread -> (chain, quad of four visibles)
+        const int nq = (D + 3) / 4;
+        for (int e = threadIdx.x; e < AIS_CHAINS * nq; e += 512) {
+            const int lc = e / nq, q = e - lc * nq;
+            float u[4];
+            philox_uniform4(A.seed, STREAM_V, id, (uint32_t)(c0 + lc) * (uint32_t)L, (uint32_t)q, u);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int d = 4 * q + i;
-            if (d < D) vs[lc * pv + d] = u[i] < det_sigmoid(bv[d]) ? 1 : 0;
+            for (int i = 0; i < 4; ++i) {
+                const int d = 4 * q + i;
+                if (d < D) vs[lc * pv + d] = u[i] < det_sigmoid(bv[d]) ? 1 : 0;
+            }
         }
     }
     const int r = lane & 31, hh = lane >> 5;
@@ -105,9 +125,11 @@ __global__ void __launch_bounds__(512) rbm_ais_mfma_kernel(AisArgs A) {
     }
     double lw = 0.0;
     __syncthreads();
-    for (int k = 1; k < L; ++k) {
-        const float bk = A.betas[k], dbk = bk - A.betas[k - 1];
-        const bool trans = k < L - 1;
+    // the rungs: k = 1 .. L-1 upwards, or k = L-1 .. 0 downwards.  dbk is b_k minus the other b of the rung's increment pair: the rung below,
+    // or downwards the rung above (the top rung itself on the first pass: dbk = 0, no increment).  The last rung of either has no draw.
+    for (int k = REVERSE ? L - 1 : 1; REVERSE ? k >= 0 : k < L; k += REVERSE ? -1 : 1) {
+        const float bk = A.betas[k], dbk = bk - A.betas[REVERSE ? min(k + 1, L - 1) : k - 1];
+        const bool trans = REVERSE ? k > 0 : k < L - 1;
         const uint32_t sub_h = c_h * (uint32_t)L + (uint32_t)k;
         // ---- hidden phase: s = v W, the weight increment, and (trans) h ~ sigmoid(bh + b_k s) ----
         for (int jt0 = 2 * (w & 3); jt0 < nht; jt0 += 8) {
@@ -131,7 +153,7 @@ __global__ void __launch_bounds__(512) rbm_ais_mfma_kernel(AisArgs A) {
                     const int j0 = 32 * jt + 8 * g4 + 4 * hh;
                     if (j0 >= Hn) continue;
                     float u[4] = {0.f, 0.f, 0.f, 0.f};
-                    if (trans) philox_uniform4(A.seed, AIS_STREAM_H, id, sub_h, (uint32_t)(j0 >> 2), u);
+                    if (trans) philox_uniform4(A.seed, STREAM_H, id, sub_h, (uint32_t)(j0 >> 2), u);
                     uint32_t pk = 0u;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -167,7 +189,7 @@ __global__ void __launch_bounds__(512) rbm_ais_mfma_kernel(AisArgs A) {
                 const int d0 = 32 * dt + 8 * g4 + 4 * hh;
                 if (d0 >= D) continue;
                 float u[4];
-                philox_uniform4(A.seed, AIS_STREAM_V, id, sub_v, (uint32_t)(d0 >> 2), u);
+                philox_uniform4(A.seed, STREAM_V, id, sub_v, (uint32_t)(d0 >> 2), u);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int d = d0 + e;
@@ -195,6 +217,9 @@ __global__ void __launch_bounds__(512) rbm_ais_mfma_kernel(AisArgs A) {
         }
 }
 
+__global__ void __launch_bounds__(512) rbm_ais_mfma_kernel(AisArgs A) { ais_mfma_chains<false>(A); }
+__global__ void __launch_bounds__(512) rbm_raise_mfma_kernel(AisArgs A) { ais_mfma_chains<true>(A); }
+
 static size_t ais_mfma_lds_bytes(int D, int Hn) {
     return (size_t)((D + 1) & ~1) * (Hn + 1) * sizeof(float) + 8 * 32 * sizeof(double) + (size_t)AIS_CHAINS * (ais_pitch(D) + ais_pitch(Hn));
 }
@@ -206,7 +231,8 @@ static size_t ais_mfma_lds_bytes(int D, int Hn) {
 // ----------------------------------------------------------------------------------------------
 #define AIS_R 8
 
-__global__ void __launch_bounds__(256) rbm_ais_stream_kernel(AisArgs A, const float* __restrict__ Wt) {
+template <bool REVERSE> __device__ __forceinline__ void ais_stream_chains(const AisArgs& A, const float* __restrict__ Wt) {
+    constexpr uint32_t STREAM_H = AisStreams<REVERSE>::H, STREAM_V = AisStreams<REVERSE>::V;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ double red[4][AIS_R];
     const int D = A.D, Hn = A.Hn, S = A.S, L = A.L;
@@ -218,18 +244,29 @@ __global__ void __launch_bounds__(256) rbm_ais_stream_kernel(AisArgs A, const fl
     const uint32_t id = ais_rowid(A.row_ids, A.row0, n);
     const float* __restrict__ bh = A.bh + (size_t)n * A.ld_bh;
     const float* __restrict__ bv = A.bv + (size_t)n * A.ld_bv;
-    for (int e = threadIdx.x; e < AIS_R * D; e += blockDim.x) {
-        const int r = e / D, d = e - r * D;
-        const float u = philox_uniform1(A.seed, AIS_STREAM_V, id, (uint32_t)(c0 + r) * (uint32_t)L, (uint32_t)d);
-        vs[r * Dp + d] = u < det_sigmoid(bv[d]) ? 1.f : 0.f;
+    if constexpr (REVERSE) {
+        // every chain starts at the row's data vector
+        const uint8_t* __restrict__ x0 = A.v_data + (size_t)n * D;
+        for (int d = threadIdx.x; d < D; d += blockDim.x) {
+            const float x = x0[d] ? 1.f : 0.f;
+#pragma unroll
+            for (int r = 0; r < AIS_R; ++r) vs[r * Dp + d] = x;
+        }
+    } else {
+        for (int e = threadIdx.x; e < AIS_R * D; e += blockDim.x) {
+            const int r = e / D, d = e - r * D;
+            const float u = philox_uniform1(A.seed, STREAM_V, id, (uint32_t)(c0 + r) * (uint32_t)L, (uint32_t)d);
+            vs[r * Dp + d] = u < det_sigmoid(bv[d]) ? 1.f : 0.f;
+        }
     }
     double lw[AIS_R];
 #pragma unroll
     for (int r = 0; r < AIS_R; ++r) lw[r] = 0.0;
     __syncthreads();
-    for (int k = 1; k < L; ++k) {
-        const float bk = A.betas[k], dbk = bk - A.betas[k - 1];
-        const bool trans = k < L - 1;
+    // the rungs, dbk and trans: as in ais_mfma_chains
+    for (int k = REVERSE ? L - 1 : 1; REVERSE ? k >= 0 : k < L; k += REVERSE ? -1 : 1) {
+        const float bk = A.betas[k], dbk = bk - A.betas[REVERSE ? min(k + 1, L - 1) : k - 1];
+        const bool trans = REVERSE ? k > 0 : k < L - 1;
         for (int j = threadIdx.x; j < Hn; j += blockDim.x) {
             float acc[AIS_R];
 #pragma unroll
@@ -247,7 +284,7 @@ __global__ void __launch_bounds__(256) rbm_ais_stream_kernel(AisArgs A, const fl
                 const float p = 1.0f / (1.0f + ex);
                 lw[r] += (double)ais_increment(z, ex, p, dbk * acc[r]);
                 if (trans) {
-                    const float u = philox_uniform1(A.seed, AIS_STREAM_H, id, (uint32_t)(c0 + r) * (uint32_t)L + (uint32_t)k, (uint32_t)j);
+                    const float u = philox_uniform1(A.seed, STREAM_H, id, (uint32_t)(c0 + r) * (uint32_t)L + (uint32_t)k, (uint32_t)j);
                     hs[r * Hp + j] = u < p ? 1.f : 0.f;
                 }
             }
@@ -267,7 +304,7 @@ __global__ void __launch_bounds__(256) rbm_ais_stream_kernel(AisArgs A, const fl
 #pragma unroll
             for (int r = 0; r < AIS_R; ++r) {
                 const float p = det_sigmoid(fmaf(bk, acc[r], bb));
-                const float u = philox_uniform1(A.seed, AIS_STREAM_V, id, (uint32_t)(c0 + r) * (uint32_t)L + (uint32_t)k, (uint32_t)d);
+                const float u = philox_uniform1(A.seed, STREAM_V, id, (uint32_t)(c0 + r) * (uint32_t)L + (uint32_t)k, (uint32_t)d);
                 vs[r * Dp + d] = u < p ? 1.f : 0.f;
             }
         }
@@ -293,12 +330,16 @@ __global__ void __launch_bounds__(256) rbm_ais_stream_kernel(AisArgs A, const fl
         }
 }
 
+__global__ void __launch_bounds__(256) rbm_ais_stream_kernel(AisArgs A, const float* __restrict__ Wt) { ais_stream_chains<false>(A, Wt); }
+__global__ void __launch_bounds__(256) rbm_raise_stream_kernel(AisArgs A, const float* __restrict__ Wt) { ais_stream_chains<true>(A, Wt); }
+
 #define AIS_STREAM_STATIC_LDS (4 * AIS_R * sizeof(double))          // the kernel's red[4][AIS_R]
 static size_t ais_stream_lds_bytes(int D, int Hn) { return (size_t)AIS_R * (((D + 3) & ~3) + ((Hn + 3) & ~3)) * sizeof(float); }
 
 // ----------------------------------------------------------------------------------------------
 // Per-row reduction (one workgroup per row, fixed-order tree sums in double):  log Z^ = log Z_0 + m + log(sum_c exp(lw_c - m)) - log S,
 // m = max_c lw_c;  stats = (ESS = (sum w)^2 / sum w^2,  stderr of log Z^ by the delta method on the mean of w = sqrt((S / ESS - 1) / (S - 1))).
+// Reverse: the chains' mean weight estimates Z_0 / Z, so log Z^_rev = log Z_0 - (m + log(sum) - log S); ESS and stderr by the same formulas.
 // ----------------------------------------------------------------------------------------------
 __device__ __forceinline__ double ais_block_sum(double x, double* buf) {
     buf[threadIdx.x] = x;
@@ -314,7 +355,7 @@ __device__ __forceinline__ double ais_block_sum(double x, double* buf) {
 
 __global__ void __launch_bounds__(256) rbm_ais_reduce_kernel(int D, int Hn, int S, const float* __restrict__ bh, int ld_bh, const float* __restrict__ bv,
                                                              int ld_bv, const double* __restrict__ lw, float* __restrict__ log_z,
-                                                             float* __restrict__ log_w, float* __restrict__ stats) {
+                                                             float* __restrict__ log_w, float* __restrict__ stats, int reverse) {
     __shared__ double buf[256];
     const int n = blockIdx.x;
     const double* x = lw + (size_t)n * S;
@@ -341,7 +382,7 @@ __global__ void __launch_bounds__(256) rbm_ais_reduce_kernel(int D, int Hn, int 
     b = ais_block_sum(b, buf);
     z0 = ais_block_sum(z0, buf);
     if (threadIdx.x == 0) {
-        log_z[n] = (float)(z0 + m + log(a) - log((double)S));
+        log_z[n] = reverse ? (float)(z0 - (m + log(a) - log((double)S))) : (float)(z0 + m + log(a) - log((double)S));
         if (stats != nullptr) {
             const double ess = a * a / b;
             stats[2 * n] = (float)ess;
@@ -363,41 +404,60 @@ extern "C" size_t mnn_rbm_ais_workspace_bytes(int N, int D, int Hn, int n_chains
     return ais_lw_bytes(N, n_chains) + (size_t)D * Hn * sizeof(float);
 }
 
-extern "C" int mnn_rbm_ais(mnn_stream_t s, int N, int D, int Hn, int n_chains, int n_betas, const float* betas, const float* W, const float* bh,
-                           int ld_bh, const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, float* log_z, float* log_w,
-                           uint8_t* v_out, float* stats, void* workspace) {
-    MNN_REQUIRE(N > 0 && D > 0 && Hn > 0, "mnn_rbm_ais: bad sizes N=%d D=%d Hn=%d", N, D, Hn);
-    MNN_REQUIRE(n_chains >= 1, "mnn_rbm_ais: n_chains=%d < 1", n_chains);
-    MNN_REQUIRE(n_betas >= 2, "mnn_rbm_ais: n_betas=%d < 2 (the ladder runs from 0 to 1)", n_betas);
-    MNN_REQUIRE((uint64_t)n_chains * (uint64_t)n_betas < (1ull << 32), "mnn_rbm_ais: n_chains * n_betas = %llu does not fit the 32-bit sub counter",
+// both entries: `what` names the entry in messages; reverse runs the chains downwards from v_data
+static int ais_launch(const char* what, mnn_stream_t s, int N, int D, int Hn, int n_chains, int n_betas, const float* betas, const float* W,
+                      const float* bh, int ld_bh, const float* bv, int ld_bv, const uint8_t* v_data, bool reverse, uint64_t seed, uint32_t row0,
+                      const uint32_t* row_ids, float* log_z, float* log_w, uint8_t* v_out, float* stats, void* workspace) {
+    MNN_REQUIRE(N > 0 && D > 0 && Hn > 0, "%s: bad sizes N=%d D=%d Hn=%d", what, N, D, Hn);
+    MNN_REQUIRE(n_chains >= 1, "%s: n_chains=%d < 1", what, n_chains);
+    MNN_REQUIRE(n_betas >= 2, "%s: n_betas=%d < 2 (the ladder runs from 0 to 1)", what, n_betas);
+    MNN_REQUIRE((uint64_t)n_chains * (uint64_t)n_betas < (1ull << 32), "%s: n_chains * n_betas = %llu does not fit the 32-bit sub counter", what,
                 (unsigned long long)n_chains * (unsigned long long)n_betas);
-    MNN_REQUIRE(betas && W && bh && bv && log_z && workspace, "mnn_rbm_ais: null pointer");
-    MNN_REQUIRE((ld_bh == 0 || ld_bh >= Hn) && (ld_bv == 0 || ld_bv >= D), "mnn_rbm_ais: bad bias leading dimension");
-    MNN_REQUIRE(ais_stream_lds_bytes(D, Hn) + AIS_STREAM_STATIC_LDS <= 160 * 1024, "mnn_rbm_ais: D+Hn too large for LDS");
+    MNN_REQUIRE(betas && W && bh && bv && log_z && workspace && (v_data || !reverse), "%s: null pointer", what);
+    MNN_REQUIRE((ld_bh == 0 || ld_bh >= Hn) && (ld_bv == 0 || ld_bv >= D), "%s: bad bias leading dimension", what);
+    MNN_REQUIRE(ais_stream_lds_bytes(D, Hn) + AIS_STREAM_STATIC_LDS <= 160 * 1024, "%s: D+Hn too large for LDS", what);
     const bool mfma = ais_use_mfma(D, Hn);
     const long blocks = (long)N * ((n_chains + (mfma ? AIS_CHAINS : AIS_R) - 1) / (mfma ? AIS_CHAINS : AIS_R));
-    MNN_REQUIRE(blocks <= 0x7fffffffL, "mnn_rbm_ais: N * chain blocks = %ld exceeds the grid", blocks);
+    MNN_REQUIRE(blocks <= 0x7fffffffL, "%s: N * chain blocks = %ld exceeds the grid", what, blocks);
     hipStream_t st = (hipStream_t)s;
     double* lw = reinterpret_cast<double*>(workspace);
-    AisArgs a{N, D, Hn, n_chains, n_betas, betas, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, lw, v_out};
+    AisArgs a{N, D, Hn, n_chains, n_betas, betas, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, lw, v_out, v_data};
     static bool raised_[64];
     bool& raised = mnn_dev_flag(raised_);
     if (!raised) {
-        MNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rbm_ais_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rbm_ais_stream_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024 - (int)AIS_STREAM_STATIC_LDS));
+        for (auto* f : {&rbm_ais_mfma_kernel, &rbm_raise_mfma_kernel})
+            MNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        for (auto* f : {&rbm_ais_stream_kernel, &rbm_raise_stream_kernel})
+            MNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        160 * 1024 - (int)AIS_STREAM_STATIC_LDS));
         raised = true;
     }
     if (mfma) {
-        hipLaunchKernelGGL(rbm_ais_mfma_kernel, dim3((unsigned)blocks), dim3(512), ais_mfma_lds_bytes(D, Hn), st, a);
+        hipLaunchKernelGGL(reverse ? rbm_raise_mfma_kernel : rbm_ais_mfma_kernel, dim3((unsigned)blocks), dim3(512), ais_mfma_lds_bytes(D, Hn), st, a);
     } else {
         float* Wt = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + ais_lw_bytes(N, n_chains));
         int rc = mnn_transpose(s, W, MNN_F32, D, Hn, Hn, Wt, MNN_F32, D);
         if (rc != MNN_OK) return rc;
-        hipLaunchKernelGGL(rbm_ais_stream_kernel, dim3((unsigned)blocks), dim3(256), ais_stream_lds_bytes(D, Hn), st, a, (const float*)Wt);
+        hipLaunchKernelGGL(reverse ? rbm_raise_stream_kernel : rbm_ais_stream_kernel, dim3((unsigned)blocks), dim3(256), ais_stream_lds_bytes(D, Hn), st,
+                           a, (const float*)Wt);
     }
     MNN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rbm_ais_reduce_kernel, dim3(N), dim3(256), 0, st, D, Hn, n_chains, bh, ld_bh, bv, ld_bv, (const double*)lw, log_z, log_w, stats);
+    hipLaunchKernelGGL(rbm_ais_reduce_kernel, dim3(N), dim3(256), 0, st, D, Hn, n_chains, bh, ld_bh, bv, ld_bv, (const double*)lw, log_z, log_w, stats,
+                       reverse ? 1 : 0);
     MNN_LAUNCH_CHECK();
     return MNN_OK;
+}
+
+extern "C" int mnn_rbm_ais(mnn_stream_t s, int N, int D, int Hn, int n_chains, int n_betas, const float* betas, const float* W, const float* bh,
+                           int ld_bh, const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, float* log_z, float* log_w,
+                           uint8_t* v_out, float* stats, void* workspace) {
+    return ais_launch("mnn_rbm_ais", s, N, D, Hn, n_chains, n_betas, betas, W, bh, ld_bh, bv, ld_bv, nullptr, false, seed, row0, row_ids, log_z, log_w,
+                      v_out, stats, workspace);
+}
+
+extern "C" int mnn_rbm_raise(mnn_stream_t s, int N, int D, int Hn, int n_chains, int n_betas, const float* betas, const float* W, const float* bh,
+                             int ld_bh, const float* bv, int ld_bv, const uint8_t* v, uint64_t seed, uint32_t row0, const uint32_t* row_ids,
+                             float* log_z, float* log_w, uint8_t* v_out, float* stats, void* workspace) {
+    return ais_launch("mnn_rbm_raise", s, N, D, Hn, n_chains, n_betas, betas, W, bh, ld_bh, bv, ld_bv, v, true, seed, row0, row_ids, log_z, log_w,
+                      v_out, stats, workspace);
 }

@@ -161,11 +161,15 @@ def evaluate(generator, X, lengths, batch_size, piece_size, device=None, nll="lo
     """utils/training.py:180-213 collect_metrics: mean generator NLL per valid row over all windows.
     nll="loss" (default): the training loss (an RBM generator's is the CD cost, a difference of free energies, not a likelihood).
     nll="ais": the model's estimate_nll(x, lengths, **ais) -- exact for NADE generators, annealed importance sampling for RBM generators
-    (biased low), summed over a mode's generators."""
+    (biased low), summed over a mode's generators.
+    nll="raise": the same with estimate_nll(method="raise") -- reverse AIS, biased the other way (conservative).
+    nll="bracket": estimate_nll(method="both"); returns {"lower": the "ais" mean, "upper": the "raise" mean, "gap": upper - lower}, each
+    equal to its own call's value: a gap well above its noise says the ladder (ais: num_betas) is too short for either end to be trusted."""
     import torch
-    if nll not in ("loss", "ais"):
-        raise ValueError(f"nll must be 'loss' or 'ais', got {nll!r}")
-    tot, cnt = 0.0, 0
+    methods = {"ais": "ais", "raise": "raise", "bracket": "both"}
+    if nll != "loss" and nll not in methods:
+        raise ValueError(f"nll must be 'loss', 'ais', 'raise' or 'bracket', got {nll!r}")
+    tot, cnt, tot_upper = 0.0, 0, 0.0
     ids = np.arange(X.shape[0])
     for w in iter_windows(ids, lengths, X.shape[1], batch_size, piece_size):
         if w is None:
@@ -173,9 +177,11 @@ def evaluate(generator, X, lengths, batch_size, piece_size, device=None, nll="lo
         song_ids, j, max_len, len_batch = w
         xb = torch.from_numpy(np.ascontiguousarray(X[song_ids, j:j + max_len])).to(device or "cuda")
         full = bool((len_batch == max_len).all())
-        if nll == "ais":
+        if nll != "loss":
             n = int(len_batch.sum())
-            tot += generator.estimate_nll(xb, None if full else torch.from_numpy(len_batch).to(xb.device), **(ais or {})).mean * n
+            est = generator.estimate_nll(xb, None if full else torch.from_numpy(len_batch).to(xb.device), **dict(ais or {}, method=methods[nll]))
+            tot += (est.lower if nll == "bracket" else est).mean * n
+            tot_upper += est.upper.mean * n if nll == "bracket" else 0.0
             cnt += n
             continue
         generator.build_pianoroll(xb, None if full else torch.from_numpy(len_batch).to(xb.device), is_train=False, mode="eval")
@@ -183,6 +189,9 @@ def evaluate(generator, X, lengths, batch_size, piece_size, device=None, nll="lo
         loss = generator.generator_loss() if hasattr(generator, "generator_loss") else generator.metrics["batch/loss"]
         tot += float(loss) * n
         cnt += n
+    if nll == "bracket":
+        lower, upper = tot / max(cnt, 1), tot_upper / max(cnt, 1)
+        return {"lower": lower, "upper": upper, "gap": upper - lower}
     return tot / max(cnt, 1)
 
 

@@ -61,7 +61,12 @@ class NllEstimate:
     """Negative log-likelihood of a built batch, per valid row in API order (b-major, then t; like RnnRBM.cost).
     nll [n] f32; log_z / free_energy [n] (AIS estimators; None where the NLL is exact); mean: mean NLL per valid row; stderr: standard error
     of `mean` (0 when exact; AIS: sqrt(sum of the rows' squared standard errors) / n, the rows' chains being independent); ess: the smallest
-    effective sample size over the rows (inf when exact).  An AIS estimate is biased LOW (E[Z^] = Z, so E[log Z^] <= log Z): optimistic."""
+    effective sample size over the rows (inf when exact).  An AIS estimate (method="ais") is biased LOW (E[Z^] = Z, so E[log Z^] <= log Z):
+    optimistic, and its own ESS / stderr cannot show chains that never reached a mode.  A reverse-AIS estimate (method="raise": the same
+    ladder run downwards from the data row, DESIGN.md section 4 "Reverse AIS") is biased the other way -- HIGH in expectation over data
+    drawn from the model: conservative.  Reported together (method="both": an NllBracket) the two bracket the NLL when the ladder is long
+    enough, and their gap says when it is not; for an arbitrary row on a short ladder the reverse estimate can fall below the truth, so the
+    bracket is not a bound per row."""
 
     def __init__(self, nll, log_z=None, free_energy=None, row_stderr=None, row_ess=None):
         self.nll, self.log_z, self.free_energy = nll, log_z, free_energy
@@ -84,6 +89,55 @@ class NllEstimate:
         se = torch.stack([p.row_stderr for p in ai]).pow(2).sum(0).sqrt() if ai else None
         ess = torch.stack([p.row_ess for p in ai]).min(0).values if ai else None
         return NllEstimate(nll, log_z, fe, se, ess)
+
+
+class NllBracket:
+    """estimate_nll(method="both"): lower = the AIS estimate (optimistic), upper = the reverse-AIS estimate (conservative), each the
+    NllEstimate its single-method call returns for the same seed.  gap = upper.mean - lower.mean: what the ladder's length leaves open (near 0,
+    within gap_stderr, when it is long enough; see NllEstimate for what the bracket does not promise).  gap_stderr: the two standard errors
+    in quadrature (the two sets of chains share no uniform).  Exact generators (NADE): lower is upper, gap 0.0."""
+
+    def __init__(self, lower, upper):
+        self.lower, self.upper = lower, upper
+        self.gap = upper.mean - lower.mean
+        self.gap_stderr = math.sqrt(lower.stderr ** 2 + upper.stderr ** 2)
+
+    @staticmethod
+    def total(parts):
+        """The joint bracket of several models of the same rows: NllEstimate.total on each side (one estimate where every part is exact)."""
+        lower = NllEstimate.total([p.lower for p in parts])
+        return NllBracket(lower, lower if all(p.lower is p.upper for p in parts) else NllEstimate.total([p.upper for p in parts]))
+
+
+NLL_METHODS = {"ais": ("ais",), "raise": ("raise",), "both": ("ais", "raise")}       # method -> the estimators it runs, lower side first
+
+
+def nll_sides(method):
+    """The estimators of an estimate_nll method; ValueError for anything else (raised before any device work)."""
+    if method not in NLL_METHODS:
+        raise ValueError(f"method must be 'ais', 'raise' or 'both', got {method!r}")
+    return NLL_METHODS[method]
+
+
+def nll_result(method, sides):
+    """What estimate_nll returns for the per-side estimates: the estimate itself, or the bracket of the two."""
+    return NllBracket(*sides) if method == "both" else sides[0]
+
+
+def total_nll(method, parts):
+    """The joint result of several models of the same rows (a mode's generators), each part a result of `method`."""
+    return NllBracket.total(parts) if method == "both" else NllEstimate.total(parts)
+
+
+def rbm_nll_side(side, rbm, v, F, bh, bv, num_chains, num_betas, betas, seed, ids):
+    """One RBM's NLL rows F + log Z^ with log Z^ from AIS (side "ais": RBM.log_partition) or reverse AIS from the rows' targets v (side
+    "raise": RBM.log_partition_reverse), chains keyed by the row ids."""
+    stats = torch.empty((bh.shape[0], 2), device=bh.device)
+    if side == "ais":
+        log_z = rbm.log_partition(bh, bv, num_chains, num_betas, betas, seed, row_ids=ids, stats=stats)
+    else:
+        log_z = rbm.log_partition_reverse(v, bh, bv, num_chains, num_betas, betas, seed, row_ids=ids, stats=stats)
+    return NllEstimate(F + log_z, log_z, F, stats[:, 1], stats[:, 0])
 
 
 def refuse_host_model(device, what):
@@ -1076,15 +1130,17 @@ class RnnEstimator(Generator):
             self._grad_sumsq = compute_gradients(optimizer, self.store, self.clip_norm, lr, reduce=False)
         return capture_train_step(feed, step, warmup, [self], lambda: [self.store], split=dp_active(), fwd_bwd=fwd_bwd, opt=opt, **kw)
 
-    def estimate_nll(self, x, lengths=None, num_chains=64, num_betas=1000, betas=None, seed=None):
+    def estimate_nll(self, x, lengths=None, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais"):
         """NLL of every step of x [B, T, F] (or [B, T, P, M]) given the steps before it: builds in eval mode (keep_prob 1) on inputs = x
         shifted by one all-zero step, targets = x, and returns an NllEstimate over the valid rows.  RnnNade: exact (the AIS arguments are
-        ignored).  RnnRBM: AIS (see RnnRBM._nll_rows_built)."""
+        ignored).  RnnRBM: AIS (see RnnRBM._nll_rows_built).  method: "ais" (biased low), "raise" (reverse AIS from the target rows, the same
+        ladder, chains and seed arguments: biased the other way) or "both" -> NllBracket(lower = the "ais" estimate, upper = the "raise" one)."""
+        nll_sides(method)
         refuse_host_model(self.store.device, "estimate_nll")
         dev = self.store.device if self.store.device is not None else default_device()
         inputs, targets = shifted_sequences(x.to(dev))
         self.build(inputs, targets, lengths, is_train=False, mode="eval")
-        return self._nll_rows_built(num_chains=num_chains, num_betas=num_betas, betas=betas, seed=seed)
+        return self._nll_rows_built(num_chains=num_chains, num_betas=num_betas, betas=betas, seed=seed, method=method)
 
     def _step_input(self, B, device):
         """[B, ld0] staging row block of single_step: the zero padding beyond the input width is written once, every step converts its
@@ -1455,10 +1511,13 @@ class RnnNade(RnnEstimator):
         r = [self._nll_tm[m][self._idx()] for m in range(self.num_tracks)]
         return r[0] if self.num_tracks == 1 else r
 
-    def _nll_rows_built(self, **ais):
-        """The exact NLL rows of the last build (API order, valid rows), summed over the NADE tracks: an NllEstimate with stderr 0."""
+    def _nll_rows_built(self, method="ais", **ais):
+        """The exact NLL rows of the last build (API order, valid rows), summed over the NADE tracks: an NllEstimate with stderr 0, whatever
+        the method ("both": the bracket of that one estimate with itself)."""
+        nll_sides(method)
         idx = self._idx()
-        return NllEstimate(sum(self._nll_tm[m][idx] for m in range(self.num_tracks)))
+        est = NllEstimate(sum(self._nll_tm[m][idx] for m in range(self.num_tracks)))
+        return nll_result(method, (est, est))
 
     @property
     def cond_probs(self):
@@ -1845,10 +1904,12 @@ class RnnRBM(RnnEstimator):
     def build_metrics(self, targets, predictions, cond_probs=None, log_probs=None):
         return self._rbm.build_metrics(targets, predictions, cond_probs, log_probs)
 
-    def _nll_rows_built(self, num_chains=64, num_betas=1000, betas=None, seed=None):
+    def _nll_rows_built(self, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais"):
         """AIS NLL of the last build's valid rows (API order):  -log p(v_t | v_<t) = F_t(v_t) + log Z_t with the row's CONDITIONAL biases
         bh_t, bv_t (the distribution sample() draws from, whatever bias_mode trained) and log Z_t estimated by RBM.log_partition -- the
-        chains keyed by the global row ids of build (t * 65536 + row0 + b), seed default self.seed.  Biased low: see NllEstimate."""
+        chains keyed by the global row ids of build (t * 65536 + row0 + b), seed default self.seed.  Biased low: see NllEstimate.
+        method "raise": log Z_t by RBM.log_partition_reverse from the row's target v_t (biased the other way); "both": the NllBracket."""
+        sides = nll_sides(method)
         cx = self._ctx
         B, T = cx["B"], cx["T"]
         D, Hn = self.num_dims, self.num_hidden[-1]
@@ -1860,13 +1921,13 @@ class RnnRBM(RnnEstimator):
         n = bh.shape[0]
         if n == 0:
             e = torch.zeros(0, device=dev)
-            return NllEstimate(e, e, e, e, e)
-        stats = torch.empty((n, 2), device=dev)
-        log_z = self._rbm.log_partition(bh, bv, num_chains, num_betas, betas, self.seed if seed is None else seed,
-                                        row_ids=rows[idx].to(torch.int32).contiguous(), stats=stats)
+            return nll_result(method, [NllEstimate(e, e, e, e, e) for _ in sides])
+        ids = rows[idx].to(torch.int32).contiguous()
+        tgt = cx["tgt"][idx].contiguous()
         F = torch.empty(n, device=dev)
-        ops.rbm_free_energy(cx["tgt"][idx].contiguous(), self._rbm.W, bh, bv, F)
-        return NllEstimate(F + log_z, log_z, F, stats[:, 1], stats[:, 0])
+        ops.rbm_free_energy(tgt, self._rbm.W, bh, bv, F)
+        s0 = self.seed if seed is None else seed
+        return nll_result(method, [rbm_nll_side(side, self._rbm, tgt, F, bh, bv, num_chains, num_betas, betas, s0, ids) for side in sides])
 
 
     def backward(self):
@@ -2155,9 +2216,11 @@ class RnnMultiRBM(RnnRBM):
     cost = property(lambda self: self._per_track(self._cost_tm))
     reconstruction_cost = property(lambda self: self._per_track(self._recon_tm))
 
-    def _nll_rows_built(self, num_chains=64, num_betas=1000, betas=None, seed=None):
+    def _nll_rows_built(self, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais"):
         """AIS NLL of the last build's valid rows: the SUM over the tracks of F_m(target_m) + log Z^_m on the row's conditional biases
-        (the tracks of a step are independent given the history), each track estimated as RnnRBM._nll_rows_built does with seed + m."""
+        (the tracks of a step are independent given the history), each track estimated as RnnRBM._nll_rows_built does with seed + m --
+        under every method; "both" sums each side of the bracket over the tracks."""
+        sides = nll_sides(method)
         cx = self._ctx
         B, T = cx["B"], cx["T"]
         bh_t, bv_t = self._split(cx["out"])
@@ -2168,17 +2231,17 @@ class RnnMultiRBM(RnnRBM):
         n = ids.numel()
         if n == 0:
             e = torch.zeros(0, device=dev)
-            return NllEstimate(e, e, e, e, e)
+            return nll_result(method, [NllEstimate(e, e, e, e, e) for _ in sides])
         s0 = self.seed if seed is None else seed
-        parts = []
+        parts = [[] for _ in sides]
         for m, r in enumerate(self._rbms):
             bh, bv = bh_t[m][idx].contiguous(), bv_t[m][idx].contiguous()
-            stats = torch.empty((n, 2), device=dev)
-            log_z = r.log_partition(bh, bv, num_chains, num_betas, betas, s0 + m, row_ids=ids, stats=stats)
+            tgt = cx["tgt"][m][idx].contiguous()
             F = torch.empty(n, device=dev)
-            ops.rbm_free_energy(cx["tgt"][m][idx].contiguous(), r.W, bh, bv, F)
-            parts.append(NllEstimate(F + log_z, log_z, F, stats[:, 1], stats[:, 0]))
-        return NllEstimate.total(parts)
+            ops.rbm_free_energy(tgt, r.W, bh, bv, F)
+            for side, part in zip(sides, parts):
+                part.append(rbm_nll_side(side, r, tgt, F, bh, bv, num_chains, num_betas, betas, s0 + m, ids))
+        return nll_result(method, [NllEstimate.total(p) for p in parts])
 
     def _backward_co(self):
         cx = self._ctx

@@ -457,17 +457,20 @@ class MultINNCore(Model):
         """The JOINT NLL of every valid time step of x [B, T, P, M] given the steps before it, summed over this mode's generators (each
         models its part of the step given the past: the per-track generators of jamming / feedback, the one generator of joint mode):
         builds in eval mode and returns a generators.NllEstimate (per valid row in API order; `mean` per valid step).  RBM generators are
-        estimated by AIS (ais: num_chains, num_betas, betas, seed -- a given seed s gives generator i the seed s + i; default: its own),
-        NADE generators are exact.  Note: generator_loss() -- what fit validates on -- is the MEAN over the generators of their losses, this
+        estimated by AIS (ais: num_chains, num_betas, betas, seed -- a given seed s gives generator i the seed s + i; default: its own --
+        and method: "ais" (default, biased low), "raise" (reverse AIS, biased the other way) or "both" -> a generators.NllBracket whose
+        sides each sum over the generators), NADE generators are exact under every method.  Note: generator_loss() -- what fit validates on -- is the MEAN over the generators of their losses, this
         is the SUM of their NLLs.  DBN encoders are refused: their generators model codes, not piano-roll cells."""
-        from .generators import NllEstimate, refuse_host_model
+        from .generators import nll_sides, total_nll, refuse_host_model
+        method = ais.get("method", "ais")
+        nll_sides(method)
         if self._encoder_type != "Pass":
             raise MnnUnsupported("estimate_nll through DBN encoders is not implemented: their generators' likelihood is over codes, not "
                                  "piano-roll cells")
         refuse_host_model(self.device, "estimate_nll")
         self.build(x, lengths=lengths, is_train=False, mode="eval")
         seed = ais.pop("seed", None)
-        return NllEstimate.total([g._nll_rows_built(seed=None if seed is None else seed + i, **ais) for i, g in enumerate(self._generators)])
+        return total_nll(method, [g._nll_rows_built(seed=None if seed is None else seed + i, **ais) for i, g in enumerate(self._generators)])
 
     def train_step(self, x, lengths, optimizer, lr=None):
         """build(x, lengths, is_train=True, mode='train') + train_generators(optimizer, lr): one optimiser step from a zero RNN state."""

@@ -772,14 +772,52 @@ def rbm_gibbs(v0, W, bh, bv, k, seed, row0=0, row_ids=None, sub0=0, p_v=None, v_
          _ptr(row_ids), int(sub0), _ptr(p_v), _ptr(v_out), _ptr(ws), _ptr(given), ld_given)
 
 
-def _check_ladder(betas):
+def _check_ladder(betas, what="rbm_ais"):
     """The AIS ladder: a float32 device vector, finite, non-decreasing, from exactly 0 to exactly 1, at least two values."""
-    _req(isinstance(betas, torch.Tensor) and betas.dtype == torch.float32 and betas.dim() == 1 and betas.is_contiguous(), "rbm_ais: betas f32 [L]")
-    _req(betas.numel() >= 2, "rbm_ais: the ladder needs at least two values (0 and 1)")
+    _req(isinstance(betas, torch.Tensor) and betas.dtype == torch.float32 and betas.dim() == 1 and betas.is_contiguous(), what + ": betas f32 [L]")
+    _req(betas.numel() >= 2, what + ": the ladder needs at least two values (0 and 1)")
     b = betas.detach().to("cpu", copy=True).double()        # a host copy: the ladder is validated before anything runs
-    _req(bool(torch.isfinite(b).all()), "rbm_ais: betas must be finite")
-    _req(bool((b[1:] >= b[:-1]).all()), "rbm_ais: betas must be non-decreasing")
-    _req(float(b[0]) == 0.0 and float(b[-1]) == 1.0, "rbm_ais: the ladder must start at 0 and end at 1")
+    _req(bool(torch.isfinite(b).all()), what + ": betas must be finite")
+    _req(bool((b[1:] >= b[:-1]).all()), what + ": betas must be non-decreasing")
+    _req(float(b[0]) == 0.0 and float(b[-1]) == 1.0, what + ": the ladder must start at 0 and end at 1")
+
+
+def _rbm_anneal(what, W, bh, bv, v, betas, num_chains, seed, row0, row_ids, log_z, log_w, v_out, stats):
+    """rbm_ais (v is None) and rbm_raise (v: the rows' data vectors): one set of checks, all before any allocation, and the call."""
+    D, Hn = W.shape
+    _req(W.dtype == torch.float32 and W.dim() == 2 and W.is_contiguous(), what + ": W f32 [D,Hn]")
+    N = max(bh.shape[0], bv.shape[0], 0 if log_z is None else log_z.shape[0], 0 if row_ids is None else row_ids.numel(),
+            v.shape[0] if isinstance(v, torch.Tensor) and v.dim() == 2 else 0)
+    _req(bh.dim() == 2 and bv.dim() == 2 and bh.shape[0] in (1, N) and bv.shape[0] in (1, N), what + ": bias rows must be 1 or N")
+    _ldb(bh, Hn), _ldb(bv, D)
+    if what == "rbm_raise":
+        _req(isinstance(v, torch.Tensor) and v.dtype == torch.uint8 and tuple(v.shape) == (N, D) and v.is_contiguous(),
+             what + ": v u8 [N, D] (one data vector per row)")
+    S = int(num_chains)
+    _req(S >= 1, what + ": num_chains >= 1")
+    _check_ladder(betas, what)
+    L = betas.numel()
+    _req(S * L < 2 ** 32, what + ": num_chains * len(betas) must be < 2^32 (the 32-bit sub counter)")
+    if row_ids is not None:
+        _req(row_ids.dtype == torch.int32 and row_ids.numel() == N and row_ids.is_contiguous(), what + ": row_ids int32 [N]")
+    dev = W.device
+    for t in (bh, bv, betas, row_ids, v):
+        _req(t is None or t.device == dev, what + ": every operand on W's device")
+    for t, shape, dt, name in ((log_z, (N,), torch.float32, "log_z f32 [N]"), (log_w, (N, S), torch.float32, "log_w f32 [N, S]"),
+                               (v_out, (N, S, D), torch.uint8, "v_out u8 [N, S, D]"), (stats, (N, 2), torch.float32, "stats f32 [N, 2]")):
+        if t is not None:
+            _req(t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, what + ": " + name)
+    _ptr(W)                                                          # no CPU path: refuse host tensors before allocating anything
+    if log_z is None:
+        log_z = torch.empty(N, device=dev)
+    ws = torch.empty(_lib.load().mnn_rbm_ais_workspace_bytes(N, D, Hn, S, L), dtype=torch.uint8, device=dev)
+    head = (_stream(), N, D, Hn, S, L, _ptr(betas), _ptr(W), _ptr(bh), _ldb(bh, Hn), _ptr(bv), _ldb(bv, D))
+    tail = (int(seed), int(row0), _ptr(row_ids), _ptr(log_z), _ptr(log_w), _ptr(v_out), _ptr(stats), _ptr(ws))
+    if v is None:
+        call("mnn_rbm_ais", *head, *tail)
+    else:
+        call("mnn_rbm_raise", *head, _ptr(v), *tail)
+    return log_z
 
 
 def rbm_ais(W, bh, bv, betas, num_chains, seed, row0=0, row_ids=None, log_z=None, log_w=None, v_out=None, stats=None):
@@ -787,32 +825,15 @@ def rbm_ais(W, bh, bv, betas, num_chains, seed, row0=0, row_ids=None, log_z=None
     have 1 or N rows (one row: shared by all N, whose chains differ by their row ids).  betas: the
     ladder, f32 device [L] (0 = b_0 <= ... <= b_{L-1} = 1).  Returns log_z f32 [N] (allocated if not given); optional outputs: log_w f32
     [N, S], v_out u8 [N, S, D] final chain states, stats f32 [N, 2] = (effective sample size, standard error of log_z).  log Z^ is biased low."""
-    D, Hn = W.shape
-    _req(W.dtype == torch.float32 and W.dim() == 2 and W.is_contiguous(), "rbm_ais: W f32 [D,Hn]")
-    N = max(bh.shape[0], bv.shape[0], 0 if log_z is None else log_z.shape[0], 0 if row_ids is None else row_ids.numel())
-    _req(bh.dim() == 2 and bv.dim() == 2 and bh.shape[0] in (1, N) and bv.shape[0] in (1, N), "rbm_ais: bias rows must be 1 or N")
-    _ldb(bh, Hn), _ldb(bv, D)
-    S = int(num_chains)
-    _req(S >= 1, "rbm_ais: num_chains >= 1")
-    _check_ladder(betas)
-    L = betas.numel()
-    _req(S * L < 2 ** 32, "rbm_ais: num_chains * len(betas) must be < 2^32 (the 32-bit sub counter)")
-    if row_ids is not None:
-        _req(row_ids.dtype == torch.int32 and row_ids.numel() == N and row_ids.is_contiguous(), "rbm_ais: row_ids int32 [N]")
-    dev = W.device
-    for t in (bh, bv, betas, row_ids):
-        _req(t is None or t.device == dev, "rbm_ais: every operand on W's device")
-    if log_z is None:
-        log_z = torch.empty(N, device=dev)
-    for t, shape, dt, what in ((log_z, (N,), torch.float32, "log_z f32 [N]"), (log_w, (N, S), torch.float32, "log_w f32 [N, S]"),
-                               (v_out, (N, S, D), torch.uint8, "v_out u8 [N, S, D]"), (stats, (N, 2), torch.float32, "stats f32 [N, 2]")):
-        if t is not None:
-            _req(t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, "rbm_ais: " + what)
-    _ptr(W)                                                          # no CPU path: refuse host tensors before allocating anything
-    ws = torch.empty(_lib.load().mnn_rbm_ais_workspace_bytes(N, D, Hn, S, L), dtype=torch.uint8, device=dev)
-    call("mnn_rbm_ais", _stream(), N, D, Hn, S, L, _ptr(betas), _ptr(W), _ptr(bh), _ldb(bh, Hn), _ptr(bv), _ldb(bv, D), int(seed), int(row0),
-         _ptr(row_ids), _ptr(log_z), _ptr(log_w), _ptr(v_out), _ptr(stats), _ptr(ws))
-    return log_z
+    return _rbm_anneal("rbm_ais", W, bh, bv, None, betas, num_chains, seed, row0, row_ids, log_z, log_w, v_out, stats)
+
+
+def rbm_raise(W, bh, bv, v, betas, num_chains, seed, row0=0, row_ids=None, log_z=None, log_w=None, v_out=None, stats=None):
+    """Reverse annealed importance sampling (mnn_rbm_raise; RAISE, Burda et al. 2015): rbm_ais's ladder run downwards from the rows' data
+    vectors v u8 [N, D], S chains per row on Philox streams 8 / 9.  Operands, checks and outputs as rbm_ais; log_z = log Z_0 - (logsumexp_c
+    log w_c - log S) is biased the other way from rbm_ais's: high in expectation over model-distributed data and, with a long enough
+    ladder, an upper end to rbm_ais's lower one -- not a bound per row."""
+    return _rbm_anneal("rbm_raise", W, bh, bv, v, betas, num_chains, seed, row0, row_ids, log_z, log_w, v_out, stats)
 
 
 def rbm_hidden(v, W, bh, stream_id, seed, row0, sub, p_h=None, h=None):

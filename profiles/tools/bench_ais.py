@@ -3,7 +3,10 @@ B x T = N rows per track, S chains, L ladder values.  Two measurements, one JSON
   model   MultINN.estimate_nll on a [B, T, 88, 5] batch (eval build of the five generators + five AIS launches), best of --reps;
   kernel  one ops.rbm_ais launch on N random bias rows at (88, 256): time, chain-steps per second (N S (L - 1)) and the fraction of the
           f32 matrix-core rate, counting 4 D Hn FLOP per chain-step against --peak TFLOP/s (155: the measured v_mfma_f32_32x32x2_f32 rate).
-`--only kernel` runs the kernel leg alone (for a `rocprofv3 --kernel-trace --stats` run of its own)."""
+  reverse one ops.rbm_raise launch (reverse AIS from random data rows) on the same rows, ladder and chains, timed in the same process in
+          alternation with the forward launch (--reps rounds of forward, reverse), and the ratio of the two best times.  The reverse run has
+          L hidden and L - 1 visible contractions against L - 1 and L - 2: parity is the expectation.
+`--only kernel` runs the kernel legs alone (for a `rocprofv3 --kernel-trace --stats` run of its own)."""
 import argparse
 import json
 import sys
@@ -62,14 +65,21 @@ def main():
         bv = torch.from_numpy((R.standard_normal((N, P)) * 0.3 - 3.0).astype(np.float32)).to(dev)
         betas = (torch.arange(L, dtype=torch.float64) / (L - 1)).float().to(dev)
         log_z = torch.empty(N, device=dev)
+        v = torch.from_numpy((R.random((N, P)) < 0.05).astype(np.uint8)).to(dev)
         ops.rbm_ais(W, bh, bv, betas, S, 1, log_z=log_z)                # warm-up
+        ops.rbm_raise(W, bh, bv, v, betas, S, 1, log_z=log_z)
         torch.cuda.synchronize()
-        t, _ = timed(lambda: ops.rbm_ais(W, bh, bv, betas, S, 1, log_z=log_z), a.reps)
+        t = t_rev = float("inf")
+        for _ in range(a.reps):                                         # alternating: both legs see the same neighbours on a shared host
+            t = min(t, timed(lambda: ops.rbm_ais(W, bh, bv, betas, S, 1, log_z=log_z), 1)[0])
+            t_rev = min(t_rev, timed(lambda: ops.rbm_raise(W, bh, bv, v, betas, S, 1, log_z=log_z), 1)[0])
         steps = N * S * (L - 1)
         flop = 4.0 * P * HN * steps
         print(json.dumps({"leg": "kernel", "rows": N, "chains": S, "betas": L, "D": P, "Hn": HN, "s": round(t, 4),
                           "chain_steps_per_s": float(f"{steps / t:.4g}"), "tflops": round(flop / t / 1e12, 2),
                           "fraction_of_f32_matrix_peak": round(flop / t / 1e12 / a.peak, 3)}), flush=True)
+        print(json.dumps({"leg": "reverse", "rows": N, "chains": S, "betas": L, "D": P, "Hn": HN, "s": round(t_rev, 4),
+                          "chain_steps_per_s": float(f"{N * S * L / t_rev:.4g}"), "ratio_to_forward": round(t_rev / t, 4)}), flush=True)
 
 
 if __name__ == "__main__":
