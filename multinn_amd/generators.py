@@ -289,6 +289,12 @@ class RnnEstimator(Generator):
     ragged_on_device = False
     _ls_dev = None
 
+    def lengths_fed(self):
+        """New lengths were copied into the static lengths of a captured ragged step.  A replay runs none of the build's Python, so the
+        API-order row index cached by `_idx()` (derived from the lengths of the replay before) is dropped here: the per-row properties
+        (log_probs, cond_probs, free_energy, cost, _outputs, ...) of the next replay index its rows by ITS lengths."""
+        self._flat_idx = None
+
     def _row_weight(self, lengths, B, T, device):
         """1/N_valid on valid rows (N_valid summed over ALL ranks), 0 on padding.  Leaves the host copy of N_valid in self._n_valid (the
         f16 loss scale is derived from it)."""
@@ -909,6 +915,8 @@ class RnnNade(RnnEstimator):
                 static_ntot.copy_(static_len.clamp(0, T).sum().float().reshape(1))
                 torch.distributed.all_reduce(static_ntot)
 
+        me = weakref.ref(self)                         # (run holds no model: capture_train_step)
+
         def feed(x=None, lengths=None):
             if x is not None:
                 static_x.copy_(x)
@@ -917,6 +925,7 @@ class RnnNade(RnnEstimator):
                     raise ValueError("this step was captured for full-length windows: capture it with lengths= to feed ragged ones")
                 static_len.copy_(lengths.to(device=dev, dtype=torch.int32))
                 set_total()
+                me().lengths_fed()
 
         set_total()
         run = self._capture_step(feed, lambda: self.build_pianoroll(static_x, static_len, is_train=True, mode="train", n_total_dev=static_ntot),

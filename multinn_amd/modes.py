@@ -21,6 +21,7 @@ scan.  The encoder-level ("global") metrics the reference adds to the graph but 
 """
 import abc
 import os
+import weakref
 
 import torch
 
@@ -499,6 +500,7 @@ class MultINNCore(Model):
         if ragged:
             for g in self._generators:
                 g.ragged_on_device = True
+        gens = [weakref.ref(g) for g in self._generators]          # (run holds no model: capture_train_step)
 
         def feed(x=None, lengths=None):
             if x is not None:
@@ -507,6 +509,8 @@ class MultINNCore(Model):
                 if not ragged:
                     raise ValueError("this step was captured for full-length windows: capture it with lengths= to feed ragged ones")
                 sl.copy_(lengths.to(device=sx.device, dtype=torch.int32))
+                for g in gens:                          # their cached row indices were derived from the lengths fed before
+                    g().lengths_fed()
 
         # warm-up steps are REAL optimiser steps: variables, persistent-kernel attributes and workspaces must exist before the capture.
         # warmup = 0 is for a caller that has just run this very step eagerly (driver._captured_step: the capture then executes nothing)

@@ -334,6 +334,57 @@ def test_numpy_vs_torch_rbm_grads():
         assert np.allclose(db, bt.grad.numpy(), rtol=1e-9, atol=1e-12)
 
 
+def test_rnn_rbm_ragged_lengths_equal_truncated_sequences_and_fd():
+    """rnn_rbm_forward / rnn_rbm_backward WITH `lengths` (the reference the ragged GPU tests compare with): a window holding a sequence of
+    length 0, one of length 1 and one of length T.  (a) loss and per-row cost equal the concatenation of per-sequence truncated calls with
+    lengths=None, the same row ids and the same dropout uniforms, to 1e-12; (b) the analytic gradients of W, Wuh, Wuv (every 23rd entry and
+    the largest one) and one entry of each LSTM kernel equal central differences (step 1e-6, the chain ends held fixed) to 1e-5 of the
+    variable's largest gradient entry."""
+    B, T, D, Hn, units, k, kp, seed = 4, 5, 12, 20, [32, 32], 3, 0.9, 13
+    lengths = np.array([5, 0, 1, 3])
+    x = (np.random.default_rng(8).random((B, T, D, 1)) < .25).astype(np.float64)
+    inp, tgt = G.joint_inputs(x)
+    p = G.init_rnn_rbm(5, D, D, Hn, units, np.float64)
+    p['bh'] += .1; p['bv'] -= .2
+    du = G.dropout_uniforms(seed, B, T, units)
+    ids = lambda b, n: np.array([t * 65536 + b for t in range(n)])
+    rows = np.concatenate([ids(b, lengths[b]) for b in range(B)]).astype(np.int64)
+    fw = G.rnn_rbm_forward(inp, tgt, lengths, p, k, seed, kp, du, row_ids=rows)
+    N = int(lengths.sum())
+    assert fw['cost'].shape == (N,) and fw['free_energy'].shape == (N,) and fw['p_v'].shape == (N, D)
+    parts = []
+    for b in range(B):
+        n = int(lengths[b])
+        if n:
+            one = G.rnn_rbm_forward(inp[b:b + 1, :n], tgt[b:b + 1, :n], None, p, k, seed, kp, [u[b:b + 1, :n] for u in du], row_ids=ids(b, n))
+            parts.append(one)
+    cost = np.concatenate([o['cost'] for o in parts])
+    assert np.abs(fw['cost'] - cost).max() < 1e-12 and abs(fw['loss'] - cost.mean()) < 1e-12
+    assert np.abs(fw['free_energy'] - np.concatenate([o['free_energy'] for o in parts])).max() < 1e-12
+    assert np.array_equal(fw['v_sample'], np.concatenate([o['v_sample'] for o in parts]))
+    g = G.rnn_rbm_backward(fw, p)
+    vs = fw['v_sample']
+
+    def loss_at(q):                                     # the chain ends are constants of the loss (stop_gradient, rbm.py:229)
+        f = G.rnn_rbm_forward(inp, tgt, lengths, q, 0, seed, kp, du, row_ids=rows)
+        return rbm.free_energy_cost(f['tgt'], vs, q['W'], f['bh_t'], f['bv_t'])[0].mean()
+
+    def fd(arr, idx):
+        old = arr[idx]
+        arr[idx] = old + 1e-6; up = loss_at(p)
+        arr[idx] = old - 1e-6; dn = loss_at(p)
+        arr[idx] = old
+        return (up - dn) / 2e-6
+    for name in ('W', 'Wuh', 'Wuv'):
+        ga = g[name]
+        picks = sorted(set(range(0, ga.size, 23)) | {int(np.abs(ga).argmax())})
+        err = max(abs(fd(p[name], np.unravel_index(i, ga.shape)) - ga.flat[i]) for i in picks)
+        assert err < 1e-5 * np.abs(ga).max(), (name, err / np.abs(ga).max())
+    for l, (dW, _) in enumerate(g['lstm']):
+        idx = np.unravel_index(int(np.abs(dW).argmax()), dW.shape)
+        assert abs(fd(p['lstm'][l][0], idx) - dW[idx]) < 1e-5 * abs(dW[idx]), l
+
+
 def test_generate_scan_shapes_and_determinism():
     p = G.init_rnn_nade(3, 8, 8, 6, [8, 5], np.float32)
     intro = (R.random((2, 3, 8)) < .3).astype(np.float32)
