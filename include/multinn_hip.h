@@ -43,7 +43,7 @@ enum { MNN_STREAM_DROPOUT = 0, MNN_STREAM_NADE = 1, MNN_STREAM_RBM_H = 2, MNN_ST
 
 /* ABI version of THIS header: bumped whenever a signature or a descriptor struct changes.  mnn_version() returns the value the library
  * was built with; a loader must compare the two before its first call (multinn_amd/_lib.py load() does) -- a library built for another
- * version reads garbage arguments without any diagnosis otherwise.  124: + mnn_rbm_ais / mnn_rbm_ais_workspace_bytes (AIS estimate of an RBM's log partition function); mnn_rbm_raise (its reverse run) joined later as a new symbol, without a bump.  123: the clamped Gibbs chain -- mnn_rbm_gibbs gained a trailing `given`, `ld_given`.  122: conditional sampling -- a trailing `given` on mnn_nade_sample and mnn_generate_scan, mnn_nade_sample_job gained `given`.  121 (round 6): + mnn_gemm_tn_rows.  120 (round 6): mnn_step_increment gained `ls_dyn`, `ls_good`, `grow_after` (dynamic f16 loss scale).  119 (round 6): mnn_det_dense_job gained `Wp`, + mnn_det_dense_pack / _pack_bytes.  118 (round 6): mnn_det_lstm_job gained `Wp`, + mnn_det_lstm_pack / _pack_bytes, mnn_generate_scan_workspace_bytes gained `n_in`.  117 (round 6): + mnn_lstm_cluster_bwd_ok, + mnn_ragged_index / mnn_rows_gather16 / mnn_rows_scatter_f32, `n_rows_dev` on the gated NADE forwards and mnn_nade_logprob_bwd, `inv` / `hdr` on mnn_pianoroll_shift_timemajor_t, + mnn_lstm_resident_{fwd,bwd}_multi / mnn_lstm_cluster_{fwd,bwd}_multi / _bwd_multi_ok, `unsafe` on mnn_nade_logprob_fwd_gated, `unsafe` on mnn_nade_logprob_bwd.  116: + mnn_lstm_cluster_ok / _fwd / _bwd.  115: mnn_step_increment gained `sumsq`, `clip_norm`.  114: + mnn_lstm_resident_ok / _fwd / _bwd.  113: mnn_pianoroll_shift_timemajor_t gained `count`.  112: + mnn_generate_scan.  111: mnn_rbm_free_energy gained `p_h`.  110: mnn_clip_adam_step gained `skipped`; the dtype arguments of
+ * version reads garbage arguments without any diagnosis otherwise.  124: + mnn_rbm_ais / mnn_rbm_ais_workspace_bytes (AIS estimate of an RBM's log partition function); mnn_rbm_raise (its reverse run) joined later as a new symbol, without a bump; so did mnn_rbm_ais_given / mnn_rbm_raise_given (the clamped estimators).  123: the clamped Gibbs chain -- mnn_rbm_gibbs gained a trailing `given`, `ld_given`.  122: conditional sampling -- a trailing `given` on mnn_nade_sample and mnn_generate_scan, mnn_nade_sample_job gained `given`.  121 (round 6): + mnn_gemm_tn_rows.  120 (round 6): mnn_step_increment gained `ls_dyn`, `ls_good`, `grow_after` (dynamic f16 loss scale).  119 (round 6): mnn_det_dense_job gained `Wp`, + mnn_det_dense_pack / _pack_bytes.  118 (round 6): mnn_det_lstm_job gained `Wp`, + mnn_det_lstm_pack / _pack_bytes, mnn_generate_scan_workspace_bytes gained `n_in`.  117 (round 6): + mnn_lstm_cluster_bwd_ok, + mnn_ragged_index / mnn_rows_gather16 / mnn_rows_scatter_f32, `n_rows_dev` on the gated NADE forwards and mnn_nade_logprob_bwd, `inv` / `hdr` on mnn_pianoroll_shift_timemajor_t, + mnn_lstm_resident_{fwd,bwd}_multi / mnn_lstm_cluster_{fwd,bwd}_multi / _bwd_multi_ok, `unsafe` on mnn_nade_logprob_fwd_gated, `unsafe` on mnn_nade_logprob_bwd.  116: + mnn_lstm_cluster_ok / _fwd / _bwd.  115: mnn_step_increment gained `sumsq`, `clip_norm`.  114: + mnn_lstm_resident_ok / _fwd / _bwd.  113: mnn_pianoroll_shift_timemajor_t gained `count`.  112: + mnn_generate_scan.  111: mnn_rbm_free_energy gained `p_h`.  110: mnn_clip_adam_step gained `skipped`; the dtype arguments of
  * mnn_pianoroll_shift_timemajor_t / mnn_grad_rows_fanout and the `f16` descriptor fields of round 3 are part of it. */
 #define MNN_ABI_VERSION 124
 int mnn_version(void);
@@ -543,6 +543,24 @@ int mnn_rbm_ais(mnn_stream_t s, int N, int D, int Hn, int n_chains, int n_betas,
 int mnn_rbm_raise(mnn_stream_t s, int N, int D, int Hn, int n_chains, int n_betas, const float* betas, const float* W, const float* bh, int ld_bh,
                   const float* bv, int ld_bv, const uint8_t* v, uint64_t seed, uint32_t row0, const uint32_t* row_ids, float* log_z, float* log_w,
                   uint8_t* v_out, float* stats, void* workspace);
+
+/* Clamped AIS / reverse AIS (DESIGN.md section 4 "Clamped AIS"): mnn_rbm_ais and mnn_rbm_raise with trailing codes `given` u8 [N, ld_given],
+ * ld_given >= D, in mnn_rbm_gibbs's convention -- 0 / 1 clamp the visible to that value, 255 leaves it free.  With G a row's clamped cells
+ * and F its free ones the target is Z_c = sum over {v : v_G = c_G} and h of exp(bv.v + bh.h + vWh): F_1(v) + log Z_c = -log p(v_F | v_G),
+ * F_1 the free energy of the full vector (mnn_rbm_free_energy).  The ladder is mnn_rbm_ais's with the clamped cells held at their codes on
+ * every rung: log Z_0 = sum_{d in F} softplus(bv_d) + sum_{d in G} bv_d c_d + sum_j softplus(bh_j); a clamped cell of the base draw is its
+ * code and consumes no uniform; the increments are unchanged (s = vW over all visibles); a transition's hidden phase is unchanged and its
+ * visible phase leaves a clamped cell at its code, every free cell drawing from the uniform it draws unclamped (the clamped chain of
+ * mnn_rbm_gibbs); the reverse chains start from v with each clamped cell replaced by its code.  log_z is log Z^_c including the sum over G.
+ * given = NULL is mnn_rbm_ais / mnn_rbm_raise (the same kernels, the same bits -- those two entries pass NULL, 0); all codes 255 gives
+ * those bits too.  The kernel form is the shape's, whatever `given`; the streaming form's LDS requirement counts the row's D code bytes.
+ * Workspace, requirements and outputs otherwise as mnn_rbm_ais / mnn_rbm_raise; both bias statements carry over. */
+int mnn_rbm_ais_given(mnn_stream_t s, int N, int D, int Hn, int n_chains, int n_betas, const float* betas, const float* W, const float* bh,
+                      int ld_bh, const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, float* log_z, float* log_w,
+                      uint8_t* v_out, float* stats, void* workspace, const uint8_t* given, int ld_given);
+int mnn_rbm_raise_given(mnn_stream_t s, int N, int D, int Hn, int n_chains, int n_betas, const float* betas, const float* W, const float* bh,
+                        int ld_bh, const float* bv, int ld_bv, const uint8_t* v, uint64_t seed, uint32_t row0, const uint32_t* row_ids,
+                        float* log_z, float* log_w, uint8_t* v_out, float* stats, void* workspace, const uint8_t* given, int ld_given);
 
 /* dz = dy * y * (1 - y) over n f32 words (dz may alias dy): backward of the sigmoid Dense layers of the feedback module (dnn.py:60-76). */
 int mnn_sigmoid_grad_f32(mnn_stream_t s, long n, const float* dy, const float* y, float* dz);

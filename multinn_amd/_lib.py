@@ -164,6 +164,8 @@ SIGNATURES["mnn_sigmoid_grad_f32"] = (_i, [_p, _l, _p, _p, _p])
 SIGNATURES["mnn_rbm_ais_workspace_bytes"] = (_sz, [_i, _i, _i, _i, _i])
 SIGNATURES["mnn_rbm_ais"] = (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _u64, _u32, _p, _p, _p, _p, _p, _p])
 SIGNATURES["mnn_rbm_raise"] = (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _p, _u64, _u32, _p, _p, _p, _p, _p, _p])
+SIGNATURES["mnn_rbm_ais_given"] = (_i, SIGNATURES["mnn_rbm_ais"][1] + [_p, _i])
+SIGNATURES["mnn_rbm_raise_given"] = (_i, SIGNATURES["mnn_rbm_raise"][1] + [_p, _i])
 SIGNATURES["mnn_rbm_gibbs_multi"] = (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _u32, _p, _u32, _p, _l, _i, _l, _p])
 SIGNATURES["mnn_rbm_free_energy_multi"] = (_i, [_p, _i, _p, _i, _i, _i, _i, _i])
 SIGNATURES["mnn_rbm_cd_rows"] = (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p])

@@ -193,6 +193,26 @@ def given_tracks(given_mask, shape):
     return [bool(v) for v in per.all(0)], [bool(v) for v in per.any(0)]
 
 
+def given_mask_tracks(given_mask, shape, tracks=1):
+    """The mask of a conditional NLL over a batch of `shape` = [B, T, F] or [B, T, P, M], seen by a model of `tracks` tracks over the
+    flattened features (feature f is track f % tracks: the joint order p M + m, the MultiNADE / MultiRBM order i tracks + m; one track: the
+    whole step).  Host checks only (ValueError for a mask that is not bool or does not broadcast to `shape`) ->
+    (mask4, shape4, whole, some): the mask as it broadcasts to shape4 = [B, T, F / tracks, tracks], and given_tracks of it."""
+    shape = tuple(int(n) for n in shape)
+    if not torch.is_tensor(given_mask):
+        raise ValueError("given_mask must be a bool tensor")
+    if len(shape) not in (3, 4):
+        raise ValueError(f"x must be [B, T, F] or [B, T, P, M], got {shape}")
+    _check_mask(shape, given_mask)
+    F = shape[2] * (shape[3] if len(shape) == 4 else 1)
+    if F % tracks:
+        raise ValueError(f"{F} features do not split into {tracks} tracks")
+    shape4 = (shape[0], shape[1], F // tracks, tracks)
+    mask4 = given_mask if shape == shape4 else given_mask.expand(shape).reshape(shape4)
+    whole, some = given_tracks(mask4, shape4)
+    return mask4, shape4, whole, some
+
+
 # --------------------------------------------------------------------------------------------
 # Sampling temperature.  A NADE generator draws visible i as u < sigmoid(logit_i / T) (its nll / probabilities stay the model's own); an RBM
 # generator runs the Gibbs chain of exp(-E / T), every conditional sigmoid(z / T).  T is one number or one per track.
@@ -655,29 +675,33 @@ class RBM(Model):
                       given=given, temperature=temperature)
         return p_v, v_s
 
-    def log_partition(self, bh=None, bv=None, num_chains=64, num_betas=1000, betas=None, seed=None, row0=0, row_ids=None, stats=None):
+    def log_partition(self, bh=None, bv=None, num_chains=64, num_betas=1000, betas=None, seed=None, row0=0, row_ids=None, stats=None, given=None):
         """log Z of each bias row by annealed importance sampling (ops.rbm_ais; DESIGN.md section 4 "AIS estimator") -> log Z^ f32 [N].
         bh / bv: [N or 1, Hn] / [N or 1, D] rows (default: this RBM's own biases).  betas: the ladder (0 = b_0 <= ... <= b_{L-1} = 1);
         default ais_ladder(num_betas), uniform -- nobody has tuned or measured it.  Z^ is unbiased for Z, so log Z^ is biased LOW.
-        stats (optional f32 [N, 2]) receives (effective sample size, standard error of log Z^)."""
+        stats (optional f32 [N, 2]) receives (effective sample size, standard error of log Z^).
+        given (optional): codes u8 [N, D] (ops.rbm_ais; 0 / 1 clamp, 255 free) -> log Z^_c of the clamped RBM (DESIGN.md section 4 "Clamped
+        AIS"): free_energy(v) + log Z^_c = -log p(v_free | v_clamped) for a v that agrees with the codes."""
         bh = bh if bh is not None else self.bh
         bv = bv if bv is not None else self.bv
         dev = self.W.device
         betas = ais_ladder(num_betas, dev) if betas is None else torch.as_tensor(betas, dtype=torch.float32).to(dev).contiguous()
-        return ops.rbm_ais(self.W, bh, bv, betas, num_chains, self.seed if seed is None else seed, row0, row_ids, stats=stats)
+        return ops.rbm_ais(self.W, bh, bv, betas, num_chains, self.seed if seed is None else seed, row0, row_ids, stats=stats, given=given)
 
-    def log_partition_reverse(self, v, bh=None, bv=None, num_chains=64, num_betas=1000, betas=None, seed=None, row0=0, row_ids=None, stats=None):
+    def log_partition_reverse(self, v, bh=None, bv=None, num_chains=64, num_betas=1000, betas=None, seed=None, row0=0, row_ids=None, stats=None,
+                              given=None):
         """log Z of each bias row by REVERSE annealed importance sampling from the row's data vector v [N, D] (ops.rbm_raise; DESIGN.md
         section 4 "Reverse AIS") -> log Z^_rev f32 [N].  Arguments as log_partition, the same ladder.  1 / Z^_rev is unbiased for the annealing
         model's likelihood ratio of v, so log Z^_rev is biased the other way from log_partition's: HIGH in expectation over data drawn from
         the model.  With a long enough ladder the two bracket log Z and their gap says whether it was long enough; for an arbitrary v on a
-        short ladder log Z^_rev can fall below the truth -- it is not a bound per row."""
+        short ladder log Z^_rev can fall below the truth -- it is not a bound per row.  given (optional): codes as log_partition takes them --
+        the reverse estimate of the clamped log Z^_c, with the same two statements about its bias and no more."""
         bh = bh if bh is not None else self.bh
         bv = bv if bv is not None else self.bv
         dev = self.W.device
         betas = ais_ladder(num_betas, dev) if betas is None else torch.as_tensor(betas, dtype=torch.float32).to(dev).contiguous()
-        return ops.rbm_raise(self.W, bh, bv, v.to(torch.uint8).contiguous(), betas, num_chains, self.seed if seed is None else seed, row0, row_ids,
-                             stats=stats)
+        return ops.rbm_raise_given(self.W, bh, bv, v.to(torch.uint8).contiguous(), given, betas, num_chains, self.seed if seed is None else seed,
+                                   row0, row_ids, stats=stats)
 
     def free_energy(self, v, bh=None, bv=None):
         bh = bh if bh is not None else self.bh

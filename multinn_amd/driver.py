@@ -157,18 +157,28 @@ def _captured_step(generator, xb, optimizer, lr, max_graphs=8, lengths=None):
     return graphs[key]
 
 
-def evaluate(generator, X, lengths, batch_size, piece_size, device=None, nll="loss", ais=None):
+def evaluate(generator, X, lengths, batch_size, piece_size, device=None, nll="loss", ais=None, given_mask=None):
     """utils/training.py:180-213 collect_metrics: mean generator NLL per valid row over all windows.
     nll="loss" (default): the training loss (an RBM generator's is the CD cost, a difference of free energies, not a likelihood).
     nll="ais": the model's estimate_nll(x, lengths, **ais) -- exact for NADE generators, annealed importance sampling for RBM generators
     (biased low), summed over a mode's generators.
     nll="raise": the same with estimate_nll(method="raise") -- reverse AIS, biased the other way (conservative).
     nll="bracket": estimate_nll(method="both"); returns {"lower": the "ais" mean, "upper": the "raise" mean, "gap": upper - lower}, each
-    equal to its own call's value: a gap well above its noise says the ladder (ais: num_betas) is too short for either end to be trusted."""
+    equal to its own call's value: a gap well above its noise says the ladder (ais: num_betas) is too short for either end to be trusted.
+    given_mask (optional, with nll "ais" / "raise" / "bracket"): a batch-independent bool mask, [M] or [P, M], passed to every window's
+    estimate_nll -- the mean CONDITIONAL NLL per valid step of the cells outside the mask given those under it (and the past)."""
     import torch
     methods = {"ais": "ais", "raise": "raise", "bracket": "both"}
     if nll != "loss" and nll not in methods:
         raise ValueError(f"nll must be 'loss', 'ais', 'raise' or 'bracket', got {nll!r}")
+    cond = {}
+    if given_mask is not None:
+        if nll == "loss":
+            raise ValueError("given_mask needs nll 'ais', 'raise' or 'bracket': the training loss has no conditional form")
+        given_mask = torch.as_tensor(given_mask)
+        if given_mask.dtype != torch.bool or given_mask.dim() not in (1, 2):
+            raise ValueError(f"given_mask must be a batch-independent bool mask [M] or [P, M], got {given_mask.dtype} {tuple(given_mask.shape)}")
+        cond = dict(given_mask=given_mask)
     tot, cnt, tot_upper = 0.0, 0, 0.0
     ids = np.arange(X.shape[0])
     for w in iter_windows(ids, lengths, X.shape[1], batch_size, piece_size):
@@ -179,7 +189,7 @@ def evaluate(generator, X, lengths, batch_size, piece_size, device=None, nll="lo
         full = bool((len_batch == max_len).all())
         if nll != "loss":
             n = int(len_batch.sum())
-            est = generator.estimate_nll(xb, None if full else torch.from_numpy(len_batch).to(xb.device), **dict(ais or {}, method=methods[nll]))
+            est = generator.estimate_nll(xb, None if full else torch.from_numpy(len_batch).to(xb.device), **dict(ais or {}, method=methods[nll]), **cond)
             tot += (est.lower if nll == "bracket" else est).mean * n
             tot_upper += est.upper.mean * n if nll == "bracket" else 0.0
             cnt += n

@@ -19,7 +19,7 @@ import weakref
 import torch
 
 from . import ops
-from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, sampling_temperature, temperature_key, glorot_uniform, zeros_init, default_device, capture_train_step
+from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, given_codes, given_mask_tracks, sampling_temperature, temperature_key, glorot_uniform, zeros_init, default_device, capture_train_step
 from .training import compute_gradients, world, dp_active, AdamOptimizer
 from ._lib import MnnUnsupported
 from .lstm_stack import LstmStack, _SINGLE, drive, drive_group, _det_f32, det_steps
@@ -130,15 +130,30 @@ def total_nll(method, parts):
     return NllBracket.total(parts) if method == "both" else NllEstimate.total(parts)
 
 
-def rbm_nll_side(side, rbm, v, F, bh, bv, num_chains, num_betas, betas, seed, ids):
+def rbm_nll_side(side, rbm, v, F, bh, bv, num_chains, num_betas, betas, seed, ids, given=None):
     """One RBM's NLL rows F + log Z^ with log Z^ from AIS (side "ais": RBM.log_partition) or reverse AIS from the rows' targets v (side
-    "raise": RBM.log_partition_reverse), chains keyed by the row ids."""
+    "raise": RBM.log_partition_reverse), chains keyed by the row ids.  given (optional): the rows' codes u8 [n, D] (targets at the given
+    cells, 255 at the free ones) -> the CONDITIONAL NLL rows -log p(v_free | v_given) = F(v) + log Z^_c (the clamped estimators)."""
     stats = torch.empty((bh.shape[0], 2), device=bh.device)
+    kw = {} if given is None else dict(given=given)
     if side == "ais":
-        log_z = rbm.log_partition(bh, bv, num_chains, num_betas, betas, seed, row_ids=ids, stats=stats)
+        log_z = rbm.log_partition(bh, bv, num_chains, num_betas, betas, seed, row_ids=ids, stats=stats, **kw)
     else:
-        log_z = rbm.log_partition_reverse(v, bh, bv, num_chains, num_betas, betas, seed, row_ids=ids, stats=stats)
+        log_z = rbm.log_partition_reverse(v, bh, bv, num_chains, num_betas, betas, seed, row_ids=ids, stats=stats, **kw)
     return NllEstimate(F + log_z, log_z, F, stats[:, 1], stats[:, 0])
+
+
+def given_nll_result(method, n, device):
+    """estimate_nll of n rows whose every cell is given: -log p(nothing | everything) = 0, exactly -- one exact estimate (no log Z^, stderr
+    0) on both sides, as an exact generator's."""
+    est = NllEstimate(torch.zeros(n, device=device))
+    return nll_result(method, (est, est))
+
+
+NADE_MASK_REFUSAL = ("the conditional NLL of a NADE under a mask that leaves it partly given is not implemented: a NADE factorises over its "
+                     "visibles in their order (the joint NADE's are ordered p M + m, all tracks of a pitch side by side), so "
+                     "-log p(free | given) is not a sum of its conditionals -- it needs the sum over the free visibles ordered before a "
+                     "given one.  A mask under which every NADE is wholly given or wholly free is exact")
 
 
 def refuse_host_model(device, what):
@@ -406,17 +421,33 @@ class RnnEstimator(Generator):
             self._grad_sumsq = compute_gradients(optimizer, self.store, self.clip_norm, lr, reduce=False)
         return capture_train_step(feed, step, warmup, [self], lambda: [self.store], split=dp_active(), fwd_bwd=fwd_bwd, opt=opt, **kw)
 
-    def estimate_nll(self, x, lengths=None, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais"):
+    def estimate_nll(self, x, lengths=None, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais", given_mask=None):
         """NLL of every step of x [B, T, F] (or [B, T, P, M]) given the steps before it: builds in eval mode (keep_prob 1) on inputs = x
         shifted by one all-zero step, targets = x, and returns an NllEstimate over the valid rows.  RnnNade: exact (the AIS arguments are
         ignored).  RnnRBM: AIS (see RnnRBM._nll_rows_built).  method: "ais" (biased low), "raise" (reverse AIS from the target rows, the same
-        ladder, chains and seed arguments: biased the other way) or "both" -> NllBracket(lower = the "ais" estimate, upper = the "raise" one)."""
+        ladder, chains and seed arguments: biased the other way) or "both" -> NllBracket(lower = the "ais" estimate, upper = the "raise" one).
+        given_mask (optional, bool, broadcastable to x): the CONDITIONAL NLL of every step -- row t is -log p(x_t,free | x_t,given, x_<t),
+        teacher-forced on all of x_<t, the cells under the mask given.  RBM estimators: the clamped estimators (DESIGN.md section 4 "Clamped
+        AIS"), any mask; a track wholly given adds exactly 0 and runs no chain.  NADE estimators: exact where every NADE is wholly given or
+        wholly free, MnnUnsupported otherwise.  The sum over t is NOT -log p(x_free | x_given) of the sequence: later given cells say
+        something about earlier free ones, which no teacher-forced row sees."""
         nll_sides(method)
+        cond = None
+        if given_mask is not None:                                  # host checks and refusals, before any device work
+            cond = given_mask_tracks(given_mask, x.shape, getattr(self, "num_tracks", 1))
+            self._refuse_nll_given(cond[2], cond[3])
         refuse_host_model(self.store.device, "estimate_nll")
         dev = self.store.device if self.store.device is not None else default_device()
         inputs, targets = shifted_sequences(x.to(dev))
         self.build(inputs, targets, lengths, is_train=False, mode="eval")
-        return self._nll_rows_built(num_chains=num_chains, num_betas=num_betas, betas=betas, seed=seed, method=method)
+        kw = {}
+        if cond is not None:
+            mask4, shape4, whole, some = cond
+            kw["given"] = (given_codes(targets.reshape(shape4), mask4, shape4).reshape(targets.shape), whole, some)
+        return self._nll_rows_built(num_chains=num_chains, num_betas=num_betas, betas=betas, seed=seed, method=method, **kw)
+
+    def _refuse_nll_given(self, whole, some):
+        """MnnUnsupported for a conditional-NLL mask this estimator cannot honour (per track of it: every / any cell given); host only."""
 
     def _step_input(self, B, device):
         """[B, ld0] staging row block of single_step: the zero padding beyond the input width is written once, every step converts its
@@ -787,12 +818,24 @@ class RnnNade(RnnEstimator):
         r = [self._nll_tm[m][self._idx()] for m in range(self.num_tracks)]
         return r[0] if self.num_tracks == 1 else r
 
-    def _nll_rows_built(self, method="ais", **ais):
+    def _refuse_nll_given(self, whole, some):
+        if any(s and not w for w, s in zip(whole, some)):
+            raise MnnUnsupported(NADE_MASK_REFUSAL)
+
+    def _nll_rows_built(self, method="ais", given=None, **ais):
         """The exact NLL rows of the last build (API order, valid rows), summed over the NADE tracks: an NllEstimate with stderr 0, whatever
-        the method ("both": the bracket of that one estimate with itself)."""
+        the method ("both": the bracket of that one estimate with itself).  given (optional): (codes, whole, some) as RnnRBM._nll_rows_built
+        takes them -- the NADE of a wholly given track adds 0, that of a wholly free track its rows (the tracks of a step are independent
+        given the history); any other mask is refused."""
         nll_sides(method)
         idx = self._idx()
-        est = NllEstimate(sum(self._nll_tm[m][idx] for m in range(self.num_tracks)))
+        free = range(self.num_tracks)
+        if given is not None:
+            self._refuse_nll_given(given[1], given[2])
+            free = [m for m in free if not given[1][m]]
+            if not free:
+                return given_nll_result(method, idx.numel(), idx.device)
+        est = NllEstimate(sum(self._nll_tm[m][idx] for m in free))
         return nll_result(method, (est, est))
 
     @property
@@ -1183,17 +1226,23 @@ class RnnRBM(RnnEstimator):
     def build_metrics(self, targets, predictions, cond_probs=None, log_probs=None):
         return self._rbm.build_metrics(targets, predictions, cond_probs, log_probs)
 
-    def _nll_rows_built(self, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais"):
+    def _nll_rows_built(self, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais", given=None):
         """AIS NLL of the last build's valid rows (API order):  -log p(v_t | v_<t) = F_t(v_t) + log Z_t with the row's CONDITIONAL biases
         bh_t, bv_t (the distribution sample() draws from, whatever bias_mode trained) and log Z_t estimated by RBM.log_partition -- the
         chains keyed by the global row ids of build (t * 65536 + row0 + b), seed default self.seed.  Biased low: see NllEstimate.
-        method "raise": log Z_t by RBM.log_partition_reverse from the row's target v_t (biased the other way); "both": the NllBracket."""
+        method "raise": log Z_t by RBM.log_partition_reverse from the row's target v_t (biased the other way); "both": the NllBracket.
+        given (optional): (codes u8 [B, T, D] -- the targets at the given cells, 255 at the free ones: common.given_codes --, whole, some:
+        one-element lists, whether every / any cell is given: common.given_tracks) -> the conditional rows -log p(v_t,free | v_t,given,
+        v_<t) = F_t(v_t) + log Z_t,c, the stationary distribution of the clamped chain generate(given=) runs at that step.  Every cell
+        given: exactly 0 and no chain; no cell given: the call without `given`."""
         sides = nll_sides(method)
         cx = self._ctx
         B, T = cx["B"], cx["T"]
         D, Hn = self.num_dims, self.num_hidden[-1]
         out, dev = cx["out"], cx["out"].device
         idx = self._idx()
+        if given is not None and given[1][0]:
+            return given_nll_result(method, idx.numel(), dev)
         rows = (torch.arange(T, device=dev)[:, None] * 65536 + (self.row0 + torch.arange(B, device=dev))[None, :]).reshape(-1)
         bh = out[:, :Hn][idx].contiguous()
         bv = out[:, Hn:Hn + D][idx].contiguous()
@@ -1206,7 +1255,10 @@ class RnnRBM(RnnEstimator):
         F = torch.empty(n, device=dev)
         ops.rbm_free_energy(tgt, self._rbm.W, bh, bv, F)
         s0 = self.seed if seed is None else seed
-        return nll_result(method, [rbm_nll_side(side, self._rbm, tgt, F, bh, bv, num_chains, num_betas, betas, s0, ids) for side in sides])
+        codes = None
+        if given is not None and given[2][0]:
+            codes = given[0].transpose(0, 1).reshape(T * B, D)[idx].contiguous()              # time-major rows, then the targets' row order
+        return nll_result(method, [rbm_nll_side(side, self._rbm, tgt, F, bh, bv, num_chains, num_betas, betas, s0, ids, codes) for side in sides])
 
 
     def backward(self):
@@ -1495,10 +1547,12 @@ class RnnMultiRBM(RnnRBM):
     cost = property(lambda self: self._per_track(self._cost_tm))
     reconstruction_cost = property(lambda self: self._per_track(self._recon_tm))
 
-    def _nll_rows_built(self, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais"):
+    def _nll_rows_built(self, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais", given=None):
         """AIS NLL of the last build's valid rows: the SUM over the tracks of F_m(target_m) + log Z^_m on the row's conditional biases
         (the tracks of a step are independent given the history), each track estimated as RnnRBM._nll_rows_built does with seed + m --
-        under every method; "both" sums each side of the bracket over the tracks."""
+        under every method; "both" sums each side of the bracket over the tracks.  given (optional): (codes u8 [B, T, D * M] in the composer
+        layout, whole, some: per track) -- each track's conditional rows as RnnRBM._nll_rows_built forms them; a wholly given track adds
+        exactly 0 and runs no chain, a track with no given cell is estimated as without `given`."""
         sides = nll_sides(method)
         cx = self._ctx
         B, T = cx["B"], cx["T"]
@@ -1512,14 +1566,20 @@ class RnnMultiRBM(RnnRBM):
             e = torch.zeros(0, device=dev)
             return nll_result(method, [NllEstimate(e, e, e, e, e) for _ in sides])
         s0 = self.seed if seed is None else seed
+        if given is not None and all(given[1]):
+            return given_nll_result(method, n, dev)
+        planes = self._planes(given[0], B, T) if given is not None and any(given[2]) else None
         parts = [[] for _ in sides]
         for m, r in enumerate(self._rbms):
+            if given is not None and given[1][m]:
+                continue
+            codes = planes[m][idx].contiguous() if planes is not None and given[2][m] else None
             bh, bv = bh_t[m][idx].contiguous(), bv_t[m][idx].contiguous()
             tgt = cx["tgt"][m][idx].contiguous()
             F = torch.empty(n, device=dev)
             ops.rbm_free_energy(tgt, r.W, bh, bv, F)
             for side, part in zip(sides, parts):
-                part.append(rbm_nll_side(side, r, tgt, F, bh, bv, num_chains, num_betas, betas, s0 + m, ids))
+                part.append(rbm_nll_side(side, r, tgt, F, bh, bv, num_chains, num_betas, betas, s0 + m, ids, codes))
         return nll_result(method, [NllEstimate.total(p) for p in parts])
 
     def _backward_co(self):

@@ -454,24 +454,59 @@ class MultINNCore(Model):
         ls = [g.metrics["batch/loss"].reshape(()) for g in self._generators]
         return ls[0] if len(ls) == 1 else torch.stack(ls).mean()
 
-    def estimate_nll(self, x, lengths=None, **ais):
+    def estimate_nll(self, x, lengths=None, given_mask=None, **ais):
         """The JOINT NLL of every valid time step of x [B, T, P, M] given the steps before it, summed over this mode's generators (each
         models its part of the step given the past: the per-track generators of jamming / feedback, the one generator of joint mode):
         builds in eval mode and returns a generators.NllEstimate (per valid row in API order; `mean` per valid step).  RBM generators are
         estimated by AIS (ais: num_chains, num_betas, betas, seed -- a given seed s gives generator i the seed s + i; default: its own --
         and method: "ais" (default, biased low), "raise" (reverse AIS, biased the other way) or "both" -> a generators.NllBracket whose
         sides each sum over the generators), NADE generators are exact under every method.  Note: generator_loss() -- what fit validates on -- is the MEAN over the generators of their losses, this
-        is the SUM of their NLLs.  DBN encoders are refused: their generators model codes, not piano-roll cells."""
+        is the SUM of their NLLs.  DBN encoders are refused: their generators model codes, not piano-roll cells.
+        given_mask (optional, bool: [M] whole tracks, [P, M] pitch ranges, or the full [B, T, P, M]): the CONDITIONAL NLL of every step, row t
+        = -log p(x_t,free | x_t,given, x_<t) with the cells under the mask given (teacher-forced on all of x_<t), summed over the
+        generators -- what generate(given=, given_mask=) draws a step from.  Joint RBM: the one RBM over p M + m takes any mask (the
+        clamped estimators, DESIGN.md section 4 "Clamped AIS").  Per-track RBM generators (jamming, feedback, composer MultiRBM): the mask
+        is split per track, seeds as without it; a wholly given track adds exactly 0 and runs no chain -- these modes factorise over the
+        tracks of a step, so their conditional is the free tracks' marginal.  NADE generators are exact where every NADE is wholly given
+        or wholly free and refused (MnnUnsupported) otherwise; the joint NADE takes all or nothing.  The sum of the rows over t is NOT
+        -log p(x_free | x_given) of the sequence: later given cells say something about earlier free ones."""
         from .generators import nll_sides, total_nll, refuse_host_model
         method = ais.get("method", "ais")
         nll_sides(method)
         if self._encoder_type != "Pass":
             raise MnnUnsupported("estimate_nll through DBN encoders is not implemented: their generators' likelihood is over codes, not "
                                  "piano-roll cells")
+        split = None
+        if given_mask is not None:                                  # host checks and refusals, before any device work
+            if not torch.is_tensor(given_mask):
+                raise ValueError("given_mask must be a bool tensor ([M], [P, M] or [B, T, P, M])")
+            if not torch.is_tensor(x) or x.dim() != 4:
+                raise ValueError("estimate_nll(given_mask=) takes x [B, T, P, M]")
+            split = self._nll_given_split(*given_tracks(given_mask, tuple(x.shape)))
+            for g, (_, whole, some) in zip(self._generators, split):
+                g._refuse_nll_given(whole, some)
         refuse_host_model(self.device, "estimate_nll")
         self.build(x, lengths=lengths, is_train=False, mode="eval")
         seed = ais.pop("seed", None)
-        return total_nll(method, [g._nll_rows_built(seed=None if seed is None else seed + i, **ais) for i, g in enumerate(self._generators)])
+        given = [{}] * len(self._generators)
+        if split is not None:
+            codes = given_codes(self._x, given_mask, tuple(self._x.shape))
+            given = [dict(given=(take(codes), whole, some)) for take, whole, some in split]
+        return total_nll(method, [g._nll_rows_built(seed=None if seed is None else seed + i, **kw, **ais)
+                                  for i, (g, kw) in enumerate(zip(self._generators, given))])
+
+    def _nll_given_split(self, whole, some):
+        """The per-generator parts of a conditional-NLL mask (whole / some: common.given_tracks, per track of the mode): one
+        (codes [B, T, P, M] -> the generator's codes [B, T, features], its whole, its some) per generator.  One generator per track: the
+        track's plane.  One generator over all tracks: the step flattened p M + m -- with the mode's tracks where the generator has them
+        (composer), as one block where it has none (joint)."""
+        gens, M = self._generators, self.num_tracks
+        if len(gens) == M and M > 1:
+            return [(lambda c, i=i: c[..., i].contiguous(), [whole[i]], [some[i]]) for i in range(M)]
+        flat = lambda c: c.reshape(c.shape[0], c.shape[1], -1)
+        if getattr(gens[0], "num_tracks", 1) == M:
+            return [(flat, list(whole), list(some))]
+        return [(flat, [all(whole)], [any(some)])]
 
     def train_step(self, x, lengths, optimizer, lr=None):
         """build(x, lengths, is_train=True, mode='train') + train_generators(optimizer, lr): one optimiser step from a zero RNN state."""

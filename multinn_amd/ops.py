@@ -782,17 +782,23 @@ def _check_ladder(betas, what="rbm_ais"):
     _req(float(b[0]) == 0.0 and float(b[-1]) == 1.0, what + ": the ladder must start at 0 and end at 1")
 
 
-def _rbm_anneal(what, W, bh, bv, v, betas, num_chains, seed, row0, row_ids, log_z, log_w, v_out, stats):
-    """rbm_ais (v is None) and rbm_raise (v: the rows' data vectors): one set of checks, all before any allocation, and the call."""
+def _rbm_anneal(what, W, bh, bv, v, betas, num_chains, seed, row0, row_ids, log_z, log_w, v_out, stats, given=None):
+    """rbm_ais (v is None) and rbm_raise (v: the rows' data vectors): one set of checks, all before any allocation, and the call.
+    given (optional): the rows' codes -- the clamped estimators' entries; None reaches mnn_rbm_ais / mnn_rbm_raise themselves."""
     D, Hn = W.shape
     _req(W.dtype == torch.float32 and W.dim() == 2 and W.is_contiguous(), what + ": W f32 [D,Hn]")
     N = max(bh.shape[0], bv.shape[0], 0 if log_z is None else log_z.shape[0], 0 if row_ids is None else row_ids.numel(),
-            v.shape[0] if isinstance(v, torch.Tensor) and v.dim() == 2 else 0)
+            v.shape[0] if isinstance(v, torch.Tensor) and v.dim() == 2 else 0,
+            given.shape[0] if isinstance(given, torch.Tensor) and given.dim() == 2 else 0)
     _req(bh.dim() == 2 and bv.dim() == 2 and bh.shape[0] in (1, N) and bv.shape[0] in (1, N), what + ": bias rows must be 1 or N")
     _ldb(bh, Hn), _ldb(bv, D)
     if what == "rbm_raise":
         _req(isinstance(v, torch.Tensor) and v.dtype == torch.uint8 and tuple(v.shape) == (N, D) and v.is_contiguous(),
              what + ": v u8 [N, D] (one data vector per row)")
+    if given is not None:
+        _req(isinstance(given, torch.Tensor) and given.dtype == torch.uint8 and given.dim() == 2 and tuple(given.shape) == (N, D)
+             and given.stride(1) == 1 and (given.stride(0) >= D or N == 1),
+             what + ": given u8 [N, D] codes (0 / 1 clamp, 255 free), unit column stride, row stride ld_given >= D")
     S = int(num_chains)
     _req(S >= 1, what + ": num_chains >= 1")
     _check_ladder(betas, what)
@@ -801,7 +807,7 @@ def _rbm_anneal(what, W, bh, bv, v, betas, num_chains, seed, row0, row_ids, log_
     if row_ids is not None:
         _req(row_ids.dtype == torch.int32 and row_ids.numel() == N and row_ids.is_contiguous(), what + ": row_ids int32 [N]")
     dev = W.device
-    for t in (bh, bv, betas, row_ids, v):
+    for t in (bh, bv, betas, row_ids, v, given):
         _req(t is None or t.device == dev, what + ": every operand on W's device")
     for t, shape, dt, name in ((log_z, (N,), torch.float32, "log_z f32 [N]"), (log_w, (N, S), torch.float32, "log_w f32 [N, S]"),
                                (v_out, (N, S, D), torch.uint8, "v_out u8 [N, S, D]"), (stats, (N, 2), torch.float32, "stats f32 [N, 2]")):
@@ -813,19 +819,23 @@ def _rbm_anneal(what, W, bh, bv, v, betas, num_chains, seed, row0, row_ids, log_
     ws = torch.empty(_lib.load().mnn_rbm_ais_workspace_bytes(N, D, Hn, S, L), dtype=torch.uint8, device=dev)
     head = (_stream(), N, D, Hn, S, L, _ptr(betas), _ptr(W), _ptr(bh), _ldb(bh, Hn), _ptr(bv), _ldb(bv, D))
     tail = (int(seed), int(row0), _ptr(row_ids), _ptr(log_z), _ptr(log_w), _ptr(v_out), _ptr(stats), _ptr(ws))
+    clamp = () if given is None else (_ptr(given), given.stride(0) if N > 1 else D)
     if v is None:
-        call("mnn_rbm_ais", *head, *tail)
+        call("mnn_rbm_ais" if given is None else "mnn_rbm_ais_given", *head, *tail, *clamp)
     else:
-        call("mnn_rbm_raise", *head, _ptr(v), *tail)
+        call("mnn_rbm_raise" if given is None else "mnn_rbm_raise_given", *head, _ptr(v), *tail, *clamp)
     return log_z
 
 
-def rbm_ais(W, bh, bv, betas, num_chains, seed, row0=0, row_ids=None, log_z=None, log_w=None, v_out=None, stats=None):
+def rbm_ais(W, bh, bv, betas, num_chains, seed, row0=0, row_ids=None, log_z=None, log_w=None, v_out=None, stats=None, given=None):
     """Annealed importance sampling of log Z for each bias row (mnn_rbm_ais): N rows (the most of: bias rows, log_z, row_ids), bh and bv
     have 1 or N rows (one row: shared by all N, whose chains differ by their row ids).  betas: the
     ladder, f32 device [L] (0 = b_0 <= ... <= b_{L-1} = 1).  Returns log_z f32 [N] (allocated if not given); optional outputs: log_w f32
-    [N, S], v_out u8 [N, S, D] final chain states, stats f32 [N, 2] = (effective sample size, standard error of log_z).  log Z^ is biased low."""
-    return _rbm_anneal("rbm_ais", W, bh, bv, None, betas, num_chains, seed, row0, row_ids, log_z, log_w, v_out, stats)
+    [N, S], v_out u8 [N, S, D] final chain states, stats f32 [N, 2] = (effective sample size, standard error of log_z).  log Z^ is biased low.
+    given (optional; mnn_rbm_ais_given, DESIGN.md section 4 "Clamped AIS"): codes u8 [N, D] (row stride >= D) as rbm_gibbs takes them -- 0 / 1
+    clamp the visible, 255 leaves it free (common.given_codes).  log_z is then the log of the sum over the vectors that agree with the
+    clamped cells, so free_energy(v) + log_z = -log p(v_free | v_clamped); all codes 255 gives the bits of the call without `given`."""
+    return _rbm_anneal("rbm_ais", W, bh, bv, None, betas, num_chains, seed, row0, row_ids, log_z, log_w, v_out, stats, given)
 
 
 def rbm_raise(W, bh, bv, v, betas, num_chains, seed, row0=0, row_ids=None, log_z=None, log_w=None, v_out=None, stats=None):
@@ -834,6 +844,13 @@ def rbm_raise(W, bh, bv, v, betas, num_chains, seed, row0=0, row_ids=None, log_z
     log w_c - log S) is biased the other way from rbm_ais's: high in expectation over model-distributed data and, with a long enough
     ladder, an upper end to rbm_ais's lower one -- not a bound per row."""
     return _rbm_anneal("rbm_raise", W, bh, bv, v, betas, num_chains, seed, row0, row_ids, log_z, log_w, v_out, stats)
+
+
+def rbm_raise_given(W, bh, bv, v, given, betas, num_chains, seed, row0=0, row_ids=None, log_z=None, log_w=None, v_out=None, stats=None):
+    """rbm_raise with codes (mnn_rbm_raise_given; rbm_raise's own parameter list is fixed): given u8 [N, D] as rbm_ais takes them, or None =
+    rbm_raise.  The chains start from v with every clamped cell at its code and hold it there; log_z estimates rbm_ais(given=)'s clamped
+    log Z from the other side, with rbm_raise's statements about its bias and no more."""
+    return _rbm_anneal("rbm_raise", W, bh, bv, v, betas, num_chains, seed, row0, row_ids, log_z, log_w, v_out, stats, given)
 
 
 def rbm_hidden(v, W, bh, stream_id, seed, row0, sub, p_h=None, h=None):
