@@ -435,6 +435,7 @@ nade_bwd_kernel(int tracks, int N, int D, int HnT, int nslice, const uint8_t* __
     // rows that flip there), h = 1 / (1 + u): mul + add + rcp instead of sub + mul + exp + add + rcp.  The scan revisits the forward's
     // pre-activations in reverse, so u stays in f32 range and nothing needs `a` itself.
     constexpr bool useu = USEU;
+    constexpr bool SPARSE = HQ >= 2 && !USEU;      // d w_enc partials exchanged only where the wave flips (the exchange below)
     float a[BWD_R][HQ], h[BWD_R][HQ], c[BWD_R][HQ], G[BWD_R][HQ];
     // all a_D loads in flight together (unconditional, clamped row / hidden unit), masked afterwards: behind `valid ? load : 0` each load
     // waited for its own round trip (s_waitcnt vmcnt(0) per element at the start of every workgroup)
@@ -474,6 +475,9 @@ nade_bwd_kernel(int tracks, int N, int D, int HnT, int nslice, const uint8_t* __
     for (int g = 0; g < RG; ++g) {
         vcur[g] = fvalid[g] && icur < D && vm[(size_t)frr[g] * D + icur] != 0;
         dcur[g] = (fvalid[g] && icur < D) ? d_bias[(size_t)frr[g] * ld_bias + dl_off + icur] : 0.f;
+        // waited for HERE: left pending into the loop, this load puts a vmcnt wait in front of the first visible of EVERY chunk, where the only
+        // operations still in flight are the atomics of the chunk before
+        if constexpr (HQ >= 2) asm volatile("" : "+v"(dcur[g]));
     }
     __syncthreads();
     for (int cc = 0; cc < nch; ++cc) {
@@ -486,6 +490,8 @@ nade_bwd_kernel(int tracks, int N, int D, int HnT, int nslice, const uint8_t* __
         uint8_t vraw[RG];
         float draw[RG];
         unsigned long long mask[RG], many = 0ull;
+        int vnext[RG];
+        float dnext[RG];
         const int inc = max(inext, 0);
 #pragma unroll
         for (int g = 0; g < RG; ++g) {
@@ -504,12 +510,15 @@ nade_bwd_kernel(int tracks, int N, int D, int HnT, int nslice, const uint8_t* __
                 const int ii = half * 4 + k;
                 const int i = i0 + ii;
 #pragma unroll
-                for (int q = 0; q < HQ; ++q) { accd[k][q] = 0.f; acce[k][q] = 0.f; }
+                for (int q = 0; q < HQ; ++q) {
+                    accd[k][q] = 0.f;
+                    if constexpr (!SPARSE) acce[k][q] = 0.f;                    // (SPARSE: started where the wave flips, exchanged only then)
+                }
                 if (i >= D) continue;                                           // block-uniform (tail chunk)
                 float wev[HQ], wdv[HQ];
-                if constexpr (HQ >= 2) {                                        // lane-major staging: one 8/16-byte LDS load per matrix
-                    lv_load<HQ>(sd + ii * W + HQ * lane, wdv);
-                    lv_load<HQ>(se + ii * W + HQ * lane, wev);
+                if constexpr (HQ >= 2) {                                        // lane-major staging: one 8/16-byte LDS load per matrix;
+                    lv_load<HQ>(sd + ii * W + HQ * lane, wdv);                  // SPARSE: w_enc[i] is read under the flip branch, its only user
+                    if constexpr (!SPARSE) lv_load<HQ>(se + ii * W + HQ * lane, wev);
                 } else {
 #pragma unroll
                     for (int q = 0; q < HQ; ++q) {
@@ -520,6 +529,11 @@ nade_bwd_kernel(int tracks, int N, int D, int HnT, int nslice, const uint8_t* __
                 // the rows are independent: first the (rare) state changes of the rows with v_i = 1 -- skipped with ONE scalar test when
                 // none of the wave's 8 rows has one (4 visibles in 5 at rho = 0.03) --, then the FMAs of all 8 rows, straight-line
                 if ((many & (0x0101010101010101ull << ii)) != 0ull) {
+                    if constexpr (SPARSE) {
+                        lv_load<HQ>(se + ii * W + HQ * lane, wev);
+#pragma unroll
+                        for (int q = 0; q < HQ; ++q) acce[k][q] = 0.f;
+                    }
                     if constexpr (useu) {
                         float ewv[HQ];
 #pragma unroll
@@ -567,6 +581,22 @@ nade_bwd_kernel(int tracks, int N, int D, int HnT, int nslice, const uint8_t* __
             // and the only younger memory operations of this wave are none -- after the exchanges the wait for them would also sit
             // behind this chunk's f32 atomics.  The other buffer of wl was last read in the previous chunk (barrier at its end).
             if (half == 1) bwd_lstore<HQ>(st, wl[(cc + 1) & 1][0], wl[(cc + 1) & 1][1]);
+            // The next chunk's v byte and d nll / d logit are evaluated HERE (second half, in front of its exchange): behind the exchange the wait
+            // for them is a wait for vmcnt(0) -- the atomics the exchange has just issued are younger and conditional -- i.e. every wave drained
+            // its atomics at the end of every chunk, and only then issued the next chunk's loads.  Here the wait covers the first half's atomics
+            // at most, four visibles old; the empty asm keeps the evaluation (and its wait) in this place.  With the wait in front of the loop
+            // (dcur, above): 3.27 -> 3.10 ms at [1024,256,88,5] (profiles/nade_bwd_sparse_exchange.md).
+            if constexpr (HQ >= 2) {
+                if (half == 0) {
+#pragma unroll
+                    for (int g = 0; g < RG; ++g) {
+                        const bool ok = fvalid[g] && inext >= 0;
+                        vnext[g] = (ok && vraw[g] != 0) ? 1 : 0;
+                        dnext[g] = ok ? draw[g] : 0.f;
+                        asm volatile("" : "+v"(vnext[g]), "+v"(dnext[g]));
+                    }
+                }
+            }
             // one cross-wave exchange per 4 visibles (the per-visible barrier was 60 % of the wave time)
             float (*red)[4][2][W] = red_[(2 * cc + 1 - half) & (NRED - 1)];
             if (NRED == 1) __syncthreads();              // the previous exchange has been read
@@ -574,26 +604,57 @@ nade_bwd_kernel(int tracks, int N, int D, int HnT, int nslice, const uint8_t* __
                 // exchange slots are LANE-major (the four hidden units lane, lane+64, lane+128, lane+192 of a lane side by side): one
                 // 16-byte LDS store per (visible, matrix) instead of four 4-byte ones, and the summing thread -- one per (visible,
                 // matrix, lane) -- reads 8 x 16 bytes instead of 32 x 4; its four atomics each still cover 256 contiguous bytes per wave
+                // The d w_enc partial of a (wave, visible) is EXACTLY zero unless one of the wave's 8 rows flips there (4 pairs in 5 at
+                // rho = 0.03), so it is exchanged only then: fm = the visibles of this half-chunk at which the wave flips (wave-uniform, from
+                // `many`), left as a flag word per wave next to the partials; the summing wave of (visible, d w_enc) adds the flagged waves'
+                // partials, in the same ascending order, and sends no atomics when there are none.  The skipped terms are +0: the sums keep
+                // their bits.  The flag words live in the d w_enc slot of (wave 1, visible 0) -- the LDS is full (80 KB: two workgroups per
+                // CU) --: wave 1 is the summing wave of that very pair and takes its own partial from its registers.  Worth 0.03 ms of the
+                // 3.10 (the exchange is not what the kernel waits for); splitting the d w_dec sum of a visible over two waves lost, 3.41 ms.
+                // The multiplicative instantiation runs on dense batches, where every flag would be set: it exchanges unconditionally (!SPARSE).
+                unsigned long long fm64 = many >> (half * 4);
+                fm64 |= fm64 >> 32; fm64 |= fm64 >> 16; fm64 |= fm64 >> 8;
+                const int fm = SPARSE ? (int)fm64 & 15 : 15;
+                float* encf = &red[1][0][1][0];
+                if (SPARSE && lane == 0) encf[w] = __int_as_float(fm);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     lv_store<HQ>(&red[w][k][0][HQ * lane], accd[k]);
-                    lv_store<HQ>(&red[w][k][1][HQ * lane], acce[k]);
+                    if (((fm >> k) & 1) != 0 && !(SPARSE && k == 0 && w == 1)) lv_store<HQ>(&red[w][k][1][HQ * lane], acce[k]);
                 }
                 __syncthreads();
                 {
-                    const int k = threadIdx.x >> 7, which = (threadIdx.x >> 6) & 1;       // 4 visibles x 2 matrices x 64 lanes = 512 threads
+                    const int k = w >> 1, which = w & 1;                                   // 4 visibles x 2 matrices x 64 lanes = 512 threads
                     const int i = i0 + half * 4 + k;
                     float sum[HQ];
 #pragma unroll
                     for (int q = 0; q < HQ; ++q) sum[q] = 0.f;
+                    unsigned from = 0xffu;                                                 // the waves whose partial is added (d w_dec: all)
+                    if (SPARSE && which == 1) from = (unsigned)__ballot(((__float_as_int(encf[lane & 7]) >> k) & 1) != 0) & 0xffu;
+                    if (!SPARSE || which == 0) {
 #pragma unroll
-                    for (int ww = 0; ww < 8; ++ww) {
-                        float pq[HQ];
-                        lv_load<HQ>(&red[ww][k][which][HQ * lane], pq);
+                        for (int ww = 0; ww < 8; ++ww) {
+                            float pq[HQ];
+                            lv_load<HQ>(&red[ww][k][which][HQ * lane], pq);
 #pragma unroll
-                        for (int q = 0; q < HQ; ++q) sum[q] += pq[q];
+                            for (int q = 0; q < HQ; ++q) sum[q] += pq[q];
+                        }
+                    } else if (from != 0u) {
+#pragma unroll
+                        for (int ww = 0; ww < 8; ++ww) {
+                            if (((from >> ww) & 1u) == 0u) continue;
+                            float pq[HQ];
+                            if (ww == 1 && k == 0) {
+#pragma unroll
+                                for (int q = 0; q < HQ; ++q) pq[q] = acce[0][q];
+                            } else {
+                                lv_load<HQ>(&red[ww][k][1][HQ * lane], pq);
+                            }
+#pragma unroll
+                            for (int q = 0; q < HQ; ++q) sum[q] += pq[q];
+                        }
                     }
-                    if (i < D) {
+                    if (i < D && from != 0u) {
                         // one f32 atomic per (visible, hidden unit) and 64-row workgroup, 256 contiguous bytes per wave.  (Per-workgroup slabs
                         // + a reduction pass instead -- bit-reproducible sums -- were measured slower, 5.1 vs 4.0 ms at [1024,256,88,5], and
                         // removed in round 4: the atomics ride under the scan's VALU work, the slab stores and their 3.7 GB read-back do not.)
@@ -630,9 +691,14 @@ nade_bwd_kernel(int tracks, int N, int D, int HnT, int nslice, const uint8_t* __
         }
 #pragma unroll
         for (int g = 0; g < RG; ++g) {
-            const bool ok = fvalid[g] && inext >= 0;
-            vcur[g] = ok && vraw[g] != 0;
-            dcur[g] = ok ? draw[g] : 0.f;
+            if constexpr (HQ >= 2) {
+                vcur[g] = vnext[g] != 0;
+                dcur[g] = dnext[g];
+            } else {
+                const bool ok = fvalid[g] && inext >= 0;
+                vcur[g] = ok && vraw[g] != 0;
+                dcur[g] = ok ? draw[g] : 0.f;
+            }
         }
         if (NRED == 1) __syncthreads();
     }
