@@ -310,6 +310,20 @@ class RnnEstimator(Generator):
         (log_probs, cond_probs, free_energy, cost, _outputs, ...) of the next replay index its rows by ITS lengths."""
         self._flat_idx = None
 
+    def _idx(self):
+        """Positions of the API-order rows (b-major, then t: sequences.py:30-31) in the arrays the kernels wrote: time-major rows, or -- for a
+        compacted ragged window -- compact rows (through the window's inverse permutation)."""
+        if self._flat_idx is None:
+            fi = flat_index(self._lengths, self._ctx["B"], self._ctx["T"], self._loss.device)
+            cp = self._ctx.get("compact")
+            self._flat_idx = cp["inv"].long()[fi] if cp is not None else fi
+        return self._flat_idx
+
+    def _row_ids(self, B, T, device):
+        """Global ids (int64, t * 65536 + row0 + b) of the time-major rows of a [B, T] window: they key the Gibbs / AIS uniforms of a row, so
+        the draws do not depend on the data-parallel split."""
+        return (torch.arange(T, device=device)[:, None] * 65536 + (self.row0 + torch.arange(B, device=device))[None, :]).reshape(-1)
+
     def _row_weight(self, lengths, B, T, device):
         """1/N_valid on valid rows (N_valid summed over ALL ranks), 0 on padding.  Leaves the host copy of N_valid in self._n_valid (the
         f16 loss scale is derived from it)."""
@@ -803,16 +817,7 @@ class RnnNade(RnnEstimator):
         self._metrics = {"batch/loss": loss, "log_likelihood": loss}
         self._metrics_upd = []
 
-    # -- API-order views of the flat outputs (b-major then t, sequences.py:30-31) ---------------
-    def _idx(self):
-        """Positions of the API-order rows (b-major, then t: sequences.py:30-31) in the arrays the kernels wrote: time-major rows, or -- for a
-        compacted ragged window -- compact rows (through the window's inverse permutation)."""
-        if self._flat_idx is None:
-            fi = flat_index(self._lengths, self._ctx["B"], self._ctx["T"], self._loss.device)
-            cp = self._ctx.get("compact")
-            self._flat_idx = cp["inv"].long()[fi] if cp is not None else fi
-        return self._flat_idx
-
+    # -- API-order views of the flat outputs (b-major then t, sequences.py:30-31; RnnEstimator._idx) ---------------
     @property
     def log_probs(self):
         r = [self._nll_tm[m][self._idx()] for m in range(self.num_tracks)]
@@ -1108,40 +1113,74 @@ class RnnRBM(RnnEstimator):
     Reference defects R1-R4 are resolved as recorded there: k = rbm.k in
     sample_single, lengths forwarded to _get_state, per-row free energy, and
     ``bias_mode='conditional'`` (Boulanger-Lewandowski) as the trained loss; 'internal'
-    reproduces the as-written metric."""
+    reproduces the as-written metric.
+
+    The step is written over the track list ``self._rbms`` (M = len; here M = 1, as RnnNade is over ``self._nades``): the Dense output of a
+    row is [bh_0 .. bh_{M-1} | bv_0 .. bv_{M-1}], the chains' inputs, targets and outputs carry a leading track axis [M, N, .].
+    RnnMultiRBM is the same code with M tracks; what it overrides is the launch form (_step_chains, _free_energies: this class calls the
+    single-job entries, never a one-job grouped launch), the presentation of per-track values (_present: tensors here, lists there), the
+    variable prefix, and the sampling step."""
 
     def __init__(self, num_dims, num_hidden, num_hidden_rnn, keep_prob=1.0, internal_bias=True, k=10, name="rnn-rbm", track_name="all",
                  bias_mode="conditional", **kw):
         self._k = k
         self.bias_mode = bias_mode
+        self._tracks = getattr(self, "_tracks", ["all"])
         super().__init__(num_dims, num_hidden, num_hidden_rnn, keep_prob, internal_bias, name, track_name, **kw)
-        self._num_output = self.num_dims
+        self._num_output = self.num_tracks * self.num_dims
 
     k = property(lambda self: self._k)
+    tracks = property(lambda self: self._tracks)
+    num_tracks = property(lambda self: len(self._tracks))
 
+    # -- what RnnMultiRBM overrides -------------------------------------------------------------
+    def _rbm_prefix(self, m):
+        return "rbm"
+
+    def _present(self, per_track):
+        """A per-track list as the API returns it: the one track's value itself."""
+        return per_track[0]
+
+    def _step_chains(self, v0, bh, bv, rows, p_v, v_s):
+        """The CD-k chains of a built step, track m from v0[m] with seed + m.  seed + step, the step read on the device (store.step_dev ==
+        store.step here): the same draws as passing seed + store.step, and a captured step (graphed_build_train) draws anew at every replay."""
+        ops.rbm_gibbs(v0[0], self._rbm.W, bh[0], bv[0], self._k, self.seed, 0, rows, 0, p_v[0], v_s[0], seed_step=self.store.step_dev)
+
+    def _free_energies(self, v, bh, bv, F, p_h):
+        """F[m] = F_m(v[m]) of every track's rows; p_h (optional): sigmoid(z) of the same pass."""
+        ops.rbm_free_energy(v[0], self._rbm.W, bh[0], bv[0], F[0], p_h=None if p_h is None else p_h[0])
+
+    # -- construction ---------------------------------------------------------------------------
     def _init_estimator(self):
-        self._rbm = RBM(self.num_dims, self.num_hidden[-1], k=self._k)
+        self._rbms = [RBM(self.num_dims, self.num_hidden[-1], k=self._k, name=self._rbm_prefix(m)) for m in range(self.num_tracks)]
+        self._rbm = self._rbms[0]
 
     def _declare(self, num_inputs):
-        """Variable order rbm [W,bv,bh], rnn, [Wuh, Wuv] (rnn_rbm.py:135-138)."""
-        D, Hn, R = self.num_dims, self.num_hidden[-1], self.num_hidden_rnn[-1]
-        self._rbm.declare(self.store, self._gen)
+        """Variable order rbm(s) [W, bv, bh], rnn, [Wuh, Wuv] (rnn_rbm.py:135-138); the columns of Wuh / Wuv are track-major."""
+        M, D, Hn, R = self.num_tracks, self.num_dims, self.num_hidden[-1], self.num_hidden_rnn[-1]
+        for m, r in enumerate(self._rbms):
+            r.declare(self.store, self._gen, prefix=self._rbm_prefix(m))
         self._rnn.declare(self.store, num_inputs, self._gen)
-        self.store.declare("Wuh", (R, Hn), glorot_uniform(self._gen, R, Hn))
-        self.store.declare("Wuv", (R, D), glorot_uniform(self._gen, R, D))
-        self.n_out = Hn + D
+        self.store.declare("Wuh", (R, M * Hn), glorot_uniform(self._gen, R, M * Hn))
+        self.store.declare("Wuv", (R, M * D), glorot_uniform(self._gen, R, M * D))
+        self.n_out = M * (Hn + D)
         self.ldo = ops.round_up(self.n_out, 64)
+
+    def _internal_biases(self):
+        """[bh_0 .. bh_{M-1}] and [bv_0 .. bv_{M-1}] as two flat vectors, in the Dense output's column order (one track: views of its own)."""
+        if len(self._rbms) == 1:
+            return self._rbm.bh.view(-1), self._rbm.bv.view(-1)
+        return torch.cat([r.bh.view(-1) for r in self._rbms]), torch.cat([r.bv.view(-1) for r in self._rbms])
 
     def _pack_estimator(self):
         dev = self.store.theta.device
-        R, Hn, D = self.num_hidden_rnn[-1], self.num_hidden[-1], self.num_dims
-        wu = torch.cat([self.store["Wuh"], self.store["Wuv"]], 1).contiguous()          # [R, Hn+D]
+        R = self.num_hidden_rnn[-1]
+        wu = torch.cat([self.store["Wuh"], self.store["Wuv"]], 1).contiguous()          # [R, M Hn + M D]
         self._wu_t = torch.empty((self.n_out, R), device=dev, dtype=self.dtype)
         ops.transpose(wu, self._wu_t)
         self._wu_p = torch.zeros((R, self.ldo), device=dev, dtype=self.dtype)
         ops.convert2d(wu, self._wu_p[:, :self.n_out])
-        self._bias_cat = torch.cat([self._rbm.bh.view(-1), self._rbm.bv.view(-1)]).contiguous() if self.internal_bias \
-            else torch.zeros(self.n_out, device=dev)
+        self._bias_cat = torch.cat(self._internal_biases()).contiguous() if self.internal_bias else torch.zeros(self.n_out, device=dev)
 
     def _biases(self, h):
         """rnn_rbm.py:240-259: bh_t = rbm.bh + o.Wuh ; bv_t = rbm.bv + o.Wuv as ONE GEMM."""
@@ -1151,122 +1190,147 @@ class RnnRBM(RnnEstimator):
         ops.gemm_tn(h, self._wu_t, out[:, :self.n_out], bias=self._bias_cat)
         return out
 
+    def _split(self, out):
+        """The per-track bias blocks of a Dense output [N, ld]: views, one leading dimension."""
+        M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
+        return ([out[:, m * Hn:(m + 1) * Hn] for m in range(M)], [out[:, M * Hn + m * D:M * Hn + (m + 1) * D] for m in range(M)])
+
+    def _planes(self, x, B, T):
+        """[B, T, D * M] composer layout (feature d * M + m) -> u8 [M, T * B, D]: every track's rows as a contiguous time-major plane."""
+        M, D = self.num_tracks, self.num_dims
+        return x[:, :, :D * M].to(torch.uint8).reshape(B, T, D, M).permute(3, 1, 0, 2).contiguous().view(M, T * B, D)
+
+    # -- forward --------------------------------------------------------------------------------
     def build(self, x=None, y=None, lengths=None, is_train=None, mode="eval"):
         """rnn_rbm.py:71-143."""
         return drive(self._build_co(x, y, lengths, is_train, mode))
 
     def _build_co(self, x=None, y=None, lengths=None, is_train=None, mode="eval"):
-        """`build` as a generator function (drive / drive_group: the LSTM recurrences are yielded to the driver)."""
+        """`build` as a generator function (drive / drive_group: the LSTM recurrences are yielded to the driver).  Track m runs a CD-k chain
+        from its slice of the inputs (rnn_rbm.py:112), cost_m = F_m(target_m) - F_m(v_s,m); the loss, `free_energy` and `log_likelihood` are
+        the MEAN over the tracks of the row-weighted values (rnn_multinade.py:199-203)."""
         Generator.build(self, x, y, lengths, is_train, mode)
         self._materialize(x.shape[-1] if x is not None else self._num_inputs)
         self._rnn.build_cell(is_train)
         if mode in ("train", "eval"):
             B, T, _ = x.shape
-            D, Hn = self.num_dims, self.num_hidden[-1]
-            N, dev = B * T, x.device
+            M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
+            N, dev, train = B * T, x.device, mode == "train"
             self._ensure_packed()
             x_tm = self._to_time_major_inputs(x)
-            v0 = x.to(torch.uint8).transpose(0, 1).contiguous().view(N, -1)       # chain starts from inputs_flat (rnn_rbm.py:112)
-            tgt = y.to(torch.uint8).transpose(0, 1).contiguous().view(N, D)
+            v0, tgt = self._planes(x, B, T), self._planes(y, B, T)
             rw = self._row_weight(lengths, B, T, dev)
             kp = self._rnn.effective_keep_prob()
             seed = self.seed + self.store.step
-            yy, ctx, _ = yield from self._stack.forward_co(x_tm, kp, self.seed, self.row0, save=(mode == "train"), state0=self._state0(B),
-                                                           step_dev=self.store.step_dev, state_grad=(mode == "train"))
+            yy, ctx, _ = yield from self._stack.forward_co(x_tm, kp, self.seed, self.row0, save=train, state0=self._state0(B),
+                                                           step_dev=self.store.step_dev, state_grad=train)
             out = self._biases(yy.view(N, -1))
-            bh_t, bv_t = out[:, :Hn], out[:, Hn:Hn + D]
-            # global flat row ids keep the Gibbs uniforms independent of the data-parallel split
-            rows = (torch.arange(T, device=dev)[:, None] * 65536 + (self.row0 + torch.arange(B, device=dev))[None, :]).reshape(-1).int()
-            p_v = torch.empty((N, D), device=dev)
-            v_s = torch.empty((N, D), device=dev, dtype=torch.uint8)
-            # seed + step, the step read on the device (store.step_dev == store.step here): the same draws as passing seed + store.step,
-            # and a captured step (graphed_build_train) draws anew at every replay
-            ops.rbm_gibbs(v0[:, :D].contiguous(), self._rbm.W, bh_t, bv_t, self._k, self.seed, 0, rows, 0, p_v, v_s, seed_step=self.store.step_dev)
+            bh_t, bv_t = self._split(out)
+            p_v = torch.empty((M, N, D), device=dev)
+            v_s = torch.empty((M, N, D), device=dev, dtype=torch.uint8)
+            self._step_chains(v0, bh_t, bv_t, self._row_ids(B, T, dev).int(), p_v, v_s)
             if self.bias_mode == "conditional":
                 bh_u, bv_u = bh_t, bv_t
             else:
-                bh_u, bv_u = self._rbm.bh, self._rbm.bv
-            Fv = torch.empty(N, device=dev); Fs = torch.empty(N, device=dev)
+                bh_u, bv_u = [r.bh for r in self._rbms], [r.bv for r in self._rbms]
+            Fv = torch.empty((M, N), device=dev); Fs = torch.empty((M, N), device=dev)
             # train mode: the same pass leaves sigmoid(z) of both chains' ends, the hidden activations of the free-energy gradient (backward)
-            sv = torch.empty((N, Hn), device=dev) if mode == "train" else None
-            ss = torch.empty((N, Hn), device=dev) if mode == "train" else None
-            ops.rbm_free_energy(tgt, self._rbm.W, bh_u, bv_u, Fv, p_h=sv)
-            ops.rbm_free_energy(v_s, self._rbm.W, bh_u, bv_u, Fs, p_h=ss)
+            sv = torch.empty((M, N, Hn), device=dev) if train else None
+            ss = torch.empty((M, N, Hn), device=dev) if train else None
+            self._free_energies(tgt, bh_u, bv_u, Fv, sv)
+            self._free_energies(v_s, bh_u, bv_u, Fs, ss)
             cost = Fv - Fs
+            rwm = rw if M == 1 else (rw / M).repeat(M)                                   # mean over the tracks of the row-weighted sums
             loss = torch.zeros(1, device=dev)
-            ops.weighted_sum(cost, rw, loss)
-            self._ctx = dict(y=yy, lstm=ctx, out=out, tgt=tgt, v_s=v_s, rw=rw, kp=kp, seed=seed, B=B, T=T, bh_u=bh_u, bv_u=bv_u,
-                             n_valid=self._n_valid, ls_dev=self._ls_dev if self._n_valid is None else None, sv=sv, ss=ss)
+            ops.weighted_sum(cost.view(-1), rwm, loss)
+            self._ctx = dict(y=yy, lstm=ctx, out=out, tgt=tgt, v_s=v_s, rw=rw, kp=kp, seed=seed, B=B, T=T, n_valid=self._n_valid,
+                             ls_dev=self._ls_dev if self._n_valid is None else None, sv=sv, ss=ss)
             self._cost_tm, self._F_tm, self._pv_tm, self._vs_tm, self._loss = cost, Fv, p_v, v_s, loss
             self._lengths, self._flat_idx = lengths, None
-            self._recon_tm = torch.empty(N, device=dev)
-            ops.log_loss_rows(tgt, p_v, self._recon_tm)                                                       # rbm.py:124-129
+            self._recon_tm = torch.empty((M, N), device=dev)
+            ops.log_loss_rows(tgt.view(M * N, D), p_v.view(M * N, D), self._recon_tm.view(-1))               # rbm.py:124-129
             fe, ll = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
-            ops.weighted_sum(Fv, rw, fe)
-            ops.weighted_sum(self._recon_tm, rw, ll)
+            ops.weighted_sum(Fv.view(-1), rwm, fe)
+            ops.weighted_sum(self._recon_tm.view(-1), rwm, ll)
             self._metrics = {"batch/loss": loss, "free_energy": fe, "log_likelihood": ll}
             self._metrics_upd = []
         self._is_built = True
 
-    def _idx(self):
-        """Positions of the API-order rows (b-major, then t: sequences.py:30-31) in the arrays the kernels wrote: time-major rows, or -- for a
-        compacted ragged window -- compact rows (through the window's inverse permutation)."""
-        if self._flat_idx is None:
-            fi = flat_index(self._lengths, self._ctx["B"], self._ctx["T"], self._loss.device)
-            cp = self._ctx.get("compact")
-            self._flat_idx = cp["inv"].long()[fi] if cp is not None else fi
-        return self._flat_idx
+    def _per_track(self, t, cast=None):
+        idx = self._idx()
+        return self._present([t[m][idx] if cast is None else t[m][idx].to(cast) for m in range(self.num_tracks)])
 
-    cond_probs = property(lambda self: self._pv_tm[self._idx()])
-    _outputs = property(lambda self: self._vs_tm[self._idx()].float())
-    free_energy = property(lambda self: self._F_tm[self._idx()])
-    cost = property(lambda self: self._cost_tm[self._idx()])
-    reconstruction_cost = property(lambda self: self._recon_tm[self._idx()])
+    cond_probs = property(lambda self: self._per_track(self._pv_tm))
+    _outputs = property(lambda self: self._per_track(self._vs_tm, torch.float32))
+    free_energy = property(lambda self: self._per_track(self._F_tm))
+    cost = property(lambda self: self._per_track(self._cost_tm))
+    reconstruction_cost = property(lambda self: self._per_track(self._recon_tm))
 
     def build_metrics(self, targets, predictions, cond_probs=None, log_probs=None):
         return self._rbm.build_metrics(targets, predictions, cond_probs, log_probs)
 
     def _nll_rows_built(self, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais", given=None):
-        """AIS NLL of the last build's valid rows (API order):  -log p(v_t | v_<t) = F_t(v_t) + log Z_t with the row's CONDITIONAL biases
-        bh_t, bv_t (the distribution sample() draws from, whatever bias_mode trained) and log Z_t estimated by RBM.log_partition -- the
-        chains keyed by the global row ids of build (t * 65536 + row0 + b), seed default self.seed.  Biased low: see NllEstimate.
-        method "raise": log Z_t by RBM.log_partition_reverse from the row's target v_t (biased the other way); "both": the NllBracket.
-        given (optional): (codes u8 [B, T, D] -- the targets at the given cells, 255 at the free ones: common.given_codes --, whole, some:
-        one-element lists, whether every / any cell is given: common.given_tracks) -> the conditional rows -log p(v_t,free | v_t,given,
-        v_<t) = F_t(v_t) + log Z_t,c, the stationary distribution of the clamped chain generate(given=) runs at that step.  Every cell
-        given: exactly 0 and no chain; no cell given: the call without `given`."""
+        """AIS NLL of the last build's valid rows (API order): the SUM over the tracks (independent given the history) of
+        -log p(v_t | v_<t) = F_t(v_t) + log Z_t with the row's CONDITIONAL biases bh_t, bv_t (the distribution sample() draws from, whatever
+        bias_mode trained) and log Z_t estimated by RBM.log_partition -- the chains keyed by the global row ids of build (_row_ids), track m
+        with seed + m, seed default self.seed.  Biased low: see NllEstimate.  method "raise": log Z_t by RBM.log_partition_reverse from the
+        row's target v_t (biased the other way); "both": the NllBracket, each side summed over the tracks.
+        given (optional): (codes u8 [B, T, D * M] in the inputs' layout -- the targets at the given cells, 255 at the free ones:
+        common.given_codes --, whole, some: per track, whether every / any cell is given: common.given_tracks) -> the conditional rows
+        -log p(v_t,free | v_t,given, v_<t) = F_t(v_t) + log Z_t,c, the stationary distribution of the clamped chain generate(given=) runs at
+        that step.  A wholly given track adds exactly 0 and runs no chain; a track with no given cell is estimated as without `given`."""
         sides = nll_sides(method)
         cx = self._ctx
         B, T = cx["B"], cx["T"]
-        D, Hn = self.num_dims, self.num_hidden[-1]
-        out, dev = cx["out"], cx["out"].device
+        bh_t, bv_t = self._split(cx["out"])
+        dev = cx["out"].device
         idx = self._idx()
-        if given is not None and given[1][0]:
-            return given_nll_result(method, idx.numel(), dev)
-        rows = (torch.arange(T, device=dev)[:, None] * 65536 + (self.row0 + torch.arange(B, device=dev))[None, :]).reshape(-1)
-        bh = out[:, :Hn][idx].contiguous()
-        bv = out[:, Hn:Hn + D][idx].contiguous()
-        n = bh.shape[0]
+        n = idx.numel()
+        if given is not None and all(given[1]):
+            return given_nll_result(method, n, dev)
         if n == 0:
             e = torch.zeros(0, device=dev)
             return nll_result(method, [NllEstimate(e, e, e, e, e) for _ in sides])
-        ids = rows[idx].to(torch.int32).contiguous()
-        tgt = cx["tgt"][idx].contiguous()
-        F = torch.empty(n, device=dev)
-        ops.rbm_free_energy(tgt, self._rbm.W, bh, bv, F)
+        ids = self._row_ids(B, T, dev)[idx].to(torch.int32).contiguous()
         s0 = self.seed if seed is None else seed
-        codes = None
-        if given is not None and given[2][0]:
-            codes = given[0].transpose(0, 1).reshape(T * B, D)[idx].contiguous()              # time-major rows, then the targets' row order
-        return nll_result(method, [rbm_nll_side(side, self._rbm, tgt, F, bh, bv, num_chains, num_betas, betas, s0, ids, codes) for side in sides])
+        planes = self._planes(given[0], B, T) if given is not None and any(given[2]) else None
+        parts = [[] for _ in sides]
+        for m, r in enumerate(self._rbms):
+            if given is not None and given[1][m]:
+                continue
+            codes = planes[m][idx].contiguous() if planes is not None and given[2][m] else None
+            bh, bv = bh_t[m][idx].contiguous(), bv_t[m][idx].contiguous()
+            tgt = cx["tgt"][m][idx].contiguous()
+            F = torch.empty(n, device=dev)
+            ops.rbm_free_energy(tgt, r.W, bh, bv, F)
+            for side, part in zip(sides, parts):
+                part.append(rbm_nll_side(side, r, tgt, F, bh, bv, num_chains, num_betas, betas, s0 + m, ids, codes))
+        return nll_result(method, [NllEstimate.total(p) for p in parts])             # (one part: total returns the part itself)
 
-
+    # -- backward -------------------------------------------------------------------------------
     def backward(self):
         return drive(self._backward_co())
 
+    def _grad_seed(self, cx):
+        """(row weights, scale, ls) of a built step's gradient rows: rbm_cd_rows weighs row n by rw[n] * scale -- the mode's weight of this
+        generator's loss, the 1 / M of the mean over the tracks and the f16 loss scale (static x the dynamic multiplier of ParamStore.ls_dyn)
+        -- and _unscale(ls) takes the loss scale out again."""
+        M = self.num_tracks
+        dyn = self.store.ls_dyn if self.dtype == torch.float16 else None
+        gs = self.grad_scale / M if M > 1 else self.grad_scale
+        if cx["n_valid"] is None:                    # ragged_on_device: the scale is a device scalar (folded into the row weights); _unscale gets its inverse
+            lsd = cx.get("ls_dev")
+            if lsd is not None and dyn is not None:
+                lsd = lsd * dyn[0:1]
+            return (cx["rw"] if lsd is None else cx["rw"] * lsd), gs, (1.0 if lsd is None else 1.0 / lsd)
+        ls = self._stack.loss_scale(cx["n_valid"])
+        if dyn is not None:
+            return cx["rw"] * dyn[0:1], gs * ls, dyn[1:2] * (1.0 / ls)
+        return cx["rw"], gs * ls, ls
+
     def _backward_co(self):
         cx = self._ctx
-        D, Hn, R = self.num_dims, self.num_hidden[-1], self.num_hidden_rnn[-1]
+        M, D, Hn, R = self.num_tracks, self.num_dims, self.num_hidden[-1], self.num_hidden_rnn[-1]
         B, T = cx["B"], cx["T"]
         N, dev = B * T, cx["out"].device
         g = self.store.gviews
@@ -1274,24 +1338,14 @@ class RnnRBM(RnnEstimator):
         sv, ss = cx.get("sv"), cx.get("ss")           # sigmoid(z(v)), sigmoid(z(v_s)): left by the forward's free-energy passes
         if sv is None:
             raise RuntimeError("build(..., mode='train') must run before train()")
-        # dF/dbh = -sigmoid(z), dF/dbv = -v, dF/dW = -v^T sigmoid(z); cost = F(v) - F(v_s), v_s constant (rbm.py:229).  One pass writes the
-        # Dense-output-shaped gradient block and the two scaled hidden blocks of d cost / d W = v_s^T (w ss) - v^T (w sv)
-        d_out = torch.empty((N, self.ldo), device=dev)
-        pos = torch.empty((N, Hn), device=dev); neg = torch.empty((N, Hn), device=dev)
-        dyn = self.store.ls_dyn if self.dtype == torch.float16 else None          # the dynamic multiplier of the f16 loss scale (ParamStore.ls_dyn)
-        if cx["n_valid"] is None:                    # ragged_on_device: the scale is a device scalar (folded into the row weights); _unscale gets its inverse
-            lsd = cx.get("ls_dev")
-            if lsd is not None and dyn is not None:
-                lsd = lsd * dyn[0:1]
-            ops.rbm_cd_rows(cx["tgt"], cx["v_s"], sv, ss, cx["rw"] if lsd is None else cx["rw"] * lsd, self.grad_scale, d_out, pos, neg)
-            ls = 1.0 if lsd is None else 1.0 / lsd
-        else:
-            ls = self._stack.loss_scale(cx["n_valid"])
-            if dyn is not None:
-                ops.rbm_cd_rows(cx["tgt"], cx["v_s"], sv, ss, cx["rw"] * dyn[0:1], self.grad_scale * ls, d_out, pos, neg)
-                ls = dyn[1:2] * (1.0 / ls)
-            else:
-                ops.rbm_cd_rows(cx["tgt"], cx["v_s"], sv, ss, cx["rw"], self.grad_scale * ls, d_out, pos, neg)
+        rw, scale, ls = self._grad_seed(cx)
+        # dF/dbh = -sigmoid(z), dF/dbv = -v, dF/dW = -v^T sigmoid(z); cost = F(v) - F(v_s), v_s constant (rbm.py:229).  Per track one pass writes
+        # the rows of its gradient block [Hn | D] and the two scaled hidden blocks of d cost / d W = v_s^T (w ss) - v^T (w sv).  One track: the
+        # block is the Dense-shaped d_out's own leading columns, written in place (padding zeroed by the pass); M tracks: a track's two column
+        # blocks are not adjacent in d_out, so the rows are staged in d_m and copied into them
+        d_out = (torch.empty if M == 1 else torch.zeros)((N, self.ldo), device=dev)
+        d_m = d_out if M == 1 else torch.empty((N, Hn + D), device=dev)
+        pos = torch.empty((M, N, Hn), device=dev); neg = torch.empty((M, N, Hn), device=dev)
         # d cost / d W = v_s^T pos + v^T neg, [D, N] . [N, Hn] with K = N rows.  16-bit modes: the operands in the compute type (v, v_s are 0 / 1:
         # exact; pos / neg are loss-scaled products of a weight and a sigmoid) on the LDS-DMA GEMM -- as f32 products on v_mfma_f32_32x32x2_f32
         # (1/16 of the 16-bit rate) the two GEMMs were 0.53 ms per track of the 3.6 ms jamming step (round 4 profile); fp32 mode keeps f32.
@@ -1303,12 +1357,20 @@ class RnnRBM(RnnEstimator):
         # two output tiles and K = N rows -- without split-K two workgroups walk the whole batch (6.7 ms of a 19.6 ms step at N = 32 768);
         # slices of >= 256 rows, up to one workgroup per CU
         sk = int(max(1, min(256 // (-(-D // 128) * -(-Hn // 128)), Np // 256)))
-        gW = g[f"{self._rbm.prefix}/W"]
-        ops.gemm_tn(tr(cx["v_s"], D), tr(pos, Hn), gW, accumulate=True, split_k=sk)
-        ops.gemm_tn(tr(cx["tgt"], D), tr(neg, Hn), gW, accumulate=True, split_k=sk)
+        dbh, dbv = self._split(d_out)
+        for m, r in enumerate(self._rbms):
+            ops.rbm_cd_rows(cx["tgt"][m], cx["v_s"][m], sv[m], ss[m], rw, scale, d_m, pos[m], neg[m])
+            if M > 1:
+                dbh[m].copy_(d_m[:, :Hn]); dbv[m].copy_(d_m[:, Hn:])
+            gW = g[f"{r.prefix}/W"]
+            ops.gemm_tn(tr(cx["v_s"][m], D), tr(pos[m], Hn), gW, accumulate=True, split_k=sk)
+            ops.gemm_tn(tr(cx["tgt"][m], D), tr(neg[m], Hn), gW, accumulate=True, split_k=sk)
+        def bias_grads(col):                             # col(lo, hi, gv): the column sums [lo, hi) of d_out, accumulated into gv by the callee
+            for m, r in enumerate(self._rbms):
+                col(m * Hn, (m + 1) * Hn, g[f"{r.prefix}/bh"].view(-1))
+                col(M * Hn + m * D, M * Hn + (m + 1) * D, g[f"{r.prefix}/bv"].view(-1))
         if self.bias_mode != "conditional":
-            ops.bias_grad(d_out[:, :Hn], g[f"{self._rbm.prefix}/bh"].view(-1), accumulate=True)
-            ops.bias_grad(d_out[:, Hn:Hn + D], g[f"{self._rbm.prefix}/bv"].view(-1), accumulate=True)
+            bias_grads(lambda lo, hi, gv: ops.bias_grad(d_out[:, lo:hi], gv, accumulate=True))
             self._dx = None
             self._unscale(ls)
             return                                   # as written: no gradient reaches the LSTM / Wuh / Wuv (R3)
@@ -1321,8 +1383,7 @@ class RnnRBM(RnnEstimator):
         doT = zalloc((self.n_out, Np8), device=dev, dtype=self.dtype)
         if self.dtype == torch.float32:
             if self.internal_bias:
-                ops.bias_grad(d_out[:, :Hn], g[f"{self._rbm.prefix}/bh"].view(-1), accumulate=True)
-                ops.bias_grad(d_out[:, Hn:Hn + D], g[f"{self._rbm.prefix}/bv"].view(-1), accumulate=True)
+                bias_grads(lambda lo, hi, gv: ops.bias_grad(d_out[:, lo:hi], gv, accumulate=True))
             ops.transpose(d_out[:, :self.n_out], doT)
             do_c = d_out
         else:
@@ -1333,22 +1394,22 @@ class RnnRBM(RnnEstimator):
             colsum = torch.zeros(self.n_out, device=dev)
             ops.grad_rows_fanout(d_out, self.n_out, do_c, doT, colsum)
             if self.internal_bias:
-                gh, gv = g[f"{self._rbm.prefix}/bh"].view(-1), g[f"{self._rbm.prefix}/bv"].view(-1)
-                ops.axpby(1.0, colsum[:Hn], 1.0, gh, gh)
-                ops.axpby(1.0, colsum[Hn:Hn + D], 1.0, gv, gv)
-        # Wuh [R,Hn] and Wuv [R,D] are separate variables: one accumulating product per block of the transposed gradient
-        ops.gemm_tn(yT, doT[:Hn], g["Wuh"], accumulate=True, split_k=LstmStack._split_k(R, Hn, Np8))
-        ops.gemm_tn(yT, doT[Hn:Hn + D], g["Wuv"], accumulate=True, split_k=LstmStack._split_k(R, D, Np8))
+                bias_grads(lambda lo, hi, gv: ops.axpby(1.0, colsum[lo:hi], 1.0, gv, gv))
+        # Wuh [R, M Hn] and Wuv [R, M D] are separate variables: one accumulating product per variable, over all tracks' blocks
+        ops.gemm_tn(yT, doT[:M * Hn], g["Wuh"], accumulate=True, split_k=LstmStack._split_k(R, M * Hn, Np8))
+        ops.gemm_tn(yT, doT[M * Hn:self.n_out], g["Wuv"], accumulate=True, split_k=LstmStack._split_k(R, M * D, Np8))
         dy = torch.empty((N, R), device=dev)
         ops.gemm_tn(do_c, self._wu_p, dy)
         self._dx = yield from self._lstm_backward_co(dy, cx)
         self._unscale(ls)
 
+    # -- states and sampling --------------------------------------------------------------------
     def zero_state(self, batch_size):
         self._materialize(self._num_inputs)
         dev = self.store.theta.device
-        return RnnEstimatorStateTuple(torch.zeros((batch_size, self.num_hidden[-1]), device=dev),
-                                      torch.zeros((batch_size, self.num_dims), device=dev), self._get_rnn_zero_state(batch_size))
+        z = lambda n: torch.zeros((batch_size, n), device=dev)
+        return RnnEstimatorStateTuple(self._present([z(self.num_hidden[-1]) for _ in self._rbms]), self._present([z(self.num_dims) for _ in self._rbms]),
+                                      self._get_rnn_zero_state(batch_size))
 
     def _get_state(self, inputs, lengths=None, initial_state=None, last_outputs=False):
         """rnn_rbm.py:184-238 (dynamic_rnn; identical to the decode loop on valid rows)."""
@@ -1364,18 +1425,29 @@ class RnnRBM(RnnEstimator):
         return self._state_from_out(out, tuple((c.clone(), h.clone()) for c, h in final))
 
     def _state_from_out(self, out, rnn_state):
-        """The estimator state of a Dense output [B, ld] = [bh_t | bv_t] (views)."""
-        Hn, D = self.num_hidden[-1], self.num_dims
-        return RnnEstimatorStateTuple(out[:, :Hn], out[:, Hn:Hn + D], rnn_state)
+        """The estimator state of a Dense output [B, ld]: the tracks' bias blocks bh_t | bv_t (views)."""
+        be, bd = self._split(out)
+        return RnnEstimatorStateTuple(self._present(be), self._present(bd), rnn_state)
+
+    _det_bias = None                       # inside RnnMultiRBM._generate_scan: True, then the internal bias vectors the scan's first Dense formed
 
     def _det_state(self, h, rnn_state):
-        """rnn_rbm.py:240-259 in the deterministic arithmetic: bh_t = rbm.bh + h . Wuh, bv_t = rbm.bv + h . Wuv (two jobs, one launch)."""
-        Hn, D = self.num_hidden[-1], self.num_dims
+        """rnn_rbm.py:240-259 in the deterministic arithmetic: [bh_0 ..] = [rbm_m.bh] + h . Wuh, [bv_0 ..] = [rbm_m.bv] + h . Wuv (two jobs,
+        one launch)."""
+        M, Hn = self.num_tracks, self.num_hidden[-1]
         out = torch.empty((h.shape[0], self.ldo), device=h.device)
-        ib = self.internal_bias
-        ops.dense_det([dict(x=h, W=self.store["Wuh"], bias=self._rbm.bh.view(-1) if ib else None, out=out[:, :Hn]),
-                       dict(x=h, W=self.store["Wuv"], bias=self._rbm.bv.view(-1) if ib else None, out=out[:, Hn:Hn + D])])
-        return RnnEstimatorStateTuple(out[:, :Hn], out[:, Hn:Hn + D], tuple(rnn_state))
+        bh = bv = None
+        if self.internal_bias:
+            ib = self._det_bias
+            if ib is None or ib is True:
+                cat = self._internal_biases()
+                if ib is True:
+                    self._det_bias = cat
+                ib = cat
+            bh, bv = ib
+        ops.dense_det([dict(x=h, W=self.store["Wuh"], bias=bh, out=out[:, :M * Hn]),
+                       dict(x=h, W=self.store["Wuv"], bias=bv, out=out[:, M * Hn:self.n_out])])
+        return self._state_from_out(out, tuple(rnn_state))
 
     def single_step(self, inputs, initial_state, x2=None):
         """rnn_rbm.py:261-281."""
@@ -1401,39 +1473,45 @@ class RnnRBM(RnnEstimator):
         return v, p_v
 
     def pretrain(self, optimizer, lr, run_optimizer=True):
-        """rnn_rbm.py:299-322: one CD-k update of the RBM module on the flattened inputs (`rbm.train`, no optimiser, no clipping).
-        Returns the documented 5-tuple (the reference returns `rbm.train`'s 3-tuple although its docstring and every caller --
-        multinn_jamming.py:219-221 -- expect five values)."""
+        """rnn_rbm.py:299-322: one CD-k update of every track's RBM on its track of the flattened inputs (`rbm.train`, seed + m; no
+        optimiser, no clipping).  Returns the documented 5-tuple (the reference returns `rbm.train`'s 3-tuple although its docstring and
+        every caller -- multinn_jamming.py:219-221 -- expect five values)."""
         x = self._inputs
         B, T, _ = x.shape
-        flat = x.to(torch.uint8)[:, :, :self.num_dims].reshape(B * T, self.num_dims)
+        M, D = self.num_tracks, self.num_dims
+        xt = x.to(torch.uint8)[:, :, :D * M].reshape(B * T, D, M)
+        keep = None
         if self._lengths is not None:
-            m = torch.arange(T, device=x.device)[None, :] < self._lengths.to(x.device)[:, None]
-            flat = flat[m.reshape(-1)]
+            keep = (torch.arange(T, device=x.device)[None, :] < self._lengths.to(x.device)[:, None]).reshape(-1)
         self._materialize(x.shape[-1])
-        if not run_optimizer:
-            # the only caller that passes False (multinn_jamming.py:219-241 without separate losses) discards the CD update ops in favour of
-            # its joint gradient step and keeps the init ops: nothing is applied here
-            return self._rbm.visible_bias_init_ops(flat.contiguous()), [], self.metrics, self.metrics_upd, self.summaries
-        # eager semantics: the CD-k update is APPLIED by this call and update_ops comes back empty, while init_ops are
-        # returned unexecuted (the reference runs them once, before the first update: train_encoders.py:150-153) -- run them BEFORE the first
-        # pretrain() call, not after it, or the first update's visible-bias delta is overwritten
-        init_ops, update_ops, self._cd_gradients = self._rbm.train(flat.contiguous(), lr, seed=self.seed + self.store.step, row0=self.row0 * T)
-        self._packed_step = -1                          # rbm.bh / rbm.bv feed the packed bias row
+        init_ops, update_ops, grads = [], [], []
+        for m, r in enumerate(self._rbms):
+            flat = (xt[:, :, m] if keep is None else xt[:, :, m][keep]).contiguous()
+            if not run_optimizer:
+                # the only caller that passes False (multinn_jamming.py:219-241 without separate losses) discards the CD update ops in favour
+                # of its joint gradient step and keeps the init ops: nothing is applied here
+                init_ops += r.visible_bias_init_ops(flat)
+                continue
+            # eager semantics: the CD-k update is APPLIED by this call and update_ops comes back empty, while init_ops are
+            # returned unexecuted (the reference runs them once, before the first update: train_encoders.py:150-153) -- run them BEFORE the
+            # first pretrain() call, not after it, or the first update's visible-bias delta is overwritten
+            io, uo, gr = r.train(flat, lr, seed=self.seed + m + self.store.step, row0=self.row0 * T)
+            init_ops += io; update_ops += uo; grads.append(gr)
+        if run_optimizer:
+            self._cd_gradients = self._present(grads)
+            self._packed_step = -1                      # rbm.bh / rbm.bv feed the packed bias row
         return init_ops, update_ops, self.metrics, self.metrics_upd, self.summaries
 
 
 # ------------------------------------------------------------------------------------------------
 class RnnMultiRBM(RnnRBM):
     """A shared-LSTM multi-track LSTM-RBM: one LSTM, one Dense (Wuh | Wuv), ``len(tracks)`` RBMs -- the structure of rnn_multinade.py with
-    the estimator of rnn_rbm.py (the reference stops at multinn_composer.py:44-45; it has no such model).
+    the estimator of rnn_rbm.py (the reference stops at multinn_composer.py:44-45; it has no such model).  The step is RnnRBM's, over M tracks.
 
     Inputs / targets are [B, T, M * D] in composer layout (feature d * M + m).  The Dense output of a step is
     [bh_0 .. bh_{M-1} | bv_0 .. bv_{M-1}] (track-major blocks: RnnNade._build_biases' split order); track m runs a CD-k chain with seed
-    ``seed + m`` from its slice of the inputs, cost_m = F_m(target_m) - F_m(v_s,m).  The optimised loss, and `free_energy` /
-    `log_likelihood`, are the MEAN over the tracks of the per-track row-weighted values (rnn_multinade.py:199-203).  The M chains of a step
-    -- training's and every sampling step's -- are ONE grouped launch (ops.rbm_gibbs_multi), the free energies one per chain end
-    (ops.rbm_free_energy_multi)."""
+    ``seed + m`` from its slice of the inputs.  The M chains of a step -- training's and every sampling step's -- are ONE grouped launch
+    (ops.rbm_gibbs_multi), the free energies one per chain end (ops.rbm_free_energy_multi); per-track values come back as lists."""
 
     def __init__(self, num_dims, num_hidden, num_hidden_rnn, tracks, keep_prob=1.0, internal_bias=True, k=10, name="rnn-multirbm",
                  bias_mode="conditional", **kw):
@@ -1441,254 +1519,19 @@ class RnnMultiRBM(RnnRBM):
         if not 1 <= len(self._tracks) <= ops.RBM_MULTI_MAX_JOBS:
             raise ValueError(f"RnnMultiRBM takes 1..{ops.RBM_MULTI_MAX_JOBS} tracks (one grouped launch), got {len(self._tracks)}")
         super().__init__(num_dims, num_hidden, num_hidden_rnn, keep_prob, internal_bias, k, name, "all", bias_mode, **kw)
-        self._num_output = self.num_tracks * self.num_dims
-        self._det_bias = None
 
-    tracks = property(lambda self: self._tracks)
-    num_tracks = property(lambda self: len(self._tracks))
+    def _rbm_prefix(self, m):
+        return f"rbm_{m}"
 
-    def _init_estimator(self):
-        self._rbms = [RBM(self.num_dims, self.num_hidden[-1], k=self._k, name=f"rbm_{m}") for m in range(self.num_tracks)]
-        self._rbm = self._rbms[0]
+    def _present(self, per_track):
+        return per_track
 
-    def _declare(self, num_inputs):
-        """Variable order rbm_m [W, bv, bh] for every track, rnn, [Wuh, Wuv]; the columns of Wuh / Wuv are track-major."""
-        M, D, Hn, R = self.num_tracks, self.num_dims, self.num_hidden[-1], self.num_hidden_rnn[-1]
-        for m, r in enumerate(self._rbms):
-            r.declare(self.store, self._gen, prefix=f"rbm_{m}")
-        self._rnn.declare(self.store, num_inputs, self._gen)
-        self.store.declare("Wuh", (R, M * Hn), glorot_uniform(self._gen, R, M * Hn))
-        self.store.declare("Wuv", (R, M * D), glorot_uniform(self._gen, R, M * D))
-        self.n_out = M * (Hn + D)
-        self.ldo = ops.round_up(self.n_out, 64)
+    def _step_chains(self, v0, bh, bv, rows, p_v, v_s):
+        ops.rbm_gibbs_multi([dict(v0=v0[m], W=r.W, bh=bh[m], bv=bv[m], seed=self.seed + m, p_v=p_v[m], v_out=v_s[m]) for m, r in enumerate(self._rbms)],
+                            self._k, 0, rows, 0, seed_step=self.store.step_dev)
 
-    def _internal_biases(self):
-        """[bh_0 .. bh_{M-1}] and [bv_0 .. bv_{M-1}] as two flat vectors, in the Dense output's column order."""
-        return torch.cat([r.bh.view(-1) for r in self._rbms]), torch.cat([r.bv.view(-1) for r in self._rbms])
-
-    def _pack_estimator(self):
-        dev = self.store.theta.device
-        R = self.num_hidden_rnn[-1]
-        wu = torch.cat([self.store["Wuh"], self.store["Wuv"]], 1).contiguous()          # [R, M Hn + M D]
-        self._wu_t = torch.empty((self.n_out, R), device=dev, dtype=self.dtype)
-        ops.transpose(wu, self._wu_t)
-        self._wu_p = torch.zeros((R, self.ldo), device=dev, dtype=self.dtype)
-        ops.convert2d(wu, self._wu_p[:, :self.n_out])
-        self._bias_cat = torch.cat(self._internal_biases()).contiguous() if self.internal_bias else torch.zeros(self.n_out, device=dev)
-
-    def _split(self, out):
-        """The per-track bias blocks of a Dense output [N, ld]: views, one leading dimension."""
-        M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
-        return ([out[:, m * Hn:(m + 1) * Hn] for m in range(M)], [out[:, M * Hn + m * D:M * Hn + (m + 1) * D] for m in range(M)])
-
-    def _planes(self, x, B, T):
-        """[B, T, D * M] composer layout -> u8 [M, T * B, D]: every track's rows as a contiguous time-major plane."""
-        M, D = self.num_tracks, self.num_dims
-        return x[:, :, :D * M].to(torch.uint8).reshape(B, T, D, M).permute(3, 1, 0, 2).contiguous().view(M, T * B, D)
-
-    def _build_co(self, x=None, y=None, lengths=None, is_train=None, mode="eval"):
-        Generator.build(self, x, y, lengths, is_train, mode)
-        self._materialize(x.shape[-1] if x is not None else self._num_inputs)
-        self._rnn.build_cell(is_train)
-        if mode in ("train", "eval"):
-            B, T, _ = x.shape
-            M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
-            N, dev = B * T, x.device
-            self._ensure_packed()
-            x_tm = self._to_time_major_inputs(x)
-            v0, tgt = self._planes(x, B, T), self._planes(y, B, T)                   # every chain starts from its track of the inputs
-            rw = self._row_weight(lengths, B, T, dev)
-            kp = self._rnn.effective_keep_prob()
-            seed = self.seed + self.store.step
-            yy, ctx, _ = yield from self._stack.forward_co(x_tm, kp, self.seed, self.row0, save=(mode == "train"), state0=self._state0(B),
-                                                           step_dev=self.store.step_dev, state_grad=(mode == "train"))
-            out = self._biases(yy.view(N, -1))
-            bh_t, bv_t = self._split(out)
-            rows = (torch.arange(T, device=dev)[:, None] * 65536 + (self.row0 + torch.arange(B, device=dev))[None, :]).reshape(-1).int()
-            p_v = torch.empty((M, N, D), device=dev)
-            v_s = torch.empty((M, N, D), device=dev, dtype=torch.uint8)
-            W = [r.W for r in self._rbms]
-            # the M chains in one launch; seed + m + step, the step read on the device (RnnRBM._build_co)
-            ops.rbm_gibbs_multi([dict(v0=v0[m], W=W[m], bh=bh_t[m], bv=bv_t[m], seed=self.seed + m, p_v=p_v[m], v_out=v_s[m]) for m in range(M)],
-                                self._k, 0, rows, 0, seed_step=self.store.step_dev)
-            if self.bias_mode == "conditional":
-                bh_u, bv_u = bh_t, bv_t
-            else:
-                bh_u, bv_u = [r.bh for r in self._rbms], [r.bv for r in self._rbms]
-            Fv = torch.empty((M, N), device=dev); Fs = torch.empty((M, N), device=dev)
-            sv = torch.empty((M, N, Hn), device=dev) if mode == "train" else None
-            ss = torch.empty((M, N, Hn), device=dev) if mode == "train" else None
-            ops.rbm_free_energy_multi([dict(v=tgt[m], W=W[m], bh=bh_u[m], bv=bv_u[m], F=Fv[m], p_h=None if sv is None else sv[m]) for m in range(M)])
-            ops.rbm_free_energy_multi([dict(v=v_s[m], W=W[m], bh=bh_u[m], bv=bv_u[m], F=Fs[m], p_h=None if ss is None else ss[m]) for m in range(M)])
-            cost = Fv - Fs
-            rwm = (rw / M).repeat(M)                                                     # mean over the tracks of the row-weighted sums
-            loss = torch.zeros(1, device=dev)
-            ops.weighted_sum(cost.view(-1), rwm, loss)
-            self._ctx = dict(y=yy, lstm=ctx, out=out, tgt=tgt, v_s=v_s, rw=rw, kp=kp, seed=seed, B=B, T=T, n_valid=self._n_valid,
-                             ls_dev=self._ls_dev if self._n_valid is None else None, sv=sv, ss=ss)
-            self._cost_tm, self._F_tm, self._pv_tm, self._vs_tm, self._loss = cost, Fv, p_v, v_s, loss
-            self._lengths, self._flat_idx = lengths, None
-            self._recon_tm = torch.empty((M, N), device=dev)
-            ops.log_loss_rows(tgt.view(M * N, D), p_v.view(M * N, D), self._recon_tm.view(-1))
-            fe, ll = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
-            ops.weighted_sum(Fv.view(-1), rwm, fe)
-            ops.weighted_sum(self._recon_tm.view(-1), rwm, ll)
-            self._metrics = {"batch/loss": loss, "free_energy": fe, "log_likelihood": ll}
-            self._metrics_upd = []
-        self._is_built = True
-
-    def _per_track(self, t, cast=None):
-        idx = self._idx()
-        return [t[m][idx] if cast is None else t[m][idx].to(cast) for m in range(self.num_tracks)]
-
-    cond_probs = property(lambda self: self._per_track(self._pv_tm))
-    _outputs = property(lambda self: self._per_track(self._vs_tm, torch.float32))
-    free_energy = property(lambda self: self._per_track(self._F_tm))
-    cost = property(lambda self: self._per_track(self._cost_tm))
-    reconstruction_cost = property(lambda self: self._per_track(self._recon_tm))
-
-    def _nll_rows_built(self, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais", given=None):
-        """AIS NLL of the last build's valid rows: the SUM over the tracks of F_m(target_m) + log Z^_m on the row's conditional biases
-        (the tracks of a step are independent given the history), each track estimated as RnnRBM._nll_rows_built does with seed + m --
-        under every method; "both" sums each side of the bracket over the tracks.  given (optional): (codes u8 [B, T, D * M] in the composer
-        layout, whole, some: per track) -- each track's conditional rows as RnnRBM._nll_rows_built forms them; a wholly given track adds
-        exactly 0 and runs no chain, a track with no given cell is estimated as without `given`."""
-        sides = nll_sides(method)
-        cx = self._ctx
-        B, T = cx["B"], cx["T"]
-        bh_t, bv_t = self._split(cx["out"])
-        dev = cx["out"].device
-        idx = self._idx()
-        rows = (torch.arange(T, device=dev)[:, None] * 65536 + (self.row0 + torch.arange(B, device=dev))[None, :]).reshape(-1)
-        ids = rows[idx].to(torch.int32).contiguous()
-        n = ids.numel()
-        if n == 0:
-            e = torch.zeros(0, device=dev)
-            return nll_result(method, [NllEstimate(e, e, e, e, e) for _ in sides])
-        s0 = self.seed if seed is None else seed
-        if given is not None and all(given[1]):
-            return given_nll_result(method, n, dev)
-        planes = self._planes(given[0], B, T) if given is not None and any(given[2]) else None
-        parts = [[] for _ in sides]
-        for m, r in enumerate(self._rbms):
-            if given is not None and given[1][m]:
-                continue
-            codes = planes[m][idx].contiguous() if planes is not None and given[2][m] else None
-            bh, bv = bh_t[m][idx].contiguous(), bv_t[m][idx].contiguous()
-            tgt = cx["tgt"][m][idx].contiguous()
-            F = torch.empty(n, device=dev)
-            ops.rbm_free_energy(tgt, r.W, bh, bv, F)
-            for side, part in zip(sides, parts):
-                part.append(rbm_nll_side(side, r, tgt, F, bh, bv, num_chains, num_betas, betas, s0 + m, ids, codes))
-        return nll_result(method, [NllEstimate.total(p) for p in parts])
-
-    def _backward_co(self):
-        cx = self._ctx
-        M, D, Hn, R = self.num_tracks, self.num_dims, self.num_hidden[-1], self.num_hidden_rnn[-1]
-        B, T = cx["B"], cx["T"]
-        N, dev = B * T, cx["out"].device
-        g = self.store.gviews
-        self.store.grad.zero_()
-        sv, ss = cx.get("sv"), cx.get("ss")
-        if sv is None:
-            raise RuntimeError("build(..., mode='train') must run before train()")
-        # row weights, scale and the f16 loss scale (static x dynamic) exactly as RnnRBM._backward_co; the 1 / M of the mean over the tracks
-        # rides on the scale
-        dyn = self.store.ls_dyn if self.dtype == torch.float16 else None
-        gs = self.grad_scale / M
-        if cx["n_valid"] is None:
-            lsd = cx.get("ls_dev")
-            if lsd is not None and dyn is not None:
-                lsd = lsd * dyn[0:1]
-            rw, scale = (cx["rw"] if lsd is None else cx["rw"] * lsd), gs
-            ls = 1.0 if lsd is None else 1.0 / lsd
-        else:
-            ls = self._stack.loss_scale(cx["n_valid"])
-            if dyn is not None:
-                rw, scale = cx["rw"] * dyn[0:1], gs * ls
-                ls = dyn[1:2] * (1.0 / ls)
-            else:
-                rw, scale = cx["rw"], gs * ls
-        # per track the rows of RnnRBM's gradient block [Hn | D], moved into the track's column blocks of the one Dense-shaped d_out
-        d_out = torch.zeros((N, self.ldo), device=dev)
-        d_m = torch.empty((N, Hn + D), device=dev)
-        pos = torch.empty((M, N, Hn), device=dev); neg = torch.empty((M, N, Hn), device=dev)
-        h16 = self._stack.h16
-        Np = ops.round_up(N, 64 if h16 else 4)
-        def tr(xm, rows):
-            o = (torch.zeros if Np != N else torch.empty)((rows, Np), device=dev, dtype=self.dtype if h16 else torch.float32)
-            return ops.transpose(xm, o)
-        sk = int(max(1, min(256 // (-(-D // 128) * -(-Hn // 128)), Np // 256)))
-        dbh, dbv = self._split(d_out)
-        for m, r in enumerate(self._rbms):
-            ops.rbm_cd_rows(cx["tgt"][m], cx["v_s"][m], sv[m], ss[m], rw, scale, d_m, pos[m], neg[m])
-            dbh[m].copy_(d_m[:, :Hn]); dbv[m].copy_(d_m[:, Hn:])
-            gW = g[f"{r.prefix}/W"]                                                      # dW_m = v_s,m^T pos_m + target_m^T neg_m
-            ops.gemm_tn(tr(cx["v_s"][m], D), tr(pos[m], Hn), gW, accumulate=True, split_k=sk)
-            ops.gemm_tn(tr(cx["tgt"][m], D), tr(neg[m], Hn), gW, accumulate=True, split_k=sk)
-        def bias_grads(col):                                                             # col(lo, hi) -> the column sums [lo, hi) of d_out, accumulated by the callee
-            for m, r in enumerate(self._rbms):
-                col(m * Hn, (m + 1) * Hn, g[f"{r.prefix}/bh"].view(-1))
-                col(M * Hn + m * D, M * Hn + (m + 1) * D, g[f"{r.prefix}/bv"].view(-1))
-        if self.bias_mode != "conditional":
-            bias_grads(lambda lo, hi, gv: ops.bias_grad(d_out[:, lo:hi], gv, accumulate=True))
-            self._dx = None
-            self._unscale(ls)
-            return                                   # as RnnRBM: no gradient reaches the LSTM / Wuh / Wuv
-        Np8 = ops.round_up(N, 64)
-        zalloc = torch.zeros if Np8 != N else torch.empty
-        yT = cx["lstm"][-1].get("yT") if cx["lstm"] else None
-        if yT is None:
-            yT = zalloc((R, Np8), device=dev, dtype=self.dtype)
-            ops.transpose(cx["y"].view(N, R), yT)
-        doT = zalloc((self.n_out, Np8), device=dev, dtype=self.dtype)
-        if self.dtype == torch.float32:
-            if self.internal_bias:
-                bias_grads(lambda lo, hi, gv: ops.bias_grad(d_out[:, lo:hi], gv, accumulate=True))
-            ops.transpose(d_out[:, :self.n_out], doT)
-            do_c = d_out
-        else:
-            do_c = torch.empty((N, self.ldo), device=dev, dtype=self.dtype)
-            colsum = torch.zeros(self.n_out, device=dev)
-            ops.grad_rows_fanout(d_out, self.n_out, do_c, doT, colsum)
-            if self.internal_bias:
-                bias_grads(lambda lo, hi, gv: ops.axpby(1.0, colsum[lo:hi], 1.0, gv, gv))
-        # one accumulating product per variable, over all tracks' blocks
-        ops.gemm_tn(yT, doT[:M * Hn], g["Wuh"], accumulate=True, split_k=LstmStack._split_k(R, M * Hn, Np8))
-        ops.gemm_tn(yT, doT[M * Hn:self.n_out], g["Wuv"], accumulate=True, split_k=LstmStack._split_k(R, M * D, Np8))
-        dy = torch.empty((N, R), device=dev)
-        ops.gemm_tn(do_c, self._wu_p, dy)
-        self._dx = yield from self._lstm_backward_co(dy, cx)
-        self._unscale(ls)
-
-    # -- states and sampling --------------------------------------------------------------------
-    def zero_state(self, batch_size):
-        self._materialize(self._num_inputs)
-        dev = self.store.theta.device
-        z = lambda n: torch.zeros((batch_size, n), device=dev)
-        return RnnEstimatorStateTuple([z(self.num_hidden[-1]) for _ in self._tracks], [z(self.num_dims) for _ in self._tracks],
-                                      self._get_rnn_zero_state(batch_size))
-
-    def _state_from_out(self, out, rnn_state):
-        """Per-track lists of bias blocks (RnnRBM._get_state / single_step form their states through this)."""
-        be, bd = self._split(out)
-        return RnnEstimatorStateTuple(be, bd, rnn_state)
-
-    def _det_state(self, h, rnn_state):
-        """The Dense of a sampling step in the deterministic arithmetic: [bh_0 ..] = [rbm_m.bh] + h . Wuh, [bv_0 ..] = [rbm_m.bv] + h . Wuv
-        (two jobs, one launch; inside a scan the concatenated internal biases are formed once)."""
-        M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
-        out = torch.empty((h.shape[0], self.ldo), device=h.device)
-        ib = self._det_bias
-        if self.internal_bias and (ib is None or ib is True):
-            cat = self._internal_biases()
-            if ib is True:
-                self._det_bias = cat
-            ib = cat
-        bh, bv = ib if self.internal_bias else (None, None)
-        ops.dense_det([dict(x=h, W=self.store["Wuh"], bias=bh, out=out[:, :M * Hn]),
-                       dict(x=h, W=self.store["Wuv"], bias=bv, out=out[:, M * Hn:self.n_out])])
-        return self._state_from_out(out, tuple(rnn_state))
+    def _free_energies(self, v, bh, bv, F, p_h):
+        ops.rbm_free_energy_multi([dict(v=v[m], W=r.W, bh=bh[m], bv=bv[m], F=F[m], p_h=None if p_h is None else p_h[m]) for m, r in enumerate(self._rbms)])
 
     def _temperature(self, temperature):
         return sampling_temperature(temperature, self.num_tracks, allow_none=False)
@@ -1714,24 +1557,3 @@ class RnnMultiRBM(RnnRBM):
                      given=None if given is None else given[:, m::M]) for m, r in enumerate(self._rbms)]
         ops.rbm_gibbs_multi(jobs, self._k, self.row0, None, getattr(self, "_gen_step", 0) * max(self._k, 1), temperature=temperature)
         return smp, p_v
-
-    def pretrain(self, optimizer, lr, run_optimizer=True):
-        """One CD-k update of every track's RBM on its track of the flattened inputs (RBM.train; RnnRBM.pretrain per track, seed + m)."""
-        x = self._inputs
-        B, T, _ = x.shape
-        M, D = self.num_tracks, self.num_dims
-        xt = x.to(torch.uint8)[:, :, :D * M].reshape(B * T, D, M)
-        keep = None
-        if self._lengths is not None:
-            keep = (torch.arange(T, device=x.device)[None, :] < self._lengths.to(x.device)[:, None]).reshape(-1)
-        self._materialize(x.shape[-1])
-        init_ops, update_ops, self._cd_gradients = [], [], []
-        for m, r in enumerate(self._rbms):
-            flat = xt[:, :, m] if keep is None else xt[:, :, m][keep]
-            if not run_optimizer:
-                init_ops += r.visible_bias_init_ops(flat.contiguous())
-                continue
-            io, uo, gr = r.train(flat.contiguous(), lr, seed=self.seed + m + self.store.step, row0=self.row0 * T)
-            init_ops += io; update_ops += uo; self._cd_gradients.append(gr)
-        self._packed_step = -1
-        return init_ops, update_ops, self.metrics, self.metrics_upd, self.summaries
