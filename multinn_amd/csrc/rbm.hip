@@ -323,7 +323,7 @@ extern "C" int mnn_rbm_cd_rows(mnn_stream_t s, int N, int D, int Hn, int ld, con
 __global__ void __launch_bounds__(256) sigmoid_grad_kernel(long n, const float* __restrict__ dy, const float* __restrict__ y, float* dz) {
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float yy = y[i];
-        dz[i] = dy[i] * (yy - yy * yy);
+        dz[i] = dy[i] * (yy * (1.f - yy));       // (not yy - yy * yy: the rounding of yy * yy is amplified by yy / (1 - yy) in the difference)
     }
 }
 extern "C" int mnn_sigmoid_grad_f32(mnn_stream_t s, long n, const float* dy, const float* y, float* dz) {

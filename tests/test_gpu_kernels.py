@@ -404,7 +404,7 @@ def _lstm_setup(ops, B, T, n_in, u, dt, seed=3):
     x = (R.random((B, T, n_in)) < .3).astype(np.float32)
     W = (R.standard_normal((n_in + u, 4 * u)) * 0.2).astype(np.float32)
     b = (R.standard_normal(4 * u) * 0.1).astype(np.float32)
-    tdt = torch.float32 if dt == "f32" else torch.bfloat16
+    tdt = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[dt]
     ld = ops.round_up(n_in, 8)
     wx_t = torch.empty((4 * u, ld), device=DEV, dtype=tdt)
     wh_t = torch.empty((4 * u, u), device=DEV, dtype=tdt)
@@ -428,10 +428,12 @@ def _unperm(z, u):
 
 @pytest.mark.parametrize("dt,B,T,n_in,u", [("f32", 5, 6, 12, 32), ("f32", 70, 4, 20, 64), ("bf16", 33, 5, 16, 64),
                                           ("bf16", 40, 3, 24, 128), ("bf16", 33, 3, 16, 256), ("bf16", 70, 3, 8, 512), ("f32", 9, 2, 8, 128),
-                                          ("bf16", 520, 3, 8, 128), ("bf16", 640, 2, 16, 512)])
+                                          ("bf16", 520, 3, 8, 128), ("bf16", 640, 2, 16, 512),
+                                          ("f16", 33, 5, 16, 64), ("f16", 40, 3, 24, 128), ("f16", 70, 3, 8, 512)])
 def test_lstm_layer_fwd_bwd(ops, dt, B, T, n_in, u):
     x, W, b, (wx_t, wh_t, wh_p, wx_p, bias_p), xin, tdt = _lstm_setup(ops, B, T, n_in, u, dt)
-    tol = 2e-5 if dt == "f32" else 3e-2
+    # f16 (the generic step kernels at every width): the bf16 tolerance scaled by the ratio of the unit roundoffs, 2^-11 against 2^-8
+    tol = {"f32": 2e-5, "bf16": 3e-2, "f16": 3e-2 / 8}[dt]
     # packing
     assert rel(_unperm(wx_t.float().cpu().numpy().T[:n_in], u), W[:n_in]) < (1e-7 if dt == "f32" else 1e-2)
     assert rel(_unperm(wh_p.float().cpu().numpy(), u), W[n_in:]) < (1e-7 if dt == "f32" else 1e-2)
@@ -525,6 +527,40 @@ def test_lstm_chunked_calls_equal_full_sequence(ops):
     # the bias gradient is the row sum of the bf16 dz^T (one pass, off the per-step chain)
     assert rel(db.cpu().numpy(), dzb1.float().view(T * B, -1).sum(0).cpu().numpy()) < 1e-5
     assert rel(db.cpu().numpy(), dz1.view(T * B, -1).sum(0).cpu().numpy()) < 1e-2
+
+
+@pytest.mark.parametrize("dt,u", [("f32", 32), ("f16", 64)])
+def test_lstm_generic_path_epilogue_outputs(ops, dt, u):
+    """The generic step kernels' epilogue (mnn_transpose / mnn_bias_grad at pointer offsets, one call per chunk): hT, dzT_t and db_p of
+    chunked lstm_seq_fwd / lstm_seq_bwd calls."""
+    B, T, n_in = 20, 7, 8
+    x, W, b, (wx_t, wh_t, wh_p, wx_p, bias_p), xin, tdt = _lstm_setup(ops, B, T, n_in, u, dt, seed=8)
+    assert not ops.lstm_fused_outputs(tdt, u)
+    xproj = torch.empty((T, B, 4 * u), device=DEV)
+    ops.gemm_tn(xin.view(T * B, -1), wx_t, xproj.view(T * B, -1), bias=bias_p)
+    gates, c, h = torch.zeros((T, B, 4 * u), device=DEV), torch.zeros((T, B, u), device=DEV), torch.zeros((T, B, u), device=DEV, dtype=tdt)
+    Np = ops.round_up(T * B, 64)
+    hT = torch.full((u, Np), 7.0, device=DEV, dtype=tdt)
+    for t0, t1 in [(0, 3), (3, 4), (4, 7)]:
+        ops.lstm_seq_fwd(xproj, wh_t, None, None, gates, c, h, t0, t1, hT)
+    assert torch.equal(hT[:, B:T * B], h[:-1].reshape((T - 1) * B, u).t())
+    assert bool((hT[:, :B] == 7.0).all()) and bool((hT[:, T * B:] == 7.0).all())          # columns [0, B) (and the padding) stay as given
+    dy = dev(np.random.default_rng(1).standard_normal((T, B, u)).astype(np.float32))
+    dz = torch.zeros((T, B, 4 * u), device=DEV)
+    dz16 = dz if dt == "f32" else torch.zeros((T, B, 4 * u), device=DEV, dtype=tdt)
+    dzT_t = torch.full((4 * u, Np), 7.0, device=DEV, dtype=tdt)
+    db_p = torch.zeros(4 * u, device=DEV)
+    ws = ops.lstm_seq_bwd_workspace(B, u, DEV)
+    chunks = [(5, 7), (2, 5), (0, 2)]
+    for t0, t1 in chunks:
+        ops.lstm_seq_bwd(dy, wh_p, gates, c, None, dz, dz16, None, None, t0, t1, ws, dzT_t, db_p)
+    assert torch.equal(dzT_t[:, :T * B], dz16.view(T * B, 4 * u).t()) and bool((dzT_t[:, T * B:] == 7.0).all())
+    # column sums of the f32 dz, one mnn_bias_grad per chunk accumulating into db_p: a term passes through at most k roundings of its
+    # thread's chain (k = the longest chunk's rows / 4 waves; one row slab per call), 8 of the workgroup's tree and g atomics (one per call)
+    dzf = dz.view(T * B, 4 * u).double().cpu().numpy()
+    k, g = max(-(-(t1 - t0) * B // 4) for t0, t1 in chunks), len(chunks)
+    assert (np.abs(db_p.cpu().numpy() - dzf.sum(0)) <= (k + 8 + g) * 2.0 ** -24 * np.abs(dzf).sum(0)).all()
+    assert float(db_p.abs().max()) > 0
 
 
 def test_lstm_initial_state_and_dh0(ops):
