@@ -17,6 +17,7 @@ import os
 import torch
 
 from . import ops
+from .switches import flag
 from ._lib import MnnError
 
 STREAM_DROPOUT, STREAM_NADE, STREAM_RBM_H, STREAM_RBM_V, STREAM_DBN_ENC, STREAM_DBN_DEC = range(6)
@@ -117,7 +118,7 @@ class ScanGraphs:
 
     @staticmethod
     def enabled(x):
-        return x.is_cuda and os.environ.get("MULTINN_GENERATE_GRAPH", "1") != "0" and not torch.cuda.is_current_stream_capturing()
+        return x.is_cuda and flag("MULTINN_GENERATE_GRAPH") and not torch.cuda.is_current_stream_capturing()
 
     def run(self, key, x, scan, warm, after_capture, extra=None):
         """scan(static_x) -> output tensor (captured); warm(static_x): a short eager run that creates parameters and

@@ -1,5 +1,6 @@
 // HBM-bound plumbing kernels: layout changes, dropout, reductions, optimiser.
 #include <stdarg.h>
+#include <stdlib.h>
 
 #include "common.h"
 
@@ -16,6 +17,35 @@ void mnn_set_error(const char* fmt, ...) {
 }
 extern "C" const char* mnn_last_error(void) { return g_err; }
 extern "C" int mnn_version(void) { return MNN_ABI_VERSION; }
+
+// host_support.h
+hipError_t mnn_current_device(int* dev) {
+    const hipError_t e = hipGetDevice(dev);
+    if (e != hipSuccess) return e;
+    return *dev >= 0 && *dev < MNN_MAX_DEVICES ? hipSuccess : hipErrorInvalidDevice;
+}
+int mnn_cu_count() {
+    static int n[MNN_MAX_DEVICES];
+    int dev = 0;
+    if (mnn_current_device(&dev) != hipSuccess) return 0;
+    if (n[dev] <= 0) {
+        hipDeviceProp_t p;
+        if (hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
+        n[dev] = p.multiProcessorCount;
+    }
+    return n[dev];
+}
+static const char* const g_switch_names[MNN_SW_COUNT] = {
+#define X(name, meaning) "MNN_" #name,
+    MNN_SWITCHES(X)
+#undef X
+};
+static const char* switch_value(MnnSwitch sw) { return getenv(g_switch_names[sw]); }
+bool mnn_switch_set(MnnSwitch sw) { return switch_value(sw) != nullptr; }
+int mnn_switch_int(MnnSwitch sw, int dflt) {
+    const char* e = switch_value(sw);
+    return e != nullptr ? atoi(e) : dflt;
+}
 
 template <typename T> __device__ __forceinline__ float ld_as_f32(const T* p, size_t i);
 template <> __device__ __forceinline__ float ld_as_f32<float>(const float* p, size_t i) { return p[i]; }

@@ -713,19 +713,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 void mnn_rp_workspace_layout(int nrt, int U, size_t* sync_bytes, size_t* xchg_off);           // lstm_rowpar.hip: the workspace both forms share
 int mnn_rp_reset_launch(hipStream_t st, void* workspace, int nrt, int U);
 
-static int cl_cu_count() {
-    static int n[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (n[dev] <= 0) {
-        hipDeviceProp_t p;
-        if (hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
-        n[dev] = p.multiProcessorCount;
-    }
-    return n[dev];
-}
 // 32 rows per cluster of eight workgroups, every workgroup on its own CU, the clusters dealt evenly over the 8 XCDs
-static bool cl_shape_ok(int B, int units) { return units == 512 && B > 0 && (B % 256) == 0 && (B / 32) * 8 <= cl_cu_count(); }
+static bool cl_shape_ok(int B, int units) { return units == 512 && B > 0 && (B % 256) == 0 && (B / 32) * 8 <= mnn_cu_count(); }
 
 typedef void (*cl_fwd_fn)(ClFwdJobs);
 template <typename F> static cl_fwd_fn cl_fwd_pick(bool drop, bool save) {
@@ -739,22 +728,13 @@ static cl_bwd_fn cl_bwd_kernel(bool f16, bool drop) {
     return drop ? lstm_cl_bwd_kernel<Bf16F, true> : lstm_cl_bwd_kernel<Bf16F, false>;
 }
 static hipError_t cl_prepare() {
-    static bool done[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (done[dev]) return hipSuccess;
-    for (int i = 0; i < 8; ++i) {
-        e = hipFuncSetAttribute((const void*)cl_fwd_kernel(i & 1, i & 2, i & 4), hipFuncAttributeMaxDynamicSharedMemorySize, ClGeom::LDS);
-        if (e != hipSuccess) return e;
-    }
-    for (int i = 0; i < 4; ++i) {
-        e = hipFuncSetAttribute((const void*)cl_bwd_kernel(i & 1, i & 2), hipFuncAttributeMaxDynamicSharedMemorySize, ClBwdGeom::LDS);
-        if (e != hipSuccess) return e;
-    }
-    done[dev] = true;
-    return hipSuccess;
+    static MnnPerDeviceOnce done;
+    return mnn_once_per_device(done, [] {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 8 && e == hipSuccess; ++i) e = mnn_raise_dynamic_lds((const void*)cl_fwd_kernel(i & 1, i & 2, i & 4), ClGeom::LDS);
+        for (int i = 0; i < 4 && e == hipSuccess; ++i) e = mnn_raise_dynamic_lds((const void*)cl_bwd_kernel(i & 1, i & 2), ClBwdGeom::LDS);
+        return e;
+    });
 }
 // (also raises the kernels' dynamic-LDS limit on this device: the host asks before every use, so never for the first time under stream capture)
 extern "C" int mnn_lstm_cluster_ok(int B, int units) {
@@ -776,9 +756,9 @@ __global__ void __launch_bounds__(256) cl_place_probe_kernel(unsigned* __restric
     }
 }
 static int cl_placement_ok(int ncl) {
-    static signed char known[64][9];                         // [device][ncl / 8]: 0 unknown, 1 every cluster on one XCD, -1 not
+    static signed char known[MNN_MAX_DEVICES][9];            // [device][ncl / 8]: 0 unknown, 1 every cluster on one XCD, -1 not
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || ncl < 8 || ncl > 64 || (ncl & 7)) return 0;
+    if (mnn_current_device(&dev) != hipSuccess || ncl < 8 || ncl > 64 || (ncl & 7)) return 0;
     signed char& k = known[dev][ncl / 8];
     if (k != 0) return k > 0;
     // may be reached for the first time while ANOTHER stream of this thread is capturing: the probe runs on its own stream, relaxed mode for its calls
@@ -789,7 +769,7 @@ static int cl_placement_ok(int ncl) {
     unsigned* d = nullptr;
     unsigned host[512];
     do {
-        if (hipFuncSetAttribute((const void*)cl_place_probe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ClBwdGeom::LDS) != hipSuccess) break;
+        if (mnn_raise_dynamic_lds((const void*)cl_place_probe_kernel, ClBwdGeom::LDS) != hipSuccess) break;
         if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) break;
         if (hipMalloc((void**)&d, 8 * ncl * sizeof(unsigned)) != hipSuccess) break;
         if (hipMemsetAsync(d, 0, 8 * ncl * sizeof(unsigned), st) != hipSuccess) break;
@@ -815,13 +795,13 @@ static int cl_placement_ok(int ncl) {
 // The caller falls back to mnn_lstm_rowpar_bwd, which reads the same saved activations.
 extern "C" int mnn_lstm_cluster_bwd_ok(int B, int units) {
     if (!mnn_lstm_cluster_ok(B, units)) return 0;
-    if (getenv("MNN_PERSIST_NO_LOCAL") != nullptr) return 0;
+    if (!mnn_persist_allow_local()) return 0;
     return cl_placement_ok(B / 32);
 }
 // ... for a launch of njobs layers (mnn_lstm_cluster_bwd_multi: the grid's clusters, later rounds included, are probed as one grid)
 extern "C" int mnn_lstm_cluster_bwd_multi_ok(int B, int units, int njobs) {
     if (!mnn_lstm_cluster_ok(B, units) || njobs < 1 || njobs > CL_MAX_JOBS || ((njobs * (B / 32)) & 7) != 0) return 0;
-    if (getenv("MNN_PERSIST_NO_LOCAL") != nullptr) return 0;
+    if (!mnn_persist_allow_local()) return 0;
     return cl_placement_ok(njobs * (B / 32));
 }
 
@@ -846,7 +826,7 @@ static int cl_fwd_fill(const mnn_lstm_fwd_layer* L, int T, int B, float keep_pro
     size_t sync_bytes = 0, xoff = 0;
     mnn_rp_workspace_layout(B / 32, 512, &sync_bytes, &xoff);
     a.sync = (unsigned*)workspace; a.xchg = (char*)workspace + xoff;
-    a.T = T; a.B = B; a.ncl = B / 32; a.kp = keep_prob; a.allow_local = getenv("MNN_PERSIST_NO_LOCAL") == nullptr;
+    a.T = T; a.B = B; a.ncl = B / 32; a.kp = keep_prob; a.allow_local = mnn_persist_allow_local();
     return MNN_OK;
 }
 // njobs layers of ONE shape and flavour in one launch (see ClFwdJobs); workspaces: one lstm_rowpar workspace per job
@@ -891,7 +871,7 @@ static int cl_bwd_fill(const mnn_lstm_bwd_layer* L, int T, int B, float keep_pro
     size_t sync_bytes = 0, xoff = 0;
     mnn_rp_workspace_layout(B / 32, 512, &sync_bytes, &xoff);
     a.sync = (unsigned*)workspace; a.xchg = (char*)workspace + xoff;
-    a.T = T; a.B = B; a.ncl = B / 32; a.kp = keep_prob; a.allow_local = getenv("MNN_PERSIST_NO_LOCAL") == nullptr;
+    a.T = T; a.B = B; a.ncl = B / 32; a.kp = keep_prob; a.allow_local = mnn_persist_allow_local();
     return MNN_OK;
 }
 // dc0: NULL, or one pointer per job (each f32 [B, u] or NULL)

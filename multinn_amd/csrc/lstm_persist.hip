@@ -822,24 +822,12 @@ __global__ void pst_poison_kernel(unsigned* sync) { sync[0] = 1u; }
 // ---------------------------------------------------------------------------------------------- host side
 static bool units_ok(int u) { return u == 128 || u == 256 || u == 512; }
 
-static int cu_count() {             // of the CURRENT device
-    static int n[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (n[dev] <= 0) {
-        hipDeviceProp_t p;
-        if (hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
-        n[dev] = p.multiProcessorCount;
-    }
-    return n[dev];
-}
-
 // G row-tile groups x (nb1 + nb2) members, R row tiles per workgroup; false when the grid cannot be resident at once.
 static bool persist_plan(int B, int u1, int u2, int& nrt, int& G, int& R) {
     if (!units_ok(u1) || !units_ok(u2) || B <= 0) return false;
     const int nm = u1 / 32 + u2 / 32;
     if (nm > 32) return false;
-    const int cus = cu_count();
+    const int cus = mnn_cu_count();
     if (cus < nm) return false;
     nrt = cdiv(B, 32);
     const int gmax = cus / nm;
@@ -920,7 +908,7 @@ extern "C" int mnn_lstm2_persist_fwd(mnn_stream_t s, int T, int B, const mnn_lst
     const int u1 = L1->units, u2 = L2->units;
     a.l1 = fwd_layer(L1); a.l2 = fwd_layer(L2);
     a.T = T; a.B = B; a.kp = keep_prob; a.sync = (unsigned*)workspace;
-    a.xcc_off = PST_FLAGS_OFF + 32 * a.nrt; a.allow_local = getenv("MNN_PERSIST_NO_LOCAL") == nullptr;
+    a.xcc_off = PST_FLAGS_OFF + 32 * a.nrt; a.allow_local = mnn_persist_allow_local();
     a.sticky_off = (int)(sticky_offset(a.nrt, L1->units, L2->units) / sizeof(unsigned));   // the aborting workgroup sets it; never re-zeroed
     const size_t per = (size_t)T * a.nrt;
     char* edge = (char*)workspace + sync_words(a.nrt) * sizeof(unsigned);
@@ -929,7 +917,7 @@ extern "C" int mnn_lstm2_persist_fwd(mnn_stream_t s, int T, int B, const mnn_lst
     a.l1.hx = x; a.l1.yx = x + per * 64 * u1; a.l2.hx = x + per * 128 * u1; a.l2.yx = nullptr;    // layer 2's dropped output is not handed off
     const int grid = a.G * (u1 / 32 + u2 / 32);
     MNN_HIP(mnn_zero_async(workspace, sync_words(a.nrt) * sizeof(unsigned) + edge_bytes(a.nrt, u1, u2, false), st));
-    if (getenv("MNN_PERSIST_TEST_ABORT")) hipLaunchKernelGGL(pst_poison_kernel, dim3(1), dim3(1), 0, st, (unsigned*)workspace);   // tests: exercise the give-up path
+    if (mnn_switch_set(MNN_SW_PERSIST_TEST_ABORT)) hipLaunchKernelGGL(pst_poison_kernel, dim3(1), dim3(1), 0, st, (unsigned*)workspace);   // tests: exercise the give-up path
     if (L1->h0 || L2->h0)
         hipLaunchKernelGGL(pst_fill_h0_kernel, dim3(a.nrt, u1 / 16 + u2 / 16), dim3(64), 0, st, (const bf16_t*)L1->h0, u1, edge,
                            (const bf16_t*)L2->h0, u2, edge + (size_t)a.nrt * 64 * u1, B);
@@ -974,7 +962,7 @@ extern "C" int mnn_lstm2_persist_bwd(mnn_stream_t s, int T, int B, const mnn_lst
     const int u1 = L1->units, u2 = L2->units;
     a.l1 = bwd_layer(L1); a.l2 = bwd_layer(L2);
     a.T = T; a.B = B; a.kp = keep_prob; a.sync = (unsigned*)workspace;
-    a.xcc_off = PST_FLAGS_OFF + 32 * a.nrt; a.allow_local = getenv("MNN_PERSIST_NO_LOCAL") == nullptr;
+    a.xcc_off = PST_FLAGS_OFF + 32 * a.nrt; a.allow_local = mnn_persist_allow_local();
     a.sticky_off = (int)(sticky_offset(a.nrt, L1->units, L2->units) / sizeof(unsigned));   // the aborting workgroup sets it; never re-zeroed
     const size_t per = (size_t)T * a.nrt;
     char* edge = (char*)workspace + sync_words(a.nrt) * sizeof(unsigned);

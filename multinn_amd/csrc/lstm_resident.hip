@@ -607,22 +607,13 @@ static res_bwd_fn res_bwd_kernel(bool f16, bool drop) {
     return drop ? lstm_res_bwd_kernel<256, Bf16F, true> : lstm_res_bwd_kernel<256, Bf16F, false>;
 }
 static hipError_t res_prepare() {
-    static bool done[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (done[dev]) return hipSuccess;
-    for (int i = 0; i < 8; ++i) {
-        e = hipFuncSetAttribute((const void*)res_fwd_kernel(i & 1, i & 2, i & 4), hipFuncAttributeMaxDynamicSharedMemorySize, ResGeom<256>::LDS);
-        if (e != hipSuccess) return e;
-    }
-    for (int i = 0; i < 4; ++i) {
-        e = hipFuncSetAttribute((const void*)res_bwd_kernel(i & 1, i & 2), hipFuncAttributeMaxDynamicSharedMemorySize, ResBwdGeom<256>::LDS);
-        if (e != hipSuccess) return e;
-    }
-    done[dev] = true;
-    return hipSuccess;
+    static MnnPerDeviceOnce done;
+    return mnn_once_per_device(done, [] {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 8 && e == hipSuccess; ++i) e = mnn_raise_dynamic_lds((const void*)res_fwd_kernel(i & 1, i & 2, i & 4), ResGeom<256>::LDS);
+        for (int i = 0; i < 4 && e == hipSuccess; ++i) e = mnn_raise_dynamic_lds((const void*)res_bwd_kernel(i & 1, i & 2), ResBwdGeom<256>::LDS);
+        return e;
+    });
 }
 
 static int res_fwd_fill(const mnn_lstm_fwd_layer* L, int T, int B, float keep_prob, ResFwdArgs& a) {

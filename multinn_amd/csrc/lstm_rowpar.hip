@@ -1110,38 +1110,25 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-static int rp_cu_count() {          // of the CURRENT device (a process may drive several)
-    static int n[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (n[dev] <= 0) {
-        hipDeviceProp_t p;
-        if (hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
-        n[dev] = p.multiProcessorCount;
-    }
-    return n[dev];
-}
 static hipError_t rp_prepare_device();
 static bool rp_units_ok(int u) { return u == 128 || u == 256 || u == 512; }
 // G row-tile groups x U/32 workgroups; every workgroup's waves own one row tile each (at most `maxw`): false when that does not cover B
 static bool rp_plan(int B, int U, bool bwd, int& nrt, int& G) {
     if (!rp_units_ok(U) || B <= 0 || (B % 32) != 0) return false;
-    const int cus = rp_cu_count(), nb = U / 32;
+    const int cus = mnn_cu_count(), nb = U / 32;
     if (cus < nb) return false;
     nrt = B / 32;
     G = cus / nb;
     if (G > nrt) G = nrt;
-    if (const char* e = getenv("MNN_ROWPAR_MAX_G")) G = std::max(1, std::min(G, atoi(e)));      // test hook: several row tiles per workgroup at small B
+    G = std::max(1, std::min(G, mnn_switch_int(MNN_SW_ROWPAR_MAX_G, G)));      // test hook: several row tiles per workgroup at small B
     const int tiles = (nrt + G - 1) / G;
     const int maxw = (bwd && U == 512) ? 3 : 4;     // LDS: the backward tile buffers are 10 KiB per wave next to 128 KiB of weights
     return tiles <= maxw;
 }
 // wave-pair forms: at most two row tiles per workgroup (two waves per item, four waves per workgroup)
 static bool rp_pair(int B, int U) {
-    static int off = -1;
-    if (off < 0) off = getenv("MNN_ROWPAR_NO_PAIR") != nullptr ? 1 : 0;
     int nrt, G;
-    if (off || !rp_plan(B, U, false, nrt, G)) return false;
+    if (mnn_switch_set(MNN_SW_ROWPAR_NO_PAIR) || !rp_plan(B, U, false, nrt, G)) return false;
     return (nrt + G - 1) / G <= 2;
 }
 static size_t rp_sync_bytes(int nrt) { return ((size_t)RP_FLAGS_OFF + 64 * (size_t)nrt) * sizeof(unsigned); }      // flag lines, then one XCC-id line per row-tile group
@@ -1204,25 +1191,20 @@ template <typename F> static rp_bwd_fn rp_bwd_kernel_x(int U, bool pair) {
 }
 static rp_bwd_fn rp_bwd_kernel(int U, bool pair, bool f16) { return f16 ? rp_bwd_kernel_x<Fp16F>(U, pair) : rp_bwd_kernel_x<Bf16F>(U, pair); }
 static hipError_t rp_prepare_device() {
-    static bool done[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (done[dev]) return hipSuccess;
-    const int us[3] = {128, 256, 512};
-    for (int ui = 0; ui < 3; ++ui)
-        for (int pair = 0; pair < 2; ++pair)
-            for (int f16 = 0; f16 < 2; ++f16) {
-                for (int xb = 0; xb < 2; ++xb) {
-                    e = hipFuncSetAttribute((const void*)rp_fwd_kernel(us[ui], pair, xb, f16), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rp_lds_fwd(us[ui], pair));
+    static MnnPerDeviceOnce done;
+    return mnn_once_per_device(done, [] {
+        for (int U : {128, 256, 512})
+            for (int pair = 0; pair < 2; ++pair)
+                for (int f16 = 0; f16 < 2; ++f16) {
+                    for (int xb = 0; xb < 2; ++xb) {
+                        const hipError_t e = mnn_raise_dynamic_lds((const void*)rp_fwd_kernel(U, pair, xb, f16), (int)rp_lds_fwd(U, pair));
+                        if (e != hipSuccess) return e;
+                    }
+                    const hipError_t e = mnn_raise_dynamic_lds((const void*)rp_bwd_kernel(U, pair, f16), (int)rp_lds_bwd(U, pair));
                     if (e != hipSuccess) return e;
                 }
-                e = hipFuncSetAttribute((const void*)rp_bwd_kernel(us[ui], pair, f16), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rp_lds_bwd(us[ui], pair));
-                if (e != hipSuccess) return e;
-            }
-    done[dev] = true;
-    return hipSuccess;
+        return hipSuccess;
+    });
 }
 
 extern "C" int mnn_lstm_rowpar_fwd(mnn_stream_t s, int T, int B, const mnn_lstm_fwd_layer* L, float keep_prob, void* workspace) {
@@ -1242,7 +1224,7 @@ extern "C" int mnn_lstm_rowpar_fwd(mnn_stream_t s, int T, int B, const mnn_lstm_
     a.xproj = L->xproj; a.wh_t = (const bf16_t*)L->wh_t; a.gates = (bf16_t*)L->gates; a.c = L->c; a.h = (bf16_t*)L->h; a.y = (bf16_t*)L->y; a.mask = L->mask;
     a.hT = (bf16_t*)L->hT; a.ld_hT = L->ld_hT; a.yT = (bf16_t*)L->yT; a.ld_yT = L->ld_yT;
     a.sync = (unsigned*)workspace; a.hx0 = (const char*)workspace + rp_sync_bytes(a.nrt); a.hx = (char*)workspace + rp_xchg_off(a.nrt, U);
-    a.T = T; a.B = B; a.kp = keep_prob; a.allow_local = getenv("MNN_PERSIST_NO_LOCAL") == nullptr;
+    a.T = T; a.B = B; a.kp = keep_prob; a.allow_local = mnn_persist_allow_local();
     hipLaunchKernelGGL(rp_reset_kernel, dim3(8), dim3(256), 0, st, (unsigned*)workspace, (int)(rp_sync_bytes(a.nrt) / sizeof(unsigned)));
     MNN_HIP(mnn_zero_async((char*)workspace + rp_sync_bytes(a.nrt), rp_edge_bytes(a.nrt, U), st));
     const int grid = a.G * (U / 32);
@@ -1268,7 +1250,7 @@ extern "C" int mnn_lstm_rowpar_bwd(mnn_stream_t s, int T, int B, const mnn_lstm_
     a.dh_ext = L->dh_ext; a.wh_p = (const bf16_t*)L->wh_p; a.gates = (const bf16_t*)L->gates; a.c = L->c; a.mask = L->mask;
     a.dzc = (bf16_t*)L->dz_T; a.dzT = (bf16_t*)L->dzT_t; a.ld_t = L->ld_t; a.db_p = L->db_p;
     a.sync = (unsigned*)workspace; a.dzx0 = (const char*)workspace + rp_sync_bytes(a.nrt); a.dzx = (char*)workspace + rp_xchg_off(a.nrt, U);
-    a.T = T; a.B = B; a.kp = keep_prob; a.allow_local = getenv("MNN_PERSIST_NO_LOCAL") == nullptr;
+    a.T = T; a.B = B; a.kp = keep_prob; a.allow_local = mnn_persist_allow_local();
     hipLaunchKernelGGL(rp_reset_kernel, dim3(8), dim3(256), 0, st, (unsigned*)workspace, (int)(rp_sync_bytes(a.nrt) / sizeof(unsigned)));
     MNN_HIP(mnn_zero_async((char*)workspace + rp_sync_bytes(a.nrt), rp_edge_bytes(a.nrt, U), st));
     const int grid = a.G * (U / 32);

@@ -328,7 +328,7 @@ extern "C" int mnn_nade_logprob_fwd_gated(mnn_stream_t s, int tracks, int N, int
 #define FWD(HQ, UT) hipLaunchKernelGGL((nade_fwd_kernel<HQ, UT>), grid, dim3(512), 0, st, tracks, N, D, Hn, v, v_track_stride, bias, ld_bias, w_enc, \
                                        w_dec, row_weight, nll, cond_p, d_bias, a_final, gate, run_if, n_rows_dev, unsafe)
     if (unsafe != nullptr) MNN_HIP(mnn_zero_async(unsafe, sizeof(int), sizeof(int), 1, st));      // counted by the launch below (a fill KERNEL: common.h on memset nodes)
-    static const bool no_ut = getenv("MNN_NADE_FWD_NO_UT") != nullptr;          // (tests: the direct form as the comparison partner)
+    const bool no_ut = mnn_switch_set(MNN_SW_NADE_FWD_NO_UT);                   // (tests: the direct form as the comparison partner)
     if (Hn <= 64) FWD(1, false);
     else if (Hn <= 128) FWD(2, false);
     else if (gate != nullptr && run_if == 1 && !no_ut) FWD(4, true);
@@ -1241,18 +1241,17 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
 }
 
 static hipError_t sample_chunk_raise_lds() {                 // the ring + a row's scratch pass the 64 KB default of dynamic LDS
-    static bool raised_[64];
-    bool& raised = mnn_dev_flag(raised_);
-    if (raised) return hipSuccess;
-    hipError_t e = hipSuccess;
-#define RAISE1(TM, FU, GV) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&nade_sample_chunk_kernel<TM, FU, 8, GV>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); \
-                           if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&nade_sample_chunk_kernel<TM, FU, 16, GV>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)
+    static MnnPerDeviceOnce raised;
+    return mnn_once_per_device(raised, [] {
+        hipError_t e = hipSuccess;
+#define RAISE1(TM, FU, GV) if (e == hipSuccess) e = mnn_raise_dynamic_lds(reinterpret_cast<const void*>(&nade_sample_chunk_kernel<TM, FU, 8, GV>), 128 * 1024); \
+                           if (e == hipSuccess) e = mnn_raise_dynamic_lds(reinterpret_cast<const void*>(&nade_sample_chunk_kernel<TM, FU, 16, GV>), 128 * 1024)
 #define RAISE(TM, FU) RAISE1(TM, FU, false); RAISE1(TM, FU, true)
-    RAISE(0, true); RAISE(1, true); RAISE(2, true); RAISE(0, false); RAISE(1, false); RAISE(2, false);
+        RAISE(0, true); RAISE(1, true); RAISE(2, true); RAISE(0, false); RAISE(1, false); RAISE(2, false);
 #undef RAISE
 #undef RAISE1
-    raised = e == hipSuccess;
-    return e;
+        return e;
+    });
 }
 
 // GV: some job carries codes (SampleJob.given) -- the GIVEN instantiations; without any, the launch is the unconditioned one
@@ -1260,13 +1259,13 @@ static hipError_t sample_chunk_raise_lds() {                 // the ring + a row
 template <bool GV>
 static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, int tmode, const SampleTemps& TT, uint32_t row0, uint32_t sub,
                            long s_row_stride, int s_elem_stride) {
-    bool chunked = Hn % 4 == 0 && Hn >= 4 && getenv("MNN_SAMPLE_NO_CHUNK") == nullptr;      // (read per call: tests compare the two forms)
+    bool chunked = Hn % 4 == 0 && Hn >= 4 && !mnn_switch_set(MNN_SW_SAMPLE_NO_CHUNK);      // (tests compare the two forms)
     for (int j = 0; j < njobs && chunked; ++j) chunked = (((uintptr_t)J.job[j].w_enc | (uintptr_t)J.job[j].w_dec) & 15) == 0;
     const size_t gbytes = GV ? (size_t)((D + 3) & ~3) : 0;   // the row's codes
     const size_t tbytes = tmode == 2 ? SAMPLE_MAX_JOBS * sizeof(float) : 0;     // the temperatures
     if (chunked) {                                           // eight visibles per pass, one wave per row
         // sixteen visibles per pass while every row has a CU of its own (96 KB of ring: one workgroup per CU); eight with more rows than that
-        const int g = (long)N * njobs <= 256 && !getenv("MNN_SAMPLE_G8") ? 16 : 8;
+        const int g = (long)N * njobs <= 256 && !mnn_switch_set(MNN_SW_SAMPLE_G8) ? 16 : 8;
         const size_t ldc = (size_t)sch_nb(g) * 2 * g * 1024 + (size_t)9 * ((D + 3) & ~3) + 1024 + gbytes + tbytes;     // <= 96 KB + 15 KB + 1 KB (D <= 1536)
         MNN_HIP(sample_chunk_raise_lds());
 #define SMC(TM, FU) do { if (g == 16) hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 16, GV>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride); \
@@ -1280,7 +1279,7 @@ static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N
     dim3 grid(cdiv(N, 4), njobs);
     const size_t lds = (size_t)36 * ((D + 3) & ~3) + 4096 + 4 * gbytes + tbytes;     // 4 waves x ((2 f32 + u8 (+ u8 code)) per visible + 256 uniforms): <= 64 KB
 #define SMP(TM, FU, SP) hipLaunchKernelGGL((nade_sample_kernel<TM, FU, SP, GV>), grid, dim3(256), lds, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride)
-    if (Hn == 256 && tmode == 1) { if (getenv("MNN_SAMPLE_NO_SPEC")) SMP(1, true, false); else SMP(1, true, true); }
+    if (Hn == 256 && tmode == 1) { if (mnn_switch_set(MNN_SW_SAMPLE_NO_SPEC)) SMP(1, true, false); else SMP(1, true, true); }
     else if (Hn == 256) { if (tmode == 0) SMP(0, true, false); else SMP(2, true, false); }
     else { if (tmode == 0) SMP(0, false, false); else if (tmode == 1) SMP(1, false, false); else SMP(2, false, false); }
 #undef SMP

@@ -506,14 +506,8 @@ static int nm_launch(mnn_stream_t s, int tracks, int N, int D, int Hn, const uin
     MNN_REQUIRE(ld_bias >= tracks * (Hn + D), "mnn_nade_logprob_fwd_mfma: ld_bias %d < tracks*(Hn+D)", ld_bias);
     MNN_REQUIRE(d_bias == nullptr || row_weight != nullptr, "mnn_nade_logprob_fwd_mfma: d_bias needs row_weight");
     MNN_REQUIRE(((uintptr_t)w_dec16 & 15) == 0, "mnn_nade_logprob_fwd_mfma: the 16-bit decoder weights must be 16-byte aligned");
-    static bool attr_set[64];
-    int dev = 0;
-    MNN_HIP(hipGetDevice(&dev));
-    MNN_REQUIRE(dev >= 0 && dev < 64, "mnn_nade_logprob_fwd_mfma: device index %d", dev);
-    if (!attr_set[dev]) {
-        MNN_HIP(hipFuncSetAttribute((const void*)nade_fwd_mfma_kernel<SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(NadeFwdSmemT<SPLIT>)));
-        attr_set[dev] = true;
-    }
+    static MnnPerDeviceOnce raised;                            // (per SPLIT: this function is instantiated once per form)
+    MNN_HIP(mnn_once_per_device(raised, [] { return mnn_raise_dynamic_lds((const void*)nade_fwd_mfma_kernel<SPLIT>, (int)sizeof(NadeFwdSmemT<SPLIT>)); }));
     dim3 grid(cdiv(N, 32), tracks);
     hipLaunchKernelGGL(nade_fwd_mfma_kernel<SPLIT>, grid, dim3(256), sizeof(NadeFwdSmemT<SPLIT>), (hipStream_t)s, tracks, N, D, v, v_track_stride, bias,
                        ld_bias, w_enc, (const bf16_t*)w_dec16, row_weight, nll, cond_p, d_bias, a_final, gate, run_if, n_rows_dev);

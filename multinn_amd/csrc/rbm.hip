@@ -164,19 +164,14 @@ static int launch_half(hipStream_t st, int N, int K, int n_out, const void* in, 
     // matrix-core form for SAMPLING half-steps of training batches (DBN encode / decode: its accumulator layout gives every Philox block to one
     // lane); a probabilities-only pass (the free-energy gradient's hidden activations) stays on the vector kernel, whose stores are
     // coalesced -- measured at [32768, 88 -> 256]: 0.11 ms vector vs 0.19 ms matrix-core per call
-    if (N >= 2048 && s_out != nullptr && half_mfma_lds_bytes(K, n_out) <= 158 * 1024 && getenv("MNN_RBM_NO_MFMA") == nullptr) {
-        static bool raised_[64];
-        bool& raised = mnn_dev_flag(raised_);
-        if (!raised) {
-            MNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rbm_half_mfma_kernel<uint8_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            MNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rbm_half_mfma_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            raised = true;
-        }
+    if (N >= 2048 && s_out != nullptr && half_mfma_lds_bytes(K, n_out) <= 158 * 1024 && !mnn_switch_set(MNN_SW_RBM_NO_MFMA)) {
+        static MnnPerDeviceOnce raised;
+        MNN_HIP(mnn_once_per_device(raised, [] {
+            const hipError_t e = mnn_raise_dynamic_lds(reinterpret_cast<const void*>(&rbm_half_mfma_kernel<uint8_t>), 160 * 1024);
+            return e != hipSuccess ? e : mnn_raise_dynamic_lds(reinterpret_cast<const void*>(&rbm_half_mfma_kernel<float>), 160 * 1024);
+        }));
         const size_t l2 = half_mfma_lds_bytes(K, n_out);
-        int dev = 0, cus = 256;
-        MNN_HIP(hipGetDevice(&dev));
-        MNN_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        const int grid = min(cdiv(N, GM_ROWS), max(cus, 1));        // one workgroup per CU walks the row tiles
+        const int grid = min(cdiv(N, GM_ROWS), max(mnn_cu_count(), 1));        // one workgroup per CU walks the row tiles
         if (in_dtype == MNN_U8)
             hipLaunchKernelGGL(rbm_half_mfma_kernel<uint8_t>, dim3(grid), dim3(512), l2, st, N, K, n_out, (const uint8_t*)in, Wk, ldw, b, ld_b,
                                stream_id, seed, row0, sub, p_out, s_out);

@@ -476,7 +476,7 @@ extern "C" int mnn_transpose(mnn_stream_t s, const void* in, int in_dtype, int R
 static size_t ais_lw_bytes(int N, int S) { return ((size_t)N * (size_t)S * sizeof(double) + 255) & ~(size_t)255; }
 
 // the form of a shape (not of N or S: a row's chains are the same bits whatever else is in the launch)
-static bool ais_use_mfma(int D, int Hn) { return Hn >= 32 && ais_mfma_lds_bytes(D, Hn) <= 158 * 1024 && getenv("MNN_RBM_NO_MFMA") == nullptr; }
+static bool ais_use_mfma(int D, int Hn) { return Hn >= 32 && ais_mfma_lds_bytes(D, Hn) <= 158 * 1024 && !mnn_switch_set(MNN_SW_RBM_NO_MFMA); }
 
 extern "C" size_t mnn_rbm_ais_workspace_bytes(int N, int D, int Hn, int n_chains, int n_betas) {
     (void)n_betas;
@@ -506,16 +506,15 @@ static int ais_launch(const char* what, mnn_stream_t s, int N, int D, int Hn, in
     hipStream_t st = (hipStream_t)s;
     double* lw = reinterpret_cast<double*>(workspace);
     AisArgs a{N, D, Hn, n_chains, n_betas, betas, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, lw, v_out, v_data, given, ld_given};
-    static bool raised_[64];
-    bool& raised = mnn_dev_flag(raised_);
-    if (!raised) {
+    static MnnPerDeviceOnce raised;
+    MNN_HIP(mnn_once_per_device(raised, [] {
+        hipError_t e = hipSuccess;
         for (auto* f : {&rbm_ais_mfma_kernel, &rbm_raise_mfma_kernel, &rbm_given_ais_mfma_kernel, &rbm_given_raise_mfma_kernel})
-            MNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            if (e == hipSuccess) e = mnn_raise_dynamic_lds(reinterpret_cast<const void*>(f), 160 * 1024);
         for (auto* f : {&rbm_ais_stream_kernel, &rbm_raise_stream_kernel, &rbm_given_ais_stream_kernel, &rbm_given_raise_stream_kernel})
-            MNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        160 * 1024 - (int)AIS_STREAM_STATIC_LDS));
-        raised = true;
-    }
+            if (e == hipSuccess) e = mnn_raise_dynamic_lds(reinterpret_cast<const void*>(f), 160 * 1024 - (int)AIS_STREAM_STATIC_LDS);
+        return e;
+    }));
     // the form is the shape's, whatever `given` is: the codes fit the LDS the form's choice leaves free
     if (mfma) {
         auto* f = given != nullptr ? (reverse ? rbm_given_raise_mfma_kernel : rbm_given_ais_mfma_kernel) : (reverse ? rbm_raise_mfma_kernel : rbm_ais_mfma_kernel);

@@ -571,14 +571,10 @@ extern "C" int mnn_transpose(mnn_stream_t s, const void* in, int in_dtype, int R
 // (nothing launched) when that is refused.
 template <auto KERNEL, typename Args>
 static bool gibbs_launch(hipStream_t st, const Args& A, int rows, int threads, size_t lds) {
-    static bool raised_[64];
-    bool& raised = mnn_dev_flag(raised_);
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        raised = true;
+    static MnnPerDeviceOnce raised;
+    if (mnn_once_per_device(raised, [] { return mnn_raise_dynamic_lds(reinterpret_cast<const void*>(KERNEL), 160 * 1024); }) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
     }
     hipLaunchKernelGGL(KERNEL, dim3(cdiv(A.N, rows), A.jobs()), dim3(threads), lds, st, A);
     return true;
@@ -592,7 +588,7 @@ static int rbm_gibbs_forms(const char* who, mnn_stream_t s, Args& A, void* works
     const size_t codes_lds = GIVEN ? (size_t)RBM_R * ((D + 3) & ~3) : 0;
     MNN_REQUIRE(rbm_lds_bytes(D, Hn) + codes_lds <= 160 * 1024, "%s: D+Hn too large for LDS", who);
     hipStream_t st = (hipStream_t)s;
-    if (N < 2048 && Hn <= 256 && D <= 256 && rbm_lds_resident_bytes(2, D, Hn) <= 158 * 1024 && getenv("MNN_RBM_STREAM_W") == nullptr) {
+    if (N < 2048 && Hn <= 256 && D <= 256 && rbm_lds_resident_bytes(2, D, Hn) <= 158 * 1024 && !mnn_switch_set(MNN_SW_RBM_STREAM_W)) {
         // sampling-sized batches: W resident in LDS, two rows per workgroup (one workgroup per CU: at training sizes -- 32 768 rows --
         // the streaming kernel's eight rows per workgroup and several workgroups per CU win, 1.5 vs 2.5 ms; round 3: also with the workgroup
         // walking over its row groups so that W is loaded once, 4.9 ms -- two rows per pass are two dependent fma chains per thread at one
@@ -607,7 +603,7 @@ static int rbm_gibbs_forms(const char* who, mnn_stream_t s, Args& A, void* works
             return MNN_OK;
         }
     }
-    if (gibbs_mfma_lds_bytes(D, Hn) <= 158 * 1024 && getenv("MNN_RBM_NO_MFMA") == nullptr) {
+    if (gibbs_mfma_lds_bytes(D, Hn) <= 158 * 1024 && !mnn_switch_set(MNN_SW_RBM_NO_MFMA)) {
         // training batches: the chain on the f32 matrix cores, 64 rows per workgroup (same draws: see rbm_gibbs_mfma_body)
         MNN_REQUIRE((gibbs_launch<&rbm_gibbs_mfma_kernel<Args, GIVEN>>(st, A, GM_ROWS, 512, gibbs_mfma_lds_bytes(D, Hn))), "%s: cannot raise the dynamic LDS limit", who);
         MNN_LAUNCH_CHECK();

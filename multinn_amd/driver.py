@@ -15,6 +15,8 @@ import time
 
 import numpy as np
 
+from .switches import flag
+
 
 class LossAccumulator:
     """Running mean of the per-batch losses of an epoch that keeps non-finite values OUT of the mean and tallies them by kind (the
@@ -140,9 +142,8 @@ def _captured_step(generator, xb, optimizer, lr, max_graphs=8, lengths=None):
     RAGGED windows (lengths given) get their own graph beside the full-length one of the same shape, which skips the compaction passes:
     ONE graph per window shape serves any lengths (the reference's data is ragged, train.py:165-173).  MULTINN_TRAIN_GRAPH=0 keeps every
     step eager."""
-    import os
     ragged = lengths is not None
-    if os.environ.get("MULTINN_TRAIN_GRAPH", "1") == "0" or not xb.is_cuda or not hasattr(generator, "capturable") \
+    if not flag("MULTINN_TRAIN_GRAPH") or not xb.is_cuda or not hasattr(generator, "capturable") \
             or not generator.capturable(tuple(xb.shape), ragged):
         return None
     key = (tuple(xb.shape), id(optimizer), lr, "ragged" if ragged else "full")

@@ -12,13 +12,13 @@ rows past ``lengths`` are masked by a zero row weight instead of being gathered 
 import abc
 import collections
 import math
-import os
 
 import weakref
 
 import torch
 
 from . import ops
+from .switches import flag, value
 from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, given_codes, given_mask_tracks, sampling_temperature, temperature_key, glorot_uniform, zeros_init, default_device, capture_train_step
 from .training import compute_gradients, world, dp_active, AdamOptimizer
 from ._lib import MnnUnsupported
@@ -352,7 +352,7 @@ class RnnEstimator(Generator):
     # and conditional is a fixed sequence of IEEE operations that the tests' C checker restates, so a whole scan is checked bit for bit
     # (BASELINE.json: "bit-exact for Bernoulli sampling indices under a fixed RNG").  MULTINN_DET_SAMPLING=0 restores the throughput
     # kernels (hardware exp2 / rcp activations, packed 16-bit weights), whose scans can only be checked to a tolerance.
-    det_sampling = os.environ.get("MULTINN_DET_SAMPLING", "1") != "0"
+    det_sampling = flag("MULTINN_DET_SAMPLING")
 
     def steps(self, inputs, initial_state=None):
         """rnn_estimator.py:237-252: run the RNN over `inputs` [B,T,Din] and return the state after the last step."""
@@ -605,9 +605,9 @@ class RnnNade(RnnEstimator):
         o = self.store.offset("nade/b_enc")
         return flat[o:o + self.n_out]
 
-    nade_mfma = os.environ.get("MULTINN_NADE_MFMA", "1") != "0"
+    nade_mfma = flag("MULTINN_NADE_MFMA")
 
-    nade_dense_above = float(os.environ.get("MULTINN_NADE_DENSE_ABOVE", "0.07"))   # density above which the f32 scan replaces the matrix-core form
+    nade_dense_above = value("MULTINN_NADE_DENSE_ABOVE")   # density above which the f32 scan replaces the matrix-core form
 
     def _nade_fwd(self, v, out, rw, nll, cond_p, d_out, a_fin, n_rows_dev=None, unsafe=None):
         M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
@@ -623,7 +623,7 @@ class RnnNade(RnnEstimator):
                                          n_rows_dev=n_rows_dev, unsafe=unsafe)
 
     # fp16 mode: the split-operand matrix-core scan (nade_mfma.hip, SPLIT: f16 hi + lo pairs, three 16-bit MFMA products) or the f32 vector scan
-    nade_exact = os.environ.get("MULTINN_NADE_EXACT_MFMA", "1") != "0"
+    nade_exact = flag("MULTINN_NADE_EXACT_MFMA")
 
     def _nade_mfma(self):
         """The matrix-core NADE forward is in use: bf16 mode (16-bit operands) or fp16 mode (hi + lo operand pairs, 22 bits), and a hidden width it covers;
@@ -678,8 +678,8 @@ class RnnNade(RnnEstimator):
         self._is_built = True
 
     # MULTINN_RAGGED_COMPACT=0: ragged windows keep their padding rows in the Dense + NADE part (weight 0), as before round 6
-    ragged_compact = os.environ.get("MULTINN_RAGGED_COMPACT", "1") != "0"
-    ragged_gemm_rows = os.environ.get("MULTINN_RAGGED_GEMM_ROWS", "1") != "0"     # the Dense GEMMs of a compacted window skip their padding too (ops.gemm_tn m_rows / k_rows)
+    ragged_compact = flag("MULTINN_RAGGED_COMPACT")
+    ragged_gemm_rows = flag("MULTINN_RAGGED_GEMM_ROWS")     # the Dense GEMMs of a compacted window skip their padding too (ops.gemm_tn m_rows / k_rows)
 
     def build_pianoroll(self, x_u8, lengths=None, is_train=True, mode="train", n_total_dev=None):
         """Fast joint path: x_u8 [B,T,P,M] piano-roll batch; fuses multinn_joint.py:83-89,132-139

@@ -1,12 +1,12 @@
 """LstmStack: a multi-layer LSTM on packed, gate-interleaved weights, and the drivers of its recurrence launches (drive / drive_group).
 Imported back by name into multinn_amd.generators, which every model builds on."""
 import math
-import os
 from typing import NamedTuple
 
 import torch
 
 from . import ops
+from .switches import flag, value
 
 
 # ------------------------------------------------------------------------------------------------
@@ -138,7 +138,7 @@ class LstmStack:
         blocks = sum(p["u"] // 32 for p in self.packed) * -(-max(B, 1) // 32)
         return blocks <= 512
 
-    persistent = os.environ.get("MULTINN_PERSIST", "1") != "0"   # one launch for all T steps (lstm_persist.hip) when the grid fits the device
+    persistent = flag("MULTINN_PERSIST")   # one launch for all T steps (lstm_persist.hip) when the grid fits the device
 
     # A persistent launch spins on its own workgroups and needs ALL of them resident: two such launches must never share the device.
     # A caller that runs several stacks on concurrent streams (the feedback sampling scan) clears this for its single steps, which then
@@ -155,15 +155,15 @@ class LstmStack:
     # Row-parallel persistent form (lstm_rowpar.hip): one launch per LAYER for all T steps, weights in LDS, a wave per 32-row tile.  For
     # large batches, where the two-layer form's fixed cost per 32-row item (K split over the waves, LDS reduction, workgroup barriers) is
     # paid several times per timestep: TGT [1024,256,88,5] forward 15.6 us per timestep there.
-    rowpar = os.environ.get("MULTINN_ROWPAR", "1") != "0"
-    rowpar_min_batch = int(os.environ.get("MULTINN_ROWPAR_MIN_BATCH", "512"))
+    rowpar = flag("MULTINN_ROWPAR")
+    rowpar_min_batch = value("MULTINN_ROWPAR_MIN_BATCH")
     # input projections the row-parallel form reads (bias included): stored in the 16-bit compute type by default (half the bytes of the
     # step's largest tensor), f32 with MULTINN_ROWPAR_XPROJ=f32
-    rowpar_xproj_f32 = os.environ.get("MULTINN_ROWPAR_XPROJ", "16") == "f32"
+    rowpar_xproj_f32 = value("MULTINN_ROWPAR_XPROJ") == "f32"
 
     # CU-resident form of a 256-unit layer inside the row-parallel path (lstm_resident.hip): the layer's whole recurrent matrix sits on every CU
     # and a workgroup owns four batch rows, so a timestep has no hand-off between workgroups (MULTINN_RESIDENT=0: row-parallel kernels only)
-    resident = os.environ.get("MULTINN_RESIDENT", "1") != "0"
+    resident = flag("MULTINN_RESIDENT")
 
     def _resident(self, l, B, T):
         # (the kernels address their tensors through 2 GB buffer descriptors: the saved gates [T, B, 4u] in 16 bits are the largest)
@@ -172,7 +172,7 @@ class LstmStack:
 
     # Cluster form of the same idea for a 512-unit layer (lstm_cluster.hip): eight CUs share 32 rows, each keeps 64 units' recurrent weights in
     # its registers, h[t] / dz[t] are exchanged through the XCD's L2 (MULTINN_CLUSTER=0: row-parallel kernels for that layer)
-    cluster = os.environ.get("MULTINN_CLUSTER", "1") != "0"
+    cluster = flag("MULTINN_CLUSTER")
 
     def _cluster(self, l, B, T):
         return (self.cluster and not self.rowpar_xproj_f32 and ops.lstm_cluster_ok(B, self.packed[l]["u"])
@@ -238,7 +238,7 @@ class LstmStack:
     # One weight-gradient GEMM per layer over the concatenated operand [x^T ; h_prev^T] (row-parallel form): dz^T is streamed once for dWx and
     # dWh, and 2 x 4 column tiles of a K slice share every dz^T panel on an XCD's L2 instead of 2 x 2 (layer 1 at [1024,256,88,5]: 1.33 ->
     # 1.03 ms for the pair, scratch/gemm_merge_probe.py).  The layer's forward writes h^T -- and the layer below its y^T -- into views of it.
-    merge_wgrads = os.environ.get("MULTINN_MERGE_WGRADS", "1") != "0"
+    merge_wgrads = flag("MULTINN_MERGE_WGRADS")
 
     def _cat_shape(self, l, Np):
         p = self.packed[l]
@@ -499,7 +499,7 @@ class LstmStack:
 
     # MULTINN_KBLOCK_WGRADS=0: dz^T as a plain [4u, N] matrix instead of the K-blocked layout.  (A third form -- no dz^T at all, the GEMM reading
     # dz row-major through transposing LDS loads -- was measured net-neutral in round 3, profiles/round3_e_kmajor.md, and removed in round 4.)
-    kblock_wgrads = os.environ.get("MULTINN_KBLOCK_WGRADS", "1") != "0"
+    kblock_wgrads = flag("MULTINN_KBLOCK_WGRADS")
 
     def _weight_grads(self, l, cx, dzT, db_p, T, B, dz=None):
         """dWx^T[4u,ld] = dz^T . inp ; dWh^T[4u,u] = dz^T . h_prev  (reduction over the N rows); dzT [4u,Np] and

@@ -29,6 +29,7 @@ from .common import Model, capture_train_step, given_codes, given_tracks, sampli
 from .encoders import PassEncoder, DBNEncoder
 from .generators import RnnNade, RnnRBM, RnnMultiNADE, RnnMultiRBM
 from . import ops
+from .switches import flag
 from ._lib import MnnUnsupported
 from .training import compute_gradients_multi, world
 
@@ -759,7 +760,7 @@ class MultINNJamming(MultIEncoderNN):
     # backward passes run in LOCKSTEP (generators.drive_group), so that the same layer's recurrence of all tracks is ONE launch of the
     # CU-resident / cluster kernels (five tracks x 256 rows fill the chip; one track alone keeps 64 CUs busy).  MULTINN_JAMMING_GROUP=0: one
     # generator after the other, each on the two-layer persistent form.
-    group_generators = os.environ.get("MULTINN_JAMMING_GROUP", "1") != "0"
+    group_generators = flag("MULTINN_JAMMING_GROUP")
 
     def _grouped(self, mode):
         """True when the generators' recurrences can share launches: a train / eval build of >= 2 like generators in a 16-bit mode whose stacks

@@ -4,12 +4,12 @@
 buffer of a ParamStore, with ONE all-reduce of that buffer when torch.distributed is initialised
 (backend "nccl" is RCCL over xGMI on ROCm; "gloo" in CPU tests).
 """
-import os
 
 import torch
 import torch.distributed as dist
 
 from . import ops
+from .switches import flag, value
 
 
 class AdamOptimizer:
@@ -37,7 +37,7 @@ def dp_active():
     process group (a 1-rank RCCL rehearsal of exactly the N>1 code path on a one-GPU box)."""
     if not (dist.is_available() and dist.is_initialized()):
         return False
-    return dist.get_world_size() > 1 or os.environ.get("MULTINN_DP_REHEARSAL") == "1"
+    return dist.get_world_size() > 1 or flag("MULTINN_DP_REHEARSAL")
 
 
 class CabiComm:
@@ -84,7 +84,7 @@ def setup_cabi_comm():
     not run inside a hipGraph capture, which is where the first all-reduce of a graphed step would otherwise create it.  Idempotent; the
     communicator is destroyed at interpreter exit."""
     global _CABI_COMM
-    if _CABI_COMM is None and dp_active() and os.environ.get("MULTINN_COMM") == "capi" and torch.cuda.is_available():
+    if _CABI_COMM is None and dp_active() and value("MULTINN_COMM") == "capi" and torch.cuda.is_available():
         import atexit
         _CABI_COMM = CabiComm(dist.get_rank(), dist.get_world_size())
         atexit.register(lambda: _CABI_COMM is not None and _CABI_COMM.close())
@@ -96,7 +96,7 @@ def allreduce_flat(grad):
     default; MULTINN_COMM=capi issues the same RCCL all-reduce through the library's own entry points (CabiComm)."""
     global _CABI_COMM
     if dp_active():
-        if os.environ.get("MULTINN_COMM") == "capi" and grad.is_cuda:
+        if value("MULTINN_COMM") == "capi" and grad.is_cuda:
             if _CABI_COMM is None:
                 if torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("MULTINN_COMM=capi: call training.setup_cabi_comm() before capturing a step (the communicator cannot be created inside a capture)")
