@@ -406,6 +406,14 @@ typedef struct {
 int mnn_nade_sample_temps(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
                           const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
                           long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given);
+/* mnn_nade_sample_temps with a sub-counter base that the kernel reads ON THE DEVICE: sub_base is NULL (mnn_nade_sample_temps, which calls this:
+ * the same launches and bits) or points at one u32, and every draw of the launch uses the Philox sub-counter sub + *sub_base (mod 2^32).  The
+ * cell holds the generated steps before a generation session's chunk: a launch captured in a hipGraph then continues the piece wherever the
+ * cell says, the way mnn_rbm_gibbs_stepped follows the optimiser's step.  The cell is written from the host side of the stream only (a fill
+ * ordered before the launch); every sampling kernel reads it once, a wave-uniform load in front of its scan. */
+int mnn_nade_sample_temps_at(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
+                             const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
+                             long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given, const uint32_t* sub_base);
 /* mnn_nade_sample for SEVERAL single-NADE generators in ONE launch (multinn_feedback.py:196: every per-track generator's sample_single in a
  * step of the feedback scan).  `jobs`: HOST array of 1..8 descriptors (passed to the kernel by value): the generator's Dense output matrix
  * bias [N, ld_bias] (b_enc at column 0, b_dec at column Hn), its weights [D, Hn], its Philox seed and where its samples go
@@ -447,6 +455,12 @@ int mnn_rbm_gibbs(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0
 int mnn_rbm_gibbs_temp(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
                        const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0,
                        float* p_v, uint8_t* v_out, void* workspace, const uint8_t* given, int ld_given, float temperature);
+/* mnn_rbm_gibbs_temp with a sub-counter base read ON THE DEVICE (sub_base: NULL = mnn_rbm_gibbs_temp, the same launches and bits; or one u32,
+ * the generated steps before this launch -- a generation session's step cell): iteration `it` of the chain draws with the sub-counter
+ * sub0 + *sub_base * max(k, 1) + it, a generated step owning max(k, 1) of them.  Every form of the chain applies it where it applies seed_step. */
+int mnn_rbm_gibbs_at(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
+                     const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0,
+                     float* p_v, uint8_t* v_out, void* workspace, const uint8_t* given, int ld_given, float temperature, const uint32_t* sub_base);
 /* The same chain with the step counter of the optimiser read ON THE DEVICE: effective seed = seed + *seed_step (NULL: seed).  A launch
  * captured in a hipGraph then draws new uniforms at every replay, like the dropout masks (mnn_dropout_mask's step pointer); the
  * reference re-runs its random ops at every sess.run (rbm.py:222-226).  Unconditioned (training's CD-k chain). */
@@ -489,6 +503,10 @@ int mnn_rbm_gibbs_multi(mnn_stream_t s, int njobs, const mnn_rbm_gibbs_job* jobs
 int mnn_rbm_gibbs_multi_temps(mnn_stream_t s, int njobs, const mnn_rbm_gibbs_job* jobs, int N, int D, int Hn, int k, int ld_bh, int ld_bv,
                               uint32_t row0, const uint32_t* row_ids, uint32_t sub0, const int* seed_step, long row_stride, int elem_stride,
                               long given_row_stride, void* workspace, const float* temps);
+/* ... and with mnn_rbm_gibbs_at's sub-counter base (NULL: mnn_rbm_gibbs_multi_temps, which calls this), shared by the jobs. */
+int mnn_rbm_gibbs_multi_at(mnn_stream_t s, int njobs, const mnn_rbm_gibbs_job* jobs, int N, int D, int Hn, int k, int ld_bh, int ld_bv,
+                           uint32_t row0, const uint32_t* row_ids, uint32_t sub0, const int* seed_step, long row_stride, int elem_stride,
+                           long given_row_stride, void* workspace, const float* temps, const uint32_t* sub_base);
 typedef struct {
     const uint8_t* v;
     const float* W;
@@ -686,6 +704,21 @@ int mnn_generate_scan_temps(mnn_stream_t s, int B, int n_intro, int num_steps, c
                             const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D, int Hn,
                             const float* w_enc, const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint8_t* samples,
                             void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0, const float* const* h0);
+/* One CHUNK of a generation session: mnn_generate_scan_temps whose state flows in and out and whose step counter has a base.
+ *   n_intro >= 0, num_steps >= 0, one of them > 0.  n_intro == 0: c_in / h_in are required and the first Dense is formed from h_in[last
+ *   layer]; n_intro > 0 with num_steps == 0 is the intro pass alone (how a session opens; samples may be NULL).
+ *   c_in / h_in: as c0 / h0 above (both NULL: the zero state).  c_out / h_out (both NULL, or arrays of n_layers f32 [B, u]): the state behind
+ *   the last step, copied on the stream after the last launch that reads c_in / h_in -- they may be the very arrays of c_in / h_in.  The Dense
+ *   output is not an output: the next chunk forms it again from h_in[last layer], the same product, the same bits.
+ *   step0, step_base (NULL, or one u32 on the device -- mnn_nade_sample_temps_at): generated step st draws with the sub-counter
+ *   step0 + *step_base + st.  samples / given: [B, num_steps, n_in] of THIS chunk.
+ * Everything else, bits included, is mnn_generate_scan_temps: chunks of n_1 + .. + n_k steps from one intro, chunk i at base n_1 + .. +
+ * n_(i-1), emit what one call of n steps emits. */
+int mnn_generate_scan_chunk(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                            const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D, int Hn,
+                            const float* w_enc, const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint8_t* samples,
+                            void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c_in, const float* const* h_in,
+                            float* const* c_out, float* const* h_out, uint32_t step0, const uint32_t* step_base);
 
 /* ------------------------------------------------------------------------------------------
  * Data-parallel exchange (the gradients of utils/training.py:151-177 as ONE flat f32 buffer): RCCL over xGMI, one

@@ -179,6 +179,11 @@ SIGNATURES["mnn_generate_scan_temps"] = (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p
                                               C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)])
 SIGNATURES["mnn_rbm_gibbs_temp"] = (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _u64, _u32, _p, _u32, _p, _p, _p, _p, _i, _f])
 SIGNATURES["mnn_rbm_gibbs_multi_temps"] = (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _u32, _p, _u32, _p, _l, _i, _l, _p, C.POINTER(C.c_float)])
+# generation sessions (additions without a version bump): a sub-counter base read on the device, and the scan as a chunk with state in and out
+SIGNATURES["mnn_nade_sample_temps_at"] = (_i, SIGNATURES["mnn_nade_sample_temps"][1] + [_p])
+SIGNATURES["mnn_rbm_gibbs_at"] = (_i, SIGNATURES["mnn_rbm_gibbs_temp"][1] + [_p])
+SIGNATURES["mnn_rbm_gibbs_multi_at"] = (_i, SIGNATURES["mnn_rbm_gibbs_multi_temps"][1] + [_p])
+SIGNATURES["mnn_generate_scan_chunk"] = (_i, SIGNATURES["mnn_generate_scan_temps"][1] + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _u32, _p])
 TEMPS_MAX = 8              # MNN_TEMPS_MAX
 
 _lib = None

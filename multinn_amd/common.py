@@ -661,10 +661,10 @@ class RBM(Model):
         ops.rbm_visible(hh.contiguous(), self.W, bv, stream, self.seed if seed is None else seed, row0, sub, p, v)
         return p, v
 
-    def sample(self, v, bh=None, bv=None, k=None, seed=None, row0=0, row_ids=None, sub0=0, given=None, temperature=1.0):
+    def sample(self, v, bh=None, bv=None, k=None, seed=None, row0=0, row_ids=None, sub0=0, given=None, temperature=1.0, sub_base=None):
         """rbm.py:192-231; k=None -> self.k (R1).  Returns (p_v, v_sample u8).  given (optional): codes u8 [N, D] (ops.rbm_gibbs) -- the
         clamped chain: v_sample equals the code at every clamped visible, the free ones are sampled conditioned on all of them.
-        temperature: the chain of exp(-E / T); p_v is then the tempered probability."""
+        temperature: the chain of exp(-E / T); p_v is then the tempered probability.  sub_base: ops.rbm_gibbs's (a session's step cell)."""
         temperature = sampling_temperature(temperature, allow_none=False, allow_sequence=False)
         k = self._k if k is None else k
         bh = bh if bh is not None else self.bh
@@ -673,7 +673,7 @@ class RBM(Model):
         p_v = torch.empty((N, D), device=v.device)
         v_s = torch.empty((N, D), device=v.device, dtype=torch.uint8)
         ops.rbm_gibbs(v.to(torch.uint8).contiguous(), self.W, bh, bv, k, self.seed if seed is None else seed, row0, row_ids, sub0, p_v, v_s,
-                      given=given, temperature=temperature)
+                      given=given, temperature=temperature, sub_base=sub_base)
         return p_v, v_s
 
     def log_partition(self, bh=None, bv=None, num_chains=64, num_betas=1000, betas=None, seed=None, row0=0, row_ids=None, stats=None, given=None):

@@ -428,15 +428,21 @@ extern "C" size_t mnn_generate_scan_workspace_bytes(int B, int n_in, int n_layer
 
 // c0 / h0 (mnn_generate_scan_state; both NULL: the zero state): per layer an f32 [B, u] array, the state the intro pass starts from -- inputs of
 // the scan (the host layer tiles a learned c0 and tanh(c0) once, on the device), handed to the first step's jobs as h_prev / c_prev.
+// The chunk form (mnn_generate_scan_chunk) adds: n_intro == 0 (the scan continues from c0 / h0, then required: the first Dense is formed from
+// h0[last layer]); num_steps == 0 with n_intro > 0 (the intro pass alone); c_out / h_out (both NULL, or per layer an f32 [B, u] array that
+// receives the state behind the last step -- copied after the last launch that reads c0 / h0, so they may be the same arrays); step0 and
+// step_base (NULL, or one u32 on the device): step st draws with sub-counter step0 + *step_base + st.
 static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
                               const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
                               int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0,
                               uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0,
-                              const float* const* h0) {
+                              const float* const* h0, float* const* c_out = nullptr, float* const* h_out = nullptr, uint32_t step0 = 0,
+                              const uint32_t* step_base = nullptr, bool chunk = false) {
     MNN_REQUIRE(temps, "mnn_generate_scan: null temps");     // (its contents: mnn_nade_sample_temps, before anything is enqueued when num_steps > 0)
-    MNN_REQUIRE(B > 0 && n_intro > 0 && num_steps >= 0 && intro && n_in > 0 && n_layers > 0 && n_layers <= MNN_SCAN_MAX_LAYERS && layers,
-                "mnn_generate_scan: B, n_intro > 0, 1..%d layers", MNN_SCAN_MAX_LAYERS);
-    MNN_REQUIRE(dense_W && tracks > 0 && D > 0 && Hn > 0 && n_out == tracks * (Hn + D) && n_in == tracks * D && w_enc && w_dec && samples,
+    MNN_REQUIRE(B > 0 && (n_intro > 0 || (chunk && n_intro == 0 && num_steps > 0 && c0 != nullptr)) && num_steps >= 0 && (intro || n_intro == 0) && n_in > 0 &&
+                n_layers > 0 && n_layers <= MNN_SCAN_MAX_LAYERS && layers,
+                "mnn_generate_scan: B, n_intro > 0 (the chunk form: or n_intro == 0 with an input state and num_steps > 0), 1..%d layers", MNN_SCAN_MAX_LAYERS);
+    MNN_REQUIRE(dense_W && tracks > 0 && D > 0 && Hn > 0 && n_out == tracks * (Hn + D) && n_in == tracks * D && w_enc && w_dec && (samples || num_steps == 0),
                 "mnn_generate_scan: the Dense layer feeds `tracks` NADEs (n_out == tracks * (Hn + D)) and a sample is the next input (n_in == tracks * D)");
     const size_t need = mnn_generate_scan_workspace_bytes(B, n_in, n_layers, layers, n_out);
     MNN_REQUIRE(workspace && need > 0 && workspace_bytes >= need && ((uintptr_t)workspace & 255) == 0,
@@ -493,7 +499,8 @@ static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps,
         mnn_det_dense_job dj;
         memset(&dj, 0, sizeof(dj));
         const int ul = layers[n_layers - 1].units;
-        dj.x = hbuf[n_layers - 1][cur]; dj.ld_x = ul; dj.K = ul; dj.W = dense_W; dj.Wp = dpack; dj.ld_w = n_out; dj.N = n_out; dj.bias = dense_bias;
+        dj.x = have_state ? hbuf[n_layers - 1][cur] : h0[n_layers - 1];      // (no step yet: a chunk without intro, h0 required)
+        dj.ld_x = ul; dj.K = ul; dj.W = dense_W; dj.Wp = dpack; dj.ld_w = n_out; dj.N = n_out; dj.bias = dense_bias;
         dj.out = out; dj.ld_out = ld_out;
         return mnn_dense_det(s, B, 1, &dj);
     };
@@ -506,15 +513,42 @@ static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps,
     const int row_stride = num_steps * n_in;
     for (int st = 0; st < num_steps; ++st) {
         uint8_t* smp = samples + (size_t)st * n_in;            // samples[:, st, :]; feature m D + i (one NADE) or i tracks + m (rnn_multinade.py:313-314)
-        rc = mnn_nade_sample_temps(s, tracks, B, D, Hn, out, ld_out, w_enc, w_dec, temps, seed, row0, (uint32_t)st, smp,
-                             tracks > 1 ? 1 : D, row_stride, tracks > 1 ? tracks : 1, nullptr, given ? given + (size_t)st * n_in : nullptr);
+        rc = mnn_nade_sample_temps_at(s, tracks, B, D, Hn, out, ld_out, w_enc, w_dec, temps, seed, row0, step0 + (uint32_t)st, smp,
+                                      tracks > 1 ? 1 : D, row_stride, tracks > 1 ? tracks : 1, nullptr, given ? given + (size_t)st * n_in : nullptr,
+                                      step_base);
         if (rc != MNN_OK) return rc;
         rc = stack_step(smp, row_stride);
         if (rc != MNN_OK) return rc;
         rc = dense();
         if (rc != MNN_OK) return rc;
     }
+    if (c_out != nullptr) {                                    // the state behind the last step (at least one ran): stream-ordered behind every read of c0 / h0
+        for (int l = 0; l < n_layers; ++l) {
+            const size_t bytes = (size_t)B * layers[l].units * sizeof(float);
+            MNN_HIP(hipMemcpyAsync(c_out[l], cbuf[l][cur], bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
+            MNN_HIP(hipMemcpyAsync(h_out[l], hbuf[l][cur], bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
+        }
+    }
     return MNN_OK;
+}
+
+// One chunk of a generation session (see generate_scan_impl): the intro pass alone (num_steps == 0), or num_steps generated steps that continue
+// from c_in / h_in (n_intro == 0) -- or both.  samples / given are [B, num_steps, n_in] of THIS chunk.  With step0 == 0, step_base == NULL and
+// no output state this is mnn_generate_scan_temps, launch for launch.
+extern "C" int mnn_generate_scan_chunk(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                       const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
+                                       int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0,
+                                       uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c_in,
+                                       const float* const* h_in, float* const* c_out, float* const* h_out, uint32_t step0, const uint32_t* step_base) {
+    MNN_REQUIRE((c_in == nullptr) == (h_in == nullptr) && (c_out == nullptr) == (h_out == nullptr),
+                "mnn_generate_scan_chunk: c_in / h_in and c_out / h_out come in pairs (arrays of n_layers pointers) or not at all");
+    MNN_REQUIRE(n_layers > 0 && n_layers <= MNN_SCAN_MAX_LAYERS, "mnn_generate_scan_chunk: 1..%d layers", MNN_SCAN_MAX_LAYERS);
+    for (int l = 0; l < n_layers; ++l)
+        MNN_REQUIRE((c_in == nullptr || (c_in[l] && h_in[l])) && (c_out == nullptr || (c_out[l] && h_out[l])), "mnn_generate_scan_chunk: layer %d has a null state array", l);
+    MNN_REQUIRE(n_intro >= 0 && num_steps >= 0 && n_intro + num_steps > 0, "mnn_generate_scan_chunk: n_intro, num_steps >= 0 and one of them > 0");
+    MNN_REQUIRE(n_intro > 0 || c_in != nullptr, "mnn_generate_scan_chunk: a chunk without intro continues from c_in / h_in");
+    return generate_scan_impl(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc, w_dec, temps,
+                              seed, row0, samples, workspace, workspace_bytes, given, c_in, h_in, c_out, h_out, step0, step_base, true);
 }
 
 // the scan with a temperature table (mnn_temps: per track of a MultiNADE, or per visible index of the one NADE) and the optional initial state

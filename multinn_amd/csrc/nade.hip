@@ -816,11 +816,15 @@ __device__ __forceinline__ void sample_temps_park(const SampleTemps& TT, int lan
 // GIVEN: conditional sampling -- a visible whose code in job.given is 0 / 1 is not drawn, its value is written and fed forward like a draw
 // (its uniform is left unused: every free visible reads the uniform of the unconditioned scan); logits are parked as before, so nll is that of
 // the emitted vector.
+// SUB_BASE: sub_base (NULL: none) points at one u32 on the device that is added to the launch's sub-counter -- the generated steps before a
+// session's chunk, so that a captured chunk replays at any position of the piece (mnn_nade_sample_temps_at).
 template <int TMODE, bool FULL, bool SPEC, bool GIVEN>
 __global__ void __launch_bounds__(256)
-nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
+nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t row0, uint32_t sub_arg, long s_row_stride, int s_elem_stride,
+                   const uint32_t* __restrict__ sub_base) {
     // per wave: logit / log term [Dp] f32, b_dec [Dp] f32, draws [Dp] u8, 256 uniforms (, GIVEN: the row's codes [Dp] u8) (, TMODE 2: 8 temperatures)
     extern __shared__ __attribute__((aligned(16))) unsigned char nade_sample_smem[];
+    uint32_t sub = sub_arg;                                 // SUB_BASE: the Philox sub-counter; the base is added in front of the first refill
     // blockIdx.y = job: a track of one MultiNADE (mnn_nade_sample) or one of several generators sampled together (mnn_nade_sample_multi)
     const SampleJob& jb = J.job[blockIdx.y];
     const float* __restrict__ bias = jb.bias;
@@ -880,6 +884,10 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t 
         philox_uniform4(seed, MNN_STREAM_NADE, row0 + (uint32_t)row, sub, b0 + (uint32_t)lane, u4);
         *reinterpret_cast<float4*>(su + 4 * lane) = make_float4(u4[0], u4[1], u4[2], u4[3]);
     };
+    // SUB_BASE: one wave-uniform (scalar) read, HERE and not at the top of the kernel.  At the top the compiler puts the load of the pointer,
+    // a wait for it and the null test in front of every other load of the kernel; here the pointer is fetched with the other arguments
+    // and the test comes behind the prologue's loads (the instruction sequences and the timings of both forms: profiles/session.md)
+    if (sub_base != nullptr) sub += *sub_base;
     if (TMODE != 0) refill();
     // TMODE 2: the temperature of visible i is stt[tix]; tix = i % n carried along (never a division per visible), or the job for good
     int tix = 0;
@@ -990,13 +998,15 @@ extern "C" int mnn_sch_trace_read(long long* host) { return hipMemcpyFromSymbol(
 // drawn -- moves the state.
 template <int TMODE, bool FULL, int G, bool GIVEN>
 __global__ void __launch_bounds__(64)
-nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
+nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t row0, uint32_t sub_arg, long s_row_stride, int s_elem_stride,
+                   const uint32_t* __restrict__ sub_base) {
     constexpr int NB = sch_nb(G);
     constexpr int KSH = G == 16 ? 2 : 3;                      // lane l decides visible l >> KSH of the chunk
     constexpr int WAITN = (NB - 2) * 2 * G;                   // copies that may still be in flight when a chunk is needed: the NB - 2 chunks behind it
     // ring [NB][w_dec | w_enc][G][256] f32 (64 KB) | logit / log term [Dp] f32 | b_dec [Dp] f32 | 256 uniforms | draws [Dp] u8 (| GIVEN: codes [Dp] u8)
     // (| TMODE 2: 8 temperatures)
     extern __shared__ __attribute__((aligned(16))) unsigned char nade_sample_smem[];
+    uint32_t sub = sub_arg;                                  // SUB_BASE: as nade_sample_kernel
     float* ring = reinterpret_cast<float*>(nade_sample_smem);
     const int Dp = (D + 3) & ~3;
     float* sp = ring + NB * 2 * G * 256;
@@ -1069,6 +1079,10 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
         philox_uniform4(seed, MNN_STREAM_NADE, row0 + (uint32_t)row, sub, b0 + (uint32_t)lane, u4);
         *reinterpret_cast<float4*>(su + 4 * lane) = make_float4(u4[0], u4[1], u4[2], u4[3]);
     };
+    // SUB_BASE: one wave-uniform (scalar) read, HERE and not at the top of the kernel.  At the top the compiler puts the load of the pointer,
+    // a wait for it and the null test in front of every other load of the kernel; here the pointer is fetched with the other arguments
+    // and the test comes behind the prologue's loads (the instruction sequences and the timings of both forms: profiles/session.md)
+    if (sub_base != nullptr) sub += *sub_base;
     if (TMODE != 0) refill();
     if (TMODE == 2) sample_temps_park(TT, lane, stt);        // (an LDS write: ahead of every copy, like the uniforms)
     asm volatile("" ::"v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(h[3]));     // the initial states are evaluated HERE: behind the copies they would wait for all 64 of them
@@ -1258,7 +1272,7 @@ static hipError_t sample_chunk_raise_lds() {                 // the ring + a row
 // tmode / TT: launch_sample's reading of the caller's mnn_temps (TT is read by the TMODE 2 instantiations only)
 template <bool GV>
 static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, int tmode, const SampleTemps& TT, uint32_t row0, uint32_t sub,
-                           long s_row_stride, int s_elem_stride) {
+                           long s_row_stride, int s_elem_stride, const uint32_t* sub_base) {
     bool chunked = Hn % 4 == 0 && Hn >= 4 && !mnn_switch_set(MNN_SW_SAMPLE_NO_CHUNK);      // (tests compare the two forms)
     for (int j = 0; j < njobs && chunked; ++j) chunked = (((uintptr_t)J.job[j].w_enc | (uintptr_t)J.job[j].w_dec) & 15) == 0;
     const size_t gbytes = GV ? (size_t)((D + 3) & ~3) : 0;   // the row's codes
@@ -1268,8 +1282,8 @@ static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N
         const int g = (long)N * njobs <= 256 && !mnn_switch_set(MNN_SW_SAMPLE_G8) ? 16 : 8;
         const size_t ldc = (size_t)sch_nb(g) * 2 * g * 1024 + (size_t)9 * ((D + 3) & ~3) + 1024 + gbytes + tbytes;     // <= 96 KB + 15 KB + 1 KB (D <= 1536)
         MNN_HIP(sample_chunk_raise_lds());
-#define SMC(TM, FU) do { if (g == 16) hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 16, GV>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride); \
-                         else hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 8, GV>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride); } while (0)
+#define SMC(TM, FU) do { if (g == 16) hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 16, GV>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base); \
+                         else hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 8, GV>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base); } while (0)
         if (Hn == 256) { if (tmode == 0) SMC(0, true); else if (tmode == 1) SMC(1, true); else SMC(2, true); }
         else { if (tmode == 0) SMC(0, false); else if (tmode == 1) SMC(1, false); else SMC(2, false); }
 #undef SMC
@@ -1278,7 +1292,7 @@ static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N
     }
     dim3 grid(cdiv(N, 4), njobs);
     const size_t lds = (size_t)36 * ((D + 3) & ~3) + 4096 + 4 * gbytes + tbytes;     // 4 waves x ((2 f32 + u8 (+ u8 code)) per visible + 256 uniforms): <= 64 KB
-#define SMP(TM, FU, SP) hipLaunchKernelGGL((nade_sample_kernel<TM, FU, SP, GV>), grid, dim3(256), lds, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride)
+#define SMP(TM, FU, SP) hipLaunchKernelGGL((nade_sample_kernel<TM, FU, SP, GV>), grid, dim3(256), lds, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base)
     if (Hn == 256 && tmode == 1) { if (mnn_switch_set(MNN_SW_SAMPLE_NO_SPEC)) SMP(1, true, false); else SMP(1, true, true); }
     else if (Hn == 256) { if (tmode == 0) SMP(0, true, false); else SMP(2, true, false); }
     else { if (tmode == 0) SMP(0, false, false); else if (tmode == 1) SMP(1, false, false); else SMP(2, false, false); }
@@ -1291,7 +1305,7 @@ static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N
 // ones a launch without temperatures always ran; anything else -> TMODE 2 with the table.  track0: the first job's index into a per-job table
 // (mnn_nade_sample walks a MultiNADE's tracks eight at a time).
 static int launch_sample(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, const mnn_temps& temps, int track0, uint32_t row0,
-                         uint32_t sub, long s_row_stride, int s_elem_stride) {
+                         uint32_t sub, long s_row_stride, int s_elem_stride, const uint32_t* sub_base = nullptr) {
     bool given = false;
     for (int j = 0; j < njobs; ++j) given = given || J.job[j].given != nullptr;
     SampleTemps TT;
@@ -1309,8 +1323,8 @@ static int launch_sample(hipStream_t st, const SampleJobs& J, int njobs, int N, 
             for (int j = 0; j < njobs; ++j) if (TT.t[j] != 1.0f) tmode = 2;
         }
     }
-    return given ? launch_sample_t<true>(st, J, njobs, N, D, Hn, tmode, TT, row0, sub, s_row_stride, s_elem_stride)
-                 : launch_sample_t<false>(st, J, njobs, N, D, Hn, tmode, TT, row0, sub, s_row_stride, s_elem_stride);
+    return given ? launch_sample_t<true>(st, J, njobs, N, D, Hn, tmode, TT, row0, sub, s_row_stride, s_elem_stride, sub_base)
+                 : launch_sample_t<false>(st, J, njobs, N, D, Hn, tmode, TT, row0, sub, s_row_stride, s_elem_stride, sub_base);
 }
 
 // n == 0 (threshold draws), or 1..8 positive finite temperatures; a per-job table (by_visible == 0) has one entry or one per job
@@ -1326,9 +1340,11 @@ static mnn_temps temps_of_scalar(float temperature) {        // the float of the
     return t;
 }
 
-extern "C" int mnn_nade_sample_temps(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
-                                     const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
-                                     long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given) {
+// mnn_nade_sample_temps with a sub-counter base read on the device: sub_base NULL (none), or one u32 -- the draws use sub + *sub_base
+extern "C" int mnn_nade_sample_temps_at(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
+                                        const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
+                                        long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given,
+                                        const uint32_t* sub_base) {
     MNN_REQUIRE(tracks > 0 && N > 0 && D > 0 && Hn > 0 && Hn <= 256, "mnn_nade_sample: need tracks,N,D>0 and 0<Hn<=256 (Hn=%d)", Hn);
     MNN_REQUIRE(bias && w_enc && w_dec && samples, "mnn_nade_sample: null pointer");
     MNN_REQUIRE(ld_bias >= tracks * (Hn + D), "mnn_nade_sample: ld_bias too small");
@@ -1344,10 +1360,17 @@ extern "C" int mnn_nade_sample_temps(mnn_stream_t s, int tracks, int N, int D, i
                                  (uint32_t)(m * D), samples + (size_t)m * s_track_stride, nll ? nll + (size_t)m * N : nullptr,
                                  given ? given + (size_t)m * s_track_stride : nullptr};
         }
-        const int rc = launch_sample((hipStream_t)s, J, nj, N, D, Hn, *temps, m0, row0, sub, s_row_stride, s_elem_stride);
+        const int rc = launch_sample((hipStream_t)s, J, nj, N, D, Hn, *temps, m0, row0, sub, s_row_stride, s_elem_stride, sub_base);
         if (rc != MNN_OK) return rc;
     }
     return MNN_OK;
+}
+
+extern "C" int mnn_nade_sample_temps(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
+                                     const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
+                                     long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given) {
+    return mnn_nade_sample_temps_at(s, tracks, N, D, Hn, bias, ld_bias, w_enc, w_dec, temps, seed, row0, sub, samples, s_track_stride, s_row_stride,
+                                    s_elem_stride, nll, given, nullptr);
 }
 
 extern "C" int mnn_nade_sample(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,

@@ -21,14 +21,16 @@ extern "C" size_t mnn_rbm_workspace_bytes(int D, int Hn) { return (size_t)D * Hn
 
 static int gibbs_single(const char* who, mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
                         const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v, uint8_t* v_out,
-                        void* workspace, const int* seed_step, const uint8_t* given, int ld_given, float temperature) {
+                        void* workspace, const int* seed_step, const uint8_t* given, int ld_given, float temperature,
+                        const uint32_t* sub_base = nullptr) {
+    const uint32_t sub_scale = (uint32_t)(k > 1 ? k : 1);      // a generated step uses max(k, 1) sub-counters
     MNN_REQUIRE(temperature > 0.f && temperature <= 3.0e38f, "%s: the temperature is a positive finite number (%g)", who, (double)temperature);
     MNN_REQUIRE(given == nullptr || ld_given >= D, "%s: ld_given=%d < D=%d", who, ld_given, D);
     if (temperature != 1.0f) {
-        GibbsArgs<true> A{N, D, Hn, k, v0, W, nullptr, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, given, ld_given, temperature, seed_step};
+        GibbsArgs<true> A{N, D, Hn, k, v0, W, nullptr, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, given, ld_given, temperature, seed_step, sub_base, sub_scale};
         return rbm_gibbs_dispatch(who, s, A, workspace);
     }
-    GibbsArgs<false> A{N, D, Hn, k, v0, W, nullptr, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, given, ld_given, 1.0f, seed_step};
+    GibbsArgs<false> A{N, D, Hn, k, v0, W, nullptr, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, given, ld_given, 1.0f, seed_step, sub_base, sub_scale};
     return rbm_gibbs_dispatch(who, s, A, workspace);
 }
 
@@ -37,6 +39,15 @@ extern "C" int mnn_rbm_gibbs_temp(mnn_stream_t s, int N, int D, int Hn, int k, c
                                   uint8_t* v_out, void* workspace, const uint8_t* given, int ld_given, float temperature) {
     return gibbs_single("mnn_rbm_gibbs_temp", s, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, workspace, nullptr, given,
                         ld_given, temperature);
+}
+
+// mnn_rbm_gibbs_temp with a sub-counter base read on the device (sub_base: NULL, or one u32 -- the generated steps before this launch): the
+// chain draws with sub-counters sub0 + *sub_base * max(k, 1) + iteration.  A captured launch follows the cell from replay to replay.
+extern "C" int mnn_rbm_gibbs_at(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,
+                                const float* bv, int ld_bv, uint64_t seed, uint32_t row0, const uint32_t* row_ids, uint32_t sub0, float* p_v,
+                                uint8_t* v_out, void* workspace, const uint8_t* given, int ld_given, float temperature, const uint32_t* sub_base) {
+    return gibbs_single("mnn_rbm_gibbs_at", s, N, D, Hn, k, v0, W, bh, ld_bh, bv, ld_bv, seed, row0, row_ids, sub0, p_v, v_out, workspace, nullptr, given,
+                        ld_given, temperature, sub_base);
 }
 
 extern "C" int mnn_rbm_gibbs_stepped(mnn_stream_t s, int N, int D, int Hn, int k, const uint8_t* v0, const float* W, const float* bh, int ld_bh,

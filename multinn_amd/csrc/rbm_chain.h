@@ -495,7 +495,7 @@ static inline size_t rbm_lds_bytes(int D, int Hn) { return (size_t)RBM_R * (((D 
 // ----------------------------------------------------------------------------------------------
 // The argument blocks of the chain kernels, passed by value.  Two shapes: the one job of mnn_rbm_gibbs / _stepped / _temp, contiguous [N, D]
 // (STRIDED = false: the bodies keep their n * D + d addressing, the view does not read blockIdx.y), and a table of up to RBM_MULTI_MAX_JOBS
-// jobs, job = blockIdx.y, STRIDED.  `given` (null: the free chain), `temp` and `seed_step` (null: none) are plain fields; whether a kernel
+// jobs, job = blockIdx.y, STRIDED.  `given` (null: the free chain), `temp`, `seed_step` and `sub_base` (null: none) are plain fields; whether a kernel
 // reads the first two is its GIVEN / TEMPERED.  For the dispatch both give view() on the device and, on the host, jobs(), weights(j),
 // set_wt(j, .) (the streaming form's transposed copy), has_given() and complete(j).
 // ----------------------------------------------------------------------------------------------
@@ -509,10 +509,13 @@ struct GibbsArgs {
     const uint8_t* v0; const float* W; const float* Wt; const float* bh; int ld_bh; const float* bv; int ld_bv;
     uint64_t seed; uint32_t row0; const uint32_t* row_ids; uint32_t sub0; float* p_v; uint8_t* v_out;
     const uint8_t* given; int ld_given; float temp; const int* seed_step;
+    const uint32_t* sub_base; uint32_t sub_scale;       // null, or the generated steps before this launch (a session's step cell): sub0 += *sub_base * sub_scale
     __device__ __forceinline__ GibbsView view() const {
         uint64_t sd = seed;
         if (seed_step != nullptr) sd += (uint64_t)(int64_t)*seed_step;      // step counter on the device: a captured launch draws anew every replay
-        return GibbsView{N, D, Hn, k, v0, W, Wt, bh, ld_bh, bv, ld_bv, sd, row0, row_ids, sub0, p_v, v_out, given, ld_given, 0, 1, temp};
+        uint32_t sb = sub0;
+        if (sub_base != nullptr) sb += *sub_base * sub_scale;               // likewise the sub-counter base: a captured chunk of a session continues the piece
+        return GibbsView{N, D, Hn, k, v0, W, Wt, bh, ld_bh, bv, ld_bv, sd, row0, row_ids, sb, p_v, v_out, given, ld_given, 0, 1, temp};
     }
     int jobs() const { return 1; }
     const float* weights(int) const { return W; }
@@ -534,11 +537,14 @@ struct GibbsTableArgs {
     uint32_t row0; const uint32_t* row_ids; uint32_t sub0; const int* seed_step;
     long rs, rs_given; int es, njobs;
     float temp[RBM_MULTI_MAX_JOBS];          // read by the TEMPERED kernels only
+    const uint32_t* sub_base; uint32_t sub_scale;       // as GibbsArgs'
     __device__ __forceinline__ GibbsView view() const {
         const GibbsJob& j = job[blockIdx.y];
         uint64_t seed = j.seed;
         if (seed_step != nullptr) seed += (uint64_t)(int64_t)*seed_step;
-        return GibbsView{N, D, Hn, k, j.v0, j.W, j.Wt, j.bh, ld_bh, j.bv, ld_bv, seed, row0, row_ids, sub0, j.p_v, j.v_out, j.given, rs_given, rs, es,
+        uint32_t sb = sub0;
+        if (sub_base != nullptr) sb += *sub_base * sub_scale;
+        return GibbsView{N, D, Hn, k, j.v0, j.W, j.Wt, j.bh, ld_bh, j.bv, ld_bv, seed, row0, row_ids, sb, j.p_v, j.v_out, j.given, rs_given, rs, es,
                          temp[blockIdx.y]};
     }
     int jobs() const { return njobs; }

@@ -10,10 +10,11 @@
 #include "rbm_chain.h"
 
 // temps: NULL (every job at temperature 1) or njobs positive finite temperatures; all of them 1 selects the untempered kernels
-extern "C" int mnn_rbm_gibbs_multi_temps(mnn_stream_t s, int njobs, const mnn_rbm_gibbs_job* jobs, int N, int D, int Hn, int k, int ld_bh, int ld_bv,
-                                         uint32_t row0, const uint32_t* row_ids, uint32_t sub0, const int* seed_step, long row_stride, int elem_stride,
-                                         long given_row_stride, void* workspace, const float* temps) {
-    const char* who = temps != nullptr ? "mnn_rbm_gibbs_multi_temps" : "mnn_rbm_gibbs_multi";
+// sub_base: NULL, or one u32 on the device (the generated steps before this launch): sub-counters sub0 + *sub_base * max(k, 1) + iteration
+extern "C" int mnn_rbm_gibbs_multi_at(mnn_stream_t s, int njobs, const mnn_rbm_gibbs_job* jobs, int N, int D, int Hn, int k, int ld_bh, int ld_bv,
+                                      uint32_t row0, const uint32_t* row_ids, uint32_t sub0, const int* seed_step, long row_stride, int elem_stride,
+                                      long given_row_stride, void* workspace, const float* temps, const uint32_t* sub_base) {
+    const char* who = sub_base != nullptr ? "mnn_rbm_gibbs_multi_at" : temps != nullptr ? "mnn_rbm_gibbs_multi_temps" : "mnn_rbm_gibbs_multi";
     MNN_REQUIRE(njobs > 0 && njobs <= RBM_MULTI_MAX_JOBS && jobs, "%s: 1..%d jobs", who, RBM_MULTI_MAX_JOBS);
     MNN_REQUIRE(elem_stride >= 1 && (row_stride >= (long)(D - 1) * elem_stride + 1 || N == 1), "%s: bad strides (row %ld, element %d)", who, row_stride,
                 elem_stride);
@@ -31,11 +32,18 @@ extern "C" int mnn_rbm_gibbs_multi_temps(mnn_stream_t s, int njobs, const mnn_rb
             A.temp[j] = tempered ? temps[j] : 1.0f;
         }
         A.njobs = njobs; A.N = N; A.D = D; A.Hn = Hn; A.k = k; A.ld_bh = ld_bh; A.ld_bv = ld_bv;
-        A.row0 = row0; A.row_ids = row_ids; A.sub0 = sub0; A.seed_step = seed_step;
+        A.row0 = row0; A.row_ids = row_ids; A.sub0 = sub0; A.seed_step = seed_step; A.sub_base = sub_base; A.sub_scale = (uint32_t)(k > 1 ? k : 1);
         A.rs_given = given_row_stride; A.rs = row_stride; A.es = elem_stride;
         return rbm_gibbs_dispatch(who, s, A, workspace);
     };
     return tempered ? run(GibbsTableArgs<true>()) : run(GibbsTableArgs<false>());
+}
+
+extern "C" int mnn_rbm_gibbs_multi_temps(mnn_stream_t s, int njobs, const mnn_rbm_gibbs_job* jobs, int N, int D, int Hn, int k, int ld_bh, int ld_bv,
+                                         uint32_t row0, const uint32_t* row_ids, uint32_t sub0, const int* seed_step, long row_stride, int elem_stride,
+                                         long given_row_stride, void* workspace, const float* temps) {
+    return mnn_rbm_gibbs_multi_at(s, njobs, jobs, N, D, Hn, k, ld_bh, ld_bv, row0, row_ids, sub0, seed_step, row_stride, elem_stride, given_row_stride,
+                                  workspace, temps, nullptr);
 }
 
 extern "C" int mnn_rbm_gibbs_multi(mnn_stream_t s, int njobs, const mnn_rbm_gibbs_job* jobs, int N, int D, int Hn, int k, int ld_bh, int ld_bv,

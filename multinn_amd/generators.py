@@ -11,6 +11,7 @@ rows past ``lengths`` are masked by a zero row weight instead of being gathered 
 """
 import abc
 import collections
+import contextlib
 import math
 
 import weakref
@@ -375,6 +376,32 @@ class RnnEstimator(Generator):
 
     def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0):
         return None                         # estimators without a one-call scan (RnnRBM) step through sample_single / single_step
+
+    # -- generation sessions (session.py) --------------------------------------------------------
+    # Set by a session around a chunk of its step loop: sample_single draws at the sub-counter (_gen_step + *_gen_base) (* max(k, 1): RBM) --
+    # _gen_base a step cell on the device that the kernels read (a captured chunk), or None (the host offset is in _gen_step).
+    _gen_base = None
+    subs_per_step = 1                       # Philox sub-counters a generated step owns (RBM estimators: max(k, 1))
+
+    def session(self, x):
+        """A generation session on the intro x [B, Ti, Din] (generate's x): session.GeneratorSession -- sess.generate(num_steps, given,
+        temperature) continues the piece chunk by chunk, the chunks concatenated being generate(x, n, ...) bit for bit."""
+        from .session import GeneratorSession
+        return GeneratorSession(self, x)
+
+    def _state_of(self, out, rnn_state):
+        """The estimator state of a Dense output block [B, ldo] and an LSTM state (a session rebuilds it from its static arrays)."""
+        raise NotImplementedError
+
+    def _scan_layers(self):
+        """What a session's one-call chunks (ops.generate_scan_chunk) need: dict(layers, dense_W, dense_bias, ...), or None for an estimator
+        without a one-call scan."""
+        return None
+
+    @contextlib.contextmanager
+    def _sampling_scope(self):
+        """Around the steps of one scan (RnnMultiRBM: its internal bias vectors are formed once per scan)."""
+        yield
 
     def _det_single_step(self, inputs, initial_state, x2=None):
         """single_step in the deterministic arithmetic: inputs u8 | f32 [B, n_x]; x2 (optional, f32 [B, F]) is concatenated behind it -- the
@@ -1042,11 +1069,18 @@ class RnnNade(RnnEstimator):
         given: the scan's codes u8 [B, num_steps, num_output] (generate)."""
         if x.dtype != torch.uint8 or x.shape[-1] != self.num_tracks * self.num_dims or int(num_steps) < 1:
             return None
+        return ops.generate_scan(x.contiguous(), num_steps, temperature=temperature, seed=self.seed, row0=self.row0, given=given,
+                                 state0=self._state0(x.shape[0], torch.float32), **self._scan_layers())      # (learn_zero_state: tiled on the device here, an input array of the scan)
+
+    def _state_of(self, out, rnn_state):
+        return self._state_from_dense(out, rnn_state)
+
+    def _scan_layers(self):
+        """The weights of the one-call scan, as keyword arguments of ops.generate_scan / generate_scan_chunk."""
         pre = self._rnn.prefix
-        layers = [(self.store[f"{pre}/cell_{l}/kernel"], self.store[f"{pre}/cell_{l}/bias"]) for l in range(len(self._rnn.num_units))]
-        return ops.generate_scan(x.contiguous(), num_steps, layers, self.store["dense/kernel"], self._det_fc_bias(), self.num_tracks, self.num_dims,
-                                 self.num_hidden[-1], self.store["nade/w_enc"], self.store["nade/w_dec"], temperature, self.seed, self.row0, given=given,
-                                 state0=self._state0(x.shape[0], torch.float32), by_visible=self.num_tracks == 1)      # (learn_zero_state: tiled on the device here, an input array of the scan)
+        return dict(layers=[(self.store[f"{pre}/cell_{l}/kernel"], self.store[f"{pre}/cell_{l}/bias"]) for l in range(len(self._rnn.num_units))],
+                    dense_W=self.store["dense/kernel"], dense_bias=self._det_fc_bias(), tracks=self.num_tracks, D=self.num_dims, Hn=self.num_hidden[-1],
+                    w_enc=self.store["nade/w_enc"], w_dec=self.store["nade/w_dec"], by_visible=self.num_tracks == 1)
 
     def _det_fc_bias(self):
         if not self.internal_bias:
@@ -1094,7 +1128,7 @@ class RnnNade(RnnEstimator):
         nll = torch.empty((M, Bn), device=out.device)
         ops.nade_sample(out, self.store["nade/w_enc"], self.store["nade/w_dec"], M, D, Hn, temperature, self.seed, self.row0,
                         getattr(self, "_gen_step", 0), smp, track_minor=(M > 1), nll=nll, given=None if given is None else given.contiguous(),
-                        by_visible=M == 1)
+                        by_visible=M == 1, sub_base=self._gen_base)
         return smp, (nll[0] if M == 1 else [nll[m] for m in range(M)])
 
 
@@ -1427,7 +1461,14 @@ class RnnRBM(RnnEstimator):
     def _state_from_out(self, out, rnn_state):
         """The estimator state of a Dense output [B, ld]: the tracks' bias blocks bh_t | bv_t (views)."""
         be, bd = self._split(out)
-        return RnnEstimatorStateTuple(self._present(be), self._present(bd), rnn_state)
+        st = RnnEstimatorStateTuple(self._present(be), self._present(bd), rnn_state)
+        st.dense = out
+        return st
+
+    def _state_of(self, out, rnn_state):
+        return self._state_from_out(out, rnn_state)
+
+    subs_per_step = property(lambda self: max(self._k, 1))
 
     _det_bias = None                       # inside RnnMultiRBM._generate_scan: True, then the internal bias vectors the scan's first Dense formed
 
@@ -1469,7 +1510,7 @@ class RnnRBM(RnnEstimator):
         generate's [B, num_steps, D] is read in place): the clamped Gibbs chain -- clamped visibles are emitted as given, every free one is
         sampled conditioned on all of them (RBM.sample); cond_prob is sigmoid(logit) at every visible."""
         p_v, v = self._rbm.sample(inputs[:, :self.num_dims], state.b_enc, state.b_dec, self._k, self.seed, self.row0, None,
-                                  getattr(self, "_gen_step", 0) * max(self._k, 1), given=given, temperature=temperature)
+                                  getattr(self, "_gen_step", 0) * max(self._k, 1), given=given, temperature=temperature, sub_base=self._gen_base)
         return v, p_v
 
     def pretrain(self, optimizer, lr, run_optimizer=True):
@@ -1537,9 +1578,14 @@ class RnnMultiRBM(RnnRBM):
         return sampling_temperature(temperature, self.num_tracks, allow_none=False)
 
     def _generate_scan(self, x, num_steps, given=None, temperature=1.0):
+        with self._sampling_scope():
+            return super()._generate_scan(x, num_steps, given, temperature)
+
+    @contextlib.contextmanager
+    def _sampling_scope(self):
         self._det_bias = True              # the first Dense of this scan forms the internal bias vectors, the later ones reuse them
         try:
-            return super()._generate_scan(x, num_steps, given, temperature)
+            yield
         finally:
             self._det_bias = None
 
@@ -1555,5 +1601,6 @@ class RnnMultiRBM(RnnRBM):
         p_v = torch.empty((Bn, M * D), device=v0.device)
         jobs = [dict(v0=v0[:, m::M], W=r.W, bh=state.b_enc[m], bv=state.b_dec[m], seed=self.seed + m, p_v=p_v[:, m::M], v_out=smp[:, m::M],
                      given=None if given is None else given[:, m::M]) for m, r in enumerate(self._rbms)]
-        ops.rbm_gibbs_multi(jobs, self._k, self.row0, None, getattr(self, "_gen_step", 0) * max(self._k, 1), temperature=temperature)
+        ops.rbm_gibbs_multi(jobs, self._k, self.row0, None, getattr(self, "_gen_step", 0) * max(self._k, 1), temperature=temperature,
+                            sub_base=self._gen_base)
         return smp, p_v

@@ -239,6 +239,13 @@ class MultINNCore(Model):
             return self.generate(num_steps, **kw)
         return self.generate(num_steps, given=given, given_mask=given_mask, **kw)
 
+    def session(self):
+        """A generation session on the built model (generate's precondition): session.ModeSession -- sess.generate(num_steps, given, given_mask,
+        temperature) continues the piece chunk by chunk, the chunks concatenated being generate(...) of the whole, bit for bit.  The joint,
+        jamming and composer modes with Pass encoders; MnnUnsupported otherwise, before any device work."""
+        from .session import ModeSession
+        return ModeSession(self)
+
     # Sampling temperature (generate(..., temperature)): one positive number, or one per track -- the drums hotter than the bass.  NADE
     # generators draw u < sigmoid(logit / T) and also take None (threshold decoding); RBM generators run the chain of exp(-E / T).  With
     # encoders the temperature acts on the generator's samples of the CODES; the encoders are untouched.  It combines with conditioning: a

@@ -664,13 +664,29 @@ def _temps(temperature, n_per_job, by_visible, what):
     return st
 
 
+def _temps_table(temperature, n_per_job, by_visible, what):
+    """The mnn_temps of ANY temperature argument (the entry points that take only a table): None -> n = 0 (threshold draws), a float -> one entry."""
+    if temperature is None:
+        return _lib.Temps()
+    return _temps((temperature,) if isinstance(temperature, (int, float)) else temperature, n_per_job, by_visible, what)
+
+
+def _sub_base(sub_base, ref, what):
+    """A generation session's step cell: None, or ONE 32-bit integer on the device of `ref` that the sampling kernels add to their sub-counter."""
+    if sub_base is not None:
+        _req(torch.is_tensor(sub_base) and sub_base.dtype == torch.int32 and sub_base.numel() == 1 and sub_base.device == ref.device,
+             f"{what}: sub_base is one int32 on the device")
+    return _ptr(sub_base)
+
+
 def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub, samples, track_minor=False, nll=None, given=None,
-                by_visible=False):
+                by_visible=False, sub_base=None):
     """samples u8 [N, tracks*D]; feature index m*D+i (track_minor False) or i*tracks+m (True, rnn_multinade.py:313-314).
     temperature: a float, None (threshold draws) or a sequence -- one temperature per track, or with by_visible the temperature of visible
     i is temperature[i % len] (a joint NADE over visibles p * M + m: one per track m).  nll stays the model's own at any temperature.
     given (optional): codes u8 [N, tracks*D] in the layout of samples -- 0 / 1 clamp the visible to that value, 255 leaves it to the draw
-    (common.given_codes)."""
+    (common.given_codes).  sub_base (optional, one int32 on the device): the draws use the sub-counter sub + *sub_base, read by the kernel
+    (mnn_nade_sample_temps_at): a captured launch follows the cell."""
     N = bias.shape[0]
     _req(bias.dtype == torch.float32 and bias.dim() == 2 and bias.stride(1) == 1 and bias.shape[1] >= tracks * (Hn + D), "sample: bias")
     _req(samples.dtype == torch.uint8 and samples.shape == (N, tracks * D) and samples.is_contiguous(), "sample: samples u8 [N,tracks*D]")
@@ -682,6 +698,11 @@ def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub,
         _req(given.dtype == torch.uint8 and tuple(given.shape) == (N, tracks * D) and given.is_contiguous() and given.device == samples.device,
              "sample: given u8 [N, tracks*D], contiguous")
     ts, es = (1, tracks) if track_minor else (D, 1)
+    if sub_base is not None:
+        tt = _temps_table(temperature, tracks, by_visible, "sample")
+        call("mnn_nade_sample_temps_at", _stream(), tracks, N, D, Hn, _ptr(bias), bias.stride(0), _ptr(w_enc), _ptr(w_dec), C.byref(tt), int(seed),
+             int(row0), int(sub), _ptr(samples), ts, tracks * D, es, _ptr(nll), _ptr(given), _sub_base(sub_base, samples, "sample"))
+        return
     tt = _temps(temperature, tracks, by_visible, "sample")
     if tt is not None:
         call("mnn_nade_sample_temps", _stream(), tracks, N, D, Hn, _ptr(bias), bias.stride(0), _ptr(w_enc), _ptr(w_dec), C.byref(tt), int(seed),
@@ -734,12 +755,15 @@ def _rbm_temperature(t, what):
     return float(t)
 
 
-def rbm_gibbs(v0, W, bh, bv, k, seed, row0=0, row_ids=None, sub0=0, p_v=None, v_out=None, seed_step=None, given=None, temperature=1.0):
+def rbm_gibbs(v0, W, bh, bv, k, seed, row0=0, row_ids=None, sub0=0, p_v=None, v_out=None, seed_step=None, given=None, temperature=1.0,
+              sub_base=None):
     """temperature (a positive float; not with seed_step): the chain of the RBM with energy E / T -- every conditional is sigmoid(z / T), p_v
     the tempered probability; 1.0 is the untempered chain, kernels and bits.
     seed_step (int32 device scalar, optional): added to `seed` on the device (graph-replay safe step-dependent draws).
     given (optional): codes u8 [N, D] (row stride >= D: a step slice given[:, s] of a [B, steps, D] block is read in place) -- 0 / 1 clamp
-    the visible to that value through the whole chain, 255 leaves it free (common.given_codes); not with seed_step (training's chain)."""
+    the visible to that value through the whole chain, 255 leaves it free (common.given_codes); not with seed_step (training's chain).
+    sub_base (optional, one int32 on the device; not with seed_step): the chain's sub-counters start at sub0 + *sub_base * max(k, 1), read
+    by the kernel (mnn_rbm_gibbs_at)."""
     N, D = v0.shape
     Hn = W.shape[1]
     _req(v0.dtype == torch.uint8 and v0.is_contiguous(), "gibbs: v0 u8 [N,D]")
@@ -758,12 +782,17 @@ def rbm_gibbs(v0, W, bh, bv, k, seed, row0=0, row_ids=None, sub0=0, p_v=None, v_
     temperature = _rbm_temperature(temperature, "gibbs")
     _req(temperature == 1.0 or seed_step is None, "gibbs: a temperature with seed_step (the stepped chain is training's, untempered)")
     ws = rbm_workspace(D, Hn, v0.device)
+    _req(sub_base is None or seed_step is None, "gibbs: sub_base with seed_step (the stepped chain is training's)")
     if seed_step is not None:
         _req(seed_step.dtype == torch.int32 and seed_step.numel() == 1, "gibbs: seed_step int32 [1]")
         call("mnn_rbm_gibbs_stepped", _stream(), N, D, Hn, int(k), _ptr(v0), _ptr(W), _ptr(bh), _ldb(bh, Hn), _ptr(bv), _ldb(bv, D), int(seed),
              int(row0), _ptr(row_ids), int(sub0), _ptr(p_v), _ptr(v_out), _ptr(ws), _ptr(seed_step))
         return
     ld_given = 0 if given is None else (given.stride(0) if N > 1 else D)
+    if sub_base is not None:
+        call("mnn_rbm_gibbs_at", _stream(), N, D, Hn, int(k), _ptr(v0), _ptr(W), _ptr(bh), _ldb(bh, Hn), _ptr(bv), _ldb(bv, D), int(seed), int(row0),
+             _ptr(row_ids), int(sub0), _ptr(p_v), _ptr(v_out), _ptr(ws), _ptr(given), ld_given, temperature, _sub_base(sub_base, v0, "gibbs"))
+        return
     if temperature != 1.0:
         call("mnn_rbm_gibbs_temp", _stream(), N, D, Hn, int(k), _ptr(v0), _ptr(W), _ptr(bh), _ldb(bh, Hn), _ptr(bv), _ldb(bv, D), int(seed), int(row0),
              _ptr(row_ids), int(sub0), _ptr(p_v), _ptr(v_out), _ptr(ws), _ptr(given), ld_given, temperature)
@@ -904,12 +933,13 @@ def _multi_bias_ld(jobs, key, n, N, what):
     return lds.pop()
 
 
-def rbm_gibbs_multi(jobs, k, row0=0, row_ids=None, sub0=0, seed_step=None, temperature=1.0):
+def rbm_gibbs_multi(jobs, k, row0=0, row_ids=None, sub0=0, seed_step=None, temperature=1.0, sub_base=None):
     """ops.rbm_gibbs for 1..8 RBMs of one shape in ONE launch (mnn_rbm_gibbs_multi).  job = dict(v0 = a u8 [N, D] VIEW (any row / column
     strides, the same for every job: e.g. x[:, m::M] of a composer-layout [N, D * M] block, or a contiguous plane), W f32 [D, Hn], bh / bv
     f32 [N or 1, >= Hn / D] (slices of one block: one leading dimension), seed, p_v f32 [N, D] / v_out u8 [N, D] views or None (the element
     strides of v0), given = None or a u8 [N, D] view of codes with v0's column stride (set on every job or on none; not with seed_step)).
     temperature: a positive float or one per job (not with seed_step); all of them 1 is the untempered launch.
+    sub_base: ops.rbm_gibbs's, shared by the jobs (mnn_rbm_gibbs_multi_at).
     Per job the results are bit for bit those of ops.rbm_gibbs (at the job's temperature) on contiguous copies."""
     _req(isinstance(jobs, (list, tuple)) and 1 <= len(jobs) <= RBM_MULTI_MAX_JOBS, f"gibbs_multi: 1..{RBM_MULTI_MAX_JOBS} jobs")
     if isinstance(temperature, (int, float)):
@@ -954,6 +984,10 @@ def rbm_gibbs_multi(jobs, k, row0=0, row_ids=None, sub0=0, seed_step=None, tempe
         a.p_v, a.v_out, a.given = _ptr(j.get("p_v")), _ptr(j.get("v_out")), _ptr(j.get("given"))
     ws = torch.empty(len(jobs) * _lib.load().mnn_rbm_workspace_bytes(D, Hn), dtype=torch.uint8, device=v0.device)
     tail = (rs if N > 1 else max(rs, (D - 1) * es + 1), es, rs_g if N > 1 else max(rs_g, (D - 1) * es + 1), _ptr(ws))
+    if sub_base is not None:
+        call("mnn_rbm_gibbs_multi_at", _stream(), len(jobs), arr, N, D, Hn, int(k), ld_bh, ld_bv, int(row0), _ptr(row_ids), int(sub0),
+             _ptr(seed_step), *tail, (C.c_float * len(jobs))(*temps) if tempered else None, _sub_base(sub_base, v0, "gibbs_multi"))
+        return
     if tempered:
         call("mnn_rbm_gibbs_multi_temps", _stream(), len(jobs), arr, N, D, Hn, int(k), ld_bh, ld_bv, int(row0), _ptr(row_ids), int(sub0),
              _ptr(seed_step), *tail, (C.c_float * len(jobs))(*temps))
@@ -1216,6 +1250,35 @@ def det_dense_pack(W, out=None):
     return out
 
 
+def _scan_tables(what, layers, n_in, n_out, dense_W, dense_bias, w_enc, w_dec, tracks, D, Hn):
+    """The host checks the scan entry points share, and the layer table (mnn_scan_lstm_layer array) they pass."""
+    arr = (_lib.ScanLstmLayer * len(layers))()
+    k_in = n_in
+    for a, (W, b) in zip(arr, layers):
+        u = b.numel() // 4
+        _req(W.dtype == torch.float32 and W.is_contiguous() and tuple(W.shape) == (k_in + u, 4 * u) and b.dtype == torch.float32 and b.is_contiguous(),
+             f"{what}: layer weights f32 [(n_in + u), 4u] / [4u]")
+        a.W, a.bias, a.units = _ptr(W), _ptr(b), u
+        k_in = u
+    _req(dense_W.dtype == torch.float32 and dense_W.is_contiguous() and tuple(dense_W.shape) == (k_in, n_out), f"{what}: Dense kernel f32 [units_last, n_out]")
+    _req(dense_bias is None or (dense_bias.dtype == torch.float32 and dense_bias.is_contiguous() and dense_bias.numel() == n_out), f"{what}: Dense bias")
+    for w in (w_enc, w_dec):
+        _req(w.dtype == torch.float32 and w.is_contiguous() and w.numel() == tracks * D * Hn, f"{what}: NADE weights f32 [tracks, D, Hn]")
+    return arr
+
+
+def _scan_state(what, state, arr, B, device):
+    """(c pointers, h pointers) of a per-layer [(c, h) f32 [B, u]] state, or (None, None)."""
+    if state is None:
+        return None, None
+    _req(len(state) == len(arr), f"{what}: one (c, h) per layer")
+    for (c, h), a in zip(state, arr):
+        for t in (c, h):
+            _req(t.dtype == torch.float32 and tuple(t.shape) == (B, a.units) and t.is_contiguous() and t.device == device,
+                 f"{what} entries f32 [B, u], contiguous")
+    return (C.c_void_p * len(arr))(*[c.data_ptr() for c, _ in state]), (C.c_void_p * len(arr))(*[h.data_ptr() for _, h in state])
+
+
 def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, given=None, state0=None,
                   by_visible=False):
     """mnn_generate_scan: the whole sampling scan of an LSTM-(Multi)NADE generator in one call.  intro u8 [B, Ti, tracks * D]; layers = [(W, bias)]
@@ -1224,18 +1287,7 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
     _req(intro.dtype == torch.uint8 and intro.dim() == 3 and intro.is_contiguous() and intro.shape[2] == tracks * D, "generate_scan: intro u8 [B, Ti, tracks * D]")
     B, Ti, n_in = intro.shape
     n_out = tracks * (Hn + D)
-    arr = (_lib.ScanLstmLayer * len(layers))()
-    k_in = n_in
-    for a, (W, b) in zip(arr, layers):
-        u = b.numel() // 4
-        _req(W.dtype == torch.float32 and W.is_contiguous() and tuple(W.shape) == (k_in + u, 4 * u) and b.dtype == torch.float32 and b.is_contiguous(),
-             "generate_scan: layer weights f32 [(n_in + u), 4u] / [4u]")
-        a.W, a.bias, a.units = _ptr(W), _ptr(b), u
-        k_in = u
-    _req(dense_W.dtype == torch.float32 and dense_W.is_contiguous() and tuple(dense_W.shape) == (k_in, n_out), "generate_scan: Dense kernel f32 [units_last, n_out]")
-    _req(dense_bias is None or (dense_bias.dtype == torch.float32 and dense_bias.is_contiguous() and dense_bias.numel() == n_out), "generate_scan: Dense bias")
-    for w in (w_enc, w_dec):
-        _req(w.dtype == torch.float32 and w.is_contiguous() and w.numel() == tracks * D * Hn, "generate_scan: NADE weights f32 [tracks, D, Hn]")
+    arr = _scan_tables("generate_scan", layers, n_in, n_out, dense_W, dense_bias, w_enc, w_dec, tracks, D, Hn)
     if given is not None:
         _req(given.dtype == torch.uint8 and tuple(given.shape) == (B, int(num_steps), n_in) and given.is_contiguous() and given.device == intro.device,
              "generate_scan: given u8 [B, num_steps, tracks * D], contiguous")
@@ -1247,15 +1299,7 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
     args = (_stream(), B, Ti, int(num_steps), _ptr(intro), n_in, len(layers), arr, _ptr(dense_W), _ptr(dense_bias), n_out, tracks, D, Hn,
             _ptr(w_enc), _ptr(w_dec), 1.0 if tt is not None else float(-1.0 if temperature is None else temperature), int(seed), int(row0),
             _ptr(samples), C.c_void_p(ws.data_ptr() + off), need, _ptr(given))        # (args[16]: the float, replaced by the table where there is one)
-    cp = hp = None
-    if state0 is not None:
-        _req(len(state0) == len(layers), "generate_scan: one (c0, h0) per layer")
-        for (c0, h0), a in zip(state0, arr):
-            for t in (c0, h0):
-                _req(t.dtype == torch.float32 and tuple(t.shape) == (B, a.units) and t.is_contiguous() and t.device == intro.device,
-                     "generate_scan: state0 entries f32 [B, u], contiguous")
-        cp = (C.c_void_p * len(layers))(*[c0.data_ptr() for c0, _ in state0])
-        hp = (C.c_void_p * len(layers))(*[h0.data_ptr() for _, h0 in state0])
+    cp, hp = _scan_state("generate_scan: state0", state0, arr, B, intro.device)
     if tt is not None:              # a temperature table: the one entry point that takes it, with or without an initial state
         call("mnn_generate_scan_temps", *args[:16], C.byref(tt), *args[17:], cp, hp)
     elif state0 is None:
@@ -1263,3 +1307,35 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
     else:
         call("mnn_generate_scan_state", *args, cp, hp)
     return samples                          # (the workspace returns to the allocator in stream order: later users are behind the scan)
+
+
+def generate_scan_chunk(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, state_in, state_out,
+                        given=None, step0=0, step_base=None, by_visible=False):
+    """mnn_generate_scan_chunk: one chunk of a generation session of an LSTM-(Multi)NADE generator.  intro u8 [B, Ti, tracks * D] or None (the
+    chunk continues from state_in); num_steps >= 0 (0 with an intro: the intro pass alone -> None); state_in: [(c, h) f32 [B, u]] per layer or
+    None (the zero state); state_out: likewise, written with the state behind the last step (may be the arrays of state_in).  Step st draws
+    with the sub-counter step0 + *step_base + st (step_base: one int32 on the device, or None).  Returns samples u8 [B, num_steps, tracks * D];
+    given (optional): the chunk's codes in that layout.  Everything else is generate_scan."""
+    ref = intro if intro is not None else state_in[0][0]
+    n_in, n_out, num_steps = tracks * D, tracks * (Hn + D), int(num_steps)
+    B, Ti = (ref.shape[0], 0) if intro is None else (intro.shape[0], intro.shape[1])
+    _req(intro is None or (intro.dtype == torch.uint8 and intro.dim() == 3 and intro.is_contiguous() and intro.shape[2] == n_in and Ti > 0),
+         "generate_scan_chunk: intro u8 [B, Ti, tracks * D]")
+    _req(num_steps >= 0 and Ti + num_steps > 0 and (Ti > 0 or state_in is not None), "generate_scan_chunk: an intro, or steps from an input state")
+    arr = _scan_tables("generate_scan_chunk", layers, n_in, n_out, dense_W, dense_bias, w_enc, w_dec, tracks, D, Hn)
+    if given is not None:
+        _req(given.dtype == torch.uint8 and tuple(given.shape) == (B, num_steps, n_in) and given.is_contiguous() and given.device == ref.device,
+             "generate_scan_chunk: given u8 [B, num_steps, tracks * D], contiguous")
+
+    ci, hi = _scan_state("generate_scan_chunk: state_in", state_in, arr, B, ref.device)
+    co, ho = _scan_state("generate_scan_chunk: state_out", state_out, arr, B, ref.device)
+    _req(0 <= int(step0) and int(step0) + num_steps <= 1 << 32, "generate_scan_chunk: step0 + num_steps passes 2^32")
+    tt = _temps_table(temperature, tracks, by_visible, "generate_scan_chunk")
+    need = int(_lib.load().mnn_generate_scan_workspace_bytes(B, n_in, len(layers), arr, n_out))
+    ws = torch.empty(need + 256, dtype=torch.uint8, device=ref.device)
+    off = (-ws.data_ptr()) % 256
+    samples = torch.empty((B, num_steps, n_in), dtype=torch.uint8, device=ref.device) if num_steps > 0 else None
+    call("mnn_generate_scan_chunk", _stream(), B, Ti, num_steps, _ptr(intro), n_in, len(layers), arr, _ptr(dense_W), _ptr(dense_bias), n_out, tracks, D, Hn,
+         _ptr(w_enc), _ptr(w_dec), C.byref(tt), int(seed), int(row0), _ptr(samples), C.c_void_p(ws.data_ptr() + off), need, _ptr(given), ci, hi, co, ho,
+         int(step0), _sub_base(step_base, ref, "generate_scan_chunk"))
+    return samples                          # (the workspace returns to the allocator in stream order: later users are behind the chunk)

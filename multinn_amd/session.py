@@ -1,0 +1,262 @@
+"""Generation sessions: continue a sampled piece in chunks, bit for bit.
+
+``generate(x, num_steps)`` runs the intro pass and the whole scan in one call and keeps nothing.  A session keeps what the scan carries from
+step to step -- the LSTM state, the last Dense output, the last emitted row (an RBM chain's start) and the number of generated steps -- so that
+
+    sess = gen.session(x);  cat([sess.generate(n_i, given=g_i, temperature=T) for i]) == gen.generate(x, sum n_i, given=cat g_i, temperature=T)
+
+in every cell, for every split.  Every draw is keyed (stream, global row, sub-counter, element) with the sub-counter "the generated step"
+(times max(k, 1) for a Gibbs chain): a chunk that starts at step s draws at s, s + 1, ...  Eagerly that offset is a host number in the launch
+arguments.  A CAPTURED chunk cannot bake it in -- every chunk would need a new capture -- so the sampling kernels read it from a one-word
+step cell on the device (mnn_nade_sample_temps_at, mnn_rbm_gibbs_at, mnn_rbm_gibbs_multi_at, mnn_generate_scan_chunk): the session fills
+the cell with ``steps`` on the stream, then replays the chunk's graph.  Graphs are cached per session by (num_steps, has given, temperature):
+the addresses of the session's state arrays are baked into them.  Each is a linear graph on one stream.
+
+GeneratorSession: one RnnEstimator (RnnNade, RnnMultiNADE, RnnRBM, RnnMultiRBM).  ModeSession: the joint, jamming and composer modes with
+Pass encoders.  Captured (common.ScanGraphs.enabled) and eager chunks run the same launches and give the same bits.
+"""
+import collections
+import contextlib
+
+import torch
+
+from . import ops
+from ._lib import MnnUnsupported
+from .common import ScanGraphs, _warm_up, graph_capture, temperature_key
+
+__all__ = ["GeneratorSession", "ModeSession"]
+
+MAX_GRAPHS = 8            # captured chunks a session keeps (least recently used first out)
+
+
+def _num_steps(steps, num_steps, subs_per_step):
+    if isinstance(num_steps, bool) or not isinstance(num_steps, int) or num_steps < 1:
+        raise ValueError(f"num_steps must be an integer >= 1, got {num_steps!r}")
+    if (int(steps) + num_steps) * max(int(subs_per_step), 1) > 1 << 32:
+        raise ValueError(f"{steps} + {num_steps} generated steps of {max(int(subs_per_step), 1)} sub-counter(s) each pass the 2^32 sub-counters of a row")
+    return num_steps
+
+
+def _chunk_arguments(gen, batch, steps, num_steps, given=None, temperature=1.0):
+    """The host checks of GeneratorSession.generate, before any device work -> (num_steps, given, temperature) normalised.  ValueError for
+    num_steps < 1, a step count that would pass 2^32 sub-counters ((steps + num_steps) * max(k, 1)), a `given` that is not u8
+    [batch, num_steps, num_output], or a bad temperature (the generator's own _temperature)."""
+    num_steps = _num_steps(steps, num_steps, gen.subs_per_step)
+    if given is not None:
+        n_out = getattr(gen, "_num_output", gen.num_dims)
+        if not torch.is_tensor(given) or given.dtype != torch.uint8 or tuple(given.shape) != (int(batch), num_steps, n_out):
+            got = f"{given.dtype} {tuple(given.shape)}" if torch.is_tensor(given) else type(given).__name__
+            raise ValueError(f"given must be u8 [{int(batch)}, {num_steps}, {n_out}], got {got}")
+    return num_steps, given, gen._temperature(temperature)
+
+
+class GeneratorSession:
+    """gen.session(x): the intro pass on x [B, Ti, Din] (from the learned state with learn_zero_state), then generate() chunk by chunk.
+
+    State (static device arrays, their addresses baked into the session's captured chunks): per LSTM layer (c, h); where the chunk is the
+    generator's step loop also the last Dense output block and the last emitted row; the step cell.  A byte piano-roll into an LSTM-(Multi)NADE
+    runs each chunk as ONE library call (mnn_generate_scan_chunk, which forms the first Dense of a chunk from h of the last layer again: the
+    same product, the same bits); every other case steps through sample_single / single_step like generate.
+    seed and row0 are the generator's when the session is opened.  For the duration of a chunk the session sets them (and the step counter
+    and cell that sample_single reads) on the generator and puts the generator's own back: sessions and generate calls on one generator may
+    interleave freely on one thread, but must not run from two threads at once."""
+
+    def __init__(self, gen, x):
+        from .generators import refuse_host_model
+        if not torch.is_tensor(x) or x.dim() != 3 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"x must be a tensor [B, Ti, Din] with at least one intro step, got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+        refuse_host_model(gen.store.device, "a generation session")
+        refuse_host_model(x.device, "a generation session")
+        self._gen, self.seed, self.row0 = gen, gen.seed, gen.row0
+        self.steps = 0
+        self.batch = int(x.shape[0])
+        self._graphs = collections.OrderedDict()
+        gen._materialize(x.shape[-1])
+        gen._rnn.build_cell(False)
+        dev = x.device
+        self._cell = torch.zeros(1, dtype=torch.int32, device=dev)            # the step cell: `steps` as 32 bits, filled before every replay
+        self._scan = gen.det_sampling and x.dtype == torch.uint8 and gen._scan_layers() is not None and x.shape[-1] == gen.num_tracks * gen.num_dims
+        if self._scan:
+            B = self.batch
+            self._rnn = [(torch.zeros((B, u), device=dev), torch.zeros((B, u), device=dev)) for u in gen._rnn.num_units]
+            self._out = self._last = None
+            ops.generate_scan_chunk(x.contiguous(), 0, temperature=1.0, seed=self.seed, row0=self.row0, state_in=gen._state0(B, torch.float32),
+                                    state_out=self._rnn, **gen._scan_layers())
+            return
+        with self._pinned(None):
+            if gen.det_sampling:
+                state = gen.steps(x)
+            else:
+                gen._ensure_packed()
+                state = gen._get_state(x, lengths=None, last_outputs=True)
+        self._rnn = [(c.clone(), h.clone()) for c, h in state.rnn_state]
+        self._out = state.dense.clone()
+        n_out = getattr(gen, "_num_output", gen.num_dims)
+        self._last = x[:, -1, :n_out].to(torch.uint8).contiguous().clone()         # the first chain's start (rnn_estimator.py:283: the intro's last row)
+
+    # -- state ----------------------------------------------------------------------------------
+    def _tensors(self):
+        ts = [t for pair in self._rnn for t in pair]
+        return ts if self._scan else ts + [self._out, self._last]
+
+    def snapshot(self):
+        """(steps, device copies of the state): restore() rewinds to it -- redraw a bar at another temperature or under another `given`."""
+        return self.steps, [t.clone() for t in self._tensors()]
+
+    def restore(self, snap):
+        steps, tensors = snap
+        mine = self._tensors()
+        if len(tensors) != len(mine) or any(a.shape != b.shape or a.dtype != b.dtype for a, b in zip(mine, tensors)):
+            raise ValueError("restore: not a snapshot of this session")
+        for a, b in zip(mine, tensors):
+            a.copy_(b)
+        self.steps = int(steps)
+
+    # -- chunks ---------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def _pinned(self, base):
+        """The generator as the session's chunks see it: seed / row0 of the opening, the step cell (or None), one sampling scope."""
+        gen = self._gen
+        saved = (gen.seed, gen.row0, getattr(gen, "_gen_step", 0))
+        gen.seed, gen.row0, gen._gen_base = self.seed, self.row0, base
+        try:
+            with gen._sampling_scope():
+                yield
+        finally:
+            gen.seed, gen.row0, gen._gen_step = saved
+            gen._gen_base = None
+
+    def _run(self, n, given, temperature, base):
+        """The launches of one chunk of n steps from the static state, which they advance in place.  base: the step cell (a captured chunk:
+        the kernels add its word to their counters) or None (eager: the host adds `steps`)."""
+        gen = self._gen
+        step0 = 0 if base is not None else self.steps
+        if self._scan:
+            return ops.generate_scan_chunk(None, n, temperature=temperature, seed=self.seed, row0=self.row0, state_in=self._rnn, state_out=self._rnn,
+                                           given=given, step0=step0, step_base=base, **gen._scan_layers())
+        with self._pinned(base):
+            if not gen.det_sampling:
+                gen._ensure_packed()
+            state = gen._state_of(self._out, tuple(self._rnn))
+            intro, out = self._last, []
+            for j in range(n):
+                gen._gen_step = step0 + j
+                kw = {} if temperature == 1.0 else dict(temperature=temperature)
+                if given is not None:
+                    kw["given"] = given[:, j]
+                samples, _ = gen.sample_single(intro, state, **kw)
+                state = gen.single_step(samples, state)
+                intro = samples
+                out.append(samples)
+            for (c, h), (nc, nh) in zip(self._rnn, state.rnn_state):      # behind the last read of the static arrays
+                c.copy_(nc)
+                h.copy_(nh)
+            self._out.copy_(state.dense)
+            self._last.copy_(intro)
+        return torch.stack(out, 1)
+
+    def generate(self, num_steps, given=None, temperature=1.0):
+        """The next num_steps steps -> u8 [B, num_steps, num_output].  given: the chunk's codes u8 [B, num_steps, num_output] as generate's
+        (None: every cell free); temperature: as generate's, and free to change from chunk to chunk."""
+        n, given, temperature = _chunk_arguments(self._gen, self.batch, self.steps, num_steps, given, temperature)
+        gen = self._gen
+        if given is not None:
+            given = given.to(self._cell.device).contiguous()
+        if not ScanGraphs.enabled(self._cell):
+            out = self._run(n, given, temperature, None)
+            self.steps += n
+            return out
+        key = (n, given is not None) + temperature_key(temperature)
+        ent = self._graphs.get(key)
+        if ent is None:
+            static_g = None if given is None else given.clone()
+            snap = self.snapshot()
+            w = min(n, 2)                            # a short eager run: kernel attributes and workspaces exist before the capture
+            _warm_up(lambda: self._run(w, None if static_g is None else static_g[:, :w].contiguous(), temperature, self._cell))
+            self.restore(snap)
+            g = torch.cuda.CUDAGraph()
+            gen._packed_step = -1                    # pack inside the graph: a replay always sees the current weights
+            with graph_capture(g, capture_error_mode="thread_local"):
+                out = self._run(n, static_g, temperature, self._cell)
+            gen._packed_step = -1                    # the packed copies now live in the graph's pool
+            ent = self._graphs[key] = (g, static_g, out)
+            while len(self._graphs) > MAX_GRAPHS:
+                self._graphs.popitem(last=False)
+        else:
+            self._graphs.move_to_end(key)
+        g, static_g, out = ent
+        if static_g is not None:
+            static_g.copy_(given)
+        self._cell.fill_(self.steps - (1 << 32) if self.steps >= 1 << 31 else self.steps)      # the word, as int32
+        g.replay()
+        self.steps += n
+        return out.clone()
+
+
+class ModeSession:
+    """model.session() of a built joint, jamming or composer model with Pass encoders (generate's precondition): one GeneratorSession per
+    generator on the model's encoded intro.  generate(num_steps, given, given_mask, temperature) -> u8 [B, num_steps, P, M]; the chunk's
+    arguments go through the mode's own _temperature / _given / _refuse_given.  Jamming: a track that a chunk gives as a whole still runs
+    through its generator's clamped scan for that chunk (the output equals the given notes), so its state and counters advance and a later
+    chunk can free it."""
+
+    def __init__(self, model):
+        from .generators import refuse_host_model
+        from .modes import MultINNCore
+        mode = model._mode
+        if mode not in ("joint", "jamming", "composer"):
+            raise MnnUnsupported(f"generation sessions exist for the joint, jamming and composer modes: the sampling scan of the {mode} mode also "
+                                 "carries its feedback module's state")
+        if model._encoder_type != "Pass":
+            raise MnnUnsupported("generation sessions through DBN encoders are not implemented: use Pass encoders")
+        refuse_host_model(model.device, "a generation session")
+        self._model, self._mode = model, mode
+        self.steps = 0
+        if model._x_encoded is None:
+            MultINNCore._build_all(model, "generate")
+        if mode == "jamming":
+            self._subs = [g.session(model._x_encoded[i]) for i, g in enumerate(model.generators)]
+        else:
+            self._subs = [model._generator.session(model._x_encoded if mode == "joint" else model._x_encoded_stack)]
+
+    def snapshot(self):
+        return self.steps, [s.snapshot() for s in self._subs]
+
+    def restore(self, snap):
+        steps, subs = snap
+        if len(subs) != len(self._subs):
+            raise ValueError("restore: not a snapshot of this session")
+        for s, sn in zip(self._subs, subs):
+            s.restore(sn)
+        self.steps = int(steps)
+
+    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0):
+        """The next num_steps steps -> u8 [B, num_steps, P, M].  given u8 [B, num_steps, P, M] / given_mask / temperature: as the mode's
+        generate, checked once per chunk, and free to change from chunk to chunk."""
+        m = self._model
+        n = _num_steps(self.steps, num_steps, max(s._gen.subs_per_step for s in self._subs))
+        temperature = m._temperature(temperature)
+        cond = m._given(n, given, given_mask)
+        P, M = m.num_dims, m.num_tracks
+        if self._mode == "jamming":
+            temps = list(temperature) if isinstance(temperature, tuple) else [temperature] * M
+            music = []
+            snap = self.snapshot()                   # the tracks advance one after another: a chunk that fails half way leaves none of them advanced
+            try:
+                for i, s in enumerate(self._subs):
+                    gv = cond[0][..., i].contiguous() if cond is not None and cond[2][i] else None
+                    music.append(m.encoders[i].decode(s.generate(n, given=gv, temperature=temps[i]))[1].to(torch.uint8))
+            except BaseException:
+                self.restore(snap)
+                raise
+            out = torch.stack(music, dim=3)
+        else:
+            gv = None if cond is None else cond[0].reshape(cond[0].shape[0], n, -1)
+            h = self._subs[0].generate(n, given=gv, temperature=temperature)
+            if self._mode == "joint":
+                out = m._encoder.decode(h)[1].reshape(-1, n, P, M).to(torch.uint8)
+            else:
+                tracks = h.reshape(h.shape[0], n, m._num_dims_generator, M).unbind(-1)
+                out = torch.stack([m.encoders[i].decode(tracks[i].contiguous())[1].to(torch.uint8) for i in range(M)], dim=3)
+        self.steps += n
+        return out
