@@ -15,22 +15,22 @@
 //   forward: A = weights, row m = 4 * (unit in tile) + gate (a tile = 8 units x {i, g, f, o}), B = h[t-1] (column n = batch row), so a lane's
 //   accumulator quads are the four gates of the (row, unit) pairs  row = l & 31, unit = 8 j + 2 q + (l >> 5), q = 0..3: the gate pointwise runs
 //   in the accumulator registers.  A wave owns two tiles (16 units), 32 k-steps each: 64 MFMAs per step (2048 cycles), 8 pairs per lane.
+//
+// Hand-off protocol: the one of lstm_handoff.h, in the row-parallel form's workspace (declared there).  Every WAVE of a cluster signals for its
+// own block: flag [HF_FLAGS_OFF + 32 cluster + 4 member + wave], polled as one 32-word line; the consumer's loads of the tile are sc1 LDS-DMA.
+// The XCD probe selects more than the store policy's aux bit here: on one XCD the tiles are stored write-BACK into a TWO-deep area, otherwise
+// write-through into one slot per timestep (a line of another XCD's L2 is never re-used within the launch).  The backward has only the
+// two-deep form and asks the host-side placement probe (cl_placement_ok) before it may run.
 #include "common.h"
+#include "lstm_handoff.h"
 #include <stdlib.h>
 
-typedef __attribute__((address_space(1))) unsigned cl_gu32;
-typedef __attribute__((address_space(3))) void* cl_lptr_t;
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
-#define CL_LIMIT 100000000LL       // spin bound: 1 s of wall_clock64() (100 MHz)
-#define CL_FLAGS_OFF 32            // words: [0] status, [1] sticky, [32 + 32 cluster + 4 member + wave] progress flags (the row-parallel workspace layout)
-#define CL_SC1 16                  // aux bit of raw buffer stores: device scope (write-through)
 // aux bits of the streamed accesses: the row-major OUTPUTS (written once, read by a later kernel) are stored non-temporal so that they do not push
 // the exchange lines out of the L2 (backward 5.0 -> 4.8 us per timestep); non-temporal LOADS of the operands were measured too and lose (6.2 us)
 #define CL_NTL 0
 #define CL_NTS 2
-#define CL_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #define CL_FENCE() asm volatile("" ::: "memory")
 
 #ifdef CL_TRACE     // development only (profiles/tools/cluster_trace.py): wall-clock stamps (100 MHz) of wave 0 of workgroup 0, [direction][step][stage]
@@ -46,65 +46,6 @@ extern "C" int mnn_lstm_cluster_trace(void* out) {
 #define CL_TR_DECL do { } while (0)
 #define CL_TR_FLUSH(dir, step) do { } while (0)
 #endif
-
-__device__ __forceinline__ unsigned cl_ld(const unsigned* p) { return __hip_atomic_load((cl_gu32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void cl_st(unsigned* p, unsigned v) { __hip_atomic_store((cl_gu32*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// One wave waits until the first n (<= 32) words of `line` are all >= need; the upper lanes watch the status word.  false: the launch is aborting.
-__device__ __forceinline__ bool cl_wait(const unsigned* line, unsigned* status, int n, unsigned need) {
-    const int lane = threadIdx.x & 63;
-    const bool mine = lane < n;
-    const unsigned* p = mine ? line + lane : status;
-    const long long t0 = wall_clock64();
-    for (unsigned spins = 1;; ++spins) {
-        const unsigned v = cl_ld(p);
-        if (__all(mine ? v >= need : v == 0u)) return true;
-        const bool dead = __any(!mine && v != 0u) || ((spins & 127u) == 0u && wall_clock64() - t0 > CL_LIMIT);
-        if (dead) {
-            if (lane == 0) { cl_st(status, 1u); cl_st(status + 1, 1u); }       // [1]: sticky, never re-zeroed by a launch
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-// Launch start: do the eight workgroups of this cluster share an XCD?  Each posts 0x100 | XCC_ID (device scope), wave 0 waits for the others
-// (bounded) and compares.  The answer selects the hand-off policy (results never depend on it): on one XCD the tiles and flags are stored
-// write-BACK into a TWO-deep area -- they stay in that XCD's L2, which the consumers' L1-bypassing loads hit --, otherwise write-through into
-// one slot per timestep (a line of another XCD's L2 is never re-used within the launch).
-__device__ __forceinline__ void cl_probe_xcd(unsigned* xline, unsigned* status, int member, int* s_local) {
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    if (threadIdx.x == 0) cl_st(xline + member, 0x100u | (xcc & 0xfu));
-    if (threadIdx.x < 64) {
-        bool same = false;
-        if (cl_wait(xline, status, 8, 1u)) {
-            const unsigned v = cl_ld(xline + (threadIdx.x < 8u ? threadIdx.x : 0));
-            same = __all(v == __builtin_amdgcn_readfirstlane(v));
-        }
-        if (threadIdx.x == 0) *s_local = same ? 1 : 0;
-    }
-}
-__device__ __forceinline__ void cl_raise(unsigned* flag, unsigned value, bool local) {        // one lane, after the wave's vmcnt(0)
-    if (local) __hip_atomic_store((cl_gu32*)flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // plain store: lands in the shared L2
-    else cl_st(flag, value);
-}
-#define CL_VMC(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-__device__ __forceinline__ void cl_wait_all_but(int n) {       // loads, stores and LDS-DMA of a wave complete in issue order (MI355X_MICROARCH.md)
-    switch (n) {
-        CL_VMC(0) CL_VMC(1) CL_VMC(2) CL_VMC(3) CL_VMC(4) CL_VMC(5) CL_VMC(6) CL_VMC(7) CL_VMC(8)
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-// LDS-DMA in inline assembly (the builtin makes the compiler drain vmcnt(0) in front of every LDS read that may alias its destination:
-// lstm_resident.hip); the sc1 form bypasses the L1 (the exchange area is re-written every other step)
-__device__ __forceinline__ void cl_dma16(const void* g, const void* l) {
-    asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"((unsigned)(uintptr_t)(cl_lptr_t)const_cast<void*>(l)), "v"(g) : "memory", "m0");
-}
-__device__ __forceinline__ void cl_dma16_sc1(const void* g, const void* l) {
-    asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off sc1" :: "s"((unsigned)(uintptr_t)(cl_lptr_t)const_cast<void*>(l)), "v"(g) : "memory", "m0");
-}
-__device__ __forceinline__ void cl_dma4(const void* g, const void* l) {
-    asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dword %1, off" :: "s"((unsigned)(uintptr_t)(cl_lptr_t)const_cast<void*>(l)), "v"(g) : "memory", "m0");
-}
 
 struct ClFwdArgs {
     const h16_t* xproj; const h16_t* wh_t; h16_t* gates; float* c; h16_t* h; h16_t* y; const uint8_t* mask;
@@ -159,10 +100,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int ub = 64 * mem + 16 * w;                                           // first unit of this wave
     const size_t us = (size_t)B * U;
     const float ikp = 1.0f / A.kp;
-    unsigned* status = A.sync;
-    unsigned* flags = A.sync + CL_FLAGS_OFF + 32 * cl;
+    unsigned* status = A.sync + HF_STATUS_WORD;
+    unsigned* flags = A.sync + HF_FLAGS_OFF + 32 * cl;
     int* s_local = reinterpret_cast<int*>(smem + G::OFF_L);
-    cl_probe_xcd(A.sync + CL_FLAGS_OFF + 32 * A.ncl + 32 * cl, status, mem, s_local);
+    hf_probe_xcd(A.sync + HF_FLAGS_OFF + 32 * A.ncl + 32 * cl, status, mem, 8, s_local);
 
     // ---- the recurrent weights of this wave's 16 units: two tiles x 32 k-steps of A fragments, all pinned to AGPRs ----
     frag_t wr[2][32];
@@ -199,16 +140,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     auto stage = [&](int t, int buf) {
         const char* xb = xsrc + (size_t)t * us * 8;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) cl_dma16(xb + (size_t)(2 * (4 * w + i)) * U * 8, smem + G::OFF_X + buf * G::XB + (4 * w + i) * G::PX);
+        for (int i = 0; i < 4; ++i) hf_dma16(xb + (size_t)(2 * (4 * w + i)) * U * 8, smem + G::OFF_X + buf * G::XB + (4 * w + i) * G::PX);
         if (DROP) {
 #pragma unroll
-            for (int i = 0; i < 2; ++i) cl_dma4(msrc + (size_t)t * us + (size_t)(4 * (2 * w + i)) * U, smem + G::OFF_M + buf * G::MB + (2 * w + i) * 256);
+            for (int i = 0; i < 2; ++i) hf_dma4(msrc + (size_t)t * us + (size_t)(4 * (2 * w + i)) * U, smem + G::OFF_M + buf * G::MB + (2 * w + i) * 256);
         }
     };
     constexpr int NSTG = 4 + (DROP ? 2 : 0);
     stage(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    CL_BARRIER();
+    hf_lds_barrier();
     const bool local = A.allow_local != 0 && *s_local != 0;
 
     // ---- the exchange area of this cluster: slots of 32 rows x 512 units (row-major, 1 KB per row) ----
@@ -218,7 +159,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     auto pull = [&](int slot, int buf) {                                        // rows 8w..8w+7 of the tile, one 1 KB row per instruction
         const char* src = xch + (size_t)slot * 32768 + lane * 16;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) cl_dma16_sc1(src + (8 * w + i) * 1024, smem + G::OFF_H + buf * G::HB + (8 * w + i) * G::PH);
+        for (int i = 0; i < 8; ++i) hf_dma16_sc1(src + (8 * w + i) * 1024, smem + G::OFF_H + buf * G::HB + (8 * w + i) * G::PH);
     };
 
     // ---- outputs (buffer stores: scalar per-step base, one lane offset; a store whose lane offset is pushed out of range is dropped) ----
@@ -252,13 +193,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     for (int t = 0; t < T; ++t) {
         CL_TR(0);
         if (t > 0) {
-            if (!cl_wait(flags, status, 32, (unsigned)t)) return;                // every wave of the cluster has stored its block of h[t-1]
+            if (!hf_wait(flags, status, 32, (unsigned)t)) return;                // every wave of the cluster has stored its block of h[t-1]
             CL_TR(1);
             pull(local ? (t - 1) & 1 : t - 1, t & 1);
         }
         stage(t + 1 < T ? t + 1 : t, (t + 1) & 1);                              // unconditional (clamped)
-        cl_wait_all_but(NSTG);                                                  // the pulled rows are in LDS (the staging of step t + 1 may still fly)
-        CL_BARRIER();
+        hf_wait_all_but(NSTG);                                                  // the pulled rows are in LDS (the staging of step t + 1 may still fly)
+        hf_lds_barrier();
         CL_TR(2);
         const char* hin = smem + G::OFF_H + (t & 1) * G::HB + row * G::PH + hf * 16;
         const char* xin = smem + G::OFF_X + (t & 1) * G::XB + (row >> 1) * G::PX + (row & 1) * 512 + (16 * w + hf) * 8;
@@ -332,7 +273,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         const u32x4_t hx = *reinterpret_cast<const u32x4_t*>(sw + G::S_H + (lane >> 1) * G::PR + (lane & 1) * 16);
         const unsigned so_x = (unsigned)((local ? t & 1 : t) * 32768);
         if (local) __builtin_amdgcn_raw_buffer_store_b128(hx, rs_x, vo_x, so_x, 0);
-        else __builtin_amdgcn_raw_buffer_store_b128(hx, rs_x, vo_x, so_x, CL_SC1);
+        else __builtin_amdgcn_raw_buffer_store_b128(hx, rs_x, vo_x, so_x, HF_SC1);
         CL_FENCE();
         // the row-major outputs are read back while the hand-off store is on its way ...
         u32x4_t og[4], oc[2], oy = hx, ohT, oyT;
@@ -346,7 +287,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         for (int i = 0; i < 2; ++i) oc[i] = *reinterpret_cast<const u32x4_t*>(sw + G::S_C + (16 * i + (lane >> 2)) * G::PC + (lane & 3) * 16);
         if (DROP) oy = *reinterpret_cast<const u32x4_t*>(sw + G::S_Y + (lane >> 1) * G::PR + (lane & 1) * 16);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                         // ... the hand-off store is out (nothing younger has been issued)
-        if (lane == 0) cl_raise(flags + 4 * mem + w, (unsigned)(t + 1), local);
+        if (lane == 0) hf_raise(flags + 4 * mem + w, (unsigned)(t + 1), local);
         CL_FENCE();
         CL_TR(4);
         // ... and leave behind the flag.  (Measured and dropped: holding them in registers and issuing them at the START of the next step, behind its
@@ -422,10 +363,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int row0 = 32 * cl;
     const size_t us = (size_t)B * U;
     const float ikp = 1.0f / A.kp;
-    unsigned* status = A.sync;
-    unsigned* flags = A.sync + CL_FLAGS_OFF + 32 * cl;
+    unsigned* status = A.sync + HF_STATUS_WORD;
+    unsigned* flags = A.sync + HF_FLAGS_OFF + 32 * cl;
     int* s_local = reinterpret_cast<int*>(smem + G::OFF_L);
-    cl_probe_xcd(A.sync + CL_FLAGS_OFF + 32 * A.ncl + 32 * cl, status, mem, s_local);
+    hf_probe_xcd(A.sync + HF_FLAGS_OFF + 32 * A.ncl + 32 * cl, status, mem, 8, s_local);
 
     // ---- producer side: Wh[unit][the member's 256 gate columns] for the units [128 w, 128 w + 128): four tiles x 16 k-steps of A fragments, in AGPRs ----
     frag_t wr[4][16];
@@ -477,12 +418,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         }
     }
     request(T - 1);
-    CL_BARRIER();
+    hf_lds_barrier();
     const bool local = A.allow_local != 0 && *s_local != 0;
     if (*s_local == 0) {
         // the two-deep exchange area is re-written every other step: only valid while the cluster shares one L2.  Give up loudly (sticky status word).
         // (mnn_lstm_cluster_bwd_ok asks the placement on the host before this form is chosen: reaching this line means the probe and the launch disagree)
-        if (tid == 0) { cl_st(status, 1u); cl_st(status + 1, 1u); }
+        if (tid == 0) hf_give_up(status);
         return;
     }
 
@@ -584,17 +525,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         pre(0);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                         // this wave's partials are out
-        if (lane == 0) cl_raise(flags + 4 * mem + w, (unsigned)(kk + 1), local);
+        if (lane == 0) hf_raise(flags + 4 * mem + w, (unsigned)(kk + 1), local);
         CL_TR(2);
         __builtin_amdgcn_sched_barrier(0);
         pre(1);
         __builtin_amdgcn_sched_barrier(0);
-        if (!cl_wait(flags, status, 32, (unsigned)(kk + 1))) return;             // every wave of the cluster has stored its partials of this step
+        if (!hf_wait(flags, status, 32, (unsigned)(kk + 1))) return;             // every wave of the cluster has stored its partials of this step
         CL_TR(3);
         float dhr[2][4];
         u32x4_t pq[8];
 #pragma unroll
-        for (int s8 = 0; s8 < 8; ++s8) pq[s8] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, vo_xl + 1024 * s8, xb, CL_SC1);
+        for (int s8 = 0; s8 < 8; ++s8) pq[s8] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, vo_xl + 1024 * s8, xb, HF_SC1);
         __builtin_amdgcn_sched_barrier(0);
         // the previous step's outputs (dz[t+1], still in the tile the MFMAs read) leave HERE, behind the requests for the partial sums and while
         // those travel: in the MFMA stream, in front of the partial stores, they delayed the flag (a wave's stores are acknowledged in issue
@@ -645,7 +586,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         }
         CL_TR(5);
         request(t > 0 ? t - 1 : 0);                     // unconditional (clamped): behind a condition the compiler COPIES the freshly requested registers at the join -- and waits for the loads to do it
-        CL_BARRIER();
+        hf_lds_barrier();
         CL_TR(6);
         CL_TR_FLUSH(1, kk);
     }
@@ -687,7 +628,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             v[1] = (unsigned)zf[2] | ((unsigned)zf[3] << 16);
             *reinterpret_cast<u32x2_t*>(smem + G::OFF_Z + (T & 1) * G::ZB + row * G::PZ + (gate_perm_col(2, u0 + 8 * a) - 256 * mem) * 2) = v;
         }
-        CL_BARRIER();
+        hf_lds_barrier();
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -710,9 +651,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-void mnn_rp_workspace_layout(int nrt, int U, size_t* sync_bytes, size_t* xchg_off);           // lstm_rowpar.hip: the workspace both forms share
-int mnn_rp_reset_launch(hipStream_t st, void* workspace, int nrt, int U);
-
 // 32 rows per cluster of eight workgroups, every workgroup on its own CU, the clusters dealt evenly over the 8 XCDs
 static bool cl_shape_ok(int B, int units) { return units == 512 && B > 0 && (B % 256) == 0 && (B / 32) * 8 <= mnn_cu_count(); }
 
@@ -748,8 +686,7 @@ extern "C" int mnn_lstm_cluster_ok(int B, int units) {
 // workgroups post their XCC id), not found out by a training step that has already consumed unwritten gradients.
 __global__ void __launch_bounds__(256) cl_place_probe_kernel(unsigned* __restrict__ out) {
     extern __shared__ char cl_probe_smem_[];
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    const unsigned xcc = hf_xcc_id();
     if (threadIdx.x == 0) {
         cl_probe_smem_[0] = (char)xcc;                       // (the dynamic LDS is what keeps one workgroup per CU, as in the real launch)
         out[blockIdx.x] = 0x100u | (xcc & 0xfu);
@@ -844,7 +781,7 @@ extern "C" int mnn_lstm_cluster_fwd_multi(mnn_stream_t s, int T, int B, int njob
     MNN_REQUIRE(((njobs * (B / 32)) & 7) == 0, "mnn_lstm_cluster_fwd_multi: the grid's clusters must be a multiple of 8");
     MNN_HIP(cl_prepare());
     for (int i = 0; i < njobs; ++i)
-        if (int rc = mnn_rp_reset_launch(st, workspaces[i], B / 32, 512)) return rc;
+        if (int rc = mnn_rp_reset_launch(st, workspaces[i], B / 32)) return rc;
     hipLaunchKernelGGL(cl_fwd_kernel(L->f16 != 0, L->mask != nullptr, L->gates != nullptr), dim3(8 * njobs * (B / 32)), dim3(256), ClGeom::LDS, st, j);
     MNN_LAUNCH_CHECK();
     return MNN_OK;
@@ -890,7 +827,7 @@ extern "C" int mnn_lstm_cluster_bwd_state_multi(mnn_stream_t s, int T, int B, in
     MNN_REQUIRE(((njobs * (B / 32)) & 7) == 0, "mnn_lstm_cluster_bwd[_state]_multi: the grid's clusters must be a multiple of 8");
     MNN_HIP(cl_prepare());
     for (int i = 0; i < njobs; ++i)
-        if (int rc = mnn_rp_reset_launch(st, workspaces[i], B / 32, 512)) return rc;
+        if (int rc = mnn_rp_reset_launch(st, workspaces[i], B / 32)) return rc;
     hipLaunchKernelGGL(cl_bwd_kernel(L->f16 != 0, j.job[0].mask != nullptr), dim3(8 * njobs * (B / 32)), dim3(256), ClBwdGeom::LDS, st, j);
     MNN_LAUNCH_CHECK();
     return MNN_OK;

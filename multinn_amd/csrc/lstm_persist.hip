@@ -6,25 +6,23 @@
 //     recurrent weights in REGISTERS (32 units x K, K split over the waves) -- weights are read once per launch;
 //   * the 32-row hidden-state tiles move between workgroups through an EXCHANGE area in global memory, laid out in MFMA
 //     A-fragment order ([t][row tile][k-step][lane][8 bf16]) so that every hand-off load and store instruction moves one
-//     contiguous KiB: 16-byte write-through (sc1) stores, `s_waitcnt vmcnt(0)` in every storing wave, workgroup
-//     barrier, one sc1 flag store per workgroup; consumers poll the flags of their row tile with sc1 loads from one wave,
-//     join a barrier, then read with 16-byte sc1 buffer loads (MI355X_MICROARCH.md, "Valid forms", first table row;
-//     cdna_hip_programming.md G16 R1).  The row-major copies the rest of the train step needs are written with plain
-//     stores one item later, off the chain (after the next hand-off's loads have been issued);
+//     contiguous KiB.  The hand-off is the protocol of lstm_handoff.h with a WORKGROUP as the unit: every storing wave
+//     drains its stores, the workgroup meets at a barrier, one lane raises the workgroup's flag (pst_publish); wave 0 of a
+//     consumer polls the flag line of its row tile and the others join it at a barrier (pst_wait).  The row-major copies
+//     the rest of the train step needs are written with plain stores one item later, off the chain (after the next
+//     hand-off's loads have been issued);
 //   * only workgroups of the same ROW TILE ever wait for each other (16 + 8 of them for units 512/256), never the grid;
 //   * layer 2 consumes layer 1's step t as soon as its flags say so: its input projection is folded into its step
 //     (K = U1 + U2), so the xproj round trip of the launch-per-step form disappears too.
-// Every spin is bounded (1 s of the 100 MHz realtime counter) and watches a status word: a workgroup that gives up
-// sets it and every other one leaves at its next poll, so the grid always drains.  The host entry refuses shapes whose
-// grid is not resident at once (one workgroup per CU).  Block -> tile map: blocks with equal (id % G) share a row tile,
-// so with G = 8 a row tile's workgroups share an XCD under round-robin dispatch (speed only, never correctness).
+// Spins, give-up and the sticky word: lstm_handoff.h.  The host entry refuses shapes whose grid is not resident at once
+// (one workgroup per CU).  Block -> tile map: blocks with equal (id % G) share a row tile, so with G = 8 a row tile's
+// workgroups share an XCD under round-robin dispatch (speed only, never correctness).
 #include "common.h"
+#include "lstm_handoff.h"
 #include <stdlib.h>
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) unsigned gu32;
 
 #ifdef PST_TRACE     // development only: per-stage timestamps of one workgroup per role (profiles/tools/persist_trace.hip reads them)
 __device__ long long pst_trace[4][512][8];
@@ -34,30 +32,16 @@ __device__ long long pst_trace[4][512][8];
 #define PST_TR(ptr, k) do { } while (0)
 #define PST_TRP(role, cond, step) nullptr
 #endif
-#define PST_LIMIT 100000000LL      // spin bound: 1 s of wall_clock64() (100 MHz)
-#define PST_FLAGS_OFF 32           // words: [0] status, [32 + 32*rt + member] progress flags, then one sticky word
-#define PST_SC1 16                 // aux bit of raw buffer loads/stores: device-scope (write-through / L1-bypassing)
+// sync words: [HF_STATUS_WORD] status, [HF_FLAGS_OFF + 32 rt + member] progress flags, one XCC-id line per row-tile group from xcc_off, and
+// the sticky word at sticky_off, behind the edge slabs (the whole sync area is zeroed by one memset per launch)
 
-__device__ __forceinline__ unsigned ld_agent(const unsigned* p) { return __hip_atomic_load((gu32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent(unsigned* p, unsigned v) { __hip_atomic_store((gu32*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t slice_rsrc(const void* base, size_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 // k-steps [f0, f0+KS) of one exchange slab ([k-step][lane][16 B]): one contiguous KiB per instruction
 template <int KS, typename V>
 __device__ __forceinline__ void load_frags_xchg(const void* slab, size_t slab_bytes, int f0, V (&f)[KS]) {
-    const __amdgpu_buffer_rsrc_t rs = slice_rsrc(slab, slab_bytes);
+    const __amdgpu_buffer_rsrc_t rs = hf_rsrc(slab, slab_bytes);
     const int off = (f0 * 64 + (int)(threadIdx.x & 63)) * 16;
 #pragma unroll
-    for (int s = 0; s < KS; ++s) f[s] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 1024 * s, 0, PST_SC1));
-}
-// `local`: every workgroup of this row tile sits on ONE XCD (checked at launch start, pst_same_xcd): then the tile is stored
-// write-BACK -- it stays in that XCD's L2, which all of them share, and the consumers' sc1 (L1-bypassing, L2-served) loads hit
-// it there instead of fetching a write-through line back through the fabric.  Otherwise write-through (device scope).
-__device__ __forceinline__ void store_frag_xchg(void* slab, size_t slab_bytes, int f, int lane, u32x4_t v, bool local) {
-    if (local) __builtin_amdgcn_raw_buffer_store_b128(v, slice_rsrc(slab, slab_bytes), (f * 64 + lane) * 16, 0, 0);
-    else __builtin_amdgcn_raw_buffer_store_b128(v, slice_rsrc(slab, slab_bytes), (f * 64 + lane) * 16, 0, PST_SC1);
+    for (int s = 0; s < KS; ++s) f[s] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 1024 * s, 0, HF_SC1));
 }
 template <int KS, typename V>
 __device__ __forceinline__ void load_frags_plain(const bf16_t* __restrict__ p, V (&f)[KS]) {
@@ -65,17 +49,13 @@ __device__ __forceinline__ void load_frags_plain(const bf16_t* __restrict__ p, V
     for (int s = 0; s < KS; ++s) f[s] = *reinterpret_cast<const V*>(p + 16 * s);
 }
 
-// Workgroup barrier that waits for this wave's LDS traffic only: __syncthreads() also drains vmcnt(0), which would make
-// every barrier of a step wait for the prefetch loads (HBM latency) and deferred stores issued just before it.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // Wave 0 polls one 128-byte line of progress flags: lanes [0,n1) need >= need1, lanes [n1,nm) need >= need2, the rest
 // watch the status word.  All threads of the workgroup call this; returns false (uniformly) when the launch is aborting.
 // `peek` (optional): this lane's word of the SAME line read ahead of time by pst_peek -- flags only grow, so an early observation that
 // already satisfies the wait is as good as a fresh one and saves the poll's round trip (~0.35 us) at the top of the item.
 __device__ __forceinline__ unsigned pst_peek(const unsigned* line, const unsigned* status, int nm) {
     const int lane = threadIdx.x & 63;                  // every wave reads (unconditional load: no wait is forced behind it); wave 0 uses it
-    return ld_agent(lane < nm ? line + lane : status);
+    return hf_ld(lane < nm ? line + lane : status);
 }
 __device__ __forceinline__ bool pst_wait(const unsigned* line, unsigned* status, int n1, unsigned need1, int nm, unsigned need2, int* s_abort,
                                          int sticky_off, bool have_peek = false, unsigned peek = 0u) {
@@ -86,17 +66,17 @@ __device__ __forceinline__ bool pst_wait(const unsigned* line, unsigned* status,
         const unsigned* p = mine ? line + lane : status;
         const long long t0 = wall_clock64();
         for (unsigned spins = 1;; ++spins) {
-            const unsigned v = (have_peek && spins == 1u) ? peek : ld_agent(p);
+            const unsigned v = (have_peek && spins == 1u) ? peek : hf_ld(p);
             if (__all(mine ? v >= need : v == 0u)) break;
-            const bool dead = __any(!mine && v != 0u) || ((spins & 127u) == 0u && wall_clock64() - t0 > PST_LIMIT);
+            const bool dead = __any(!mine && v != 0u) || ((spins & 127u) == 0u && wall_clock64() - t0 > HF_LIMIT);
             if (dead) {
-                if (lane == 0) { st_agent(status, 1u); st_agent(status + sticky_off, 1u); *s_abort = 1; }   // sticky: survives the next launch's re-zeroing
+                if (lane == 0) { hf_give_up(status, sticky_off); *s_abort = 1; }
                 break;
             }
             __builtin_amdgcn_s_sleep(1);
         }
     }
-    lds_barrier();
+    hf_lds_barrier();
     return *reinterpret_cast<volatile int*>(s_abort) == 0;
 }
 
@@ -104,21 +84,17 @@ __device__ __forceinline__ bool pst_wait(const unsigned* line, unsigned* status,
 __device__ __forceinline__ void pst_publish(unsigned* flag, unsigned value, bool local) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) {
-        if (local) __hip_atomic_store((gu32*)flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);     // plain store: lands in the shared L2
-        else st_agent(flag, value);
-    }
+    if (threadIdx.x == 0) hf_raise(flag, value, local);
 }
 
 // Launch start: do the nm workgroups of this row-tile group share an XCD?  Each posts 0x100 | XCC_ID (device scope), waits for
 // the others (bounded) and compares.  The answer only selects the store policy of the hand-offs; results never depend on it.
 __device__ __forceinline__ bool pst_same_xcd(unsigned* xline, unsigned* status, int member, int nm, int* s_abort, int* s_local, int sticky_off) {
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    if (threadIdx.x == 0) st_agent(xline + member, 0x100u | (xcc & 0xfu));
+    const unsigned xcc = hf_xcc_id();
+    if (threadIdx.x == 0) hf_st(xline + member, 0x100u | (xcc & 0xfu));
     if (!pst_wait(xline, status, nm, 1u, nm, 1u, s_abort, sticky_off)) return false;
     if (threadIdx.x < 64) {
-        const unsigned v = ld_agent(xline + (threadIdx.x < (unsigned)nm ? threadIdx.x : 0));
+        const unsigned v = hf_ld(xline + (threadIdx.x < (unsigned)nm ? threadIdx.x : 0));
         const unsigned v0 = __builtin_amdgcn_readfirstlane(v);
         const bool same = __all(v == v0);
         if (threadIdx.x == 0) *s_local = same ? 1 : 0;
@@ -172,7 +148,7 @@ __device__ __forceinline__ void pf_finish(const PFwdLayer& L, FwdTiles& S, int T
         if (L.yT != nullptr) S.sYT[r][lr] = yb;
     }
     tl.t = t; tl.m0 = rt * 32; tl.valid = true;
-    lds_barrier();
+    hf_lds_barrier();
     PST_TR(trc, 3);
     {   // exchange slab of (t, row tile): k-steps 2nt, 2nt+1 of this unit tile; waves 0,1 store h, waves 2,3 the dropped y
         const size_t slab = (size_t)(L.U / 16) * 1024;
@@ -181,7 +157,7 @@ __device__ __forceinline__ void pf_finish(const PFwdLayer& L, FwdTiles& S, int T
         if (!second || (drop && L.yx != nullptr)) {
             const bf16_t (*src)[40] = second ? S.sY : S.sH;
             const u32x4_t v = *reinterpret_cast<const u32x4_t*>(&src[r][ks * 16 + hh * 8]);
-            store_frag_xchg((second ? L.yx : L.hx) + ((size_t)t * nrt + rt) * slab, slab, 2 * nt + ks, lane, v, local);
+            hf_store_frag(hf_rsrc((second ? L.yx : L.hx) + ((size_t)t * nrt + rt) * slab, slab), 2 * nt + ks, lane, v, local);
         }
     }
     pst_publish(flag, (unsigned)(t + 1), local);
@@ -316,8 +292,8 @@ __global__ void __launch_bounds__(256) lstm2_persist_fwd_kernel(PFwdArgs A) {
     const int r = lane & 31, hh = lane >> 5;
     const int T = A.T, B = A.B, nrt = A.nrt;
     const int Rv = (nrt - grp + A.G - 1) / A.G;            // row tiles of this workgroup: grp, grp + G, ...
-    unsigned* status = A.sync;
-    unsigned* flags = A.sync + PST_FLAGS_OFF;
+    unsigned* status = A.sync + HF_STATUS_WORD;
+    unsigned* flags = A.sync + HF_FLAGS_OFF;
     const float* zero = reinterpret_cast<const float*>(A.sync + 4);
     if (threadIdx.x == 0) { S.abort = 0; S.local = 0; }
     __syncthreads();
@@ -400,7 +376,7 @@ __global__ void __launch_bounds__(256) lstm2_persist_fwd_kernel(PFwdArgs A) {
 #pragma unroll
                 for (int wc = 0; wc < 4; ++wc)
                     red4[((w * 4 + g) * 4 + wc) * 64 + lane] = make_float4(acc[g][4 * wc], acc[g][4 * wc + 1], acc[g][4 * wc + 2], acc[g][4 * wc + 3]);
-            lds_barrier();
+            hf_lds_barrier();
             float z[4][4], cp[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -496,7 +472,7 @@ __global__ void __launch_bounds__(256) lstm2_persist_fwd_kernel(PFwdArgs A) {
 #pragma unroll
                 for (int wc = 0; wc < 4; ++wc)
                     red4[((w * 4 + g) * 4 + wc) * 64 + lane] = make_float4(acc[g][4 * wc], acc[g][4 * wc + 1], acc[g][4 * wc + 2], acc[g][4 * wc + 3]);
-            lds_barrier();
+            hf_lds_barrier();
             float z[4][4], cp[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -588,12 +564,12 @@ __device__ __forceinline__ void pb_finish(const PBwdLayer& L, BwdTiles& S, int B
         }
     }
     tl.t = t; tl.m0 = rt * 32; tl.valid = true;
-    lds_barrier();
+    hf_lds_barrier();
     PST_TR(trc, 3);
     {   // k-steps 8nt .. 8nt+7 of the slab, one per wave: a contiguous KiB per store instruction
         const size_t slab = (size_t)(4 * L.U / 16) * 1024;
         const u32x4_t v = *reinterpret_cast<const u32x4_t*>(&S.sZ[r][w * 16 + hh * 8]);
-        store_frag_xchg(L.dzx + ((size_t)t * nrt + rt) * slab, slab, 8 * nt + w, lane, v, local);
+        hf_store_frag(hf_rsrc(L.dzx + ((size_t)t * nrt + rt) * slab, slab), 8 * nt + w, lane, v, local);
     }
     pst_publish(flag, epoch, local);
     PST_TR(trc, 4);
@@ -681,8 +657,8 @@ __global__ void __launch_bounds__(512) lstm2_persist_bwd_kernel(PBwdArgs A) {
     const int T = A.T, B = A.B, nrt = A.nrt;
     const int Rv = (nrt - grp + A.G - 1) / A.G;
     const int n_items = T * Rv;
-    unsigned* status = A.sync;
-    unsigned* flags = A.sync + PST_FLAGS_OFF;
+    unsigned* status = A.sync + HF_STATUS_WORD;
+    unsigned* flags = A.sync + HF_FLAGS_OFF;
     const float* zero = reinterpret_cast<const float*>(A.sync + 4);
     if (threadIdx.x == 0) { S.abort = 0; S.local = 0; }
     __syncthreads();
@@ -731,7 +707,7 @@ __global__ void __launch_bounds__(512) lstm2_persist_bwd_kernel(PBwdArgs A) {
             pb_tail(L, S, B, Rv, nt, tl);                    // the previous item's plain stores issue while the MFMA chain runs
 #pragma unroll
             for (int wc = 0; wc < 8; ++wc) red2[((0 * 8 + w) * 8 + wc) * 64 + lane] = make_float2(acc[2 * wc], acc[2 * wc + 1]);     // 8-byte slots: see the forward kernel
-            lds_barrier();
+            hf_lds_barrier();
             float dh[2], e_dc[2];
             float sum2[2] = {0.f, 0.f};
 #pragma unroll
@@ -794,7 +770,7 @@ __global__ void __launch_bounds__(512) lstm2_persist_bwd_kernel(PBwdArgs A) {
                 red2[((0 * 8 + w) * 8 + wc) * 64 + lane] = make_float2(accq[2 * wc], accq[2 * wc + 1]);
                 red2[((1 * 8 + w) * 8 + wc) * 64 + lane] = make_float2(accw[2 * wc], accw[2 * wc + 1]);
             }
-            lds_barrier();
+            hf_lds_barrier();
             float dh[2], e_dc[2];
             float sq2[2] = {0.f, 0.f}, sw2[2] = {0.f, 0.f};
 #pragma unroll
@@ -838,7 +814,7 @@ static bool persist_plan(int B, int u1, int u2, int& nrt, int& G, int& R) {
 
 // workspace: [status | 31 zero words][32 flags per row tile][boundary slabs: layer 1, layer 2 (zeros / h0)] -- one memset
 // per call covers all of that -- [sticky word, padded][exchange area]
-static size_t sync_words(int nrt) { return (size_t)PST_FLAGS_OFF + 64 * (size_t)nrt; }       // flags lines, then one XCC-id line per row-tile group
+static size_t sync_words(int nrt) { return (size_t)HF_FLAGS_OFF + 64 * (size_t)nrt; }       // flags lines, then one XCC-id line per row-tile group
 static size_t edge_bytes(int nrt, int u1, int u2, bool bwd) { return (size_t)nrt * (bwd ? 256 : 64) * ((size_t)u1 + u2); }
 static size_t edge_max(int nrt, int u1, int u2) { return edge_bytes(nrt, u1, u2, true); }
 static size_t sticky_offset(int nrt, int u1, int u2) { return sync_words(nrt) * sizeof(unsigned) + edge_max(nrt, u1, u2); }
@@ -908,7 +884,7 @@ extern "C" int mnn_lstm2_persist_fwd(mnn_stream_t s, int T, int B, const mnn_lst
     const int u1 = L1->units, u2 = L2->units;
     a.l1 = fwd_layer(L1); a.l2 = fwd_layer(L2);
     a.T = T; a.B = B; a.kp = keep_prob; a.sync = (unsigned*)workspace;
-    a.xcc_off = PST_FLAGS_OFF + 32 * a.nrt; a.allow_local = mnn_persist_allow_local();
+    a.xcc_off = HF_FLAGS_OFF + 32 * a.nrt; a.allow_local = mnn_persist_allow_local();
     a.sticky_off = (int)(sticky_offset(a.nrt, L1->units, L2->units) / sizeof(unsigned));   // the aborting workgroup sets it; never re-zeroed
     const size_t per = (size_t)T * a.nrt;
     char* edge = (char*)workspace + sync_words(a.nrt) * sizeof(unsigned);
@@ -962,7 +938,7 @@ extern "C" int mnn_lstm2_persist_bwd(mnn_stream_t s, int T, int B, const mnn_lst
     const int u1 = L1->units, u2 = L2->units;
     a.l1 = bwd_layer(L1); a.l2 = bwd_layer(L2);
     a.T = T; a.B = B; a.kp = keep_prob; a.sync = (unsigned*)workspace;
-    a.xcc_off = PST_FLAGS_OFF + 32 * a.nrt; a.allow_local = mnn_persist_allow_local();
+    a.xcc_off = HF_FLAGS_OFF + 32 * a.nrt; a.allow_local = mnn_persist_allow_local();
     a.sticky_off = (int)(sticky_offset(a.nrt, L1->units, L2->units) / sizeof(unsigned));   // the aborting workgroup sets it; never re-zeroed
     const size_t per = (size_t)T * a.nrt;
     char* edge = (char*)workspace + sync_words(a.nrt) * sizeof(unsigned);

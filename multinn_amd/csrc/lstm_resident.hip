@@ -15,11 +15,13 @@
 // A wave owns 64 units = 4 groups = 4 pairs per lane; the 12 of 16 MFMA columns that repeat rows are the price of a 4-row workgroup (the
 // matrix must be streamed through the matrix cores once per step whatever the row count: 2048 cycles), which in turn is what spreads the
 // pointwise of B x u pairs over all 1024 SIMDs.
+//
+// Of lstm_handoff.h only the single-workgroup pieces are used: the counted vmcnt wait for the step's own LDS-DMA, the LDS-only barrier, the DMA forms.
 #include "common.h"
+#include "lstm_handoff.h"
 
 __device__ __forceinline__ float dpp_xor2(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xf, 0xf, false)); }
 __device__ __forceinline__ float dpp_xor1(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, false)); }
-#define RES_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 #ifdef RES_TRACE     // development only (profiles/tools/resident_trace.py): wall-clock stamps (100 MHz) of wave 0 of workgroup 0, [direction][step][stage]
 __device__ long long res_trace[2][512][12];
@@ -71,18 +73,7 @@ template <int U> struct ResGeom {
 // the 8-byte pieces that neighbouring row groups write into one 128-byte line of a transposed output then meet in ONE L2
 __device__ __forceinline__ int res_row_group(int b, int nblk) { return (nblk & 7) == 0 ? (b & 7) * (nblk >> 3) + (b >> 3) : b; }
 
-typedef __attribute__((address_space(1))) const void* res_gptr_t;
-typedef __attribute__((address_space(3))) void* res_lptr_t;
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-#define RES_VMC(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-__device__ __forceinline__ void res_wait_all_but(int n) {       // loads, stores and LDS-DMA of a wave complete in issue order (MI355X_MICROARCH.md)
-    switch (n) {
-        RES_VMC(0) RES_VMC(1) RES_VMC(2) RES_VMC(3) RES_VMC(4) RES_VMC(5) RES_VMC(6) RES_VMC(7) RES_VMC(8) RES_VMC(9) RES_VMC(10) RES_VMC(11) RES_VMC(12)
-        RES_VMC(13) RES_VMC(14) RES_VMC(15) RES_VMC(16)
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
 
 template <int U, typename F, bool DROP, bool SAVE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) lstm_res_fwd_kernel(ResFwdJobs J) {
@@ -138,25 +129,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     // ---- staging of a step's xproj rows (4 x 8u bytes) and keep bytes (4 x u) a step ahead, global -> LDS without registers: wave w moves row w ----
     const char* xsrc = reinterpret_cast<const char*>(A.xproj) + ((size_t)(row0 + w) * U) * 8 + lane * 16;
     const uint8_t* msrc = DROP ? A.mask + (size_t)(row0 + w) * U + lane * 4 : nullptr;
-    // LDS-DMA in inline assembly: the compiler puts `s_waitcnt vmcnt(0)` in front of every LDS read that may alias the destination of a
-    // __builtin_amdgcn_global_load_lds -- here the reads of THIS step's staged rows, one buffer over: the whole memory latency on the chain of
-    // every step (3.5 us per step measured).  The step waits for its own DMA itself (res_wait_all_but, in-order completion), one barrier later.
-    auto dma16 = [&](const void* g, const void* l) {
-        asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"((unsigned)(uintptr_t)(res_lptr_t)const_cast<void*>(l)), "v"(g) : "memory", "m0");
-    };
-    auto dma4 = [&](const void* g, const void* l) {
-        asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dword %1, off" :: "s"((unsigned)(uintptr_t)(res_lptr_t)const_cast<void*>(l)), "v"(g) : "memory", "m0");
-    };
+    // LDS-DMA in inline assembly (hf_dma16 / hf_dma4), not the builtin, whose compiler-placed vmcnt(0) in front of the reads of THIS step's staged
+    // rows, one buffer over, cost 3.5 us per step measured.  The step waits for its own DMA itself (hf_wait_all_but), one barrier later.
     auto stage = [&](int t, int buf) {
         const char* xb = xsrc + (size_t)t * us * 8;
         char* xs = smem + G::OFF_X + buf * 4 * G::PX + w * G::PX;
 #pragma unroll
-        for (int i = 0; i < U * 8 / 1024; ++i) dma16(xb + i * 1024, xs + i * 1024);
-        if (DROP) dma4(msrc + (size_t)t * us, smem + G::OFF_M + buf * 4 * U + w * U);
+        for (int i = 0; i < U * 8 / 1024; ++i) hf_dma16(xb + i * 1024, xs + i * 1024);
+        if (DROP) hf_dma4(msrc + (size_t)t * us, smem + G::OFF_M + buf * 4 * U + w * U);
     };
     stage(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RES_BARRIER();
+    hf_lds_barrier();
 
     // ---- what leaves a step through LDS: h / y row-major (16-byte pieces) and h^T / y^T (a unit's four rows = 8 bytes).  Branch-free: buffer
     // stores whose offset is pushed out of range are dropped by the hardware, so the step's code stays one scheduling region ----
@@ -319,9 +303,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             pointwise(q, acc[q & 1]);
             RES_TR(3 + q);
         }
-        res_wait_all_but(EMIT_STORES + G::NG * (SAVE ? 2 : 1));               // the staged rows of step t + 1 are in LDS (the pointwise stores behind them may not be out)
+        hf_wait_all_but(EMIT_STORES + G::NG * (SAVE ? 2 : 1));               // the staged rows of step t + 1 are in LDS (the pointwise stores behind them may not be out)
         RES_TR(7);
-        RES_BARRIER();
+        hf_lds_barrier();
         RES_TR(8);
         RES_TR_FLUSH(0, t);
     }
@@ -467,7 +451,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 
     const uint4* wl = reinterpret_cast<const uint4*>(smem + G::OFF_W) + (size_t)w * 4 * G::KL * 64 + lane;
     constexpr int PFB = 3;
-    RES_BARRIER();
+    hf_lds_barrier();
     RES_TR_DECL;
     for (int kk = 0; kk < T; ++kk) {
         const int t = T - 1 - kk;
@@ -540,7 +524,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         }
         RES_TR(2);
         request(t > 0 ? t - 1 : 0);                     // unconditional (clamped): behind a condition the compiler copies the freshly requested registers at the join and waits for the loads to do it
-        RES_BARRIER();
+        hf_lds_barrier();
         RES_TR(3);
         RES_TR_FLUSH(1, kk);
     }
@@ -562,7 +546,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         v[0] = (unsigned)zf[0] | ((unsigned)zf[1] << 16);
         v[1] = (unsigned)zf[2] | ((unsigned)zf[3] << 16);
         *reinterpret_cast<u32x2_t*>(smem + G::OFF_Z + (T & 1) * 4 * G::PZ + row * G::PZ + gate_perm_col(2, u0) * 2) = v;
-        RES_BARRIER();
+        hf_lds_barrier();
     }
     emit_read(T & 1, 0);
     emit_store(0, 0);

@@ -13,34 +13,30 @@
 //     the weights are loaded;
 //   * the layers run as separate launches (the input projection of the next layer is one large GEMM between them), which keeps K at
 //     the layer's own width: backward, 4U = 2048 columns of dz for 512 units fit LDS (128 KiB); the fused K = 4 U1 + 4 U2 does not.
-// Hand-off protocol: the one of lstm_persist.hip (cdna_hip_programming.md G16 R1; MI355X_MICROARCH.md "Valid forms", first table row)
-// with the workgroup replaced by the wave: 16-byte sc1 (write-through) stores of the tile in A-fragment order -> the storing wave's
-// `s_waitcnt vmcnt(0)` -> ONE sc1 flag store by that wave; the consumer wave polls the flags of its row tile with sc1 loads and only
-// then issues its sc1 loads of the tile.  Every spin is bounded and watches a status word; a give-up is sticky (mnn_lstm_rowpar_status).
+// Hand-off protocol: the one of lstm_handoff.h with the workgroup replaced by the WAVE: a wave stores its fragments of the tile (A-fragment
+// order), waits for them alone with a counted vmcnt wait and raises its own flag, [HF_FLAGS_OFF + 32 rt + member], with no workgroup barrier;
+// the consumer wave polls the flags of its row tile itself and only then issues its sc1 loads of the tile.  mnn_lstm_rowpar_status reads
+// the sticky give-up word.
 #include "common.h"
+#include "lstm_handoff.h"
 #include <stdlib.h>
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) unsigned gu32;
 
-#define RP_LIMIT 100000000LL       // spin bound: 1 s of wall_clock64() (100 MHz)
-#define RP_FLAGS_OFF 32            // words: [0] status, [1] sticky, [32 + 32 rt + member] progress flags
 #ifndef RP_STG
 #define RP_STG 33   // f32 words per staged row (32 + pad)
 #endif
 #ifndef RP_RING
 #define RP_RING 3                  // backward: chunks of the dz tile in the register ring (8 KiB each)
 #endif
-#define RP_SC1 16                  // aux bit of raw buffer loads/stores: device scope (write-through / L1-bypassing)
 #ifndef RP_A_AUX
 #define RP_A_AUX 0                  // pair forward, same-XCD mode: state-tile loads through the L1
 #endif
 // The per-wave LDS tiles are written element-wise (bf16) and read back 16 bytes at a time by OTHER lanes of the same wave: the LDS serves a
 // wave's instructions in order, but the compiler must not move the differently-typed accesses across one another
 #define RP_LDS_FENCE() asm volatile("" ::: "memory")
-// Behind the hand-off stores: rp_wait_all_but(N) counts the vector-memory operations written AFTER them in the source, so neither the
+// Behind the hand-off stores: hf_wait_all_but(N) counts the vector-memory operations written AFTER them in the source, so neither the
 // scheduler nor the memory-dependence analysis may move one of those above the hand-off (vmcnt retires in issue order)
 // (the marker comment lets tests/test_build_guards.py find the fence in the compiler's output)
 #define RP_HANDOFF_FENCE() do { __builtin_amdgcn_sched_barrier(0); asm volatile("; RP_HANDOFF_FENCE" ::: "memory"); } while (0)
@@ -55,31 +51,8 @@ extern "C" int mnn_lstm_rowpar_trace(void* out) {
 #define RP_TR(dir, cond, step, k) do { } while (0)
 #endif
 
-__device__ __forceinline__ unsigned rp_ld(const unsigned* p) { return __hip_atomic_load((gu32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void rp_st(unsigned* p, unsigned v) { __hip_atomic_store((gu32*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rp_rsrc(const void* base, size_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 // fragment row of C register k in lane half hh (v_mfma_f32_32x32x16_bf16): (k & 3) + 8 (k >> 2) + 4 hh
 __device__ __forceinline__ constexpr int rp_krow(int k) { return (k & 3) + 8 * (k >> 2); }
-
-// One wave waits until the first n words of `line` are all >= need; the other lanes watch the status word.  false: the launch is aborting.
-__device__ __forceinline__ bool rp_wait(const unsigned* line, unsigned* status, int n, unsigned need) {
-    const int lane = threadIdx.x & 63;
-    const bool mine = lane < n;
-    const unsigned* p = mine ? line + lane : status;
-    const long long t0 = wall_clock64();
-    for (unsigned spins = 1;; ++spins) {
-        const unsigned v = rp_ld(p);
-        if (__all(mine ? v >= need : v == 0u)) return true;
-        const bool dead = __any(!mine && v != 0u) || ((spins & 127u) == 0u && wall_clock64() - t0 > RP_LIMIT);
-        if (dead) {
-            if (lane == 0) { rp_st(status, 1u); rp_st(status + 1, 1u); }       // [1]: sticky, never re-zeroed by a launch
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
 
 struct RFwdArgs {
     const float* xproj; const bf16_t* wh_t; bf16_t* gates; float* c; bf16_t* h; bf16_t* y; const uint8_t* mask;
@@ -98,45 +71,6 @@ template <typename F> struct RpX<true, F> {
     static __device__ __forceinline__ float4 get(const uint2& v) { return make_float4(F::lo(v.x), F::hi(v.x), F::lo(v.y), F::hi(v.y)); }
 };
 
-// Launch start: do the U/32 workgroups of this row-tile group share an XCD?  Each posts 0x100 | XCC_ID (device scope), wave 0 waits for the
-// others (bounded) and compares; the answer reaches the other waves through LDS at the barrier that follows the weight load.  It only
-// selects the store policy of the hand-offs (results never depend on it): on one XCD the tile and the flag are stored write-BACK -- they stay
-// in that XCD's L2, which the consumers' sc1 (L1-bypassing, L2-served) loads hit -- otherwise write-through (device scope).
-__device__ __forceinline__ void rp_probe_xcd(unsigned* xline, unsigned* status, int member, int nb, int* s_local) {
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    if (threadIdx.x == 0) rp_st(xline + member, 0x100u | (xcc & 0xfu));
-    if (threadIdx.x < 64) {
-        bool same = false;
-        if (rp_wait(xline, status, nb, 1u)) {
-            const unsigned v = rp_ld(xline + (threadIdx.x < (unsigned)nb ? threadIdx.x : 0));
-            same = __all(v == __builtin_amdgcn_readfirstlane(v));
-        }
-        if (threadIdx.x == 0) *s_local = same ? 1 : 0;
-    }
-}
-__device__ __forceinline__ void rp_store_frag(const __amdgpu_buffer_rsrc_t rs, int f, int lane, u32x4_t v, bool local) {
-    if (local) __builtin_amdgcn_raw_buffer_store_b128(v, rs, (f * 64 + lane) * 16, 0, 0);
-    else __builtin_amdgcn_raw_buffer_store_b128(v, rs, (f * 64 + lane) * 16, 0, RP_SC1);
-}
-__device__ __forceinline__ void rp_raise(unsigned* flag, unsigned value, bool local) {        // one lane, after the wave's vmcnt(0)
-    if (local) __hip_atomic_store((gu32*)flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // plain store: lands in the shared L2
-    else rp_st(flag, value);
-}
-
-// `s_waitcnt vmcnt(N)` with N a run-time count of the stores issued BEHIND the hand-off stores (loads, stores and atomics of a wave complete in
-// issue order: MI355X_MICROARCH.md, cycle constants): the hand-off tile is out, the younger row-major stores may still be in flight
-#define RP_VMC(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-__device__ __forceinline__ void rp_wait_all_but(int n) {
-    switch (n) {
-        RP_VMC(0) RP_VMC(1) RP_VMC(2) RP_VMC(3) RP_VMC(4) RP_VMC(5) RP_VMC(6) RP_VMC(7) RP_VMC(8) RP_VMC(9) RP_VMC(10) RP_VMC(11) RP_VMC(12)
-        RP_VMC(13) RP_VMC(14) RP_VMC(15) RP_VMC(16) RP_VMC(17) RP_VMC(18) RP_VMC(19) RP_VMC(20) RP_VMC(21) RP_VMC(22) RP_VMC(23) RP_VMC(24)
-        RP_VMC(25) RP_VMC(26) RP_VMC(27) RP_VMC(28) RP_VMC(29) RP_VMC(30) RP_VMC(31) RP_VMC(32) RP_VMC(33) RP_VMC(34) RP_VMC(35) RP_VMC(36)
-        RP_VMC(37) RP_VMC(38) RP_VMC(39) RP_VMC(40) RP_VMC(41) RP_VMC(42) RP_VMC(43) RP_VMC(44) RP_VMC(45) RP_VMC(46) RP_VMC(47) RP_VMC(48)
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-
 // ---- wave pairs (the *2 kernels below): two waves of a workgroup share one (row tile, unit tile) and exchange through LDS ----
 // LDS serves one wave's instructions in order and is one memory for the whole workgroup, so "data words, then the step word" by the writer and
 // "step word, then data words" by the reader needs no hardware fence; RP_LDS_FENCE keeps the compiler from moving the accesses across each other.
@@ -149,9 +83,9 @@ __device__ __forceinline__ bool rp_pair_wait(const unsigned* word, unsigned need
     for (unsigned spins = 1;; ++spins) {
         if (rp_lds_ld(word) >= need) return true;
         if ((spins & 255u) == 0u) {
-            if (rp_ld(status) != 0u) return false;
-            if (wall_clock64() - t0 > RP_LIMIT) {
-                if ((threadIdx.x & 63) == 0) { rp_st(status, 1u); rp_st(status + 1, 1u); }
+            if (hf_ld(status) != 0u) return false;
+            if (wall_clock64() - t0 > HF_LIMIT) {
+                if ((threadIdx.x & 63) == 0) hf_give_up(status);
                 return false;
             }
         }
@@ -175,8 +109,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int r = lane & 31, hh = lane >> 5;
     const int T = A.T, B = A.B, nrt = A.nrt;
     const int nb = U / 32;
-    unsigned* status = A.sync;
-    rp_probe_xcd(A.sync + RP_FLAGS_OFF + 32 * nrt + 32 * grp, status, nt, nb, s_local);
+    unsigned* status = A.sync + HF_STATUS_WORD;
+    hf_probe_xcd(A.sync + HF_FLAGS_OFF + 32 * nrt + 32 * grp, status, nt, nb, s_local);
     const int rot = (2 * nt) & (KS - 1);           // rotation of this member's k-step order (speed only: the sum over k is taken in that order)
     {   // this workgroup's 128 gate-interleaved rows of wh_t [4U, U] -> LDS, once, k-steps in the member's rotated order
         const int n0 = nt * 128;
@@ -193,7 +127,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     if (rt >= nrt) return;
     bf16_t (*sH)[40] = reinterpret_cast<bf16_t (*)[40]>(smem + (size_t)KS * 4096 + (size_t)w * 5120);          // tile [row][unit] (+pad)
     bf16_t (*sT)[40] = reinterpret_cast<bf16_t (*)[40]>(smem + (size_t)KS * 4096 + (size_t)w * 5120 + 2560);   // tile [unit][row]
-    unsigned* flags = A.sync + RP_FLAGS_OFF + rt * 32;
+    unsigned* flags = A.sync + HF_FLAGS_OFF + rt * 32;
     const int m0 = rt * 32, unit = nt * 32 + r;
     const size_t us = (size_t)B * U, slab = (size_t)KS * 1024;
     const bool drop = A.mask != nullptr;
@@ -226,14 +160,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const bool trc = nt == 0 && rt == 0;
     for (int t = 0; t < T; ++t) {
         RP_TR(0, trc, t, 0);
-        if (t > 0 && !rp_wait(flags, status, nb, (unsigned)t)) return;
+        if (t > 0 && !hf_wait(flags, status, nb, (unsigned)t)) return;
         RP_TR(0, trc, t, 1);
         typename F::x8 a[KS];
         {
-            const __amdgpu_buffer_rsrc_t rs = rp_rsrc(t > 0 ? A.hx + ((size_t)(t - 1) * nrt + rt) * slab : A.hx0 + (size_t)rt * slab, slab);
+            const __amdgpu_buffer_rsrc_t rs = hf_rsrc(t > 0 ? A.hx + ((size_t)(t - 1) * nrt + rt) * slab : A.hx0 + (size_t)rt * slab, slab);
 #pragma unroll
             for (int s = 0; s < KS; ++s)        // k-step s of this member is slab k-step (s + rot) % KS: the members of a row tile start at different lines
-                a[s] = __builtin_bit_cast(typename F::x8, __builtin_amdgcn_raw_buffer_load_b128(rs, ((((s + rot) & (KS - 1)) * 64 + lane) * 16), 0, RP_SC1));
+                a[s] = __builtin_bit_cast(typename F::x8, __builtin_amdgcn_raw_buffer_load_b128(rs, ((((s + rot) & (KS - 1)) * 64 + lane) * 16), 0, HF_SC1));
         }
         // all KS loads are in flight before anything else: left alone, the scheduler sinks every load next to its use and waits vmcnt(0) per MFMA
         __builtin_amdgcn_sched_barrier(0);
@@ -282,9 +216,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         RP_LDS_FENCE();
         RP_TR(0, trc, t, 3);
         {   // hand-off: k-steps 2 nt, 2 nt + 1 of the (t, row tile) slab, A-fragment order (row = lane & 31, 8 units per lane half)
-            const __amdgpu_buffer_rsrc_t rs = rp_rsrc(A.hx + ((size_t)t * nrt + rt) * slab, slab);
+            const __amdgpu_buffer_rsrc_t rs = hf_rsrc(A.hx + ((size_t)t * nrt + rt) * slab, slab);
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) rp_store_frag(rs, 2 * nt + ks, lane, *reinterpret_cast<const u32x4_t*>(&sH[r][ks * 16 + hh * 8]), local);
+            for (int ks = 0; ks < 2; ++ks) hf_store_frag(rs, 2 * nt + ks, lane, *reinterpret_cast<const u32x4_t*>(&sH[r][ks * 16 + hh * 8]), local);
         }
         RP_HANDOFF_FENCE();
         RP_TR(0, trc, t, 4);
@@ -337,8 +271,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         }
         RP_LDS_FENCE();
         RP_TR(0, trc, t, 5);
-        rp_wait_all_but(behind);                                      // the hand-off tile is out
-        if (lane == 0) rp_raise(flags + nt, (unsigned)(t + 1), local);
+        hf_wait_all_but(behind);                                      // the hand-off tile is out
+        if (lane == 0) hf_raise(flags + nt, (unsigned)(t + 1), local);
         RP_TR(0, trc, t, 6);
         {
             char* cb = reinterpret_cast<char*>(A.c + (size_t)t * us + (size_t)m0 * U) + oc;
@@ -373,8 +307,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int r = lane & 31, hh = lane >> 5;
     const int T = A.T, B = A.B, nrt = A.nrt;
     const int nb = U / 32;
-    unsigned* status = A.sync;
-    rp_probe_xcd(A.sync + RP_FLAGS_OFF + 32 * nrt + 32 * grp, status, nt, nb, s_local);
+    unsigned* status = A.sync + HF_STATUS_WORD;
+    hf_probe_xcd(A.sync + HF_FLAGS_OFF + 32 * nrt + 32 * grp, status, nt, nb, s_local);
     const int rot = (8 * nt) & (KS4 - 1);          // rotation of this member's k-step order, in whole chunks (speed only)
 #pragma unroll 4
     for (int i = 0; i < KS4 / 4; ++i) {
@@ -389,7 +323,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     char* tile = smem + (size_t)KS4 * 1024 + (size_t)w * 10240;
     bf16_t (*sZ)[136] = reinterpret_cast<bf16_t (*)[136]>(tile);               // dz tile [row][gate*32 + unit] (+pad): 8704 bytes
     bf16_t (*sT)[32][40] = reinterpret_cast<bf16_t (*)[32][40]>(tile);         // dz tile [gate][unit][row]: 10240 bytes, AFTER sZ has been read
-    unsigned* flags = A.sync + RP_FLAGS_OFF + rt * 32;
+    unsigned* flags = A.sync + HF_FLAGS_OFF + rt * 32;
     const int m0 = rt * 32, unit = nt * 32 + r;
     const size_t us = (size_t)B * U, slab = (size_t)KS4 * 1024;
     const bool drop = A.mask != nullptr;
@@ -435,16 +369,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     for (int kk = 0; kk < T; ++kk) {
         const int t = T - 1 - kk;
         RP_TR(1, trc, kk, 0);
-        if (kk > 0 && !rp_wait(flags, status, nb, (unsigned)kk)) return;
+        if (kk > 0 && !hf_wait(flags, status, nb, (unsigned)kk)) return;
         RP_TR(1, trc, kk, 1);
         f32x16_t acc;
         {
-            const __amdgpu_buffer_rsrc_t rs = rp_rsrc(kk > 0 ? A.dzx + ((size_t)(t + 1) * nrt + rt) * slab : A.dzx0 + (size_t)rt * slab, slab);
+            const __amdgpu_buffer_rsrc_t rs = hf_rsrc(kk > 0 ? A.dzx + ((size_t)(t + 1) * nrt + rt) * slab : A.dzx0 + (size_t)rt * slab, slab);
             typename F::x8 a[RP_RING][CH];            // ring of chunks of eight k-steps (8 KiB each), all but one in flight
             auto issue = [&](int ch) {
 #pragma unroll
                 for (int s = 0; s < CH; ++s)
-                    a[ch % RP_RING][s] = __builtin_bit_cast(typename F::x8, __builtin_amdgcn_raw_buffer_load_b128(rs, ((((ch * CH + s + rot) & (KS4 - 1)) * 64 + lane) * 16), 0, RP_SC1));
+                    a[ch % RP_RING][s] = __builtin_bit_cast(typename F::x8, __builtin_amdgcn_raw_buffer_load_b128(rs, ((((ch * CH + s + rot) & (KS4 - 1)) * 64 + lane) * 16), 0, HF_SC1));
             };
 #pragma unroll
             for (int ch = 0; ch < RP_RING - 1 && ch < NCH; ++ch) issue(ch);
@@ -527,9 +461,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         RP_LDS_FENCE();
         RP_TR(1, trc, kk, 3);
         {   // hand-off: k-steps 8 nt .. 8 nt + 7 of the (t, row tile) slab
-            const __amdgpu_buffer_rsrc_t rs = rp_rsrc(A.dzx + ((size_t)t * nrt + rt) * slab, slab);
+            const __amdgpu_buffer_rsrc_t rs = hf_rsrc(A.dzx + ((size_t)t * nrt + rt) * slab, slab);
 #pragma unroll
-            for (int ks = 0; ks < 8; ++ks) rp_store_frag(rs, 8 * nt + ks, lane, *reinterpret_cast<const u32x4_t*>(&sZ[r][ks * 16 + hh * 8]), local);
+            for (int ks = 0; ks < 8; ++ks) hf_store_frag(rs, 8 * nt + ks, lane, *reinterpret_cast<const u32x4_t*>(&sZ[r][ks * 16 + hh * 8]), local);
         }
         RP_HANDOFF_FENCE();
         RP_TR(1, trc, kk, 4);
@@ -566,8 +500,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         }
         RP_LDS_FENCE();
         RP_TR(1, trc, kk, 5);
-        rp_wait_all_but(behind);
-        if (lane == 0) rp_raise(flags + nt, (unsigned)(kk + 1), local);
+        hf_wait_all_but(behind);
+        if (lane == 0) hf_raise(flags + nt, (unsigned)(kk + 1), local);
         RP_TR(1, trc, kk, 6);
         RP_TR(1, trc, kk, 7);
     }
@@ -607,9 +541,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int r = lane & 31, hh = lane >> 5;
     const int T = A.T, B = A.B, nrt = A.nrt;
     const int nb = U / 32;
-    unsigned* status = A.sync;
+    unsigned* status = A.sync + HF_STATUS_WORD;
     if (threadIdx.x < 8) hs[threadIdx.x] = 0u;
-    rp_probe_xcd(A.sync + RP_FLAGS_OFF + 32 * nrt + 32 * grp, status, nt, nb, s_local);
+    hf_probe_xcd(A.sync + HF_FLAGS_OFF + 32 * nrt + 32 * grp, status, nt, nb, s_local);
     const int rot = (2 * nt) & (KS - 1);
     {
         const int n0 = nt * 128;
@@ -632,7 +566,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const unsigned* peer_ready = hs + slot * 4 + (half ^ 1);
     unsigned* my_taken = hs + slot * 4 + 2 + half;          // "I have read the partner's words of step .."
     const unsigned* peer_taken = hs + slot * 4 + 2 + (half ^ 1);
-    unsigned* flags = A.sync + RP_FLAGS_OFF + rt * 32;
+    unsigned* flags = A.sync + HF_FLAGS_OFF + rt * 32;
     const int m0 = rt * 32, unit = nt * 32 + r;
     const int rb = 16 * half + 4 * hh;              // global row (inside the tile) of local register row 0; register kl: rb + rp_krow(kl)
     const size_t us = (size_t)B * U, slab = (size_t)KS * 1024;
@@ -676,11 +610,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             for (int k = 0; k < 8; ++k) mk[k] = mt[(rp_krow(k) + 4 * hh) * 32 + r];
             RP_LDS_FENCE();
         }
-        if (t > 0 && !rp_wait(flags, status, 2 * nb, (unsigned)t)) return;
+        if (t > 0 && !hf_wait(flags, status, 2 * nb, (unsigned)t)) return;
         RP_TR(0, trc, t, 1);
         typename F::x8 a[KS];
         {
-            const __amdgpu_buffer_rsrc_t rs = rp_rsrc(t > 0 ? A.hx + ((size_t)(t - 1) * nrt + rt) * slab : A.hx0 + (size_t)rt * slab, slab);
+            const __amdgpu_buffer_rsrc_t rs = hf_rsrc(t > 0 ? A.hx + ((size_t)(t - 1) * nrt + rt) * slab : A.hx0 + (size_t)rt * slab, slab);
             // same-XCD mode: through the CU's L1 -- both waves of the pair (and the second pair) read the same 1-KiB lines within a microsecond,
             // and a slab address is written once per launch before anybody reads it (the L1 starts the launch empty), so a hit is never stale
             if (local) {
@@ -690,7 +624,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             } else {
 #pragma unroll
                 for (int s = 0; s < KS; ++s)
-                    a[s] = __builtin_bit_cast(typename F::x8, __builtin_amdgcn_raw_buffer_load_b128(rs, ((((s + rot) & (KS - 1)) * 64 + lane) * 16), 0, RP_SC1));
+                    a[s] = __builtin_bit_cast(typename F::x8, __builtin_amdgcn_raw_buffer_load_b128(rs, ((((s + rot) & (KS - 1)) * 64 + lane) * 16), 0, HF_SC1));
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -766,12 +700,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         RP_LDS_FENCE();
         RP_TR(0, trc, t, 3);
         {   // hand-off of this wave's 16 rows: k-steps 2 nt, 2 nt + 1 of the slab in ONE store (lane -> k-step, unit half, row)
-            const __amdgpu_buffer_rsrc_t rs = rp_rsrc(A.hx + ((size_t)t * nrt + rt) * slab, slab);
+            const __amdgpu_buffer_rsrc_t rs = hf_rsrc(A.hx + ((size_t)t * nrt + rt) * slab, slab);
             const int ks = lane >> 5, kh = (lane >> 4) & 1, rl = lane & 15;
             const u32x4_t v = *reinterpret_cast<const u32x4_t*>(&sH[rl][ks * 16 + kh * 8]);
             const int off = (((2 * nt + ks) * 64) + kh * 32 + 16 * half + rl) * 16;
             if (local) __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 0);
-            else __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, RP_SC1);
+            else __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, HF_SC1);
         }
         RP_HANDOFF_FENCE();
         RP_TR(0, trc, t, 4);
@@ -815,8 +749,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         }
         RP_LDS_FENCE();
         RP_TR(0, trc, t, 5);
-        rp_wait_all_but(behind);
-        if (lane == 0) rp_raise(flags + 2 * nt + half, (unsigned)(t + 1), local);
+        hf_wait_all_but(behind);
+        if (lane == 0) hf_raise(flags + 2 * nt + half, (unsigned)(t + 1), local);
         RP_TR(0, trc, t, 6);
         if (A.gates != nullptr) {
             char* gb = reinterpret_cast<char*>(A.gates + (size_t)t * 4 * us + (size_t)m0 * 4 * U) + og / 2;
@@ -851,9 +785,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int r = lane & 31, hh = lane >> 5;
     const int T = A.T, B = A.B, nrt = A.nrt;
     const int nb = U / 32;
-    unsigned* status = A.sync;
+    unsigned* status = A.sync + HF_STATUS_WORD;
     if (threadIdx.x < 8) hs[threadIdx.x] = 0u;
-    rp_probe_xcd(A.sync + RP_FLAGS_OFF + 32 * nrt + 32 * grp, status, nt, nb, s_local);
+    hf_probe_xcd(A.sync + HF_FLAGS_OFF + 32 * nrt + 32 * grp, status, nt, nb, s_local);
     const int rot = (8 * nt) & (HK - 1);            // rotation of the walk inside a K half, in whole chunks (speed only)
 #pragma unroll 4
     for (int i = 0; i < KS4 / 4; ++i) {
@@ -874,7 +808,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const unsigned* peer_ready = hs + slot * 4 + (half ^ 1);
     unsigned* my_taken = hs + slot * 4 + 2 + half;
     const unsigned* peer_taken = hs + slot * 4 + 2 + (half ^ 1);
-    unsigned* flags = A.sync + RP_FLAGS_OFF + rt * 32;
+    unsigned* flags = A.sync + HF_FLAGS_OFF + rt * 32;
     const int m0 = rt * 32, unit = nt * 32 + r;
     const int rb = 16 * half + 4 * hh;
     const size_t us = (size_t)B * U, slab = (size_t)KS4 * 1024;
@@ -918,17 +852,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     for (int kk = 0; kk < T; ++kk) {
         const int t = T - 1 - kk;
         RP_TR(1, trc, kk, 0);
-        if (kk > 0 && !rp_wait(flags + half * nb, status, nb, (unsigned)kk)) return;      // the producers of this wave's K half (both row halves)
+        if (kk > 0 && !hf_wait(flags + half * nb, status, nb, (unsigned)kk)) return;      // the producers of this wave's K half (both row halves)
         RP_TR(1, trc, kk, 1);
         f32x16_t acc;
         {
-            const __amdgpu_buffer_rsrc_t rs = rp_rsrc(kk > 0 ? A.dzx + ((size_t)(t + 1) * nrt + rt) * slab : A.dzx0 + (size_t)rt * slab, slab);
+            const __amdgpu_buffer_rsrc_t rs = hf_rsrc(kk > 0 ? A.dzx + ((size_t)(t + 1) * nrt + rt) * slab : A.dzx0 + (size_t)rt * slab, slab);
             typename F::x8 a[RP_RING][CH];
             auto issue = [&](int ch) {
 #pragma unroll
                 for (int s = 0; s < CH; ++s)
                     a[ch % RP_RING][s] = __builtin_bit_cast(typename F::x8, __builtin_amdgcn_raw_buffer_load_b128(
-                        rs, (((half * HK + ((ch * CH + s + rot) & (HK - 1))) * 64 + lane) * 16), 0, RP_SC1));
+                        rs, (((half * HK + ((ch * CH + s + rot) & (HK - 1))) * 64 + lane) * 16), 0, HF_SC1));
             };
 #pragma unroll
             for (int ch = 0; ch < RP_RING - 1 && ch < NCH; ++ch) issue(ch);
@@ -1035,7 +969,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         RP_LDS_FENCE();
         RP_TR(1, trc, kk, 3);
         {   // hand-off of this wave's 16 rows: k-steps 8 nt .. 8 nt + 7 of the slab, two k-steps per store
-            const __amdgpu_buffer_rsrc_t rs = rp_rsrc(A.dzx + ((size_t)t * nrt + rt) * slab, slab);
+            const __amdgpu_buffer_rsrc_t rs = hf_rsrc(A.dzx + ((size_t)t * nrt + rt) * slab, slab);
             const int kh = (lane >> 4) & 1, rl = lane & 15;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -1043,7 +977,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
                 const u32x4_t v = *reinterpret_cast<const u32x4_t*>(&sZ[rl][ks * 16 + kh * 8]);
                 const int off = (((8 * nt + ks) * 64) + kh * 32 + 16 * half + rl) * 16;
                 if (local) __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 0);
-                else __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, RP_SC1);
+                else __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, HF_SC1);
             }
         }
         RP_HANDOFF_FENCE();
@@ -1077,8 +1011,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         }
         RP_LDS_FENCE();
         RP_TR(1, trc, kk, 5);
-        rp_wait_all_but(behind);
-        if (lane == 0) rp_raise(flags + 2 * nt + half, (unsigned)(kk + 1), local);
+        hf_wait_all_but(behind);
+        if (lane == 0) hf_raise(flags + 2 * nt + half, (unsigned)(kk + 1), local);
         if (A.dzc != nullptr) {
             auto put = [&](int j, const u32x4_t& v) {
                 const int p = j * 64 + lane, row = p >> 4, pc = p & 15;
@@ -1131,9 +1065,10 @@ static bool rp_pair(int B, int U) {
     if (mnn_switch_set(MNN_SW_ROWPAR_NO_PAIR) || !rp_plan(B, U, false, nrt, G)) return false;
     return (nrt + G - 1) / G <= 2;
 }
-static size_t rp_sync_bytes(int nrt) { return ((size_t)RP_FLAGS_OFF + 64 * (size_t)nrt) * sizeof(unsigned); }      // flag lines, then one XCC-id line per row-tile group
-static size_t rp_edge_bytes(int nrt, int U) { return (size_t)nrt * (size_t)(U / 4) * 1024; }         // zero slabs standing for dz[T] (>= h[-1]'s)
-static size_t rp_xchg_off(int nrt, int U) { return (rp_sync_bytes(nrt) + rp_edge_bytes(nrt, U) + 255) / 256 * 256; }
+// the workspace layout and the per-launch reset, shared with the cluster form: declared in lstm_handoff.h
+size_t rp_sync_bytes(int nrt) { return ((size_t)HF_FLAGS_OFF + 64 * (size_t)nrt) * sizeof(unsigned); }
+size_t rp_edge_bytes(int nrt, int U) { return (size_t)nrt * (size_t)(U / 4) * 1024; }         // zero slabs standing for dz[T] (>= h[-1]'s)
+size_t rp_xchg_off(int nrt, int U) { return (rp_sync_bytes(nrt) + rp_edge_bytes(nrt, U) + 255) / 256 * 256; }
 
 extern "C" int mnn_lstm_rowpar_ok(int B, int units) {
     int nrt, G;
@@ -1147,23 +1082,20 @@ extern "C" size_t mnn_lstm_rowpar_workspace_bytes(int T, int B, int units) {
 extern "C" int mnn_lstm_rowpar_status(const void* workspace, int* status) {
     MNN_REQUIRE(workspace && status, "mnn_lstm_rowpar_status: bad arguments");
     unsigned v = 0;
-    MNN_HIP(hipMemcpy(&v, (const char*)workspace + sizeof(unsigned), sizeof(v), hipMemcpyDeviceToHost));
+    MNN_HIP(hipMemcpy(&v, (const char*)workspace + HF_STICKY_WORD * sizeof(unsigned), sizeof(v), hipMemcpyDeviceToHost));
     *status = (int)v;
     return MNN_OK;
 }
 
-__global__ void rp_reset_kernel(unsigned* sync, int words) {          // progress words back to zero; [1] (sticky) is left alone
+__global__ void rp_reset_kernel(unsigned* sync, int words) {          // status and progress words back to zero; the sticky word is left alone
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < words; i += gridDim.x * blockDim.x)
-        if (i != 1) sync[i] = 0u;
+        if (i != HF_STICKY_WORD) sync[i] = 0u;
 }
-
-// the workspace layout and the per-launch reset, for the cluster form (lstm_cluster.hip), which takes the same workspace
 void mnn_rp_workspace_layout(int nrt, int U, size_t* sync_bytes, size_t* xchg_off) {
     *sync_bytes = rp_sync_bytes(nrt);
     *xchg_off = rp_xchg_off(nrt, U);
 }
-int mnn_rp_reset_launch(hipStream_t st, void* workspace, int nrt, int U) {
-    (void)U;
+int mnn_rp_reset_launch(hipStream_t st, void* workspace, int nrt) {
     hipLaunchKernelGGL(rp_reset_kernel, dim3(8), dim3(256), 0, st, (unsigned*)workspace, (int)(rp_sync_bytes(nrt) / sizeof(unsigned)));
     MNN_LAUNCH_CHECK();
     return MNN_OK;
@@ -1225,7 +1157,7 @@ extern "C" int mnn_lstm_rowpar_fwd(mnn_stream_t s, int T, int B, const mnn_lstm_
     a.hT = (bf16_t*)L->hT; a.ld_hT = L->ld_hT; a.yT = (bf16_t*)L->yT; a.ld_yT = L->ld_yT;
     a.sync = (unsigned*)workspace; a.hx0 = (const char*)workspace + rp_sync_bytes(a.nrt); a.hx = (char*)workspace + rp_xchg_off(a.nrt, U);
     a.T = T; a.B = B; a.kp = keep_prob; a.allow_local = mnn_persist_allow_local();
-    hipLaunchKernelGGL(rp_reset_kernel, dim3(8), dim3(256), 0, st, (unsigned*)workspace, (int)(rp_sync_bytes(a.nrt) / sizeof(unsigned)));
+    if (int rc = mnn_rp_reset_launch(st, workspace, a.nrt)) return rc;
     MNN_HIP(mnn_zero_async((char*)workspace + rp_sync_bytes(a.nrt), rp_edge_bytes(a.nrt, U), st));
     const int grid = a.G * (U / 32);
     const bool pair = rp_pair(B, U);
@@ -1251,7 +1183,7 @@ extern "C" int mnn_lstm_rowpar_bwd(mnn_stream_t s, int T, int B, const mnn_lstm_
     a.dzc = (bf16_t*)L->dz_T; a.dzT = (bf16_t*)L->dzT_t; a.ld_t = L->ld_t; a.db_p = L->db_p;
     a.sync = (unsigned*)workspace; a.dzx0 = (const char*)workspace + rp_sync_bytes(a.nrt); a.dzx = (char*)workspace + rp_xchg_off(a.nrt, U);
     a.T = T; a.B = B; a.kp = keep_prob; a.allow_local = mnn_persist_allow_local();
-    hipLaunchKernelGGL(rp_reset_kernel, dim3(8), dim3(256), 0, st, (unsigned*)workspace, (int)(rp_sync_bytes(a.nrt) / sizeof(unsigned)));
+    if (int rc = mnn_rp_reset_launch(st, workspace, a.nrt)) return rc;
     MNN_HIP(mnn_zero_async((char*)workspace + rp_sync_bytes(a.nrt), rp_edge_bytes(a.nrt, U), st));
     const int grid = a.G * (U / 32);
     const bool pair = rp_pair(B, U);

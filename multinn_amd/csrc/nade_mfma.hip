@@ -15,6 +15,7 @@
 // adds, one sigmoid per state element and the per-(row, d) pointwise.  w_enc stays f32 (a is exact up to f32
 // summation order and is handed to the backward pass as a_final); w_dec is read as a bf16 copy.
 #include "common.h"
+#include "lstm_handoff.h"     // hf_lds_barrier: the workgroup barrier that waits for LDS traffic only (no vmcnt drain at the tile's barriers)
 typedef float nm_f4 __attribute__((ext_vector_type(4)));
 // results (conditionals, d nll / d logit, a_final) are written once and read by later kernels: stored non-temporal, they leave the decoder / encoder
 // weights every workgroup re-reads in the L2 (2.19 -> 2.17 ms at [262144, 440, 256]; same in the backward's d b_enc store)
@@ -39,10 +40,6 @@ __device__ long long nm_trace[16];
 #define NM_H 256          // hidden width this kernel is specialised for
 #define NM_PITCH 264      // bf16 elements per state-tile row (256 + 8 pad: rows 16 B aligned, 4-bank skew)
 #define NM_LP 36          // floats per logit-tile row
-
-// Workgroup barrier that waits for this wave's LDS traffic only.  __syncthreads() also drains vmcnt(0), i.e. every
-// prefetch load and every result store in flight would be waited for at each of the tile's barriers.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __device__ __forceinline__ float nm_ln(float x) { return __builtin_amdgcn_logf(x) * LN2F; }
 
@@ -302,7 +299,7 @@ nade_fwd_mfma_body(int tracks, int N, int D, const uint8_t* __restrict__ v, long
             if (c + 2 < ntile) load_v(c + 2, vb);
         }
         NM_T(0);
-        lds_barrier();                                     // B1: sLb complete, sH consumed, next masks written
+        hf_lds_barrier();                                     // B1: sLb complete, sH consumed, next masks written
         NM_T(1);
         const int F = (int)S.sSb[buf][32];
         const unsigned mk = S.sMask[buf][en];
@@ -390,13 +387,13 @@ nade_fwd_mfma_body(int tracks, int N, int D, const uint8_t* __restrict__ v, long
             NM_T(2);
             if (k0 == 0 && c + 1 < ntile) build_list(nbuf);
             NM_T(3);
-            lds_barrier();                                 // B2: sF complete (and the next tile's list)
+            hf_lds_barrier();                                 // B2: sF complete (and the next tile's list)
             NM_T(4);
             // ---- S2: flip logits; each pair whose state sits in this chunk picks its logit ----
             nm_logit_tile<SPLIT>(S.sF, w, lane, bfr, S.sLf);
             if (k0 == 0 && F <= 32 && c + 1 < ntile) load_we(c + 1, nbuf, 0, wev);     // behind the MFMAs: the next tile's encoder rows
             NM_T(5);
-            lds_barrier();                                 // B3: sLf ready
+            hf_lds_barrier();                                 // B3: sLf ready
             NM_T(6);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -406,7 +403,7 @@ nade_fwd_mfma_body(int tracks, int N, int D, const uint8_t* __restrict__ v, long
         }
         if (F == 0 && c + 1 < ntile) {                       // no flip in this tile: the bookkeeping of the loop body still has to happen
             build_list(nbuf);
-            lds_barrier();
+            hf_lds_barrier();
             load_we(c + 1, nbuf, 0, wev);
         } else if (F > 32 && c + 1 < ntile) {
             load_we(c + 1, nbuf, 0, wev);                    // the extra chunks overwrote the prefetched values

@@ -104,7 +104,7 @@ def test_resident_recurrence_keeps_its_weights_in_registers(tmp_path):
         assert "v_accvgpr_read" not in "".join(b for b, n in zip(blocks, per_block) if n == 128), body[:60]
         if re.match(r"_Z\w*lstm_res_fwd_kernel", body):
             # The step waits for the NEXT step's LDS-DMA with `s_waitcnt vmcnt(N)`, N = the buffer stores WRITTEN behind the DMA in the source
-            # (res_wait_all_but(EMIT_STORES + NG * (SAVE ? 2 : 1))).  The wait covers the DMA only if exactly N vector-memory operations, all of
+            # (hf_wait_all_but(EMIT_STORES + NG * (SAVE ? 2 : 1))).  The wait covers the DMA only if exactly N vector-memory operations, all of
             # them stores, stand between the last global_load_lds and that wait in the ISA: a merged, elided or extra memory operation would make
             # step t + 1 read rows that have not landed.
             big = [b for b, n in zip(blocks, per_block) if n == 128][0].split("\n")
