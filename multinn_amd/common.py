@@ -9,6 +9,7 @@ its gradient and Adam slots; that flat gradient buffer is also the data-parallel
 buffer.
 """
 import abc
+import collections
 import contextlib
 import gc
 import math
@@ -112,7 +113,6 @@ class ScanGraphs:
     MULTINN_GENERATE_GRAPH=0 keeps the eager loop."""
 
     def __init__(self, max_entries=4):
-        import collections
         self._cache = collections.OrderedDict()
         self._max = max_entries
 
@@ -148,11 +148,53 @@ class ScanGraphs:
         g.replay()
         return out.clone()
 
+    @staticmethod
+    def generate(owner, key, x, num_steps, given, temperature, scan, stale):
+        """The one capture wrapper of a `generate`: scan(x, num_steps, given, temperature) eagerly where graphs are off, else one replay of
+        the scan captured under key + ("given",) + temperature_key (a new given of the same shape replays the same graph; the temperature
+        is baked into the captured launches, nothing at 1.0: the scan captured without it) from the cache kept on `owner`.  stale(): mark
+        the owner's packed weight copies stale -- before the capture (the graph packs them itself: a replay always sees the current
+        weights) and after it (the packed copies then live in the graph's pool).  The warm-up is the scan's first min(num_steps, 2) steps."""
+        if not ScanGraphs.enabled(x):
+            return scan(x, num_steps, given, temperature)
+        if getattr(owner, "_scan_graphs", None) is None:
+            owner._scan_graphs = ScanGraphs()
+        if given is not None:
+            key = key + ("given",)
+        key = key + temperature_key(temperature)
+
+        def captured(sx, sg=None):
+            stale()
+            return scan(sx, num_steps, sg, temperature)
+
+        def warm(sx, sg=None):
+            n = min(int(num_steps), 2)
+            return scan(sx, n, None if sg is None else sg[:, :n].contiguous(), temperature)
+
+        return owner._scan_graphs.run(key, x, captured, warm, stale, extra=given)
+
 
 # --------------------------------------------------------------------------------------------
-# Conditional generation.  A visible of a sampling scan is given a code: 0 or 1 clamps it to that value (it is not drawn; its value is fed
+# The Philox position of a sampling step's draws: (stream, global row, sub-counter, element) with seed and row0 naming the stream and the
+# first row, and the sub-counter "the generated step" (times max(k, 1) for a Gibbs chain).  step: the generated step, a host number; base
+# (optional): a one-word step cell on the device that the kernels add to it (a session's captured chunk).  Every sample_single takes one
+# (`at`) and reads its position from nothing else.
+DrawAt = collections.namedtuple("DrawAt", ("seed", "row0", "step", "base"), defaults=(None,))
+
+
+# --------------------------------------------------------------------------------------------
+# Conditional generation. A visible of a sampling scan is given a code: 0 or 1 clamps it to that value (it is not drawn; its value is fed
 # forward exactly like a draw), 255 leaves it free (ops.nade_sample / generate_scan: `given`).
 GIVEN_FREE = 255
+
+
+def check_given(given, batch, num_steps, *tail):
+    """The one shape check of a scan's codes, on the host: u8 [batch, num_steps, *tail] (tail: a generator's num_output, or the feedback
+    scan's P, M), ValueError otherwise."""
+    want = [int(batch), int(num_steps)] + [int(n) for n in tail]
+    if not torch.is_tensor(given) or given.dtype != torch.uint8 or list(given.shape) != want:
+        got = f"{given.dtype} {tuple(given.shape)}" if torch.is_tensor(given) else type(given).__name__
+        raise ValueError(f"given must be u8 {want}, got {got}")
 
 
 def _check_mask(given_shape, given_mask):

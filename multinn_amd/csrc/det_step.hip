@@ -525,8 +525,8 @@ static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps,
     if (c_out != nullptr) {                                    // the state behind the last step (at least one ran): stream-ordered behind every read of c0 / h0
         for (int l = 0; l < n_layers; ++l) {
             const size_t bytes = (size_t)B * layers[l].units * sizeof(float);
-            MNN_HIP(hipMemcpyAsync(c_out[l], cbuf[l][cur], bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
-            MNN_HIP(hipMemcpyAsync(h_out[l], hbuf[l][cur], bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
+            MNN_HIP(mnn_copy_async(c_out[l], cbuf[l][cur], bytes, (hipStream_t)s));      // (kernel nodes, not memcpy nodes: common.h)
+            MNN_HIP(mnn_copy_async(h_out[l], hbuf[l][cur], bytes, (hipStream_t)s));
         }
     }
     return MNN_OK;

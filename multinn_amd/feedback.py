@@ -6,7 +6,7 @@ import weakref
 import torch
 
 from . import ops
-from .common import Model, RNN, ParamStore
+from .common import Model, RNN, ParamStore, DrawAt, check_given
 from .generators import LstmStack, RnnEstimator, RnnNade, _compute_dtype, det_steps
 
 
@@ -207,32 +207,15 @@ class FeedbackRnnSampler:
         device (common.ScanGraphs): the M generators and the feedback module step inside the same captured scan.
         given (optional): codes u8 [B, num_steps, P, M] (common.given_codes), see generate_encoded.
         temperature: one for all generators or generator m's own, temperature[m]; 1.0 is the call (and the captured scan) without it."""
-        from .common import ScanGraphs, temperature_key
-        temperature = self._temperature(temperature)
-        if not ScanGraphs.enabled(x_u8):
-            return self._generate_scan(x_u8, num_steps, given, temperature)
-        if getattr(self, "_scan_graphs", None) is None:
-            self._scan_graphs = ScanGraphs()
-        key = (tuple(x_u8.shape), int(num_steps), tuple((g.seed, g.row0) for g in self.generators))
-        if given is not None:
-            key = key + ("given",)
-        key = key + temperature_key(temperature)
+        from .common import ScanGraphs
 
         def stale():
             for g in self.generators:
                 g._packed_step = -1
             if hasattr(self.feedback, "_packed_step"):
                 self.feedback._packed_step = -1
-
-        def scan(sx, sg=None):
-            stale()                                    # pack inside the graph: a replay always sees the current weights
-            return self._generate_scan(sx, num_steps, sg, temperature)
-
-        def warm(sx, sg=None):
-            n = min(int(num_steps), 2)
-            return self._generate_scan(sx, n, None if sg is None else sg[:, :n].contiguous(), temperature)
-
-        return self._scan_graphs.run(key, x_u8, scan, warm, stale, extra=given)
+        return ScanGraphs.generate(self, (tuple(x_u8.shape), int(num_steps), tuple((g.seed, g.row0) for g in self.generators)), x_u8, num_steps,
+                                   given, self._temperature(temperature), self._generate_scan, stale)
 
     def _group_dense(self, hs, rnn_states):
         """The M generators' Dense layers on their top outputs in one launch -> their RnnEstimatorStateTuples."""
@@ -284,9 +267,8 @@ class FeedbackRnnSampler:
                 states.append(g.steps(torch.cat([enc_tracks[i].float(), x_fb], -1)))                # multinn_feedback.py:143-149
         out = torch.empty((B, num_steps, P, M), device=dev, dtype=torch.uint8)
         if given is not None:
-            if given.dtype != torch.uint8 or tuple(given.shape) != (B, int(num_steps), P, M):
-                raise ValueError(f"given must be u8 [{B}, {int(num_steps)}, {P}, {M}], got {given.dtype} {tuple(given.shape)}")
-            given = given.contiguous()                      # (the strides of out: its [:, s, :, i] views are the sample views')
+            check_given(given, B, num_steps, P, M)
+            given = given.contiguous()                     # (the strides of out: its [:, s, :, i] views are the sample views')
         # Inside a step the tracks are independent: generator i's {sample | LSTM step, Dense} run on stream i, joined on
         # the main stream around the feedback step.  Their single steps take the launch-per-step LSTM kernels: persistent launches
         # spin on their own workgroups and must not share the device with one another (LstmStack.persist_single_step).
@@ -325,16 +307,11 @@ class FeedbackRnnSampler:
                     if par and (s == 0 or group):           # grouped steps run on the main stream: every lane waits for their Dense outputs
                         lanes[i].wait_stream(main)
                     with on(i):
-                        g._gen_step = s
-                        g._last_dense = states[i].dense
                         gi = None if given is None else given[:, s, :, i]
-                        kw = {} if temps[i] == 1.0 else dict(temperature=temps[i])
-                        if gi is None:
-                            smp, _ = g.sample_single(None, states[i], **kw)
-                        elif isinstance(g, RnnNade):
-                            smp, _ = g.sample_single(None, states[i], given=gi.contiguous(), **kw)
-                        else:                               # a wholly given track pasted over the RBM's sample
-                            smp, _ = g.sample_single(None, states[i], **kw)
+                        clamp = gi is not None and isinstance(g, RnnNade)
+                        smp, _ = g.sample_single(None, states[i], given=gi.contiguous() if clamp else None, temperature=temps[i],
+                                                 at=DrawAt(g.seed, g.row0, s))
+                        if gi is not None and not clamp:    # a wholly given track pasted over the RBM's sample
                             smp = torch.where(gi != 255, gi, smp)
                     samples.append(smp)
                 if par:

@@ -20,7 +20,7 @@ import torch
 
 from . import ops
 from .switches import flag, value
-from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, given_codes, given_mask_tracks, sampling_temperature, temperature_key, glorot_uniform, zeros_init, default_device, capture_train_step
+from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, DrawAt, check_given, given_codes, given_mask_tracks, sampling_temperature, glorot_uniform, zeros_init, default_device, capture_train_step
 from .training import compute_gradients, world, dp_active, AdamOptimizer
 from ._lib import MnnUnsupported
 from .lstm_stack import LstmStack, _SINGLE, drive, drive_group, _det_f32, det_steps
@@ -378,10 +378,7 @@ class RnnEstimator(Generator):
         return None                         # estimators without a one-call scan (RnnRBM) step through sample_single / single_step
 
     # -- generation sessions (session.py) --------------------------------------------------------
-    # Set by a session around a chunk of its step loop: sample_single draws at the sub-counter (_gen_step + *_gen_base) (* max(k, 1): RBM) --
-    # _gen_base a step cell on the device that the kernels read (a captured chunk), or None (the host offset is in _gen_step).
-    _gen_base = None
-    subs_per_step = 1                       # Philox sub-counters a generated step owns (RBM estimators: max(k, 1))
+    subs_per_step = 1                      # Philox sub-counters a generated step owns (RBM estimators: max(k, 1))
 
     def session(self, x):
         """A generation session on the intro x [B, Ti, Din] (generate's x): session.GeneratorSession -- sess.generate(num_steps, given,
@@ -510,56 +507,39 @@ class RnnEstimator(Generator):
         given (optional): codes u8 [B, num_steps, num_output] in the generator's feature order (common.given_codes): a clamped visible is
         emitted as given and fed forward like a draw, every free one is drawn from the uniform it draws unconditioned."""
         if given is not None:
-            n_out = getattr(self, "_num_output", self.num_dims)
-            if given.dtype != torch.uint8 or tuple(given.shape) != (x.shape[0], int(num_steps), n_out):
-                raise ValueError(f"given must be u8 [{x.shape[0]}, {int(num_steps)}, {n_out}], got {given.dtype} {tuple(given.shape)}")
+            check_given(given, x.shape[0], num_steps, self._num_output)
             given = given.contiguous()
-        temperature = self._temperature(temperature)
-        if not ScanGraphs.enabled(x):
-            return self._generate_scan(x, num_steps, given, temperature)
-        if getattr(self, "_scan_graphs", None) is None:
-            self._scan_graphs = ScanGraphs()
-        key = (tuple(x.shape), x.dtype, int(num_steps), self.seed, self.row0)
-        if given is not None:
-            key = key + ("given",)                     # a new given of the same shape replays the same graph
-        key = key + temperature_key(temperature)       # (baked into the captured launches; nothing at 1.0: the scan captured without it)
 
-        def scan(sx, sg=None):
-            self._packed_step = -1                     # pack inside the graph: a replay always sees the current weights
-            return self._generate_scan(sx, num_steps, sg, temperature)
-
-        def after():
-            self._packed_step = -1                     # the packed copies now live in the graph's pool
-
-        def warm(sx, sg=None):
-            n = min(int(num_steps), 2)
-            return self._generate_scan(sx, n, None if sg is None else sg[:, :n].contiguous(), temperature)
-
-        return self._scan_graphs.run(key, x, scan, warm, after, extra=given)
+        def stale():
+            self._packed_step = -1
+        return ScanGraphs.generate(self, (tuple(x.shape), x.dtype, int(num_steps), self.seed, self.row0), x, num_steps, given,
+                                   self._temperature(temperature), self._generate_scan, stale)
 
     def _generate_scan(self, x, num_steps, given=None, temperature=1.0):
         self._materialize(x.shape[-1])
         self._rnn.build_cell(False)
-        if self.det_sampling:
-            whole = self._scan_in_one_call(x, num_steps, given, temperature)     # LSTM-(Multi)NADE on a byte piano-roll: mnn_generate_scan runs the whole scan
-            if whole is not None:
-                return whole
-            state = self.steps(x)
-        else:
-            self._ensure_packed()
-            state = self._get_state(x, lengths=None, last_outputs=True)
-        intro = x[:, -1, :]
+        with self._sampling_scope():
+            if self.det_sampling:
+                whole = self._scan_in_one_call(x, num_steps, given, temperature)     # LSTM-(Multi)NADE on a byte piano-roll: mnn_generate_scan runs the whole scan
+                if whole is not None:
+                    return whole
+                state = self.steps(x)
+            else:
+                self._ensure_packed()
+                state = self._get_state(x, lengths=None, last_outputs=True)
+            return self._scan_steps(state, x[:, -1, :], num_steps, DrawAt(self.seed, self.row0, 0), given, temperature)[0]
+
+    def _scan_steps(self, state, last_row, n, at0, given=None, temperature=1.0):
+        """The step loop of a single generator (rnn_estimator.py:283-298): n x {sample_single, single_step} from `state` and the last emitted
+        row, step j drawing at at0's position moved on by j steps under given[:, j] -> (samples u8 [B, n, num_output], state, last row).
+        generate runs it from step 0, a session's chunk from where the piece stands."""
         out = []
-        for s in range(num_steps):
-            self._gen_step = s
-            kw = {} if temperature == 1.0 else dict(temperature=temperature)
-            if given is not None:
-                kw["given"] = given[:, s]
-            samples, _ = self.sample_single(intro, state, **kw)
-            state = self.single_step(samples, state)
-            intro = samples
-            out.append(samples)
-        return torch.stack(out, 1)
+        for j in range(n):
+            last_row, _ = self.sample_single(last_row, state, given=None if given is None else given[:, j], temperature=temperature,
+                                             at=at0._replace(step=at0.step + j))
+            state = self.single_step(last_row, state)
+            out.append(last_row)
+        return torch.stack(out, 1), state, last_row
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1034,7 +1014,6 @@ class RnnNade(RnnEstimator):
         be, bd = self._build_biases(out)
         st = RnnEstimatorStateTuple(be, bd, rnn_state)
         st.dense = out
-        self._last_dense = out
         return st
 
     def _get_state(self, inputs, lengths=None, initial_state=None, last_outputs=False):
@@ -1116,19 +1095,20 @@ class RnnNade(RnnEstimator):
         state = self._get_state(inputs, lengths=lengths)
         return self._nade.log_prob(targets_flat, state.b_enc, state.b_dec)
 
-    def sample_single(self, inputs, state, temperature=1.0, given=None):
+    def sample_single(self, inputs, state, *, given=None, temperature=1.0, at=None):
         """rnn_nade.py:304-318 / rnn_multinade.py:295-317: returns (sample u8 [B,num_output], nll).  given (optional): codes u8
         [B, num_output] (ops.nade_sample): clamped visibles are emitted as given, nll is that of the emitted vector.
         temperature: a float, None (threshold draws), or a sequence -- per track of a MultiNADE, by visible index modulo its length for
-        the one NADE; the returned nll stays the model's own."""
+        the one NADE; the returned nll stays the model's own.  at (common.DrawAt; None: this generator's seed and row0, step 0): where
+        the draws stand.  The biases are the state's Dense block (state.dense: every state a step or an intro pass returns has one)."""
         M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
-        out = state.dense if getattr(state, "dense", None) is not None else self._last_dense
+        at = DrawAt(self.seed, self.row0, 0) if at is None else at
+        out = state.dense
         Bn = out.shape[0]
         smp = torch.empty((Bn, M * D), device=out.device, dtype=torch.uint8)
         nll = torch.empty((M, Bn), device=out.device)
-        ops.nade_sample(out, self.store["nade/w_enc"], self.store["nade/w_dec"], M, D, Hn, temperature, self.seed, self.row0,
-                        getattr(self, "_gen_step", 0), smp, track_minor=(M > 1), nll=nll, given=None if given is None else given.contiguous(),
-                        by_visible=M == 1, sub_base=self._gen_base)
+        ops.nade_sample(out, self.store["nade/w_enc"], self.store["nade/w_dec"], M, D, Hn, temperature, at.seed, at.row0, at.step, smp,
+                        track_minor=(M > 1), nll=nll, given=None if given is None else given.contiguous(), by_visible=M == 1, sub_base=at.base)
         return smp, (nll[0] if M == 1 else [nll[m] for m in range(M)])
 
 
@@ -1470,7 +1450,7 @@ class RnnRBM(RnnEstimator):
 
     subs_per_step = property(lambda self: max(self._k, 1))
 
-    _det_bias = None                       # inside RnnMultiRBM._generate_scan: True, then the internal bias vectors the scan's first Dense formed
+    _det_bias = None                       # inside RnnMultiRBM._sampling_scope: True, then the internal bias vectors the scan's first Dense formed
 
     def _det_state(self, h, rnn_state):
         """rnn_rbm.py:240-259 in the deterministic arithmetic: [bh_0 ..] = [rbm_m.bh] + h . Wuh, [bv_0 ..] = [rbm_m.bv] + h . Wuv (two jobs,
@@ -1504,13 +1484,15 @@ class RnnRBM(RnnEstimator):
     def _temperature(self, temperature):
         return sampling_temperature(temperature, allow_none=False, allow_sequence=False)
 
-    def sample_single(self, inputs, state, given=None, temperature=1.0):
+    def sample_single(self, inputs, state, *, given=None, temperature=1.0, at=None):
         """rnn_rbm.py:283-297 with k = rbm.k (R1): returns (sample u8, cond_prob).  temperature: the chain of exp(-E / T), cond_prob the
         tempered probability.  given (optional): codes u8 [B, D] (a step slice of
         generate's [B, num_steps, D] is read in place): the clamped Gibbs chain -- clamped visibles are emitted as given, every free one is
-        sampled conditioned on all of them (RBM.sample); cond_prob is sigmoid(logit) at every visible."""
-        p_v, v = self._rbm.sample(inputs[:, :self.num_dims], state.b_enc, state.b_dec, self._k, self.seed, self.row0, None,
-                                  getattr(self, "_gen_step", 0) * max(self._k, 1), given=given, temperature=temperature, sub_base=self._gen_base)
+        sampled conditioned on all of them (RBM.sample); cond_prob is sigmoid(logit) at every visible.  at (common.DrawAt; None: this
+        generator's seed and row0, step 0): where the chain's draws stand -- a step owns max(k, 1) sub-counters."""
+        at = DrawAt(self.seed, self.row0, 0) if at is None else at
+        p_v, v = self._rbm.sample(inputs[:, :self.num_dims], state.b_enc, state.b_dec, self._k, at.seed, at.row0, None,
+                                  at.step * self.subs_per_step, given=given, temperature=temperature, sub_base=at.base)
         return v, p_v
 
     def pretrain(self, optimizer, lr, run_optimizer=True):
@@ -1577,10 +1559,6 @@ class RnnMultiRBM(RnnRBM):
     def _temperature(self, temperature):
         return sampling_temperature(temperature, self.num_tracks, allow_none=False)
 
-    def _generate_scan(self, x, num_steps, given=None, temperature=1.0):
-        with self._sampling_scope():
-            return super()._generate_scan(x, num_steps, given, temperature)
-
     @contextlib.contextmanager
     def _sampling_scope(self):
         self._det_bias = True              # the first Dense of this scan forms the internal bias vectors, the later ones reuse them
@@ -1589,18 +1567,19 @@ class RnnMultiRBM(RnnRBM):
         finally:
             self._det_bias = None
 
-    def sample_single(self, inputs, state, given=None, temperature=1.0):
+    def sample_single(self, inputs, state, *, given=None, temperature=1.0, at=None):
         """The M chains of a sampling step in ONE grouped launch (temperature: one for all, or track m's chain at temperature[m]): the previous row is read, and the new one written, in composer layout in
         place (element stride M), track m with seed + m.  Returns (sample u8 [B, M * D], cond_prob f32 [B, M * D]).  given (optional):
-        codes u8 [B, M * D] in the same layout (a step slice of generate's block is read in place): every track runs the clamped chain."""
+        codes u8 [B, M * D] in the same layout (a step slice of generate's block is read in place): every track runs the clamped chain.
+        at: RnnRBM.sample_single's."""
         M, D = self.num_tracks, self.num_dims
+        at = DrawAt(self.seed, self.row0, 0) if at is None else at
         v0 = inputs[:, :M * D]
         v0 = (v0 if v0.dtype == torch.uint8 else v0.to(torch.uint8)).contiguous()
         Bn = v0.shape[0]
         smp = torch.empty((Bn, M * D), device=v0.device, dtype=torch.uint8)
         p_v = torch.empty((Bn, M * D), device=v0.device)
-        jobs = [dict(v0=v0[:, m::M], W=r.W, bh=state.b_enc[m], bv=state.b_dec[m], seed=self.seed + m, p_v=p_v[:, m::M], v_out=smp[:, m::M],
+        jobs = [dict(v0=v0[:, m::M], W=r.W, bh=state.b_enc[m], bv=state.b_dec[m], seed=at.seed + m, p_v=p_v[:, m::M], v_out=smp[:, m::M],
                      given=None if given is None else given[:, m::M]) for m, r in enumerate(self._rbms)]
-        ops.rbm_gibbs_multi(jobs, self._k, self.row0, None, getattr(self, "_gen_step", 0) * max(self._k, 1), temperature=temperature,
-                            sub_base=self._gen_base)
+        ops.rbm_gibbs_multi(jobs, self._k, at.row0, None, at.step * self.subs_per_step, temperature=temperature, sub_base=at.base)
         return smp, p_v

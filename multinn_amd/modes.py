@@ -20,6 +20,7 @@ scan.  The encoder-level ("global") metrics the reference adds to the graph but 
 (HIP kernels behind the C ABI); this file only slices, stacks and reshapes device tensors.
 """
 import abc
+import functools
 import os
 import weakref
 
@@ -286,6 +287,45 @@ class MultINNCore(Model):
     def _refuse_given(self, whole, some):
         """NotImplementedError for a mask this mode's generators cannot honour (every generator of the joint, composer and jamming modes
         clamps inside its sampling kernels; see MultINNFeedback)."""
+
+    def _generate_arguments(self, num_steps, given, given_mask, temperature):
+        """The head of every generate and of a session's chunk, on the host: the temperature first, then the codes -> (temperature, cond)."""
+        temperature = self._temperature(temperature)
+        return temperature, self._given(num_steps, given, given_mask)
+
+    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0):
+        """-> u8 `[B, num_steps, P, M]` (multinn_joint.py:188-215, multinn_jamming.py:101-133, multinn_composer.py:114-151): every generator's
+        scan on its encoded intro, decoded per track.  temperature: _temperature; given / given_mask: conditional generation (_given).
+        What the modes differ in is in _generator_inputs, _generator_given and _decode_samples."""
+        temperature, cond = self._generate_arguments(num_steps, given, given_mask, temperature)
+        if self._x_encoded is None:
+            MultINNCore._build_all(self, "generate")
+        scans = [functools.partial(g.generate, x) for g, x in zip(self.generators, self._generator_inputs())]
+        return self._sample_generators(scans, num_steps, cond, temperature)
+
+    def _sample_generators(self, scans, num_steps, cond, temperature, session=False):
+        """scans: per generator its scan(num_steps, given=, temperature=) -- its generate on its intro, or its session's chunk -> the
+        decoded piano-roll.  One generator takes the whole temperature, M generators one each; a generator whose scan does not run
+        (_generator_given) emits its codes."""
+        n = len(scans)
+        temps = list(temperature) if isinstance(temperature, tuple) and n > 1 else [temperature] * n
+        givens = [(None, True)] * n if cond is None else self._generator_given(cond, session)
+        samples = [scan(num_steps, given=gv, temperature=t) if run else gv for scan, (gv, run), t in zip(scans, givens, temps)]
+        return self._decode_samples(samples, num_steps)
+
+    def _generator_inputs(self):
+        """The generators' encoded intros, one per generator (here: the one generator of the joint mode)."""
+        return [self._x_encoded]
+
+    def _generator_given(self, cond, session=False):
+        """cond = (codes u8 [B, n, P, M], whole, some) -> per generator (its `given` or None, whether its scan runs).  Here one generator
+        over all tracks: the codes in feature order p M + m -- the joint NADE's order, and the MultiNADE's / MultiRBM's i tracks + m."""
+        codes = cond[0]
+        return [(codes.reshape(codes.shape[0], codes.shape[1], -1), True)]
+
+    def _decode_samples(self, samples, num_steps):
+        """The generators' samples (a list, one u8 [B, n, .] per generator) -> u8 [B, n, P, M] through the encoders."""
+        raise NotImplementedError
 
     def evaluator(self):
         """multinn_core.py:343-362: musical metrics of the fed batch reshaped into bars `[B, bars, 4*beat_resolution, pitch_span, M]`."""
@@ -656,24 +696,13 @@ class MultINNJoint(MultINNCore):
         rbm = self._generator_type == "RBM"
         return sampling_temperature(temperature, self.num_tracks, allow_none=not rbm, allow_sequence=not rbm and self._encoder_type == "Pass")
 
-    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0):
-        """multinn_joint.py:188-215 -> u8 `[B, num_steps, P, M]`.  temperature: MultINNCore._temperature; a sequence tempers each conditional
-        of the NADE by its track.  given / given_mask: conditional generation (MultINNCore._given), codes in
-        p M + m order.  The one NADE orders the visibles of a step p M + m: a free visible is conditioned on the clamped visibles ordered
+    def _decode_samples(self, samples, num_steps):
+        """multinn_joint.py:188-215: the one encoder's decode, then [B, n, P, M].  A temperature sequence tempers each conditional of the
+        NADE by its track.  The one NADE orders the visibles of a step p M + m: a free visible is conditioned on the clamped visibles ordered
         BEFORE it only (the ones after it are fed forward to the later visibles and steps) -- what a NADE offers without importance sampling.
         An RBM generator runs the clamped Gibbs chain: every free visible is conditioned on ALL clamped ones, in any position."""
-        temperature = self._temperature(temperature)
-        kw = {} if temperature == 1.0 else dict(temperature=temperature)
-        cond = self._given(num_steps, given, given_mask)
-        if self._x_encoded is None:
-            MultINNCore._build_all(self, "generate")
-        if cond is None:
-            samples_h = self._generator.generate(self._x_encoded, num_steps, **kw)
-        else:
-            codes = cond[0]
-            samples_h = self._generator.generate(self._x_encoded, num_steps, given=codes.reshape(codes.shape[0], num_steps, -1), **kw)
-        _, samples = self._encoder.decode(samples_h)
-        return samples.reshape(-1, num_steps, self.num_dims, self.num_tracks).to(torch.uint8)
+        _, music = self._encoder.decode(samples[0])
+        return music.reshape(-1, num_steps, self.num_dims, self.num_tracks).to(torch.uint8)
 
     def train_encoders(self, optimizer, lr, layer=0):
         if self._inputs is None:
@@ -747,6 +776,10 @@ class MultIEncoderNN(MultINNCore):
             probs.append(p); outs.append(d)
         return probs, outs
 
+    def _decode_samples(self, samples, num_steps):
+        """One sampled code block u8 [B, n, E] per track (the jamming mode's generators) -> track i through encoder i, stacked [B, n, P, M]."""
+        return torch.stack([self.encoders[i].decode(h)[1].to(torch.uint8) for i, h in enumerate(samples)], dim=3)
+
 
 class MultINNJamming(MultIEncoderNN):
     """multinn_jamming.py: M independent per-track generators."""
@@ -813,27 +846,16 @@ class MultINNJamming(MultIEncoderNN):
     def _decode_generator_outputs(self):
         return self._decode_tracks(self._x_hidden)
 
-    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0):
-        """multinn_jamming.py:101-133 -> u8 `[B, num_steps, P, M]`.  temperature (MultINNCore._temperature): generator m samples at its own.  given / given_mask (MultINNCore._given): the generators are independent --
-        a wholly given track is not sampled at all, a partly given one is clamped inside its generator's scan (the NADE sampling kernels, or
-        an RBM generator's clamped Gibbs chain)."""
-        temperature = self._temperature(temperature)
-        temps = list(temperature) if isinstance(temperature, tuple) else [temperature] * self.num_tracks
-        cond = self._given(num_steps, given, given_mask)
-        if self._x_encoded is None:
-            MultINNCore._build_all(self, "generate")
-        music = []
-        for i in range(self.num_tracks):
-            kw = {} if temps[i] == 1.0 else dict(temperature=temps[i])
-            if cond is not None and cond[1][i]:
-                music.append(cond[0][..., i].contiguous())
-                continue
-            if cond is not None and cond[2][i]:
-                samples_h = self.generators[i].generate(self._x_encoded[i], num_steps, given=cond[0][..., i].contiguous(), **kw)
-            else:
-                samples_h = self.generators[i].generate(self._x_encoded[i], num_steps, **kw)
-            music.append(self.encoders[i].decode(samples_h)[1].to(torch.uint8))
-        return torch.stack(music, dim=3)
+    def _generator_inputs(self):
+        return self._x_encoded
+
+    def _generator_given(self, cond, session=False):
+        """multinn_jamming.py:101-133, conditioned: the generators are independent, generator m samples at its own temperature.  A partly
+        given track is clamped inside its generator's scan (the NADE sampling kernels, or an RBM generator's clamped Gibbs chain).  A wholly
+        given track: generate does not sample it at all (its codes are its notes); a SESSION still runs its clamped chunk -- the output
+        equals the given notes -- so that its state and counters advance and a later chunk can free it."""
+        codes, whole, some = cond
+        return [(codes[..., i].contiguous() if some[i] else None, session or not whole[i]) for i in range(self.num_tracks)]
 
     def pretrain_generators(self, optimizer, lr, separate_losses=False):
         return self._train_generators(optimizer, lr, pretrain=True, separate_losses=separate_losses)
@@ -928,23 +950,16 @@ class MultINNComposer(MultIEncoderNN):
     def _decode_generator_outputs(self):
         return self._decode_tracks(self._x_hidden)
 
-    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0):
-        """multinn_composer.py:114-151 -> u8 `[B, num_steps, P, M]`.  temperature (MultINNCore._temperature): track m's NADE scan or Gibbs
-        chain runs at its own.  given / given_mask (MultINNCore._given): the tracks of a step are
+    def _generator_inputs(self):
+        return [self._x_encoded_stack]
+
+    def _decode_samples(self, samples, num_steps):
+        """multinn_composer.py:114-151: the one generator's block [B, n, E * M] (feature e M + m) unbound into its tracks, then
+        MultIEncoderNN's per-track decode.  Track m's NADE scan or Gibbs chain runs at its own temperature; the tracks of a step are
         conditionally independent given the history, so clamping whole tracks conditions the others exactly."""
-        temperature = self._temperature(temperature)
-        kw = {} if temperature == 1.0 else dict(temperature=temperature)
-        cond = self._given(num_steps, given, given_mask)
-        if self._x_encoded is None:
-            MultINNCore._build_all(self, "generate")
-        if cond is None:
-            samples_h = self._generator.generate(self._x_encoded_stack, num_steps, **kw)
-        else:
-            codes = cond[0]                                         # [B, steps, P, M] -> feature p M + m: the MultiNADE's i tracks + m
-            samples_h = self._generator.generate(self._x_encoded_stack, num_steps, given=codes.reshape(codes.shape[0], num_steps, -1), **kw)
-        samples_h = samples_h.reshape(samples_h.shape[0], num_steps, self._num_dims_generator, self.num_tracks).unbind(-1)
-        music = [self.encoders[i].decode(samples_h[i].contiguous())[1].to(torch.uint8) for i in range(self.num_tracks)]
-        return torch.stack(music, dim=3)
+        h = samples[0]
+        tracks = h.reshape(h.shape[0], num_steps, self._num_dims_generator, self.num_tracks).unbind(-1)
+        return super()._decode_samples([t.contiguous() for t in tracks], num_steps)
 
     def pretrain_generators(self, optimizer, lr, separate_losses=False):
         return self._generator.pretrain(optimizer, lr)
@@ -1025,9 +1040,7 @@ class MultINNFeedback(MultINNJamming):
         temperature (MultINNCore._temperature): generator m samples at its own inside the scan.
         given / given_mask (MultINNCore._given): NADE generators clamp inside the scan, RBM generators take whole given tracks only."""
         from .feedback import FeedbackRnnSampler
-        temperature = self._temperature(temperature)
-        kw = {} if temperature == 1.0 else dict(temperature=temperature)
-        cond = self._given(num_steps, given, given_mask)
+        temperature, cond = self._generate_arguments(num_steps, given, given_mask, temperature)
         if self._x_encoded is None:
             self._inputs = self._build_inputs()
             self._build_encoders("eval")
@@ -1036,15 +1049,11 @@ class MultINNFeedback(MultINNJamming):
             self._feedback_layer = self._init_feedback(self._num_dims_generator * self.num_tracks)
         if getattr(self, "_sampler", None) is None:
             self._sampler = FeedbackRnnSampler(self.generators, self._feedback_layer)
-        if self._encoder_type == "Pass":
-            if cond is None:
-                samples_h = self._sampler.generate(self._x, num_steps, **kw)                      # whole scan = one hipGraph replay
-            else:
-                samples_h = self._sampler.generate(self._x, num_steps, given=cond[0], **kw)
+        if self._encoder_type == "Pass":                                                          # whole scan = one hipGraph replay
+            samples_h = self._sampler.generate(self._x, num_steps, given=None if cond is None else cond[0], temperature=temperature)
         else:
-            samples_h = self._sampler.generate_encoded([e.to(torch.uint8) for e in self._x_encoded], num_steps, **kw)
-        music = [self.encoders[i].decode(samples_h[..., i].contiguous())[1].to(torch.uint8) for i in range(self.num_tracks)]
-        return torch.stack(music, dim=3)
+            samples_h = self._sampler.generate_encoded([e.to(torch.uint8) for e in self._x_encoded], num_steps, temperature=temperature)
+        return self._decode_samples([samples_h[..., i].contiguous() for i in range(self.num_tracks)], num_steps)
 
     @property
     def trainable_feedback_variables(self):

@@ -1279,34 +1279,41 @@ def _scan_state(what, state, arr, B, device):
     return (C.c_void_p * len(arr))(*[c.data_ptr() for c, _ in state]), (C.c_void_p * len(arr))(*[h.data_ptr() for _, h in state])
 
 
+def _scan_call(what, ref, intro, Ti, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, seed, row0, given):
+    """What generate_scan and generate_scan_chunk share: the table and `given` checks, the workspace (256-byte aligned) and the samples
+    u8 [B, num_steps, tracks * D] on ref's device -> (layer table, launch).  launch(symbol, temps, *state) makes the call -- the 16 leading
+    arguments, the temperature slot, seed .. given, then the entry point's own state arguments -- and returns the samples."""
+    B, n_in, n_out = ref.shape[0], tracks * D, tracks * (Hn + D)
+    arr = _scan_tables(what, layers, n_in, n_out, dense_W, dense_bias, w_enc, w_dec, tracks, D, Hn)
+    if given is not None:
+        _req(given.dtype == torch.uint8 and tuple(given.shape) == (B, num_steps, n_in) and given.is_contiguous() and given.device == ref.device,
+             f"{what}: given u8 [B, num_steps, tracks * D], contiguous")
+    need = int(_lib.load().mnn_generate_scan_workspace_bytes(B, n_in, len(layers), arr, n_out))
+    ws = torch.empty(need + 256, dtype=torch.uint8, device=ref.device)
+    off = (-ws.data_ptr()) % 256
+    samples = torch.empty((B, num_steps, n_in), dtype=torch.uint8, device=ref.device)
+
+    def launch(symbol, temps, *state):
+        call(symbol, _stream(), B, Ti, num_steps, _ptr(intro), n_in, len(layers), arr, _ptr(dense_W), _ptr(dense_bias), n_out, tracks, D, Hn,
+             _ptr(w_enc), _ptr(w_dec), temps, int(seed), int(row0), _ptr(samples), C.c_void_p(ws.data_ptr() + off), need, _ptr(given), *state)
+        return samples                      # (the workspace returns to the allocator in stream order: later users are behind the scan)
+    return arr, launch
+
+
 def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, given=None, state0=None,
                   by_visible=False):
     """mnn_generate_scan: the whole sampling scan of an LSTM-(Multi)NADE generator in one call.  intro u8 [B, Ti, tracks * D]; layers = [(W, bias)]
     f32 master weights; returns samples u8 [B, num_steps, tracks * D].  given (optional): codes u8 [B, num_steps, tracks * D] in the layout of
     the samples (see nade_sample).  temperature: a float, None, or a sequence (per track, or by visible index: nade_sample).  state0 (optional, mnn_generate_scan_state): [(c0, h0) f32 [B, u]] per layer, the state the intro pass starts from."""
     _req(intro.dtype == torch.uint8 and intro.dim() == 3 and intro.is_contiguous() and intro.shape[2] == tracks * D, "generate_scan: intro u8 [B, Ti, tracks * D]")
-    B, Ti, n_in = intro.shape
-    n_out = tracks * (Hn + D)
-    arr = _scan_tables("generate_scan", layers, n_in, n_out, dense_W, dense_bias, w_enc, w_dec, tracks, D, Hn)
-    if given is not None:
-        _req(given.dtype == torch.uint8 and tuple(given.shape) == (B, int(num_steps), n_in) and given.is_contiguous() and given.device == intro.device,
-             "generate_scan: given u8 [B, num_steps, tracks * D], contiguous")
+    arr, launch = _scan_call("generate_scan", intro, intro, intro.shape[1], int(num_steps), layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec,
+                             seed, row0, given)
     tt = _temps(temperature, tracks, by_visible, "generate_scan")
-    need = int(_lib.load().mnn_generate_scan_workspace_bytes(B, n_in, len(layers), arr, n_out))
-    ws = torch.empty(need + 256, dtype=torch.uint8, device=intro.device)
-    off = (-ws.data_ptr()) % 256
-    samples = torch.empty((B, int(num_steps), n_in), dtype=torch.uint8, device=intro.device)
-    args = (_stream(), B, Ti, int(num_steps), _ptr(intro), n_in, len(layers), arr, _ptr(dense_W), _ptr(dense_bias), n_out, tracks, D, Hn,
-            _ptr(w_enc), _ptr(w_dec), 1.0 if tt is not None else float(-1.0 if temperature is None else temperature), int(seed), int(row0),
-            _ptr(samples), C.c_void_p(ws.data_ptr() + off), need, _ptr(given))        # (args[16]: the float, replaced by the table where there is one)
-    cp, hp = _scan_state("generate_scan: state0", state0, arr, B, intro.device)
+    cp, hp = _scan_state("generate_scan: state0", state0, arr, intro.shape[0], intro.device)
     if tt is not None:              # a temperature table: the one entry point that takes it, with or without an initial state
-        call("mnn_generate_scan_temps", *args[:16], C.byref(tt), *args[17:], cp, hp)
-    elif state0 is None:
-        call("mnn_generate_scan", *args)
-    else:
-        call("mnn_generate_scan_state", *args, cp, hp)
-    return samples                          # (the workspace returns to the allocator in stream order: later users are behind the scan)
+        return launch("mnn_generate_scan_temps", C.byref(tt), cp, hp)
+    t = float(-1.0 if temperature is None else temperature)
+    return launch("mnn_generate_scan", t) if state0 is None else launch("mnn_generate_scan_state", t, cp, hp)
 
 
 def generate_scan_chunk(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, state_in, state_out,
@@ -1317,25 +1324,14 @@ def generate_scan_chunk(intro, num_steps, layers, dense_W, dense_bias, tracks, D
     with the sub-counter step0 + *step_base + st (step_base: one int32 on the device, or None).  Returns samples u8 [B, num_steps, tracks * D];
     given (optional): the chunk's codes in that layout.  Everything else is generate_scan."""
     ref = intro if intro is not None else state_in[0][0]
-    n_in, n_out, num_steps = tracks * D, tracks * (Hn + D), int(num_steps)
-    B, Ti = (ref.shape[0], 0) if intro is None else (intro.shape[0], intro.shape[1])
-    _req(intro is None or (intro.dtype == torch.uint8 and intro.dim() == 3 and intro.is_contiguous() and intro.shape[2] == n_in and Ti > 0),
+    num_steps, Ti = int(num_steps), 0 if intro is None else intro.shape[1]
+    _req(intro is None or (intro.dtype == torch.uint8 and intro.dim() == 3 and intro.is_contiguous() and intro.shape[2] == tracks * D and Ti > 0),
          "generate_scan_chunk: intro u8 [B, Ti, tracks * D]")
     _req(num_steps >= 0 and Ti + num_steps > 0 and (Ti > 0 or state_in is not None), "generate_scan_chunk: an intro, or steps from an input state")
-    arr = _scan_tables("generate_scan_chunk", layers, n_in, n_out, dense_W, dense_bias, w_enc, w_dec, tracks, D, Hn)
-    if given is not None:
-        _req(given.dtype == torch.uint8 and tuple(given.shape) == (B, num_steps, n_in) and given.is_contiguous() and given.device == ref.device,
-             "generate_scan_chunk: given u8 [B, num_steps, tracks * D], contiguous")
-
-    ci, hi = _scan_state("generate_scan_chunk: state_in", state_in, arr, B, ref.device)
-    co, ho = _scan_state("generate_scan_chunk: state_out", state_out, arr, B, ref.device)
+    arr, launch = _scan_call("generate_scan_chunk", ref, intro, Ti, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, seed, row0, given)
+    ci, hi = _scan_state("generate_scan_chunk: state_in", state_in, arr, ref.shape[0], ref.device)
+    co, ho = _scan_state("generate_scan_chunk: state_out", state_out, arr, ref.shape[0], ref.device)
     _req(0 <= int(step0) and int(step0) + num_steps <= 1 << 32, "generate_scan_chunk: step0 + num_steps passes 2^32")
     tt = _temps_table(temperature, tracks, by_visible, "generate_scan_chunk")
-    need = int(_lib.load().mnn_generate_scan_workspace_bytes(B, n_in, len(layers), arr, n_out))
-    ws = torch.empty(need + 256, dtype=torch.uint8, device=ref.device)
-    off = (-ws.data_ptr()) % 256
-    samples = torch.empty((B, num_steps, n_in), dtype=torch.uint8, device=ref.device) if num_steps > 0 else None
-    call("mnn_generate_scan_chunk", _stream(), B, Ti, num_steps, _ptr(intro), n_in, len(layers), arr, _ptr(dense_W), _ptr(dense_bias), n_out, tracks, D, Hn,
-         _ptr(w_enc), _ptr(w_dec), C.byref(tt), int(seed), int(row0), _ptr(samples), C.c_void_p(ws.data_ptr() + off), need, _ptr(given), ci, hi, co, ho,
-         int(step0), _sub_base(step_base, ref, "generate_scan_chunk"))
-    return samples                          # (the workspace returns to the allocator in stream order: later users are behind the chunk)
+    samples = launch("mnn_generate_scan_chunk", C.byref(tt), ci, hi, co, ho, int(step0), _sub_base(step_base, ref, "generate_scan_chunk"))
+    return samples if num_steps > 0 else None

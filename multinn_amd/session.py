@@ -16,13 +16,12 @@ GeneratorSession: one RnnEstimator (RnnNade, RnnMultiNADE, RnnRBM, RnnMultiRBM).
 Pass encoders.  Captured (common.ScanGraphs.enabled) and eager chunks run the same launches and give the same bits.
 """
 import collections
-import contextlib
 
 import torch
 
 from . import ops
 from ._lib import MnnUnsupported
-from .common import ScanGraphs, _warm_up, graph_capture, temperature_key
+from .common import DrawAt, ScanGraphs, _warm_up, check_given, graph_capture, temperature_key
 
 __all__ = ["GeneratorSession", "ModeSession"]
 
@@ -43,10 +42,7 @@ def _chunk_arguments(gen, batch, steps, num_steps, given=None, temperature=1.0):
     [batch, num_steps, num_output], or a bad temperature (the generator's own _temperature)."""
     num_steps = _num_steps(steps, num_steps, gen.subs_per_step)
     if given is not None:
-        n_out = getattr(gen, "_num_output", gen.num_dims)
-        if not torch.is_tensor(given) or given.dtype != torch.uint8 or tuple(given.shape) != (int(batch), num_steps, n_out):
-            got = f"{given.dtype} {tuple(given.shape)}" if torch.is_tensor(given) else type(given).__name__
-            raise ValueError(f"given must be u8 [{int(batch)}, {num_steps}, {n_out}], got {got}")
+        check_given(given, batch, num_steps, gen._num_output)
     return num_steps, given, gen._temperature(temperature)
 
 
@@ -57,9 +53,11 @@ class GeneratorSession:
     generator's step loop also the last Dense output block and the last emitted row; the step cell.  A byte piano-roll into an LSTM-(Multi)NADE
     runs each chunk as ONE library call (mnn_generate_scan_chunk, which forms the first Dense of a chunk from h of the last layer again: the
     same product, the same bits); every other case steps through sample_single / single_step like generate.
-    seed and row0 are the generator's when the session is opened.  For the duration of a chunk the session sets them (and the step counter
-    and cell that sample_single reads) on the generator and puts the generator's own back: sessions and generate calls on one generator may
-    interleave freely on one thread, but must not run from two threads at once."""
+    seed and row0 are the generator's when the session is opened; every chunk hands them, the step and the step cell to the generator's
+    draws as a common.DrawAt, and nothing on the generator is set or restored: changing gen.seed / gen.row0 later moves generate, not the
+    session.  Sessions and generate calls on one generator interleave freely.  What they still share is the generator's per-scan state --
+    RnnMultiRBM._det_bias inside _sampling_scope, the packed weight copies, the step staging buffer -- so two scans of ONE generator must
+    not run from two threads at once."""
 
     def __init__(self, gen, x):
         from .generators import refuse_host_model
@@ -83,7 +81,7 @@ class GeneratorSession:
             ops.generate_scan_chunk(x.contiguous(), 0, temperature=1.0, seed=self.seed, row0=self.row0, state_in=gen._state0(B, torch.float32),
                                     state_out=self._rnn, **gen._scan_layers())
             return
-        with self._pinned(None):
+        with gen._sampling_scope():
             if gen.det_sampling:
                 state = gen.steps(x)
             else:
@@ -91,8 +89,7 @@ class GeneratorSession:
                 state = gen._get_state(x, lengths=None, last_outputs=True)
         self._rnn = [(c.clone(), h.clone()) for c, h in state.rnn_state]
         self._out = state.dense.clone()
-        n_out = getattr(gen, "_num_output", gen.num_dims)
-        self._last = x[:, -1, :n_out].to(torch.uint8).contiguous().clone()         # the first chain's start (rnn_estimator.py:283: the intro's last row)
+        self._last = x[:, -1, :gen._num_output].to(torch.uint8).contiguous().clone()         # the first chain's start (rnn_estimator.py:283: the intro's last row)
 
     # -- state ----------------------------------------------------------------------------------
     def _tensors(self):
@@ -113,19 +110,6 @@ class GeneratorSession:
         self.steps = int(steps)
 
     # -- chunks ---------------------------------------------------------------------------------
-    @contextlib.contextmanager
-    def _pinned(self, base):
-        """The generator as the session's chunks see it: seed / row0 of the opening, the step cell (or None), one sampling scope."""
-        gen = self._gen
-        saved = (gen.seed, gen.row0, getattr(gen, "_gen_step", 0))
-        gen.seed, gen.row0, gen._gen_base = self.seed, self.row0, base
-        try:
-            with gen._sampling_scope():
-                yield
-        finally:
-            gen.seed, gen.row0, gen._gen_step = saved
-            gen._gen_base = None
-
     def _run(self, n, given, temperature, base):
         """The launches of one chunk of n steps from the static state, which they advance in place.  base: the step cell (a captured chunk:
         the kernels add its word to their counters) or None (eager: the host adds `steps`)."""
@@ -134,26 +118,17 @@ class GeneratorSession:
         if self._scan:
             return ops.generate_scan_chunk(None, n, temperature=temperature, seed=self.seed, row0=self.row0, state_in=self._rnn, state_out=self._rnn,
                                            given=given, step0=step0, step_base=base, **gen._scan_layers())
-        with self._pinned(base):
+        with gen._sampling_scope():
             if not gen.det_sampling:
                 gen._ensure_packed()
-            state = gen._state_of(self._out, tuple(self._rnn))
-            intro, out = self._last, []
-            for j in range(n):
-                gen._gen_step = step0 + j
-                kw = {} if temperature == 1.0 else dict(temperature=temperature)
-                if given is not None:
-                    kw["given"] = given[:, j]
-                samples, _ = gen.sample_single(intro, state, **kw)
-                state = gen.single_step(samples, state)
-                intro = samples
-                out.append(samples)
+            out, state, last = gen._scan_steps(gen._state_of(self._out, tuple(self._rnn)), self._last, n,
+                                               DrawAt(self.seed, self.row0, step0, base), given, temperature)
             for (c, h), (nc, nh) in zip(self._rnn, state.rnn_state):      # behind the last read of the static arrays
                 c.copy_(nc)
                 h.copy_(nh)
             self._out.copy_(state.dense)
-            self._last.copy_(intro)
-        return torch.stack(out, 1)
+            self._last.copy_(last)
+        return out
 
     def generate(self, num_steps, given=None, temperature=1.0):
         """The next num_steps steps -> u8 [B, num_steps, num_output].  given: the chunk's codes u8 [B, num_steps, num_output] as generate's
@@ -210,14 +185,11 @@ class ModeSession:
         if model._encoder_type != "Pass":
             raise MnnUnsupported("generation sessions through DBN encoders are not implemented: use Pass encoders")
         refuse_host_model(model.device, "a generation session")
-        self._model, self._mode = model, mode
+        self._model = model
         self.steps = 0
         if model._x_encoded is None:
             MultINNCore._build_all(model, "generate")
-        if mode == "jamming":
-            self._subs = [g.session(model._x_encoded[i]) for i, g in enumerate(model.generators)]
-        else:
-            self._subs = [model._generator.session(model._x_encoded if mode == "joint" else model._x_encoded_stack)]
+        self._subs = [g.session(x) for g, x in zip(model.generators, model._generator_inputs())]
 
     def snapshot(self):
         return self.steps, [s.snapshot() for s in self._subs]
@@ -235,28 +207,13 @@ class ModeSession:
         generate, checked once per chunk, and free to change from chunk to chunk."""
         m = self._model
         n = _num_steps(self.steps, num_steps, max(s._gen.subs_per_step for s in self._subs))
-        temperature = m._temperature(temperature)
-        cond = m._given(n, given, given_mask)
-        P, M = m.num_dims, m.num_tracks
-        if self._mode == "jamming":
-            temps = list(temperature) if isinstance(temperature, tuple) else [temperature] * M
-            music = []
-            snap = self.snapshot()                   # the tracks advance one after another: a chunk that fails half way leaves none of them advanced
-            try:
-                for i, s in enumerate(self._subs):
-                    gv = cond[0][..., i].contiguous() if cond is not None and cond[2][i] else None
-                    music.append(m.encoders[i].decode(s.generate(n, given=gv, temperature=temps[i]))[1].to(torch.uint8))
-            except BaseException:
+        temperature, cond = m._generate_arguments(n, given, given_mask, temperature)
+        snap = self.snapshot() if len(self._subs) > 1 else None      # several generators advance one after another: a chunk that fails half way leaves none of them advanced
+        try:
+            out = m._sample_generators([s.generate for s in self._subs], n, cond, temperature, session=True)
+        except BaseException:
+            if snap is not None:
                 self.restore(snap)
-                raise
-            out = torch.stack(music, dim=3)
-        else:
-            gv = None if cond is None else cond[0].reshape(cond[0].shape[0], n, -1)
-            h = self._subs[0].generate(n, given=gv, temperature=temperature)
-            if self._mode == "joint":
-                out = m._encoder.decode(h)[1].reshape(-1, n, P, M).to(torch.uint8)
-            else:
-                tracks = h.reshape(h.shape[0], n, m._num_dims_generator, M).unbind(-1)
-                out = torch.stack([m.encoders[i].decode(tracks[i].contiguous())[1].to(torch.uint8) for i in range(M)], dim=3)
+            raise
         self.steps += n
         return out

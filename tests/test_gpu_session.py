@@ -348,3 +348,62 @@ def test_jamming_track_given_whole_in_one_chunk_and_free_in_the_next(gen):
     got = torch.cat([c1, c2], 1)
     assert torch.equal(got, one), int((got != one).sum())
     assert torch.equal(got[:, :3, :, 0], given[:, :3, :, 0])
+
+
+# ------------------------------------------------------------------------------------------------
+# 7. the draw position is a value (common.DrawAt): a session sets nothing on its generator, and the generator's seed / row0 do not reach it
+def _position_case(kind):
+    """nade: a byte intro (the one-call chunks); nade_float: the same generator on a float intro (the step loop); rbm: the step loop, k = 4."""
+    if kind == "rbm":
+        B, Ti, D, steps = 10, 4, 24, 9
+        gen, _ = rbm_gen(D, 40, [64, 32], 4)
+        return gen, dev((np.random.default_rng(26).random((B, Ti, D)) < .3).astype(np.uint8)), steps, (4, 1, 4)
+    B, Ti, E, steps = 5, 4, 8, 6
+    gen, _ = nade_gen(1, E, 16, [32, 32])
+    x = dev((np.random.default_rng(6).random((B, Ti, E)) < .3).astype(np.uint8))
+    return gen, (x.float() if kind == "nade_float" else x), steps, (1, 2, 3)
+
+
+@pytest.mark.parametrize("graph", ["captured", "eager"])
+@pytest.mark.parametrize("kind", ["nade", "nade_float", "rbm"])
+def test_session_and_generator_are_independent(monkeypatch, kind, graph):
+    if graph == "eager":
+        monkeypatch.setenv("MULTINN_GENERATE_GRAPH", "0")
+    gen, x, steps, split = _position_case(kind)
+    one = gen.generate(x, steps)
+    sess = gen.session(x)
+    assert sess._scan == (kind == "nade")
+    mine = (gen.seed + 5, gen.row0 + 3)
+    gen.seed, gen.row0 = mine                                       # after the opening: the session keeps the opening's
+    other = gen.generate(x, steps)
+    assert not torch.equal(other, one)
+
+    def untouched():
+        return (gen.seed, gen.row0) == mine and not any(a.startswith("_gen_") for a in dir(gen))
+    out = []
+    for i, n in enumerate(split):
+        if i == 1:                                                  # a chunk that raises leaves the generator, and the session, as they were
+            with pytest.raises(ValueError, match="given"):
+                sess.generate(n, given=torch.zeros((1, n, 1), dtype=torch.uint8, device=DEV))
+            assert untouched() and sess.steps == sum(split[:1])
+        out.append(sess.generate(n))
+        assert untouched()
+    assert torch.equal(torch.cat(out, 1), one)                      # the opening seed / row0
+    assert torch.equal(gen.generate(x, steps), other)               # the generator's own, with a session in between
+    gen.seed, gen.row0 = mine[0] - 5, mine[1] - 3
+    assert torch.equal(gen.generate(x, steps), one)
+
+
+@pytest.mark.parametrize("kind", ["nade", "rbm"])
+def test_sample_single_at_a_position(kind):
+    from multinn_amd.common import DrawAt
+    gen, x, steps, _ = _position_case(kind)
+    one = gen.generate(x, steps)
+    out, state, last = gen._scan_steps(gen.steps(x), x[:, -1, :], 3, DrawAt(gen.seed, gen.row0, 0))
+    assert torch.equal(out, one[:, :3])
+    row, _ = gen.sample_single(last, state, at=DrawAt(gen.seed, gen.row0, 3))
+    assert torch.equal(row, one[:, 3])
+    seed, row0 = gen.seed, gen.row0
+    gen.seed, gen.row0 = seed + 1, row0 + 1                          # the position comes from `at` and from nothing else
+    assert torch.equal(gen.sample_single(last, state, at=DrawAt(seed, row0, 3))[0], row)
+    assert not torch.equal(gen.sample_single(last, state)[0], row)   # at=None: the generator's own seed and row0, step 0

@@ -295,7 +295,6 @@ def test_rnn_nade_generate_scalar(monkeypatch):
     assert np.array_equal(gen.generate(dev(intro), STEPS, temperature=None).cpu().numpy(), det.rnn_nade_generate(intro, STEPS, p, 31, temperature=None))
     # sample_single has the argument, and its nll is the model's own
     state = gen.steps(dev(intro))
-    gen._gen_step = 0
     s1, n1 = gen.sample_single(None, state, temperature=0.8)
     assert np.array_equal(s1.cpu().numpy(), ref[:, 0])
 
