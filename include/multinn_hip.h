@@ -414,6 +414,25 @@ int mnn_nade_sample_temps(mnn_stream_t s, int tracks, int N, int D, int Hn, cons
 int mnn_nade_sample_temps_at(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
                              const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
                              long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given, const uint32_t* sub_base);
+/* Polyphony caps of the NADE entry points that end in _caps / _caps_at (added without a version bump; the _temps entry points are wrappers that
+ * pass NULL): at most cap[.] ones per counter and row.  The scan of a row keeps one count per counter of the ones emitted so far, given ones as
+ * well as drawn ones; a FREE visible whose counter has reached its cap is a settled 0 -- not drawn, its uniform left unused, no state moved,
+ * its logit kept, so nll stays the model's own for the emitted vector -- and every visible that is drawn reads the uniform of the uncapped
+ * scan: a cap that no row reaches returns the uncapped bits.  A given cell always wins: a given 1 past the cap is emitted and counted.  The
+ * cap acts on threshold draws (temps n = 0) in the same way.  caps NULL or n = 0: no caps.  n = 1: cap[0] for every track / job.  n > 1 with
+ * by_visible = 0: counter = track (n = tracks) or job (n = njobs).  n > 1 with by_visible = 1: visible i of every track / job counts in
+ * cap[i % n] -- a NADE over visibles p * M + m with one cap per track m.  A negative entry is no cap.  A launch in which no counter can
+ * run out (every cap >= the visibles it counts) runs the kernels of the launch without caps.  The emitted ones are the FIRST cap[.] in
+ * visible order that the scan would have emitted: the constrained ancestral sampler, not a sample from p(v | count <= cap). */
+typedef struct {
+    int n;
+    int by_visible;
+    int32_t cap[MNN_TEMPS_MAX];
+} mnn_caps;
+int mnn_nade_sample_caps_at(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
+                            const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed, uint32_t row0, uint32_t sub,
+                            uint8_t* samples, long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given,
+                            const uint32_t* sub_base);
 /* mnn_nade_sample for SEVERAL single-NADE generators in ONE launch (multinn_feedback.py:196: every per-track generator's sample_single in a
  * step of the feedback scan).  `jobs`: HOST array of 1..8 descriptors (passed to the kernel by value): the generator's Dense output matrix
  * bias [N, ld_bias] (b_enc at column 0, b_dec at column Hn), its weights [D, Hn], its Philox seed and where its samples go
@@ -429,6 +448,9 @@ int mnn_nade_sample_multi(mnn_stream_t s, int njobs, const mnn_nade_sample_job* 
                           uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride);
 int mnn_nade_sample_multi_temps(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, const mnn_temps* temps,
                                 uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride);
+/* ... with polyphony caps (mnn_caps: one, or job j's own; NULL = mnn_nade_sample_multi_temps, which calls this) */
+int mnn_nade_sample_multi_caps(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, const mnn_temps* temps,
+                               const mnn_caps* caps, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride);
 
 /* ------------------------------------------------------------------------------------------
  * RBM (models/common/rbm.py).  W f32 [D,Hn]; bh f32 [N or 1, Hn] (ld_bh = 0 broadcasts one row);
@@ -719,6 +741,19 @@ int mnn_generate_scan_chunk(mnn_stream_t s, int B, int n_intro, int num_steps, c
                             const float* w_enc, const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint8_t* samples,
                             void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c_in, const float* const* h_in,
                             float* const* c_out, float* const* h_out, uint32_t step0, const uint32_t* step_base);
+/* mnn_generate_scan_temps and mnn_generate_scan_chunk with polyphony caps (mnn_caps, above: per track of a MultiNADE, or -- by_visible -- by
+ * visible index of the one NADE) on every sample call of the scan; caps NULL: the entry points above, which call these. */
+int mnn_generate_scan_caps(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                           const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D, int Hn,
+                           const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed, uint32_t row0,
+                           uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0,
+                           const float* const* h0);
+int mnn_generate_scan_chunk_caps(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                 const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
+                                 int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed,
+                                 uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given,
+                                 const float* const* c_in, const float* const* h_in, float* const* c_out, float* const* h_out, uint32_t step0,
+                                 const uint32_t* step_base);
 
 /* ------------------------------------------------------------------------------------------
  * Data-parallel exchange (the gradients of utils/training.py:151-177 as ONE flat f32 buffer): RCCL over xGMI, one

@@ -88,6 +88,11 @@ class Temps(C.Structure):
     _fields_ = [("n", _i), ("by_visible", _i), ("t", _f * 8)]
 
 
+class Caps(C.Structure):
+    """mnn_caps (include/multinn_hip.h)."""
+    _fields_ = [("n", _i), ("by_visible", _i), ("cap", C.c_int32 * 8)]
+
+
 class RbmGibbsJob(C.Structure):
     """mnn_rbm_gibbs_job (include/multinn_hip.h)."""
     _fields_ = [("W", _p), ("bh", _p), ("bv", _p), ("seed", _u64), ("v0", _p), ("p_v", _p), ("v_out", _p), ("given", _p)]
@@ -184,6 +189,18 @@ SIGNATURES["mnn_nade_sample_temps_at"] = (_i, SIGNATURES["mnn_nade_sample_temps"
 SIGNATURES["mnn_rbm_gibbs_at"] = (_i, SIGNATURES["mnn_rbm_gibbs_temp"][1] + [_p])
 SIGNATURES["mnn_rbm_gibbs_multi_at"] = (_i, SIGNATURES["mnn_rbm_gibbs_multi_temps"][1] + [_p])
 SIGNATURES["mnn_generate_scan_chunk"] = (_i, SIGNATURES["mnn_generate_scan_temps"][1] + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _u32, _p])
+# polyphony caps (additions without a version bump): the _temps entry points with a const mnn_caps* behind the temperature table
+
+
+def _with_caps(symbol, temps_at):
+    args = SIGNATURES[symbol][1]
+    return (_i, args[:temps_at + 1] + [_p] + args[temps_at + 1:])
+
+
+SIGNATURES["mnn_nade_sample_caps_at"] = _with_caps("mnn_nade_sample_temps_at", 9)
+SIGNATURES["mnn_nade_sample_multi_caps"] = _with_caps("mnn_nade_sample_multi_temps", 6)
+SIGNATURES["mnn_generate_scan_caps"] = _with_caps("mnn_generate_scan_temps", 16)
+SIGNATURES["mnn_generate_scan_chunk_caps"] = _with_caps("mnn_generate_scan_chunk", 16)
 TEMPS_MAX = 8              # MNN_TEMPS_MAX
 
 _lib = None

@@ -149,27 +149,29 @@ class ScanGraphs:
         return out.clone()
 
     @staticmethod
-    def generate(owner, key, x, num_steps, given, temperature, scan, stale):
+    def generate(owner, key, x, num_steps, given, temperature, scan, stale, max_notes=None):
         """The one capture wrapper of a `generate`: scan(x, num_steps, given, temperature) eagerly where graphs are off, else one replay of
         the scan captured under key + ("given",) + temperature_key (a new given of the same shape replays the same graph; the temperature
-        is baked into the captured launches, nothing at 1.0: the scan captured without it) from the cache kept on `owner`.  stale(): mark
+        is baked into the captured launches, nothing at 1.0: the scan captured without it) from the cache kept on `owner`.  max_notes (a
+        normalised polyphony cap; None: the call, the key and the captured scan without one): a fifth argument of scan, and max_notes_key.  stale(): mark
         the owner's packed weight copies stale -- before the capture (the graph packs them itself: a replay always sees the current
         weights) and after it (the packed copies then live in the graph's pool).  The warm-up is the scan's first min(num_steps, 2) steps."""
+        cap = () if max_notes is None else (max_notes,)
         if not ScanGraphs.enabled(x):
-            return scan(x, num_steps, given, temperature)
+            return scan(x, num_steps, given, temperature, *cap)
         if getattr(owner, "_scan_graphs", None) is None:
             owner._scan_graphs = ScanGraphs()
         if given is not None:
             key = key + ("given",)
-        key = key + temperature_key(temperature)
+        key = key + temperature_key(temperature) + max_notes_key(max_notes)
 
         def captured(sx, sg=None):
             stale()
-            return scan(sx, num_steps, sg, temperature)
+            return scan(sx, num_steps, sg, temperature, *cap)
 
         def warm(sx, sg=None):
             n = min(int(num_steps), 2)
-            return scan(sx, n, None if sg is None else sg[:, :n].contiguous(), temperature)
+            return scan(sx, n, None if sg is None else sg[:, :n].contiguous(), temperature, *cap)
 
         return owner._scan_graphs.run(key, x, captured, warm, stale, extra=given)
 
@@ -301,6 +303,51 @@ def sampling_temperature(temperature, num_tracks=None, allow_none=True, allow_se
 def temperature_key(temperature):
     """What a scan-graph key gains from a (normalised) temperature: nothing at 1.0 -- the key, and the captured scan, of a call without one."""
     return () if temperature == 1.0 else (("temperature", temperature),)
+
+
+# --------------------------------------------------------------------------------------------
+# Polyphony cap.  A NADE generator emits at most K ones per track and generated step: the scan counts the ones of a track, given ones as well
+# as drawn ones, and a free visible of a track that has reached its cap is a settled 0 (ops.nade_sample: `max_notes`).  K is one number or
+# one per track (None: that track has no cap).  An RBM generator has none: a Gibbs chain has no visible order in which to stop.
+def sampling_max_notes(max_notes, num_tracks=None, num_dims=None, collapse=True, what="max_notes"):
+    """The one normalisation of a `max_notes` argument, on the host, before any device work.  Returns None (no cap), an int >= 0, or a tuple
+    of num_tracks entries, each an int >= 0 or None.  Accepted: None; an integer >= 0; a sequence of num_tracks entries (at most
+    MAX_TEMPERATURE_TRACKS), each an integer >= 0 or None.  num_dims (the visibles of a track, where known): a cap >= num_dims can never be
+    reached and is None.  A sequence of equal entries IS the scalar (collapse=False: where a sequence counts by visible index inside ONE
+    NADE and a scalar counts the whole of it, the sequence stays), and all-None is None: the kernels, bits and captured scans of a call
+    without the argument.  Anything else -- a bool, a float, a negative number, a wrong length -- raises ValueError."""
+    import numbers
+    if max_notes is None:
+        return None
+
+    def one(k):
+        if k is None:
+            return None
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral) or k < 0:
+            raise ValueError(f"{what} must be an integer >= 0 (or None: no cap), got {k!r}")
+        return None if num_dims is not None and int(k) >= int(num_dims) else int(k)
+
+    if torch.is_tensor(max_notes):
+        max_notes = max_notes.detach().to("cpu").tolist()
+    if isinstance(max_notes, numbers.Real):
+        return one(max_notes)
+    try:
+        seq = list(max_notes)
+    except TypeError:
+        raise ValueError(f"{what} must be an integer >= 0, None, or a sequence of them, got {max_notes!r}") from None
+    if len(seq) > MAX_TEMPERATURE_TRACKS:
+        raise ValueError(f"{what}: at most {MAX_TEMPERATURE_TRACKS} tracks, got {len(seq)} values")
+    if num_tracks is None or len(seq) != int(num_tracks):
+        raise ValueError(f"{what}: a sequence needs one value per track ({num_tracks}), got {len(seq)}")
+    seq = tuple(one(k) for k in seq)
+    if all(k is None for k in seq):
+        return None
+    return seq[0] if collapse and all(k == seq[0] for k in seq) else seq
+
+
+def max_notes_key(max_notes):
+    """What a scan-graph key gains from a (normalised) cap: nothing at None -- the key, and the captured scan, of a call without one."""
+    return () if max_notes is None else (("max_notes", max_notes),)
 
 
 # --------------------------------------------------------------------------------------------

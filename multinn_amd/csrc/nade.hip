@@ -810,6 +810,39 @@ __device__ __forceinline__ void sample_temps_park(const SampleTemps& TT, int lan
     for (int k = 1; k < SAMPLE_MAX_JOBS; ++k) tv = (lane & (SAMPLE_MAX_JOBS - 1)) == k ? TT.t[k] : tv;
     if (lane < SAMPLE_MAX_JOBS) stt[lane] = tv;
 }
+// The polyphony caps of a launch (the CAP instantiations' LAST kernel argument: the other arguments stay where they were).  cap[k]: how many
+// ones counter k may still emit, SAMPLE_CAP_NONE for no cap.  by_visible == 0: job j (blockIdx.y) counts in cap[j];
+// by_visible == 1: visible i of every job counts in cap[i % n] (the joint NADE: one cap per track).
+struct SampleCaps { int cap[SAMPLE_MAX_JOBS]; int n; int by_visible; };
+#define SAMPLE_CAP_NONE 0x3fffffff
+// what a kernel takes as its last argument: the caps where it is a CAP instantiation, nothing (an empty argument: no bytes among the kernel's
+// arguments) where it is not
+struct SampleNoCaps {};
+template <bool CAP> struct SampleCapsArg { typedef SampleNoCaps T; };
+template <> struct SampleCapsArg<true> { typedef SampleCaps T; };
+// The counters of one scan: what each may still emit, and the set of the exhausted ones (bit k: rem[k] <= 0).  Wave-uniform, in registers:
+// every access is a chain over constant indices (a dynamically indexed array would go to scratch, and an LDS write inside the chunk loop waits
+// for every ring copy in flight).  A per-job launch counts in rem[0] alone (n = 1).
+struct CapCount { int rem[SAMPLE_MAX_JOBS]; int ex; int n; };
+__device__ __forceinline__ void sample_caps_init(const SampleCaps& CC, int job, CapCount& cc) {
+    int own = CC.cap[0];
+#pragma unroll
+    for (int k = 1; k < SAMPLE_MAX_JOBS; ++k) own = job == k ? CC.cap[k] : own;
+    cc.ex = 0;
+    cc.n = CC.by_visible ? CC.n : 1;
+#pragma unroll
+    for (int k = 0; k < SAMPLE_MAX_JOBS; ++k) {
+        cc.rem[k] = CC.by_visible ? CC.cap[k] : (k == 0 ? own : SAMPLE_CAP_NONE);
+        cc.ex |= cc.rem[k] <= 0 ? 1 << k : 0;
+    }
+}
+__device__ __forceinline__ void sample_caps_take(CapCount& cc, int t) {     // a one of counter t (wave-uniform), drawn or given
+#pragma unroll
+    for (int k = 0; k < SAMPLE_MAX_JOBS; ++k) {
+        cc.rem[k] -= t == k ? 1 : 0;
+        cc.ex |= (t == k && cc.rem[k] <= 0) ? 1 << k : 0;
+    }
+}
 
 // TMODE: 0 = threshold draws (temperature None / <= 0), 1 = temperature 1, 2 = any other temperature: the table TT, per job or per visible.
 // FULL: Hn == 256, no lane is idle.
@@ -818,10 +851,13 @@ __device__ __forceinline__ void sample_temps_park(const SampleTemps& TT, int lan
 // the emitted vector.
 // SUB_BASE: sub_base (NULL: none) points at one u32 on the device that is added to the launch's sub-counter -- the generated steps before a
 // session's chunk, so that a captured chunk replays at any position of the piece (mnn_nade_sample_temps_at).
-template <int TMODE, bool FULL, bool SPEC, bool GIVEN>
+// CAP (with GIVEN: a job without codes has every visible free): polyphony caps -- a free visible whose counter (SampleCaps) is exhausted is a
+// settled 0: not drawn, its uniform unused, its logit parked like any other; every one that is emitted, given or drawn, is counted.
+template <int TMODE, bool FULL, bool SPEC, bool GIVEN, bool CAP = false>
 __global__ void __launch_bounds__(256)
 nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t row0, uint32_t sub_arg, long s_row_stride, int s_elem_stride,
-                   const uint32_t* __restrict__ sub_base) {
+                   const uint32_t* __restrict__ sub_base, typename SampleCapsArg<CAP>::T CC) {
+    static_assert(GIVEN || !CAP, "the capped scan reads the codes");
     // per wave: logit / log term [Dp] f32, b_dec [Dp] f32, draws [Dp] u8, 256 uniforms (, GIVEN: the row's codes [Dp] u8) (, TMODE 2: 8 temperatures)
     extern __shared__ __attribute__((aligned(16))) unsigned char nade_sample_smem[];
     uint32_t sub = sub_arg;                                 // SUB_BASE: the Philox sub-counter; the base is added in front of the first refill
@@ -897,6 +933,10 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t 
         tix = TT.by_visible ? 0 : (int)blockIdx.y;
         t_cur = stt[tix];
     }
+    // CAP: the counter of visible i is cix = i % n, carried like tix
+    CapCount cc;
+    int cix = 0;
+    if constexpr (CAP) sample_caps_init(CC, (int)blockIdx.y, cc);
     auto dot = [&](int k) {                                 // sum_j h_j w_dec[visible of ring slot k][j], the contract's order
         float acc = 0.f;
 #pragma unroll
@@ -928,6 +968,8 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t 
                 bool on;
                 if (GIVEN && code != 255) {                 // clamped: the given value moves a / h like a draw (and the speculation holds as for one)
                     on = code != 0;
+                } else if (CAP && ((cc.ex >> cix) & 1) != 0) {     // capped: a settled 0, nothing is drawn (the speculation holds as for a drawn 0)
+                    on = false;
                 } else if (TMODE != 0) {
                     on = draw_below(u_cur, TMODE == 1 ? l : l / t_cur);
                 } else {
@@ -940,6 +982,7 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t 
                         h[q] = det_sigmoid(a[q]);
                     }
                     acc = dot((k + 1) % RING);
+                    if (CAP) sample_caps_take(cc, cix);
                 } else {
                     acc = SPEC ? spec : dot((k + 1) % RING);
                 }
@@ -950,6 +993,7 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t 
                     tix = tix + 1 == TT.n ? 0 : tix + 1;
                     t_cur = stt[tix];
                 }
+                if (CAP) cix = cix + 1 == cc.n ? 0 : cix + 1;
             }
             __builtin_amdgcn_sched_barrier(0);
             fetch(k, i + RING);
@@ -996,10 +1040,14 @@ extern "C" int mnn_sch_trace_read(long long* host) { return hipMemcpyFromSymbol(
 #endif
 // GIVEN: as nade_sample_kernel.  A clamped lane's `on` is its code; the tie ballot counts free lanes only, and the first 1 of a pass -- given or
 // drawn -- moves the state.
-template <int TMODE, bool FULL, int G, bool GIVEN>
+// CAP: as nade_sample_kernel.  At the top of a pass the free lanes whose counter is exhausted are forced to 0 and, like clamped lanes, kept out of
+// the tie ballot; the first 1 of the pass is counted before the re-evaluation behind it (the lanes behind it are discarded anyway, so the counts
+// taken at the top of the pass are exact for every lane that is kept).
+template <int TMODE, bool FULL, int G, bool GIVEN, bool CAP = false>
 __global__ void __launch_bounds__(64)
 nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t row0, uint32_t sub_arg, long s_row_stride, int s_elem_stride,
-                   const uint32_t* __restrict__ sub_base) {
+                   const uint32_t* __restrict__ sub_base, typename SampleCapsArg<CAP>::T CC) {
+    static_assert(GIVEN || !CAP, "the capped scan reads the codes");
     constexpr int NB = sch_nb(G);
     constexpr int KSH = G == 16 ? 2 : 3;                      // lane l decides visible l >> KSH of the chunk
     constexpr int WAITN = (NB - 2) * 2 * G;                   // copies that may still be in flight when a chunk is needed: the NB - 2 chunks behind it
@@ -1097,6 +1145,14 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
     if (TMODE == 2) {
         tix = TT.by_visible ? kq % TT.n : (int)blockIdx.y;
         tstep = TT.by_visible ? G % TT.n : 0;
+    }
+    // CAP: this lane's visible of chunk c counts in counter (c G + kq) % n, carried like tix; the counters themselves are wave-uniform registers
+    CapCount cc;
+    int cix = 0, cstep = 0;
+    if constexpr (CAP) {
+        sample_caps_init(CC, (int)blockIdx.y, cc);
+        cix = kq % cc.n;
+        cstep = G % cc.n;
     }
     // what a chunk's passes read besides h: its eight w_dec rows -- visibles (2 p, 2 p + 1) side by side, one packed FMA serves both --, the lane's
     // b_dec and uniform.  (Measured and dropped: fetching them one chunk AHEAD, under the previous chunk's passes -- 47.0 vs 46.5 us per call: a lone
@@ -1199,7 +1255,9 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
                     if (sfrom == 0) { asm volatile("" ::"v"(l)); SCH_TR(5, c); }
 #endif
                     const bool open = mine && kq >= sfrom;   // lanes whose visible is still undecided
-                    const bool drawn = !GIVEN || ci.code == 255;     // (a clamped lane takes its code below, whatever its comparison says)
+                    const bool free_ = !GIVEN || ci.code == 255;     // (a clamped lane takes its code below, whatever its comparison says)
+                    const bool capped = CAP && free_ && ((cc.ex >> cix) & 1) != 0;     // (and a capped one is 0)
+                    const bool drawn = free_ && !capped;
                     bool on;
                     if (TMODE != 0) {                        // u < det_sigmoid(l / T), settled by the hardware sigmoid unless within 1e-4 of a tie (draw_below)
                         const float xa = TMODE == 1 ? l : l / ci.t;
@@ -1214,7 +1272,8 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
                         if (__builtin_amdgcn_ballot_w64(tie && open && drawn) == 0ull) on = d > 0.f;
                         else on = det_sigmoid(l) >= 0.5f;
                     }
-                    if (GIVEN && !drawn) on = ci.code != 0;
+                    if (GIVEN && !free_) on = ci.code != 0;
+                    if (CAP && capped) on = false;
                     const uint64_t m = __builtin_amdgcn_ballot_w64(on && open) & (G == 16 ? 0x1111111111111111ull : 0x0101010101010101ull);
                     const int f = m != 0ull ? (int)(__builtin_ctzll(m) >> KSH) : G;     // the first draw of 1 (uniform)
 #ifdef SCH_TRACE
@@ -1225,6 +1284,7 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
                         son[iv] = kq == f ? 1 : 0;
                     }
                     if (f >= G) break;
+                    if (CAP) sample_caps_take(cc, __builtin_amdgcn_readlane(cix, f << KSH));     // the first 1's counter (lane f << KSH decides visible f)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const float x2 = re[f * 256 + off[q]];
@@ -1236,6 +1296,10 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
                 }
                 SCH_TR(2, c);
                 SCH_TR(3, c);
+                if (CAP) {                                   // the next chunk's counter index
+                    cix += cstep;
+                    if (cix >= cc.n) cix -= cc.n;
+                }
             }
         }
     }
@@ -1258,9 +1322,9 @@ static hipError_t sample_chunk_raise_lds() {                 // the ring + a row
     static MnnPerDeviceOnce raised;
     return mnn_once_per_device(raised, [] {
         hipError_t e = hipSuccess;
-#define RAISE1(TM, FU, GV) if (e == hipSuccess) e = mnn_raise_dynamic_lds(reinterpret_cast<const void*>(&nade_sample_chunk_kernel<TM, FU, 8, GV>), 128 * 1024); \
-                           if (e == hipSuccess) e = mnn_raise_dynamic_lds(reinterpret_cast<const void*>(&nade_sample_chunk_kernel<TM, FU, 16, GV>), 128 * 1024)
-#define RAISE(TM, FU) RAISE1(TM, FU, false); RAISE1(TM, FU, true)
+#define RAISE1(TM, FU, GV, CP) if (e == hipSuccess) e = mnn_raise_dynamic_lds(reinterpret_cast<const void*>(&nade_sample_chunk_kernel<TM, FU, 8, GV, CP>), 128 * 1024); \
+                               if (e == hipSuccess) e = mnn_raise_dynamic_lds(reinterpret_cast<const void*>(&nade_sample_chunk_kernel<TM, FU, 16, GV, CP>), 128 * 1024)
+#define RAISE(TM, FU) RAISE1(TM, FU, false, false); RAISE1(TM, FU, true, false); RAISE1(TM, FU, true, true)
         RAISE(0, true); RAISE(1, true); RAISE(2, true); RAISE(0, false); RAISE(1, false); RAISE(2, false);
 #undef RAISE
 #undef RAISE1
@@ -1270,9 +1334,12 @@ static hipError_t sample_chunk_raise_lds() {                 // the ring + a row
 
 // GV: some job carries codes (SampleJob.given) -- the GIVEN instantiations; without any, the launch is the unconditioned one
 // tmode / TT: launch_sample's reading of the caller's mnn_temps (TT is read by the TMODE 2 instantiations only)
-template <bool GV>
-static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, int tmode, const SampleTemps& TT, uint32_t row0, uint32_t sub,
-                           long s_row_stride, int s_elem_stride, const uint32_t* sub_base) {
+// CP: some counter of the launch can run out (launch_sample) -- the CAP instantiations, which are GIVEN ones; CC is read by them only
+template <bool GV, bool CP>
+static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, int tmode, const SampleTemps& TT, const SampleCaps& caps,
+                           uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride, const uint32_t* sub_base) {
+    typename SampleCapsArg<CP>::T CC;                        // the kernels' last argument: the caps, or nothing
+    if constexpr (CP) CC = caps;
     bool chunked = Hn % 4 == 0 && Hn >= 4 && !mnn_switch_set(MNN_SW_SAMPLE_NO_CHUNK);      // (tests compare the two forms)
     for (int j = 0; j < njobs && chunked; ++j) chunked = (((uintptr_t)J.job[j].w_enc | (uintptr_t)J.job[j].w_dec) & 15) == 0;
     const size_t gbytes = GV ? (size_t)((D + 3) & ~3) : 0;   // the row's codes
@@ -1282,8 +1349,8 @@ static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N
         const int g = (long)N * njobs <= 256 && !mnn_switch_set(MNN_SW_SAMPLE_G8) ? 16 : 8;
         const size_t ldc = (size_t)sch_nb(g) * 2 * g * 1024 + (size_t)9 * ((D + 3) & ~3) + 1024 + gbytes + tbytes;     // <= 96 KB + 15 KB + 1 KB (D <= 1536)
         MNN_HIP(sample_chunk_raise_lds());
-#define SMC(TM, FU) do { if (g == 16) hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 16, GV>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base); \
-                         else hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 8, GV>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base); } while (0)
+#define SMC(TM, FU) do { if (g == 16) hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 16, GV, CP>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base, CC); \
+                         else hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 8, GV, CP>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base, CC); } while (0)
         if (Hn == 256) { if (tmode == 0) SMC(0, true); else if (tmode == 1) SMC(1, true); else SMC(2, true); }
         else { if (tmode == 0) SMC(0, false); else if (tmode == 1) SMC(1, false); else SMC(2, false); }
 #undef SMC
@@ -1292,7 +1359,7 @@ static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N
     }
     dim3 grid(cdiv(N, 4), njobs);
     const size_t lds = (size_t)36 * ((D + 3) & ~3) + 4096 + 4 * gbytes + tbytes;     // 4 waves x ((2 f32 + u8 (+ u8 code)) per visible + 256 uniforms): <= 64 KB
-#define SMP(TM, FU, SP) hipLaunchKernelGGL((nade_sample_kernel<TM, FU, SP, GV>), grid, dim3(256), lds, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base)
+#define SMP(TM, FU, SP) hipLaunchKernelGGL((nade_sample_kernel<TM, FU, SP, GV, CP>), grid, dim3(256), lds, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base, CC)
     if (Hn == 256 && tmode == 1) { if (mnn_switch_set(MNN_SW_SAMPLE_NO_SPEC)) SMP(1, true, false); else SMP(1, true, true); }
     else if (Hn == 256) { if (tmode == 0) SMP(0, true, false); else SMP(2, true, false); }
     else { if (tmode == 0) SMP(0, false, false); else if (tmode == 1) SMP(1, false, false); else SMP(2, false, false); }
@@ -1304,8 +1371,10 @@ static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N
 // temps (validated by sample_temps_ok): n == 0 -> threshold draws; every temperature this launch uses equal to 1 -> the TMODE 1 kernels, the
 // ones a launch without temperatures always ran; anything else -> TMODE 2 with the table.  track0: the first job's index into a per-job table
 // (mnn_nade_sample walks a MultiNADE's tracks eight at a time).
-static int launch_sample(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, const mnn_temps& temps, int track0, uint32_t row0,
-                         uint32_t sub, long s_row_stride, int s_elem_stride, const uint32_t* sub_base = nullptr) {
+// caps (NULL, or validated by sample_caps_ok): read like temps -- one cap, one per job from track0 on, or by visible index; negative: none.  A
+// launch in which no counter can run out (no cap below the visibles it counts) is the launch without caps: the kernels that never read CC.
+static int launch_sample(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, const mnn_temps& temps, const mnn_caps* caps, int track0,
+                         uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride, const uint32_t* sub_base = nullptr) {
     bool given = false;
     for (int j = 0; j < njobs; ++j) given = given || J.job[j].given != nullptr;
     SampleTemps TT;
@@ -1323,8 +1392,26 @@ static int launch_sample(hipStream_t st, const SampleJobs& J, int njobs, int N, 
             for (int j = 0; j < njobs; ++j) if (TT.t[j] != 1.0f) tmode = 2;
         }
     }
-    return given ? launch_sample_t<true>(st, J, njobs, N, D, Hn, tmode, TT, row0, sub, s_row_stride, s_elem_stride, sub_base)
-                 : launch_sample_t<false>(st, J, njobs, N, D, Hn, tmode, TT, row0, sub, s_row_stride, s_elem_stride, sub_base);
+    SampleCaps CC;
+    memset(&CC, 0, sizeof(CC));
+    bool capped = false;
+    if (caps != nullptr && caps->n > 0) {
+        auto entry = [&](int e) { return e < caps->n && caps->cap[e] >= 0 ? (int)caps->cap[e] : SAMPLE_CAP_NONE; };
+        if (caps->by_visible && caps->n > 1) {
+            CC.n = caps->n; CC.by_visible = 1;
+            for (int e = 0; e < SAMPLE_MAX_JOBS; ++e) {
+                CC.cap[e] = entry(e);
+                capped = capped || (e < caps->n && CC.cap[e] < (D - e + caps->n - 1) / caps->n);     // (the visibles e, e + n, ... below D)
+            }
+        } else {
+            CC.n = SAMPLE_MAX_JOBS; CC.by_visible = 0;
+            for (int j = 0; j < SAMPLE_MAX_JOBS; ++j) CC.cap[j] = caps->n == 1 ? entry(0) : entry(track0 + j);
+            for (int j = 0; j < njobs; ++j) capped = capped || CC.cap[j] < D;
+        }
+    }
+    if (capped) return launch_sample_t<true, true>(st, J, njobs, N, D, Hn, tmode, TT, CC, row0, sub, s_row_stride, s_elem_stride, sub_base);
+    return given ? launch_sample_t<true, false>(st, J, njobs, N, D, Hn, tmode, TT, CC, row0, sub, s_row_stride, s_elem_stride, sub_base)
+                 : launch_sample_t<false, false>(st, J, njobs, N, D, Hn, tmode, TT, CC, row0, sub, s_row_stride, s_elem_stride, sub_base);
 }
 
 // n == 0 (threshold draws), or 1..8 positive finite temperatures; a per-job table (by_visible == 0) has one entry or one per job
@@ -1333,6 +1420,12 @@ static bool sample_temps_ok(const mnn_temps* t, int njobs) {
     for (int e = 0; e < t->n; ++e) if (!(t->t[e] > 0.f) || !(t->t[e] <= 3.0e38f)) return false;
     return t->n <= 1 || t->by_visible != 0 || t->n == njobs;
 }
+// NULL or n == 0 (no caps), or 1..8 entries (negative: no cap for that one); a per-job table (by_visible == 0) has one entry or one per job
+static bool sample_caps_ok(const mnn_caps* c, int njobs) {
+    if (c == nullptr) return true;
+    if (c->n < 0 || c->n > MNN_TEMPS_MAX) return false;
+    return c->n <= 1 || c->by_visible != 0 || c->n == njobs;
+}
 static mnn_temps temps_of_scalar(float temperature) {        // the float of the entry points without a table: <= 0 is the threshold mode
     mnn_temps t;
     memset(&t, 0, sizeof(t));
@@ -1340,16 +1433,18 @@ static mnn_temps temps_of_scalar(float temperature) {        // the float of the
     return t;
 }
 
-// mnn_nade_sample_temps with a sub-counter base read on the device: sub_base NULL (none), or one u32 -- the draws use sub + *sub_base
-extern "C" int mnn_nade_sample_temps_at(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
-                                        const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
-                                        long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given,
-                                        const uint32_t* sub_base) {
+// mnn_nade_sample_temps with a sub-counter base read on the device: sub_base NULL (none), or one u32 -- the draws use sub + *sub_base -- and
+// with polyphony caps: caps NULL (none), or at most caps->cap[.] ones per track and row (launch_sample)
+extern "C" int mnn_nade_sample_caps_at(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
+                                       const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed, uint32_t row0, uint32_t sub,
+                                       uint8_t* samples, long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given,
+                                       const uint32_t* sub_base) {
     MNN_REQUIRE(tracks > 0 && N > 0 && D > 0 && Hn > 0 && Hn <= 256, "mnn_nade_sample: need tracks,N,D>0 and 0<Hn<=256 (Hn=%d)", Hn);
     MNN_REQUIRE(bias && w_enc && w_dec && samples, "mnn_nade_sample: null pointer");
     MNN_REQUIRE(ld_bias >= tracks * (Hn + D), "mnn_nade_sample: ld_bias too small");
     MNN_REQUIRE(D <= 1536, "mnn_nade_sample: D <= 1536 (logits, b_dec and draws of a row are parked in LDS, 36 B per visible and wave; D=%d)", D);
     MNN_REQUIRE(sample_temps_ok(temps, tracks), "mnn_nade_sample: temps: 0..%d positive finite temperatures, per track one or `tracks` of them", MNN_TEMPS_MAX);
+    MNN_REQUIRE(sample_caps_ok(caps, tracks), "mnn_nade_sample: caps: 0..%d entries, per track one or `tracks` of them", MNN_TEMPS_MAX);
     for (int m0 = 0; m0 < tracks; m0 += SAMPLE_MAX_JOBS) {            // the tracks of a MultiNADE: up to eight per launch
         SampleJobs J;
         memset(&J, 0, sizeof(J));
@@ -1360,10 +1455,18 @@ extern "C" int mnn_nade_sample_temps_at(mnn_stream_t s, int tracks, int N, int D
                                  (uint32_t)(m * D), samples + (size_t)m * s_track_stride, nll ? nll + (size_t)m * N : nullptr,
                                  given ? given + (size_t)m * s_track_stride : nullptr};
         }
-        const int rc = launch_sample((hipStream_t)s, J, nj, N, D, Hn, *temps, m0, row0, sub, s_row_stride, s_elem_stride, sub_base);
+        const int rc = launch_sample((hipStream_t)s, J, nj, N, D, Hn, *temps, caps, m0, row0, sub, s_row_stride, s_elem_stride, sub_base);
         if (rc != MNN_OK) return rc;
     }
     return MNN_OK;
+}
+
+extern "C" int mnn_nade_sample_temps_at(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
+                                        const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
+                                        long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given,
+                                        const uint32_t* sub_base) {
+    return mnn_nade_sample_caps_at(s, tracks, N, D, Hn, bias, ld_bias, w_enc, w_dec, temps, nullptr, seed, row0, sub, samples, s_track_stride,
+                                   s_row_stride, s_elem_stride, nll, given, sub_base);
 }
 
 extern "C" int mnn_nade_sample_temps(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
@@ -1383,12 +1486,14 @@ extern "C" int mnn_nade_sample(mnn_stream_t s, int tracks, int N, int D, int Hn,
 
 // The same scan for SEVERAL single-NADE generators in one launch (the M per-track generators of a feedback-scan step,
 // multinn_feedback.py:196: `generators[i].sample_single` for every track): job j has its own Dense output matrix, weights, seed and output
-// pointer -- and, with a table of njobs entries, its own temperature; rows, widths, the RNG row / sub counters and the output strides are shared.
-extern "C" int mnn_nade_sample_multi_temps(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, const mnn_temps* temps,
-                                           uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
+// pointer -- and, with a table of njobs entries, its own temperature and its own cap; rows, widths, the RNG row / sub counters and the output
+// strides are shared.
+extern "C" int mnn_nade_sample_multi_caps(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, const mnn_temps* temps,
+                                          const mnn_caps* caps, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
     MNN_REQUIRE(njobs > 0 && njobs <= SAMPLE_MAX_JOBS && jobs && N > 0 && D > 0 && Hn > 0 && Hn <= 256 && D <= 1536,
                 "mnn_nade_sample_multi: 1..%d jobs, N, D > 0, 0 < Hn <= 256, D <= 1536", SAMPLE_MAX_JOBS);
     MNN_REQUIRE(sample_temps_ok(temps, njobs), "mnn_nade_sample_multi: temps: 0..%d positive finite temperatures, per job one or `njobs` of them", MNN_TEMPS_MAX);
+    MNN_REQUIRE(sample_caps_ok(caps, njobs), "mnn_nade_sample_multi: caps: 0..%d entries, per job one or `njobs` of them", MNN_TEMPS_MAX);
     SampleJobs J;
     memset(&J, 0, sizeof(J));
     for (int j = 0; j < njobs; ++j) {
@@ -1396,7 +1501,12 @@ extern "C" int mnn_nade_sample_multi_temps(mnn_stream_t s, int njobs, const mnn_
         MNN_REQUIRE(q.bias && q.w_enc && q.w_dec && q.samples && q.ld_bias >= Hn + D, "mnn_nade_sample_multi: job %d: null pointer or ld_bias < Hn + D", j);
         J.job[j] = SampleJob{q.bias, q.ld_bias, 0, Hn, q.w_enc, q.w_dec, q.seed, 0u, q.samples, q.nll, q.given};
     }
-    return launch_sample((hipStream_t)s, J, njobs, N, D, Hn, *temps, 0, row0, sub, s_row_stride, s_elem_stride);
+    return launch_sample((hipStream_t)s, J, njobs, N, D, Hn, *temps, caps, 0, row0, sub, s_row_stride, s_elem_stride);
+}
+
+extern "C" int mnn_nade_sample_multi_temps(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, const mnn_temps* temps,
+                                           uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
+    return mnn_nade_sample_multi_caps(s, njobs, jobs, N, D, Hn, temps, nullptr, row0, sub, s_row_stride, s_elem_stride);
 }
 
 extern "C" int mnn_nade_sample_multi(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, float temperature,

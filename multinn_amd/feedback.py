@@ -1,12 +1,14 @@
 """Feedback-RNN sampling scan: multinn_feedback.py:120-218 with the recurrent feedback
 module of multinn_feedback_rnn.py:41-79.  Composition of the per-track RnnNade generators and one more
 LSTM stack, all running through the same C-ABI kernels."""
+import functools
 import weakref
 
 import torch
 
 from . import ops
 from .common import Model, RNN, ParamStore, DrawAt, check_given
+from ._lib import MnnUnsupported
 from .generators import LstmStack, RnnEstimator, RnnNade, _compute_dtype, det_steps
 
 
@@ -202,11 +204,24 @@ class FeedbackRnnSampler:
         from .common import sampling_temperature
         return sampling_temperature(temperature, self.num_tracks, allow_none=all(isinstance(g, RnnNade) for g in self.generators))
 
-    def generate(self, x_u8, num_steps, given=None, temperature=1.0):
+    def _max_notes(self, max_notes, num_dims=None):
+        """One cap or one per generator (common.sampling_max_notes; num_dims: the visibles of a track); MnnUnsupported unless every generator
+        is a NADE -- a Gibbs chain has no visible order in which to stop."""
+        from .common import sampling_max_notes
+        if max_notes is None:
+            return None
+        max_notes = sampling_max_notes(max_notes, self.num_tracks, num_dims)
+        if not all(isinstance(g, RnnNade) for g in self.generators):
+            raise MnnUnsupported("max_notes exists for NADE generators only: a Gibbs chain has no visible order in which a track's count could stop it")
+        return max_notes
+
+    def generate(self, x_u8, num_steps, given=None, temperature=1.0, max_notes=None):
         """x_u8 [B,Ti,P,M] intro piano-rolls -> samples u8 [B,num_steps,P,M].  One hipGraph replay per call on the
         device (common.ScanGraphs): the M generators and the feedback module step inside the same captured scan.
         given (optional): codes u8 [B, num_steps, P, M] (common.given_codes), see generate_encoded.
-        temperature: one for all generators or generator m's own, temperature[m]; 1.0 is the call (and the captured scan) without it."""
+        temperature: one for all generators or generator m's own, temperature[m]; 1.0 is the call (and the captured scan) without it.
+        max_notes: None, one cap (an integer >= 0) for all generators or generator m's own, max_notes[m] (None: no cap); None is the call
+        (and the captured scan) without it."""
         from .common import ScanGraphs
 
         def stale():
@@ -215,7 +230,7 @@ class FeedbackRnnSampler:
             if hasattr(self.feedback, "_packed_step"):
                 self.feedback._packed_step = -1
         return ScanGraphs.generate(self, (tuple(x_u8.shape), int(num_steps), tuple((g.seed, g.row0) for g in self.generators)), x_u8, num_steps,
-                                   given, self._temperature(temperature), self._generate_scan, stale)
+                                   given, self._temperature(temperature), self._generate_scan, stale, self._max_notes(max_notes, x_u8.shape[2]))
 
     def _group_dense(self, hs, rnn_states):
         """The M generators' Dense layers on their top outputs in one launch -> their RnnEstimatorStateTuples."""
@@ -223,21 +238,24 @@ class FeedbackRnnSampler:
         ops.dense_det(list(jobs))
         return [g._state_from_dense(o, tuple(st)) for g, o, st in zip(self.generators, outs, rnn_states)]
 
-    def _generate_scan(self, x_u8, num_steps, given=None, temperature=1.0):
+    def _generate_scan(self, x_u8, num_steps, given=None, temperature=1.0, max_notes=None):
         B, Ti, P, M = x_u8.shape
         assert M == self.num_tracks
         enc = torch.cat([torch.zeros((B, 1, P, M), device=x_u8.device, dtype=torch.uint8), x_u8], 1)      # multi_encoder_nn.py:73-76
-        return self.generate_encoded([enc[..., i] for i in range(M)], num_steps, given, temperature)
+        return self.generate_encoded([enc[..., i] for i in range(M)], num_steps, given, temperature, max_notes)
 
-    def generate_encoded(self, enc_tracks, num_steps, given=None, temperature=1.0):
+    def generate_encoded(self, enc_tracks, num_steps, given=None, temperature=1.0, max_notes=None):
         """The scan on per-track ENCODED inputs (multinn_feedback.py:120-173 between the encoders): enc_tracks = M x u8
         [B, Ti+1, E] (zero first step included) -> sampled codes u8 [B, num_steps, E, M]; the caller decodes them through
         its encoders (identity for PassEncoder).  given (optional): codes u8 [B, num_steps, E, M] (common.given_codes).  NADE
         generators clamp inside their sampling kernels; an RBM generator's track is pasted over its sample before the feedback step
         (whole tracks only: the mode classes refuse partial masks on RBM generators).  temperature: as generate; it acts on the generators'
-        samples of the codes."""
+        samples of the codes; max_notes: as generate, at most that many ones per track of a
+        step."""
         M = self.num_tracks
         temperature = self._temperature(temperature)
+        max_notes = self._max_notes(max_notes, enc_tracks[0].shape[-1])
+        caps = list(max_notes) if isinstance(max_notes, tuple) else [max_notes] * M               # generator i emits at most caps[i] ones per step
         temps = list(temperature) if isinstance(temperature, tuple) else [temperature] * M          # generator i samples at temps[i]
         enc_tracks = [e.contiguous() for e in enc_tracks]            # (views of a [B, T, P, M] roll have inner stride M)
         B, _, P = enc_tracks[0].shape
@@ -284,7 +302,7 @@ class FeedbackRnnSampler:
                 views = [out[:, s, :, i] for i in range(M)]                                          # u8 [B, P] views of track i (element stride M)
                 ops.nade_sample_multi([dict(bias=states[i].dense, w_enc=g.store["nade/w_enc"][0], w_dec=g.store["nade/w_dec"][0], seed=g.seed,
                                             samples=views[i], given=None if given is None else given[:, s, :, i])
-                                       for i, g in enumerate(gs)], P, Hn, temperature, gs[0].row0, s)
+                                       for i, g in enumerate(gs)], P, Hn, temperature, gs[0].row0, s, max_notes=max_notes)
                 st = out[:, s].reshape(B, P * M)                                                     # [B, P*M] view, feature p*M+m
                 fb, fb_state = self.feedback.single(st if fb_strided else st.contiguous(), fb_state)
                 res = det_steps([g._stack for g in gs], views, [list(s_.rnn_state) for s_ in states], [fb] * M)
@@ -309,8 +327,9 @@ class FeedbackRnnSampler:
                     with on(i):
                         gi = None if given is None else given[:, s, :, i]
                         clamp = gi is not None and isinstance(g, RnnNade)
-                        smp, _ = g.sample_single(None, states[i], given=gi.contiguous() if clamp else None, temperature=temps[i],
-                                                 at=DrawAt(g.seed, g.row0, s))
+                        sample = g.sample_single if caps[i] is None else functools.partial(g.sample_single_capped, max_notes=caps[i])
+                        smp, _ = sample(None, states[i], given=gi.contiguous() if clamp else None, temperature=temps[i],
+                                        at=DrawAt(g.seed, g.row0, s))
                         if gi is not None and not clamp:    # a wholly given track pasted over the RBM's sample
                             smp = torch.where(gi != 255, gi, smp)
                     samples.append(smp)

@@ -12,7 +12,9 @@ rows past ``lengths`` are masked by a zero row weight instead of being gathered 
 import abc
 import collections
 import contextlib
+import functools
 import math
+import numbers
 
 import weakref
 
@@ -20,7 +22,7 @@ import torch
 
 from . import ops
 from .switches import flag, value
-from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, DrawAt, check_given, given_codes, given_mask_tracks, sampling_temperature, glorot_uniform, zeros_init, default_device, capture_train_step
+from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, DrawAt, check_given, given_codes, given_mask_tracks, sampling_temperature, sampling_max_notes, glorot_uniform, zeros_init, default_device, capture_train_step
 from .training import compute_gradients, world, dp_active, AdamOptimizer
 from ._lib import MnnUnsupported
 from .lstm_stack import LstmStack, _SINGLE, drive, drive_group, _det_f32, det_steps
@@ -206,7 +208,7 @@ class Generator(Model):
         return self._outputs
 
     @abc.abstractmethod
-    def generate(self, x, num_steps, given=None, temperature=1.0):
+    def generate(self, x, num_steps, given=None, temperature=1.0, max_notes=None):
         ...
 
     def pretrain(self, optimizer, lr, run_optimizer=True):
@@ -374,7 +376,15 @@ class RnnEstimator(Generator):
         MultiNADE, or by visible index for the one NADE of joint mode), RBM estimators a positive number (per track: RnnMultiRBM)."""
         raise NotImplementedError
 
-    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0):
+    def _max_notes(self, max_notes):
+        """generate's `max_notes`, normalised on the host (common.sampling_max_notes) before any device work.  Here: the refusal of the
+        estimators that have no cap (RBM: a Gibbs chain has no visible order in which to stop); the NADE estimators override it."""
+        if max_notes is not None:
+            raise MnnUnsupported(f"max_notes exists for NADE generators only: the Gibbs chain of {type(self).__name__} updates all visibles of a "
+                                 "step at once and has no visible order in which a track's count could stop it")
+        return None
+
+    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0, max_notes=None):
         return None                         # estimators without a one-call scan (RnnRBM) step through sample_single / single_step
 
     # -- generation sessions (session.py) --------------------------------------------------------
@@ -498,8 +508,11 @@ class RnnEstimator(Generator):
         return buf
 
     # -- sampling -------------------------------------------------------------------------------
-    def generate(self, x, num_steps, given=None, temperature=1.0):
+    def generate(self, x, num_steps, given=None, temperature=1.0, max_notes=None):
         """rnn_estimator.py:271-298: intro pass, then num_steps x {sample_single, single_step}.
+        max_notes (NADE estimators; common.sampling_max_notes): at most K ones per track and generated step -- an integer >= 0, or one per
+        track (None: no cap for that track); the scan counts a track's ones, given ones included, and a free visible of a track that has
+        reached its cap is a settled 0.  None is the call without it: the same kernels, bits and captured scan.
         temperature: a positive float, one per track where the estimator has tracks, or (NADE estimators) None for threshold decoding --
         common.sampling_temperature.  1.0 is the call without it: the same kernels, bits and captured scan.
         x [B,Ti,Din]; returns samples u8 [B,num_steps,num_output].  On the device the whole scan is ONE hipGraph
@@ -509,34 +522,39 @@ class RnnEstimator(Generator):
         if given is not None:
             check_given(given, x.shape[0], num_steps, self._num_output)
             given = given.contiguous()
+        max_notes = self._max_notes(max_notes)
+        if max_notes is not None:
+            refuse_host_model(self.store.device, "generate(max_notes=)")
 
         def stale():
             self._packed_step = -1
         return ScanGraphs.generate(self, (tuple(x.shape), x.dtype, int(num_steps), self.seed, self.row0), x, num_steps, given,
-                                   self._temperature(temperature), self._generate_scan, stale)
+                                   self._temperature(temperature), self._generate_scan, stale, max_notes)
 
-    def _generate_scan(self, x, num_steps, given=None, temperature=1.0):
+    def _generate_scan(self, x, num_steps, given=None, temperature=1.0, max_notes=None):
         self._materialize(x.shape[-1])
         self._rnn.build_cell(False)
         with self._sampling_scope():
             if self.det_sampling:
-                whole = self._scan_in_one_call(x, num_steps, given, temperature)     # LSTM-(Multi)NADE on a byte piano-roll: mnn_generate_scan runs the whole scan
+                whole = self._scan_in_one_call(x, num_steps, given, temperature, max_notes)     # LSTM-(Multi)NADE on a byte piano-roll: mnn_generate_scan runs the whole scan
                 if whole is not None:
                     return whole
                 state = self.steps(x)
             else:
                 self._ensure_packed()
                 state = self._get_state(x, lengths=None, last_outputs=True)
-            return self._scan_steps(state, x[:, -1, :], num_steps, DrawAt(self.seed, self.row0, 0), given, temperature)[0]
+            return self._scan_steps(state, x[:, -1, :], num_steps, DrawAt(self.seed, self.row0, 0), given, temperature, max_notes)[0]
 
-    def _scan_steps(self, state, last_row, n, at0, given=None, temperature=1.0):
+    def _scan_steps(self, state, last_row, n, at0, given=None, temperature=1.0, max_notes=None):
         """The step loop of a single generator (rnn_estimator.py:283-298): n x {sample_single, single_step} from `state` and the last emitted
         row, step j drawing at at0's position moved on by j steps under given[:, j] -> (samples u8 [B, n, num_output], state, last row).
-        generate runs it from step 0, a session's chunk from where the piece stands."""
+        generate runs it from step 0, a session's chunk from where the piece stands.  max_notes (normalised; None: the call without it)
+        makes every step a sample_single_capped, which the estimators that have caps define."""
         out = []
+        sample = self.sample_single if max_notes is None else functools.partial(self.sample_single_capped, max_notes=max_notes)
         for j in range(n):
-            last_row, _ = self.sample_single(last_row, state, given=None if given is None else given[:, j], temperature=temperature,
-                                             at=at0._replace(step=at0.step + j))
+            last_row, _ = sample(last_row, state, given=None if given is None else given[:, j], temperature=temperature,
+                                 at=at0._replace(step=at0.step + j))
             state = self.single_step(last_row, state)
             out.append(last_row)
         return torch.stack(out, 1), state, last_row
@@ -1042,13 +1060,26 @@ class RnnNade(RnnEstimator):
             n = len(temperature)
         return sampling_temperature(temperature, n, what="temperature (one NADE: a sequence whose length divides its visibles)")
 
-    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0):
+    def _max_notes(self, max_notes):
+        if self.num_tracks > 1:                        # a MultiNADE: track m's NADE emits at most max_notes[m] ones
+            return sampling_max_notes(max_notes, self.num_tracks, self.num_dims)
+        # one NADE: an integer caps the whole vector; a sequence of n entries (n divides the visibles) caps the visibles i with i % n == m at
+        # entry m -- the tracks of joint mode, as _temperature's sequence (equal entries are NOT the integer here: they count apart)
+        if max_notes is None or isinstance(max_notes, numbers.Real):
+            return sampling_max_notes(max_notes, None, self.num_dims)
+        n = None
+        if hasattr(max_notes, "__len__") and len(max_notes) > 0 and self.num_dims % len(max_notes) == 0:
+            n = len(max_notes)
+        return sampling_max_notes(max_notes, n, None if n is None else self.num_dims // n, collapse=n == 1,
+                                  what="max_notes (one NADE: a sequence whose length divides its visibles)")
+
+    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0, max_notes=None):
         """rnn_estimator.py:271-298 through ONE C-ABI call (mnn_generate_scan: intro pass + num_steps x {NADE sample, LSTM step, Dense} enqueued
         by the library's own host loop) when the inputs are the byte piano-roll itself; the same kernels and bits as the step-by-step path.
         given: the scan's codes u8 [B, num_steps, num_output] (generate)."""
         if x.dtype != torch.uint8 or x.shape[-1] != self.num_tracks * self.num_dims or int(num_steps) < 1:
             return None
-        return ops.generate_scan(x.contiguous(), num_steps, temperature=temperature, seed=self.seed, row0=self.row0, given=given,
+        return ops.generate_scan(x.contiguous(), num_steps, temperature=temperature, seed=self.seed, row0=self.row0, given=given, max_notes=max_notes,
                                  state0=self._state0(x.shape[0], torch.float32), **self._scan_layers())      # (learn_zero_state: tiled on the device here, an input array of the scan)
 
     def _state_of(self, out, rnn_state):
@@ -1101,6 +1132,12 @@ class RnnNade(RnnEstimator):
         temperature: a float, None (threshold draws), or a sequence -- per track of a MultiNADE, by visible index modulo its length for
         the one NADE; the returned nll stays the model's own.  at (common.DrawAt; None: this generator's seed and row0, step 0): where
         the draws stand.  The biases are the state's Dense block (state.dense: every state a step or an intro pass returns has one)."""
+        return self.sample_single_capped(inputs, state, given=given, temperature=temperature, at=at)
+
+    def sample_single_capped(self, inputs, state, *, given=None, temperature=1.0, at=None, max_notes=None):
+        """sample_single under a polyphony cap: max_notes is None (sample_single itself, which calls this), an integer, or a sequence read
+        like the temperature's -- at most that many ones per track of this step (ops.nade_sample).  The signature every estimator's
+        sample_single shares stays as it is; only the NADE estimators have this one."""
         M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
         at = DrawAt(self.seed, self.row0, 0) if at is None else at
         out = state.dense
@@ -1108,7 +1145,8 @@ class RnnNade(RnnEstimator):
         smp = torch.empty((Bn, M * D), device=out.device, dtype=torch.uint8)
         nll = torch.empty((M, Bn), device=out.device)
         ops.nade_sample(out, self.store["nade/w_enc"], self.store["nade/w_dec"], M, D, Hn, temperature, at.seed, at.row0, at.step, smp,
-                        track_minor=(M > 1), nll=nll, given=None if given is None else given.contiguous(), by_visible=M == 1, sub_base=at.base)
+                        track_minor=(M > 1), nll=nll, given=None if given is None else given.contiguous(), by_visible=M == 1, sub_base=at.base,
+                        max_notes=max_notes)
         return smp, (nll[0] if M == 1 else [nll[m] for m in range(M)])
 
 

@@ -26,7 +26,7 @@ import weakref
 
 import torch
 
-from .common import Model, capture_train_step, given_codes, given_tracks, sampling_temperature
+from .common import Model, capture_train_step, given_codes, given_tracks, sampling_max_notes, sampling_temperature
 from .encoders import PassEncoder, DBNEncoder
 from .generators import RnnNade, RnnRBM, RnnMultiNADE, RnnMultiRBM
 from . import ops
@@ -229,13 +229,15 @@ class MultINNCore(Model):
     metrics_upd = property(lambda self: (self._ensure_global_metrics(), self._metrics_upd)[1])
 
     # -- sampling -------------------------------------------------------------------------------
-    def sampler(self, num_beats, given=None, given_mask=None, temperature=1.0):
-        """multinn_core.py:324-341: number of model time steps in `num_beats` beats, then generate() (given / given_mask / temperature: see
-        generate)."""
+    def sampler(self, num_beats, given=None, given_mask=None, temperature=1.0, max_notes=None):
+        """multinn_core.py:324-341: number of model time steps in `num_beats` beats, then generate() (given / given_mask / temperature /
+        max_notes: see generate)."""
         d = self._config["data"]
         pitch_span = d["pitch_range"]["highest"] - d["pitch_range"]["lowest"]
         num_steps = num_beats * d["beat_resolution"] * pitch_span // self._num_dims
         kw = {} if isinstance(temperature, (int, float)) and temperature == 1.0 else dict(temperature=temperature)
+        if max_notes is not None:
+            kw["max_notes"] = max_notes
         if given is None and given_mask is None:
             return self.generate(num_steps, **kw)
         return self.generate(num_steps, given=given, given_mask=given_mask, **kw)
@@ -258,6 +260,32 @@ class MultINNCore(Model):
         finite, a sequence of the wrong length or of more than 8 tracks, None with RBM generators, a sequence where no per-track exists."""
         rbm = self._generator_type in ("RBM", "MultiRBM")
         return sampling_temperature(temperature, self.num_tracks, allow_none=not rbm, allow_sequence=self._temperature_per_track)
+
+    # Polyphony cap (generate(..., max_notes)): at most K notes per track and generated step -- one integer >= 0, or one per track (None: that
+    # track has no cap): a monophonic bass, a drum track of at most four hits.  NADE generators only: the sampling scan counts a track's
+    # ones, given ones as well as drawn ones, and a free visible of a track that has reached its cap is a settled 0; a given cell always
+    # wins.  It keeps the FIRST K ones in visible order (ascending pitch) that the scan would have emitted -- the constrained ancestral
+    # sampler, not a sample from p(v | count <= K).  None (or a cap no track can reach) is the call without it, down to the captured scan.
+    def _max_notes(self, max_notes):
+        """Normalised on the host before any device work (common.sampling_max_notes): ValueError for an entry that is not an integer >= 0
+        or None, a sequence of the wrong length or of more than 8 tracks; MnnUnsupported with RBM generators (a Gibbs chain has no visible
+        order in which to stop), with DBN encoders (codes are not notes) and for a model on the host."""
+        if max_notes is None:
+            return None
+        normalised = sampling_max_notes(max_notes, self.num_tracks, self.num_dims if self._encoder_type == "Pass" else None)
+        if self._generator_type in ("RBM", "MultiRBM"):
+            raise MnnUnsupported("max_notes exists for NADE generators only: a Gibbs chain updates all visibles of a step at once and has no "
+                                 "visible order in which a track's count could stop it")
+        if self._encoder_type != "Pass":
+            raise MnnUnsupported("max_notes through DBN encoders is not implemented: the generators sample codes, and codes are not notes")
+        if self.device is not None and torch.device(self.device).type != "cuda":
+            raise MnnUnsupported(f"max_notes runs in the HIP sampling kernels: this model lives on {self.device}, not a ROCm device")
+        return normalised
+
+    def _generator_max_notes(self, max_notes):
+        """The normalised cap per generator.  Here the one NADE of the joint mode, whose visibles are ordered p M + m: one entry per track,
+        counted by visible index (an integer alone would cap the whole step)."""
+        return [None if max_notes is None else (max_notes,) * self.num_tracks if isinstance(max_notes, int) else max_notes]
 
     # Conditional generation (generate(num_steps, given, given_mask)): given u8 [B, num_steps, P, M] (nonzero = note on), given_mask bool
     # broadcastable to it -- [M] whole tracks (accompaniment), [P, M] pitch ranges, the full shape any cells (infilling); None = every cell.
@@ -288,29 +316,34 @@ class MultINNCore(Model):
         """NotImplementedError for a mask this mode's generators cannot honour (every generator of the joint, composer and jamming modes
         clamps inside its sampling kernels; see MultINNFeedback)."""
 
-    def _generate_arguments(self, num_steps, given, given_mask, temperature):
-        """The head of every generate and of a session's chunk, on the host: the temperature first, then the codes -> (temperature, cond)."""
+    def _generate_arguments(self, num_steps, given, given_mask, temperature, max_notes=None):
+        """The head of every generate and of a session's chunk, on the host: the temperature first, then the cap, then the codes ->
+        (temperature, cond, max_notes)."""
         temperature = self._temperature(temperature)
-        return temperature, self._given(num_steps, given, given_mask)
+        max_notes = self._max_notes(max_notes)
+        return temperature, self._given(num_steps, given, given_mask), max_notes
 
-    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0):
+    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0, max_notes=None):
         """-> u8 `[B, num_steps, P, M]` (multinn_joint.py:188-215, multinn_jamming.py:101-133, multinn_composer.py:114-151): every generator's
-        scan on its encoded intro, decoded per track.  temperature: _temperature; given / given_mask: conditional generation (_given).
+        scan on its encoded intro, decoded per track.  temperature: _temperature; max_notes: _max_notes; given / given_mask: conditional
+        generation (_given).
         What the modes differ in is in _generator_inputs, _generator_given and _decode_samples."""
-        temperature, cond = self._generate_arguments(num_steps, given, given_mask, temperature)
+        temperature, cond, max_notes = self._generate_arguments(num_steps, given, given_mask, temperature, max_notes)
         if self._x_encoded is None:
             MultINNCore._build_all(self, "generate")
         scans = [functools.partial(g.generate, x) for g, x in zip(self.generators, self._generator_inputs())]
-        return self._sample_generators(scans, num_steps, cond, temperature)
+        return self._sample_generators(scans, num_steps, cond, temperature, max_notes=max_notes)
 
-    def _sample_generators(self, scans, num_steps, cond, temperature, session=False):
+    def _sample_generators(self, scans, num_steps, cond, temperature, session=False, max_notes=None):
         """scans: per generator its scan(num_steps, given=, temperature=) -- its generate on its intro, or its session's chunk -> the
         decoded piano-roll.  One generator takes the whole temperature, M generators one each; a generator whose scan does not run
-        (_generator_given) emits its codes."""
+        (_generator_given) emits its codes.  max_notes (normalised): _generator_max_notes gives each generator its own; a generator without
+        one is called as before."""
         n = len(scans)
         temps = list(temperature) if isinstance(temperature, tuple) and n > 1 else [temperature] * n
         givens = [(None, True)] * n if cond is None else self._generator_given(cond, session)
-        samples = [scan(num_steps, given=gv, temperature=t) if run else gv for scan, (gv, run), t in zip(scans, givens, temps)]
+        caps = [{} if k is None else dict(max_notes=k) for k in (self._generator_max_notes(max_notes) if max_notes is not None else [None] * n)]
+        samples = [scan(num_steps, given=gv, temperature=t, **cap) if run else gv for scan, (gv, run), t, cap in zip(scans, givens, temps, caps)]
         return self._decode_samples(samples, num_steps)
 
     def _generator_inputs(self):
@@ -849,6 +882,10 @@ class MultINNJamming(MultIEncoderNN):
     def _generator_inputs(self):
         return self._x_encoded
 
+    def _generator_max_notes(self, max_notes):
+        """Generator m caps its own track."""
+        return list(max_notes) if isinstance(max_notes, tuple) else [max_notes] * self.num_tracks
+
     def _generator_given(self, cond, session=False):
         """multinn_jamming.py:101-133, conditioned: the generators are independent, generator m samples at its own temperature.  A partly
         given track is clamped inside its generator's scan (the NADE sampling kernels, or an RBM generator's clamped Gibbs chain).  A wholly
@@ -953,6 +990,10 @@ class MultINNComposer(MultIEncoderNN):
     def _generator_inputs(self):
         return [self._x_encoded_stack]
 
+    def _generator_max_notes(self, max_notes):
+        """The one MultiNADE takes the whole cap: track m's NADE scan counts its own ones."""
+        return [max_notes]
+
     def _decode_samples(self, samples, num_steps):
         """multinn_composer.py:114-151: the one generator's block [B, n, E * M] (feature e M + m) unbound into its tracks, then
         MultIEncoderNN's per-track decode.  Track m's NADE scan or Gibbs chain runs at its own temperature; the tracks of a step are
@@ -1035,12 +1076,14 @@ class MultINNFeedback(MultINNJamming):
             if isinstance(g, RnnRBM) and some[i] and not whole[i]:
                 raise NotImplementedError(f"track {i}: in feedback mode an RBM generator takes whole given tracks only (no clamped chain in the feedback scan)")
 
-    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0):
+    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0, max_notes=None):
         """multinn_feedback.py:120-173 -> u8 `[B, num_steps, P, M]`: one joint scan over the M generators and the feedback module.
-        temperature (MultINNCore._temperature): generator m samples at its own inside the scan.
+        temperature (MultINNCore._temperature): generator m samples at its own inside the scan.  max_notes (MultINNCore._max_notes):
+        generator m caps its own track.
         given / given_mask (MultINNCore._given): NADE generators clamp inside the scan, RBM generators take whole given tracks only."""
         from .feedback import FeedbackRnnSampler
-        temperature, cond = self._generate_arguments(num_steps, given, given_mask, temperature)
+        temperature, cond, max_notes = self._generate_arguments(num_steps, given, given_mask, temperature, max_notes)
+        cap = {} if max_notes is None else dict(max_notes=max_notes)
         if self._x_encoded is None:
             self._inputs = self._build_inputs()
             self._build_encoders("eval")
@@ -1050,9 +1093,9 @@ class MultINNFeedback(MultINNJamming):
         if getattr(self, "_sampler", None) is None:
             self._sampler = FeedbackRnnSampler(self.generators, self._feedback_layer)
         if self._encoder_type == "Pass":                                                          # whole scan = one hipGraph replay
-            samples_h = self._sampler.generate(self._x, num_steps, given=None if cond is None else cond[0], temperature=temperature)
+            samples_h = self._sampler.generate(self._x, num_steps, given=None if cond is None else cond[0], temperature=temperature, **cap)
         else:
-            samples_h = self._sampler.generate_encoded([e.to(torch.uint8) for e in self._x_encoded], num_steps, temperature=temperature)
+            samples_h = self._sampler.generate_encoded([e.to(torch.uint8) for e in self._x_encoded], num_steps, temperature=temperature, **cap)
         return self._decode_samples([samples_h[..., i].contiguous() for i in range(self.num_tracks)], num_steps)
 
     @property

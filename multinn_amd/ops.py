@@ -671,6 +671,25 @@ def _temps_table(temperature, n_per_job, by_visible, what):
     return _temps((temperature,) if isinstance(temperature, (int, float)) else temperature, n_per_job, by_visible, what)
 
 
+def _caps(max_notes, n_per_job, by_visible, what):
+    """None (no cap: the entry points without one serve the call, as they always did) or the mnn_caps of a `max_notes`: an int >= 0 (one
+    cap for every track / job) or a sequence of ints >= 0 / None (no cap for that one) -- one per track / job (n_per_job of them), or --
+    by_visible -- visible i counts in max_notes[i % len(max_notes)]."""
+    if max_notes is None:
+        return None
+    seq = (max_notes,) if isinstance(max_notes, int) else tuple(max_notes)
+    _req(1 <= len(seq) <= _lib.TEMPS_MAX and all(k is None or (isinstance(k, int) and not isinstance(k, bool) and k >= 0) for k in seq),
+         f"{what}: max_notes: 1..{_lib.TEMPS_MAX} integers >= 0 (None: no cap)")
+    _req(by_visible or len(seq) in (1, n_per_job), f"{what}: one cap, or one per track / job ({n_per_job})")
+    if all(k is None for k in seq):
+        return None
+    sc = _lib.Caps()
+    sc.n, sc.by_visible = len(seq), 1 if by_visible else 0
+    for i, k in enumerate(seq):
+        sc.cap[i] = -1 if k is None else min(k, 0x3fffffff)
+    return sc
+
+
 def _sub_base(sub_base, ref, what):
     """A generation session's step cell: None, or ONE 32-bit integer on the device of `ref` that the sampling kernels add to their sub-counter."""
     if sub_base is not None:
@@ -680,13 +699,15 @@ def _sub_base(sub_base, ref, what):
 
 
 def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub, samples, track_minor=False, nll=None, given=None,
-                by_visible=False, sub_base=None):
+                by_visible=False, sub_base=None, max_notes=None):
     """samples u8 [N, tracks*D]; feature index m*D+i (track_minor False) or i*tracks+m (True, rnn_multinade.py:313-314).
     temperature: a float, None (threshold draws) or a sequence -- one temperature per track, or with by_visible the temperature of visible
     i is temperature[i % len] (a joint NADE over visibles p * M + m: one per track m).  nll stays the model's own at any temperature.
     given (optional): codes u8 [N, tracks*D] in the layout of samples -- 0 / 1 clamp the visible to that value, 255 leaves it to the draw
     (common.given_codes).  sub_base (optional, one int32 on the device): the draws use the sub-counter sub + *sub_base, read by the kernel
-    (mnn_nade_sample_temps_at): a captured launch follows the cell."""
+    (mnn_nade_sample_temps_at): a captured launch follows the cell.  max_notes (optional, mnn_nade_sample_caps_at): at most that many ones per
+    track and row -- an int, or a sequence read like a temperature sequence (per track, or by visible index), None entries uncapped; given
+    ones count, a free visible of an exhausted track is a settled 0 that uses no uniform.  None: the calls below, as without the argument."""
     N = bias.shape[0]
     _req(bias.dtype == torch.float32 and bias.dim() == 2 and bias.stride(1) == 1 and bias.shape[1] >= tracks * (Hn + D), "sample: bias")
     _req(samples.dtype == torch.uint8 and samples.shape == (N, tracks * D) and samples.is_contiguous(), "sample: samples u8 [N,tracks*D]")
@@ -698,6 +719,12 @@ def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub,
         _req(given.dtype == torch.uint8 and tuple(given.shape) == (N, tracks * D) and given.is_contiguous() and given.device == samples.device,
              "sample: given u8 [N, tracks*D], contiguous")
     ts, es = (1, tracks) if track_minor else (D, 1)
+    cc = _caps(max_notes, tracks, by_visible, "sample")
+    if cc is not None:
+        tt = _temps_table(temperature, tracks, by_visible, "sample")
+        call("mnn_nade_sample_caps_at", _stream(), tracks, N, D, Hn, _ptr(bias), bias.stride(0), _ptr(w_enc), _ptr(w_dec), C.byref(tt), C.byref(cc),
+             int(seed), int(row0), int(sub), _ptr(samples), ts, tracks * D, es, _ptr(nll), _ptr(given), _sub_base(sub_base, samples, "sample"))
+        return
     if sub_base is not None:
         tt = _temps_table(temperature, tracks, by_visible, "sample")
         call("mnn_nade_sample_temps_at", _stream(), tracks, N, D, Hn, _ptr(bias), bias.stride(0), _ptr(w_enc), _ptr(w_dec), C.byref(tt), int(seed),
@@ -712,11 +739,12 @@ def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub,
          float(-1.0 if temperature is None else temperature), int(seed), int(row0), int(sub), _ptr(samples), ts, tracks * D, es, _ptr(nll), _ptr(given))
 
 
-def nade_sample_multi(jobs, D, Hn, temperature, row0, sub):
+def nade_sample_multi(jobs, D, Hn, temperature, row0, sub, max_notes=None):
     """mnn_nade_sample for up to 8 single-NADE generators in ONE launch.  job = dict(bias f32 [N, >= Hn + D] (the generator's Dense output),
     w_enc / w_dec f32 [D, Hn], seed, samples = a u8 [N, D] VIEW (any strides, the same for every job: e.g. out[:, s, :, m] of a
     [B, steps, P, M] piano-roll), nll f32 [N] or None, given = None or a u8 [N, D] view of codes with the strides of samples).
-    temperature: a float, None, or a sequence with one temperature per job."""
+    temperature: a float, None, or a sequence with one temperature per job.  max_notes: None, an int, or a sequence with one cap (or None)
+    per job (nade_sample)."""
     _req(1 <= len(jobs) <= 8, "nade_sample_multi: 1..8 jobs")
     arr = (_lib.NadeSampleJob * len(jobs))()
     N = jobs[0]["bias"].shape[0]
@@ -733,6 +761,11 @@ def nade_sample_multi(jobs, D, Hn, temperature, row0, sub):
              "sample_multi: given u8 [N, D] with the strides of samples")
         a.bias, a.ld_bias, a.w_enc, a.w_dec, a.seed, a.samples, a.nll = _ptr(b), b.stride(0), _ptr(j["w_enc"]), _ptr(j["w_dec"]), int(j["seed"]), _ptr(smp), _ptr(nll)
         a.given = _ptr(gv)
+    cc = _caps(max_notes, len(jobs), False, "sample_multi")
+    if cc is not None:
+        tt = _temps_table(temperature, len(jobs), False, "sample_multi")
+        call("mnn_nade_sample_multi_caps", _stream(), len(jobs), arr, N, D, Hn, C.byref(tt), C.byref(cc), int(row0), int(sub), rs, es)
+        return
     tt = _temps(temperature, len(jobs), False, "sample_multi")
     if tt is not None:
         call("mnn_nade_sample_multi_temps", _stream(), len(jobs), arr, N, D, Hn, C.byref(tt), int(row0), int(sub), rs, es)
@@ -1282,7 +1315,8 @@ def _scan_state(what, state, arr, B, device):
 def _scan_call(what, ref, intro, Ti, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, seed, row0, given):
     """What generate_scan and generate_scan_chunk share: the table and `given` checks, the workspace (256-byte aligned) and the samples
     u8 [B, num_steps, tracks * D] on ref's device -> (layer table, launch).  launch(symbol, temps, *state) makes the call -- the 16 leading
-    arguments, the temperature slot, seed .. given, then the entry point's own state arguments -- and returns the samples."""
+    arguments, the temperature slot (`temps`: one argument, or the pair (temps, caps) of the _caps entry points), seed .. given, then the entry
+    point's own state arguments -- and returns the samples."""
     B, n_in, n_out = ref.shape[0], tracks * D, tracks * (Hn + D)
     arr = _scan_tables(what, layers, n_in, n_out, dense_W, dense_bias, w_enc, w_dec, tracks, D, Hn)
     if given is not None:
@@ -1295,13 +1329,13 @@ def _scan_call(what, ref, intro, Ti, num_steps, layers, dense_W, dense_bias, tra
 
     def launch(symbol, temps, *state):
         call(symbol, _stream(), B, Ti, num_steps, _ptr(intro), n_in, len(layers), arr, _ptr(dense_W), _ptr(dense_bias), n_out, tracks, D, Hn,
-             _ptr(w_enc), _ptr(w_dec), temps, int(seed), int(row0), _ptr(samples), C.c_void_p(ws.data_ptr() + off), need, _ptr(given), *state)
+             _ptr(w_enc), _ptr(w_dec), *(temps if isinstance(temps, tuple) else (temps,)), int(seed), int(row0), _ptr(samples), C.c_void_p(ws.data_ptr() + off), need, _ptr(given), *state)
         return samples                      # (the workspace returns to the allocator in stream order: later users are behind the scan)
     return arr, launch
 
 
 def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, given=None, state0=None,
-                  by_visible=False):
+                  by_visible=False, max_notes=None):
     """mnn_generate_scan: the whole sampling scan of an LSTM-(Multi)NADE generator in one call.  intro u8 [B, Ti, tracks * D]; layers = [(W, bias)]
     f32 master weights; returns samples u8 [B, num_steps, tracks * D].  given (optional): codes u8 [B, num_steps, tracks * D] in the layout of
     the samples (see nade_sample).  temperature: a float, None, or a sequence (per track, or by visible index: nade_sample).  state0 (optional, mnn_generate_scan_state): [(c0, h0) f32 [B, u]] per layer, the state the intro pass starts from."""
@@ -1310,6 +1344,9 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
                              seed, row0, given)
     tt = _temps(temperature, tracks, by_visible, "generate_scan")
     cp, hp = _scan_state("generate_scan: state0", state0, arr, intro.shape[0], intro.device)
+    cc = _caps(max_notes, tracks, by_visible, "generate_scan")
+    if cc is not None:              # polyphony caps (nade_sample): the entry point that takes both tables
+        return launch("mnn_generate_scan_caps", (C.byref(_temps_table(temperature, tracks, by_visible, "generate_scan")), C.byref(cc)), cp, hp)
     if tt is not None:              # a temperature table: the one entry point that takes it, with or without an initial state
         return launch("mnn_generate_scan_temps", C.byref(tt), cp, hp)
     t = float(-1.0 if temperature is None else temperature)
@@ -1317,7 +1354,7 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
 
 
 def generate_scan_chunk(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, state_in, state_out,
-                        given=None, step0=0, step_base=None, by_visible=False):
+                        given=None, step0=0, step_base=None, by_visible=False, max_notes=None):
     """mnn_generate_scan_chunk: one chunk of a generation session of an LSTM-(Multi)NADE generator.  intro u8 [B, Ti, tracks * D] or None (the
     chunk continues from state_in); num_steps >= 0 (0 with an intro: the intro pass alone -> None); state_in: [(c, h) f32 [B, u]] per layer or
     None (the zero state); state_out: likewise, written with the state behind the last step (may be the arrays of state_in).  Step st draws
@@ -1333,5 +1370,10 @@ def generate_scan_chunk(intro, num_steps, layers, dense_W, dense_bias, tracks, D
     co, ho = _scan_state("generate_scan_chunk: state_out", state_out, arr, ref.shape[0], ref.device)
     _req(0 <= int(step0) and int(step0) + num_steps <= 1 << 32, "generate_scan_chunk: step0 + num_steps passes 2^32")
     tt = _temps_table(temperature, tracks, by_visible, "generate_scan_chunk")
+    cc = _caps(max_notes, tracks, by_visible, "generate_scan_chunk")
+    if cc is not None:
+        samples = launch("mnn_generate_scan_chunk_caps", (C.byref(tt), C.byref(cc)), ci, hi, co, ho, int(step0),
+                         _sub_base(step_base, ref, "generate_scan_chunk"))
+        return samples if num_steps > 0 else None
     samples = launch("mnn_generate_scan_chunk", C.byref(tt), ci, hi, co, ho, int(step0), _sub_base(step_base, ref, "generate_scan_chunk"))
     return samples if num_steps > 0 else None

@@ -5,11 +5,11 @@ step to step -- the LSTM state, the last Dense output, the last emitted row (an 
 
     sess = gen.session(x);  cat([sess.generate(n_i, given=g_i, temperature=T) for i]) == gen.generate(x, sum n_i, given=cat g_i, temperature=T)
 
-in every cell, for every split.  Every draw is keyed (stream, global row, sub-counter, element) with the sub-counter "the generated step"
+in every cell, for every split (with ``sess.max_notes = K`` set first: ``gen.generate(..., max_notes=K)``).  Every draw is keyed (stream, global row, sub-counter, element) with the sub-counter "the generated step"
 (times max(k, 1) for a Gibbs chain): a chunk that starts at step s draws at s, s + 1, ...  Eagerly that offset is a host number in the launch
 arguments.  A CAPTURED chunk cannot bake it in -- every chunk would need a new capture -- so the sampling kernels read it from a one-word
 step cell on the device (mnn_nade_sample_temps_at, mnn_rbm_gibbs_at, mnn_rbm_gibbs_multi_at, mnn_generate_scan_chunk): the session fills
-the cell with ``steps`` on the stream, then replays the chunk's graph.  Graphs are cached per session by (num_steps, has given, temperature):
+the cell with ``steps`` on the stream, then replays the chunk's graph.  Graphs are cached per session by (num_steps, has given, temperature, max_notes):
 the addresses of the session's state arrays are baked into them.  Each is a linear graph on one stream.
 
 GeneratorSession: one RnnEstimator (RnnNade, RnnMultiNADE, RnnRBM, RnnMultiRBM).  ModeSession: the joint, jamming and composer modes with
@@ -21,7 +21,7 @@ import torch
 
 from . import ops
 from ._lib import MnnUnsupported
-from .common import DrawAt, ScanGraphs, _warm_up, check_given, graph_capture, temperature_key
+from .common import DrawAt, ScanGraphs, _warm_up, check_given, graph_capture, max_notes_key, temperature_key
 
 __all__ = ["GeneratorSession", "ModeSession"]
 
@@ -66,6 +66,7 @@ class GeneratorSession:
         refuse_host_model(gen.store.device, "a generation session")
         refuse_host_model(x.device, "a generation session")
         self._gen, self.seed, self.row0 = gen, gen.seed, gen.row0
+        self._max_notes = None
         self.steps = 0
         self.batch = int(x.shape[0])
         self._graphs = collections.OrderedDict()
@@ -110,19 +111,19 @@ class GeneratorSession:
         self.steps = int(steps)
 
     # -- chunks ---------------------------------------------------------------------------------
-    def _run(self, n, given, temperature, base):
+    def _run(self, n, given, temperature, base, max_notes=None):
         """The launches of one chunk of n steps from the static state, which they advance in place.  base: the step cell (a captured chunk:
         the kernels add its word to their counters) or None (eager: the host adds `steps`)."""
         gen = self._gen
         step0 = 0 if base is not None else self.steps
         if self._scan:
             return ops.generate_scan_chunk(None, n, temperature=temperature, seed=self.seed, row0=self.row0, state_in=self._rnn, state_out=self._rnn,
-                                           given=given, step0=step0, step_base=base, **gen._scan_layers())
+                                           given=given, step0=step0, step_base=base, max_notes=max_notes, **gen._scan_layers())
         with gen._sampling_scope():
             if not gen.det_sampling:
                 gen._ensure_packed()
             out, state, last = gen._scan_steps(gen._state_of(self._out, tuple(self._rnn)), self._last, n,
-                                               DrawAt(self.seed, self.row0, step0, base), given, temperature)
+                                               DrawAt(self.seed, self.row0, step0, base), given, temperature, max_notes)
             for (c, h), (nc, nh) in zip(self._rnn, state.rnn_state):      # behind the last read of the static arrays
                 c.copy_(nc)
                 h.copy_(nh)
@@ -130,29 +131,42 @@ class GeneratorSession:
             self._last.copy_(last)
         return out
 
+    # The polyphony cap of the chunks to come (generate's max_notes): a property of the session, set between chunks -- `sess.max_notes = (1,
+    # None, 4)` -- and checked when it is set (the generator's own _max_notes: ValueError, or MnnUnsupported on an RBM generator, before
+    # any device work).  None, the default, is the session without it: the same launches, keys and captured chunks.
+    @property
+    def max_notes(self):
+        return self._max_notes
+
+    @max_notes.setter
+    def max_notes(self, value):
+        self._max_notes = self._gen._max_notes(value)
+
     def generate(self, num_steps, given=None, temperature=1.0):
         """The next num_steps steps -> u8 [B, num_steps, num_output].  given: the chunk's codes u8 [B, num_steps, num_output] as generate's
-        (None: every cell free); temperature: as generate's, and free to change from chunk to chunk."""
+        (None: every cell free); temperature: as generate's, and free to change from chunk to chunk.  The chunk runs under the session's
+        max_notes."""
         n, given, temperature = _chunk_arguments(self._gen, self.batch, self.steps, num_steps, given, temperature)
+        max_notes = self._max_notes
         gen = self._gen
         if given is not None:
             given = given.to(self._cell.device).contiguous()
         if not ScanGraphs.enabled(self._cell):
-            out = self._run(n, given, temperature, None)
+            out = self._run(n, given, temperature, None, max_notes)
             self.steps += n
             return out
-        key = (n, given is not None) + temperature_key(temperature)
+        key = (n, given is not None) + temperature_key(temperature) + max_notes_key(max_notes)
         ent = self._graphs.get(key)
         if ent is None:
             static_g = None if given is None else given.clone()
             snap = self.snapshot()
             w = min(n, 2)                            # a short eager run: kernel attributes and workspaces exist before the capture
-            _warm_up(lambda: self._run(w, None if static_g is None else static_g[:, :w].contiguous(), temperature, self._cell))
+            _warm_up(lambda: self._run(w, None if static_g is None else static_g[:, :w].contiguous(), temperature, self._cell, max_notes))
             self.restore(snap)
             g = torch.cuda.CUDAGraph()
             gen._packed_step = -1                    # pack inside the graph: a replay always sees the current weights
             with graph_capture(g, capture_error_mode="thread_local"):
-                out = self._run(n, static_g, temperature, self._cell)
+                out = self._run(n, static_g, temperature, self._cell, max_notes)
             gen._packed_step = -1                    # the packed copies now live in the graph's pool
             ent = self._graphs[key] = (g, static_g, out)
             while len(self._graphs) > MAX_GRAPHS:
@@ -187,6 +201,7 @@ class ModeSession:
         refuse_host_model(model.device, "a generation session")
         self._model = model
         self.steps = 0
+        self._max_notes = None
         if model._x_encoded is None:
             MultINNCore._build_all(model, "generate")
         self._subs = [g.session(x) for g, x in zip(model.generators, model._generator_inputs())]
@@ -202,12 +217,26 @@ class ModeSession:
             s.restore(sn)
         self.steps = int(steps)
 
+    # The polyphony cap of the chunks to come, as GeneratorSession's: set between chunks, checked by the mode's own _max_notes when it is
+    # set, handed to every generator's session as the mode's generate hands it to the generators (_generator_max_notes).
+    @property
+    def max_notes(self):
+        return self._max_notes
+
+    @max_notes.setter
+    def max_notes(self, value):
+        m = self._model
+        value = m._max_notes(value)
+        for s, k in zip(self._subs, m._generator_max_notes(value) if value is not None else [None] * len(self._subs)):
+            s.max_notes = k
+        self._max_notes = value
+
     def generate(self, num_steps, given=None, given_mask=None, temperature=1.0):
         """The next num_steps steps -> u8 [B, num_steps, P, M].  given u8 [B, num_steps, P, M] / given_mask / temperature: as the mode's
-        generate, checked once per chunk, and free to change from chunk to chunk."""
+        generate, checked once per chunk, and free to change from chunk to chunk.  The chunk runs under the session's max_notes."""
         m = self._model
         n = _num_steps(self.steps, num_steps, max(s._gen.subs_per_step for s in self._subs))
-        temperature, cond = m._generate_arguments(n, given, given_mask, temperature)
+        temperature, cond, _ = m._generate_arguments(n, given, given_mask, temperature)
         snap = self.snapshot() if len(self._subs) > 1 else None      # several generators advance one after another: a chunk that fails half way leaves none of them advanced
         try:
             out = m._sample_generators([s.generate for s in self._subs], n, cond, temperature, session=True)
