@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import nade as onade, rbm as orbm, lstm as olstm, philox, det, generators as G   # noqa: E402
 from oracle import tf_semantics as S   # noqa: E402
+import lstm_float64 as L64   # noqa: E402  (tests/lstm_float64.py: the float64 reference of the single-layer persistent recurrences)
 
 DEV = "cuda:0"
 
@@ -1101,12 +1102,6 @@ def test_nade_sample_multi_equals_per_generator_launches():
 
 
 # ------------------------------------------------------------------------------------------------
-def _gate_perm(u):
-    """natural TF column g * u + unit -> (unit / 32) * 128 + g * 32 + unit % 32 (DESIGN.md "LSTM layout")"""
-    unit = np.arange(u)
-    return np.stack([(unit >> 5) * 128 + g * 32 + (unit & 31) for g in range(4)])        # [gate][unit]
-
-
 @pytest.mark.parametrize("dt", ["fp16", "bf16"])
 @pytest.mark.parametrize("B,T,keep,layout,save", [(8, 6, 0.9, "plain", True), (64, 5, 0.9, "kblock", True), (36, 4, 1.0, "plain", True), (12, 7, 0.9, None, False),
                                                    (2048, 2, 0.9, "kblock", True)])
@@ -1139,21 +1134,10 @@ def test_lstm_resident_recurrence_vs_float64(ops, B, T, keep, layout, save, dt):
     ops.lstm_resident_fwd(T, B, L, keep)
     torch.cuda.synchronize()
     # ---- float64 forward on the same operands ----
-    perm = _gate_perm(u)
     W = wh_t.double().numpy()                                                        # z[n] += sum_k h[k] W[n][k]
-    X = xproj.double().numpy()
-    sig = lambda a: 1.0 / (1.0 + np.exp(-a))                                        # noqa: E731
-    hp, cp = np.zeros((B, u)), np.zeros((B, u))
-    ref = dict(g=np.zeros((T, B, u, 4)), c=np.zeros((T, B, u)), h=np.zeros((T, B, u)))
-    for t in range(T):
-        z = np.stack([X[t, :, :, g] + hp @ W[perm[g]].T for g in range(4)], -1)     # [B, u, 4]
-        gi, gg, gf, go = sig(z[..., 0]), np.tanh(z[..., 1]), sig(z[..., 2]), sig(z[..., 3])
-        cp = gg * gi + cp * gf
-        hv = np.tanh(cp) * go
-        ref["g"][t] = np.stack([gi, gg, gf, go], -1)
-        ref["c"][t] = cp
-        ref["h"][t] = hv
-        hp = h[t].double().cpu().numpy() if (mask is None or t + 1 == T) else r16(hv).double().numpy()     # the 16-bit state the kernel feeds back
+    hk = h.double().cpu().numpy()
+    # the 16-bit state the kernel feeds back
+    ref = L64.forward(W, xproj.double().numpy(), lambda t, hv: hk[t] if (mask is None or t + 1 == T) else r16(hv).double().numpy())
     got_c = c.cpu().numpy()
     assert np.abs(got_c - ref["c"]).max() < 4 * eps, np.abs(got_c - ref["c"]).max()
     if mask is None:
@@ -1185,20 +1169,8 @@ def test_lstm_resident_recurrence_vs_float64(ops, B, T, keep, layout, save, dt):
     torch.cuda.synchronize()
     Gs = gates.double().cpu().numpy().reshape(T, B, u, 4)
     Cs = c.double().cpu().numpy()
-    dz_ref = np.zeros((T, B, 4 * u))
-    dcv, dz_next = np.zeros((B, u)), np.zeros((B, 4 * u))
-    for t in range(T - 1, -1, -1):
-        gi, gg, gf, go = (Gs[t, :, :, k] for k in range(4))
-        dhv = dh[t].double().cpu().numpy() * (mask[t] / keep if mask is not None else 1.0) + dz_next @ W      # sum_n dz[n] W[n][k]
-        tc = np.tanh(Cs[t])
-        d_o = dhv * tc
-        d_c = dhv * go * (1 - tc * tc) + dcv
-        cprev = Cs[t - 1] if t > 0 else np.zeros((B, u))
-        dzs = [d_c * gg * gi * (1 - gi), d_c * gi * (1 - gg * gg), d_c * cprev * gf * (1 - gf), d_o * go * (1 - go)]
-        dcv = d_c * gf
-        for g in range(4):
-            dz_ref[t][:, perm[g]] = dzs[g]
-        dz_next = dzc[t].double().cpu().numpy()                                      # the 16-bit values the kernel feeds back
+    dzk = dzc.double().cpu().numpy()
+    dz_ref = L64.backward(W, Gs, Cs, dh.double().cpu().numpy(), mask, keep, lambda t, dz: dzk[t])      # the 16-bit values the kernel feeds back
     scale = np.abs(dz_ref).max()
     got = dzc.double().cpu().numpy()
     assert np.abs(got - dz_ref).max() < 3 * eps * scale, (np.abs(got - dz_ref).max(), scale)
@@ -1388,21 +1360,10 @@ def test_lstm_cluster_recurrence_vs_float64(ops, monkeypatch, B, T, keep, layout
     torch.cuda.synchronize()
     ops.lstm_rowpar_check(ws)
     # ---- float64 forward on the same operands ----
-    perm = _gate_perm(u)
     W = wh_t.double().numpy()                                                        # z[n] += sum_k h[k] W[n][k]
-    X = xproj.double().numpy()
-    sig = lambda a: 1.0 / (1.0 + np.exp(-a))                                        # noqa: E731
-    hp, cp = np.zeros((B, u)), np.zeros((B, u))
-    ref = dict(g=np.zeros((T, B, u, 4)), c=np.zeros((T, B, u)), h=np.zeros((T, B, u)))
-    for t in range(T):
-        z = np.stack([X[t, :, :, g] + hp @ W[perm[g]].T for g in range(4)], -1)     # [B, u, 4]
-        gi, gg, gf, go = sig(z[..., 0]), np.tanh(z[..., 1]), sig(z[..., 2]), sig(z[..., 3])
-        cp = gg * gi + cp * gf
-        hv = np.tanh(cp) * go
-        ref["g"][t] = np.stack([gi, gg, gf, go], -1)
-        ref["c"][t] = cp
-        ref["h"][t] = hv
-        hp = h[t].double().cpu().numpy() if (mask is None or t + 1 == T) else r16(hv).double().numpy()     # the 16-bit state the kernel feeds back
+    hk = h.double().cpu().numpy()
+    # the 16-bit state the kernel feeds back
+    ref = L64.forward(W, xproj.double().numpy(), lambda t, hv: hk[t] if (mask is None or t + 1 == T) else r16(hv).double().numpy())
     got_c = c.cpu().numpy()
     assert np.abs(got_c - ref["c"]).max() < 4 * eps, np.abs(got_c - ref["c"]).max()
     if mask is None:
@@ -1434,20 +1395,8 @@ def test_lstm_cluster_recurrence_vs_float64(ops, monkeypatch, B, T, keep, layout
     ops.lstm_rowpar_check(ws)
     Gs = gates.double().cpu().numpy().reshape(T, B, u, 4)
     Cs = c.double().cpu().numpy()
-    dz_ref = np.zeros((T, B, 4 * u))
-    dcv, dz_next = np.zeros((B, u)), np.zeros((B, 4 * u))
-    for t in range(T - 1, -1, -1):
-        gi, gg, gf, go = (Gs[t, :, :, k] for k in range(4))
-        dhv = dh[t].double().cpu().numpy() * (mask[t] / keep if mask is not None else 1.0) + dz_next @ W      # sum_n dz[n] W[n][k]
-        tc = np.tanh(Cs[t])
-        d_o = dhv * tc
-        d_c = dhv * go * (1 - tc * tc) + dcv
-        cprev = Cs[t - 1] if t > 0 else np.zeros((B, u))
-        dzs = [d_c * gg * gi * (1 - gi), d_c * gi * (1 - gg * gg), d_c * cprev * gf * (1 - gf), d_o * go * (1 - go)]
-        dcv = d_c * gf
-        for g in range(4):
-            dz_ref[t][:, perm[g]] = dzs[g]
-        dz_next = dzc[t].double().cpu().numpy()                                      # the 16-bit values the kernel feeds back
+    dzk = dzc.double().cpu().numpy()
+    dz_ref = L64.backward(W, Gs, Cs, dh.double().cpu().numpy(), mask, keep, lambda t, dz: dzk[t])      # the 16-bit values the kernel feeds back
     scale = np.abs(dz_ref).max()
     got = dzc.double().cpu().numpy()
     assert np.abs(got - dz_ref).max() < 3 * eps * scale, (np.abs(got - dz_ref).max(), scale)

@@ -178,18 +178,36 @@ def test_target_shape_train_step_properties(precision):
     assert all(np.isfinite(ls)) and ls[-1] < ls[0], ls
 
 
+NO_RESIDENT = dict(resident=False)
+# (the first five keep the ids pytest gave them before the `stack` column existed)
+ROWPAR_CASES = [pytest.param([512, 256], 64, 8, None, {}, id="units0-64-8-None"), pytest.param([128, 128, 128], 96, 6, None, {}, id="units1-96-6-None"),
+                pytest.param([256], 32, 5, None, {}, id="units2-32-5-None"), pytest.param([512, 256], 64, 6, 1, {}, id="units3-64-6-1"),
+                pytest.param([256], 128, 5, 1, {}, id="units4-128-5-1"),
+                pytest.param([512, 256], 64, 6, None, NO_RESIDENT, id="512+256-64-6-noresident"),
+                pytest.param([512, 256], 64, 6, None, dict(resident=False, rowpar_xproj_f32=True), id="512+256-64-6-noresident-xproj32"),
+                pytest.param([256], 128, 5, 1, NO_RESIDENT, id="256-128-5-maxg1-noresident")]
+
+
 @pytest.mark.parametrize("precision", ["bf16", "fp16"])
-@pytest.mark.parametrize("units,B,T,max_g", [([512, 256], 64, 8, None), ([128, 128, 128], 96, 6, None), ([256], 32, 5, None),
-                                             ([512, 256], 64, 6, 1), ([256], 128, 5, 1)])
-def test_rowpar_recurrence_vs_oracle(units, B, T, max_g, precision, monkeypatch):
-    """The row-parallel persistent recurrence (lstm_rowpar.hip: one launch per layer, weights in LDS, a wave per 32-row tile -- the form
-    for B >= 512) against the float64 oracle, with its batch threshold lowered so the oracle stays quick: loss, NLL and every gradient
-    within the bf16 bounds of the two-layer persistent form; it must also agree with the launch-per-step kernels on the same weights.
+@pytest.mark.parametrize("units,B,T,max_g,stack", ROWPAR_CASES)
+def test_rowpar_recurrence_vs_oracle(units, B, T, max_g, stack, precision, monkeypatch):
+    """The row-parallel path of LstmStack (one launch per layer for all T steps) against the float64 oracle, with its batch threshold lowered
+    so the oracle stays quick: loss, NLL and every gradient within the bf16 bounds of the two-layer persistent form; it must also agree with
+    the launch-per-step kernels on the same weights.  Which kernels run: a 512- or 128-unit layer takes lstm_rowpar.hip (weights in LDS, a
+    wave or a wave pair per 32-row tile); a 256-unit layer takes the CU-RESIDENT recurrence (lstm_resident.hip) at every B % 4 == 0, so of
+    the first five cases `[256]` (both batches) and layer 2 of `[512, 256]` run the resident kernel, whatever `max_g` says.  The `stack`
+    column overrides LstmStack switches: `resident=False` sends the 256-unit layers to lstm_rowpar.hip too (every layer's forward and
+    backward is asserted "rowpar"), `rowpar_xproj_f32` keeps the input projections in f32 (the XB = false forward kernels).
     Up to two row tiles per workgroup run as wave pairs (two waves per (row tile, unit tile) item); `max_g` = 1 (test hook MNN_ROWPAR_MAX_G)
-    puts all row tiles of the small batch on one workgroup per unit tile: two tiles = both pair slots, four tiles = the one-wave-per-tile form."""
+    puts all row tiles of the small batch on one workgroup per unit tile: two tiles = both pair slots, four tiles (`[256]`, B = 128,
+    resident=False) = the one-wave-per-tile form.  Kernel by kernel: tests/test_gpu_rowpar_kernels.py."""
     from multinn_amd import RnnNade
+    from multinn_amd.lstm_stack import LstmStack
     if max_g is not None:
         monkeypatch.setenv("MNN_ROWPAR_MAX_G", str(max_g))
+    for k, v in stack.items():
+        assert hasattr(LstmStack, k)
+        monkeypatch.setattr(LstmStack, k, v)
     rho = 0.05
     x = synth(B, T, 29, rho)
     p = G.init_rnn_nade(31, D, D, HN, units, np.float64)
@@ -206,6 +224,9 @@ def test_rowpar_recurrence_vs_oracle(units, B, T, max_g, precision, monkeypatch)
     gen._stack.keep_debug = True
     gen.build_pianoroll(dev(x), None, is_train=True, mode="train")
     assert gen._stack._rowpar(B, T) and gen._ctx["lstm"][0].get("rowpar")
+    if stack:
+        plan = gen._stack.plan(B, T)
+        assert plan.path == "rowpar" and set(plan.fwd) == {"rowpar"} and set(plan.bwd) == {"rowpar"}, plan
     loss = float(gen.metrics["batch/loss"])
     nll = gen.log_probs.cpu().numpy()
     gen.backward()
@@ -216,7 +237,7 @@ def test_rowpar_recurrence_vs_oracle(units, B, T, max_g, precision, monkeypatch)
         got = gen.store.gviews[name].cpu().numpy().reshape(ref.shape)
         errs[name] = rel(got, ref)
         cosv[name] = cosine(got, ref)
-    print(f"\n[rowpar {precision} units={units} B={B} T={T}] relative error vs float64 oracle:")
+    print(f"\n[rowpar {precision} units={units} B={B} T={T} {stack}] relative error vs float64 oracle:")
     for k, v in errs.items():
         print(f"    {k:24s} {v:.3e}" + (f"   cos {cosv[k]:.6f}" if k in cosv else ""))
     if precision == "fp16":     # the benchmarked mode and form: BASELINE.json's 1e-4 on the loss and every row's NLL
