@@ -7,7 +7,7 @@
 //     logits[row, d] = state(row, d) . w_dec[d]
 // A workgroup owns 32 rows and walks the visibles in tiles of 32 columns.  Per tile:
 //   * base states (one per row, as of the tile's first column) x w_dec tile  -> 32 x 32 logits on MFMA
-//   * every flip (v = 1) inside the tile creates a new state: a += w_enc[d] in f32 (thread = hidden unit),
+//   * every flip (v = 1) inside the tile creates a new state: a += w_enc[d] in f32 (the wave that owns the row, four hidden units a lane),
 //     h = sigmoid(a) -> bf16 into a flip-state tile; flip states x w_dec tile -> 32-slot x 32 logits on MFMA
 //   * each (row, d) picks the logit of the latest state created before d (popcount of the row's v bits), adds
 //     b_dec, and finishes p, the NLL term and d nll / d b_dec.
@@ -20,7 +20,6 @@ typedef float nm_f4 __attribute__((ext_vector_type(4)));
 // results (conditionals, d nll / d logit, a_final) are written once and read by later kernels: stored non-temporal, they leave the decoder / encoder
 // weights every workgroup re-reads in the L2 (2.19 -> 2.17 ms at [262144, 440, 256]; same in the backward's d b_enc store)
 #define NM_ST4(dst, a) __builtin_nontemporal_store((nm_f4){a[0], a[1], a[2], a[3]}, reinterpret_cast<nm_f4*>(dst))
-#define NM_ST1(dst, x) __builtin_nontemporal_store((float)(x), dst)
 #include <algorithm>
 #include <type_traits>
 
@@ -65,16 +64,14 @@ __device__ __forceinline__ unsigned nm_pack_hl(float x) {
 
 template <bool SPLIT>
 struct NadeFwdSmemT {
-    float sA[SPLIT ? 1 : 32][NM_H];     // pre-activations a[row][hidden] (f32; thread = hidden unit owns a column); split form: in registers
     typename NmState<SPLIT>::T sH[32][NmState<SPLIT>::PITCH];            // current state of every row (as of the tile being processed)
-    typename NmState<SPLIT>::T sF[32][NmState<SPLIT>::PITCH];            // states created by the flips of the tile (one chunk of 32 slots)
+    typename NmState<SPLIT>::T sF[32][NmState<SPLIT>::PITCH];            // states created by the flips of the tile (one chunk of 32 slots, row-major)
     float sLb[32][NM_LP];               // logits of the base states  [row][column]
     float sLf[32][NM_LP];               // logits of the flip states  [slot][column]
     unsigned sMask[2][32];              // v bits of the tile, per row (double buffered: tile c, tile c+1)
-    unsigned sSb[2][33];                // exclusive prefix of popcounts (slot of a row's first flip); [32] = flips in the tile
-    unsigned short sFl[2][1024];        // flips in pass order: row << 5 | column
-    unsigned short sPs[2][34];          // first slot of pass j (the j-th flips of the rows)
-    unsigned sAct[2][32];               // rows taking part in pass j (bit n: row n has more than j flips in the tile)
+    unsigned sSb[2][32];                // flips of the owning wave's rows in front of the row (the wave adds the flips of the waves before it)
+    unsigned sCnt[2][4];                // flips of the tile in each wave's eight rows
+    unsigned char sFl[2][4][256];       // each wave's flips in row-major order: (row - 8w) << 5 | column
 };
 
 // 16 rows x K=256 of a state tile as MFMA A fragments (lane: row l & 15, k = 32 s + 8 (l >> 4) + j)
@@ -130,9 +127,17 @@ __device__ __forceinline__ void nm_logit_tile(const Tile& tile, int w, int lane,
     for (int i = 0; i < 4; ++i) out[16 * mi + 4 * (lane >> 4) + i][16 * ni + (lane & 15)] = acc[i];
 }
 
-// thread = hidden unit: the 32 rows' pre-activations a[32] live in registers and are indexed by the (wave-uniform) row of
-// each flip -- the compiler lowers that to s_set_gpr_idx, no scratch.  Per flip the VALU does one add, one sigmoid,
-// one bf16 convert and two LDS writes; everything it needs (the flip list, the flips' w_enc values) was fetched a tile ahead.
+// Ownership of the sparse side: WAVE w owns rows 8w .. 8w+7 of the workgroup -- their v bytes, their flips, their pre-activations and their
+// part of the flip list -- and a LANE owns the four consecutive hidden units 4 lane .. 4 lane + 3.  The 8 x 4 pre-activations live in
+// registers, indexed by the (wave-uniform) row of each flip -- the compiler lowers that to s_set_gpr_idx, no scratch.  A flip is executed by
+// ONE wave for all 256 hidden units: 4 adds, 4 sigmoids, 4 state words, one 16-byte (bf16 form: 8-byte) LDS store into its slot of sF and one
+// into its row of sH; what a flip costs besides (list entry, register index, addresses) is paid once per 256 units.
+// Slots are ROW-MAJOR: slot of (row n, its j-th flip) = flips of the rows before n + j, so a wave's flips are consecutive slots, a row's flips
+// keep their column order across the 32-slot chunks, and no wave builds a list for the others: each derives its entries from the ballots of
+// its own rows and learns the other waves' counts (sCnt) at the tile's first barrier.
+#define NM_P 12           // w_enc rows a wave fetches a tile ahead (16 bytes per lane each); a wave's flips beyond them are fetched in place
+typedef float nm_f2 __attribute__((ext_vector_type(2)));
+typedef float nm_f4u __attribute__((ext_vector_type(4), aligned(4)));          // 16-byte global access at 4-byte alignment (rows of `bias` at any ld_bias)
 template <bool SPLIT>
 __device__ __forceinline__ void
 nade_fwd_mfma_body(int tracks, int N, int D, const uint8_t* __restrict__ v, long v_track_stride, const float* __restrict__ bias, int ld_bias,
@@ -141,9 +146,11 @@ nade_fwd_mfma_body(int tracks, int N, int D, const uint8_t* __restrict__ v, long
                      const int* __restrict__ gate, int run_if, const int* __restrict__ n_rows_dev) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     typedef NadeFwdSmemT<SPLIT> NadeFwdSmem;
-    typedef typename NmState<SPLIT>::T state_t;
+    typedef typename std::conditional<SPLIT, uint4, ushort4>::type state4_t;      // the four states of a lane: one LDS store
     typedef typename std::conditional<SPLIT, NmPairB, bf16x8_t>::type bfrag_t;
     constexpr int KS = 8;                                    // k-steps of 32 hidden units
+    constexpr int P = NM_P;
+    static_assert(P % 4 == 0 && P <= 16, "the prefetched rows are handled four at a time; their list entries sit in lanes 0..15");
     NadeFwdSmem& S = *reinterpret_cast<NadeFwdSmem*>(smem_raw);
     if (gate != nullptr && *gate != run_if) return;          // density-gated pair of launches: uniform exit
     constexpr int Hn = NM_H;
@@ -167,22 +174,31 @@ nade_fwd_mfma_body(int tracks, int N, int D, const uint8_t* __restrict__ v, long
         return;
     }
 
-    // split form: the pre-activations of this thread's hidden unit for the 32 rows live in REGISTERS, indexed by the wave-uniform row of each
-    // flip (indirect register addressing); that frees 32 KiB of LDS (two workgroups per CU with the doubled state tiles) and takes the
-    // LDS round trip out of every flip's read-modify-write
-    float areg[SPLIT ? 32 : 1];
+    auto state4 = [&](const float (&x)[4]) {
+        state4_t h;
+        h.x = nm_state<SPLIT>(fast_sigmoid(x[0])); h.y = nm_state<SPLIT>(fast_sigmoid(x[1]));
+        h.z = nm_state<SPLIT>(fast_sigmoid(x[2])); h.w = nm_state<SPLIT>(fast_sigmoid(x[3]));
+        return h;
+    };
+    // pre-activations of this wave's 8 rows x this lane's 4 hidden units: registers, indexed by the wave-uniform row of a flip.  Held as
+    // two arrays of eight 64-BIT words (units 0, 1 | units 2, 3 of a row): an indexed move then carries two units, and the two arrays share one
+    // index, so a row is read with one s_set_gpr_idx_on / off pair around two 64-bit moves and written with another (a float[32] took a pair
+    // per unit and direction; arrays of eight 32-bit words are compiled into select chains)
+    unsigned long long a01[8], a23[8];
+    auto pair_of = [](float lo, float hi) { return __builtin_bit_cast(unsigned long long, (nm_f2){lo, hi}); };
     {
-        // all 32 encoder-bias loads in flight before the first is used (unconditional, from clamped rows): with `row < N ? load : 0` every
-        // load sat behind its own branch and s_waitcnt vmcnt(0) -- 32 memory round trips in a row at the start of every workgroup
-        float av[32];
+        // all 8 encoder-bias loads in flight before the first is used (unconditional, from clamped rows)
+        nm_f4 av[8];
 #pragma unroll
-        for (int n = 0; n < 32; ++n) av[n] = bias[(size_t)min(rb + n, N - 1) * ld_bias + m * Hn + tid];
+        for (int r = 0; r < 8; ++r)
+            av[r] = *reinterpret_cast<const nm_f4u*>(&bias[(size_t)min(rb + 8 * w + r, N - 1) * ld_bias + m * Hn + 4 * lane]);
 #pragma unroll
-        for (int n = 0; n < 32; ++n) {
-            const float x = rb + n < N ? av[n] : 0.f;
-            if constexpr (SPLIT) areg[n] = x;
-            else S.sA[n][tid] = x;
-            S.sH[n][tid] = nm_state<SPLIT>(fast_sigmoid(x));
+        for (int r = 0; r < 8; ++r) {
+            float x[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) x[q] = rb + 8 * w + r < N ? av[r][q] : 0.f;
+            a01[r] = pair_of(x[0], x[1]); a23[r] = pair_of(x[2], x[3]);
+            *reinterpret_cast<state4_t*>(&S.sH[8 * w + r][4 * lane]) = state4(x);
         }
     }
     // v bytes of rows 8w .. 8w+7 of a tile: lane -> (row 8w + 2i + (lane >> 5), column lane & 31)
@@ -193,37 +209,26 @@ nade_fwd_mfma_body(int tracks, int N, int D, const uint8_t* __restrict__ v, long
             vb[i] = vm[(size_t)row * D + dd];
         }
     };
-    auto ballots = [&](int c, const unsigned char (&vb)[4], unsigned (&msk)[32]) {
+    // The wave's share of a tile's bookkeeping, from the four ballots of its rows: the rows' masks, the flips in front of each row, the wave's
+    // flips in row-major order (ballot i covers rows 2i, 2i+1, so entry = 64 i + lane = (row - 8w) << 5 | column and its rank is the count of
+    // set bits below it) and the wave's count.  Returns the count.
+    auto ballots = [&](int c, const unsigned char (&vb)[4], int b) {
+        int cum = 0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int row = rb + 8 * w + 2 * i + (lane >> 5), dd = 32 * c + (lane & 31);
-            const unsigned long long bal = __ballot(row < N && dd < D && vb[i] != 0);
-            if (lane == 0) { msk[8 * w + 2 * i] = (unsigned)bal; msk[8 * w + 2 * i + 1] = (unsigned)(bal >> 32); }
-        }
-    };
-    // wave 0: flip list of the tile whose masks are in sMask[buf], in PASS order (all first flips of the rows, then all second
-    // flips, ...): consecutive entries touch different rows, so their read-modify-writes of sA are independent.
-    // sSb[buf][n] keeps the rank-0 slot of row n; the slot of its j-th flip is looked up through sPs (start of pass j).
-    auto build_list = [&](int buf) {
-        if (w == 0) {
-            const unsigned mk = lane < 32 ? S.sMask[buf][lane] : 0u;
-            const int cnt = __popc(mk);
-            unsigned rest = mk;
-            int base = 0;
-            for (int j = 0; j < 32; ++j) {                   // pass j: rows with more than j flips, in row order
-                const unsigned act = (unsigned)__ballot(cnt > j);
-                if (lane == 0) { S.sPs[buf][j] = (unsigned short)base; S.sAct[buf][j] = act; }
-                if (act == 0u) break;
-                if (cnt > j) {
-                    const int pos = base + __popc(act & ((1u << lane) - 1u));
-                    const int dpos = __builtin_ctz(rest);
-                    rest &= rest - 1;
-                    S.sFl[buf][pos] = (unsigned short)((lane << 5) | dpos);
-                }
-                base += __popc(act);
+            const bool on = row < N && dd < D && vb[i] != 0;
+            const unsigned long long bal = __ballot(on);
+            const unsigned lo = (unsigned)bal, hi = (unsigned)(bal >> 32);
+            if ((lane & 31) == 0) {
+                S.sMask[b][8 * w + 2 * i + (lane >> 5)] = lane ? hi : lo;
+                S.sSb[b][8 * w + 2 * i + (lane >> 5)] = (unsigned)(cum + (lane ? __popc(lo) : 0));
             }
-            if (lane == 0) S.sSb[buf][32] = (unsigned)base;
+            if (on) S.sFl[b][w][cum + (int)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u))] = (unsigned char)(64 * i + lane);
+            cum += __popcll(bal);
         }
+        if (lane == 0) S.sCnt[b][w] = (unsigned)cum;
+        return cum;
     };
     auto load_b = [&](int c, bfrag_t (&b)[KS]) {            // lane: column l & 15 of the wave's column half, k = 32 s + 8 (l >> 4) + j
         const int d = min(32 * c + 16 * ni + (lane & 15), D - 1);
@@ -240,34 +245,35 @@ nade_fwd_mfma_body(int tracks, int N, int D, const uint8_t* __restrict__ v, long
             for (int s = 0; s < KS; ++s) b[s] = *reinterpret_cast<const bf16x8_t*>(p + 32 * s);
         }
     };
-    // w_enc[column of flip k0+u][this hidden unit] for the 32 flips of a chunk (entries past the tile's count re-read flip 0's row)
+    // w_enc[column of the wave's flip j0 + u][this lane's 4 hidden units], u < P, for the flips below jend; four at a time, a group with no flip
+    // is not requested (the values of entries past jend inside a group are never used: their list bytes are stale, their columns clamped)
     const __amdgpu_buffer_rsrc_t we_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(we), 0, D * Hn * 4, 0x00020000);
-    auto load_we = [&](int c, int buf, int k0, float (&wv)[32]) {
-        const int F = (int)S.sSb[buf][32];
-        // ONE list read per lane (lane u holds entry k0 + u), the entries then come out of the lanes with v_readlane: a uniform LDS read per
-        // entry followed by v_readfirstlane is compiled into one LDS round trip per entry, 32 in a row
-        const int entv = (int)S.sFl[buf][(k0 + (lane & 31) < F) ? k0 + (lane & 31) : 0];
+    auto load_we = [&](int c, int b, int j0, int jend, nm_f4 (&wv)[P]) {
+        // ONE list read per lane (lane u holds entry j0 + u), the entries then come out of the lanes with v_readlane
+        const int entv = (int)S.sFl[b][w][min(j0 + (lane & 15), 255)];
 #pragma unroll
-        for (int u = 0; u < 32; ++u) {
-            // buffer load: the row offset rides in the instruction's SCALAR offset operand, the lane offset (4 tid) is one loop-invariant
-            // register -- no vector ALU work per load (a global load took a 64-bit vector add per row: 32 per tile and thread)
-            const int e = __builtin_amdgcn_readlane(entv, u);
-            wv[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(we_rs, tid * 4, min(32 * c + (e & 31), D - 1) * (Hn * 4), 0));
+        for (int g = 0; g < P; g += 4) {
+            if (j0 + g < jend) {
+#pragma unroll
+                for (int u = g; u < g + 4; ++u) {
+                    // buffer load: the row offset rides in the instruction's SCALAR offset operand, the lane offset (16 lane) is one loop-invariant register
+                    const int e = __builtin_amdgcn_readlane(entv, u);
+                    wv[u] = __builtin_bit_cast(nm_f4, __builtin_amdgcn_raw_buffer_load_b128(we_rs, lane * 16, min(32 * c + (e & 31), D - 1) * (Hn * 4), 0));
+                }
+            }
         }
     };
     unsigned char vb[4];
     bfrag_t bfr[KS];
-    float wev[32];
+    nm_f4 wev[P];
     load_v(0, vb);
     load_b(0, bfr);
-    ballots(0, vb, S.sMask[0]);
+    int nxt_cnt = ballots(0, vb, 0);                         // this wave's flips in the tile ahead
     if (ntile > 1) load_v(1, vb);
+    load_we(0, 0, 0, nxt_cnt, wev);                          // the wave's own list: ordered by the wave's own LDS queue
     __syncthreads();
-    build_list(0);
-    __syncthreads();
-    load_we(0, 0, 0, wev);
 
-    // epilogue ownership: thread -> row n = tid >> 3, columns 4 (tid & 7) + k
+    // epilogue ownership: thread -> row n = tid >> 3 (one of its wave's rows), columns 4 (tid & 7) + k
     const int en = tid >> 3, ed0 = 4 * (tid & 7), erow = rb + en;
     const bool evalid = erow < N;
     const int err = evalid ? erow : N - 1;
@@ -295,103 +301,69 @@ nade_fwd_mfma_body(int tracks, int N, int D, const uint8_t* __restrict__ v, long
         __builtin_amdgcn_sched_barrier(0);
         nm_logit_tile<SPLIT>(S.sH, w, lane, bfr, S.sLb);
         if (c + 1 < ntile) {
-            ballots(c + 1, vb, S.sMask[nbuf]);               // v bytes requested one tile ago
+            nxt_cnt = ballots(c + 1, vb, nbuf);              // v bytes requested one tile ago
             if (c + 2 < ntile) load_v(c + 2, vb);
         }
         NM_T(0);
-        hf_lds_barrier();                                     // B1: sLb complete, sH consumed, next masks written
+        hf_lds_barrier();                                     // B1: sLb complete, sH consumed, the waves' counts written
         NM_T(1);
-        const int F = (int)S.sSb[buf][32];
+        // every wave's count of the tile: the wave's first slot and the tile's total, as scalars
+        const int cntv = (int)S.sCnt[buf][lane & 3];
+        const int c0 = __builtin_amdgcn_readlane(cntv, 0), c1 = __builtin_amdgcn_readlane(cntv, 1), c2 = __builtin_amdgcn_readlane(cntv, 2),
+                  c3 = __builtin_amdgcn_readlane(cntv, 3);
+        const int F = c0 + c1 + c2 + c3;
+        const int wbase = (w > 0 ? c0 : 0) + (w > 1 ? c1 : 0) + (w > 2 ? c2 : 0);
+        const int wcnt = w == 0 ? c0 : w == 1 ? c1 : w == 2 ? c2 : c3;
         const unsigned mk = S.sMask[buf][en];
+        const int sb = wbase + (int)S.sSb[buf][en];          // slot of the row's first flip
         float lsel[4];                                       // the logit of each of this thread's 4 (row, column) pairs
-        int jj[4];
+        int slot_of[4];                                      // slot of the state each pair uses: the row's latest flip before the column
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            jj[k] = __popc(mk & ((1u << (ed0 + k)) - 1u));   // flips of this row strictly before the column
+            const int jj = __popc(mk & ((1u << (ed0 + k)) - 1u));               // flips of this row strictly before the column
+            slot_of[k] = jj > 0 ? sb + jj - 1 : -1;
             lsel[k] = S.sLb[en][ed0 + k];
         }
-        int slot_of[4];                                      // slot of the state each pair uses: pass jj-1, rank of the row among that pass's rows
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int pj = max(jj[k] - 1, 0);
-            slot_of[k] = jj[k] > 0 ? (int)S.sPs[buf][pj] + __popc(S.sAct[buf][pj] & ((1u << en) - 1u)) : -1;
-        }
         for (int k0 = 0; k0 < F; k0 += 32) {
-            // ---- S1: the chunk's flips in pass order: a[row] += w_enc[d]; new state -> sF[slot] and the row's current state.
-            //      Eight at a time: within a pass the rows are distinct (and ascending), so the eight read-modify-writes of
-            //      sA are issued together and the in-order VALU sees eight independent chains.
-            if (k0 > 0) load_we(c, buf, k0, wev);            // rare: more than 32 flips in one tile
-            const int cnt = min(32, F - k0);
-            const int flv = (int)S.sFl[buf][min(k0 + (lane & 31), F - 1)];       // the chunk's list entries, one per lane (see load_we)
+            // ---- S1: the wave's flips whose slots lie in this chunk (j = index among the wave's flips of the tile, slot = wbase + j), in
+            //      row-major order: a[row] += w_enc[d]; new state -> sF[slot] and the row's current state.  P at a time, the first P of a
+            //      tile from the rows fetched a tile ahead.
+            const int jhi = min(k0 + 32 - wbase, wcnt);
+            for (int jb = max(k0 - wbase, 0); jb < jhi; jb += P) {
+                if (jb > 0) load_we(c, buf, jb, jhi, wev);   // beyond the prefetched rows (or a second chunk): fetched in place
+                const int cnt = jhi - jb;
+                const int flv = (int)S.sFl[buf][w][min(jb + (lane & 15), jhi - 1)];      // the batch's list entries, one per lane (see load_we)
 #pragma unroll
-            for (int u0 = 0; u0 < 32; u0 += 8) {
-                if (u0 < cnt) {
-                    int n[8];
+                for (int u0 = 0; u0 < P; u0 += 4) {
+                    if (u0 < cnt) {
+                        // One flip after the other, in list order (a row may appear more than once), each under its own wave-uniform branch:
+                        // two 64-bit indexed reads, two packed adds, two 64-bit indexed writes (in place: the branch costs no register copies),
+                        // then four sigmoids and state words.  (Four flips interleaved without branches -- entries past the count adding 0 to
+                        // the last flip's row -- cost four selects per flip and measured the same: the flip pass is bound by its 8
+                        // transcendentals and ~45 other instructions per flip, and the other workgroup's wave fills the latencies.)
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) n[i] = __builtin_amdgcn_readlane(flv, u0 + i) >> 5;
-                    if constexpr (SPLIT) {
-                        // pre-activations in registers: the read-modify-writes of the batch run in list order (a row may appear twice in a
-                        // batch that straddles two passes), each a register move with a wave-uniform index and one add; the eight sigmoids
-                        // are independent of each other; entries past the count add 0 to the row of the last flip.  Kept free of branches
-                        // so that the indexed writes happen in place (a conditional write made the compiler copy all 32 registers per flip)
-                        float x[8];
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            x[i] = areg[n[i]] + ((u0 + i < cnt) ? wev[u0 + i] : 0.f);
-                            areg[n[i]] = x[i];
-                        }
-                        state_t hb[8];
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) hb[i] = nm_state<SPLIT>(fast_sigmoid(x[i]));
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) {
+                        for (int i = 0; i < 4; ++i) {
                             if (u0 + i < cnt) {
-                                S.sF[u0 + i][tid] = hb[i];
-                                S.sH[n[i]][tid] = hb[i];
-                            }
-                        }
-                    } else {
-                        bool indep = u0 + 8 <= cnt;          // a full batch inside one pass: rows strictly ascending, hence distinct
-#pragma unroll
-                        for (int i = 0; i < 7; ++i) indep = indep && n[i] < n[i + 1];
-                        if (indep) {
-                            float x[8];
-#pragma unroll
-                            for (int i = 0; i < 8; ++i) x[i] = S.sA[n[i]][tid];
-#pragma unroll
-                            for (int i = 0; i < 8; ++i) x[i] += wev[u0 + i];
-                            state_t hb[8];
-#pragma unroll
-                            for (int i = 0; i < 8; ++i) hb[i] = nm_state<SPLIT>(fast_sigmoid(x[i]));
-#pragma unroll
-                            for (int i = 0; i < 8; ++i) {
-                                S.sA[n[i]][tid] = x[i];
-                                S.sF[u0 + i][tid] = hb[i];
-                                S.sH[n[i]][tid] = hb[i];
-                            }
-                        } else {
-#pragma unroll
-                            for (int i = 0; i < 8; ++i) {
-                                if (u0 + i < cnt) {
-                                    const float av = S.sA[n[i]][tid] + wev[u0 + i];
-                                    S.sA[n[i]][tid] = av;
-                                    const state_t hb1 = nm_state<SPLIT>(fast_sigmoid(av));
-                                    S.sF[u0 + i][tid] = hb1;
-                                    S.sH[n[i]][tid] = hb1;
-                                }
+                                const int r = __builtin_amdgcn_readlane(flv, u0 + i) >> 5;
+                                const nm_f2 p01 = __builtin_bit_cast(nm_f2, a01[r]), p23 = __builtin_bit_cast(nm_f2, a23[r]);
+                                const float x[4] = {p01[0] + wev[u0 + i][0], p01[1] + wev[u0 + i][1], p23[0] + wev[u0 + i][2], p23[1] + wev[u0 + i][3]};
+                                a01[r] = pair_of(x[0], x[1]); a23[r] = pair_of(x[2], x[3]);
+                                __builtin_amdgcn_sched_barrier(0);        // the four indexed moves of the write stay adjacent: one index-mode pair, not three
+                                const state4_t hb = state4(x);
+                                *reinterpret_cast<state4_t*>(&S.sF[wbase + jb + u0 + i - k0][4 * lane]) = hb;
+                                *reinterpret_cast<state4_t*>(&S.sH[8 * w + r][4 * lane]) = hb;
                             }
                         }
                     }
                 }
             }
             NM_T(2);
-            if (k0 == 0 && c + 1 < ntile) build_list(nbuf);
             NM_T(3);
-            hf_lds_barrier();                                 // B2: sF complete (and the next tile's list)
+            hf_lds_barrier();                                 // B2: sF complete
             NM_T(4);
             // ---- S2: flip logits; each pair whose state sits in this chunk picks its logit ----
             nm_logit_tile<SPLIT>(S.sF, w, lane, bfr, S.sLf);
-            if (k0 == 0 && F <= 32 && c + 1 < ntile) load_we(c + 1, nbuf, 0, wev);     // behind the MFMAs: the next tile's encoder rows
+            if (k0 + 32 >= F && c + 1 < ntile) load_we(c + 1, nbuf, 0, nxt_cnt, wev);    // behind the tile's last MFMAs: the next tile's encoder rows
             NM_T(5);
             hf_lds_barrier();                                 // B3: sLf ready
             NM_T(6);
@@ -401,12 +373,9 @@ nade_fwd_mfma_body(int tracks, int N, int D, const uint8_t* __restrict__ v, long
                 if (slot_of[k] >= 0 && slot >= 0 && slot < 32) lsel[k] = S.sLf[slot][ed0 + k];
             }
         }
-        if (F == 0 && c + 1 < ntile) {                       // no flip in this tile: the bookkeeping of the loop body still has to happen
-            build_list(nbuf);
+        if (F == 0 && c + 1 < ntile) {                       // no flip in this tile: sLb, the masks and the counts are still read; the next S0 writes them
             hf_lds_barrier();
-            load_we(c + 1, nbuf, 0, wev);
-        } else if (F > 32 && c + 1 < ntile) {
-            load_we(c + 1, nbuf, 0, wev);                    // the extra chunks overwrote the prefetched values
+            load_we(c + 1, nbuf, 0, nxt_cnt, wev);
         }
         // b_dec of this tile (requested at its top) is waited for HERE, in front of the w_dec request: the wait the compiler puts in front of
         // the pointwise must hold on every path that reaches it (also the last tile's, which requests nothing), so it is `vmcnt(3)` -- placed
@@ -460,8 +429,10 @@ nade_fwd_mfma_body(int tracks, int N, int D, const uint8_t* __restrict__ v, long
     if ((tid & 7) == 0 && evalid && nll != nullptr) nll[(size_t)m * N + erow] = -lp;
     if (a_final != nullptr) {
 #pragma unroll
-        for (int n = 0; n < 32; ++n)
-            if (rb + n < N) NM_ST1(&a_final[((size_t)m * N + rb + n) * Hn + tid], SPLIT ? areg[SPLIT ? n : 0] : S.sA[SPLIT ? 0 : n][tid]);
+        for (int r = 0; r < 8; ++r)
+            if (rb + 8 * w + r < N)
+                __builtin_nontemporal_store(__builtin_shufflevector(__builtin_bit_cast(nm_f2, a01[r]), __builtin_bit_cast(nm_f2, a23[r]), 0, 1, 2, 3),
+                                            reinterpret_cast<nm_f4u*>(&a_final[((size_t)m * N + rb + 8 * w + r) * Hn + 4 * lane]));
     }
 }
 
@@ -503,6 +474,7 @@ static int nm_launch(mnn_stream_t s, int tracks, int N, int D, int Hn, const uin
     MNN_REQUIRE(ld_bias >= tracks * (Hn + D), "mnn_nade_logprob_fwd_mfma: ld_bias %d < tracks*(Hn+D)", ld_bias);
     MNN_REQUIRE(d_bias == nullptr || row_weight != nullptr, "mnn_nade_logprob_fwd_mfma: d_bias needs row_weight");
     MNN_REQUIRE(((uintptr_t)w_dec16 & 15) == 0, "mnn_nade_logprob_fwd_mfma: the 16-bit decoder weights must be 16-byte aligned");
+    static_assert(sizeof(NadeFwdSmemT<SPLIT>) <= 80 * 1024, "two workgroups share a CU's 160 KB of LDS");
     static MnnPerDeviceOnce raised;                            // (per SPLIT: this function is instantiated once per form)
     MNN_HIP(mnn_once_per_device(raised, [] { return mnn_raise_dynamic_lds((const void*)nade_fwd_mfma_kernel<SPLIT>, (int)sizeof(NadeFwdSmemT<SPLIT>)); }));
     dim3 grid(cdiv(N, 32), tracks);

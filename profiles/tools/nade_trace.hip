@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <vector>
 void mnn_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fprintf(stderr, "\n"); }
+hipError_t mnn_current_device(int* dev) { return hipGetDevice(dev); }      // host_support.h (the library's lives in elementwise.hip)
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s line %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
 int main(int argc, char** argv) {
     const int N = (argc > 1 ? atoi(argv[1]) : 32768), D = 440, Hn = 256, ld = Hn + D;
@@ -28,7 +29,7 @@ int main(int argc, char** argv) {
 #endif
         CK(hipEventRecord(e0));
 #ifdef SPLIT_FORM      // the fp16 mode's split-operand form (f16 hi + lo decoder weights, 4 bytes per weight, zeros here)
-        if (mnn_nade_logprob_fwd_mfma_f32(nullptr, 1, N, D, Hn, v, (long)N * D, bias, ld, we, wdp, rw, nll, cp, db, af, nullptr, 0)) return 1;
+        if (mnn_nade_logprob_fwd_mfma_f32(nullptr, 1, N, D, Hn, v, (long)N * D, bias, ld, we, wdp, rw, nll, cp, db, af, nullptr, 0, nullptr)) return 1;
 #else
         if (mnn_nade_logprob_fwd_mfma(nullptr, 1, N, D, Hn, v, (long)N * D, bias, ld, we, wd, rw, nll, cp, db, af)) return 1;
 #endif
@@ -38,7 +39,7 @@ int main(int argc, char** argv) {
         CK(hipMemcpyFromSymbol(z, HIP_SYMBOL(nm_trace), sizeof(z)));
 #endif
         printf("fwd %.3f ms; block phases (us):", ms);
-        const char* names[9] = {"S0 base logits + ballots", "B1", "S1 flips", "list (wave 0)", "B2", "S2 flip logits + w_enc requests", "B3", "select + w_dec requests", "S3 pointwise + stores"};
+        const char* names[9] = {"S0 base logits + ballots", "B1", "S1 flips (wave 0's rows)", "list (none: every wave lists its rows with the ballots)", "B2", "S2 flip logits + w_enc requests", "B3", "select + w_dec requests", "S3 pointwise + stores"};
         for (int k = 0; k < 9; ++k) printf(" [%s]=%.1f", names[k], z[k] * 0.01);
         printf("\n");
     }
