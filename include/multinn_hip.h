@@ -451,6 +451,30 @@ int mnn_nade_sample_multi_temps(mnn_stream_t s, int njobs, const mnn_nade_sample
 /* ... with polyphony caps (mnn_caps: one, or job j's own; NULL = mnn_nade_sample_multi_temps, which calls this) */
 int mnn_nade_sample_multi_caps(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, const mnn_temps* temps,
                                const mnn_caps* caps, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride);
+/* The polyphony cap by REJECTION: the entry points that end in _redraw / _redraw_at (added without a version bump; the _caps entry points are
+ * wrappers that pass NULL).  With tries = R > 0 and a cap that can bind, the scan of a row runs in attempts.  Attempt 0 is the uncapped scan
+ * on its own uniforms (stream MNN_STREAM_NADE), except that a FREE visible drawn 1 while its counter is exhausted is a violation: the
+ * attempt is abandoned there and the row starts the next one from the step's initial state and zero counts.  Attempts 1 .. R - 1 do the same
+ * on fresh uniforms; attempt R, the last, is the truncating scan of mnn_caps on its uniforms and never abandons (a row that meets a violation
+ * there is a fallback).  Attempt a >= 1 reads stream MNN_STREAM_NADE_REDRAW at the same row and sub-counter (sub + *sub_base) and element
+ * (a - 1) E4 + e, where e is the element attempt 0 reads and E4 the launch's element count -- tracks * D (mnn_nade_sample_redraw_at, the
+ * scans), D per job (mnn_nade_sample_multi_redraw) -- rounded up to a multiple of 4.  A row that never violates returns the uncapped bits; an
+ * accepted row is an exact draw from the (clamped, tempered) ancestral distribution restricted to "no free 1 past a cap".  Given cells are as
+ * with mnn_caps and never a violation; nll stays the model's own for the emitted vector.  Threshold draws (temps n = 0) cannot be redrawn:
+ * tries > 0 with them is refused.  redraw NULL, tries == 0, or a launch in which no counter can run out: the _caps call, launch for launch.
+ * stats: NULL, or two u32 on the device that the kernels ADD to (the caller zeroes them): [0] scans (row x track / job) redrawn at least once,
+ * [1] fallback scans. */
+enum { MNN_STREAM_NADE_REDRAW = 10 };
+typedef struct {
+    int tries;               /* R: 0..255 */
+    uint32_t* stats;         /* device, or NULL */
+} mnn_redraw;
+int mnn_nade_sample_redraw_at(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
+                              const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed, uint32_t row0, uint32_t sub,
+                              uint8_t* samples, long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given,
+                              const uint32_t* sub_base, const mnn_redraw* redraw);
+int mnn_nade_sample_multi_redraw(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, const mnn_temps* temps,
+                                 const mnn_caps* caps, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride, const mnn_redraw* redraw);
 
 /* ------------------------------------------------------------------------------------------
  * RBM (models/common/rbm.py).  W f32 [D,Hn]; bh f32 [N or 1, Hn] (ld_bh = 0 broadcasts one row);
@@ -754,6 +778,19 @@ int mnn_generate_scan_chunk_caps(mnn_stream_t s, int B, int n_intro, int num_ste
                                  uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given,
                                  const float* const* c_in, const float* const* h_in, float* const* c_out, float* const* h_out, uint32_t step0,
                                  const uint32_t* step_base);
+/* ... and with redraws (mnn_redraw, above) on every sample call of the scan; redraw NULL or tries == 0: the _caps entry points, which call
+ * these.  The statistics add up over the steps. */
+int mnn_generate_scan_redraw(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                             const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D, int Hn,
+                             const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed, uint32_t row0,
+                             uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0,
+                             const float* const* h0, const mnn_redraw* redraw);
+int mnn_generate_scan_chunk_redraw(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                   const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
+                                   int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed,
+                                   uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given,
+                                   const float* const* c_in, const float* const* h_in, float* const* c_out, float* const* h_out, uint32_t step0,
+                                   const uint32_t* step_base, const mnn_redraw* redraw);
 
 /* ------------------------------------------------------------------------------------------
  * Data-parallel exchange (the gradients of utils/training.py:151-177 as ONE flat f32 buffer): RCCL over xGMI, one

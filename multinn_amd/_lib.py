@@ -93,6 +93,11 @@ class Caps(C.Structure):
     _fields_ = [("n", _i), ("by_visible", _i), ("cap", C.c_int32 * 8)]
 
 
+class Redraw(C.Structure):
+    """mnn_redraw (include/multinn_hip.h)."""
+    _fields_ = [("tries", _i), ("stats", _p)]
+
+
 class RbmGibbsJob(C.Structure):
     """mnn_rbm_gibbs_job (include/multinn_hip.h)."""
     _fields_ = [("W", _p), ("bh", _p), ("bv", _p), ("seed", _u64), ("v0", _p), ("p_v", _p), ("v_out", _p), ("given", _p)]
@@ -201,7 +206,13 @@ SIGNATURES["mnn_nade_sample_caps_at"] = _with_caps("mnn_nade_sample_temps_at", 9
 SIGNATURES["mnn_nade_sample_multi_caps"] = _with_caps("mnn_nade_sample_multi_temps", 6)
 SIGNATURES["mnn_generate_scan_caps"] = _with_caps("mnn_generate_scan_temps", 16)
 SIGNATURES["mnn_generate_scan_chunk_caps"] = _with_caps("mnn_generate_scan_chunk", 16)
+# the cap by rejection (additions without a version bump): the _caps entry points with a trailing const mnn_redraw*
+SIGNATURES["mnn_nade_sample_redraw_at"] = (_i, SIGNATURES["mnn_nade_sample_caps_at"][1] + [_p])
+SIGNATURES["mnn_nade_sample_multi_redraw"] = (_i, SIGNATURES["mnn_nade_sample_multi_caps"][1] + [_p])
+SIGNATURES["mnn_generate_scan_redraw"] = (_i, SIGNATURES["mnn_generate_scan_caps"][1] + [_p])
+SIGNATURES["mnn_generate_scan_chunk_redraw"] = (_i, SIGNATURES["mnn_generate_scan_chunk_caps"][1] + [_p])
 TEMPS_MAX = 8              # MNN_TEMPS_MAX
+REDRAWS_MAX = 255          # mnn_redraw.tries
 
 _lib = None
 

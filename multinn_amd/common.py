@@ -149,21 +149,22 @@ class ScanGraphs:
         return out.clone()
 
     @staticmethod
-    def generate(owner, key, x, num_steps, given, temperature, scan, stale, max_notes=None):
+    def generate(owner, key, x, num_steps, given, temperature, scan, stale, max_notes=None, redraws=0):
         """The one capture wrapper of a `generate`: scan(x, num_steps, given, temperature) eagerly where graphs are off, else one replay of
         the scan captured under key + ("given",) + temperature_key (a new given of the same shape replays the same graph; the temperature
         is baked into the captured launches, nothing at 1.0: the scan captured without it) from the cache kept on `owner`.  max_notes (a
-        normalised polyphony cap; None: the call, the key and the captured scan without one): a fifth argument of scan, and max_notes_key.  stale(): mark
+        normalised polyphony cap; None: the call, the key and the captured scan without one): a fifth argument of scan, and max_notes_key;
+        redraws (normalised, sampling_redraws; 0: nothing changes): a sixth argument of scan, and redraws_key.  stale(): mark
         the owner's packed weight copies stale -- before the capture (the graph packs them itself: a replay always sees the current
         weights) and after it (the packed copies then live in the graph's pool).  The warm-up is the scan's first min(num_steps, 2) steps."""
-        cap = () if max_notes is None else (max_notes,)
+        cap = () if max_notes is None else ((max_notes,) if not redraws else (max_notes, redraws))
         if not ScanGraphs.enabled(x):
             return scan(x, num_steps, given, temperature, *cap)
         if getattr(owner, "_scan_graphs", None) is None:
             owner._scan_graphs = ScanGraphs()
         if given is not None:
             key = key + ("given",)
-        key = key + temperature_key(temperature) + max_notes_key(max_notes)
+        key = key + temperature_key(temperature) + max_notes_key(max_notes) + redraws_key(redraws)
 
         def captured(sx, sg=None):
             stale()
@@ -348,6 +349,49 @@ def sampling_max_notes(max_notes, num_tracks=None, num_dims=None, collapse=True,
 def max_notes_key(max_notes):
     """What a scan-graph key gains from a (normalised) cap: nothing at None -- the key, and the captured scan, of a call without one."""
     return () if max_notes is None else (("max_notes", max_notes),)
+
+
+# --------------------------------------------------------------------------------------------
+# The cap by rejection.  With `redraws=R` a row whose step would emit a 1 past a cap is thrown away and drawn again, at most R times, before
+# the truncating scan of `max_notes` serves it (ops.nade_sample: `redraws`): an accepted row is an exact draw from the step distribution
+# restricted to the caps.  R stands beside max_notes wherever that is accepted and means nothing without it.
+MAX_REDRAWS = 255
+
+
+def sampling_redraws(redraws, max_notes, temperature, what="redraws"):
+    """The one normalisation of a `redraws` argument, on the host, before any device work: an integer 0..MAX_REDRAWS.  max_notes: the
+    NORMALISED cap of the call -- None: nothing can be violated, and the result is 0 (the kernels, bits and captured scans of a call
+    without the argument).  A bool, a non-integer, a value out of range, or redraws > 0 under threshold decoding (temperature None: a
+    redraw would emit the same vector again) raise ValueError."""
+    import numbers
+    if isinstance(redraws, bool) or not isinstance(redraws, numbers.Integral) or not 0 <= redraws <= MAX_REDRAWS:
+        raise ValueError(f"{what} must be an integer 0..{MAX_REDRAWS}, got {redraws!r}")
+    if redraws > 0 and temperature is None:
+        raise ValueError(f"{what} > 0 needs a temperature: threshold decoding (temperature=None) would emit the same vector again")
+    return 0 if max_notes is None else int(redraws)
+
+
+def redraws_key(redraws):
+    """What a scan-graph key gains from (normalised) redraws: nothing at 0 -- the key, and the captured scan, of a call without them."""
+    return (("redraws", redraws),) if redraws else ()
+
+
+def redraw_cell(owner, device):
+    """A generator's static statistics cell, int32[2] on the device: (scans redrawn at least once, fallback scans) of its last generate call or
+    session chunk.  Created once per owner and device (before any capture: the warm-up of a captured scan runs first)."""
+    cell = getattr(owner, "_redraw_stats", None)
+    if cell is None or cell.device != torch.device(device):
+        cell = owner._redraw_stats = torch.zeros(2, dtype=torch.int32, device=device)
+    return cell
+
+
+def redraw_counts(owner):
+    """(redrawn, fallback) of the owner's last generate call or session chunk, as ints (scans: row x track x step); synchronises.  (0, 0)
+    where that call ran without redraws: the cell was not written, and is not read."""
+    if not getattr(owner, "_redraw_live", False):
+        return 0, 0
+    n = owner._redraw_stats.cpu()
+    return int(n[0]), int(n[1])
 
 
 # --------------------------------------------------------------------------------------------

@@ -844,6 +844,21 @@ __device__ __forceinline__ void sample_caps_take(CapCount& cc, int t) {     // a
     }
 }
 
+// The redraws of a launch (the REDRAW instantiations' argument behind the caps; nothing otherwise, like SampleNoCaps).  tries: attempts that
+// may be abandoned before the last, truncating one; eq: Philox blocks per attempt on MNN_STREAM_NADE_REDRAW (the launch's element count
+// rounded up to a multiple of 4, over 4): attempt a >= 1 reads element (a - 1) 4 eq + e where attempt 0 reads e; stats: NULL or two counters
+// on the device, [0] scans redrawn at least once, [1] scans whose last attempt truncated.
+struct SampleRedraw { int tries; uint32_t eq; uint32_t* stats; };
+struct SampleNoRedraw {};
+template <bool REDRAW> struct SampleRedrawArg { typedef SampleNoRedraw T; };
+template <> struct SampleRedrawArg<true> { typedef SampleRedraw T; };
+__device__ __forceinline__ void sample_redraw_count(const SampleRedraw& RD, int lane, int att, bool fell) {     // one lane of the scan's wave
+    if (RD.stats != nullptr && lane == 0 && att > 0) {
+        atomicAdd(RD.stats, 1u);
+        if (fell) atomicAdd(RD.stats + 1, 1u);
+    }
+}
+
 // TMODE: 0 = threshold draws (temperature None / <= 0), 1 = temperature 1, 2 = any other temperature: the table TT, per job or per visible.
 // FULL: Hn == 256, no lane is idle.
 // GIVEN: conditional sampling -- a visible whose code in job.given is 0 / 1 is not drawn, its value is written and fed forward like a draw
@@ -853,11 +868,16 @@ __device__ __forceinline__ void sample_caps_take(CapCount& cc, int t) {     // a
 // session's chunk, so that a captured chunk replays at any position of the piece (mnn_nade_sample_temps_at).
 // CAP (with GIVEN: a job without codes has every visible free): polyphony caps -- a free visible whose counter (SampleCaps) is exhausted is a
 // settled 0: not drawn, its uniform unused, its logit parked like any other; every one that is emitted, given or drawn, is counted.
-template <int TMODE, bool FULL, bool SPEC, bool GIVEN, bool CAP = false>
+// REDRAW (with CAP, TMODE 1 / 2): the cap by rejection.  A free visible whose counter is exhausted IS drawn, from the uniform of the uncapped
+// scan; a 1 there is a violation: the wave abandons the attempt at that visible and scans the row again from b_enc and zero counts on the next
+// attempt's uniforms (SampleRedraw) -- a counted loop, at most tries + 1 scans.  The last attempt emits the 0 in place of the violation, which is
+// the scan without REDRAW on that attempt's uniforms.  The four waves of a workgroup restart on their own: the kernel has no workgroup barrier.
+template <int TMODE, bool FULL, bool SPEC, bool GIVEN, bool CAP = false, bool REDRAW = false>
 __global__ void __launch_bounds__(256)
 nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t row0, uint32_t sub_arg, long s_row_stride, int s_elem_stride,
-                   const uint32_t* __restrict__ sub_base, typename SampleCapsArg<CAP>::T CC) {
+                   const uint32_t* __restrict__ sub_base, typename SampleCapsArg<CAP>::T CC, typename SampleRedrawArg<REDRAW>::T RD) {
     static_assert(GIVEN || !CAP, "the capped scan reads the codes");
+    static_assert(!REDRAW || (CAP && TMODE != 0), "a redraw needs a cap to violate and fresh uniforms to draw again");
     // per wave: logit / log term [Dp] f32, b_dec [Dp] f32, draws [Dp] u8, 256 uniforms (, GIVEN: the row's codes [Dp] u8) (, TMODE 2: 8 temperatures)
     extern __shared__ __attribute__((aligned(16))) unsigned char nade_sample_smem[];
     uint32_t sub = sub_arg;                                 // SUB_BASE: the Philox sub-counter; the base is added in front of the first refill
@@ -882,7 +902,7 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t 
     const float* __restrict__ we = jb.w_enc;
     const float* __restrict__ wd = jb.w_dec;
     const float* __restrict__ bd = bias + (size_t)row * ld_bias + jb.dec_off;
-    float a[4], h[4];
+    float a[4], h[4], a0[4];                                // (a0, REDRAW: the row's b_enc, what a restart restores -- kept, never reloaded under a branch)
     bool in[4];
     int off[4];                                             // hidden index of (lane, q), 0 where there is none: loads are never predicated
 #pragma unroll                                              // (a load under a branch is waited for right behind it -- the ring would be no ring)
@@ -891,6 +911,7 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t 
         off[q] = in[q] ? lane + 64 * q : 0;
         const float av = bias[(size_t)row * ld_bias + jb.enc_off + off[q]];
         a[q] = in[q] ? av : 0.f;
+        a0[q] = a[q];
         h[q] = det_sigmoid(a[q]);
     }
     constexpr int RING = 8;                                 // visibles in flight: RING x (time per visible) must cover an L2 round trip
@@ -915,9 +936,10 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t 
     }
     const uint32_t e0 = jb.elem0;                           // element index of visible 0 (RNG contract: elem = m D + i)
     uint32_t b0 = e0 >> 2;                                  // lane l holds the uniforms of Philox block b0 + l
+    uint32_t rstream = MNN_STREAM_NADE, rblock = 0;         // REDRAW: the attempt's stream and first block (constants otherwise)
     auto refill = [&]() {                                   // lane l: the four uniforms of Philox block b0 + l, parked in LDS (one broadcast read per visible)
         float u4[4];
-        philox_uniform4(seed, MNN_STREAM_NADE, row0 + (uint32_t)row, sub, b0 + (uint32_t)lane, u4);
+        philox_uniform4(seed, rstream, row0 + (uint32_t)row, sub, rblock + b0 + (uint32_t)lane, u4);
         *reinterpret_cast<float4*>(su + 4 * lane) = make_float4(u4[0], u4[1], u4[2], u4[3]);
     };
     // SUB_BASE: one wave-uniform (scalar) read, HERE and not at the top of the kernel.  At the top the compiler puts the load of the pointer,
@@ -955,11 +977,16 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t 
     };
     float u_cur = TMODE != 0 ? uniform_of(0) : 0.f;
     float acc = dot(0);
-    for (int i0 = 0; i0 < D; i0 += RING) {
+    int tries = 0, att = 0;                                 // REDRAW: the attempt; without it the loop below is one pass
+    bool fell = false;                                      // the last attempt met a violation: the emitted row is the truncated one
+    if constexpr (REDRAW) tries = RD.tries;
+    for (att = 0; att <= tries; ++att) {
+    bool viol = false;
+    for (int i0 = 0; i0 < D && !(REDRAW && viol); i0 += RING) {
 #pragma unroll
         for (int k = 0; k < RING; ++k) {
             const int i = i0 + k;
-            if (i < D) {                                    // uniform
+            if (i < D && !(REDRAW && viol)) {               // uniform (REDRAW: an abandoned attempt decides nothing more)
                 // speculation: if this draw is 0 the hidden state does not change, and visible i + 1's dot product is this one -- it has
                 // no dependence on the sigmoid / draw chain below and fills its issue slots (a draw of 1 recomputes it)
                 const float spec = SPEC ? dot((k + 1) % RING) : 0.f;
@@ -968,10 +995,17 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t 
                 bool on;
                 if (GIVEN && code != 255) {                 // clamped: the given value moves a / h like a draw (and the speculation holds as for one)
                     on = code != 0;
-                } else if (CAP && ((cc.ex >> cix) & 1) != 0) {     // capped: a settled 0, nothing is drawn (the speculation holds as for a drawn 0)
+                } else if (CAP && !REDRAW && ((cc.ex >> cix) & 1) != 0) {     // capped: a settled 0, nothing is drawn (the speculation holds as for a drawn 0)
                     on = false;
                 } else if (TMODE != 0) {
-                    on = draw_below(u_cur, TMODE == 1 ? l : l / t_cur);
+                    on = draw_below(u_cur, TMODE == 1 ? l : l / t_cur);     // (REDRAW: a capped visible is drawn like any other, ties included)
+                    if constexpr (REDRAW) {
+                        if (on && ((cc.ex >> cix) & 1) != 0) {     // uniform: a 1 past the cap
+                            viol = att < tries;             // abandoned here: what this visible still writes below is scanned over by the next attempt
+                            fell = !viol;                   // the last attempt truncates
+                            on = false;
+                        }
+                    }
                 } else {
                     on = prob_at_least_half(l);              // nade.py:278-279
                 }
@@ -1000,6 +1034,33 @@ nade_sample_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t 
             __builtin_amdgcn_sched_barrier(0);
         }
     }
+    if (!REDRAW || !viol) break;
+    if constexpr (REDRAW) {                                 // the next attempt: the step's initial state, zero counts, its own uniforms, the ring from visible 0
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            a[q] = a0[q];
+            h[q] = det_sigmoid(a[q]);
+        }
+        sample_caps_init(CC, (int)blockIdx.y, cc);
+        cix = 0;
+        if (TMODE == 2) {
+            tix = TT.by_visible ? 0 : (int)blockIdx.y;
+            t_cur = stt[tix];
+        }
+        rstream = MNN_STREAM_NADE_REDRAW;
+        rblock = (uint32_t)att * RD.eq;                     // attempt att + 1 starts at element att * (4 eq)
+        b0 = e0 >> 2;
+        refill();
+#pragma unroll
+        for (int k = 0; k < RING; ++k) {
+            fetch(k, k);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        u_cur = uniform_of(0);
+        acc = dot(0);
+    }
+    }
+    if constexpr (REDRAW) sample_redraw_count(RD, lane, att, fell);
     // after the scan: samples out, log terms 64 at a time, then their sum in visible order (LDS operations of one wave execute in order)
     for (int i = lane; i < D; i += 64) {
         const float p = det_sigmoid(sp[i]);
@@ -1043,11 +1104,16 @@ extern "C" int mnn_sch_trace_read(long long* host) { return hipMemcpyFromSymbol(
 // CAP: as nade_sample_kernel.  At the top of a pass the free lanes whose counter is exhausted are forced to 0 and, like clamped lanes, kept out of
 // the tie ballot; the first 1 of the pass is counted before the re-evaluation behind it (the lanes behind it are discarded anyway, so the counts
 // taken at the top of the pass are exact for every lane that is kept).
-template <int TMODE, bool FULL, int G, bool GIVEN, bool CAP = false>
+// REDRAW: as nade_sample_kernel.  The capped free lanes are compared like the others (and stand in the tie ballot); a violation is an open one of
+// them whose comparison says 1 and whose visible lies before the first kept 1 of the pass -- up to there the counts taken at the top of the pass
+// are exact, by the argument above.  A restart first drains the ring (no LDS write of the new attempt may race a copy in flight), then stages
+// NB - 1 chunks again: chunk 0 meets the constant WAITN as it did the first time.
+template <int TMODE, bool FULL, int G, bool GIVEN, bool CAP = false, bool REDRAW = false>
 __global__ void __launch_bounds__(64)
 nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uint32_t row0, uint32_t sub_arg, long s_row_stride, int s_elem_stride,
-                   const uint32_t* __restrict__ sub_base, typename SampleCapsArg<CAP>::T CC) {
+                   const uint32_t* __restrict__ sub_base, typename SampleCapsArg<CAP>::T CC, typename SampleRedrawArg<REDRAW>::T RD) {
     static_assert(GIVEN || !CAP, "the capped scan reads the codes");
+    static_assert(!REDRAW || (CAP && TMODE != 0), "a redraw needs a cap to violate and fresh uniforms to draw again");
     constexpr int NB = sch_nb(G);
     constexpr int KSH = G == 16 ? 2 : 3;                      // lane l decides visible l >> KSH of the chunk
     constexpr int WAITN = (NB - 2) * 2 * G;                   // copies that may still be in flight when a chunk is needed: the NB - 2 chunks behind it
@@ -1104,7 +1170,7 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
             __builtin_amdgcn_global_load_lds((nade_gas_ptr_t)(we + (size_t)ii * Hn + src_off), (nade_lds_ptr_t)(ring + ((b * 2 + 1) * G + k) * 256), 16, 0, 0);
         }
     };
-    float a[4], h[4];
+    float a[4], h[4], a0[4];                                 // (a0, REDRAW: what a restart restores)
     bool in[4];
     int off[4];
 #pragma unroll
@@ -1113,6 +1179,7 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
         off[q] = in[q] ? lane + 64 * q : 0;
         const float av = bias[(size_t)row * ld_bias + jb.enc_off + off[q]];
         a[q] = in[q] ? av : 0.f;
+        a0[q] = a[q];
         h[q] = det_sigmoid(a[q]);
     }
     for (int i = lane; i < D; i += 64) sbd[i] = bd[i];
@@ -1122,9 +1189,10 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
     }
     const uint32_t e0 = jb.elem0;
     uint32_t b0 = e0 >> 2;
+    uint32_t rstream = MNN_STREAM_NADE, rblock = 0;          // REDRAW: the attempt's stream and first block (constants otherwise)
     auto refill = [&]() {                                    // (an LDS write waits for every copy in flight -- the compiler cannot tell them apart: once per ~31 chunks)
         float u4[4];
-        philox_uniform4(seed, MNN_STREAM_NADE, row0 + (uint32_t)row, sub, b0 + (uint32_t)lane, u4);
+        philox_uniform4(seed, rstream, row0 + (uint32_t)row, sub, rblock + b0 + (uint32_t)lane, u4);
         *reinterpret_cast<float4*>(su + 4 * lane) = make_float4(u4[0], u4[1], u4[2], u4[3]);
     };
     // SUB_BASE: one wave-uniform (scalar) read, HERE and not at the top of the kernel.  At the top the compiler puts the load of the pointer,
@@ -1154,6 +1222,7 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
         cix = kq % cc.n;
         cstep = G % cc.n;
     }
+    const int tix0 = tix, cix0 = cix;                        // REDRAW: chunk 0's indices, for a restart (no second division)
     // what a chunk's passes read besides h: its eight w_dec rows -- visibles (2 p, 2 p + 1) side by side, one packed FMA serves both --, the lane's
     // b_dec and uniform.  (Measured and dropped: fetching them one chunk AHEAD, under the previous chunk's passes -- 47.0 vs 46.5 us per call: a lone
     // wave spends ~10 cycles per instruction of this chain whatever flies beside it.)
@@ -1189,11 +1258,16 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
             ci.u = su[e0 + (uint32_t)ivc - 4u * b0];
         }
     };
-    for (int c0 = 0; c0 < nchunks; c0 += NB) {
+    int tries = 0, att = 0;                                  // REDRAW: the attempt; without it the loop below is one pass
+    bool fell = false;                                       // the last attempt met a violation: the emitted row is the truncated one
+    if constexpr (REDRAW) tries = RD.tries;
+    for (att = 0; att <= tries; ++att) {
+    bool viol = false;
+    for (int c0 = 0; c0 < nchunks && !(REDRAW && viol); c0 += NB) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             const int c = c0 + b;
-            if (c < nchunks) {                               // uniform
+            if (c < nchunks && !(REDRAW && viol)) {          // uniform (REDRAW: an abandoned attempt decides nothing more)
                 // chunk c's 2 G copies are the oldest in flight; (NB - 2) chunks behind them may still be on their way
                 SCH_TR(0, c);
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAITN) : "memory");
@@ -1257,7 +1331,7 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
                     const bool open = mine && kq >= sfrom;   // lanes whose visible is still undecided
                     const bool free_ = !GIVEN || ci.code == 255;     // (a clamped lane takes its code below, whatever its comparison says)
                     const bool capped = CAP && free_ && ((cc.ex >> cix) & 1) != 0;     // (and a capped one is 0)
-                    const bool drawn = free_ && !capped;
+                    const bool drawn = free_ && (REDRAW || !capped);     // (REDRAW: a capped lane is drawn too, and stands in the tie ballot)
                     bool on;
                     if (TMODE != 0) {                        // u < det_sigmoid(l / T), settled by the hardware sigmoid unless within 1e-4 of a tie (draw_below)
                         const float xa = TMODE == 1 ? l : l / ci.t;
@@ -1273,9 +1347,18 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
                         else on = det_sigmoid(l) >= 0.5f;
                     }
                     if (GIVEN && !free_) on = ci.code != 0;
+                    const bool past = REDRAW && capped && on && open;     // a drawn 1 past the cap (capped lanes are free ones: `on` is the comparison)
                     if (CAP && capped) on = false;
                     const uint64_t m = __builtin_amdgcn_ballot_w64(on && open) & (G == 16 ? 0x1111111111111111ull : 0x0101010101010101ull);
                     const int f = m != 0ull ? (int)(__builtin_ctzll(m) >> KSH) : G;     // the first draw of 1 (uniform)
+                    if constexpr (REDRAW) {                  // a violation counts where it lies before the first kept 1: behind it the pass is discarded
+                        const uint64_t vm = __builtin_amdgcn_ballot_w64(past) & (G == 16 ? 0x1111111111111111ull : 0x0101010101010101ull);
+                        if (vm != 0ull && (int)(__builtin_ctzll(vm) >> KSH) < f) {     // uniform
+                            fell = att == tries;             // the last attempt truncates: the lane is the 0 it has been made
+                            viol = !fell;
+                        }
+                        if (viol) break;                     // abandoned: the row starts over below
+                    }
 #ifdef SCH_TRACE
                     if (sfrom == 0) { asm volatile("" ::"s"(f)); SCH_TR(6, c); }
 #endif
@@ -1303,6 +1386,28 @@ nade_sample_chunk_kernel(SampleJobs J, int N, int D, int Hn, SampleTemps TT, uin
             }
         }
     }
+    if (!REDRAW || !viol) break;
+    if constexpr (REDRAW) {                                  // the next attempt: the step's initial state, zero counts, its own uniforms, the ring from chunk 0
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // every copy in flight has landed: the uniforms below and the new chunks write into a quiet LDS
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            a[q] = a0[q];
+            h[q] = det_sigmoid(a[q]);
+        }
+        sample_caps_init(CC, (int)blockIdx.y, cc);
+        cix = cix0;
+        tix = tix0;
+        rstream = MNN_STREAM_NADE_REDRAW;
+        rblock = (uint32_t)att * RD.eq;                      // attempt att + 1 starts at element att * (4 eq)
+        b0 = e0 >> 2;
+        refill();
+        asm volatile("" ::"v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(h[3]));
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int b = 0; b < NB - 1; ++b) stage(b, b);
+    }
+    }
+    if constexpr (REDRAW) sample_redraw_count(RD, lane, att, fell);
     // after the scan: as nade_sample_kernel
     for (int i = lane; i < D; i += 64) {
         const float p = det_sigmoid(sp[i]);
@@ -1328,6 +1433,10 @@ static hipError_t sample_chunk_raise_lds() {                 // the ring + a row
         RAISE(0, true); RAISE(1, true); RAISE(2, true); RAISE(0, false); RAISE(1, false); RAISE(2, false);
 #undef RAISE
 #undef RAISE1
+#define RAISE1(TM, FU) if (e == hipSuccess) e = mnn_raise_dynamic_lds(reinterpret_cast<const void*>(&nade_sample_chunk_kernel<TM, FU, 8, true, true, true>), 128 * 1024); \
+                       if (e == hipSuccess) e = mnn_raise_dynamic_lds(reinterpret_cast<const void*>(&nade_sample_chunk_kernel<TM, FU, 16, true, true, true>), 128 * 1024)
+        RAISE1(1, true); RAISE1(2, true); RAISE1(1, false); RAISE1(2, false);      // the REDRAW instantiations
+#undef RAISE1
         return e;
     });
 }
@@ -1335,11 +1444,18 @@ static hipError_t sample_chunk_raise_lds() {                 // the ring + a row
 // GV: some job carries codes (SampleJob.given) -- the GIVEN instantiations; without any, the launch is the unconditioned one
 // tmode / TT: launch_sample's reading of the caller's mnn_temps (TT is read by the TMODE 2 instantiations only)
 // CP: some counter of the launch can run out (launch_sample) -- the CAP instantiations, which are GIVEN ones; CC is read by them only
-template <bool GV, bool CP>
+// RW: CP with redraws (launch_sample) -- the REDRAW instantiations, TMODE 1 and 2 only (the entry points refuse threshold draws); RD is theirs
+template <bool GV, bool CP, bool RW = false>
 static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, int tmode, const SampleTemps& TT, const SampleCaps& caps,
-                           uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride, const uint32_t* sub_base) {
-    typename SampleCapsArg<CP>::T CC;                        // the kernels' last argument: the caps, or nothing
+                           uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride, const uint32_t* sub_base,
+                           const SampleRedraw& redraw = SampleRedraw{0, 0u, nullptr}) {
+    typename SampleCapsArg<CP>::T CC;                        // the kernels' last arguments: the caps and the redraws, or nothing
     if constexpr (CP) CC = caps;
+    typename SampleRedrawArg<RW>::T RD;
+    if constexpr (RW) {
+        RD = redraw;
+        MNN_REQUIRE(tmode != 0, "nade sample: redraws need a temperature (the entry points check it)");
+    }
     bool chunked = Hn % 4 == 0 && Hn >= 4 && !mnn_switch_set(MNN_SW_SAMPLE_NO_CHUNK);      // (tests compare the two forms)
     for (int j = 0; j < njobs && chunked; ++j) chunked = (((uintptr_t)J.job[j].w_enc | (uintptr_t)J.job[j].w_dec) & 15) == 0;
     const size_t gbytes = GV ? (size_t)((D + 3) & ~3) : 0;   // the row's codes
@@ -1349,20 +1465,20 @@ static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N
         const int g = (long)N * njobs <= 256 && !mnn_switch_set(MNN_SW_SAMPLE_G8) ? 16 : 8;
         const size_t ldc = (size_t)sch_nb(g) * 2 * g * 1024 + (size_t)9 * ((D + 3) & ~3) + 1024 + gbytes + tbytes;     // <= 96 KB + 15 KB + 1 KB (D <= 1536)
         MNN_HIP(sample_chunk_raise_lds());
-#define SMC(TM, FU) do { if (g == 16) hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 16, GV, CP>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base, CC); \
-                         else hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 8, GV, CP>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base, CC); } while (0)
-        if (Hn == 256) { if (tmode == 0) SMC(0, true); else if (tmode == 1) SMC(1, true); else SMC(2, true); }
-        else { if (tmode == 0) SMC(0, false); else if (tmode == 1) SMC(1, false); else SMC(2, false); }
+#define SMC(TM, FU) do { if (g == 16) hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 16, GV, CP, RW>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base, CC, RD); \
+                         else hipLaunchKernelGGL((nade_sample_chunk_kernel<TM, FU, 8, GV, CP, RW>), dim3(N, njobs), dim3(64), ldc, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base, CC, RD); } while (0)
+        if (Hn == 256) { if (tmode == 0) { if constexpr (!RW) SMC(0, true); } else if (tmode == 1) SMC(1, true); else SMC(2, true); }
+        else { if (tmode == 0) { if constexpr (!RW) SMC(0, false); } else if (tmode == 1) SMC(1, false); else SMC(2, false); }
 #undef SMC
         MNN_LAUNCH_CHECK();
         return MNN_OK;
     }
     dim3 grid(cdiv(N, 4), njobs);
     const size_t lds = (size_t)36 * ((D + 3) & ~3) + 4096 + 4 * gbytes + tbytes;     // 4 waves x ((2 f32 + u8 (+ u8 code)) per visible + 256 uniforms): <= 64 KB
-#define SMP(TM, FU, SP) hipLaunchKernelGGL((nade_sample_kernel<TM, FU, SP, GV, CP>), grid, dim3(256), lds, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base, CC)
+#define SMP(TM, FU, SP) hipLaunchKernelGGL((nade_sample_kernel<TM, FU, SP, GV, CP, RW>), grid, dim3(256), lds, st, J, N, D, Hn, TT, row0, sub, s_row_stride, s_elem_stride, sub_base, CC, RD)
     if (Hn == 256 && tmode == 1) { if (mnn_switch_set(MNN_SW_SAMPLE_NO_SPEC)) SMP(1, true, false); else SMP(1, true, true); }
-    else if (Hn == 256) { if (tmode == 0) SMP(0, true, false); else SMP(2, true, false); }
-    else { if (tmode == 0) SMP(0, false, false); else if (tmode == 1) SMP(1, false, false); else SMP(2, false, false); }
+    else if (Hn == 256) { if (tmode == 0) { if constexpr (!RW) SMP(0, true, false); } else SMP(2, true, false); }
+    else { if (tmode == 0) { if constexpr (!RW) SMP(0, false, false); } else if (tmode == 1) SMP(1, false, false); else SMP(2, false, false); }
 #undef SMP
     MNN_LAUNCH_CHECK();
     return MNN_OK;
@@ -1373,8 +1489,11 @@ static int launch_sample_t(hipStream_t st, const SampleJobs& J, int njobs, int N
 // (mnn_nade_sample walks a MultiNADE's tracks eight at a time).
 // caps (NULL, or validated by sample_caps_ok): read like temps -- one cap, one per job from track0 on, or by visible index; negative: none.  A
 // launch in which no counter can run out (no cap below the visibles it counts) is the launch without caps: the kernels that never read CC.
+// redraw (NULL or tries == 0: none; validated by sample_redraw_ok) with a launch in which a counter can run out: the REDRAW kernels; elems:
+// the launch key's element count (tracks D of a MultiNADE, D per job), whose multiple of 4 separates the attempts' Philox elements.
 static int launch_sample(hipStream_t st, const SampleJobs& J, int njobs, int N, int D, int Hn, const mnn_temps& temps, const mnn_caps* caps, int track0,
-                         uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride, const uint32_t* sub_base = nullptr) {
+                         uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride, const uint32_t* sub_base = nullptr,
+                         const mnn_redraw* redraw = nullptr, long elems = 0) {
     bool given = false;
     for (int j = 0; j < njobs; ++j) given = given || J.job[j].given != nullptr;
     SampleTemps TT;
@@ -1409,6 +1528,9 @@ static int launch_sample(hipStream_t st, const SampleJobs& J, int njobs, int N, 
             for (int j = 0; j < njobs; ++j) capped = capped || CC.cap[j] < D;
         }
     }
+    if (capped && redraw != nullptr && redraw->tries > 0)
+        return launch_sample_t<true, true, true>(st, J, njobs, N, D, Hn, tmode, TT, CC, row0, sub, s_row_stride, s_elem_stride, sub_base,
+                                                 SampleRedraw{redraw->tries, (uint32_t)((elems + 3) >> 2), redraw->stats});
     if (capped) return launch_sample_t<true, true>(st, J, njobs, N, D, Hn, tmode, TT, CC, row0, sub, s_row_stride, s_elem_stride, sub_base);
     return given ? launch_sample_t<true, false>(st, J, njobs, N, D, Hn, tmode, TT, CC, row0, sub, s_row_stride, s_elem_stride, sub_base)
                  : launch_sample_t<false, false>(st, J, njobs, N, D, Hn, tmode, TT, CC, row0, sub, s_row_stride, s_elem_stride, sub_base);
@@ -1426,6 +1548,12 @@ static bool sample_caps_ok(const mnn_caps* c, int njobs) {
     if (c->n < 0 || c->n > MNN_TEMPS_MAX) return false;
     return c->n <= 1 || c->by_visible != 0 || c->n == njobs;
 }
+// NULL or tries == 0 (no redraws), or 1..255 tries with temperatures to draw again from (threshold decoding would repeat the vector) and
+// attempts whose elements stay below 2^32
+static bool sample_redraw_ok(const mnn_redraw* r, const mnn_temps* t, long elems) {
+    if (r == nullptr || r->tries == 0) return true;
+    return r->tries > 0 && r->tries <= 255 && t != nullptr && t->n > 0 && (elems + 3) / 4 * 4 * (long)r->tries < (1L << 32);
+}
 static mnn_temps temps_of_scalar(float temperature) {        // the float of the entry points without a table: <= 0 is the threshold mode
     mnn_temps t;
     memset(&t, 0, sizeof(t));
@@ -1435,16 +1563,18 @@ static mnn_temps temps_of_scalar(float temperature) {        // the float of the
 
 // mnn_nade_sample_temps with a sub-counter base read on the device: sub_base NULL (none), or one u32 -- the draws use sub + *sub_base -- and
 // with polyphony caps: caps NULL (none), or at most caps->cap[.] ones per track and row (launch_sample)
-extern "C" int mnn_nade_sample_caps_at(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
-                                       const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed, uint32_t row0, uint32_t sub,
-                                       uint8_t* samples, long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given,
-                                       const uint32_t* sub_base) {
+// ... and with redraws: redraw NULL or tries == 0 (none: mnn_nade_sample_caps_at, which calls this), or the cap by rejection (mnn_redraw)
+extern "C" int mnn_nade_sample_redraw_at(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
+                                         const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed, uint32_t row0, uint32_t sub,
+                                         uint8_t* samples, long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given,
+                                         const uint32_t* sub_base, const mnn_redraw* redraw) {
     MNN_REQUIRE(tracks > 0 && N > 0 && D > 0 && Hn > 0 && Hn <= 256, "mnn_nade_sample: need tracks,N,D>0 and 0<Hn<=256 (Hn=%d)", Hn);
     MNN_REQUIRE(bias && w_enc && w_dec && samples, "mnn_nade_sample: null pointer");
     MNN_REQUIRE(ld_bias >= tracks * (Hn + D), "mnn_nade_sample: ld_bias too small");
     MNN_REQUIRE(D <= 1536, "mnn_nade_sample: D <= 1536 (logits, b_dec and draws of a row are parked in LDS, 36 B per visible and wave; D=%d)", D);
     MNN_REQUIRE(sample_temps_ok(temps, tracks), "mnn_nade_sample: temps: 0..%d positive finite temperatures, per track one or `tracks` of them", MNN_TEMPS_MAX);
     MNN_REQUIRE(sample_caps_ok(caps, tracks), "mnn_nade_sample: caps: 0..%d entries, per track one or `tracks` of them", MNN_TEMPS_MAX);
+    MNN_REQUIRE(sample_redraw_ok(redraw, temps, (long)tracks * D), "mnn_nade_sample: redraw: 0..255 tries, and none with threshold draws");
     for (int m0 = 0; m0 < tracks; m0 += SAMPLE_MAX_JOBS) {            // the tracks of a MultiNADE: up to eight per launch
         SampleJobs J;
         memset(&J, 0, sizeof(J));
@@ -1455,10 +1585,19 @@ extern "C" int mnn_nade_sample_caps_at(mnn_stream_t s, int tracks, int N, int D,
                                  (uint32_t)(m * D), samples + (size_t)m * s_track_stride, nll ? nll + (size_t)m * N : nullptr,
                                  given ? given + (size_t)m * s_track_stride : nullptr};
         }
-        const int rc = launch_sample((hipStream_t)s, J, nj, N, D, Hn, *temps, caps, m0, row0, sub, s_row_stride, s_elem_stride, sub_base);
+        const int rc = launch_sample((hipStream_t)s, J, nj, N, D, Hn, *temps, caps, m0, row0, sub, s_row_stride, s_elem_stride, sub_base, redraw,
+                                     (long)tracks * D);
         if (rc != MNN_OK) return rc;
     }
     return MNN_OK;
+}
+
+extern "C" int mnn_nade_sample_caps_at(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
+                                       const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed, uint32_t row0, uint32_t sub,
+                                       uint8_t* samples, long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given,
+                                       const uint32_t* sub_base) {
+    return mnn_nade_sample_redraw_at(s, tracks, N, D, Hn, bias, ld_bias, w_enc, w_dec, temps, caps, seed, row0, sub, samples, s_track_stride,
+                                     s_row_stride, s_elem_stride, nll, given, sub_base, nullptr);
 }
 
 extern "C" int mnn_nade_sample_temps_at(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
@@ -1488,12 +1627,14 @@ extern "C" int mnn_nade_sample(mnn_stream_t s, int tracks, int N, int D, int Hn,
 // multinn_feedback.py:196: `generators[i].sample_single` for every track): job j has its own Dense output matrix, weights, seed and output
 // pointer -- and, with a table of njobs entries, its own temperature and its own cap; rows, widths, the RNG row / sub counters and the output
 // strides are shared.
-extern "C" int mnn_nade_sample_multi_caps(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, const mnn_temps* temps,
-                                          const mnn_caps* caps, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
+extern "C" int mnn_nade_sample_multi_redraw(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, const mnn_temps* temps,
+                                            const mnn_caps* caps, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride,
+                                            const mnn_redraw* redraw) {
     MNN_REQUIRE(njobs > 0 && njobs <= SAMPLE_MAX_JOBS && jobs && N > 0 && D > 0 && Hn > 0 && Hn <= 256 && D <= 1536,
                 "mnn_nade_sample_multi: 1..%d jobs, N, D > 0, 0 < Hn <= 256, D <= 1536", SAMPLE_MAX_JOBS);
     MNN_REQUIRE(sample_temps_ok(temps, njobs), "mnn_nade_sample_multi: temps: 0..%d positive finite temperatures, per job one or `njobs` of them", MNN_TEMPS_MAX);
     MNN_REQUIRE(sample_caps_ok(caps, njobs), "mnn_nade_sample_multi: caps: 0..%d entries, per job one or `njobs` of them", MNN_TEMPS_MAX);
+    MNN_REQUIRE(sample_redraw_ok(redraw, temps, (long)D), "mnn_nade_sample_multi: redraw: 0..255 tries, and none with threshold draws");
     SampleJobs J;
     memset(&J, 0, sizeof(J));
     for (int j = 0; j < njobs; ++j) {
@@ -1501,7 +1642,12 @@ extern "C" int mnn_nade_sample_multi_caps(mnn_stream_t s, int njobs, const mnn_n
         MNN_REQUIRE(q.bias && q.w_enc && q.w_dec && q.samples && q.ld_bias >= Hn + D, "mnn_nade_sample_multi: job %d: null pointer or ld_bias < Hn + D", j);
         J.job[j] = SampleJob{q.bias, q.ld_bias, 0, Hn, q.w_enc, q.w_dec, q.seed, 0u, q.samples, q.nll, q.given};
     }
-    return launch_sample((hipStream_t)s, J, njobs, N, D, Hn, *temps, caps, 0, row0, sub, s_row_stride, s_elem_stride);
+    return launch_sample((hipStream_t)s, J, njobs, N, D, Hn, *temps, caps, 0, row0, sub, s_row_stride, s_elem_stride, nullptr, redraw, (long)D);
+}
+
+extern "C" int mnn_nade_sample_multi_caps(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, const mnn_temps* temps,
+                                          const mnn_caps* caps, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride) {
+    return mnn_nade_sample_multi_redraw(s, njobs, jobs, N, D, Hn, temps, caps, row0, sub, s_row_stride, s_elem_stride, nullptr);
 }
 
 extern "C" int mnn_nade_sample_multi_temps(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, const mnn_temps* temps,

@@ -215,14 +215,24 @@ class FeedbackRnnSampler:
             raise MnnUnsupported("max_notes exists for NADE generators only: a Gibbs chain has no visible order in which a track's count could stop it")
         return max_notes
 
-    def generate(self, x_u8, num_steps, given=None, temperature=1.0, max_notes=None):
+    def redraw_counts(self):
+        """(redrawn, fallback) of the last generate / generate_encoded call, over all generators (common.redraw_counts): the scan's sample
+        launches add to the sampler's own cell."""
+        from .common import redraw_counts
+        return redraw_counts(self)
+
+    def generate(self, x_u8, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0):
         """x_u8 [B,Ti,P,M] intro piano-rolls -> samples u8 [B,num_steps,P,M].  One hipGraph replay per call on the
         device (common.ScanGraphs): the M generators and the feedback module step inside the same captured scan.
         given (optional): codes u8 [B, num_steps, P, M] (common.given_codes), see generate_encoded.
         temperature: one for all generators or generator m's own, temperature[m]; 1.0 is the call (and the captured scan) without it.
         max_notes: None, one cap (an integer >= 0) for all generators or generator m's own, max_notes[m] (None: no cap); None is the call
-        (and the captured scan) without it."""
-        from .common import ScanGraphs
+        (and the captured scan) without it.  redraws (common.sampling_redraws): the cap by rejection in every generator's step; 0, or
+        no cap, is the call (and the captured scan) without it."""
+        from .common import ScanGraphs, sampling_redraws
+        temperature, max_notes = self._temperature(temperature), self._max_notes(max_notes, x_u8.shape[2])
+        redraws = sampling_redraws(redraws, max_notes, temperature)
+        self._redraw_live = redraws > 0                    # per call, here: a replay of a captured scan does not pass through generate_encoded
 
         def stale():
             for g in self.generators:
@@ -230,7 +240,7 @@ class FeedbackRnnSampler:
             if hasattr(self.feedback, "_packed_step"):
                 self.feedback._packed_step = -1
         return ScanGraphs.generate(self, (tuple(x_u8.shape), int(num_steps), tuple((g.seed, g.row0) for g in self.generators)), x_u8, num_steps,
-                                   given, self._temperature(temperature), self._generate_scan, stale, self._max_notes(max_notes, x_u8.shape[2]))
+                                   given, temperature, self._generate_scan, stale, max_notes, redraws)
 
     def _group_dense(self, hs, rnn_states):
         """The M generators' Dense layers on their top outputs in one launch -> their RnnEstimatorStateTuples."""
@@ -238,13 +248,13 @@ class FeedbackRnnSampler:
         ops.dense_det(list(jobs))
         return [g._state_from_dense(o, tuple(st)) for g, o, st in zip(self.generators, outs, rnn_states)]
 
-    def _generate_scan(self, x_u8, num_steps, given=None, temperature=1.0, max_notes=None):
+    def _generate_scan(self, x_u8, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0):
         B, Ti, P, M = x_u8.shape
         assert M == self.num_tracks
         enc = torch.cat([torch.zeros((B, 1, P, M), device=x_u8.device, dtype=torch.uint8), x_u8], 1)      # multi_encoder_nn.py:73-76
-        return self.generate_encoded([enc[..., i] for i in range(M)], num_steps, given, temperature, max_notes)
+        return self.generate_encoded([enc[..., i] for i in range(M)], num_steps, given, temperature, max_notes, redraws)
 
-    def generate_encoded(self, enc_tracks, num_steps, given=None, temperature=1.0, max_notes=None):
+    def generate_encoded(self, enc_tracks, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0):
         """The scan on per-track ENCODED inputs (multinn_feedback.py:120-173 between the encoders): enc_tracks = M x u8
         [B, Ti+1, E] (zero first step included) -> sampled codes u8 [B, num_steps, E, M]; the caller decodes them through
         its encoders (identity for PassEncoder).  given (optional): codes u8 [B, num_steps, E, M] (common.given_codes).  NADE
@@ -255,6 +265,13 @@ class FeedbackRnnSampler:
         M = self.num_tracks
         temperature = self._temperature(temperature)
         max_notes = self._max_notes(max_notes, enc_tracks[0].shape[-1])
+        from .common import sampling_redraws, redraw_cell
+        redraws = sampling_redraws(redraws, max_notes, temperature)
+        self._redraw_live = redraws > 0
+        stats = None
+        if redraws:                                        # the call's statistics, from zero (in the captured scan: a fill node)
+            stats = redraw_cell(self, enc_tracks[0].device)
+            stats.zero_()
         caps = list(max_notes) if isinstance(max_notes, tuple) else [max_notes] * M               # generator i emits at most caps[i] ones per step
         temps = list(temperature) if isinstance(temperature, tuple) else [temperature] * M          # generator i samples at temps[i]
         enc_tracks = [e.contiguous() for e in enc_tracks]            # (views of a [B, T, P, M] roll have inner stride M)
@@ -302,7 +319,7 @@ class FeedbackRnnSampler:
                 views = [out[:, s, :, i] for i in range(M)]                                          # u8 [B, P] views of track i (element stride M)
                 ops.nade_sample_multi([dict(bias=states[i].dense, w_enc=g.store["nade/w_enc"][0], w_dec=g.store["nade/w_dec"][0], seed=g.seed,
                                             samples=views[i], given=None if given is None else given[:, s, :, i])
-                                       for i, g in enumerate(gs)], P, Hn, temperature, gs[0].row0, s, max_notes=max_notes)
+                                       for i, g in enumerate(gs)], P, Hn, temperature, gs[0].row0, s, max_notes=max_notes, redraws=redraws, redraw_stats=stats)
                 st = out[:, s].reshape(B, P * M)                                                     # [B, P*M] view, feature p*M+m
                 fb, fb_state = self.feedback.single(st if fb_strided else st.contiguous(), fb_state)
                 res = det_steps([g._stack for g in gs], views, [list(s_.rnn_state) for s_ in states], [fb] * M)
@@ -328,6 +345,8 @@ class FeedbackRnnSampler:
                         gi = None if given is None else given[:, s, :, i]
                         clamp = gi is not None and isinstance(g, RnnNade)
                         sample = g.sample_single if caps[i] is None else functools.partial(g.sample_single_capped, max_notes=caps[i])
+                        if redraws and caps[i] is not None:
+                            sample = functools.partial(g.sample_single_redrawn, max_notes=caps[i], redraws=redraws, redraw_stats=stats)
                         smp, _ = sample(None, states[i], given=gi.contiguous() if clamp else None, temperature=temps[i],
                                         at=DrawAt(g.seed, g.row0, s))
                         if gi is not None and not clamp:    # a wholly given track pasted over the RBM's sample

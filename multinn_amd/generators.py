@@ -22,7 +22,7 @@ import torch
 
 from . import ops
 from .switches import flag, value
-from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, DrawAt, check_given, given_codes, given_mask_tracks, sampling_temperature, sampling_max_notes, glorot_uniform, zeros_init, default_device, capture_train_step
+from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, DrawAt, check_given, given_codes, given_mask_tracks, sampling_temperature, sampling_max_notes, sampling_redraws, redraw_cell, redraw_counts, glorot_uniform, zeros_init, default_device, capture_train_step
 from .training import compute_gradients, world, dp_active, AdamOptimizer
 from ._lib import MnnUnsupported
 from .lstm_stack import LstmStack, _SINGLE, drive, drive_group, _det_f32, det_steps
@@ -208,7 +208,7 @@ class Generator(Model):
         return self._outputs
 
     @abc.abstractmethod
-    def generate(self, x, num_steps, given=None, temperature=1.0, max_notes=None):
+    def generate(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0):
         ...
 
     def pretrain(self, optimizer, lr, run_optimizer=True):
@@ -384,7 +384,7 @@ class RnnEstimator(Generator):
                                  "step at once and has no visible order in which a track's count could stop it")
         return None
 
-    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0, max_notes=None):
+    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0):
         return None                         # estimators without a one-call scan (RnnRBM) step through sample_single / single_step
 
     # -- generation sessions (session.py) --------------------------------------------------------
@@ -508,8 +508,11 @@ class RnnEstimator(Generator):
         return buf
 
     # -- sampling -------------------------------------------------------------------------------
-    def generate(self, x, num_steps, given=None, temperature=1.0, max_notes=None):
+    def generate(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0):
         """rnn_estimator.py:271-298: intro pass, then num_steps x {sample_single, single_step}.
+        redraws (0..255, with max_notes; common.sampling_redraws): the cap by rejection -- a row whose step would emit a 1 past a cap is
+        drawn again, up to `redraws` times, before the truncating scan serves it; redraw_counts() reports what happened.  0, or no cap, is
+        the call without it: the same kernels, bits and captured scan.
         max_notes (NADE estimators; common.sampling_max_notes): at most K ones per track and generated step -- an integer >= 0, or one per
         track (None: no cap for that track); the scan counts a track's ones, given ones included, and a free visible of a track that has
         reached its cap is a settled 0.  None is the call without it: the same kernels, bits and captured scan.
@@ -523,35 +526,48 @@ class RnnEstimator(Generator):
             check_given(given, x.shape[0], num_steps, self._num_output)
             given = given.contiguous()
         max_notes = self._max_notes(max_notes)
+        temperature = self._temperature(temperature)
+        redraws = sampling_redraws(redraws, max_notes, temperature)
         if max_notes is not None:
             refuse_host_model(self.store.device, "generate(max_notes=)")
+        self._redraw_live = redraws > 0
 
         def stale():
             self._packed_step = -1
         return ScanGraphs.generate(self, (tuple(x.shape), x.dtype, int(num_steps), self.seed, self.row0), x, num_steps, given,
-                                   self._temperature(temperature), self._generate_scan, stale, max_notes)
+                                   temperature, self._generate_scan, stale, max_notes, redraws)
 
-    def _generate_scan(self, x, num_steps, given=None, temperature=1.0, max_notes=None):
+    def redraw_counts(self):
+        """(redrawn, fallback) of the last generate call or session chunk: how many scans -- one per row, track and generated step -- were
+        drawn again at least once, and how many of them fell back to the truncating scan (and carry its bias).  Ints; synchronises."""
+        return redraw_counts(self)
+
+    def _generate_scan(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0):
         self._materialize(x.shape[-1])
         self._rnn.build_cell(False)
+        if redraws:
+            redraw_cell(self, x.device).zero_()        # the call's statistics start at zero (in a captured scan: a fill node of the graph)
         with self._sampling_scope():
             if self.det_sampling:
-                whole = self._scan_in_one_call(x, num_steps, given, temperature, max_notes)     # LSTM-(Multi)NADE on a byte piano-roll: mnn_generate_scan runs the whole scan
+                whole = self._scan_in_one_call(x, num_steps, given, temperature, max_notes, redraws)     # LSTM-(Multi)NADE on a byte piano-roll: mnn_generate_scan runs the whole scan
                 if whole is not None:
                     return whole
                 state = self.steps(x)
             else:
                 self._ensure_packed()
                 state = self._get_state(x, lengths=None, last_outputs=True)
-            return self._scan_steps(state, x[:, -1, :], num_steps, DrawAt(self.seed, self.row0, 0), given, temperature, max_notes)[0]
+            return self._scan_steps(state, x[:, -1, :], num_steps, DrawAt(self.seed, self.row0, 0), given, temperature, max_notes, redraws)[0]
 
-    def _scan_steps(self, state, last_row, n, at0, given=None, temperature=1.0, max_notes=None):
+    def _scan_steps(self, state, last_row, n, at0, given=None, temperature=1.0, max_notes=None, redraws=0):
         """The step loop of a single generator (rnn_estimator.py:283-298): n x {sample_single, single_step} from `state` and the last emitted
         row, step j drawing at at0's position moved on by j steps under given[:, j] -> (samples u8 [B, n, num_output], state, last row).
         generate runs it from step 0, a session's chunk from where the piece stands.  max_notes (normalised; None: the call without it)
-        makes every step a sample_single_capped, which the estimators that have caps define."""
+        makes every step a sample_single_capped, which the estimators that have caps define; redraws (normalised; 0: nothing changes) a
+        sample_single_redrawn that adds to the generator's statistics cell."""
         out = []
         sample = self.sample_single if max_notes is None else functools.partial(self.sample_single_capped, max_notes=max_notes)
+        if redraws:
+            sample = functools.partial(self.sample_single_redrawn, max_notes=max_notes, redraws=redraws, redraw_stats=redraw_cell(self, last_row.device))
         for j in range(n):
             last_row, _ = sample(last_row, state, given=None if given is None else given[:, j], temperature=temperature,
                                  at=at0._replace(step=at0.step + j))
@@ -1073,13 +1089,14 @@ class RnnNade(RnnEstimator):
         return sampling_max_notes(max_notes, n, None if n is None else self.num_dims // n, collapse=n == 1,
                                   what="max_notes (one NADE: a sequence whose length divides its visibles)")
 
-    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0, max_notes=None):
+    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0):
         """rnn_estimator.py:271-298 through ONE C-ABI call (mnn_generate_scan: intro pass + num_steps x {NADE sample, LSTM step, Dense} enqueued
         by the library's own host loop) when the inputs are the byte piano-roll itself; the same kernels and bits as the step-by-step path.
         given: the scan's codes u8 [B, num_steps, num_output] (generate)."""
         if x.dtype != torch.uint8 or x.shape[-1] != self.num_tracks * self.num_dims or int(num_steps) < 1:
             return None
         return ops.generate_scan(x.contiguous(), num_steps, temperature=temperature, seed=self.seed, row0=self.row0, given=given, max_notes=max_notes,
+                                 redraws=redraws, redraw_stats=redraw_cell(self, x.device) if redraws else None,
                                  state0=self._state0(x.shape[0], torch.float32), **self._scan_layers())      # (learn_zero_state: tiled on the device here, an input array of the scan)
 
     def _state_of(self, out, rnn_state):
@@ -1138,6 +1155,13 @@ class RnnNade(RnnEstimator):
         """sample_single under a polyphony cap: max_notes is None (sample_single itself, which calls this), an integer, or a sequence read
         like the temperature's -- at most that many ones per track of this step (ops.nade_sample).  The signature every estimator's
         sample_single shares stays as it is; only the NADE estimators have this one."""
+        return self.sample_single_redrawn(inputs, state, given=given, temperature=temperature, at=at, max_notes=max_notes)
+
+    def sample_single_redrawn(self, inputs, state, *, given=None, temperature=1.0, at=None, max_notes=None, redraws=0, redraw_stats=None):
+        """sample_single_capped with the cap by rejection: redraws (0: sample_single_capped itself, which calls this) tries before the
+        truncating step (ops.nade_sample); redraw_stats: None, or an int32[2] on the device that gains this step's (redrawn, fallback)
+        scans -- the caller's own cell: the generator's is written by generate and by sessions only."""
+        redraws = sampling_redraws(redraws, max_notes, temperature)
         M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
         at = DrawAt(self.seed, self.row0, 0) if at is None else at
         out = state.dense
@@ -1146,7 +1170,7 @@ class RnnNade(RnnEstimator):
         nll = torch.empty((M, Bn), device=out.device)
         ops.nade_sample(out, self.store["nade/w_enc"], self.store["nade/w_dec"], M, D, Hn, temperature, at.seed, at.row0, at.step, smp,
                         track_minor=(M > 1), nll=nll, given=None if given is None else given.contiguous(), by_visible=M == 1, sub_base=at.base,
-                        max_notes=max_notes)
+                        max_notes=max_notes, redraws=redraws, redraw_stats=redraw_stats)
         return smp, (nll[0] if M == 1 else [nll[m] for m in range(M)])
 
 

@@ -26,7 +26,7 @@ import weakref
 
 import torch
 
-from .common import Model, capture_train_step, given_codes, given_tracks, sampling_max_notes, sampling_temperature
+from .common import Model, capture_train_step, given_codes, given_tracks, sampling_max_notes, sampling_redraws, sampling_temperature
 from .encoders import PassEncoder, DBNEncoder
 from .generators import RnnNade, RnnRBM, RnnMultiNADE, RnnMultiRBM
 from . import ops
@@ -229,15 +229,17 @@ class MultINNCore(Model):
     metrics_upd = property(lambda self: (self._ensure_global_metrics(), self._metrics_upd)[1])
 
     # -- sampling -------------------------------------------------------------------------------
-    def sampler(self, num_beats, given=None, given_mask=None, temperature=1.0, max_notes=None):
+    def sampler(self, num_beats, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0):
         """multinn_core.py:324-341: number of model time steps in `num_beats` beats, then generate() (given / given_mask / temperature /
-        max_notes: see generate)."""
+        max_notes / redraws: see generate)."""
         d = self._config["data"]
         pitch_span = d["pitch_range"]["highest"] - d["pitch_range"]["lowest"]
         num_steps = num_beats * d["beat_resolution"] * pitch_span // self._num_dims
         kw = {} if isinstance(temperature, (int, float)) and temperature == 1.0 else dict(temperature=temperature)
         if max_notes is not None:
             kw["max_notes"] = max_notes
+        if redraws != 0 or isinstance(redraws, bool):      # (anything but the default goes to generate, which checks it)
+            kw["redraws"] = redraws
         if given is None and given_mask is None:
             return self.generate(num_steps, **kw)
         return self.generate(num_steps, given=given, given_mask=given_mask, **kw)
@@ -282,6 +284,21 @@ class MultINNCore(Model):
             raise MnnUnsupported(f"max_notes runs in the HIP sampling kernels: this model lives on {self.device}, not a ROCm device")
         return normalised
 
+    # The cap by rejection (generate(..., max_notes, redraws=R)): a step that would put a note past a cap is drawn again, up to R times, before
+    # the truncating scan above serves it.  An accepted step is an exact draw from the step distribution restricted to the caps -- the bias of
+    # "the first K in ascending pitch" is gone for it -- and a step that fell back after R redraws carries that bias; redraw_counts() says how
+    # many of each the last call had.  0 (or no cap) is the call without it, down to the captured scan.
+    def _redraws(self, redraws, max_notes, temperature):
+        """Normalised on the host (common.sampling_redraws), behind the cap's own refusals: max_notes and temperature are the normalised ones."""
+        return sampling_redraws(redraws, max_notes, temperature)
+
+    def redraw_counts(self):
+        """(redrawn, fallback) of the last generate call or session chunk, summed over the generators (a feedback mode: its sampler's):
+        scans -- one per row, track and generated step -- drawn again at least once, and those that fell back.  Ints; synchronises."""
+        owners = [self._sampler] if getattr(self, "_sampler", None) is not None else list(self.generators)
+        counts = [o.redraw_counts() for o in owners if hasattr(o, "redraw_counts")]
+        return sum(c[0] for c in counts), sum(c[1] for c in counts)
+
     def _generator_max_notes(self, max_notes):
         """The normalised cap per generator.  Here the one NADE of the joint mode, whose visibles are ordered p M + m: one entry per track,
         counted by visible index (an integer alone would cap the whole step)."""
@@ -323,26 +340,31 @@ class MultINNCore(Model):
         max_notes = self._max_notes(max_notes)
         return temperature, self._given(num_steps, given, given_mask), max_notes
 
-    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0, max_notes=None):
+    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0):
         """-> u8 `[B, num_steps, P, M]` (multinn_joint.py:188-215, multinn_jamming.py:101-133, multinn_composer.py:114-151): every generator's
-        scan on its encoded intro, decoded per track.  temperature: _temperature; max_notes: _max_notes; given / given_mask: conditional
-        generation (_given).
+        scan on its encoded intro, decoded per track.  temperature: _temperature; max_notes: _max_notes; redraws: _redraws; given /
+        given_mask: conditional generation (_given).
         What the modes differ in is in _generator_inputs, _generator_given and _decode_samples."""
         temperature, cond, max_notes = self._generate_arguments(num_steps, given, given_mask, temperature, max_notes)
+        redraws = self._redraws(redraws, max_notes, temperature)
         if self._x_encoded is None:
             MultINNCore._build_all(self, "generate")
         scans = [functools.partial(g.generate, x) for g, x in zip(self.generators, self._generator_inputs())]
-        return self._sample_generators(scans, num_steps, cond, temperature, max_notes=max_notes)
+        return self._sample_generators(scans, num_steps, cond, temperature, max_notes=max_notes, redraws=redraws)
 
-    def _sample_generators(self, scans, num_steps, cond, temperature, session=False, max_notes=None):
+    def _sample_generators(self, scans, num_steps, cond, temperature, session=False, max_notes=None, redraws=0):
         """scans: per generator its scan(num_steps, given=, temperature=) -- its generate on its intro, or its session's chunk -> the
         decoded piano-roll.  One generator takes the whole temperature, M generators one each; a generator whose scan does not run
         (_generator_given) emits its codes.  max_notes (normalised): _generator_max_notes gives each generator its own; a generator without
-        one is called as before."""
+        one is called as before; redraws (normalised) go to every generator that has a cap, and every other one reports none."""
         n = len(scans)
         temps = list(temperature) if isinstance(temperature, tuple) and n > 1 else [temperature] * n
         givens = [(None, True)] * n if cond is None else self._generator_given(cond, session)
         caps = [{} if k is None else dict(max_notes=k) for k in (self._generator_max_notes(max_notes) if max_notes is not None else [None] * n)]
+        for g, cap in zip(self.generators, caps):
+            g._redraw_live = False                   # (a generator whose scan does not run this call reports nothing; its generate / chunk sets it where it runs)
+            if cap and redraws and not session:      # (a session's generators carry their redraws themselves)
+                cap["redraws"] = redraws
         samples = [scan(num_steps, given=gv, temperature=t, **cap) if run else gv for scan, (gv, run), t, cap in zip(scans, givens, temps, caps)]
         return self._decode_samples(samples, num_steps)
 
@@ -1076,14 +1098,16 @@ class MultINNFeedback(MultINNJamming):
             if isinstance(g, RnnRBM) and some[i] and not whole[i]:
                 raise NotImplementedError(f"track {i}: in feedback mode an RBM generator takes whole given tracks only (no clamped chain in the feedback scan)")
 
-    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0, max_notes=None):
+    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0):
         """multinn_feedback.py:120-173 -> u8 `[B, num_steps, P, M]`: one joint scan over the M generators and the feedback module.
+        redraws (MultINNCore._redraws): the cap by rejection, inside the scan.
         temperature (MultINNCore._temperature): generator m samples at its own inside the scan.  max_notes (MultINNCore._max_notes):
         generator m caps its own track.
         given / given_mask (MultINNCore._given): NADE generators clamp inside the scan, RBM generators take whole given tracks only."""
         from .feedback import FeedbackRnnSampler
         temperature, cond, max_notes = self._generate_arguments(num_steps, given, given_mask, temperature, max_notes)
-        cap = {} if max_notes is None else dict(max_notes=max_notes)
+        redraws = self._redraws(redraws, max_notes, temperature)
+        cap = {} if max_notes is None else (dict(max_notes=max_notes, redraws=redraws) if redraws else dict(max_notes=max_notes))
         if self._x_encoded is None:
             self._inputs = self._build_inputs()
             self._build_encoders("eval")

@@ -690,6 +690,22 @@ def _caps(max_notes, n_per_job, by_visible, what):
     return sc
 
 
+def _redraw(redraws, redraw_stats, cc, temperature, ref, what):
+    """None (no redraws, or no caps to violate: the entry points without them serve the call, as they always did) or the mnn_redraw of
+    `redraws` tries; redraw_stats: None, or two int32 on the device of `ref` that the kernels add their (redrawn, fallback) scans to."""
+    _req(isinstance(redraws, int) and not isinstance(redraws, bool) and 0 <= redraws <= _lib.REDRAWS_MAX,
+         f"{what}: redraws: an integer 0..{_lib.REDRAWS_MAX}")
+    if redraw_stats is not None:
+        _req(torch.is_tensor(redraw_stats) and redraw_stats.dtype == torch.int32 and redraw_stats.numel() == 2 and redraw_stats.is_contiguous()
+             and redraw_stats.device == ref.device, f"{what}: redraw_stats is int32[2] on the device")
+    _req(redraws == 0 or temperature is not None, f"{what}: redraws need a temperature (threshold decoding would draw the same vector again)")
+    if redraws == 0 or cc is None:
+        return None
+    rd = _lib.Redraw()
+    rd.tries, rd.stats = redraws, _ptr(redraw_stats)
+    return rd
+
+
 def _sub_base(sub_base, ref, what):
     """A generation session's step cell: None, or ONE 32-bit integer on the device of `ref` that the sampling kernels add to their sub-counter."""
     if sub_base is not None:
@@ -699,7 +715,7 @@ def _sub_base(sub_base, ref, what):
 
 
 def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub, samples, track_minor=False, nll=None, given=None,
-                by_visible=False, sub_base=None, max_notes=None):
+                by_visible=False, sub_base=None, max_notes=None, redraws=0, redraw_stats=None):
     """samples u8 [N, tracks*D]; feature index m*D+i (track_minor False) or i*tracks+m (True, rnn_multinade.py:313-314).
     temperature: a float, None (threshold draws) or a sequence -- one temperature per track, or with by_visible the temperature of visible
     i is temperature[i % len] (a joint NADE over visibles p * M + m: one per track m).  nll stays the model's own at any temperature.
@@ -707,7 +723,10 @@ def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub,
     (common.given_codes).  sub_base (optional, one int32 on the device): the draws use the sub-counter sub + *sub_base, read by the kernel
     (mnn_nade_sample_temps_at): a captured launch follows the cell.  max_notes (optional, mnn_nade_sample_caps_at): at most that many ones per
     track and row -- an int, or a sequence read like a temperature sequence (per track, or by visible index), None entries uncapped; given
-    ones count, a free visible of an exhausted track is a settled 0 that uses no uniform.  None: the calls below, as without the argument."""
+    ones count, a free visible of an exhausted track is a settled 0 that uses no uniform.  None: the calls below, as without the argument.
+    redraws (0..255, mnn_nade_sample_redraw_at): the cap by rejection -- a row that would emit a 1 past a cap is drawn again, up to `redraws`
+    times, before the truncating scan above serves it; redraw_stats (optional int32[2] on the device) gains the (redrawn, fallback) scans.
+    redraws = 0, or caps that cannot bind: the calls below."""
     N = bias.shape[0]
     _req(bias.dtype == torch.float32 and bias.dim() == 2 and bias.stride(1) == 1 and bias.shape[1] >= tracks * (Hn + D), "sample: bias")
     _req(samples.dtype == torch.uint8 and samples.shape == (N, tracks * D) and samples.is_contiguous(), "sample: samples u8 [N,tracks*D]")
@@ -720,6 +739,13 @@ def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub,
              "sample: given u8 [N, tracks*D], contiguous")
     ts, es = (1, tracks) if track_minor else (D, 1)
     cc = _caps(max_notes, tracks, by_visible, "sample")
+    rd = _redraw(redraws, redraw_stats, cc, temperature, samples, "sample")
+    if rd is not None:
+        tt = _temps_table(temperature, tracks, by_visible, "sample")
+        call("mnn_nade_sample_redraw_at", _stream(), tracks, N, D, Hn, _ptr(bias), bias.stride(0), _ptr(w_enc), _ptr(w_dec), C.byref(tt), C.byref(cc),
+             int(seed), int(row0), int(sub), _ptr(samples), ts, tracks * D, es, _ptr(nll), _ptr(given), _sub_base(sub_base, samples, "sample"),
+             C.byref(rd))
+        return
     if cc is not None:
         tt = _temps_table(temperature, tracks, by_visible, "sample")
         call("mnn_nade_sample_caps_at", _stream(), tracks, N, D, Hn, _ptr(bias), bias.stride(0), _ptr(w_enc), _ptr(w_dec), C.byref(tt), C.byref(cc),
@@ -739,12 +765,12 @@ def nade_sample(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub,
          float(-1.0 if temperature is None else temperature), int(seed), int(row0), int(sub), _ptr(samples), ts, tracks * D, es, _ptr(nll), _ptr(given))
 
 
-def nade_sample_multi(jobs, D, Hn, temperature, row0, sub, max_notes=None):
+def nade_sample_multi(jobs, D, Hn, temperature, row0, sub, max_notes=None, redraws=0, redraw_stats=None):
     """mnn_nade_sample for up to 8 single-NADE generators in ONE launch.  job = dict(bias f32 [N, >= Hn + D] (the generator's Dense output),
     w_enc / w_dec f32 [D, Hn], seed, samples = a u8 [N, D] VIEW (any strides, the same for every job: e.g. out[:, s, :, m] of a
     [B, steps, P, M] piano-roll), nll f32 [N] or None, given = None or a u8 [N, D] view of codes with the strides of samples).
     temperature: a float, None, or a sequence with one temperature per job.  max_notes: None, an int, or a sequence with one cap (or None)
-    per job (nade_sample)."""
+    per job (nade_sample).  redraws / redraw_stats: nade_sample's (mnn_nade_sample_multi_redraw)."""
     _req(1 <= len(jobs) <= 8, "nade_sample_multi: 1..8 jobs")
     arr = (_lib.NadeSampleJob * len(jobs))()
     N = jobs[0]["bias"].shape[0]
@@ -762,6 +788,11 @@ def nade_sample_multi(jobs, D, Hn, temperature, row0, sub, max_notes=None):
         a.bias, a.ld_bias, a.w_enc, a.w_dec, a.seed, a.samples, a.nll = _ptr(b), b.stride(0), _ptr(j["w_enc"]), _ptr(j["w_dec"]), int(j["seed"]), _ptr(smp), _ptr(nll)
         a.given = _ptr(gv)
     cc = _caps(max_notes, len(jobs), False, "sample_multi")
+    rd = _redraw(redraws, redraw_stats, cc, temperature, jobs[0]["samples"], "sample_multi")
+    if rd is not None:
+        tt = _temps_table(temperature, len(jobs), False, "sample_multi")
+        call("mnn_nade_sample_multi_redraw", _stream(), len(jobs), arr, N, D, Hn, C.byref(tt), C.byref(cc), int(row0), int(sub), rs, es, C.byref(rd))
+        return
     if cc is not None:
         tt = _temps_table(temperature, len(jobs), False, "sample_multi")
         call("mnn_nade_sample_multi_caps", _stream(), len(jobs), arr, N, D, Hn, C.byref(tt), C.byref(cc), int(row0), int(sub), rs, es)
@@ -1335,7 +1366,7 @@ def _scan_call(what, ref, intro, Ti, num_steps, layers, dense_W, dense_bias, tra
 
 
 def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, given=None, state0=None,
-                  by_visible=False, max_notes=None):
+                  by_visible=False, max_notes=None, redraws=0, redraw_stats=None):
     """mnn_generate_scan: the whole sampling scan of an LSTM-(Multi)NADE generator in one call.  intro u8 [B, Ti, tracks * D]; layers = [(W, bias)]
     f32 master weights; returns samples u8 [B, num_steps, tracks * D].  given (optional): codes u8 [B, num_steps, tracks * D] in the layout of
     the samples (see nade_sample).  temperature: a float, None, or a sequence (per track, or by visible index: nade_sample).  state0 (optional, mnn_generate_scan_state): [(c0, h0) f32 [B, u]] per layer, the state the intro pass starts from."""
@@ -1345,6 +1376,10 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
     tt = _temps(temperature, tracks, by_visible, "generate_scan")
     cp, hp = _scan_state("generate_scan: state0", state0, arr, intro.shape[0], intro.device)
     cc = _caps(max_notes, tracks, by_visible, "generate_scan")
+    rd = _redraw(redraws, redraw_stats, cc, temperature, intro, "generate_scan")
+    if rd is not None:              # the cap by rejection (nade_sample): the caps entry point with the redraws behind its state
+        return launch("mnn_generate_scan_redraw", (C.byref(_temps_table(temperature, tracks, by_visible, "generate_scan")), C.byref(cc)), cp, hp,
+                      C.byref(rd))
     if cc is not None:              # polyphony caps (nade_sample): the entry point that takes both tables
         return launch("mnn_generate_scan_caps", (C.byref(_temps_table(temperature, tracks, by_visible, "generate_scan")), C.byref(cc)), cp, hp)
     if tt is not None:              # a temperature table: the one entry point that takes it, with or without an initial state
@@ -1354,7 +1389,7 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
 
 
 def generate_scan_chunk(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, state_in, state_out,
-                        given=None, step0=0, step_base=None, by_visible=False, max_notes=None):
+                        given=None, step0=0, step_base=None, by_visible=False, max_notes=None, redraws=0, redraw_stats=None):
     """mnn_generate_scan_chunk: one chunk of a generation session of an LSTM-(Multi)NADE generator.  intro u8 [B, Ti, tracks * D] or None (the
     chunk continues from state_in); num_steps >= 0 (0 with an intro: the intro pass alone -> None); state_in: [(c, h) f32 [B, u]] per layer or
     None (the zero state); state_out: likewise, written with the state behind the last step (may be the arrays of state_in).  Step st draws
@@ -1371,6 +1406,11 @@ def generate_scan_chunk(intro, num_steps, layers, dense_W, dense_bias, tracks, D
     _req(0 <= int(step0) and int(step0) + num_steps <= 1 << 32, "generate_scan_chunk: step0 + num_steps passes 2^32")
     tt = _temps_table(temperature, tracks, by_visible, "generate_scan_chunk")
     cc = _caps(max_notes, tracks, by_visible, "generate_scan_chunk")
+    rd = _redraw(redraws, redraw_stats, cc, temperature, ref, "generate_scan_chunk")
+    if rd is not None:
+        samples = launch("mnn_generate_scan_chunk_redraw", (C.byref(tt), C.byref(cc)), ci, hi, co, ho, int(step0),
+                         _sub_base(step_base, ref, "generate_scan_chunk"), C.byref(rd))
+        return samples if num_steps > 0 else None
     if cc is not None:
         samples = launch("mnn_generate_scan_chunk_caps", (C.byref(tt), C.byref(cc)), ci, hi, co, ho, int(step0),
                          _sub_base(step_base, ref, "generate_scan_chunk"))

@@ -21,7 +21,7 @@ import torch
 
 from . import ops
 from ._lib import MnnUnsupported
-from .common import DrawAt, ScanGraphs, _warm_up, check_given, graph_capture, max_notes_key, temperature_key
+from .common import DrawAt, ScanGraphs, _warm_up, check_given, graph_capture, max_notes_key, redraw_cell, redraws_key, sampling_redraws, temperature_key
 
 __all__ = ["GeneratorSession", "ModeSession"]
 
@@ -67,6 +67,7 @@ class GeneratorSession:
         refuse_host_model(x.device, "a generation session")
         self._gen, self.seed, self.row0 = gen, gen.seed, gen.row0
         self._max_notes = None
+        self._redraws = 0
         self.steps = 0
         self.batch = int(x.shape[0])
         self._graphs = collections.OrderedDict()
@@ -111,19 +112,25 @@ class GeneratorSession:
         self.steps = int(steps)
 
     # -- chunks ---------------------------------------------------------------------------------
-    def _run(self, n, given, temperature, base, max_notes=None):
+    def _run(self, n, given, temperature, base, max_notes=None, redraws=0):
         """The launches of one chunk of n steps from the static state, which they advance in place.  base: the step cell (a captured chunk:
-        the kernels add its word to their counters) or None (eager: the host adds `steps`)."""
+        the kernels add its word to their counters) or None (eager: the host adds `steps`).  redraws > 0: the chunk first zeroes the
+        generator's statistics cell (a fill node of a captured chunk)."""
         gen = self._gen
         step0 = 0 if base is not None else self.steps
+        stats = None
+        if redraws:
+            stats = redraw_cell(gen, self._cell.device)
+            stats.zero_()
         if self._scan:
             return ops.generate_scan_chunk(None, n, temperature=temperature, seed=self.seed, row0=self.row0, state_in=self._rnn, state_out=self._rnn,
-                                           given=given, step0=step0, step_base=base, max_notes=max_notes, **gen._scan_layers())
+                                           given=given, step0=step0, step_base=base, max_notes=max_notes, redraws=redraws, redraw_stats=stats,
+                                           **gen._scan_layers())
         with gen._sampling_scope():
             if not gen.det_sampling:
                 gen._ensure_packed()
             out, state, last = gen._scan_steps(gen._state_of(self._out, tuple(self._rnn)), self._last, n,
-                                               DrawAt(self.seed, self.row0, step0, base), given, temperature, max_notes)
+                                               DrawAt(self.seed, self.row0, step0, base), given, temperature, max_notes, redraws)
             for (c, h), (nc, nh) in zip(self._rnn, state.rnn_state):      # behind the last read of the static arrays
                 c.copy_(nc)
                 h.copy_(nh)
@@ -142,31 +149,47 @@ class GeneratorSession:
     def max_notes(self, value):
         self._max_notes = self._gen._max_notes(value)
 
+    # The redraws of the chunks to come (generate's redraws), beside max_notes: set between chunks, checked when set; 0, the default, or no
+    # cap: the session without them.  Against the chunk's temperature they are checked per chunk (threshold decoding cannot be redrawn).
+    @property
+    def redraws(self):
+        return self._redraws
+
+    @redraws.setter
+    def redraws(self, value):
+        self._redraws = sampling_redraws(value, 0, 1.0)
+
+    def redraw_counts(self):
+        """The generator's redraw_counts(): (redrawn, fallback) of the last chunk (or generate call) that ran on it."""
+        return self._gen.redraw_counts()
+
     def generate(self, num_steps, given=None, temperature=1.0):
         """The next num_steps steps -> u8 [B, num_steps, num_output].  given: the chunk's codes u8 [B, num_steps, num_output] as generate's
         (None: every cell free); temperature: as generate's, and free to change from chunk to chunk.  The chunk runs under the session's
-        max_notes."""
+        max_notes and redraws."""
         n, given, temperature = _chunk_arguments(self._gen, self.batch, self.steps, num_steps, given, temperature)
         max_notes = self._max_notes
+        redraws = sampling_redraws(self._redraws, max_notes, temperature)
         gen = self._gen
+        gen._redraw_live = redraws > 0
         if given is not None:
             given = given.to(self._cell.device).contiguous()
         if not ScanGraphs.enabled(self._cell):
-            out = self._run(n, given, temperature, None, max_notes)
+            out = self._run(n, given, temperature, None, max_notes, redraws)
             self.steps += n
             return out
-        key = (n, given is not None) + temperature_key(temperature) + max_notes_key(max_notes)
+        key = (n, given is not None) + temperature_key(temperature) + max_notes_key(max_notes) + redraws_key(redraws)
         ent = self._graphs.get(key)
         if ent is None:
             static_g = None if given is None else given.clone()
             snap = self.snapshot()
             w = min(n, 2)                            # a short eager run: kernel attributes and workspaces exist before the capture
-            _warm_up(lambda: self._run(w, None if static_g is None else static_g[:, :w].contiguous(), temperature, self._cell, max_notes))
+            _warm_up(lambda: self._run(w, None if static_g is None else static_g[:, :w].contiguous(), temperature, self._cell, max_notes, redraws))
             self.restore(snap)
             g = torch.cuda.CUDAGraph()
             gen._packed_step = -1                    # pack inside the graph: a replay always sees the current weights
             with graph_capture(g, capture_error_mode="thread_local"):
-                out = self._run(n, static_g, temperature, self._cell, max_notes)
+                out = self._run(n, static_g, temperature, self._cell, max_notes, redraws)
             gen._packed_step = -1                    # the packed copies now live in the graph's pool
             ent = self._graphs[key] = (g, static_g, out)
             while len(self._graphs) > MAX_GRAPHS:
@@ -202,6 +225,7 @@ class ModeSession:
         self._model = model
         self.steps = 0
         self._max_notes = None
+        self._redraws = 0
         if model._x_encoded is None:
             MultINNCore._build_all(model, "generate")
         self._subs = [g.session(x) for g, x in zip(model.generators, model._generator_inputs())]
@@ -231,9 +255,28 @@ class ModeSession:
             s.max_notes = k
         self._max_notes = value
 
+    # The redraws of the chunks to come, as GeneratorSession's: checked when set, handed to every generator's session (one without a cap
+    # ignores them).
+    @property
+    def redraws(self):
+        return self._redraws
+
+    @redraws.setter
+    def redraws(self, value):
+        value = sampling_redraws(value, 0, 1.0)
+        for s in self._subs:
+            s.redraws = value
+        self._redraws = value
+
+    def redraw_counts(self):
+        """(redrawn, fallback) of the last chunk, summed over the generators."""
+        counts = [s.redraw_counts() for s in self._subs]
+        return sum(c[0] for c in counts), sum(c[1] for c in counts)
+
     def generate(self, num_steps, given=None, given_mask=None, temperature=1.0):
         """The next num_steps steps -> u8 [B, num_steps, P, M].  given u8 [B, num_steps, P, M] / given_mask / temperature: as the mode's
-        generate, checked once per chunk, and free to change from chunk to chunk.  The chunk runs under the session's max_notes."""
+        generate, checked once per chunk, and free to change from chunk to chunk.  The chunk runs under the session's max_notes and
+        redraws."""
         m = self._model
         n = _num_steps(self.steps, num_steps, max(s._gen.subs_per_step for s in self._subs))
         temperature, cond, _ = m._generate_arguments(n, given, given_mask, temperature)
