@@ -626,6 +626,31 @@ int mnn_rbm_raise_given(mnn_stream_t s, int N, int D, int Hn, int n_chains, int 
                         int ld_bh, const float* bv, int ld_bv, const uint8_t* v, uint64_t seed, uint32_t row0, const uint32_t* row_ids,
                         float* log_z, float* log_w, uint8_t* v_out, float* stats, void* workspace, const uint8_t* given, int ld_given);
 
+/* The NADE importance estimator (added without a version bump; DESIGN.md section 4 "NADE importance estimator"): log p(x_G) of a partly
+ * given NADE row, G its given cells and F its free ones, so that NLL(x) + log p(x_G) = -log p(x_F | x_G) with NLL(x) the exact row of
+ * mnn_nade_logprob_fwd.  Operands are mnn_nade_sample's: bias [N, ld_bias] holds b_enc of track m at column m Hn and b_dec at tracks Hn + m D,
+ * the weights are [tracks, D, Hn]; given u8 [tracks][N, D] (g_track_stride elements between tracks) are the codes -- 0 / 1 given, 255 free.
+ * A PARTICLE is one clamped scan of one (row, track): a given visible takes its code, is not drawn (its uniform is left unused) and moves
+ * the state like a draw; a free visible is drawn u < det_sigmoid(logit), u = Philox(stream, row = row_ids ? row_ids[n] : row0 + n, sub = c,
+ * elem = m D + i) -- the dot product and the draw of mnn_nade_sample at temperature 1.  log w_c = sum_{i in G} log(1e-6 + q_i), q_i the
+ * conditional of the emitted value: the term mnn_nade_sample's nll sums, so a row with every cell given has log w = -nll.  E[w] = p(x_G).
+ *   data == NULL, the LOWER side: C = n_particles proposal particles on stream MNN_STREAM_NADE_IS; log_pg = logsumexp_c(log w_c) - log C is
+ *   biased LOW (E[p^] = p(x_G)), and so is the NLL built from it: optimistic, the bias statement of mnn_rbm_ais.
+ *   data u8 [tracks][N, D] (d_track_stride), the UPPER side: the stream is MNN_STREAM_NADE_IS_DATA, particle 0 is not drawn -- its free cells
+ *   are data's (nonzero = 1) and it consumes no uniform --, particles 1 .. C - 1 are proposal draws.  With x_F ~ p(. | x_G) the C particles
+ *   are a draw from the extended target whose ratio to the proposal is p^ / p(x_G), so E[log p^] >= log p(x_G): conservative in expectation
+ *   over data drawn from the model, not a bound per row -- the two caveats of mnn_rbm_raise.  The two sides of one seed share no uniform.
+ * Outputs: log_pg f32 [tracks, N]; log_w f32 [tracks, N, C] (optional); v_out u8 [tracks, N, C, D] the particles' vectors (optional; without
+ * it a scan stops behind the row's last given visible, which changes no bit of log_w); stats f32 [tracks, N, 2] (optional): the effective
+ * sample size (sum w)^2 / sum w^2 and the standard error of log_pg by the delta method (inf with one particle), mnn_rbm_ais's formulas.
+ * A particle's log w depends on its own counters only (not on C, N, or the rows launched with it); a row's particles are reduced in a fixed
+ * order by a second launch.  Requires D <= 1536, 0 < Hn <= 256, n_particles >= 1, non-null given; workspace: mnn_nade_given_is_workspace_bytes. */
+enum { MNN_STREAM_NADE_IS = 11, MNN_STREAM_NADE_IS_DATA = 12 };
+size_t mnn_nade_given_is_workspace_bytes(int tracks, int N, int n_particles);
+int mnn_nade_given_is(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc, const float* w_dec,
+                      const uint8_t* given, long g_track_stride, const uint8_t* data, long d_track_stride, int n_particles, uint64_t seed,
+                      uint32_t row0, const uint32_t* row_ids, float* log_pg, float* log_w, uint8_t* v_out, float* stats, void* workspace);
+
 /* dz = dy * y * (1 - y) over n f32 words (dz may alias dy): backward of the sigmoid Dense layers of the feedback module (dnn.py:60-76). */
 int mnn_sigmoid_grad_f32(mnn_stream_t s, long n, const float* dy, const float* y, float* dz);
 

@@ -211,6 +211,9 @@ SIGNATURES["mnn_nade_sample_redraw_at"] = (_i, SIGNATURES["mnn_nade_sample_caps_
 SIGNATURES["mnn_nade_sample_multi_redraw"] = (_i, SIGNATURES["mnn_nade_sample_multi_caps"][1] + [_p])
 SIGNATURES["mnn_generate_scan_redraw"] = (_i, SIGNATURES["mnn_generate_scan_caps"][1] + [_p])
 SIGNATURES["mnn_generate_scan_chunk_redraw"] = (_i, SIGNATURES["mnn_generate_scan_chunk_caps"][1] + [_p])
+# the NADE importance estimator (additions without a version bump)
+SIGNATURES["mnn_nade_given_is_workspace_bytes"] = (_sz, [_i, _i, _i])
+SIGNATURES["mnn_nade_given_is"] = (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _l, _p, _l, _i, _u64, _u32, _p, _p, _p, _p, _p, _p])
 TEMPS_MAX = 8              # MNN_TEMPS_MAX
 REDRAWS_MAX = 255          # mnn_redraw.tries
 

@@ -10,8 +10,8 @@
 // Sampling (one wave/row):   deterministic summation order + IEEE-only sigmoid so Bernoulli draws are
 //                            bit-identical to oracle/det_ref.c.
 #include "common.h"
+#include "nade_scan.h"       // NADE_EPS, the DPP xor steps, wave_xor_sum and the draw of the sampling contract (shared with nade_is.hip)
 
-#define NADE_EPS 1e-6f
 #define LN2 0.6931471805599453f
 
 __device__ __forceinline__ float fast_ln(float x) { return __builtin_amdgcn_logf(x) * LN2; }
@@ -41,17 +41,8 @@ __device__ __forceinline__ void nade_zero_rows(float* __restrict__ d_bias, int l
 // v_permlane16_swap, DPP/swizzle xor steps): ~2.5 VALU ops per output instead of a 6-step reduction each,
 // and lane L ends up owning the logit of (row L>>3, visible L&7).
 // ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ float dpp_xor8(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, false)); }
+// (dpp_xor8 / dpp_xor4 / dpp_xor2 / dpp_xor1: nade_scan.h)
 __device__ __forceinline__ float swz_xor4(float x) { return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(x), 0x101F)); }
-// x[l ^ 4] without the LDS crossbar (a ds_swizzle is ~100 cycles on a dependent chain): two row shifts by four lanes, each written to the
-// banks (groups of four lanes) it is right for -- row_shl:4 (lane l reads l + 4) into banks 0 and 2, row_shr:4 (l - 4) into banks 1 and 3
-__device__ __forceinline__ float dpp_xor4(float x) {
-    int t = __builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x104, 0xf, 0x5, false);
-    t = __builtin_amdgcn_update_dpp(t, __float_as_int(x), 0x114, 0xf, 0xa, false);
-    return __int_as_float(t);
-}
-__device__ __forceinline__ float dpp_xor2(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xf, 0xf, false)); }
-__device__ __forceinline__ float dpp_xor1(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, false)); }
 
 // Halving butterfly, applied in two parts.  rows8(): the 8 per-row partials of ONE visible -> one value per
 // lane, lane bits 5..3 selecting the row (3 steps: permlane32_swap, permlane16_swap, xor-8).  vis8(): the 8
@@ -754,39 +745,7 @@ extern "C" int mnn_nade_logprob_bwd(mnn_stream_t s, int tracks, int N, int D, in
 //     (the same sum as adding inside the loop), samples leave in one strided pass.
 // 487 -> see profiles/round1_d_notes.md (us per call at D = 440, Hn = 256).
 // ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_xor_sum(float x) {
-    {
-        auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);     // x[l] + x[l ^ 32]
-        x = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-    {
-        auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);     // x[l] + x[l ^ 16]
-        x = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-    x = x + dpp_xor8(x);
-    x = x + dpp_xor4(x);
-    x = x + dpp_xor2(x);
-    x = x + dpp_xor1(x);
-    return x;
-}
-
-// The draw 1[u < det_sigmoid(x)] (or det_sigmoid(x) >= 1/2) decided WITHOUT the 35-operation deterministic sigmoid on the serial chain:
-// the hardware exp2 / rcp give the probability to ~1e-5 relative (argument scaling of exp2 included), which settles every draw
-// whose uniform is not within 1e-4 (relative) of it; the rare rest takes the exact comparison.  The outcome is the exact one always.
-__device__ __forceinline__ float sig_approx(float x) {
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-x * 1.4426950408889634f));
-}
-__device__ __forceinline__ bool draw_below(float u, float x) {          // u < det_sigmoid(x); wave-uniform operands
-    const float r = sig_approx(x);
-    const float d = u - r;
-    if (__builtin_amdgcn_ballot_w64(fabsf(d) > 1e-4f * r + 1e-30f) != 0ull) return __builtin_amdgcn_ballot_w64(d < 0.f) != 0ull;
-    return __builtin_amdgcn_ballot_w64(u < det_sigmoid(x)) != 0ull;
-}
-__device__ __forceinline__ bool prob_at_least_half(float x) {           // det_sigmoid(x) >= 0.5f
-    const float d = sig_approx(x) - 0.5f;
-    if (__builtin_amdgcn_ballot_w64(fabsf(d) > 1e-4f) != 0ull) return __builtin_amdgcn_ballot_w64(d > 0.f) != 0ull;
-    return __builtin_amdgcn_ballot_w64(det_sigmoid(x) >= 0.5f) != 0ull;
-}
+// wave_xor_sum, and the draw decided without the deterministic sigmoid on the serial chain (draw_below, prob_at_least_half): nade_scan.h
 
 // one (generator, track) of a launch: where its biases, weights, uniforms and outputs are
 struct SampleJob {

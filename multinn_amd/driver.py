@@ -158,7 +158,7 @@ def _captured_step(generator, xb, optimizer, lr, max_graphs=8, lengths=None):
     return graphs[key]
 
 
-def evaluate(generator, X, lengths, batch_size, piece_size, device=None, nll="loss", ais=None, given_mask=None):
+def evaluate(generator, X, lengths, batch_size, piece_size, device=None, nll="loss", ais=None, given_mask=None, partial="refuse"):
     """utils/training.py:180-213 collect_metrics: mean generator NLL per valid row over all windows.
     nll="loss" (default): the training loss (an RBM generator's is the CD cost, a difference of free energies, not a likelihood).
     nll="ais": the model's estimate_nll(x, lengths, **ais) -- exact for NADE generators, annealed importance sampling for RBM generators
@@ -167,19 +167,23 @@ def evaluate(generator, X, lengths, batch_size, piece_size, device=None, nll="lo
     nll="bracket": estimate_nll(method="both"); returns {"lower": the "ais" mean, "upper": the "raise" mean, "gap": upper - lower}, each
     equal to its own call's value: a gap well above its noise says the ladder (ais: num_betas) is too short for either end to be trusted.
     given_mask (optional, with nll "ais" / "raise" / "bracket"): a batch-independent bool mask, [M] or [P, M], passed to every window's
-    estimate_nll -- the mean CONDITIONAL NLL per valid step of the cells outside the mask given those under it (and the past)."""
+    estimate_nll -- the mean CONDITIONAL NLL per valid step of the cells outside the mask given those under it (and the past).
+    partial ("refuse" or "importance", with given_mask): estimate_nll's -- "importance" estimates a NADE that the mask leaves partly given
+    by importance sampling (ais: num_chains particles per row) where "refuse" raises; nll "bracket" then reports its two sides and their gap."""
     import torch
     methods = {"ais": "ais", "raise": "raise", "bracket": "both"}
     if nll != "loss" and nll not in methods:
         raise ValueError(f"nll must be 'loss', 'ais', 'raise' or 'bracket', got {nll!r}")
     cond = {}
+    if partial not in ("refuse", "importance"):
+        raise ValueError(f"partial must be 'refuse' or 'importance', got {partial!r}")
     if given_mask is not None:
         if nll == "loss":
             raise ValueError("given_mask needs nll 'ais', 'raise' or 'bracket': the training loss has no conditional form")
         given_mask = torch.as_tensor(given_mask)
         if given_mask.dtype != torch.bool or given_mask.dim() not in (1, 2):
             raise ValueError(f"given_mask must be a batch-independent bool mask [M] or [P, M], got {given_mask.dtype} {tuple(given_mask.shape)}")
-        cond = dict(given_mask=given_mask)
+        cond = dict(given_mask=given_mask) if partial == "refuse" else dict(given_mask=given_mask, partial=partial)
     tot, cnt, tot_upper = 0.0, 0, 0.0
     ids = np.arange(X.shape[0])
     for w in iter_windows(ids, lengths, X.shape[1], batch_size, piece_size):

@@ -159,6 +159,30 @@ NADE_MASK_REFUSAL = ("the conditional NLL of a NADE under a mask that leaves it 
                      "given one.  A mask under which every NADE is wholly given or wholly free is exact")
 
 
+NLL_PARTIAL = ("refuse", "importance")
+
+
+def nll_partial(partial, num_chains=None):
+    """estimate_nll's `partial`: what a NADE does under a mask that leaves it partly given -- "refuse" (MnnUnsupported, NADE_MASK_REFUSAL) or
+    "importance" (the importance estimator of DESIGN.md section 4, num_chains particles per row).  ValueError for anything else, and for
+    fewer than one particle where they would be drawn (num_chains given); raised before any device work."""
+    if partial not in NLL_PARTIAL:
+        raise ValueError(f"partial must be 'refuse' or 'importance', got {partial!r}")
+    if partial == "importance" and num_chains is not None and (isinstance(num_chains, bool) or not isinstance(num_chains, int) or num_chains < 1):
+        raise ValueError(f"partial='importance' draws num_chains particles per row: an integer >= 1, got {num_chains!r}")
+    return partial
+
+
+def nade_is_side(side, bias, w_enc, w_dec, tracks, D, Hn, codes, tgt, rows, part, num_chains, seed, ids):
+    """The importance estimates of one side for the partly given tracks `part` of a (Multi)NADE: one launch over all tracks (codes u8 [tracks,
+    n, D], all 255 on the tracks that are not in `part`: nothing is scanned there), particles keyed by the row ids like an RBM's chains.
+    side "ais": the lower side; "raise": the upper side, particle 0's free cells the targets tgt.  rows[m]: the exact NLL(x) rows of track m.
+    -> {m: NllEstimate(rows[m] + log p^(x_G), log_z = log p^(x_G), free_energy = rows[m], row standard errors, row ESS)}."""
+    stats = torch.empty((tracks, bias.shape[0], 2), device=bias.device)
+    log_pg = ops.nade_given_is(bias, w_enc, w_dec, tracks, D, Hn, codes, num_chains, seed, row_ids=ids, data=tgt if side == "raise" else None, stats=stats)
+    return {m: NllEstimate(rows[m] + log_pg[m], log_pg[m], rows[m], stats[m, :, 1], stats[m, :, 0]) for m in part}
+
+
 def refuse_host_model(device, what):
     """MnnUnsupported (an MnnError and a NotImplementedError) for a model that does not live on a ROCm device: raised before any device work."""
     if device is not None and torch.device(device).type != "cuda":
@@ -469,7 +493,7 @@ class RnnEstimator(Generator):
             self._grad_sumsq = compute_gradients(optimizer, self.store, self.clip_norm, lr, reduce=False)
         return capture_train_step(feed, step, warmup, [self], lambda: [self.store], split=dp_active(), fwd_bwd=fwd_bwd, opt=opt, **kw)
 
-    def estimate_nll(self, x, lengths=None, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais", given_mask=None):
+    def estimate_nll(self, x, lengths=None, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais", given_mask=None, partial="refuse"):
         """NLL of every step of x [B, T, F] (or [B, T, P, M]) given the steps before it: builds in eval mode (keep_prob 1) on inputs = x
         shifted by one all-zero step, targets = x, and returns an NllEstimate over the valid rows.  RnnNade: exact (the AIS arguments are
         ignored).  RnnRBM: AIS (see RnnRBM._nll_rows_built).  method: "ais" (biased low), "raise" (reverse AIS from the target rows, the same
@@ -478,12 +502,19 @@ class RnnEstimator(Generator):
         teacher-forced on all of x_<t, the cells under the mask given.  RBM estimators: the clamped estimators (DESIGN.md section 4 "Clamped
         AIS"), any mask; a track wholly given adds exactly 0 and runs no chain.  NADE estimators: exact where every NADE is wholly given or
         wholly free, MnnUnsupported otherwise.  The sum over t is NOT -log p(x_free | x_given) of the sequence: later given cells say
-        something about earlier free ones, which no teacher-forced row sees."""
+        something about earlier free ones, which no teacher-forced row sees.
+        partial ("refuse", the default, or "importance"; RBM estimators accept and ignore it -- they take any mask): what a NADE does under
+        a mask that leaves it partly given.  "importance": the importance estimator (DESIGN.md section 4 "NADE importance estimator") --
+        row t of a partly given track is NLL(x_t) + log p^(x_t,given), with log p^ from num_chains clamped ancestral scans per row (seed:
+        default self.seed; particles keyed by the row ids like an RBM's chains).  method "ais": the lower side, biased LOW; "raise": the
+        upper side (one particle carries the targets' free cells), biased HIGH in expectation over data drawn from the model, not a bound
+        per row; "both": the NllBracket.  The estimate's log_z is log p^(x_given) and its free_energy the exact NLL(x) of the whole row."""
         nll_sides(method)
+        nll_partial(partial)
         cond = None
         if given_mask is not None:                                  # host checks and refusals, before any device work
             cond = given_mask_tracks(given_mask, x.shape, getattr(self, "num_tracks", 1))
-            self._refuse_nll_given(cond[2], cond[3])
+            self._refuse_nll_given(cond[2], cond[3], partial, num_chains)
         refuse_host_model(self.store.device, "estimate_nll")
         dev = self.store.device if self.store.device is not None else default_device()
         inputs, targets = shifted_sequences(x.to(dev))
@@ -492,10 +523,13 @@ class RnnEstimator(Generator):
         if cond is not None:
             mask4, shape4, whole, some = cond
             kw["given"] = (given_codes(targets.reshape(shape4), mask4, shape4).reshape(targets.shape), whole, some)
+        if partial != "refuse":
+            kw["partial"] = partial
         return self._nll_rows_built(num_chains=num_chains, num_betas=num_betas, betas=betas, seed=seed, method=method, **kw)
 
-    def _refuse_nll_given(self, whole, some):
-        """MnnUnsupported for a conditional-NLL mask this estimator cannot honour (per track of it: every / any cell given); host only."""
+    def _refuse_nll_given(self, whole, some, partial="refuse", num_chains=None):
+        """MnnUnsupported for a conditional-NLL mask this estimator cannot honour (per track of it: every / any cell given); host only.
+        partial / num_chains: estimate_nll's (nll_partial) -- an estimator that takes any mask ignores them."""
 
     def _step_input(self, B, device):
         """[B, ld0] staging row block of single_step: the zero padding beyond the input width is written once, every step converts its
@@ -864,25 +898,50 @@ class RnnNade(RnnEstimator):
         r = [self._nll_tm[m][self._idx()] for m in range(self.num_tracks)]
         return r[0] if self.num_tracks == 1 else r
 
-    def _refuse_nll_given(self, whole, some):
+    def _refuse_nll_given(self, whole, some, partial="refuse", num_chains=None):
         if any(s and not w for w, s in zip(whole, some)):
-            raise MnnUnsupported(NADE_MASK_REFUSAL)
+            if nll_partial(partial, num_chains) == "refuse":
+                raise MnnUnsupported(NADE_MASK_REFUSAL)
 
-    def _nll_rows_built(self, method="ais", given=None, **ais):
+    def _nll_rows_built(self, method="ais", given=None, partial="refuse", num_chains=64, seed=None, **ais):
         """The exact NLL rows of the last build (API order, valid rows), summed over the NADE tracks: an NllEstimate with stderr 0, whatever
         the method ("both": the bracket of that one estimate with itself).  given (optional): (codes, whole, some) as RnnRBM._nll_rows_built
         takes them -- the NADE of a wholly given track adds 0, that of a wholly free track its rows (the tracks of a step are independent
-        given the history); any other mask is refused."""
-        nll_sides(method)
+        given the history); any other mask is refused, or with partial "importance" estimated: a partly given track adds NLL(x) + log
+        p^(x_given) (nade_is_side: num_chains particles per row keyed by the row ids of build, seed default self.seed, the tracks apart
+        by their elements m D + i), the parts combined by NllEstimate.total -- so log_z sums the log p^ and free_energy the exact rows of
+        the partly given tracks.  The remaining AIS arguments are ignored."""
+        sides = nll_sides(method)
         idx = self._idx()
-        free = range(self.num_tracks)
+        M = self.num_tracks
+        free, part = range(M), []
         if given is not None:
-            self._refuse_nll_given(given[1], given[2])
+            self._refuse_nll_given(given[1], given[2], partial, num_chains)
             free = [m for m in free if not given[1][m]]
+            part = [m for m in free if given[2][m]]
             if not free:
                 return given_nll_result(method, idx.numel(), idx.device)
-        est = NllEstimate(sum(self._nll_tm[m][idx] for m in free))
-        return nll_result(method, (est, est))
+        if not part or idx.numel() == 0:
+            est = NllEstimate(sum(self._nll_tm[m][idx] for m in free))
+            return nll_result(method, (est, est))
+        cx = self._ctx
+        B, T, D, Hn = cx["B"], cx["T"], self.num_dims, self.num_hidden[-1]
+        dev = cx["out"].device
+        # the codes of the partly given tracks as time-major planes (track-minor features d M + m: build's reshape of the targets); every
+        # other track all free: its scans have nothing to weigh
+        planes = given[0].to(torch.uint8).reshape(B, T, D, M).permute(3, 1, 0, 2).reshape(M, T * B, D)[:, idx]
+        codes = torch.full_like(planes, 255)
+        codes[part] = planes[part]
+        tgt = cx["v"].view(M, T * B, D)[:, idx].contiguous()
+        bias = cx["out"][idx].contiguous()
+        ids = self._row_ids(B, T, dev)[idx].to(torch.int32).contiguous()
+        rows = {m: self._nll_tm[m][idx] for m in free}
+        s0 = self.seed if seed is None else seed
+        out = []
+        for side in sides:
+            est = nade_is_side(side, bias, self.store["nade/w_enc"], self.store["nade/w_dec"], M, D, Hn, codes, tgt, rows, part, num_chains, s0, ids)
+            out.append(NllEstimate.total([est[m] if m in est else NllEstimate(rows[m]) for m in free]))
+        return nll_result(method, out)
 
     @property
     def cond_probs(self):
@@ -1345,7 +1404,7 @@ class RnnRBM(RnnEstimator):
     def build_metrics(self, targets, predictions, cond_probs=None, log_probs=None):
         return self._rbm.build_metrics(targets, predictions, cond_probs, log_probs)
 
-    def _nll_rows_built(self, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais", given=None):
+    def _nll_rows_built(self, num_chains=64, num_betas=1000, betas=None, seed=None, method="ais", given=None, partial="refuse"):
         """AIS NLL of the last build's valid rows (API order): the SUM over the tracks (independent given the history) of
         -log p(v_t | v_<t) = F_t(v_t) + log Z_t with the row's CONDITIONAL biases bh_t, bv_t (the distribution sample() draws from, whatever
         bias_mode trained) and log Z_t estimated by RBM.log_partition -- the chains keyed by the global row ids of build (_row_ids), track m
@@ -1354,8 +1413,10 @@ class RnnRBM(RnnEstimator):
         given (optional): (codes u8 [B, T, D * M] in the inputs' layout -- the targets at the given cells, 255 at the free ones:
         common.given_codes --, whole, some: per track, whether every / any cell is given: common.given_tracks) -> the conditional rows
         -log p(v_t,free | v_t,given, v_<t) = F_t(v_t) + log Z_t,c, the stationary distribution of the clamped chain generate(given=) runs at
-        that step.  A wholly given track adds exactly 0 and runs no chain; a track with no given cell is estimated as without `given`."""
+        that step.  A wholly given track adds exactly 0 and runs no chain; a track with no given cell is estimated as without `given`.
+        partial: estimate_nll's, accepted and ignored -- the clamped estimators take any mask."""
         sides = nll_sides(method)
+        nll_partial(partial)
         cx = self._ctx
         B, T = cx["B"], cx["T"]
         bh_t, bv_t = self._split(cx["out"])

@@ -557,7 +557,7 @@ class MultINNCore(Model):
         ls = [g.metrics["batch/loss"].reshape(()) for g in self._generators]
         return ls[0] if len(ls) == 1 else torch.stack(ls).mean()
 
-    def estimate_nll(self, x, lengths=None, given_mask=None, **ais):
+    def estimate_nll(self, x, lengths=None, given_mask=None, partial="refuse", **ais):
         """The JOINT NLL of every valid time step of x [B, T, P, M] given the steps before it, summed over this mode's generators (each
         models its part of the step given the past: the per-track generators of jamming / feedback, the one generator of joint mode):
         builds in eval mode and returns a generators.NllEstimate (per valid row in API order; `mean` per valid step).  RBM generators are
@@ -572,10 +572,14 @@ class MultINNCore(Model):
         is split per track, seeds as without it; a wholly given track adds exactly 0 and runs no chain -- these modes factorise over the
         tracks of a step, so their conditional is the free tracks' marginal.  NADE generators are exact where every NADE is wholly given
         or wholly free and refused (MnnUnsupported) otherwise; the joint NADE takes all or nothing.  The sum of the rows over t is NOT
-        -log p(x_free | x_given) of the sequence: later given cells say something about earlier free ones."""
-        from .generators import nll_sides, total_nll, refuse_host_model
+        -log p(x_free | x_given) of the sequence: later given cells say something about earlier free ones.
+        partial ("refuse", the default, or "importance"): passed to every generator (RnnEstimator.estimate_nll).  With "importance" a partly
+        given NADE -- one track of the joint NADE given the others, a pitch range of any NADE -- is estimated by importance sampling with
+        ais's num_chains particles per row: method "ais" the lower side, "raise" the upper, "both" the bracket; RBM generators ignore it."""
+        from .generators import nll_sides, nll_partial, total_nll, refuse_host_model
         method = ais.get("method", "ais")
         nll_sides(method)
+        nll_partial(partial)
         if self._encoder_type != "Pass":
             raise MnnUnsupported("estimate_nll through DBN encoders is not implemented: their generators' likelihood is over codes, not "
                                  "piano-roll cells")
@@ -587,14 +591,15 @@ class MultINNCore(Model):
                 raise ValueError("estimate_nll(given_mask=) takes x [B, T, P, M]")
             split = self._nll_given_split(*given_tracks(given_mask, tuple(x.shape)))
             for g, (_, whole, some) in zip(self._generators, split):
-                g._refuse_nll_given(whole, some)
+                g._refuse_nll_given(whole, some, partial, ais.get("num_chains", 64))
         refuse_host_model(self.device, "estimate_nll")
         self.build(x, lengths=lengths, is_train=False, mode="eval")
         seed = ais.pop("seed", None)
         given = [{}] * len(self._generators)
         if split is not None:
             codes = given_codes(self._x, given_mask, tuple(self._x.shape))
-            given = [dict(given=(take(codes), whole, some)) for take, whole, some in split]
+            more = {} if partial == "refuse" else dict(partial=partial)
+            given = [dict(given=(take(codes), whole, some), **more) for take, whole, some in split]
         return total_nll(method, [g._nll_rows_built(seed=None if seed is None else seed + i, **kw, **ais)
                                   for i, (g, kw) in enumerate(zip(self._generators, given))])
 

@@ -804,6 +804,49 @@ def nade_sample_multi(jobs, D, Hn, temperature, row0, sub, max_notes=None, redra
     call("mnn_nade_sample_multi", _stream(), len(jobs), arr, N, D, Hn, float(-1.0 if temperature is None else temperature), int(row0), int(sub), rs, es)
 
 
+def nade_given_is(bias, w_enc, w_dec, tracks, D, Hn, given, num_particles, seed, row0=0, row_ids=None, data=None, log_pg=None, log_w=None,
+                  v_out=None, stats=None):
+    """Importance-sampling estimate of log p(x_G) per (track, row) of a partly given NADE (mnn_nade_given_is; DESIGN.md section 4 "NADE
+    importance estimator").  bias f32 [N, >= tracks * (Hn + D)] and the weights [tracks, D, Hn] as nade_sample takes them; given u8
+    [tracks, N, D]: the codes, 0 / 1 given, 255 free (common.given_codes, one contiguous plane per track).  C = num_particles clamped scans
+    per (row, track), keyed by (seed, row id, particle): row ids row0 + n, or row_ids int32 [N].  data None: the lower side -- log_pg =
+    logsumexp_c(log w_c) - log C is biased LOW.  data u8 [tracks, N, D]: the upper side -- particle 0's free cells are data's, the others
+    are drawn on a stream of their own; biased HIGH in expectation over data drawn from the model, not a bound per row.  Returns log_pg f32
+    [tracks, N] (allocated if not given); optional outputs: log_w f32 [tracks, N, C], v_out u8 [tracks, N, C, D] the particles' vectors,
+    stats f32 [tracks, N, 2] = (effective sample size, standard error of log_pg; inf with one particle)."""
+    what = "nade_given_is"
+    _req(isinstance(tracks, int) and isinstance(D, int) and isinstance(Hn, int) and tracks >= 1 and 1 <= D <= 1536 and 1 <= Hn <= 256,
+         what + ": tracks >= 1, 1 <= D <= 1536, 1 <= Hn <= 256")
+    _req(torch.is_tensor(bias) and bias.dtype == torch.float32 and bias.dim() == 2 and bias.stride(1) == 1 and bias.shape[0] >= 1
+         and bias.shape[1] >= tracks * (Hn + D) and (bias.stride(0) >= bias.shape[1] or bias.shape[0] == 1), what + ": bias f32 [N, >= tracks * (Hn + D)]")
+    N = bias.shape[0]
+    for w in (w_enc, w_dec):
+        _req(torch.is_tensor(w) and w.dtype == torch.float32 and w.is_contiguous() and w.numel() == tracks * D * Hn, what + ": weights f32 [tracks, D, Hn]")
+    for t, name in ((given, "given"), (data, "data")):
+        _req((t is None and name == "data") or (torch.is_tensor(t) and t.dtype == torch.uint8 and tuple(t.shape) == (tracks, N, D) and t.is_contiguous()),
+             f"{what}: {name} u8 [tracks, N, D], contiguous")
+    S = int(num_particles)
+    _req(S >= 1, what + ": num_particles >= 1")
+    _req(tracks * N * S * D < 2 ** 62, what + ": too many particles")
+    if row_ids is not None:
+        _req(torch.is_tensor(row_ids) and row_ids.dtype == torch.int32 and row_ids.numel() == N and row_ids.is_contiguous(), what + ": row_ids int32 [N]")
+    dev = bias.device
+    for t in (w_enc, w_dec, given, data, row_ids):
+        _req(t is None or t.device == dev, what + ": every operand on bias's device")
+    for t, shape, dt, name in ((log_pg, (tracks, N), torch.float32, "log_pg f32 [tracks, N]"), (log_w, (tracks, N, S), torch.float32, "log_w f32 [tracks, N, C]"),
+                               (v_out, (tracks, N, S, D), torch.uint8, "v_out u8 [tracks, N, C, D]"),
+                               (stats, (tracks, N, 2), torch.float32, "stats f32 [tracks, N, 2]")):
+        if t is not None:
+            _req(t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, what + ": " + name)
+    _ptr(bias)                                                       # no CPU path: refuse host tensors before allocating anything
+    if log_pg is None:
+        log_pg = torch.empty((tracks, N), device=dev)
+    ws = torch.empty(_lib.load().mnn_nade_given_is_workspace_bytes(tracks, N, S), dtype=torch.uint8, device=dev)
+    call("mnn_nade_given_is", _stream(), tracks, N, D, Hn, _ptr(bias), bias.stride(0) if N > 1 else bias.shape[1], _ptr(w_enc), _ptr(w_dec),
+         _ptr(given), N * D, _ptr(data), N * D, S, int(seed), int(row0), _ptr(row_ids), _ptr(log_pg), _ptr(log_w), _ptr(v_out), _ptr(stats), _ptr(ws))
+    return log_pg
+
+
 # ------------------------------------------------------------------------------------------------
 def _ldb(b, n):
     _req(b.dtype == torch.float32 and b.dim() == 2 and b.stride(1) == 1 and b.shape[1] >= n, "rbm: bias must be f32 [N or 1, n]")
