@@ -475,6 +475,35 @@ int mnn_nade_sample_redraw_at(mnn_stream_t s, int tracks, int N, int D, int Hn, 
                               const uint32_t* sub_base, const mnn_redraw* redraw);
 int mnn_nade_sample_multi_redraw(mnn_stream_t s, int njobs, const mnn_nade_sample_job* jobs, int N, int D, int Hn, const mnn_temps* temps,
                                  const mnn_caps* caps, uint32_t row0, uint32_t sub, long s_row_stride, int s_elem_stride, const mnn_redraw* redraw);
+/* Conditional generation by IMPORTANCE RESAMPLING: the entry points that end in _sir / _sir_at (added without a version bump).  A SCAN is one
+ * (row, track, generated step); G its given cells.  With particles = C >= 2 and codes, a scan runs C clamped ancestral scans and emits one.
+ *   Particle 0 is the scan of the call without particles: stream MNN_STREAM_NADE, the same row, sub-counter (sub + *sub_base) and element
+ *     e = m D + i, the same clamp, the same bits.
+ *   Particle c >= 1 is the same clamped scan on stream MNN_STREAM_NADE_SIR at the same row and sub-counter and element (c - 1) E4 + e, E4 =
+ *     tracks * D rounded up to a multiple of 4 (the layout of the redraw attempts on stream 10).  A particle's draws depend on its own
+ *     counters only -- not on C, N, the rows launched with it or the chunking of a session; a larger C extends a smaller C's particle set.
+ *   Weight: log w_c = sum_{i in G} log(1e-6 + q_i), q_i the conditional of the emitted (given) value at the scan's temperature -- the number
+ *     the tempered draw compares its uniform against; at temperature 1 mnn_nade_given_is's weight, term for term and in its order.
+ *   Pick: one uniform u on stream MNN_STREAM_NADE_SIR_PICK at (row, sub-counter, element = track).  In float64: e_c = exp(log w_c -
+ *     max_c log w_c), a running sum over c = 0 .. C - 1 in that order (serial, one lane), total = the last running sum; the pick is the
+ *     smallest c whose running sum exceeds u * total, C - 1 if none does.  ess = total^2 / sum_c e_c^2.
+ *   Short cut, decided on the device per scan: no given cell ordered behind a free one (nothing given, everything given, a given prefix) ->
+ *     all weights are equal; the scan runs and emits particle 0 alone: the bits of the call without particles, ess = C, pick = 0.
+ *   Outputs: the picked particle's vector through the sample strides; nll (optional) the model's own NLL of it; ess f32 and pick i32, both
+ *     [tracks, N] and written for every scan; log_w (optional, for tests) f32 [tracks, N, C]: every particle's log weight (a short-cut
+ *     scan: particle 0's, C times).
+ * The emitted vector is an approximate draw from p(x_F | x_G, past) -- exact as C grows -- conditioned on THIS step's given cells and the
+ * past only; nothing is carried across steps.  workspace: mnn_nade_sample_sir_workspace_bytes() bytes, 256-byte aligned, caller-owned: the
+ * particles between the two launches (log w and nll f32 [tracks, N, C] each, a flag per scan, the vectors u8 [tracks, N, C, D]).
+ * sir NULL or particles <= 1: mnn_nade_sample_temps_at, launch for launch.  given NULL: that call, with ess = C and pick = 0 written.
+ * Refused: particles > 1024, threshold draws (temps n = 0), a missing or short workspace, missing ess / pick, D > 1536, Hn > 256. */
+enum { MNN_STREAM_NADE_SIR = 13, MNN_STREAM_NADE_SIR_PICK = 14 };
+typedef struct { int particles; float* ess; int32_t* pick; void* workspace; size_t workspace_bytes; } mnn_sir;
+size_t mnn_nade_sample_sir_workspace_bytes(int tracks, int N, int D, int particles);
+int mnn_nade_sample_sir_at(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
+                           const float* w_dec, const mnn_temps* temps, uint64_t seed, uint32_t row0, uint32_t sub, uint8_t* samples,
+                           long s_track_stride, int s_row_stride, int s_elem_stride, float* nll, const uint8_t* given, const uint32_t* sub_base,
+                           const mnn_sir* sir, float* log_w);
 
 /* ------------------------------------------------------------------------------------------
  * RBM (models/common/rbm.py).  W f32 [D,Hn]; bh f32 [N or 1, Hn] (ld_bh = 0 broadcasts one row);
@@ -816,6 +845,20 @@ int mnn_generate_scan_chunk_redraw(mnn_stream_t s, int B, int n_intro, int num_s
                                    uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given,
                                    const float* const* c_in, const float* const* h_in, float* const* c_out, float* const* h_out, uint32_t step0,
                                    const uint32_t* step_base, const mnn_redraw* redraw);
+/* ... and with importance resampling (mnn_sir, above) on every sample call of the scan: sir->ess / sir->pick are [num_steps, tracks, B]
+ * (of this chunk), step st's sample call writes -- not accumulates -- plane st; the workspace is one step's (mnn_nade_sample_sir_workspace_bytes
+ * (tracks, B, D, particles)).  sir NULL or particles <= 1: the _redraw entry points, which call these.  Particles with caps or with redraws (tries > 0) are refused. */
+int mnn_generate_scan_sir(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                          const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D, int Hn,
+                          const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed, uint32_t row0,
+                          uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0,
+                          const float* const* h0, const mnn_redraw* redraw, const mnn_sir* sir);
+int mnn_generate_scan_chunk_sir(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
+                                int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed,
+                                uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given,
+                                const float* const* c_in, const float* const* h_in, float* const* c_out, float* const* h_out, uint32_t step0,
+                                const uint32_t* step_base, const mnn_redraw* redraw, const mnn_sir* sir);
 
 /* ------------------------------------------------------------------------------------------
  * Data-parallel exchange (the gradients of utils/training.py:151-177 as ONE flat f32 buffer): RCCL over xGMI, one

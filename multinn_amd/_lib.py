@@ -98,6 +98,11 @@ class Redraw(C.Structure):
     _fields_ = [("tries", _i), ("stats", _p)]
 
 
+class Sir(C.Structure):
+    """mnn_sir (include/multinn_hip.h)."""
+    _fields_ = [("particles", _i), ("ess", _p), ("pick", _p), ("workspace", _p), ("workspace_bytes", _sz)]
+
+
 class RbmGibbsJob(C.Structure):
     """mnn_rbm_gibbs_job (include/multinn_hip.h)."""
     _fields_ = [("W", _p), ("bh", _p), ("bv", _p), ("seed", _u64), ("v0", _p), ("p_v", _p), ("v_out", _p), ("given", _p)]
@@ -214,6 +219,12 @@ SIGNATURES["mnn_generate_scan_chunk_redraw"] = (_i, SIGNATURES["mnn_generate_sca
 # the NADE importance estimator (additions without a version bump)
 SIGNATURES["mnn_nade_given_is_workspace_bytes"] = (_sz, [_i, _i, _i])
 SIGNATURES["mnn_nade_given_is"] = (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _l, _p, _l, _i, _u64, _u32, _p, _p, _p, _p, _p, _p])
+# importance resampling (additions without a version bump): a trailing const mnn_sir* (the step op: and the optional log_w)
+SIGNATURES["mnn_nade_sample_sir_workspace_bytes"] = (_sz, [_i, _i, _i, _i])
+SIGNATURES["mnn_nade_sample_sir_at"] = (_i, SIGNATURES["mnn_nade_sample_temps_at"][1] + [_p, _p])
+SIGNATURES["mnn_generate_scan_sir"] = (_i, SIGNATURES["mnn_generate_scan_redraw"][1] + [_p])
+SIGNATURES["mnn_generate_scan_chunk_sir"] = (_i, SIGNATURES["mnn_generate_scan_chunk_redraw"][1] + [_p])
+PARTICLES_MAX = 1024       # mnn_sir.particles
 TEMPS_MAX = 8              # MNN_TEMPS_MAX
 REDRAWS_MAX = 255          # mnn_redraw.tries
 

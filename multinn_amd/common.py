@@ -19,7 +19,7 @@ import torch
 
 from . import ops
 from .switches import flag
-from ._lib import MnnError
+from ._lib import MnnError, MnnUnsupported
 
 STREAM_DROPOUT, STREAM_NADE, STREAM_RBM_H, STREAM_RBM_V, STREAM_DBN_ENC, STREAM_DBN_DEC = range(6)
 
@@ -115,6 +115,7 @@ class ScanGraphs:
     def __init__(self, max_entries=4):
         self._cache = collections.OrderedDict()
         self._max = max_entries
+        self._stats = {}                 # key -> the particle statistics arrays its captured scan writes (dropped with the entry)
 
     @staticmethod
     def enabled(x):
@@ -149,30 +150,43 @@ class ScanGraphs:
         return out.clone()
 
     @staticmethod
-    def generate(owner, key, x, num_steps, given, temperature, scan, stale, max_notes=None, redraws=0):
+    def generate(owner, key, x, num_steps, given, temperature, scan, stale, max_notes=None, redraws=0, particles=0, stats_shape=None):
         """The one capture wrapper of a `generate`: scan(x, num_steps, given, temperature) eagerly where graphs are off, else one replay of
         the scan captured under key + ("given",) + temperature_key (a new given of the same shape replays the same graph; the temperature
         is baked into the captured launches, nothing at 1.0: the scan captured without it) from the cache kept on `owner`.  max_notes (a
         normalised polyphony cap; None: the call, the key and the captured scan without one): a fifth argument of scan, and max_notes_key;
-        redraws (normalised, sampling_redraws; 0: nothing changes): a sixth argument of scan, and redraws_key.  stale(): mark
+        redraws (normalised, sampling_redraws; 0: nothing changes): a sixth argument of scan, and redraws_key; particles (normalised,
+        sampling_particles; 0: nothing changes): the keyword `particles` of scan, and particles_key; with them stats_shape = (num_steps,
+        tracks, B): the owner's `_particle_live` becomes the statistics arrays this scan writes -- new ones for an eager call, the graph
+        entry's for a captured one (created before the capture, dropped with the entry).  stale(): mark
         the owner's packed weight copies stale -- before the capture (the graph packs them itself: a replay always sees the current
         weights) and after it (the packed copies then live in the graph's pool).  The warm-up is the scan's first min(num_steps, 2) steps."""
         cap = () if max_notes is None else ((max_notes,) if not redraws else (max_notes, redraws))
+        kw = dict(particles=particles) if particles else {}
         if not ScanGraphs.enabled(x):
-            return scan(x, num_steps, given, temperature, *cap)
+            if particles and stats_shape is not None:
+                owner._particle_live = new_particle_cells(*stats_shape, x.device)
+            return scan(x, num_steps, given, temperature, *cap, **kw)
         if getattr(owner, "_scan_graphs", None) is None:
             owner._scan_graphs = ScanGraphs()
         if given is not None:
             key = key + ("given",)
-        key = key + temperature_key(temperature) + max_notes_key(max_notes) + redraws_key(redraws)
+        key = key + temperature_key(temperature) + max_notes_key(max_notes) + redraws_key(redraws) + particles_key(particles)
+        if particles and stats_shape is not None:
+            graphs = owner._scan_graphs
+            graphs._stats = {k: v for k, v in graphs._stats.items() if k in graphs._cache}
+            if key not in graphs._stats:
+                graphs._cache.pop(key, None)         # (never both: an entry without its arrays is captured again)
+                graphs._stats[key] = new_particle_cells(*stats_shape, x.device)
+            owner._particle_live = graphs._stats[key]
 
         def captured(sx, sg=None):
             stale()
-            return scan(sx, num_steps, sg, temperature, *cap)
+            return scan(sx, num_steps, sg, temperature, *cap, **kw)
 
         def warm(sx, sg=None):
             n = min(int(num_steps), 2)
-            return scan(sx, n, None if sg is None else sg[:, :n].contiguous(), temperature, *cap)
+            return scan(sx, n, None if sg is None else sg[:, :n].contiguous(), temperature, *cap, **kw)
 
         return owner._scan_graphs.run(key, x, captured, warm, stale, extra=given)
 
@@ -392,6 +406,68 @@ def redraw_counts(owner):
         return 0, 0
     n = owner._redraw_stats.cpu()
     return int(n[0]), int(n[1])
+
+
+# --------------------------------------------------------------------------------------------
+# Importance resampling.  With `particles=C` a partly given NADE step runs C clamped scans and emits one of them, picked with probability
+# proportional to the probability it gives the step's given cells (ops.nade_sample_sir): an approximate draw from p(free | given, past),
+# exact as C grows.  None, 0 and 1 are the call without the argument.
+MAX_PARTICLES = 1024
+
+
+def sampling_particles(particles, temperature=1.0, max_notes=None, given=True, what="particles"):
+    """The one normalisation of a `particles` argument, on the host, before any device work: 0 (the kernels, bits and captured scans of a call
+    without the argument) or an integer 2..MAX_PARTICLES.  None, 0 and 1 are 0, and so is any value where nothing is given (given False /
+    None).  A bool, a non-integer or a value outside 0..MAX_PARTICLES raise ValueError, as do particles > 1 under threshold decoding
+    (temperature None draws nothing); particles > 1 with a (normalised) max_notes raise MnnUnsupported: a cap changes the proposal."""
+    import numbers
+    if particles is None:
+        return 0
+    if isinstance(particles, bool) or not isinstance(particles, numbers.Integral) or not 0 <= particles <= MAX_PARTICLES:
+        raise ValueError(f"{what} must be None or an integer 0..{MAX_PARTICLES}, got {particles!r}")
+    if particles <= 1 or given is None or given is False:
+        return 0
+    if temperature is None:
+        raise ValueError(f"{what} > 1 needs a temperature: threshold decoding (temperature=None) draws nothing to resample")
+    if max_notes is not None:
+        raise MnnUnsupported(f"{what} > 1 with max_notes is not supported: a polyphony cap changes the proposal the weights belong to")
+    return int(particles)
+
+
+def particles_key(particles):
+    """What a scan-graph key gains from (normalised) particles: nothing at 0 -- the key, and the captured scan, of a call without them."""
+    return (("particles", particles),) if particles else ()
+
+
+def refuse_particles(particles, who):
+    """The paths without a particle form (the feedback modes' grouped multi-job sample launch): particles > 1 raise MnnUnsupported, after the
+    argument's own checks."""
+    if sampling_particles(particles):
+        raise MnnUnsupported(f"{who}: particles > 1 are not supported here (the grouped multi-job sample launch has no particle form)")
+
+
+def new_particle_cells(num_steps, tracks, B, device):
+    """The statistics arrays of a scan of num_steps steps: (ess f32, pick int32), both [num_steps, tracks, B] on the device, WRITTEN by the
+    kernels.  Who keeps them: an eager call only its owner's `_particle_live` until the next call; a captured scan its graph entry, whose
+    replays write to their addresses (ScanGraphs.generate, session.GeneratorSession) -- they go when the entry leaves its bounded cache."""
+    shape = (int(num_steps), int(tracks), int(B))
+    return torch.zeros(shape, device=device), torch.zeros(shape, dtype=torch.int32, device=device)
+
+
+def particle_cells(owner, num_steps, tracks, B, device):
+    """What a scan of num_steps steps writes its statistics to: the owner's live arrays where they are this scan's (the caller of the scan
+    set them), else arrays of its own that nobody reads (the short warm-up run in front of a capture)."""
+    live = getattr(owner, "_particle_live", None)
+    if live is not None and tuple(live[0].shape) == (int(num_steps), int(tracks), int(B)) and live[0].device == torch.device(device):
+        return live
+    return new_particle_cells(num_steps, tracks, B, device)
+
+
+def particle_stats(owner, which):
+    """The ess (which = 0) or the picks (1) of the owner's last generate call or session chunk as [B, num_steps, tracks]; synchronises.  None
+    where that call ran without particles: nothing was written, and nothing is read."""
+    live = getattr(owner, "_particle_live", None)
+    return None if live is None else live[which].permute(2, 0, 1).contiguous().cpu()
 
 
 # --------------------------------------------------------------------------------------------

@@ -438,11 +438,22 @@ static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps,
                               uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0,
                               const float* const* h0, float* const* c_out = nullptr, float* const* h_out = nullptr, uint32_t step0 = 0,
                               const uint32_t* step_base = nullptr, bool chunk = false, const mnn_caps* caps = nullptr,
-                              const mnn_redraw* redraw = nullptr) {
+                              const mnn_redraw* redraw = nullptr, const mnn_sir* sir = nullptr) {
     MNN_REQUIRE(temps, "mnn_generate_scan: null temps");     // (its contents: mnn_nade_sample_temps, before anything is enqueued when num_steps > 0)
     // redraw (NULL: none): the redraws of every sample call (mnn_nade_sample_redraw_at, which checks them again with the rest) -- here in front of the intro pass
     MNN_REQUIRE(redraw == nullptr || redraw->tries == 0 || (redraw->tries > 0 && redraw->tries <= 255 && temps->n > 0),
                 "mnn_generate_scan: redraw: 0..255 tries, and none with threshold draws");
+    // sir (NULL or particles <= 1: none): importance resampling on every sample call (mnn_nade_sample_sir_at, which checks the rest again); step
+    // st writes plane st of ess / pick [num_steps, tracks, B]
+    const bool resample = sir != nullptr && sir->particles > 1;
+    if (resample) {
+        MNN_REQUIRE(caps == nullptr || caps->n == 0, "mnn_generate_scan: particles with polyphony caps are not supported");
+        MNN_REQUIRE(redraw == nullptr || redraw->tries == 0, "mnn_generate_scan: particles with redraws are not supported (there is no cap to violate)");
+        MNN_REQUIRE(temps->n > 0, "mnn_generate_scan: particles need a temperature (threshold decoding draws nothing)");
+        MNN_REQUIRE(sir->particles <= 1024 && sir->ess && sir->pick, "mnn_generate_scan: sir: 2..1024 particles, ess and pick [num_steps, tracks, B]");
+        MNN_REQUIRE(sir->workspace && sir->workspace_bytes >= mnn_nade_sample_sir_workspace_bytes(tracks, B, D, sir->particles),
+                    "mnn_generate_scan: sir: workspace of mnn_nade_sample_sir_workspace_bytes(tracks, B, D, particles) bytes");
+    }
     MNN_REQUIRE(B > 0 && (n_intro > 0 || (chunk && n_intro == 0 && num_steps > 0 && c0 != nullptr)) && num_steps >= 0 && (intro || n_intro == 0) && n_in > 0 &&
                 n_layers > 0 && n_layers <= MNN_SCAN_MAX_LAYERS && layers,
                 "mnn_generate_scan: B, n_intro > 0 (the chunk form: or n_intro == 0 with an input state and num_steps > 0), 1..%d layers", MNN_SCAN_MAX_LAYERS);
@@ -517,9 +528,17 @@ static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps,
     const int row_stride = num_steps * n_in;
     for (int st = 0; st < num_steps; ++st) {
         uint8_t* smp = samples + (size_t)st * n_in;            // samples[:, st, :]; feature m D + i (one NADE) or i tracks + m (rnn_multinade.py:313-314)
-        rc = mnn_nade_sample_redraw_at(s, tracks, B, D, Hn, out, ld_out, w_enc, w_dec, temps, caps, seed, row0, step0 + (uint32_t)st, smp,
-                                       tracks > 1 ? 1 : D, row_stride, tracks > 1 ? tracks : 1, nullptr, given ? given + (size_t)st * n_in : nullptr,
-                                       step_base, redraw);
+        if (resample) {
+            mnn_sir step = *sir;
+            step.ess = sir->ess + (size_t)st * tracks * B;
+            step.pick = sir->pick + (size_t)st * tracks * B;
+            rc = mnn_nade_sample_sir_at(s, tracks, B, D, Hn, out, ld_out, w_enc, w_dec, temps, seed, row0, step0 + (uint32_t)st, smp, tracks > 1 ? 1 : D,
+                                        row_stride, tracks > 1 ? tracks : 1, nullptr, given ? given + (size_t)st * n_in : nullptr, step_base, &step, nullptr);
+        } else {
+            rc = mnn_nade_sample_redraw_at(s, tracks, B, D, Hn, out, ld_out, w_enc, w_dec, temps, caps, seed, row0, step0 + (uint32_t)st, smp,
+                                           tracks > 1 ? 1 : D, row_stride, tracks > 1 ? tracks : 1, nullptr, given ? given + (size_t)st * n_in : nullptr,
+                                           step_base, redraw);
+        }
         if (rc != MNN_OK) return rc;
         rc = stack_step(smp, row_stride);
         if (rc != MNN_OK) return rc;
@@ -541,12 +560,14 @@ static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps,
 // no output state this is mnn_generate_scan_temps, launch for launch.
 // caps (NULL: none): the polyphony caps of every sample call of the chunk (mnn_nade_sample_caps_at).
 // redraw (NULL: none): their redraws (mnn_redraw).
-extern "C" int mnn_generate_scan_chunk_redraw(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
-                                              const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks,
-                                              int D, int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps,
-                                              uint64_t seed, uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes,
-                                              const uint8_t* given, const float* const* c_in, const float* const* h_in, float* const* c_out,
-                                              float* const* h_out, uint32_t step0, const uint32_t* step_base, const mnn_redraw* redraw) {
+// sir (NULL: none): their importance resampling (mnn_sir).
+extern "C" int mnn_generate_scan_chunk_sir(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                           const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks,
+                                           int D, int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps,
+                                           uint64_t seed, uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes,
+                                           const uint8_t* given, const float* const* c_in, const float* const* h_in, float* const* c_out,
+                                           float* const* h_out, uint32_t step0, const uint32_t* step_base, const mnn_redraw* redraw,
+                                           const mnn_sir* sir) {
     MNN_REQUIRE((c_in == nullptr) == (h_in == nullptr) && (c_out == nullptr) == (h_out == nullptr),
                 "mnn_generate_scan_chunk: c_in / h_in and c_out / h_out come in pairs (arrays of n_layers pointers) or not at all");
     MNN_REQUIRE(n_layers > 0 && n_layers <= MNN_SCAN_MAX_LAYERS, "mnn_generate_scan_chunk: 1..%d layers", MNN_SCAN_MAX_LAYERS);
@@ -555,7 +576,17 @@ extern "C" int mnn_generate_scan_chunk_redraw(mnn_stream_t s, int B, int n_intro
     MNN_REQUIRE(n_intro >= 0 && num_steps >= 0 && n_intro + num_steps > 0, "mnn_generate_scan_chunk: n_intro, num_steps >= 0 and one of them > 0");
     MNN_REQUIRE(n_intro > 0 || c_in != nullptr, "mnn_generate_scan_chunk: a chunk without intro continues from c_in / h_in");
     return generate_scan_impl(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc, w_dec, temps,
-                              seed, row0, samples, workspace, workspace_bytes, given, c_in, h_in, c_out, h_out, step0, step_base, true, caps, redraw);
+                              seed, row0, samples, workspace, workspace_bytes, given, c_in, h_in, c_out, h_out, step0, step_base, true, caps, redraw, sir);
+}
+extern "C" int mnn_generate_scan_chunk_redraw(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                              const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks,
+                                              int D, int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps,
+                                              uint64_t seed, uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes,
+                                              const uint8_t* given, const float* const* c_in, const float* const* h_in, float* const* c_out,
+                                              float* const* h_out, uint32_t step0, const uint32_t* step_base, const mnn_redraw* redraw) {
+    return mnn_generate_scan_chunk_sir(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc,
+                                       w_dec, temps, caps, seed, row0, samples, workspace, workspace_bytes, given, c_in, h_in, c_out, h_out, step0,
+                                       step_base, redraw, nullptr);
 }
 extern "C" int mnn_generate_scan_chunk_caps(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
                                             const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks,
@@ -579,18 +610,27 @@ extern "C" int mnn_generate_scan_chunk(mnn_stream_t s, int B, int n_intro, int n
 // the scan with a temperature table (mnn_temps: per track of a MultiNADE, or per visible index of the one NADE) and the optional initial state
 // ... and polyphony caps (NULL: none)
 // ... and redraws (NULL: none)
-extern "C" int mnn_generate_scan_redraw(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
-                                        const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
-                                        int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed,
-                                        uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given,
-                                        const float* const* c0, const float* const* h0, const mnn_redraw* redraw) {
+// ... and importance resampling (NULL: none)
+extern "C" int mnn_generate_scan_sir(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                     const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
+                                     int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed,
+                                     uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given,
+                                     const float* const* c0, const float* const* h0, const mnn_redraw* redraw, const mnn_sir* sir) {
     MNN_REQUIRE((c0 == nullptr) == (h0 == nullptr), "mnn_generate_scan_state: c0 and h0 come together (arrays of n_layers pointers) or not at all");
     if (c0 != nullptr) {
         MNN_REQUIRE(n_layers > 0 && n_layers <= MNN_SCAN_MAX_LAYERS, "mnn_generate_scan_state: 1..%d layers", MNN_SCAN_MAX_LAYERS);
         for (int l = 0; l < n_layers; ++l) MNN_REQUIRE(c0[l] && h0[l], "mnn_generate_scan_state: layer %d has no initial state", l);
     }
     return generate_scan_impl(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc, w_dec, temps,
-                              seed, row0, samples, workspace, workspace_bytes, given, c0, h0, nullptr, nullptr, 0, nullptr, false, caps, redraw);
+                              seed, row0, samples, workspace, workspace_bytes, given, c0, h0, nullptr, nullptr, 0, nullptr, false, caps, redraw, sir);
+}
+extern "C" int mnn_generate_scan_redraw(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                        const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
+                                        int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed,
+                                        uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given,
+                                        const float* const* c0, const float* const* h0, const mnn_redraw* redraw) {
+    return mnn_generate_scan_sir(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc, w_dec, temps,
+                                 caps, seed, row0, samples, workspace, workspace_bytes, given, c0, h0, redraw, nullptr);
 }
 extern "C" int mnn_generate_scan_caps(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
                                       const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,

@@ -221,15 +221,19 @@ class FeedbackRnnSampler:
         from .common import redraw_counts
         return redraw_counts(self)
 
-    def generate(self, x_u8, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0):
-        """x_u8 [B,Ti,P,M] intro piano-rolls -> samples u8 [B,num_steps,P,M].  One hipGraph replay per call on the
+    def generate(self, x_u8, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=None):
+        """x_u8 [B,Ti,P,M] intro piano-rolls -> samples u8 [B,num_steps,P,M].  particles > 1 with given: MnnUnsupported (the grouped
+        multi-job sample launch of a step has no particle form).  One hipGraph replay per call on the
         device (common.ScanGraphs): the M generators and the feedback module step inside the same captured scan.
         given (optional): codes u8 [B, num_steps, P, M] (common.given_codes), see generate_encoded.
         temperature: one for all generators or generator m's own, temperature[m]; 1.0 is the call (and the captured scan) without it.
         max_notes: None, one cap (an integer >= 0) for all generators or generator m's own, max_notes[m] (None: no cap); None is the call
         (and the captured scan) without it.  redraws (common.sampling_redraws): the cap by rejection in every generator's step; 0, or
         no cap, is the call (and the captured scan) without it."""
-        from .common import ScanGraphs, sampling_redraws
+        from .common import ScanGraphs, refuse_particles, sampling_particles, sampling_redraws
+        if given is not None:
+            refuse_particles(particles, "FeedbackRnnSampler")
+        sampling_particles(particles)
         temperature, max_notes = self._temperature(temperature), self._max_notes(max_notes, x_u8.shape[2])
         redraws = sampling_redraws(redraws, max_notes, temperature)
         self._redraw_live = redraws > 0                    # per call, here: a replay of a captured scan does not pass through generate_encoded

@@ -22,7 +22,7 @@ import torch
 
 from . import ops
 from .switches import flag, value
-from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, DrawAt, check_given, given_codes, given_mask_tracks, sampling_temperature, sampling_max_notes, sampling_redraws, redraw_cell, redraw_counts, glorot_uniform, zeros_init, default_device, capture_train_step
+from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, DrawAt, check_given, given_codes, given_mask_tracks, sampling_temperature, sampling_max_notes, sampling_redraws, sampling_particles, particle_cells, particle_stats, redraw_cell, redraw_counts, glorot_uniform, zeros_init, default_device, capture_train_step
 from .training import compute_gradients, world, dp_active, AdamOptimizer
 from ._lib import MnnUnsupported
 from .lstm_stack import LstmStack, _SINGLE, drive, drive_group, _det_f32, det_steps
@@ -232,7 +232,7 @@ class Generator(Model):
         return self._outputs
 
     @abc.abstractmethod
-    def generate(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0):
+    def generate(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=None):
         ...
 
     def pretrain(self, optimizer, lr, run_optimizer=True):
@@ -408,7 +408,12 @@ class RnnEstimator(Generator):
                                  "step at once and has no visible order in which a track's count could stop it")
         return None
 
-    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0):
+    def _particles(self, particles, temperature, max_notes, given):
+        """generate's `particles`, normalised on the host before any device work.  Here: the estimators that ignore it (RBM: the clamped
+        Gibbs chain already conditions on every given cell); the NADE estimators override it."""
+        return 0
+
+    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=0):
         return None                         # estimators without a one-call scan (RnnRBM) step through sample_single / single_step
 
     # -- generation sessions (session.py) --------------------------------------------------------
@@ -542,8 +547,12 @@ class RnnEstimator(Generator):
         return buf
 
     # -- sampling -------------------------------------------------------------------------------
-    def generate(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0):
+    def generate(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=None):
         """rnn_estimator.py:271-298: intro pass, then num_steps x {sample_single, single_step}.
+        particles (NADE estimators, with given; common.sampling_particles): importance resampling -- every partly given step runs C clamped
+        scans and emits one, picked with probability proportional to the probability it gives the step's given cells: an approximate draw
+        from p(free | this step's given cells, the past), exact as C grows; particle_ess() / particle_picks() report how approximate.  None,
+        0, 1, or no given, is the call without it: the same kernels, bits and captured scan.  RBM estimators ignore it.
         redraws (0..255, with max_notes; common.sampling_redraws): the cap by rejection -- a row whose step would emit a 1 past a cap is
         drawn again, up to `redraws` times, before the truncating scan serves it; redraw_counts() reports what happened.  0, or no cap, is
         the call without it: the same kernels, bits and captured scan.
@@ -562,47 +571,67 @@ class RnnEstimator(Generator):
         max_notes = self._max_notes(max_notes)
         temperature = self._temperature(temperature)
         redraws = sampling_redraws(redraws, max_notes, temperature)
+        particles = self._particles(particles, temperature, max_notes, given)
         if max_notes is not None:
             refuse_host_model(self.store.device, "generate(max_notes=)")
+        if particles:
+            refuse_host_model(self.store.device, "generate(particles=)")
         self._redraw_live = redraws > 0
+        self._particle_live = None          # (with particles: set by ScanGraphs.generate to the arrays the scan writes)
 
         def stale():
             self._packed_step = -1
         return ScanGraphs.generate(self, (tuple(x.shape), x.dtype, int(num_steps), self.seed, self.row0), x, num_steps, given,
-                                   temperature, self._generate_scan, stale, max_notes, redraws)
+                                   temperature, self._generate_scan, stale, max_notes, redraws, particles,
+                                   stats_shape=(int(num_steps), self.num_tracks, x.shape[0]) if particles else None)
+
+    def particle_ess(self):
+        """The effective sample size (sum w)^2 / sum w^2 of every scan of the last generate call or session chunk that ran with particles:
+        f32 [B, num_steps, tracks] on the host, in [1, C] -- C where nothing was resampled (no given cell behind a free one), near 1 where
+        one particle carried the weight and the emitted vector is little better than the clamped scan's.  None without particles.
+        Synchronises."""
+        return particle_stats(self, 0)
+
+    def particle_picks(self):
+        """The picked particle of every scan, int32 [B, num_steps, tracks] (0: the scan of the call without particles); see particle_ess."""
+        return particle_stats(self, 1)
 
     def redraw_counts(self):
         """(redrawn, fallback) of the last generate call or session chunk: how many scans -- one per row, track and generated step -- were
         drawn again at least once, and how many of them fell back to the truncating scan (and carry its bias).  Ints; synchronises."""
         return redraw_counts(self)
 
-    def _generate_scan(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0):
+    def _generate_scan(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=0):
         self._materialize(x.shape[-1])
         self._rnn.build_cell(False)
         if redraws:
             redraw_cell(self, x.device).zero_()        # the call's statistics start at zero (in a captured scan: a fill node of the graph)
         with self._sampling_scope():
             if self.det_sampling:
-                whole = self._scan_in_one_call(x, num_steps, given, temperature, max_notes, redraws)     # LSTM-(Multi)NADE on a byte piano-roll: mnn_generate_scan runs the whole scan
+                whole = self._scan_in_one_call(x, num_steps, given, temperature, max_notes, redraws, particles)     # LSTM-(Multi)NADE on a byte piano-roll: mnn_generate_scan runs the whole scan
                 if whole is not None:
                     return whole
                 state = self.steps(x)
             else:
                 self._ensure_packed()
                 state = self._get_state(x, lengths=None, last_outputs=True)
-            return self._scan_steps(state, x[:, -1, :], num_steps, DrawAt(self.seed, self.row0, 0), given, temperature, max_notes, redraws)[0]
+            return self._scan_steps(state, x[:, -1, :], num_steps, DrawAt(self.seed, self.row0, 0), given, temperature, max_notes, redraws, particles)[0]
 
-    def _scan_steps(self, state, last_row, n, at0, given=None, temperature=1.0, max_notes=None, redraws=0):
+    def _scan_steps(self, state, last_row, n, at0, given=None, temperature=1.0, max_notes=None, redraws=0, particles=0):
         """The step loop of a single generator (rnn_estimator.py:283-298): n x {sample_single, single_step} from `state` and the last emitted
         row, step j drawing at at0's position moved on by j steps under given[:, j] -> (samples u8 [B, n, num_output], state, last row).
         generate runs it from step 0, a session's chunk from where the piece stands.  max_notes (normalised; None: the call without it)
         makes every step a sample_single_capped, which the estimators that have caps define; redraws (normalised; 0: nothing changes) a
-        sample_single_redrawn that adds to the generator's statistics cell."""
+        sample_single_redrawn that adds to the generator's statistics cell; particles (normalised; 0: nothing changes) a
+        sample_single_resampled that writes step j's plane of the generator's particle statistics."""
         out = []
+        cells = particle_cells(self, n, self.num_tracks, last_row.shape[0], last_row.device) if particles and given is not None else None
         sample = self.sample_single if max_notes is None else functools.partial(self.sample_single_capped, max_notes=max_notes)
         if redraws:
             sample = functools.partial(self.sample_single_redrawn, max_notes=max_notes, redraws=redraws, redraw_stats=redraw_cell(self, last_row.device))
         for j in range(n):
+            if cells is not None:
+                sample = functools.partial(self.sample_single_resampled, particles=particles, ess=cells[0][j], pick=cells[1][j])
             last_row, _ = sample(last_row, state, given=None if given is None else given[:, j], temperature=temperature,
                                  at=at0._replace(step=at0.step + j))
             state = self.single_step(last_row, state)
@@ -1148,14 +1177,21 @@ class RnnNade(RnnEstimator):
         return sampling_max_notes(max_notes, n, None if n is None else self.num_dims // n, collapse=n == 1,
                                   what="max_notes (one NADE: a sequence whose length divides its visibles)")
 
-    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0):
+    def _particles(self, particles, temperature, max_notes, given):
+        return sampling_particles(particles, temperature, max_notes, given)
+
+    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=0):
         """rnn_estimator.py:271-298 through ONE C-ABI call (mnn_generate_scan: intro pass + num_steps x {NADE sample, LSTM step, Dense} enqueued
         by the library's own host loop) when the inputs are the byte piano-roll itself; the same kernels and bits as the step-by-step path.
         given: the scan's codes u8 [B, num_steps, num_output] (generate)."""
         if x.dtype != torch.uint8 or x.shape[-1] != self.num_tracks * self.num_dims or int(num_steps) < 1:
             return None
+        sir = {}
+        if particles and given is not None:
+            ess, pick = particle_cells(self, num_steps, self.num_tracks, x.shape[0], x.device)
+            sir = dict(particles=particles, ess=ess, pick=pick)
         return ops.generate_scan(x.contiguous(), num_steps, temperature=temperature, seed=self.seed, row0=self.row0, given=given, max_notes=max_notes,
-                                 redraws=redraws, redraw_stats=redraw_cell(self, x.device) if redraws else None,
+                                 **sir, redraws=redraws, redraw_stats=redraw_cell(self, x.device) if redraws else None,
                                  state0=self._state0(x.shape[0], torch.float32), **self._scan_layers())      # (learn_zero_state: tiled on the device here, an input array of the scan)
 
     def _state_of(self, out, rnn_state):
@@ -1230,6 +1266,24 @@ class RnnNade(RnnEstimator):
         ops.nade_sample(out, self.store["nade/w_enc"], self.store["nade/w_dec"], M, D, Hn, temperature, at.seed, at.row0, at.step, smp,
                         track_minor=(M > 1), nll=nll, given=None if given is None else given.contiguous(), by_visible=M == 1, sub_base=at.base,
                         max_notes=max_notes, redraws=redraws, redraw_stats=redraw_stats)
+        return smp, (nll[0] if M == 1 else [nll[m] for m in range(M)])
+
+
+    def sample_single_resampled(self, inputs, state, *, given=None, temperature=1.0, at=None, particles=None, ess=None, pick=None):
+        """sample_single by importance resampling (ops.nade_sample_sir): particles = C clamped scans of this step, one emitted.  None, 0, 1
+        or no given: sample_single itself.  ess f32 / pick int32 [num_tracks, B] (optional, on the device) receive the step's statistics;
+        the returned nll is the model's own of the emitted vector."""
+        particles = sampling_particles(particles, temperature, None, given)
+        if not particles:
+            return self.sample_single(inputs, state, given=given, temperature=temperature, at=at)
+        M, D, Hn = self.num_tracks, self.num_dims, self.num_hidden[-1]
+        at = DrawAt(self.seed, self.row0, 0) if at is None else at
+        out = state.dense
+        Bn = out.shape[0]
+        smp = torch.empty((Bn, M * D), device=out.device, dtype=torch.uint8)
+        nll = torch.empty((M, Bn), device=out.device)
+        ops.nade_sample_sir(out, self.store["nade/w_enc"], self.store["nade/w_dec"], M, D, Hn, temperature, at.seed, at.row0, at.step, smp,
+                            given.contiguous(), particles, track_minor=(M > 1), nll=nll, by_visible=M == 1, sub_base=at.base, ess=ess, pick=pick)
         return smp, (nll[0] if M == 1 else [nll[m] for m in range(M)])
 
 

@@ -26,7 +26,7 @@ import weakref
 
 import torch
 
-from .common import Model, capture_train_step, given_codes, given_tracks, sampling_max_notes, sampling_redraws, sampling_temperature
+from .common import Model, capture_train_step, given_codes, given_tracks, refuse_particles, sampling_max_notes, sampling_particles, sampling_redraws, sampling_temperature
 from .encoders import PassEncoder, DBNEncoder
 from .generators import RnnNade, RnnRBM, RnnMultiNADE, RnnMultiRBM
 from . import ops
@@ -229,9 +229,9 @@ class MultINNCore(Model):
     metrics_upd = property(lambda self: (self._ensure_global_metrics(), self._metrics_upd)[1])
 
     # -- sampling -------------------------------------------------------------------------------
-    def sampler(self, num_beats, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0):
+    def sampler(self, num_beats, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0, particles=None):
         """multinn_core.py:324-341: number of model time steps in `num_beats` beats, then generate() (given / given_mask / temperature /
-        max_notes / redraws: see generate)."""
+        max_notes / redraws / particles: see generate)."""
         d = self._config["data"]
         pitch_span = d["pitch_range"]["highest"] - d["pitch_range"]["lowest"]
         num_steps = num_beats * d["beat_resolution"] * pitch_span // self._num_dims
@@ -240,6 +240,8 @@ class MultINNCore(Model):
             kw["max_notes"] = max_notes
         if redraws != 0 or isinstance(redraws, bool):      # (anything but the default goes to generate, which checks it)
             kw["redraws"] = redraws
+        if particles is not None:
+            kw["particles"] = particles
         if given is None and given_mask is None:
             return self.generate(num_steps, **kw)
         return self.generate(num_steps, given=given, given_mask=given_mask, **kw)
@@ -292,6 +294,28 @@ class MultINNCore(Model):
         """Normalised on the host (common.sampling_redraws), behind the cap's own refusals: max_notes and temperature are the normalised ones."""
         return sampling_redraws(redraws, max_notes, temperature)
 
+    # Importance resampling (generate(..., given, particles=C)): every partly given step of a NADE generator runs C clamped scans and emits
+    # one, picked with probability proportional to the probability it gives the step's given cells -- the free cells then know of the given
+    # notes ordered BEHIND them in the same step (the bass of the drum hits above it), which the clamped scan alone never tells them.  The
+    # emitted step is an approximate draw from p(free | this step's given cells, the past), exact as C grows; given cells of later steps
+    # say nothing to earlier ones.  None, 0, 1, or nothing given, is the call without it, down to the captured scan.  RBM generators ignore
+    # it (their clamped chain already conditions on every given cell); max_notes with it, and the feedback modes, are refused.
+    def _particles(self, particles, temperature, max_notes, cond):
+        """Normalised on the host (common.sampling_particles), behind the temperature's and the cap's own refusals."""
+        if self._generator_type in ("RBM", "MultiRBM"):
+            return 0
+        return sampling_particles(particles, temperature, max_notes, cond)
+
+    def particle_ess(self):
+        """Per generator its particle_ess() of the last generate call or session chunk: f32 [B, num_steps, tracks of that generator] on the
+        host -- the effective sample size of every scan, in [1, C], C where nothing was resampled -- or None for a generator that ran
+        without particles.  Synchronises."""
+        return [g.particle_ess() if hasattr(g, "particle_ess") else None for g in self.generators]
+
+    def particle_picks(self):
+        """Per generator its particle_picks() (int32, 0: the scan of the call without particles), as particle_ess."""
+        return [g.particle_picks() if hasattr(g, "particle_picks") else None for g in self.generators]
+
     def redraw_counts(self):
         """(redrawn, fallback) of the last generate call or session chunk, summed over the generators (a feedback mode: its sampler's):
         scans -- one per row, track and generated step -- drawn again at least once, and those that fell back.  Ints; synchronises."""
@@ -340,19 +364,20 @@ class MultINNCore(Model):
         max_notes = self._max_notes(max_notes)
         return temperature, self._given(num_steps, given, given_mask), max_notes
 
-    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0):
+    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0, particles=None):
         """-> u8 `[B, num_steps, P, M]` (multinn_joint.py:188-215, multinn_jamming.py:101-133, multinn_composer.py:114-151): every generator's
         scan on its encoded intro, decoded per track.  temperature: _temperature; max_notes: _max_notes; redraws: _redraws; given /
-        given_mask: conditional generation (_given).
+        given_mask: conditional generation (_given); particles: importance resampling of the partly given steps (_particles).
         What the modes differ in is in _generator_inputs, _generator_given and _decode_samples."""
         temperature, cond, max_notes = self._generate_arguments(num_steps, given, given_mask, temperature, max_notes)
         redraws = self._redraws(redraws, max_notes, temperature)
+        particles = self._particles(particles, temperature, max_notes, cond)
         if self._x_encoded is None:
             MultINNCore._build_all(self, "generate")
         scans = [functools.partial(g.generate, x) for g, x in zip(self.generators, self._generator_inputs())]
-        return self._sample_generators(scans, num_steps, cond, temperature, max_notes=max_notes, redraws=redraws)
+        return self._sample_generators(scans, num_steps, cond, temperature, max_notes=max_notes, redraws=redraws, particles=particles)
 
-    def _sample_generators(self, scans, num_steps, cond, temperature, session=False, max_notes=None, redraws=0):
+    def _sample_generators(self, scans, num_steps, cond, temperature, session=False, max_notes=None, redraws=0, particles=0):
         """scans: per generator its scan(num_steps, given=, temperature=) -- its generate on its intro, or its session's chunk -> the
         decoded piano-roll.  One generator takes the whole temperature, M generators one each; a generator whose scan does not run
         (_generator_given) emits its codes.  max_notes (normalised): _generator_max_notes gives each generator its own; a generator without
@@ -363,8 +388,11 @@ class MultINNCore(Model):
         caps = [{} if k is None else dict(max_notes=k) for k in (self._generator_max_notes(max_notes) if max_notes is not None else [None] * n)]
         for g, cap in zip(self.generators, caps):
             g._redraw_live = False                   # (a generator whose scan does not run this call reports nothing; its generate / chunk sets it where it runs)
+            g._particle_live = None
             if cap and redraws and not session:      # (a session's generators carry their redraws themselves)
                 cap["redraws"] = redraws
+            if particles and not session:            # (and their particles)
+                cap["particles"] = particles
         samples = [scan(num_steps, given=gv, temperature=t, **cap) if run else gv for scan, (gv, run), t, cap in zip(scans, givens, temps, caps)]
         return self._decode_samples(samples, num_steps)
 
@@ -1103,8 +1131,9 @@ class MultINNFeedback(MultINNJamming):
             if isinstance(g, RnnRBM) and some[i] and not whole[i]:
                 raise NotImplementedError(f"track {i}: in feedback mode an RBM generator takes whole given tracks only (no clamped chain in the feedback scan)")
 
-    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0):
+    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0, particles=None):
         """multinn_feedback.py:120-173 -> u8 `[B, num_steps, P, M]`: one joint scan over the M generators and the feedback module.
+        particles > 1 with given: MnnUnsupported (the scan's grouped multi-job sample launch has no particle form).
         redraws (MultINNCore._redraws): the cap by rejection, inside the scan.
         temperature (MultINNCore._temperature): generator m samples at its own inside the scan.  max_notes (MultINNCore._max_notes):
         generator m caps its own track.
@@ -1112,6 +1141,9 @@ class MultINNFeedback(MultINNJamming):
         from .feedback import FeedbackRnnSampler
         temperature, cond, max_notes = self._generate_arguments(num_steps, given, given_mask, temperature, max_notes)
         redraws = self._redraws(redraws, max_notes, temperature)
+        sampling_particles(particles)
+        if cond is not None:
+            refuse_particles(particles, f"the {self._mode} mode")
         cap = {} if max_notes is None else (dict(max_notes=max_notes, redraws=redraws) if redraws else dict(max_notes=max_notes))
         if self._x_encoded is None:
             self._inputs = self._build_inputs()

@@ -804,6 +804,78 @@ def nade_sample_multi(jobs, D, Hn, temperature, row0, sub, max_notes=None, redra
     call("mnn_nade_sample_multi", _stream(), len(jobs), arr, N, D, Hn, float(-1.0 if temperature is None else temperature), int(row0), int(sub), rs, es)
 
 
+def _sir(what, particles, ess, pick, shape, tracks, N, D, ref):
+    """The mnn_sir of a call with particles = C >= 2 (and the workspace tensor that backs it, to be kept until the call is enqueued): ess f32 and
+    pick int32 of `shape` on ref's device, written by the kernels."""
+    _req(isinstance(particles, int) and not isinstance(particles, bool) and 2 <= particles <= _lib.PARTICLES_MAX,
+         f"{what}: particles: an integer 2..{_lib.PARTICLES_MAX}")
+    for t, dt, name in ((ess, torch.float32, "ess f32"), (pick, torch.int32, "pick int32")):
+        _req(torch.is_tensor(t) and t.dtype == dt and tuple(t.shape) == tuple(shape) and t.is_contiguous() and t.device == ref.device,
+             f"{what}: {name} {list(shape)} on the device")
+    need = int(_lib.load().mnn_nade_sample_sir_workspace_bytes(tracks, N, D, particles))
+    ws = torch.empty(need + 256, dtype=torch.uint8, device=ref.device)
+    sr = _lib.Sir()
+    sr.particles, sr.ess, sr.pick = particles, _ptr(ess), _ptr(pick)
+    sr.workspace, sr.workspace_bytes = C.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256), need
+    return sr, ws
+
+
+def nade_sample_sir_workspace_bytes(tracks, N, D, particles):
+    """mnn_nade_sample_sir_workspace_bytes: what a step's particles take between its two launches (0 for particles <= 1)."""
+    return int(_lib.load().mnn_nade_sample_sir_workspace_bytes(int(tracks), int(N), int(D), int(particles)))
+
+
+def nade_sample_sir(bias, w_enc, w_dec, tracks, D, Hn, temperature, seed, row0, sub, samples, given, particles, track_minor=False, nll=None,
+                    by_visible=False, sub_base=None, ess=None, pick=None, log_w=None, v_out=None):
+    """nade_sample(given=) by importance resampling (mnn_nade_sample_sir_at; DESIGN.md section 4 "NADE importance resampling"): every scan
+    (row, track) runs C = particles clamped scans -- particle 0 the scan of nade_sample, the others on Philox stream 13 -- weighs each by the
+    probability of its given cells (at the scan's temperature) and emits one, picked with probability w_c / sum w (one uniform on stream 14).
+    samples / given: u8 [N, tracks * D] contiguous as nade_sample takes them (track_minor likewise), or -- tracks == 1 -- two [N, D] VIEWS of
+    equal strides (e.g. out[:, s, :, m] of a [B, steps, P, M] piano-roll).  temperature: a float or a sequence (nade_sample), not None.
+    Outputs: nll f32 [tracks, N] (optional) the model's own of the emitted vector; ess f32 / pick int32 [tracks, N] (allocated if not given;
+    returned; given None: nade_sample's launch, ess = C and pick = 0 written); log_w f32 [tracks, N, C] (optional): every particle's log weight; v_out u8 [tracks, N, C, D] (optional, for tests): the
+    particles' vectors, copied out of the workspace.  A scan with no given cell behind a free one runs particle 0 alone: nade_sample's
+    bits, ess = C, pick = 0 (and of v_out only its particle 0 is written)."""
+    what = "nade_sample_sir"
+    N = bias.shape[0]
+    _req(bias.dtype == torch.float32 and bias.dim() == 2 and bias.stride(1) == 1 and bias.shape[1] >= tracks * (Hn + D), what + ": bias")
+    _req(temperature is not None, what + ": particles need a temperature (threshold decoding draws nothing)")
+    _req(torch.is_tensor(samples) and samples.dtype == torch.uint8 and samples.device == bias.device
+         and (given is None or (torch.is_tensor(given) and given.dtype == torch.uint8 and given.device == samples.device)),
+         what + ": samples and given are u8 tensors on bias's device")
+    if given is not None and tracks == 1 and samples.dim() == 2 and tuple(samples.shape) == (N, D) and not samples.is_contiguous():
+        rs, es = samples.stride()
+        _req(es >= 1 and rs >= 1 and tuple(given.shape) == (N, D) and given.stride() == (rs, es), what + ": given u8 [N, D] with the strides of samples")
+        ts = D
+    else:
+        _req(samples.shape == (N, tracks * D) and samples.is_contiguous(), what + ": samples u8 [N, tracks*D]")
+        _req(given is None or (tuple(given.shape) == (N, tracks * D) and given.is_contiguous()), what + ": given u8 [N, tracks*D], contiguous")
+        ts, es = (1, tracks) if track_minor else (D, 1)
+        rs = tracks * D
+    for w in (w_enc, w_dec):
+        _req(w.dtype == torch.float32 and w.is_contiguous() and w.numel() == tracks * D * Hn, what + ": weights")
+    if nll is not None:
+        _req(nll.dtype == torch.float32 and nll.numel() == tracks * N and nll.is_contiguous(), what + ": nll")
+    if ess is None:
+        ess = torch.empty((tracks, N), device=bias.device)
+    if pick is None:
+        pick = torch.empty((tracks, N), dtype=torch.int32, device=bias.device)
+    sr, ws = _sir(what, particles, ess, pick, (tracks, N), tracks, N, D, bias)
+    if log_w is not None:
+        _req(log_w.dtype == torch.float32 and tuple(log_w.shape) == (tracks, N, particles) and log_w.is_contiguous() and log_w.device == bias.device,
+             what + ": log_w f32 [tracks, N, C]")
+    tt = _temps_table(temperature, tracks, by_visible, what)
+    call("mnn_nade_sample_sir_at", _stream(), tracks, N, D, Hn, _ptr(bias), bias.stride(0), _ptr(w_enc), _ptr(w_dec), C.byref(tt), int(seed),
+         int(row0), int(sub), _ptr(samples), ts, rs, es, _ptr(nll), _ptr(given), _sub_base(sub_base, samples, what), C.byref(sr), _ptr(log_w))
+    if v_out is not None and given is not None:      # the workspace's last block (mnn_nade_sample_sir_at): behind log w, nll and the flags, each 256-byte aligned
+        _req(v_out.dtype == torch.uint8 and tuple(v_out.shape) == (tracks, N, particles, D) and v_out.is_contiguous() and v_out.device == bias.device,
+             what + ": v_out u8 [tracks, N, C, D]")
+        scans = tracks * N
+        first = (-ws.data_ptr()) % 256 + 2 * round_up(scans * particles * 4, 256) + round_up(scans, 256)
+        v_out.view(-1).copy_(ws[first:first + v_out.numel()])
+    return ess, pick
+
+
 def nade_given_is(bias, w_enc, w_dec, tracks, D, Hn, given, num_particles, seed, row0=0, row_ids=None, data=None, log_pg=None, log_w=None,
                   v_out=None, stats=None):
     """Importance-sampling estimate of log p(x_G) per (track, row) of a partly given NADE (mnn_nade_given_is; DESIGN.md section 4 "NADE
@@ -1409,7 +1481,7 @@ def _scan_call(what, ref, intro, Ti, num_steps, layers, dense_W, dense_bias, tra
 
 
 def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, given=None, state0=None,
-                  by_visible=False, max_notes=None, redraws=0, redraw_stats=None):
+                  by_visible=False, max_notes=None, redraws=0, redraw_stats=None, particles=0, ess=None, pick=None):
     """mnn_generate_scan: the whole sampling scan of an LSTM-(Multi)NADE generator in one call.  intro u8 [B, Ti, tracks * D]; layers = [(W, bias)]
     f32 master weights; returns samples u8 [B, num_steps, tracks * D].  given (optional): codes u8 [B, num_steps, tracks * D] in the layout of
     the samples (see nade_sample).  temperature: a float, None, or a sequence (per track, or by visible index: nade_sample).  state0 (optional, mnn_generate_scan_state): [(c0, h0) f32 [B, u]] per layer, the state the intro pass starts from."""
@@ -1420,6 +1492,10 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
     cp, hp = _scan_state("generate_scan: state0", state0, arr, intro.shape[0], intro.device)
     cc = _caps(max_notes, tracks, by_visible, "generate_scan")
     rd = _redraw(redraws, redraw_stats, cc, temperature, intro, "generate_scan")
+    if particles and particles > 1 and given is not None:      # importance resampling (nade_sample_sir): ess / pick [num_steps, tracks, B] are written
+        _req(cc is None and temperature is not None, "generate_scan: particles go with a temperature and without max_notes")
+        sr, ws = _sir("generate_scan", particles, ess, pick, (int(num_steps), tracks, intro.shape[0]), tracks, intro.shape[0], D, intro)
+        return launch("mnn_generate_scan_sir", (C.byref(_temps_table(temperature, tracks, by_visible, "generate_scan")), None), cp, hp, None, C.byref(sr))
     if rd is not None:              # the cap by rejection (nade_sample): the caps entry point with the redraws behind its state
         return launch("mnn_generate_scan_redraw", (C.byref(_temps_table(temperature, tracks, by_visible, "generate_scan")), C.byref(cc)), cp, hp,
                       C.byref(rd))
@@ -1432,7 +1508,8 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
 
 
 def generate_scan_chunk(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, state_in, state_out,
-                        given=None, step0=0, step_base=None, by_visible=False, max_notes=None, redraws=0, redraw_stats=None):
+                        given=None, step0=0, step_base=None, by_visible=False, max_notes=None, redraws=0, redraw_stats=None, particles=0, ess=None,
+                        pick=None):
     """mnn_generate_scan_chunk: one chunk of a generation session of an LSTM-(Multi)NADE generator.  intro u8 [B, Ti, tracks * D] or None (the
     chunk continues from state_in); num_steps >= 0 (0 with an intro: the intro pass alone -> None); state_in: [(c, h) f32 [B, u]] per layer or
     None (the zero state); state_out: likewise, written with the state behind the last step (may be the arrays of state_in).  Step st draws
@@ -1450,6 +1527,11 @@ def generate_scan_chunk(intro, num_steps, layers, dense_W, dense_bias, tracks, D
     tt = _temps_table(temperature, tracks, by_visible, "generate_scan_chunk")
     cc = _caps(max_notes, tracks, by_visible, "generate_scan_chunk")
     rd = _redraw(redraws, redraw_stats, cc, temperature, ref, "generate_scan_chunk")
+    if particles and particles > 1 and given is not None and num_steps > 0:      # importance resampling: generate_scan's
+        _req(cc is None and temperature is not None, "generate_scan_chunk: particles go with a temperature and without max_notes")
+        sr, ws = _sir("generate_scan_chunk", particles, ess, pick, (num_steps, tracks, ref.shape[0]), tracks, ref.shape[0], D, ref)
+        return launch("mnn_generate_scan_chunk_sir", (C.byref(tt), None), ci, hi, co, ho, int(step0), _sub_base(step_base, ref, "generate_scan_chunk"),
+                      None, C.byref(sr))
     if rd is not None:
         samples = launch("mnn_generate_scan_chunk_redraw", (C.byref(tt), C.byref(cc)), ci, hi, co, ho, int(step0),
                          _sub_base(step_base, ref, "generate_scan_chunk"), C.byref(rd))

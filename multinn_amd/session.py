@@ -21,7 +21,7 @@ import torch
 
 from . import ops
 from ._lib import MnnUnsupported
-from .common import DrawAt, ScanGraphs, _warm_up, check_given, graph_capture, max_notes_key, redraw_cell, redraws_key, sampling_redraws, temperature_key
+from .common import DrawAt, ScanGraphs, _warm_up, check_given, graph_capture, max_notes_key, new_particle_cells, particle_cells, particles_key, redraw_cell, redraws_key, sampling_particles, sampling_redraws, temperature_key
 
 __all__ = ["GeneratorSession", "ModeSession"]
 
@@ -68,6 +68,7 @@ class GeneratorSession:
         self._gen, self.seed, self.row0 = gen, gen.seed, gen.row0
         self._max_notes = None
         self._redraws = 0
+        self._particles = 0
         self.steps = 0
         self.batch = int(x.shape[0])
         self._graphs = collections.OrderedDict()
@@ -112,11 +113,16 @@ class GeneratorSession:
         self.steps = int(steps)
 
     # -- chunks ---------------------------------------------------------------------------------
-    def _run(self, n, given, temperature, base, max_notes=None, redraws=0):
+    def _run(self, n, given, temperature, base, max_notes=None, redraws=0, particles=0):
         """The launches of one chunk of n steps from the static state, which they advance in place.  base: the step cell (a captured chunk:
         the kernels add its word to their counters) or None (eager: the host adds `steps`).  redraws > 0: the chunk first zeroes the
-        generator's statistics cell (a fill node of a captured chunk)."""
+        generator's statistics cell (a fill node of a captured chunk).  particles > 0: the chunk writes the generator's particle statistics
+        of a scan of n steps (common.particle_cells)."""
         gen = self._gen
+        sir = {}
+        if particles and given is not None and self._scan:
+            ess, pick = particle_cells(gen, n, gen.num_tracks, self.batch, self._cell.device)
+            sir = dict(particles=particles, ess=ess, pick=pick)
         step0 = 0 if base is not None else self.steps
         stats = None
         if redraws:
@@ -125,12 +131,13 @@ class GeneratorSession:
         if self._scan:
             return ops.generate_scan_chunk(None, n, temperature=temperature, seed=self.seed, row0=self.row0, state_in=self._rnn, state_out=self._rnn,
                                            given=given, step0=step0, step_base=base, max_notes=max_notes, redraws=redraws, redraw_stats=stats,
-                                           **gen._scan_layers())
+                                           **sir, **gen._scan_layers())
         with gen._sampling_scope():
             if not gen.det_sampling:
                 gen._ensure_packed()
             out, state, last = gen._scan_steps(gen._state_of(self._out, tuple(self._rnn)), self._last, n,
-                                               DrawAt(self.seed, self.row0, step0, base), given, temperature, max_notes, redraws)
+                                               DrawAt(self.seed, self.row0, step0, base), given, temperature, max_notes, redraws,
+                                               **(dict(particles=particles) if particles else {}))
             for (c, h), (nc, nh) in zip(self._rnn, state.rnn_state):      # behind the last read of the static arrays
                 c.copy_(nc)
                 h.copy_(nh)
@@ -163,6 +170,24 @@ class GeneratorSession:
         """The generator's redraw_counts(): (redrawn, fallback) of the last chunk (or generate call) that ran on it."""
         return self._gen.redraw_counts()
 
+    # The particles of the chunks to come (generate's particles): set between chunks, checked when set (common.sampling_particles); None, 0
+    # and 1 are the session without them.  Against the chunk's temperature and the session's max_notes they are checked per chunk; a chunk
+    # without `given`, and an RBM generator, run without them.
+    @property
+    def particles(self):
+        return self._particles
+
+    @particles.setter
+    def particles(self, value):
+        self._particles = sampling_particles(value)
+
+    def particle_ess(self):
+        """The generator's particle_ess() of the last chunk: f32 [B, num_steps, tracks], or None where it ran without particles."""
+        return self._gen.particle_ess()
+
+    def particle_picks(self):
+        return self._gen.particle_picks()
+
     def generate(self, num_steps, given=None, temperature=1.0):
         """The next num_steps steps -> u8 [B, num_steps, num_output].  given: the chunk's codes u8 [B, num_steps, num_output] as generate's
         (None: every cell free); temperature: as generate's, and free to change from chunk to chunk.  The chunk runs under the session's
@@ -171,32 +196,37 @@ class GeneratorSession:
         max_notes = self._max_notes
         redraws = sampling_redraws(self._redraws, max_notes, temperature)
         gen = self._gen
+        particles = gen._particles(self._particles, temperature, max_notes, given)
         gen._redraw_live = redraws > 0
+        fresh = (lambda: new_particle_cells(n, gen.num_tracks, self.batch, self._cell.device)) if particles else (lambda: None)
+        gen._particle_live = None
         if given is not None:
             given = given.to(self._cell.device).contiguous()
         if not ScanGraphs.enabled(self._cell):
-            out = self._run(n, given, temperature, None, max_notes, redraws)
+            gen._particle_live = fresh()
+            out = self._run(n, given, temperature, None, max_notes, redraws, particles)
             self.steps += n
             return out
-        key = (n, given is not None) + temperature_key(temperature) + max_notes_key(max_notes) + redraws_key(redraws)
+        key = (n, given is not None) + temperature_key(temperature) + max_notes_key(max_notes) + redraws_key(redraws) + particles_key(particles)
         ent = self._graphs.get(key)
         if ent is None:
             static_g = None if given is None else given.clone()
+            cells = gen._particle_live = fresh()     # the statistics arrays of this graph: created before the capture, kept with its entry
             snap = self.snapshot()
             w = min(n, 2)                            # a short eager run: kernel attributes and workspaces exist before the capture
-            _warm_up(lambda: self._run(w, None if static_g is None else static_g[:, :w].contiguous(), temperature, self._cell, max_notes, redraws))
+            _warm_up(lambda: self._run(w, None if static_g is None else static_g[:, :w].contiguous(), temperature, self._cell, max_notes, redraws, particles))
             self.restore(snap)
             g = torch.cuda.CUDAGraph()
             gen._packed_step = -1                    # pack inside the graph: a replay always sees the current weights
             with graph_capture(g, capture_error_mode="thread_local"):
-                out = self._run(n, static_g, temperature, self._cell, max_notes, redraws)
+                out = self._run(n, static_g, temperature, self._cell, max_notes, redraws, particles)
             gen._packed_step = -1                    # the packed copies now live in the graph's pool
-            ent = self._graphs[key] = (g, static_g, out)
+            ent = self._graphs[key] = (g, static_g, out, cells)
             while len(self._graphs) > MAX_GRAPHS:
                 self._graphs.popitem(last=False)
         else:
             self._graphs.move_to_end(key)
-        g, static_g, out = ent
+        g, static_g, out, gen._particle_live = ent
         if static_g is not None:
             static_g.copy_(given)
         self._cell.fill_(self.steps - (1 << 32) if self.steps >= 1 << 31 else self.steps)      # the word, as int32
@@ -226,6 +256,7 @@ class ModeSession:
         self.steps = 0
         self._max_notes = None
         self._redraws = 0
+        self._particles = 0
         if model._x_encoded is None:
             MultINNCore._build_all(model, "generate")
         self._subs = [g.session(x) for g, x in zip(model.generators, model._generator_inputs())]
@@ -267,6 +298,26 @@ class ModeSession:
         for s in self._subs:
             s.redraws = value
         self._redraws = value
+
+    # The particles of the chunks to come, as GeneratorSession's: checked when set, handed to every generator's session (an RBM generator
+    # ignores them).
+    @property
+    def particles(self):
+        return self._particles
+
+    @particles.setter
+    def particles(self, value):
+        value = sampling_particles(value)
+        for s in self._subs:
+            s.particles = value
+        self._particles = value
+
+    def particle_ess(self):
+        """The mode's particle_ess() of the last chunk: per generator f32 [B, num_steps, its tracks], or None where it ran without particles."""
+        return self._model.particle_ess()
+
+    def particle_picks(self):
+        return self._model.particle_picks()
 
     def redraw_counts(self):
         """(redrawn, fallback) of the last chunk, summed over the generators."""
