@@ -209,8 +209,9 @@ int mnn_lstm2_seq_bwd(mnn_stream_t s, int T, int B, const mnn_lstm_bwd_layer* L1
  * mnn_lstm2_seq_fwd / _bwd; same layer descriptors, same outputs).  A workgroup keeps its slice of the recurrent weights in
  * registers for the whole sequence and hands 32-row state tiles to the workgroups of the same row tile through
  * write-through stores into an exchange area + progress flags (multinn_amd/csrc/lstm_persist.hip).  Layer 2's input
- * projection is folded into its step, so L2->xproj is not used (may be NULL); backward, L1->dh_ext and both dz_T are
- * not used (may be NULL) and dz must be NULL.  Backward, L2->mask (optional): when given, L2->dh_ext is the gradient wrt
+ * projection is folded into its step, so L2->xproj is not used (may be NULL); backward, both dz_T are not used (may be
+ * NULL), and dz and L1->dh_ext must be NULL: layer 1's gradient comes from layer 2 inside the launch (dz2 . Wx2 through layer 1's
+ * dropout), so an external one would be dropped -- the entry refuses it.  Backward, L2->mask (optional): when given, L2->dh_ext is the gradient wrt
  * layer 2's DROPPED output and the launch applies the dropout backward itself (dh_ext / keep_prob * mask, the arithmetic of
  * mnn_dropout_bwd); when NULL, dh_ext is taken as the gradient wrt h2.
  * workspace: mnn_lstm2_persist_workspace_bytes(T,B,u1,u2) bytes of device memory, 256-byte aligned, zeroed ONCE by the

@@ -929,6 +929,7 @@ extern "C" int mnn_lstm2_persist_bwd(mnn_stream_t s, int T, int B, const mnn_lst
                 "mnn_lstm2_persist_bwd: units must be 128/256/512 with (u1+u2)/32 <= 32 and the grid must fit the device (B=%d u=%d,%d)", B,
                 L1->units, L2->units);
     MNN_REQUIRE(L2->dh_ext && L2->wx_p, "mnn_lstm2_persist_bwd: layer 2 needs dh_ext and wx_p (its input weights, [u1, 4u2])");
+    MNN_REQUIRE(L1->dh_ext == nullptr, "mnn_lstm2_persist_bwd: layer 1 takes no dh_ext (its gradient comes from layer 2 inside the launch)");
     for (const mnn_lstm_bwd_layer* L : {L1, L2}) {
         MNN_REQUIRE(L->wh_p && L->gates && L->c && L->workspace, "mnn_lstm2_persist_bwd: null pointer");
         MNN_REQUIRE(L->dz == nullptr, "mnn_lstm2_persist_bwd: an f32 dz output is not produced by the persistent form");

@@ -18,12 +18,14 @@ def _sig(a):
     return 1.0 / (1.0 + np.exp(-a))
 
 
-def forward(W, X, feedback=None):
+def forward(W, X, feedback=None, h0=None, c0=None):
     """W: wh_t [4u, u], X: xproj [T, B, u, 4], both float64.  feedback(t, h_t) -> the state step t + 1 reads (None: h_t itself).
-    Returns dict(g = activations [T, B, u, 4], c [T, B, u], h [T, B, u]) from a zero initial state."""
+    h0 / c0: the state step 0 starts from, [B, u] float64 (None: zeros).
+    Returns dict(g = activations [T, B, u, 4], c [T, B, u], h [T, B, u])."""
     T, B, u, _ = X.shape
     perm = gate_perm(u)
-    hp, cp = np.zeros((B, u)), np.zeros((B, u))
+    hp = np.zeros((B, u)) if h0 is None else np.asarray(h0, np.float64)
+    cp = np.zeros((B, u)) if c0 is None else np.asarray(c0, np.float64)
     ref = dict(g=np.zeros((T, B, u, 4)), c=np.zeros((T, B, u)), h=np.zeros((T, B, u)))
     for t in range(T):
         z = np.stack([X[t, :, :, g] + hp @ W[perm[g]].T for g in range(4)], -1)     # [B, u, 4]
@@ -37,10 +39,10 @@ def forward(W, X, feedback=None):
     return ref
 
 
-def backward(W, Gs, Cs, dh, mask=None, keep=1.0, feedback=None):
+def backward(W, Gs, Cs, dh, mask=None, keep=1.0, feedback=None, c0=None):
     """W: wh_t [4u, u]; Gs: saved activations [T, B, u, 4]; Cs: saved cell states [T, B, u]; dh: external gradient of the layer's output
     [T, B, u] (of y = h / keep * mask when a keep mask [T, B, u] is given), all float64.  feedback(t, dz_t) -> the dz[t] step t - 1 reads
-    (None: dz_t itself).  Returns dz [T, B, 4u]: pre-activation gradients in gate-interleaved columns."""
+    (None: dz_t itself).  c0: the initial cell state [B, u] the forward started from (None: zeros) -- c[t - 1] of step 0.  Returns dz [T, B, 4u]: pre-activation gradients in gate-interleaved columns."""
     T, B, u = Cs.shape
     perm = gate_perm(u)
     dz_ref = np.zeros((T, B, 4 * u))
@@ -51,7 +53,7 @@ def backward(W, Gs, Cs, dh, mask=None, keep=1.0, feedback=None):
         tc = np.tanh(Cs[t])
         d_o = dhv * tc
         d_c = dhv * go * (1 - tc * tc) + dcv
-        cprev = Cs[t - 1] if t > 0 else np.zeros((B, u))
+        cprev = Cs[t - 1] if t > 0 else (np.zeros((B, u)) if c0 is None else np.asarray(c0, np.float64))
         dzs = [d_c * gg * gi * (1 - gi), d_c * gi * (1 - gg * gg), d_c * cprev * gf * (1 - gf), d_o * go * (1 - go)]
         dcv = d_c * gf
         for g in range(4):
