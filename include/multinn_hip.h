@@ -769,6 +769,12 @@ typedef struct {
     const float* Wp;                                        /* optional: W repacked by mnn_det_dense_pack (see mnn_det_lstm_job.Wp) */
 } mnn_det_dense_job;
 int mnn_lstm_step_det(mnn_stream_t s, int B, int njobs, const mnn_det_lstm_job* jobs);
+/* Step t of RAGGED prompts (added without a version bump; DESIGN.md section 4 "Ragged prompts"): mnn_lstm_step_det in which, for every job
+ * of the launch, a row with t >= lengths[row] is FROZEN -- its c_out / h_out are copies of c_prev / h_prev (zeros where those are NULL) --
+ * and every other row is mnn_lstm_step_det's, bit for bit, whatever the frozen rows' inputs hold.  lengths: int32 [B] on the DEVICE, read
+ * there (only t is an argument of the launch: a captured launch follows new lengths); NULL is refused.  No value of a length makes the
+ * kernel index out of bounds.  A tile of 32 rows that are all frozen only copies.  c_out / h_out may not alias c_prev / h_prev. */
+int mnn_lstm_step_det_ragged(mnn_stream_t s, int B, int njobs, const mnn_det_lstm_job* jobs, const int32_t* lengths, int t);
 /* W f32 [K = inputs + units, 4 units] (TF layout) -> Wp (mnn_det_lstm_pack_bytes(K, units) bytes, 16-byte aligned) for mnn_det_lstm_job.Wp; to be
  * redone whenever W changes (mnn_generate_scan does it once per scan, into its workspace) */
 size_t mnn_det_lstm_pack_bytes(int K, int units);
@@ -860,6 +866,24 @@ int mnn_generate_scan_chunk_sir(mnn_stream_t s, int B, int n_intro, int num_step
                                 uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given,
                                 const float* const* c_in, const float* const* h_in, float* const* c_out, float* const* h_out, uint32_t step0,
                                 const uint32_t* step_base, const mnn_redraw* redraw, const mnn_sir* sir);
+/* ... and with RAGGED prompts (added without a version bump): intro_lengths int32 [B] on the device, row b's prompt being intro[b, 0 ..
+ * intro_lengths[b]) -- intro step t is mnn_lstm_step_det_ragged with t, so a row's state stops at its own length and whatever lies behind it
+ * in `intro` is never part of its arithmetic; everything behind the intro pass (the first Dense, the sample / step / Dense loop, the state
+ * copies) is untouched.  Row b is then, bit for bit, the one-row scan on intro[b, :intro_lengths[b]] with row0 + b; its generated step j is
+ * the step at absolute time intro_lengths[b] + j (samples, given and the counters stay row-relative).  Values are expected in 1..n_intro (the
+ * caller's to check: the device never reads them back); n_intro == 0 with lengths is refused.  intro_lengths NULL: the _sir entry points,
+ * which call these. */
+int mnn_generate_scan_ragged(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                             const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D, int Hn,
+                             const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed, uint32_t row0,
+                             uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0,
+                             const float* const* h0, const mnn_redraw* redraw, const mnn_sir* sir, const int32_t* intro_lengths);
+int mnn_generate_scan_chunk_ragged(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                   const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
+                                   int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed,
+                                   uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given,
+                                   const float* const* c_in, const float* const* h_in, float* const* c_out, float* const* h_out, uint32_t step0,
+                                   const uint32_t* step_base, const mnn_redraw* redraw, const mnn_sir* sir, const int32_t* intro_lengths);
 
 /* ------------------------------------------------------------------------------------------
  * Data-parallel exchange (the gradients of utils/training.py:151-177 as ONE flat f32 buffer): RCCL over xGMI, one

@@ -224,6 +224,10 @@ SIGNATURES["mnn_nade_sample_sir_workspace_bytes"] = (_sz, [_i, _i, _i, _i])
 SIGNATURES["mnn_nade_sample_sir_at"] = (_i, SIGNATURES["mnn_nade_sample_temps_at"][1] + [_p, _p])
 SIGNATURES["mnn_generate_scan_sir"] = (_i, SIGNATURES["mnn_generate_scan_redraw"][1] + [_p])
 SIGNATURES["mnn_generate_scan_chunk_sir"] = (_i, SIGNATURES["mnn_generate_scan_chunk_redraw"][1] + [_p])
+# ragged prompts (additions without a version bump): the step with (lengths, t); the _sir scans with a trailing const int32_t* intro_lengths
+SIGNATURES["mnn_lstm_step_det_ragged"] = (_i, SIGNATURES["mnn_lstm_step_det"][1] + [_p, _i])
+SIGNATURES["mnn_generate_scan_ragged"] = (_i, SIGNATURES["mnn_generate_scan_sir"][1] + [_p])
+SIGNATURES["mnn_generate_scan_chunk_ragged"] = (_i, SIGNATURES["mnn_generate_scan_chunk_sir"][1] + [_p])
 PARTICLES_MAX = 1024       # mnn_sir.particles
 TEMPS_MAX = 8              # MNN_TEMPS_MAX
 REDRAWS_MAX = 255          # mnn_redraw.tries

@@ -121,36 +121,41 @@ class ScanGraphs:
     def enabled(x):
         return x.is_cuda and flag("MULTINN_GENERATE_GRAPH") and not torch.cuda.is_current_stream_capturing()
 
-    def run(self, key, x, scan, warm, after_capture, extra=None):
+    def run(self, key, x, scan, warm, after_capture, extra=None, lengths=None):
         """scan(static_x) -> output tensor (captured); warm(static_x): a short eager run that creates parameters and
         workspaces before the capture; after_capture(): drop host-side caches that now point into the graph's pool.
         extra (optional, e.g. the codes of a conditioned scan): a second input, then scan(static_x, static_extra) and
-        warm(static_x, static_extra)."""
+        warm(static_x, static_extra).  lengths (optional, the prompt lengths of a ragged scan: int32 [B] on the device): a third input,
+        handed on as the keyword `lengths` of scan and warm."""
         ent = self._cache.get(key)
         if ent is None:
             static_x = x.clone()
             static_e = None if extra is None else extra.clone()
+            static_l = None if lengths is None else lengths.clone()
             args = (static_x,) if extra is None else (static_x, static_e)
-            _warm_up(lambda: warm(*args))
+            kw = {} if lengths is None else dict(lengths=static_l)
+            _warm_up(lambda: warm(*args, **kw))
             g = torch.cuda.CUDAGraph()
             with graph_capture(g, capture_error_mode="thread_local"):
-                out = scan(*args)
+                out = scan(*args, **kw)
             after_capture()
-            ent = (g, static_x, out, static_e)
+            ent = (g, static_x, out, static_e, static_l)
             self._cache[key] = ent
             while len(self._cache) > self._max:
                 self._cache.popitem(last=False)
         else:
             self._cache.move_to_end(key)
-        g, static_x, out, static_e = ent
+        g, static_x, out, static_e, static_l = ent
         static_x.copy_(x)
         if static_e is not None:
             static_e.copy_(extra)
+        if static_l is not None:
+            static_l.copy_(lengths)
         g.replay()
         return out.clone()
 
     @staticmethod
-    def generate(owner, key, x, num_steps, given, temperature, scan, stale, max_notes=None, redraws=0, particles=0, stats_shape=None):
+    def generate(owner, key, x, num_steps, given, temperature, scan, stale, max_notes=None, redraws=0, particles=0, stats_shape=None, lengths=None):
         """The one capture wrapper of a `generate`: scan(x, num_steps, given, temperature) eagerly where graphs are off, else one replay of
         the scan captured under key + ("given",) + temperature_key (a new given of the same shape replays the same graph; the temperature
         is baked into the captured launches, nothing at 1.0: the scan captured without it) from the cache kept on `owner`.  max_notes (a
@@ -158,7 +163,9 @@ class ScanGraphs:
         redraws (normalised, sampling_redraws; 0: nothing changes): a sixth argument of scan, and redraws_key; particles (normalised,
         sampling_particles; 0: nothing changes): the keyword `particles` of scan, and particles_key; with them stats_shape = (num_steps,
         tracks, B): the owner's `_particle_live` becomes the statistics arrays this scan writes -- new ones for an eager call, the graph
-        entry's for a captured one (created before the capture, dropped with the entry).  stale(): mark
+        entry's for a captured one (created before the capture, dropped with the entry).  lengths (normalised prompt lengths on the
+        device, int32 [B]; None: nothing changes): the keyword `lengths` of scan, the key gains ("lengths",) and nothing else -- they are
+        a third static input, so other lengths of the same shape replay the same graph.  stale(): mark
         the owner's packed weight copies stale -- before the capture (the graph packs them itself: a replay always sees the current
         weights) and after it (the packed copies then live in the graph's pool).  The warm-up is the scan's first min(num_steps, 2) steps."""
         cap = () if max_notes is None else ((max_notes,) if not redraws else (max_notes, redraws))
@@ -166,12 +173,16 @@ class ScanGraphs:
         if not ScanGraphs.enabled(x):
             if particles and stats_shape is not None:
                 owner._particle_live = new_particle_cells(*stats_shape, x.device)
+            if lengths is not None:
+                kw["lengths"] = lengths
             return scan(x, num_steps, given, temperature, *cap, **kw)
         if getattr(owner, "_scan_graphs", None) is None:
             owner._scan_graphs = ScanGraphs()
         if given is not None:
             key = key + ("given",)
         key = key + temperature_key(temperature) + max_notes_key(max_notes) + redraws_key(redraws) + particles_key(particles)
+        if lengths is not None:
+            key = key + ("lengths",)
         if particles and stats_shape is not None:
             graphs = owner._scan_graphs
             graphs._stats = {k: v for k, v in graphs._stats.items() if k in graphs._cache}
@@ -180,14 +191,16 @@ class ScanGraphs:
                 graphs._stats[key] = new_particle_cells(*stats_shape, x.device)
             owner._particle_live = graphs._stats[key]
 
-        def captured(sx, sg=None):
+        def captured(sx, sg=None, **lk):
             stale()
-            return scan(sx, num_steps, sg, temperature, *cap, **kw)
+            return scan(sx, num_steps, sg, temperature, *cap, **kw, **lk)
 
-        def warm(sx, sg=None):
+        def warm(sx, sg=None, **lk):
             n = min(int(num_steps), 2)
-            return scan(sx, n, None if sg is None else sg[:, :n].contiguous(), temperature, *cap, **kw)
+            return scan(sx, n, None if sg is None else sg[:, :n].contiguous(), temperature, *cap, **kw, **lk)
 
+        if lengths is not None:
+            return owner._scan_graphs.run(key, x, captured, warm, stale, extra=given, lengths=lengths)
         return owner._scan_graphs.run(key, x, captured, warm, stale, extra=given)
 
 
@@ -406,6 +419,69 @@ def redraw_counts(owner):
         return 0, 0
     n = owner._redraw_stats.cpu()
     return int(n[0]), int(n[1])
+
+
+# --------------------------------------------------------------------------------------------
+# Ragged prompts.  With `lengths` row b of an intro x [B, Ti, ...] is the prompt x[b, :lengths[b]]: the intro pass stops that row's LSTM state
+# at its own length (ops.lstm_step_det: lengths, t) and generated step j of the row is the step at absolute time lengths[b] + j.  Row b of
+# the call is then, bit for bit, the one-row call on x[b:b+1, :lengths[b]] with row0 + b (DESIGN.md section 4 "Ragged prompts").
+def prompt_lengths(lengths, B, Ti, what="lengths"):
+    """The one normalisation of a generation call's prompt lengths, on the host, before any device work: None (the entries, kernels, bits,
+    graph key and captured scan of a call without the argument) or a tuple of B ints in 1..Ti that are not all Ti.  Accepted: a sequence of
+    ints, an integer NumPy array or an integer CPU tensor of B entries; None and "every entry equals Ti" are None.  ValueError: bools,
+    non-integers, a wrong count, a value outside 1..Ti -- and a tensor on a device, which could only be checked by synchronising.
+    B = Ti = None (a mode whose x is not built yet): only what needs neither is checked, and the tuple is returned."""
+    import numbers
+    import numpy as np
+    if lengths is None:
+        return None
+    if B is None or Ti is None:
+        B = Ti = None
+    else:
+        B, Ti = int(B), int(Ti)
+    if torch.is_tensor(lengths):
+        if lengths.device.type != "cpu":
+            raise ValueError(f"{what} must live on the host (a sequence, a NumPy array or a CPU tensor): checking a tensor on {lengths.device} "
+                             "would synchronise")
+        if lengths.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64) or lengths.dim() != 1:
+            raise ValueError(f"{what} must be integers, one per row, got a {lengths.dtype} tensor of shape {tuple(lengths.shape)}")
+        vals = lengths.tolist()
+    elif isinstance(lengths, np.ndarray):
+        if lengths.dtype.kind not in "iu" or lengths.ndim != 1:
+            raise ValueError(f"{what} must be integers, one per row, got a {lengths.dtype} array of shape {lengths.shape}")
+        vals = lengths.tolist()
+    elif isinstance(lengths, (list, tuple)):
+        vals = list(lengths)
+        if any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in vals):
+            raise ValueError(f"{what} must be integers, one per row, got {lengths!r}")
+        vals = [int(v) for v in vals]
+    else:
+        raise ValueError(f"{what} must be None, a sequence of ints, an integer NumPy array or an integer CPU tensor, got {type(lengths).__name__}")
+    if B is None:
+        if any(v < 1 for v in vals):
+            raise ValueError(f"{what} must be >= 1, got {vals}")
+        return tuple(vals)
+    if len(vals) != B:
+        raise ValueError(f"{what} must have one entry per row ({B}), got {len(vals)}")
+    if any(not 1 <= v <= Ti for v in vals):
+        raise ValueError(f"{what} must lie in 1..{Ti} (the intro's steps), got {vals}")
+    return None if all(v == Ti for v in vals) else tuple(vals)
+
+
+def prompt_lengths_device(lengths, device):
+    """Normalised prompt lengths (a tuple) as the int32 [B] array the kernels read, on `device`."""
+    return torch.tensor(lengths, dtype=torch.int32).to(device)
+
+
+def last_prompt_rows(x, lengths_dev):
+    """x[b, lengths[b] - 1] of every row, gathered on the device: the last row of each prompt (a Gibbs chain's start)."""
+    return x[torch.arange(x.shape[0], device=x.device), lengths_dev.long() - 1]
+
+
+def refuse_prompt_lengths(lengths, who, why):
+    """The paths without a ragged form: any lengths (None excepted) raise MnnUnsupported, before any device work."""
+    if lengths is not None:
+        raise MnnUnsupported(f"{who}: prompt lengths are not supported here ({why})")
 
 
 # --------------------------------------------------------------------------------------------

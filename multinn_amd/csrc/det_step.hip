@@ -202,13 +202,42 @@ extern "C" int mnn_ds_trace_read(long long* host) { return hipMemcpyFromSymbol(h
 #else
 #define DS_TR(k) do { } while (0)
 #endif
-__global__ void __launch_bounds__(256) lstm_step_det_kernel(DetLstmJobs J, int B) {
+// RAGGED (mnn_lstm_step_det_ragged; DESIGN.md section 4 "Ragged prompts"): step t of prompts of different lengths.  A row with
+// t >= lengths[row] is FROZEN -- its c_out / h_out are copies of c_prev / h_prev (zeros where those are NULL) --, a live row is the step
+// without the argument, bit for bit: a row is one column of the MFMA's B operand, so whatever a frozen row stages (padding, NaN) reaches
+// no other row.  lengths is read on the device (only t is an argument of the launch); rows past B are never looked up, so no value of a
+// length indexes anything.  The argument is an empty type for RAGGED = false (as SampleCapsArg in nade.hip): that instantiation is the
+// kernel as it was.
+struct DetRagged { const int32_t* lengths; int t; };
+struct DetNoRagged {};
+template <bool RAGGED> struct DetRaggedArg { typedef DetNoRagged T; };
+template <> struct DetRaggedArg<true> { typedef DetRagged T; };
+
+template <bool RAGGED>
+__global__ void __launch_bounds__(256) lstm_step_det_kernel(DetLstmJobs J, int B, typename DetRaggedArg<RAGGED>::T RG) {
     extern __shared__ __attribute__((aligned(16))) float ds_smem[];
     DS_TR(0);
     const mnn_det_lstm_job& jb = J.job[blockIdx.z];
     const int u = jb.units, ub = blockIdx.x * 8;
     if (ub >= u) return;                             // the grid covers the widest job
     const int r0 = blockIdx.y * 32;
+    unsigned live_rows = 0xffffffffu;                // RAGGED: bit rr = row r0 + rr takes the step
+    if constexpr (RAGGED) {
+        // every wave forms the tile's 32 bits itself (lanes l and l + 32 look at row r0 + l): the same word in all four waves, so the
+        // decision below is workgroup-uniform without a barrier
+        const int lr = r0 + (threadIdx.x & 31);
+        const bool lv = lr < B && RG.t < RG.lengths[min(lr, B - 1)];
+        live_rows = (unsigned)__ballot(lv);
+        if (live_rows == 0) {                        // a tile whose rows are all frozen: no staging, no chain -- the copies alone
+            const int row = r0 + (threadIdx.x >> 3), un = ub + (threadIdx.x & 7);
+            if (row < B) {
+                const size_t at = (size_t)row * u + un;
+                jb.c_out[at] = jb.c_prev != nullptr ? jb.c_prev[at] : 0.f;
+                jb.h_out[at] = jb.h_prev != nullptr ? jb.h_prev[at] : 0.f;
+            }
+            return;
+        }
+    }
     const int n1 = jb.n_x, n2 = jb.n_x2;
     const int K = n1 + n2 + u;
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r = lane & 31, hh = lane >> 5;    // (w in a scalar register: the chain's bounds tests are then scalar branches, not an exec-mask dance around every MFMA)
@@ -259,6 +288,14 @@ __global__ void __launch_bounds__(256) lstm_step_det_kernel(DetLstmJobs J, int B
     // pointwise: thread -> (unit ub + (t & 7), row r0 + (t >> 3)); accumulator register of A row i = g * 8 + uu: e = 4 g + (uu & 3), lane half uu >> 2
     const int uu = threadIdx.x & 7, rr = threadIdx.x >> 3, row = r0 + rr, un = ub + uu;
     if (row >= B) return;
+    if constexpr (RAGGED) {
+        if (!((live_rows >> rr) & 1u)) {             // a frozen row of a mixed tile
+            const size_t at = (size_t)row * u + un;
+            jb.c_out[at] = jb.c_prev != nullptr ? jb.c_prev[at] : 0.f;
+            jb.h_out[at] = jb.h_prev != nullptr ? jb.h_prev[at] : 0.f;
+            return;
+        }
+    }
     float z[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -332,7 +369,8 @@ static size_t ds_lds_bytes(int K) { const int kc = (min(DS_KC, K) + 1) & ~1; ret
 static hipError_t ds_raise_lds() {
     static MnnPerDeviceOnce raised;
     return mnn_once_per_device(raised, [] {
-        const hipError_t e = mnn_raise_dynamic_lds(reinterpret_cast<const void*>(&lstm_step_det_kernel), 160 * 1024);
+        hipError_t e = mnn_raise_dynamic_lds(reinterpret_cast<const void*>(&lstm_step_det_kernel<false>), 160 * 1024);
+        if (e == hipSuccess) e = mnn_raise_dynamic_lds(reinterpret_cast<const void*>(&lstm_step_det_kernel<true>), 160 * 1024);
         return e != hipSuccess ? e : mnn_raise_dynamic_lds(reinterpret_cast<const void*>(&dense_det_kernel), 160 * 1024);
     });
 }
@@ -361,11 +399,11 @@ extern "C" int mnn_det_dense_pack(mnn_stream_t s, const float* W, int K, int N, 
     return MNN_OK;
 }
 
-extern "C" int mnn_lstm_step_det(mnn_stream_t s, int B, int njobs, const mnn_det_lstm_job* jobs) {
+// the checks of a step launch and its argument block -> MNN_OK; umax / kmax: the widest job and the longest chain (grid, LDS)
+static int ds_lstm_jobs(int B, int njobs, const mnn_det_lstm_job* jobs, DetLstmJobs& J, int& umax, int& kmax) {
     MNN_REQUIRE(B > 0 && njobs > 0 && njobs <= DS_MAXJOBS && jobs != nullptr, "mnn_lstm_step_det: 1..%d jobs, B > 0", DS_MAXJOBS);
-    DetLstmJobs J;
     memset(&J, 0, sizeof(J));
-    int umax = 0, kmax = 0;
+    umax = kmax = 0;
     for (int j = 0; j < njobs; ++j) {
         const mnn_det_lstm_job& jb = jobs[j];
         MNN_REQUIRE(jb.units > 0 && jb.units % 32 == 0 && jb.W && jb.bias && jb.c_out && jb.h_out, "mnn_lstm_step_det: job %d: units %% 32, W, bias, c_out, h_out", j);
@@ -376,9 +414,33 @@ extern "C" int mnn_lstm_step_det(mnn_stream_t s, int B, int njobs, const mnn_det
         umax = max(umax, jb.units);
         kmax = max(kmax, jb.n_x + jb.n_x2 + jb.units);
     }
+    return MNN_OK;
+}
+
+extern "C" int mnn_lstm_step_det(mnn_stream_t s, int B, int njobs, const mnn_det_lstm_job* jobs) {
+    DetLstmJobs J;
+    int umax, kmax;
+    const int rc = ds_lstm_jobs(B, njobs, jobs, J, umax, kmax);
+    if (rc != MNN_OK) return rc;
     MNN_HIP(ds_raise_lds());
     dim3 grid(umax / 8, cdiv(B, 32), njobs);
-    hipLaunchKernelGGL(lstm_step_det_kernel, grid, dim3(256), ds_lds_bytes(kmax), (hipStream_t)s, J, B);
+    hipLaunchKernelGGL(lstm_step_det_kernel<false>, grid, dim3(256), ds_lds_bytes(kmax), (hipStream_t)s, J, B, DetNoRagged());
+    MNN_LAUNCH_CHECK();
+    return MNN_OK;
+}
+
+// step t of ragged prompts: every job of the launch freezes the rows with t >= lengths[row] (int32 [B] on the device, read there)
+extern "C" int mnn_lstm_step_det_ragged(mnn_stream_t s, int B, int njobs, const mnn_det_lstm_job* jobs, const int32_t* lengths, int t) {
+    MNN_REQUIRE(lengths != nullptr, "mnn_lstm_step_det_ragged: null lengths (mnn_lstm_step_det is the step without them)");
+    DetLstmJobs J;
+    int umax, kmax;
+    const int rc = ds_lstm_jobs(B, njobs, jobs, J, umax, kmax);
+    if (rc != MNN_OK) return rc;
+    MNN_HIP(ds_raise_lds());
+    dim3 grid(umax / 8, cdiv(B, 32), njobs);
+    DetRagged RG;
+    RG.lengths = lengths; RG.t = t;
+    hipLaunchKernelGGL(lstm_step_det_kernel<true>, grid, dim3(256), ds_lds_bytes(kmax), (hipStream_t)s, J, B, RG);
     MNN_LAUNCH_CHECK();
     return MNN_OK;
 }
@@ -438,7 +500,7 @@ static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps,
                               uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given, const float* const* c0,
                               const float* const* h0, float* const* c_out = nullptr, float* const* h_out = nullptr, uint32_t step0 = 0,
                               const uint32_t* step_base = nullptr, bool chunk = false, const mnn_caps* caps = nullptr,
-                              const mnn_redraw* redraw = nullptr, const mnn_sir* sir = nullptr) {
+                              const mnn_redraw* redraw = nullptr, const mnn_sir* sir = nullptr, const int32_t* intro_lengths = nullptr) {
     MNN_REQUIRE(temps, "mnn_generate_scan: null temps");     // (its contents: mnn_nade_sample_temps, before anything is enqueued when num_steps > 0)
     // redraw (NULL: none): the redraws of every sample call (mnn_nade_sample_redraw_at, which checks them again with the rest) -- here in front of the intro pass
     MNN_REQUIRE(redraw == nullptr || redraw->tries == 0 || (redraw->tries > 0 && redraw->tries <= 255 && temps->n > 0),
@@ -492,7 +554,8 @@ static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps,
     }
     int cur = 0;                                               // generation holding the current state; -1 before the first step (zero state)
     bool have_state = false;
-    auto stack_step = [&](const uint8_t* x, int ld_x) -> int {      // one step of the whole stack on a u8 input block
+    // one step of the whole stack on a u8 input block; rt >= 0: intro step rt of ragged prompts (intro_lengths), whose finished rows keep their state
+    auto stack_step = [&](const uint8_t* x, int ld_x, int rt = -1) -> int {
         const int nxt = cur ^ 1;
         for (int l = 0; l < n_layers; ++l) {
             mnn_det_lstm_job jb;
@@ -503,7 +566,7 @@ static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps,
             jb.h_prev = have_state ? hbuf[l][cur] : (h0 ? h0[l] : nullptr);
             jb.c_prev = have_state ? cbuf[l][cur] : (c0 ? c0[l] : nullptr);
             jb.W = layers[l].W; jb.Wp = wpack[l]; jb.bias = layers[l].bias; jb.c_out = cbuf[l][nxt]; jb.h_out = hbuf[l][nxt]; jb.units = u;
-            const int rc = mnn_lstm_step_det(s, B, 1, &jb);
+            const int rc = rt >= 0 ? mnn_lstm_step_det_ragged(s, B, 1, &jb, intro_lengths, rt) : mnn_lstm_step_det(s, B, 1, &jb);
             if (rc != MNN_OK) return rc;
         }
         cur = nxt;
@@ -520,7 +583,7 @@ static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps,
         return mnn_dense_det(s, B, 1, &dj);
     };
     for (int t = 0; t < n_intro; ++t) {
-        const int rc = stack_step(intro + (size_t)t * n_in, n_intro * n_in);
+        const int rc = stack_step(intro + (size_t)t * n_in, n_intro * n_in, intro_lengths != nullptr ? t : -1);
         if (rc != MNN_OK) return rc;
     }
     int rc = dense();
@@ -561,13 +624,15 @@ static int generate_scan_impl(mnn_stream_t s, int B, int n_intro, int num_steps,
 // caps (NULL: none): the polyphony caps of every sample call of the chunk (mnn_nade_sample_caps_at).
 // redraw (NULL: none): their redraws (mnn_redraw).
 // sir (NULL: none): their importance resampling (mnn_sir).
-extern "C" int mnn_generate_scan_chunk_sir(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
-                                           const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks,
-                                           int D, int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps,
-                                           uint64_t seed, uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes,
-                                           const uint8_t* given, const float* const* c_in, const float* const* h_in, float* const* c_out,
-                                           float* const* h_out, uint32_t step0, const uint32_t* step_base, const mnn_redraw* redraw,
-                                           const mnn_sir* sir) {
+// intro_lengths (NULL: none): ragged prompts -- int32 [B] on the device; intro step t is mnn_lstm_step_det_ragged with t, the rest as without.
+extern "C" int mnn_generate_scan_chunk_ragged(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                              const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks,
+                                              int D, int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps,
+                                              uint64_t seed, uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes,
+                                              const uint8_t* given, const float* const* c_in, const float* const* h_in, float* const* c_out,
+                                              float* const* h_out, uint32_t step0, const uint32_t* step_base, const mnn_redraw* redraw,
+                                              const mnn_sir* sir, const int32_t* intro_lengths) {
+    MNN_REQUIRE(intro_lengths == nullptr || n_intro > 0, "mnn_generate_scan_chunk_ragged: intro_lengths without an intro (n_intro == 0)");
     MNN_REQUIRE((c_in == nullptr) == (h_in == nullptr) && (c_out == nullptr) == (h_out == nullptr),
                 "mnn_generate_scan_chunk: c_in / h_in and c_out / h_out come in pairs (arrays of n_layers pointers) or not at all");
     MNN_REQUIRE(n_layers > 0 && n_layers <= MNN_SCAN_MAX_LAYERS, "mnn_generate_scan_chunk: 1..%d layers", MNN_SCAN_MAX_LAYERS);
@@ -576,7 +641,19 @@ extern "C" int mnn_generate_scan_chunk_sir(mnn_stream_t s, int B, int n_intro, i
     MNN_REQUIRE(n_intro >= 0 && num_steps >= 0 && n_intro + num_steps > 0, "mnn_generate_scan_chunk: n_intro, num_steps >= 0 and one of them > 0");
     MNN_REQUIRE(n_intro > 0 || c_in != nullptr, "mnn_generate_scan_chunk: a chunk without intro continues from c_in / h_in");
     return generate_scan_impl(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc, w_dec, temps,
-                              seed, row0, samples, workspace, workspace_bytes, given, c_in, h_in, c_out, h_out, step0, step_base, true, caps, redraw, sir);
+                              seed, row0, samples, workspace, workspace_bytes, given, c_in, h_in, c_out, h_out, step0, step_base, true, caps, redraw, sir,
+                              intro_lengths);
+}
+extern "C" int mnn_generate_scan_chunk_sir(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                           const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks,
+                                           int D, int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps,
+                                           uint64_t seed, uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes,
+                                           const uint8_t* given, const float* const* c_in, const float* const* h_in, float* const* c_out,
+                                           float* const* h_out, uint32_t step0, const uint32_t* step_base, const mnn_redraw* redraw,
+                                           const mnn_sir* sir) {
+    return mnn_generate_scan_chunk_ragged(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc,
+                                          w_dec, temps, caps, seed, row0, samples, workspace, workspace_bytes, given, c_in, h_in, c_out, h_out, step0,
+                                          step_base, redraw, sir, nullptr);
 }
 extern "C" int mnn_generate_scan_chunk_redraw(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
                                               const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks,
@@ -611,18 +688,30 @@ extern "C" int mnn_generate_scan_chunk(mnn_stream_t s, int B, int n_intro, int n
 // ... and polyphony caps (NULL: none)
 // ... and redraws (NULL: none)
 // ... and importance resampling (NULL: none)
-extern "C" int mnn_generate_scan_sir(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
-                                     const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
-                                     int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed,
-                                     uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given,
-                                     const float* const* c0, const float* const* h0, const mnn_redraw* redraw, const mnn_sir* sir) {
+// ... and ragged prompts (intro_lengths int32 [B] on the device; NULL: none)
+extern "C" int mnn_generate_scan_ragged(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                        const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
+                                        int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed,
+                                        uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given,
+                                        const float* const* c0, const float* const* h0, const mnn_redraw* redraw, const mnn_sir* sir,
+                                        const int32_t* intro_lengths) {
+    MNN_REQUIRE(intro_lengths == nullptr || n_intro > 0, "mnn_generate_scan_ragged: intro_lengths without an intro (n_intro == 0)");
     MNN_REQUIRE((c0 == nullptr) == (h0 == nullptr), "mnn_generate_scan_state: c0 and h0 come together (arrays of n_layers pointers) or not at all");
     if (c0 != nullptr) {
         MNN_REQUIRE(n_layers > 0 && n_layers <= MNN_SCAN_MAX_LAYERS, "mnn_generate_scan_state: 1..%d layers", MNN_SCAN_MAX_LAYERS);
         for (int l = 0; l < n_layers; ++l) MNN_REQUIRE(c0[l] && h0[l], "mnn_generate_scan_state: layer %d has no initial state", l);
     }
     return generate_scan_impl(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc, w_dec, temps,
-                              seed, row0, samples, workspace, workspace_bytes, given, c0, h0, nullptr, nullptr, 0, nullptr, false, caps, redraw, sir);
+                              seed, row0, samples, workspace, workspace_bytes, given, c0, h0, nullptr, nullptr, 0, nullptr, false, caps, redraw, sir,
+                              intro_lengths);
+}
+extern "C" int mnn_generate_scan_sir(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
+                                     const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,
+                                     int Hn, const float* w_enc, const float* w_dec, const mnn_temps* temps, const mnn_caps* caps, uint64_t seed,
+                                     uint32_t row0, uint8_t* samples, void* workspace, size_t workspace_bytes, const uint8_t* given,
+                                     const float* const* c0, const float* const* h0, const mnn_redraw* redraw, const mnn_sir* sir) {
+    return mnn_generate_scan_ragged(s, B, n_intro, num_steps, intro, n_in, n_layers, layers, dense_W, dense_bias, n_out, tracks, D, Hn, w_enc, w_dec,
+                                    temps, caps, seed, row0, samples, workspace, workspace_bytes, given, c0, h0, redraw, sir, nullptr);
 }
 extern "C" int mnn_generate_scan_redraw(mnn_stream_t s, int B, int n_intro, int num_steps, const uint8_t* intro, int n_in, int n_layers,
                                         const mnn_scan_lstm_layer* layers, const float* dense_W, const float* dense_bias, int n_out, int tracks, int D,

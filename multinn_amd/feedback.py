@@ -221,16 +221,19 @@ class FeedbackRnnSampler:
         from .common import redraw_counts
         return redraw_counts(self)
 
-    def generate(self, x_u8, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=None):
+    def generate(self, x_u8, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=None, lengths=None):
         """x_u8 [B,Ti,P,M] intro piano-rolls -> samples u8 [B,num_steps,P,M].  particles > 1 with given: MnnUnsupported (the grouped
-        multi-job sample launch of a step has no particle form).  One hipGraph replay per call on the
+        multi-job sample launch of a step has no particle form).  lengths (common.prompt_lengths) other than None / all Ti:
+        MnnUnsupported (the intro pass of this scan also carries the feedback module's state).  One hipGraph replay per call on the
         device (common.ScanGraphs): the M generators and the feedback module step inside the same captured scan.
         given (optional): codes u8 [B, num_steps, P, M] (common.given_codes), see generate_encoded.
         temperature: one for all generators or generator m's own, temperature[m]; 1.0 is the call (and the captured scan) without it.
         max_notes: None, one cap (an integer >= 0) for all generators or generator m's own, max_notes[m] (None: no cap); None is the call
         (and the captured scan) without it.  redraws (common.sampling_redraws): the cap by rejection in every generator's step; 0, or
         no cap, is the call (and the captured scan) without it."""
-        from .common import ScanGraphs, refuse_particles, sampling_particles, sampling_redraws
+        from .common import ScanGraphs, prompt_lengths, refuse_particles, refuse_prompt_lengths, sampling_particles, sampling_redraws
+        refuse_prompt_lengths(prompt_lengths(lengths, x_u8.shape[0], x_u8.shape[1]), "FeedbackRnnSampler",
+                              "the intro pass of the feedback scan also carries the feedback module's state")
         if given is not None:
             refuse_particles(particles, "FeedbackRnnSampler")
         sampling_particles(particles)

@@ -22,7 +22,7 @@ import torch
 
 from . import ops
 from .switches import flag, value
-from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, DrawAt, check_given, given_codes, given_mask_tracks, sampling_temperature, sampling_max_notes, sampling_redraws, sampling_particles, particle_cells, particle_stats, redraw_cell, redraw_counts, glorot_uniform, zeros_init, default_device, capture_train_step
+from .common import Model, RNN, NADE, RBM, ParamStore, ScanGraphs, DrawAt, check_given, given_codes, given_mask_tracks, sampling_temperature, sampling_max_notes, sampling_redraws, sampling_particles, prompt_lengths, prompt_lengths_device, last_prompt_rows, particle_cells, particle_stats, redraw_cell, redraw_counts, glorot_uniform, zeros_init, default_device, capture_train_step
 from .training import compute_gradients, world, dp_active, AdamOptimizer
 from ._lib import MnnUnsupported
 from .lstm_stack import LstmStack, _SINGLE, drive, drive_group, _det_f32, det_steps
@@ -232,7 +232,7 @@ class Generator(Model):
         return self._outputs
 
     @abc.abstractmethod
-    def generate(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=None):
+    def generate(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=None, lengths=None):
         ...
 
     def pretrain(self, optimizer, lr, run_optimizer=True):
@@ -381,19 +381,43 @@ class RnnEstimator(Generator):
     # kernels (hardware exp2 / rcp activations, packed 16-bit weights), whose scans can only be checked to a tolerance.
     det_sampling = flag("MULTINN_DET_SAMPLING")
 
-    def steps(self, inputs, initial_state=None):
-        """rnn_estimator.py:237-252: run the RNN over `inputs` [B,T,Din] and return the state after the last step."""
+    def steps(self, inputs, initial_state=None, lengths=None):
+        """rnn_estimator.py:237-252: run the RNN over `inputs` [B,T,Din] and return the state after the last step.  lengths (optional;
+        common.prompt_lengths): row b's sequence is inputs[b, :lengths[b]] and its state the one behind ITS last step -- bit for bit the
+        state of the one-row call on that slice, whatever lies behind it in `inputs`."""
+        if inputs.dim() == 2:
+            lengths = prompt_lengths(lengths, inputs.shape[0], 1)
+        else:
+            lengths = prompt_lengths(lengths, inputs.shape[0], inputs.shape[1])
+        if lengths is not None:
+            self._refuse_prompt_lengths("steps(lengths=)")
+            return self._det_steps(inputs, initial_state, prompt_lengths_device(lengths, inputs.device))
         if self.det_sampling:
-            self._materialize(inputs.shape[-1])
-            if inputs.dim() == 2:
-                inputs = inputs[:, None, :]
-            x = inputs if inputs.dtype in (torch.uint8, torch.float32) else inputs.float()
-            st = self._state0(x.shape[0], torch.float32) if initial_state is None else [(c, h) for c, h in initial_state.rnn_state]
-            h = None
-            for t in range(x.shape[1]):
-                h, st = self._stack.det_step(x[:, t], st)
-            return self._det_state(h, st)
+            return self._det_steps(inputs, initial_state)
         return self._get_state(inputs, initial_state=initial_state, last_outputs=True)
+
+    def _det_steps(self, inputs, initial_state=None, lengths=None):
+        """steps in the deterministic arithmetic; lengths: normalised prompt lengths on the device (int32 [B]) or None."""
+        self._materialize(inputs.shape[-1])
+        if inputs.dim() == 2:
+            inputs = inputs[:, None, :]
+        x = inputs if inputs.dtype in (torch.uint8, torch.float32) else inputs.float()
+        st = self._state0(x.shape[0], torch.float32) if initial_state is None else [(c, h) for c, h in initial_state.rnn_state]
+        h = None
+        for t in range(x.shape[1]):
+            if lengths is None:
+                h, st = self._stack.det_step(x[:, t], st)
+            else:                           # a row whose prompt has ended keeps its state: h is then its last live step's output
+                h, st = self._stack.det_step(x[:, t], st, lengths=lengths, t=t)
+        return self._det_state(h, st)
+
+    def _refuse_prompt_lengths(self, what):
+        """MnnUnsupported, before any device work, where prompt lengths have no form: a model on the host, and the throughput recurrences
+        (MULTINN_DET_SAMPLING=0), which return only the state behind the intro's last step."""
+        refuse_host_model(self.store.device, what)
+        if not self.det_sampling:
+            raise MnnUnsupported(f"{what} needs the deterministic sampling steps: with MULTINN_DET_SAMPLING=0 the intro pass runs the throughput "
+                                 "recurrences, which return only the state behind the intro's last step")
 
     def _temperature(self, temperature):
         """generate's `temperature`, normalised (common.sampling_temperature): NADE estimators take None and one value per track (of a
@@ -413,7 +437,7 @@ class RnnEstimator(Generator):
         Gibbs chain already conditions on every given cell); the NADE estimators override it."""
         return 0
 
-    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=0):
+    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=0, lengths=None):
         return None                         # estimators without a one-call scan (RnnRBM) step through sample_single / single_step
 
     # -- generation sessions (session.py) --------------------------------------------------------
@@ -424,6 +448,12 @@ class RnnEstimator(Generator):
         temperature) continues the piece chunk by chunk, the chunks concatenated being generate(x, n, ...) bit for bit."""
         from .session import GeneratorSession
         return GeneratorSession(self, x)
+
+    def ragged_session(self, x, lengths):
+        """session(x) on ragged prompts: generate's `lengths` (GeneratorSession(gen, x, lengths)).  The session opens behind every row's own
+        prompt; its chunks need nothing new, and concatenated they are generate(x, n, ..., lengths=lengths) bit for bit."""
+        from .session import GeneratorSession
+        return GeneratorSession(self, x, lengths)
 
     def _state_of(self, out, rnn_state):
         """The estimator state of a Dense output block [B, ldo] and an LSTM state (a session rebuilds it from its static arrays)."""
@@ -547,8 +577,12 @@ class RnnEstimator(Generator):
         return buf
 
     # -- sampling -------------------------------------------------------------------------------
-    def generate(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=None):
+    def generate(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=None, lengths=None):
         """rnn_estimator.py:271-298: intro pass, then num_steps x {sample_single, single_step}.
+        lengths (common.prompt_lengths: B ints in 1..Ti on the host): ragged prompts -- row b continues x[b, :lengths[b]], its generated
+        step j being the step at absolute time lengths[b] + j; the row is, bit for bit, the one-row call on that slice with row0 + b, under
+        any given / temperature / max_notes / redraws / particles, and no cell of x behind a row's length is part of its arithmetic.  The
+        output, and given, stay row-relative.  None, or every entry Ti, is the call without it: the same kernels, bits and captured scan.
         particles (NADE estimators, with given; common.sampling_particles): importance resampling -- every partly given step runs C clamped
         scans and emits one, picked with probability proportional to the probability it gives the step's given cells: an approximate draw
         from p(free | this step's given cells, the past), exact as C grows; particle_ess() / particle_picks() report how approximate.  None,
@@ -576,6 +610,9 @@ class RnnEstimator(Generator):
             refuse_host_model(self.store.device, "generate(max_notes=)")
         if particles:
             refuse_host_model(self.store.device, "generate(particles=)")
+        lengths = prompt_lengths(lengths, x.shape[0], x.shape[1])
+        if lengths is not None:
+            self._refuse_prompt_lengths("generate(lengths=)")
         self._redraw_live = redraws > 0
         self._particle_live = None          # (with particles: set by ScanGraphs.generate to the arrays the scan writes)
 
@@ -583,7 +620,8 @@ class RnnEstimator(Generator):
             self._packed_step = -1
         return ScanGraphs.generate(self, (tuple(x.shape), x.dtype, int(num_steps), self.seed, self.row0), x, num_steps, given,
                                    temperature, self._generate_scan, stale, max_notes, redraws, particles,
-                                   stats_shape=(int(num_steps), self.num_tracks, x.shape[0]) if particles else None)
+                                   stats_shape=(int(num_steps), self.num_tracks, x.shape[0]) if particles else None,
+                                   **({} if lengths is None else dict(lengths=prompt_lengths_device(lengths, x.device))))
 
     def particle_ess(self):
         """The effective sample size (sum w)^2 / sum w^2 of every scan of the last generate call or session chunk that ran with particles:
@@ -601,21 +639,25 @@ class RnnEstimator(Generator):
         drawn again at least once, and how many of them fell back to the truncating scan (and carry its bias).  Ints; synchronises."""
         return redraw_counts(self)
 
-    def _generate_scan(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=0):
+    def _generate_scan(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=0, lengths=None):
+        """The scan of generate; lengths: normalised prompt lengths on the device (int32 [B]; a static input of a captured scan) or None."""
         self._materialize(x.shape[-1])
         self._rnn.build_cell(False)
         if redraws:
             redraw_cell(self, x.device).zero_()        # the call's statistics start at zero (in a captured scan: a fill node of the graph)
         with self._sampling_scope():
             if self.det_sampling:
-                whole = self._scan_in_one_call(x, num_steps, given, temperature, max_notes, redraws, particles)     # LSTM-(Multi)NADE on a byte piano-roll: mnn_generate_scan runs the whole scan
+                whole = self._scan_in_one_call(x, num_steps, given, temperature, max_notes, redraws, particles,     # LSTM-(Multi)NADE on a byte piano-roll: mnn_generate_scan runs the whole scan
+                                               **({} if lengths is None else dict(lengths=lengths)))
                 if whole is not None:
                     return whole
-                state = self.steps(x)
+                state = self.steps(x) if lengths is None else self._det_steps(x, None, lengths)
             else:
                 self._ensure_packed()
                 state = self._get_state(x, lengths=None, last_outputs=True)
-            return self._scan_steps(state, x[:, -1, :], num_steps, DrawAt(self.seed, self.row0, 0), given, temperature, max_notes, redraws, particles)[0]
+            # the first chain's start: the intro's last row -- with prompt lengths every row's own, gathered on the device
+            last_row = x[:, -1, :] if lengths is None else last_prompt_rows(x, lengths)
+            return self._scan_steps(state, last_row, num_steps, DrawAt(self.seed, self.row0, 0), given, temperature, max_notes, redraws, particles)[0]
 
     def _scan_steps(self, state, last_row, n, at0, given=None, temperature=1.0, max_notes=None, redraws=0, particles=0):
         """The step loop of a single generator (rnn_estimator.py:283-298): n x {sample_single, single_step} from `state` and the last emitted
@@ -1180,7 +1222,7 @@ class RnnNade(RnnEstimator):
     def _particles(self, particles, temperature, max_notes, given):
         return sampling_particles(particles, temperature, max_notes, given)
 
-    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=0):
+    def _scan_in_one_call(self, x, num_steps, given=None, temperature=1.0, max_notes=None, redraws=0, particles=0, lengths=None):
         """rnn_estimator.py:271-298 through ONE C-ABI call (mnn_generate_scan: intro pass + num_steps x {NADE sample, LSTM step, Dense} enqueued
         by the library's own host loop) when the inputs are the byte piano-roll itself; the same kernels and bits as the step-by-step path.
         given: the scan's codes u8 [B, num_steps, num_output] (generate)."""
@@ -1192,6 +1234,7 @@ class RnnNade(RnnEstimator):
             sir = dict(particles=particles, ess=ess, pick=pick)
         return ops.generate_scan(x.contiguous(), num_steps, temperature=temperature, seed=self.seed, row0=self.row0, given=given, max_notes=max_notes,
                                  **sir, redraws=redraws, redraw_stats=redraw_cell(self, x.device) if redraws else None,
+                                 **({} if lengths is None else dict(lengths=lengths)),
                                  state0=self._state0(x.shape[0], torch.float32), **self._scan_layers())      # (learn_zero_state: tiled on the device here, an input array of the scan)
 
     def _state_of(self, out, rnn_state):

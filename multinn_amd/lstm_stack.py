@@ -679,19 +679,21 @@ class LstmStack:
         return dict(x=x, n_x=n_x, x2=x2, h_prev=None if st is None else st[1], c_prev=None if st is None else st[0],
                     W=self.store[f"{pre}/cell_{l}/kernel"], Wp=self._det_pack[l], bias=self.store[f"{pre}/cell_{l}/bias"], c_out=c, h_out=h)
 
-    def det_step(self, x, state, x2=None):
+    def det_step(self, x, state, x2=None, lengths=None, t=0):
         """One deterministic f32 step of the stack: x u8 | f32 [B, n_x] (unit inner stride), optional x2 f32 [B, n_x2] concatenated behind
-        it; state [(c, h)...] f32 or None (zero state) -> (h_top f32 [B, u_last], new_state)."""
-        return det_steps([self], [x], [state], [x2])[0]
+        it; state [(c, h)...] f32 or None (zero state) -> (h_top f32 [B, u_last], new_state).  lengths (int32 [B] on the device), t: step t
+        of ragged prompts -- a row with t >= lengths[row] keeps its state (ops.lstm_step_det)."""
+        return det_steps([self], [x], [state], [x2], lengths=lengths, t=t)[0]
 
 
 def _det_f32(t):
     return t if t is None or t.dtype == torch.float32 else t.float()
 
 
-def det_steps(stacks, xs, states, x2s=None):
+def det_steps(stacks, xs, states, x2s=None, lengths=None, t=0):
     """One deterministic step of several LSTM stacks of equal depth (the M per-track generators of a feedback-scan step): layer by layer,
-    the stacks' jobs of a layer run as ONE launch.  Returns [(h_top, new_state)] per stack."""
+    the stacks' jobs of a layer run as ONE launch.  Returns [(h_top, new_state)] per stack.  lengths, t (optional): step t of ragged
+    prompts, for every layer's launch (ops.lstm_step_det)."""
     n = len(stacks)
     x2s = x2s if x2s is not None else [None] * n
     L = len(stacks[0].rnn.num_units)
@@ -707,7 +709,10 @@ def det_steps(stacks, xs, states, x2s=None):
             st = None if states[i] is None else (_det_f32(states[i][l][0]).contiguous(), _det_f32(states[i][l][1]).contiguous())
             n_x = s.rnn.layer_inputs()[l] - (inp2[i].shape[1] if inp2[i] is not None else 0)
             jobs.append(s.det_job(l, x, n_x, inp2[i], st))
-        ops.lstm_step_det(jobs)
+        if lengths is None:
+            ops.lstm_step_det(jobs)
+        else:
+            ops.lstm_step_det(jobs, lengths=lengths, t=t)
         for i, j in enumerate(jobs):
             new[i].append((j["c_out"], j["h_out"]))
             inp[i], inp2[i] = j["h_out"], None

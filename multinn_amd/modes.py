@@ -26,7 +26,7 @@ import weakref
 
 import torch
 
-from .common import Model, capture_train_step, given_codes, given_tracks, refuse_particles, sampling_max_notes, sampling_particles, sampling_redraws, sampling_temperature
+from .common import Model, capture_train_step, given_codes, given_tracks, prompt_lengths, refuse_particles, sampling_max_notes, sampling_particles, sampling_redraws, sampling_temperature
 from .encoders import PassEncoder, DBNEncoder
 from .generators import RnnNade, RnnRBM, RnnMultiNADE, RnnMultiRBM
 from . import ops
@@ -229,9 +229,9 @@ class MultINNCore(Model):
     metrics_upd = property(lambda self: (self._ensure_global_metrics(), self._metrics_upd)[1])
 
     # -- sampling -------------------------------------------------------------------------------
-    def sampler(self, num_beats, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0, particles=None):
+    def sampler(self, num_beats, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0, particles=None, intro_lengths=None):
         """multinn_core.py:324-341: number of model time steps in `num_beats` beats, then generate() (given / given_mask / temperature /
-        max_notes / redraws / particles: see generate)."""
+        max_notes / redraws / particles / intro_lengths: see generate)."""
         d = self._config["data"]
         pitch_span = d["pitch_range"]["highest"] - d["pitch_range"]["lowest"]
         num_steps = num_beats * d["beat_resolution"] * pitch_span // self._num_dims
@@ -242,6 +242,8 @@ class MultINNCore(Model):
             kw["redraws"] = redraws
         if particles is not None:
             kw["particles"] = particles
+        if intro_lengths is not None:
+            kw["intro_lengths"] = intro_lengths
         if given is None and given_mask is None:
             return self.generate(num_steps, **kw)
         return self.generate(num_steps, given=given, given_mask=given_mask, **kw)
@@ -252,6 +254,37 @@ class MultINNCore(Model):
         jamming and composer modes with Pass encoders; MnnUnsupported otherwise, before any device work."""
         from .session import ModeSession
         return ModeSession(self)
+
+    def ragged_session(self, intro_lengths):
+        """session() on ragged prompts: generate's `intro_lengths` (ModeSession(model, intro_lengths))."""
+        from .session import ModeSession
+        return ModeSession(self, intro_lengths)
+
+    # Ragged prompts (generate(..., intro_lengths)): row b of the built x [B, T, P, M] is the prompt x[b, :intro_lengths[b]], and the row is
+    # continued from there -- bit for bit what the model built on that one row's slice generates with its generators' row0 moved on by b.
+    # Every generator's encoded intro has the zero step in front (multinn_joint.py:83-89), so a generator's own lengths are these plus one.
+    # None, or every entry T, is the call without it, down to the captured scan.
+    def _intro_lengths(self, intro_lengths, who="generate"):
+        """Normalised on the host (common.prompt_lengths) -> None, or the generators' lengths (a tuple).  MnnUnsupported, before any device
+        work: DBN encoders (as for sessions), a model on the host, generators on the throughput recurrences (MULTINN_DET_SAMPLING=0)."""
+        if intro_lengths is None:
+            return None
+        built = self._x is not None
+        lengths = prompt_lengths(intro_lengths, self._x.shape[0] if built else None, self._x.shape[1] if built else None, what="intro_lengths")
+        if lengths is None:
+            return None
+        self._refuse_intro_lengths(who)
+        if not built:
+            raise ValueError("intro_lengths are the prompt lengths of the built x: build the model first")
+        return tuple(v + 1 for v in lengths)
+
+    def _refuse_intro_lengths(self, who):
+        if self._encoder_type != "Pass":
+            raise MnnUnsupported(f"{who}(intro_lengths=) through DBN encoders is not implemented: use Pass encoders")
+        if self.device is not None and torch.device(self.device).type != "cuda":
+            raise MnnUnsupported(f"{who}(intro_lengths=) runs in the HIP sampling kernels: this model lives on {self.device}, not a ROCm device")
+        for g in self.generators:
+            g._refuse_prompt_lengths(f"{who}(intro_lengths=)")
 
     # Sampling temperature (generate(..., temperature)): one positive number, or one per track -- the drums hotter than the bass.  NADE
     # generators draw u < sigmoid(logit / T) and also take None (threshold decoding); RBM generators run the chain of exp(-E / T).  With
@@ -364,17 +397,20 @@ class MultINNCore(Model):
         max_notes = self._max_notes(max_notes)
         return temperature, self._given(num_steps, given, given_mask), max_notes
 
-    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0, particles=None):
+    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0, particles=None, intro_lengths=None):
         """-> u8 `[B, num_steps, P, M]` (multinn_joint.py:188-215, multinn_jamming.py:101-133, multinn_composer.py:114-151): every generator's
         scan on its encoded intro, decoded per track.  temperature: _temperature; max_notes: _max_notes; redraws: _redraws; given /
-        given_mask: conditional generation (_given); particles: importance resampling of the partly given steps (_particles).
+        given_mask: conditional generation (_given); particles: importance resampling of the partly given steps (_particles);
+        intro_lengths: ragged prompts (_intro_lengths), handed to every generator.
         What the modes differ in is in _generator_inputs, _generator_given and _decode_samples."""
         temperature, cond, max_notes = self._generate_arguments(num_steps, given, given_mask, temperature, max_notes)
         redraws = self._redraws(redraws, max_notes, temperature)
         particles = self._particles(particles, temperature, max_notes, cond)
+        lengths = self._intro_lengths(intro_lengths)
         if self._x_encoded is None:
             MultINNCore._build_all(self, "generate")
-        scans = [functools.partial(g.generate, x) for g, x in zip(self.generators, self._generator_inputs())]
+        ragged = {} if lengths is None else dict(lengths=lengths)
+        scans = [functools.partial(g.generate, x, **ragged) for g, x in zip(self.generators, self._generator_inputs())]
         return self._sample_generators(scans, num_steps, cond, temperature, max_notes=max_notes, redraws=redraws, particles=particles)
 
     def _sample_generators(self, scans, num_steps, cond, temperature, session=False, max_notes=None, redraws=0, particles=0):
@@ -1131,9 +1167,14 @@ class MultINNFeedback(MultINNJamming):
             if isinstance(g, RnnRBM) and some[i] and not whole[i]:
                 raise NotImplementedError(f"track {i}: in feedback mode an RBM generator takes whole given tracks only (no clamped chain in the feedback scan)")
 
-    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0, particles=None):
+    def _refuse_intro_lengths(self, who):
+        raise MnnUnsupported(f"{who}(intro_lengths=) is not supported in the {self._mode} mode: the intro pass of its sampling scan also carries the "
+                             "feedback module's state")
+
+    def generate(self, num_steps, given=None, given_mask=None, temperature=1.0, max_notes=None, redraws=0, particles=None, intro_lengths=None):
         """multinn_feedback.py:120-173 -> u8 `[B, num_steps, P, M]`: one joint scan over the M generators and the feedback module.
         particles > 1 with given: MnnUnsupported (the scan's grouped multi-job sample launch has no particle form).
+        intro_lengths other than None / all T: MnnUnsupported (the intro pass also carries the feedback module's state).
         redraws (MultINNCore._redraws): the cap by rejection, inside the scan.
         temperature (MultINNCore._temperature): generator m samples at its own inside the scan.  max_notes (MultINNCore._max_notes):
         generator m caps its own track.
@@ -1144,6 +1185,7 @@ class MultINNFeedback(MultINNJamming):
         sampling_particles(particles)
         if cond is not None:
             refuse_particles(particles, f"the {self._mode} mode")
+        self._intro_lengths(intro_lengths)
         cap = {} if max_notes is None else (dict(max_notes=max_notes, redraws=redraws) if redraws else dict(max_notes=max_notes))
         if self._x_encoded is None:
             self._inputs = self._build_inputs()

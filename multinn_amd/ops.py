@@ -1138,14 +1138,15 @@ def rbm_gibbs_multi(jobs, k, row0=0, row_ids=None, sub0=0, seed_step=None, tempe
     _req(es >= 1 and (N == 1 or rs >= (D - 1) * es + 1), "gibbs_multi: v0 needs a positive column stride and rows that do not overlap")
     has_given = jobs[0].get("given") is not None
     rs_g = jobs[0]["given"].stride(0) if has_given else 0
+    same_strides = lambda t: t.stride(1) == es and (N == 1 or t.stride(0) == rs)      # (one row: its stride is never multiplied by a row index)
     _req(not (has_given and seed_step is not None), "gibbs_multi: given with seed_step (the stepped chain is training's, unconditioned)")
     for j in jobs:
         v, W = j["v0"], j["W"]
-        _req(torch.is_tensor(v) and v.dtype == torch.uint8 and tuple(v.shape) == (N, D) and v.stride() == (rs, es) and v.device == v0.device,
+        _req(torch.is_tensor(v) and v.dtype == torch.uint8 and tuple(v.shape) == (N, D) and same_strides(v) and v.device == v0.device,
              "gibbs_multi: v0 u8 [N, D] views of equal shape and strides")
         _req(torch.is_tensor(W) and W.dtype == torch.float32 and tuple(W.shape) == (D, Hn) and W.is_contiguous(), "gibbs_multi: W f32 [D, Hn], one shape for every job")
         for t, dt, what in ((j.get("p_v"), torch.float32, "p_v f32"), (j.get("v_out"), torch.uint8, "v_out u8")):
-            _req(t is None or (t.dtype == dt and tuple(t.shape) == (N, D) and t.stride() == (rs, es)), f"gibbs_multi: {what} [N, D] with the strides of v0")
+            _req(t is None or (t.dtype == dt and tuple(t.shape) == (N, D) and same_strides(t)), f"gibbs_multi: {what} [N, D] with the strides of v0")
         g = j.get("given")
         _req((g is not None) == has_given, "gibbs_multi: given on every job or on none")
         _req(g is None or (g.dtype == torch.uint8 and tuple(g.shape) == (N, D) and g.stride(1) == es and g.stride(0) == rs_g
@@ -1346,9 +1347,18 @@ def log_loss_rows(targets, probs, out):
 
 # ------------------------------------------------------------------------------------------------
 # deterministic f32 single steps of the sampling scan (csrc/det_step.hip)
-def lstm_step_det(jobs):
+def _prompt_lengths_dev(lengths, B, device, what):
+    """A launch's ragged-prompt lengths: int32 [B], contiguous, on `device` (common.prompt_lengths checks the values, on the host)."""
+    _req(torch.is_tensor(lengths) and lengths.dtype == torch.int32 and tuple(lengths.shape) == (B,) and lengths.is_contiguous() and lengths.device == device,
+         f"{what}: lengths int32 [B], contiguous, on the device of the call")
+    return _ptr(lengths)
+
+
+def lstm_step_det(jobs, lengths=None, t=0):
     """One LSTMBlockCell step per job, ALL jobs in one launch.  job = dict(x=[B, >= n_x] u8 | f32 (or None), n_x, x2=f32 [B, n_x2] or None,
-    h_prev / c_prev f32 [B, u] or None (zero state), W f32 [(n_x + n_x2 + u), 4u] (TF layout), bias f32 [4u], c_out / h_out f32 [B, u])."""
+    h_prev / c_prev f32 [B, u] or None (zero state), W f32 [(n_x + n_x2 + u), 4u] (TF layout), bias f32 [4u], c_out / h_out f32 [B, u]).
+    lengths (int32 [B] on the device), t (mnn_lstm_step_det_ragged): step t of ragged prompts -- a row with t >= lengths[row] is frozen,
+    its c_out / h_out copies of c_prev / h_prev (zeros without them), every other row the step without the argument, bit for bit."""
     _req(1 <= len(jobs) <= 8, "lstm_step_det: 1..8 jobs")
     arr = (_lib.DetLstmJob * len(jobs))()
     B = jobs[0]["c_out"].shape[0]
@@ -1361,8 +1371,8 @@ def lstm_step_det(jobs):
         _req(W.dtype == torch.float32 and W.is_contiguous() and tuple(W.shape) == (n_x + n_x2 + u, 4 * u), f"lstm_step_det: W {tuple(W.shape)} != ({n_x + n_x2 + u}, {4 * u})")
         _req(b.dtype == torch.float32 and b.is_contiguous() and b.numel() == 4 * u, "lstm_step_det: bias f32 [4u]")
         for k in ("c_out", "h_out", "h_prev", "c_prev"):
-            t = j.get(k)
-            _req(t is None or (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, u)), f"lstm_step_det: {k} must be contiguous f32 [B, u]")
+            st = j.get(k)
+            _req(st is None or (st.dtype == torch.float32 and st.is_contiguous() and tuple(st.shape) == (B, u)), f"lstm_step_det: {k} must be contiguous f32 [B, u]")
         if x is not None:         # any 2-D view: element (row, k) at row * stride(0) + k * stride(1) (one track of a [B, P, M] step has stride(1) = M)
             _req(x.dim() == 2 and x.stride(1) >= 1 and x.shape[0] == B and x.shape[1] >= n_x and x.dtype in (torch.uint8, torch.float32),
                  "lstm_step_det: x is a u8 / f32 [B, >= n_x] view")
@@ -1378,7 +1388,10 @@ def lstm_step_det(jobs):
         _req(Wp is None or (Wp.dtype == torch.float32 and Wp.is_contiguous() and Wp.numel() * 4 == det_lstm_pack_bytes(n_x + n_x2 + u, u) and Wp.data_ptr() % 16 == 0),
              "lstm_step_det: Wp is det_lstm_pack(W, units)")
         a.Wp = _ptr(Wp)
-    call("mnn_lstm_step_det", _stream(), B, len(jobs), arr)
+    if lengths is None:
+        return call("mnn_lstm_step_det", _stream(), B, len(jobs), arr)
+    _req(isinstance(t, int) and not isinstance(t, bool) and t >= 0, "lstm_step_det: t is a step number")
+    call("mnn_lstm_step_det_ragged", _stream(), B, len(jobs), arr, _prompt_lengths_dev(lengths, B, jobs[0]["c_out"].device, "lstm_step_det"), t)
 
 
 def det_lstm_pack_bytes(K, units):
@@ -1481,10 +1494,12 @@ def _scan_call(what, ref, intro, Ti, num_steps, layers, dense_W, dense_bias, tra
 
 
 def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, given=None, state0=None,
-                  by_visible=False, max_notes=None, redraws=0, redraw_stats=None, particles=0, ess=None, pick=None):
+                  by_visible=False, max_notes=None, redraws=0, redraw_stats=None, particles=0, ess=None, pick=None, lengths=None):
     """mnn_generate_scan: the whole sampling scan of an LSTM-(Multi)NADE generator in one call.  intro u8 [B, Ti, tracks * D]; layers = [(W, bias)]
     f32 master weights; returns samples u8 [B, num_steps, tracks * D].  given (optional): codes u8 [B, num_steps, tracks * D] in the layout of
-    the samples (see nade_sample).  temperature: a float, None, or a sequence (per track, or by visible index: nade_sample).  state0 (optional, mnn_generate_scan_state): [(c0, h0) f32 [B, u]] per layer, the state the intro pass starts from."""
+    the samples (see nade_sample).  temperature: a float, None, or a sequence (per track, or by visible index: nade_sample).  state0 (optional, mnn_generate_scan_state): [(c0, h0) f32 [B, u]] per layer, the state the intro pass starts from.
+    lengths (optional, mnn_generate_scan_ragged): int32 [B] on the device, row b's prompt being intro[b, :lengths[b]]; without it every
+    call below is the entry point it was."""
     _req(intro.dtype == torch.uint8 and intro.dim() == 3 and intro.is_contiguous() and intro.shape[2] == tracks * D, "generate_scan: intro u8 [B, Ti, tracks * D]")
     arr, launch = _scan_call("generate_scan", intro, intro, intro.shape[1], int(num_steps), layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec,
                              seed, row0, given)
@@ -1492,6 +1507,14 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
     cp, hp = _scan_state("generate_scan: state0", state0, arr, intro.shape[0], intro.device)
     cc = _caps(max_notes, tracks, by_visible, "generate_scan")
     rd = _redraw(redraws, redraw_stats, cc, temperature, intro, "generate_scan")
+    if lengths is not None:         # ragged prompts: the one entry point that takes them, with everything else a call can carry
+        lp = _prompt_lengths_dev(lengths, intro.shape[0], intro.device, "generate_scan")
+        sr = None
+        if particles and particles > 1 and given is not None:
+            _req(cc is None and temperature is not None, "generate_scan: particles go with a temperature and without max_notes")
+            sr, ws = _sir("generate_scan", particles, ess, pick, (int(num_steps), tracks, intro.shape[0]), tracks, intro.shape[0], D, intro)
+        return launch("mnn_generate_scan_ragged", (C.byref(_temps_table(temperature, tracks, by_visible, "generate_scan")), None if cc is None else C.byref(cc)),
+                      cp, hp, None if rd is None else C.byref(rd), None if sr is None else C.byref(sr), lp)
     if particles and particles > 1 and given is not None:      # importance resampling (nade_sample_sir): ess / pick [num_steps, tracks, B] are written
         _req(cc is None and temperature is not None, "generate_scan: particles go with a temperature and without max_notes")
         sr, ws = _sir("generate_scan", particles, ess, pick, (int(num_steps), tracks, intro.shape[0]), tracks, intro.shape[0], D, intro)
@@ -1509,12 +1532,13 @@ def generate_scan(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, 
 
 def generate_scan_chunk(intro, num_steps, layers, dense_W, dense_bias, tracks, D, Hn, w_enc, w_dec, temperature, seed, row0, state_in, state_out,
                         given=None, step0=0, step_base=None, by_visible=False, max_notes=None, redraws=0, redraw_stats=None, particles=0, ess=None,
-                        pick=None):
+                        pick=None, lengths=None):
     """mnn_generate_scan_chunk: one chunk of a generation session of an LSTM-(Multi)NADE generator.  intro u8 [B, Ti, tracks * D] or None (the
     chunk continues from state_in); num_steps >= 0 (0 with an intro: the intro pass alone -> None); state_in: [(c, h) f32 [B, u]] per layer or
     None (the zero state); state_out: likewise, written with the state behind the last step (may be the arrays of state_in).  Step st draws
     with the sub-counter step0 + *step_base + st (step_base: one int32 on the device, or None).  Returns samples u8 [B, num_steps, tracks * D];
-    given (optional): the chunk's codes in that layout.  Everything else is generate_scan."""
+    given (optional): the chunk's codes in that layout.  lengths (optional, with an intro; mnn_generate_scan_chunk_ragged): the prompt
+    lengths, int32 [B] on the device.  Everything else is generate_scan."""
     ref = intro if intro is not None else state_in[0][0]
     num_steps, Ti = int(num_steps), 0 if intro is None else intro.shape[1]
     _req(intro is None or (intro.dtype == torch.uint8 and intro.dim() == 3 and intro.is_contiguous() and intro.shape[2] == tracks * D and Ti > 0),
@@ -1527,6 +1551,16 @@ def generate_scan_chunk(intro, num_steps, layers, dense_W, dense_bias, tracks, D
     tt = _temps_table(temperature, tracks, by_visible, "generate_scan_chunk")
     cc = _caps(max_notes, tracks, by_visible, "generate_scan_chunk")
     rd = _redraw(redraws, redraw_stats, cc, temperature, ref, "generate_scan_chunk")
+    if lengths is not None:         # ragged prompts: generate_scan's
+        _req(Ti > 0, "generate_scan_chunk: lengths go with an intro")
+        lp = _prompt_lengths_dev(lengths, ref.shape[0], ref.device, "generate_scan_chunk")
+        sr = None
+        if particles and particles > 1 and given is not None and num_steps > 0:
+            _req(cc is None and temperature is not None, "generate_scan_chunk: particles go with a temperature and without max_notes")
+            sr, ws = _sir("generate_scan_chunk", particles, ess, pick, (num_steps, tracks, ref.shape[0]), tracks, ref.shape[0], D, ref)
+        samples = launch("mnn_generate_scan_chunk_ragged", (C.byref(tt), None if cc is None else C.byref(cc)), ci, hi, co, ho, int(step0),
+                         _sub_base(step_base, ref, "generate_scan_chunk"), None if rd is None else C.byref(rd), None if sr is None else C.byref(sr), lp)
+        return samples if num_steps > 0 else None
     if particles and particles > 1 and given is not None and num_steps > 0:      # importance resampling: generate_scan's
         _req(cc is None and temperature is not None, "generate_scan_chunk: particles go with a temperature and without max_notes")
         sr, ws = _sir("generate_scan_chunk", particles, ess, pick, (num_steps, tracks, ref.shape[0]), tracks, ref.shape[0], D, ref)

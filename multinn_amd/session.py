@@ -21,7 +21,7 @@ import torch
 
 from . import ops
 from ._lib import MnnUnsupported
-from .common import DrawAt, ScanGraphs, _warm_up, check_given, graph_capture, max_notes_key, new_particle_cells, particle_cells, particles_key, redraw_cell, redraws_key, sampling_particles, sampling_redraws, temperature_key
+from .common import DrawAt, ScanGraphs, _warm_up, check_given, graph_capture, last_prompt_rows, max_notes_key, new_particle_cells, particle_cells, particles_key, prompt_lengths, prompt_lengths_device, redraw_cell, redraws_key, sampling_particles, sampling_redraws, temperature_key
 
 __all__ = ["GeneratorSession", "ModeSession"]
 
@@ -48,6 +48,8 @@ def _chunk_arguments(gen, batch, steps, num_steps, given=None, temperature=1.0):
 
 class GeneratorSession:
     """gen.session(x): the intro pass on x [B, Ti, Din] (from the learned state with learn_zero_state), then generate() chunk by chunk.
+    gen.ragged_session(x, lengths) = GeneratorSession(gen, x, lengths): generate's prompt lengths -- the intro pass stops every row at its own length and the first chain starts from
+    the row's own last prompt row; the chunks are those of any session.
 
     State (static device arrays, their addresses baked into the session's captured chunks): per LSTM layer (c, h); where the chunk is the
     generator's step loop also the last Dense output block and the last emitted row; the step cell.  A byte piano-roll into an LSTM-(Multi)NADE
@@ -59,10 +61,13 @@ class GeneratorSession:
     RnnMultiRBM._det_bias inside _sampling_scope, the packed weight copies, the step staging buffer -- so two scans of ONE generator must
     not run from two threads at once."""
 
-    def __init__(self, gen, x):
+    def __init__(self, gen, x, lengths=None):
         from .generators import refuse_host_model
         if not torch.is_tensor(x) or x.dim() != 3 or x.shape[0] < 1 or x.shape[1] < 1:
             raise ValueError(f"x must be a tensor [B, Ti, Din] with at least one intro step, got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+        lengths = prompt_lengths(lengths, x.shape[0], x.shape[1])
+        if lengths is not None:
+            gen._refuse_prompt_lengths("ragged_session")
         refuse_host_model(gen.store.device, "a generation session")
         refuse_host_model(x.device, "a generation session")
         self._gen, self.seed, self.row0 = gen, gen.seed, gen.row0
@@ -76,23 +81,27 @@ class GeneratorSession:
         gen._rnn.build_cell(False)
         dev = x.device
         self._cell = torch.zeros(1, dtype=torch.int32, device=dev)            # the step cell: `steps` as 32 bits, filled before every replay
+        ldev = None if lengths is None else prompt_lengths_device(lengths, dev)
         self._scan = gen.det_sampling and x.dtype == torch.uint8 and gen._scan_layers() is not None and x.shape[-1] == gen.num_tracks * gen.num_dims
         if self._scan:
             B = self.batch
             self._rnn = [(torch.zeros((B, u), device=dev), torch.zeros((B, u), device=dev)) for u in gen._rnn.num_units]
             self._out = self._last = None
             ops.generate_scan_chunk(x.contiguous(), 0, temperature=1.0, seed=self.seed, row0=self.row0, state_in=gen._state0(B, torch.float32),
-                                    state_out=self._rnn, **gen._scan_layers())
+                                    state_out=self._rnn, **({} if ldev is None else dict(lengths=ldev)), **gen._scan_layers())
             return
         with gen._sampling_scope():
-            if gen.det_sampling:
+            if ldev is not None:
+                state = gen._det_steps(x, None, ldev)
+            elif gen.det_sampling:
                 state = gen.steps(x)
             else:
                 gen._ensure_packed()
                 state = gen._get_state(x, lengths=None, last_outputs=True)
         self._rnn = [(c.clone(), h.clone()) for c, h in state.rnn_state]
         self._out = state.dense.clone()
-        self._last = x[:, -1, :gen._num_output].to(torch.uint8).contiguous().clone()         # the first chain's start (rnn_estimator.py:283: the intro's last row)
+        last = x[:, -1] if ldev is None else last_prompt_rows(x, ldev)                      # the first chain's start (rnn_estimator.py:283: the intro's last row; with prompt lengths every row's own)
+        self._last = last[:, :gen._num_output].to(torch.uint8).contiguous().clone()
 
     # -- state ----------------------------------------------------------------------------------
     def _tensors(self):
@@ -242,7 +251,7 @@ class ModeSession:
     through its generator's clamped scan for that chunk (the output equals the given notes), so its state and counters advance and a later
     chunk can free it."""
 
-    def __init__(self, model):
+    def __init__(self, model, intro_lengths=None):
         from .generators import refuse_host_model
         from .modes import MultINNCore
         mode = model._mode
@@ -252,6 +261,7 @@ class ModeSession:
         if model._encoder_type != "Pass":
             raise MnnUnsupported("generation sessions through DBN encoders are not implemented: use Pass encoders")
         refuse_host_model(model.device, "a generation session")
+        lengths = model._intro_lengths(intro_lengths, "ragged_session")
         self._model = model
         self.steps = 0
         self._max_notes = None
@@ -259,7 +269,7 @@ class ModeSession:
         self._particles = 0
         if model._x_encoded is None:
             MultINNCore._build_all(model, "generate")
-        self._subs = [g.session(x) for g, x in zip(model.generators, model._generator_inputs())]
+        self._subs = [g.session(x) if lengths is None else g.ragged_session(x, lengths) for g, x in zip(model.generators, model._generator_inputs())]
 
     def snapshot(self):
         return self.steps, [s.snapshot() for s in self._subs]
