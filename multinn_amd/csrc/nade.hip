@@ -10,7 +10,7 @@
 // Sampling (one wave/row):   deterministic summation order + IEEE-only sigmoid so Bernoulli draws are
 //                            bit-identical to oracle/det_ref.c.
 #include "common.h"
-#include "nade_scan.h"       // NADE_EPS, the DPP xor steps, wave_xor_sum and the draw of the sampling contract (shared with nade_is.hip)
+#include "nade_scan.h"       // NADE_EPS, the DPP xor steps, wave_xor_sum and the draw of the sampling contract, SampleTemps (shared with nade_particle.h)
 
 #define LN2 0.6931471805599453f
 
@@ -757,18 +757,8 @@ struct SampleJob {
 };
 #define SAMPLE_MAX_JOBS 8
 struct SampleJobs { SampleJob job[SAMPLE_MAX_JOBS]; };
-// The temperatures of a launch (TMODE 2 only; the other modes never read it).  by_visible == 0: job j (blockIdx.y) draws at t[j] -- the launcher
-// fills all eight entries, a scalar eight times; by_visible == 1: visible i of every job draws at t[i % n] (the joint NADE orders its visibles
-// p M + m: one temperature per track).
-struct SampleTemps { float t[SAMPLE_MAX_JOBS]; int n; int by_visible; };
-// the table parked in LDS (eight floats at `stt`): every lane selects its entry with constant indices -- the by-value argument stays in scalar
-// registers -- and the scan then reads the entry of a running index, a broadcast (kernel below) or per-lane (chunk kernel) LDS read
-__device__ __forceinline__ void sample_temps_park(const SampleTemps& TT, int lane, float* stt) {
-    float tv = TT.t[0];
-#pragma unroll
-    for (int k = 1; k < SAMPLE_MAX_JOBS; ++k) tv = (lane & (SAMPLE_MAX_JOBS - 1)) == k ? TT.t[k] : tv;
-    if (lane < SAMPLE_MAX_JOBS) stt[lane] = tv;
-}
+// the temperatures of a launch (SampleTemps, sample_temps_park): nade_scan.h -- one entry per job of a launch
+static_assert(SAMPLE_MAX_JOBS == MNN_TEMPS_MAX, "SampleTemps holds one temperature per job of a launch");
 // The polyphony caps of a launch (the CAP instantiations' LAST kernel argument: the other arguments stay where they were).  cap[k]: how many
 // ones counter k may still emit, SAMPLE_CAP_NONE for no cap.  by_visible == 0: job j (blockIdx.y) counts in cap[j];
 // by_visible == 1: visible i of every job counts in cap[i % n] (the joint NADE: one cap per track).

@@ -1,10 +1,23 @@
-// Device helpers of the NADE visible-order scans that more than one translation unit uses (nade.hip: log_prob, sampling; nade_is.hip: the
-// importance estimator's clamped scans).  The arithmetic of the sampling contract lives here, so every scan that states "the dot product and
-// the draw of nade_sample_kernel" runs the same instructions.
+// Device helpers of the NADE visible-order scans that more than one translation unit uses (nade.hip: log_prob, sampling; nade_particle.h: the
+// clamped particle scan of nade_is.hip and nade_sir.hip).  The arithmetic of the sampling contract lives here, so every scan that states "the
+// dot product and the draw of nade_sample_kernel" runs the same instructions.
 #pragma once
 #include "common.h"
 
 #define NADE_EPS 1e-6f
+
+// The temperatures of a launch (nade.hip: TMODE 2 only, the other modes never read it; nade_sir.hip: the TEMP instantiations).  by_visible == 0:
+// job / track j (blockIdx.y) draws at t[j] -- the launcher fills all eight entries, a scalar eight times; by_visible == 1: visible i of every
+// job draws at t[i % n] (the joint NADE orders its visibles p M + m: one temperature per track).
+struct SampleTemps { float t[MNN_TEMPS_MAX]; int n; int by_visible; };
+// the table parked in LDS (eight floats at `stt`): every lane selects its entry with constant indices -- the by-value argument stays in scalar
+// registers -- and the scan then reads the entry of a running index, a broadcast (visible-at-a-time scans) or per-lane (chunk kernel) LDS read
+__device__ __forceinline__ void sample_temps_park(const SampleTemps& TT, int lane, float* stt) {
+    float tv = TT.t[0];
+#pragma unroll
+    for (int k = 1; k < MNN_TEMPS_MAX; ++k) tv = (lane & (MNN_TEMPS_MAX - 1)) == k ? TT.t[k] : tv;
+    if (lane < MNN_TEMPS_MAX) stt[lane] = tv;
+}
 
 __device__ __forceinline__ float dpp_xor8(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, false)); }
 // x[l ^ 4] without the LDS crossbar (a ds_swizzle is ~100 cycles on a dependent chain): two row shifts by four lanes, each written to the

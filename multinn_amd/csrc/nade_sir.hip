@@ -21,19 +21,16 @@
 //   OUTPUTS: the picked particle's vector through the sample strides of mnn_nade_sample, nll = the model's own NLL of it (untempered, summed in
 //     visible order like nade_sample_kernel's), ess and pick per scan [tracks, N].
 //
-// Shape of the work, as nade_is_kernel: one wave per particle (a lane owns four hidden units), the four waves of a workgroup take particles of
-// the SAME scan -- its b_dec, codes and temperatures are staged in LDS once, b_enc and h(b_enc) stay in registers across a wave's particles --
-// and a workgroup strides over the scan's particle groups.  A particle's logits and draws are parked in LDS; behind the scan its vector leaves
-// for the workspace, the log terms are formed 64 at a time, the given cells' summed as above and all cells' in visible order.
+// Shape of the work, as nade_is_kernel: one wave per particle, the four waves of a workgroup take particles of the SAME scan -- its b_dec,
+// codes and temperatures are staged in LDS once -- and a workgroup strides over the scan's particle groups.  The particle's scan and the given
+// cells' weight pass are nade_particle.h's; behind them the particle's vector leaves for the workspace and all cells' log terms (the model's
+// own) are formed 64 at a time and summed in visible order.
 // Between the two launches a scan's particles live in the workspace: log w f32 [tracks, N, C] | nll f32 [tracks, N, C] | short-cut flag u8
 // [tracks, N] | vectors u8 [tracks, N, C, D] (mnn_nade_sample_sir_workspace_bytes).  The second launch, one wave per scan, picks and copies.
 #include "common.h"
-#include "nade_scan.h"
+#include "nade_particle.h"
 
-#define SIR_FREE 255
 #define SIR_MAX_C 1024
-
-struct SirTemps { float t[MNN_TEMPS_MAX]; int n; int by_visible; };      // by_visible == 0: track m draws at t[m] (a scalar: eight times)
 
 struct SirArgs {
     int tracks, N, D, Hn, C, G;                              // G: workgroups per scan
@@ -42,41 +39,28 @@ struct SirArgs {
     const uint8_t* given; long s_track_stride; long s_row_stride; int s_elem_stride;      // the codes, with the strides of the samples
     uint64_t seed; uint32_t row0, sub; const uint32_t* sub_base;
     uint32_t eq;                                             // Philox blocks per particle on MNN_STREAM_NADE_SIR: E4 / 4
-    SirTemps TT;
+    SampleTemps TT;                                          // by_visible == 0: track m draws at t[m] (a scalar: eight times)
     float* log_w; float* nll_c; uint8_t* flag; uint8_t* v;   // the workspace (log_w: or the caller's)
 };
 
-static size_t sir_lds_bytes(int D) { return (size_t)25 * ((D + 15) & ~15) + 4096 + 64; }      // <= 42560 (D <= 1536)
-
-// the table parked in LDS: every lane selects its entry with constant indices (the by-value argument stays in scalar registers)
-__device__ __forceinline__ void sir_temps_park(const SirTemps& TT, int t, float* stt) {
-    float tv = TT.t[0];
-#pragma unroll
-    for (int k = 1; k < MNN_TEMPS_MAX; ++k) tv = (t & (MNN_TEMPS_MAX - 1)) == k ? TT.t[k] : tv;
-    if (t < MNN_TEMPS_MAX) stt[t] = tv;
-}
+static size_t sir_lds_bytes(int D) { return 64 + (size_t)5 * nade_dq(D) + 4 * nade_wave_lds_bytes(D); }      // <= 42560 (D <= 1536)
 
 // FULL: Hn == 256, no lane is idle.  TEMP: some temperature of the launch is not 1 (the table; without it the scan is nade_is_kernel's)
 template <bool FULL, bool TEMP>
 __global__ void __launch_bounds__(256) nade_sir_kernel(SirArgs A) {
-    // workgroup: temperatures [8] f32 (+ pad to 64 B) | b_dec [Dq] f32 | codes [Dq] u8; then per wave: logits / log terms [Dq] f32 | 256 uniforms |
-    // draws [Dq] u8.  Dq = D rounded up to 16: every carve offset is a multiple of 16 bytes.
+    // workgroup: temperatures [8] f32 (+ pad to 64 B) | b_dec [Dq] f32 | codes [Dq] u8; then the four waves' parts (NadeWaveLds; the logits
+    // make room for the log terms)
     extern __shared__ __attribute__((aligned(16))) unsigned char nade_sir_smem[];
     const int D = A.D, Hn = A.Hn, C = A.C;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int n = blockIdx.x / A.G, slot = blockIdx.x - n * A.G;       // n < N by the grid
     const int m = blockIdx.y;
-    const int Dq = (D + 15) & ~15;
+    const int Dq = nade_dq(D);
     float* stt = reinterpret_cast<float*>(nade_sir_smem);
     float* sbd = reinterpret_cast<float*>(nade_sir_smem + 64);
     unsigned char* sg = nade_sir_smem + 64 + (size_t)4 * Dq;
-    unsigned char* wbase = nade_sir_smem + 64 + (size_t)5 * Dq + (size_t)wv * ((size_t)5 * Dq + 1024);
-    float* sp = reinterpret_cast<float*>(wbase);
-    float* su = reinterpret_cast<float*>(wbase + (size_t)4 * Dq);
-    unsigned char* son = wbase + (size_t)4 * Dq + 1024;
+    const NadeWaveLds W = nade_wave_lds(nade_sir_smem + 64 + (size_t)5 * Dq, wv, D);
     const float* __restrict__ bias = A.bias + (size_t)n * A.ld_bias;
-    const float* __restrict__ we = A.w_enc + (size_t)m * D * Hn;
-    const float* __restrict__ wd = A.w_dec + (size_t)m * D * Hn;
     {   // the scan's b_dec, codes and temperatures: one pass of the workgroup, a broadcast read per visible afterwards
         const float* __restrict__ bd = bias + A.tracks * Hn + m * D;
         const uint8_t* __restrict__ gv = A.given + (size_t)m * A.s_track_stride + (size_t)n * A.s_row_stride;
@@ -84,149 +68,53 @@ __global__ void __launch_bounds__(256) nade_sir_kernel(SirArgs A) {
             sbd[i] = bd[i];
             sg[i] = gv[(size_t)i * A.s_elem_stride];
         }
-        if (TEMP) sir_temps_park(A.TT, (int)threadIdx.x, stt);
+        if (TEMP) sample_temps_park(A.TT, (int)threadIdx.x, stt);
     }
     __syncthreads();                                         // the only barrier: every wave reaches it, the particle loop below has none
     // the short cut: no given cell behind a free one (first free visible > last given visible), from the staged codes -- wave-uniform
     int last = -1, first = D;
-    for (int i = D - 1 - lane; i >= 0; i -= 64) first = sg[i] == SIR_FREE ? i : first;
-    for (int i = lane; i < D; i += 64) last = sg[i] != SIR_FREE ? i : last;
+    for (int i = D - 1 - lane; i >= 0; i -= 64) first = sg[i] == NADE_FREE ? i : first;
+    for (int i = lane; i < D; i += 64) last = sg[i] != NADE_FREE ? i : last;
     for (int o = 32; o > 0; o >>= 1) {
         last = max(last, __shfl_xor(last, o));
         first = min(first, __shfl_xor(first, o));
     }
     const bool shortcut = last < first;
-    float a0[4], h0[4];
-    bool in[4];
-    int off[4];                                              // hidden index of (lane, q), 0 where there is none: loads are never predicated
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        in[q] = FULL || lane + 64 * q < Hn;
-        off[q] = in[q] ? lane + 64 * q : 0;
-        const float av = bias[m * Hn + off[q]];
-        a0[q] = in[q] ? av : 0.f;
-        h0[q] = det_sigmoid(a0[q]);
-    }
+    const NadeLane L = nade_lane_setup<FULL>(bias, m * Hn, Hn, lane);
     const uint32_t rid = A.row0 + (uint32_t)n;
     uint32_t sub = A.sub;
     if (A.sub_base != nullptr) sub += *A.sub_base;           // one wave-uniform read, behind the loads above (nade_sample_kernel)
-    const uint32_t e0 = (uint32_t)m * (uint32_t)D;           // element index of visible 0 (RNG contract: elem = m D + i)
     // a per-track table has n == tracks <= MNN_TEMPS_MAX entries; a scalar fills all of them, and is entry 0 for the tracks past the table
-    const int tjob = A.TT.by_visible || m >= MNN_TEMPS_MAX ? 0 : m;
-    constexpr int RING = 8;                                  // visibles in flight, as nade_sample_kernel
+    const int tix = A.TT.by_visible || m >= MNN_TEMPS_MAX ? 0 : m;
+    const int tn = A.TT.by_visible ? A.TT.n : 0;
+    NadeParticle P;
+    P.D = D, P.Hn = Hn, P.Ds = D;
+    P.we = A.w_enc + (size_t)m * D * Hn, P.wd = A.w_dec + (size_t)m * D * Hn;
+    P.sbd = sbd, P.codes = sg, P.held = false;
+    P.seed = A.seed, P.row = rid, P.sub = sub;
+    P.e0 = (uint32_t)m * (uint32_t)D;
+    P.stt = stt, P.tix = tix, P.tn = tn;
     for (int c = slot * 4 + wv; c < C; c += 4 * A.G) {       // wave-uniform
         if (shortcut && c > 0) break;                        // equal weights: particle 0 is the scan's vector
-        const uint32_t stream = c == 0 ? MNN_STREAM_NADE : MNN_STREAM_NADE_SIR;
-        const uint32_t rblock = c == 0 ? 0u : (uint32_t)(c - 1) * A.eq;
-        float a[4], h[4];
-        // the hidden indices through an opaque zero: the addresses of the prologue's loads do not depend on the particle, and hoisted out of
-        // this loop they are held in registers across it (nade_is_kernel; profiles/nade_is.md)
-        int zero = 0;
-        asm volatile("" : "+v"(zero));
-        int offp[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            a[q] = a0[q];
-            h[q] = h0[q];
-            offp[q] = off[q] + zero;
-        }
-        float wdr[RING][4], wer[RING][4];                    // ring: the weight rows of visibles i .. i + RING - 1
-        auto fetch = [&](int k, int i) {
-            const int ii = min(i, D - 1);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                wdr[k][q] = wd[(size_t)ii * Hn + offp[q]];
-                wer[k][q] = we[(size_t)ii * Hn + offp[q]];
-            }
-        };
-#pragma unroll
-        for (int k = 0; k < RING; ++k) {
-            fetch(k, k);
-            __builtin_amdgcn_sched_barrier(0);               // issue order = ring order (the waits count loads)
-        }
-        uint32_t b0 = e0 >> 2;                               // lane l holds the uniforms of Philox block b0 + l
-        auto refill = [&]() {
-            float u4[4];
-            philox_uniform4(A.seed, stream, rid, sub, rblock + b0 + (uint32_t)lane, u4);
-            *reinterpret_cast<float4*>(su + 4 * lane) = make_float4(u4[0], u4[1], u4[2], u4[3]);
-        };
-        refill();
-        auto dot = [&](int k) {                              // sum_j h_j w_dec[visible of ring slot k][j], the contract's order
-            float acc = 0.f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc = fmaf(h[q], in[q] ? wdr[k][q] : 0.f, acc);
-            return wave_xor_sum(acc);
-        };
-        auto uniform_of = [&](int i) {                       // fetched one visible ahead, with the rare Philox refill
-            const uint32_t e = e0 + (uint32_t)min(i, D - 1);
-            if ((e >> 2) >= b0 + 64u) {
-                b0 += 64u;
-                refill();
-            }
-            return su[e - 4u * b0];
-        };
-        int tix = tjob;                                      // TEMP: the temperature of visible i is stt[tix]; tix = i % n carried along, or the track
-        float t_cur = TEMP ? stt[tix] : 1.0f;
-        float u_cur = uniform_of(0);
-        float acc = dot(0);
-        for (int i0 = 0; i0 < D; i0 += RING) {
-#pragma unroll
-            for (int k = 0; k < RING; ++k) {
-                const int i = i0 + k;
-                if (i < D) {                                 // uniform
-                    // speculation (Hn == 256): a 0 leaves the hidden state, so visible i + 1's dot product is this one
-                    const float spec = FULL ? dot((k + 1) % RING) : 0.f;
-                    const float l = sbd[i] + acc;
-                    const int code = __builtin_amdgcn_readfirstlane((int)sg[i]);     // the same byte in every lane: a uniform branch
-                    bool on;
-                    if (code != SIR_FREE) on = code != 0;    // held: moves a / h like a draw, its uniform is left unused
-                    else on = draw_below(u_cur, TEMP ? l / t_cur : l);
-                    if (on) {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            a[q] = a[q] + (in[q] ? wer[k][q] : 0.f);
-                            h[q] = det_sigmoid(a[q]);
-                        }
-                        acc = dot((k + 1) % RING);
-                    } else {
-                        acc = FULL ? spec : dot((k + 1) % RING);
-                    }
-                    sp[i] = l;                               // every lane holds the same logit and draw: one merged LDS write each
-                    son[i] = on ? 1 : 0;
-                    u_cur = uniform_of(i + 1);
-                    if (TEMP && A.TT.by_visible) {           // uniform; fetched one visible ahead like the uniform
-                        tix = tix + 1 == A.TT.n ? 0 : tix + 1;
-                        t_cur = stt[tix];
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                fetch(k, i + RING);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
+        P.stream = c == 0 ? MNN_STREAM_NADE : MNN_STREAM_NADE_SIR;
+        P.block0 = c == 0 ? 0u : (uint32_t)(c - 1) * A.eq;
+        nade_particle_scan<FULL, TEMP>(P, L, W, lane);
         // behind the scan: the vector out; the log terms 64 at a time -- the given cells' (at the scan's temperature) summed per lane in visible
-        // order and across the lanes by the butterfly, all cells' (the model's own) left in LDS for the sum in visible order
+        // order and across the lanes by the butterfly (the order of nade_given_log_weight, in this pass: no cell's term is formed twice), all
+        // cells' (the model's own) left in LDS for the sum in visible order
         const size_t pc = ((size_t)m * A.N + n) * C + c;
         float part = 0.f;
         for (int i = lane; i < D; i += 64) {
-            const float l = sp[i];
-            const bool on = son[i] != 0;
+            const float l = W.sp[i];
+            const bool on = W.son[i] != 0;
             A.v[pc * D + i] = on ? 1 : 0;
-            const float p = det_sigmoid(l);
-            const float term = on ? logf(NADE_EPS + p) : logf(NADE_EPS + (1.0f - p));
-            if (sg[i] != SIR_FREE) {
-                if (TEMP) {
-                    const float pt = det_sigmoid(l / stt[A.TT.by_visible ? i % A.TT.n : tjob]);
-                    part += on ? logf(NADE_EPS + pt) : logf(NADE_EPS + (1.0f - pt));
-                } else {
-                    part += term;
-                }
-            }
-            sp[i] = term;
+            const float term = nade_log_term(l, on);
+            if (sg[i] != NADE_FREE) part += TEMP ? nade_log_term(l / stt[tn != 0 ? i % tn : tix], on) : term;     // (tn != 0: tix == 0)
+            W.sp[i] = term;
         }
         const float lw = wave_xor_sum(part);
         float logp = 0.f;                                    // (LDS operations of one wave execute in order)
-        for (int i = 0; i < D; ++i) logp += sp[i];
+        for (int i = 0; i < D; ++i) logp += W.sp[i];
         if (lane == 0) {
             A.log_w[pc] = lw;
             A.nll_c[pc] = -logp;
@@ -306,12 +194,10 @@ __global__ void __launch_bounds__(256) nade_sir_const_kernel(long count, float C
     }
 }
 
-static size_t sir_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 extern "C" size_t mnn_nade_sample_sir_workspace_bytes(int tracks, int N, int D, int particles) {
     if (tracks <= 0 || N <= 0 || D <= 0 || particles <= 1) return 0;
     const size_t scans = (size_t)tracks * (size_t)N;
-    return 2 * sir_align(scans * (size_t)particles * sizeof(float)) + sir_align(scans) + sir_align(scans * (size_t)particles * (size_t)D);
+    return 2 * nade_align256(scans * (size_t)particles * sizeof(float)) + nade_align256(scans) + nade_align256(scans * (size_t)particles * (size_t)D);
 }
 
 extern "C" int mnn_nade_sample_sir_at(mnn_stream_t s, int tracks, int N, int D, int Hn, const float* bias, int ld_bias, const float* w_enc,
@@ -324,11 +210,9 @@ extern "C" int mnn_nade_sample_sir_at(mnn_stream_t s, int tracks, int N, int D, 
     const int C = sir->particles;
     MNN_REQUIRE(C <= SIR_MAX_C, "mnn_nade_sample_sir: particles=%d > %d", C, SIR_MAX_C);
     MNN_REQUIRE(temps != nullptr && temps->n > 0, "mnn_nade_sample_sir: particles need a temperature (threshold decoding draws nothing)");
-    MNN_REQUIRE(tracks > 0 && tracks <= 65535 && N > 0 && D > 0 && Hn > 0 && Hn <= 256,
-                "mnn_nade_sample_sir: need 0<tracks<=65535, N,D>0 and 0<Hn<=256 (tracks=%d N=%d D=%d Hn=%d)", tracks, N, D, Hn);
-    MNN_REQUIRE(D <= 1536, "mnn_nade_sample_sir: D <= 1536 (a scan's b_dec and codes and a particle's logits and draws are parked in LDS; D=%d)", D);
+    int G;                                                   // (the grid bound is checked here, ahead of the hand-off of a call without codes below)
+    if (const int rc = nade_particle_check("mnn_nade_sample_sir", "scan", tracks, N, D, Hn, ld_bias, C, &G)) return rc;
     MNN_REQUIRE(bias && w_enc && w_dec && samples && sir->ess && sir->pick, "mnn_nade_sample_sir: null pointer");
-    MNN_REQUIRE(ld_bias >= tracks * (Hn + D), "mnn_nade_sample_sir: ld_bias too small");
     MNN_REQUIRE(temps->n <= MNN_TEMPS_MAX && (temps->n == 1 || temps->by_visible != 0 || temps->n == tracks),
                 "mnn_nade_sample_sir: temps: 1..%d positive finite temperatures, per track one or `tracks` of them", MNN_TEMPS_MAX);
     for (int e = 0; e < temps->n; ++e)
@@ -351,13 +235,13 @@ extern "C" int mnn_nade_sample_sir_at(mnn_stream_t s, int tracks, int N, int D, 
     const size_t scans = (size_t)tracks * (size_t)N;
     char* wp = static_cast<char*>(sir->workspace);
     float* lw = log_w != nullptr ? log_w : reinterpret_cast<float*>(wp);
-    wp += sir_align(scans * C * sizeof(float));
+    wp += nade_align256(scans * C * sizeof(float));
     float* nll_c = reinterpret_cast<float*>(wp);
-    wp += sir_align(scans * C * sizeof(float));
+    wp += nade_align256(scans * C * sizeof(float));
     uint8_t* flag = reinterpret_cast<uint8_t*>(wp);
-    wp += sir_align(scans);
+    wp += nade_align256(scans);
     uint8_t* v = reinterpret_cast<uint8_t*>(wp);
-    SirTemps TT;
+    SampleTemps TT;
     memset(&TT, 0, sizeof(TT));
     bool tempered = false;
     if (temps->by_visible && temps->n > 1) {
@@ -369,12 +253,6 @@ extern "C" int mnn_nade_sample_sir_at(mnn_stream_t s, int tracks, int N, int D, 
         for (int j = 0; j < MNN_TEMPS_MAX; ++j) TT.t[j] = temps->n == 1 ? temps->t[0] : (j < temps->n ? temps->t[j] : 1.0f);
         for (int j = 0; j < tracks && j < MNN_TEMPS_MAX; ++j) tempered = tempered || TT.t[j] != 1.0f;
     }
-    // workgroups per scan: a workgroup's four waves take four particles at a time and stride over the scan's groups (mnn_nade_given_is)
-    const int groups = cdiv(C, 4);
-    const long most = cdiv(65536, (long)N * tracks);
-    const int per = cdiv(groups, most < 1 ? 1 : most);
-    const int G = cdiv(groups, per);
-    MNN_REQUIRE((long)N * G <= 0x7fffffffL, "mnn_nade_sample_sir: N * workgroups per scan = %ld exceeds the grid", (long)N * G);
     SirArgs a{tracks, N, D, Hn, C, G, bias, ld_bias, w_enc, w_dec, given, s_track_stride, (long)s_row_stride, s_elem_stride, seed, row0, sub, sub_base,
               (uint32_t)(E4 >> 2), TT, lw, nll_c, flag, v};
     const dim3 grid((unsigned)((long)N * G), (unsigned)tracks);

@@ -159,6 +159,28 @@ def test_counter_independence(ops, N, D, Hn, tracks):
     assert lower[2][:, :, 1:].tobytes() != upper[2][:, :, 1:].tobytes()      # the two sides of one seed share no uniform
 
 
+@pytest.mark.parametrize("N,D,Hn,tracks,C,H", [(4, 7, 256, 2, 40001, 20100), (3, 61, 30, 2, 50001, 25100)])
+def test_a_workgroup_that_outlives_one_particle_group(ops, N, D, Hn, tracks, C, H):
+    """More particle groups than a row gets workgroups (10001 / 12501 groups of four against 8192 / 10923 workgroups: every workgroup takes two,
+    G = 5001 / 6251), so a wave runs a second particle, c >= 4 G = 20004 / 25004, from the state it kept.  The first 33 particles are the
+    bits of the C = 33 launch that test_particles_bit_exact_and_weights_against_float64 checks against the reference, and the first H, which
+    reach behind 4 G, those of a C = H launch in which every particle is its wave's first (H / 4 groups fit the workgroups)."""
+    most = -(-65536 // (N * tracks))
+    groups = -(-C // 4)
+    G = -(-groups // -(-groups // most))
+    assert groups > most and 4 * G + 64 < H and -(-H // 4) <= most
+    bias, we, wd, codes, data, ids = problem(N, D, Hn, tracks)
+    for side in (None, data):
+        small = run(ops, bias, we, wd, codes, side, 33, 77, ids)
+        first = run(ops, bias, we, wd, codes, side, H, 77, ids)
+        large = run(ops, bias, we, wd, codes, side, C, 77, ids)
+        assert large[1][:, :, :33].tobytes() == small[1].tobytes()
+        assert large[2][:, :, :33].tobytes() == small[2].tobytes()
+        assert large[1][:, :, :H].tobytes() == first[1].tobytes()
+        assert large[2][:, :, :H].tobytes() == first[2].tobytes()
+        assert np.all(np.isfinite(large[0]))
+
+
 # 4. the estimates against enumeration, and the direction of the two biases (the toy and seeds of tests/test_nade_is_cpu.py)
 def toy_run(ops, p, side_data):
     bias, we, wd, x, codes = REF.toy_problem(p["n_rows"], p["w_scale"], p["seed"])

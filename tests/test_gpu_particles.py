@@ -153,6 +153,36 @@ def test_particles_do_not_depend_on_their_company(ops):
     assert full[4].tobytes() == np.ascontiguousarray(twice[4][:, :, :5]).tobytes()
 
 
+@pytest.mark.parametrize("N,D,Hn,tracks,temps", [(150, 7, 256, 2, (1.0, False)), (150, 13, 32, 2, (REF.VISIBLE_TEMPS, True))])
+def test_a_workgroup_that_outlives_one_particle_group(ops, N, D, Hn, tracks, temps):
+    """C = 1021 is 256 groups of four against 219 workgroups a scan gets, so every workgroup takes two (G = 128) and a wave runs a second
+    particle, c >= 4 G = 512, from the state it kept: the first five particles (their vectors out of the workspace, their log weights) are the
+    bytes of the C = 5 launch, and the first 600, which reach behind 4 G, those of a C = 600 launch in which every particle is its wave's
+    first (150 groups fit the workgroups)."""
+    C, H = 1021, 600
+    most = -(-65536 // (N * tracks))
+    assert -(-C // 4) == 256 > most >= -(-H // 4) and 4 * 128 + 64 < H
+    bias, we, wd, codes = REF.problem(N, D, Hn, tracks)
+    got = []
+    for c in (5, H, C):
+        out = torch.full((N, tracks * D), 9, device=DEV, dtype=torch.uint8)
+        v = torch.full((tracks, N, c, D), 9, device=DEV, dtype=torch.uint8)
+        log_w = torch.full((tracks, N, c), 7.0, device=DEV)
+        ops.nade_sample_sir(dev(bias), dev(we), dev(wd), tracks, D, Hn, temps[0], SEED, ROW0, SUB, out, dev(flat(codes)), c, by_visible=temps[1],
+                            sub_base=torch.tensor([SUB_CELL], dtype=torch.int32, device=DEV), log_w=log_w, v_out=v)
+        got.append((v.cpu().numpy(), log_w.cpu().numpy()))
+    (v5, lw5), (vh, lwh), (vc, lwc) = got
+    for m in range(tracks):
+        sc = REF.is_shortcut(codes[m])
+        assert sc.any() and not sc.all()
+        assert vc[m][~sc][:, :5].tobytes() == v5[m][~sc].tobytes()
+        assert vc[m][sc, 0].tobytes() == v5[m][sc, 0].tobytes()
+        assert lwc[m][:, :5].tobytes() == lw5[m].tobytes()
+        assert vc[m][~sc][:, :H].tobytes() == vh[m][~sc].tobytes()
+        assert vc[m][sc, 0].tobytes() == vh[m][sc, 0].tobytes()
+        assert lwc[m][:, :H].tobytes() == lwh[m].tobytes()
+
+
 def test_strides(ops):
     """Track-minor samples (feature i tracks + m), and a view of track m of a [B, steps, P, M] roll: the bytes of the contiguous call."""
     N, D, Hn, tracks = SHAPES[0]
