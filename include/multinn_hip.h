@@ -125,6 +125,19 @@ int mnn_rows_scatter_f32(mnn_stream_t s, const float* src /* compact [N, C] */, 
 /* per-track variant: targets_tracks u8 [M,T,B,P] from x u8 [B,T,P,M]  (multi_encoder_nn.py:66-76) */
 int mnn_pianoroll_split_tracks(mnn_stream_t s, const uint8_t* x, int B, int T, int P, int M, uint8_t* targets_tracks);
 
+/* A training window cut out of a dataset that lives on the device (an addition without a version bump; train.py:164-173 slices the
+ * host array):  out[b, t, d] = X[ids[b], j + t, e0 + d * es]  for t < Tw, d < Dout, and optionally the clipped lengths of its rows.
+ *   e0 = 0, es = 1, Dout = D: the joint window -- row b is one contiguous run of Tw * D bytes, copied with vectors of the widest power of
+ *                             two (<= 16 bytes) that divides D and both base addresses, on a grid sized by the bytes to move;
+ *   es = M, e0 = m, Dout = P: track m of a [S, T, P, M] roll, a strided byte gather.
+ * Every offset into X is 64-bit.  An id outside [0, S) reads nothing of X: its row is zeros, its length 0.  Refused on the host, before
+ * any device work: a non-positive S, T, D, B, Tw or Dout; j < 0 or j + Tw > T; es < 1, e0 < 0 or e0 + (Dout - 1) * es >= D; a NULL X, ids
+ * or out; out_len without lengths. */
+int mnn_window_gather(mnn_stream_t s, const uint8_t* X /* u8 [S, T, D], D = P * M, feature p * M + m */, long S, int T, int D,
+                      const int32_t* ids /* device [B]: the song of output row b */, int B, int j, int Tw /* steps j .. j + Tw - 1 */,
+                      int e0, int es, int Dout, const int32_t* lengths /* device [S] or NULL */, uint8_t* out /* [B, Tw, Dout] contiguous */,
+                      int32_t* out_len /* [B] or NULL: clamp(lengths[ids[b]] - j, 0, Tw) */);
+
 /* ------------------------------------------------------------------------------------------
  * LSTM (tf.contrib.cudnn_rnn.CudnnCompatibleLSTMCell == LSTMBlockCell, gate order i,ci,f,o,
  * forget_bias 0; rnn.py:104-145).  Internal pre-activation layout is gate-interleaved:

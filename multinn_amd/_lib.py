@@ -228,7 +228,9 @@ SIGNATURES["mnn_generate_scan_chunk_sir"] = (_i, SIGNATURES["mnn_generate_scan_c
 SIGNATURES["mnn_lstm_step_det_ragged"] = (_i, SIGNATURES["mnn_lstm_step_det"][1] + [_p, _i])
 SIGNATURES["mnn_generate_scan_ragged"] = (_i, SIGNATURES["mnn_generate_scan_sir"][1] + [_p])
 SIGNATURES["mnn_generate_scan_chunk_ragged"] = (_i, SIGNATURES["mnn_generate_scan_chunk_sir"][1] + [_p])
-PARTICLES_MAX = 1024       # mnn_sir.particles
+# device-resident dataset (an addition without a version bump): a window [B, Tw, Dout] cut out of u8 [S, T, D] by song id
+SIGNATURES["mnn_window_gather"] = (_i, [_p, _p, _l, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p])
+PARTICLES_MAX = 1024      # mnn_sir.particles
 TEMPS_MAX = 8              # MNN_TEMPS_MAX
 REDRAWS_MAX = 255          # mnn_redraw.tries
 

@@ -113,9 +113,105 @@ def iter_windows(ids, lengths, T_total, batch_size, piece_size):
         yield None                                    # end of a song batch: stats.new_step() (train.py:194)
 
 
-def train_epoch(generator, X, lengths, ids, batch_size, piece_size, optimizer, loss_accum, stats, lr=None, device=None):
-    """One epoch of train.py:164-194.  X uint8 [S,T,P,M] (numpy); every window starts from a ZERO rnn state."""
+def _dataset(X):
+    """X if it is a device-resident dataset (device_data.DeviceDataset), else None: a NumPy X keeps the host path of every function below."""
+    if isinstance(X, np.ndarray):
+        return None
+    from .device_data import DeviceDataset
+    return X if isinstance(X, DeviceDataset) else None
+
+
+def _host_only(drain_every):
+    if drain_every is not None:
+        raise ValueError("drain_every batches the loss read-backs of a DeviceDataset; a NumPy X reads every loss as it is produced")
+
+
+def _dataset_windows(ds, lengths, ids, batch_size, piece_size):
+    """iter_windows over a DeviceDataset, with the song ids of the WHOLE epoch uploaded once (int32, the windows' ids back to back) in front
+    of the first step: yields None, or (song_ids, j, max_length, clipped_lengths, ids_dev) with ids_dev the window's slice of that upload."""
+    if lengths is not None and not np.array_equal(np.asarray(lengths), ds.lengths):
+        raise ValueError("the lengths passed beside a DeviceDataset differ from the dataset's own (pass None, or the ones it was built with)")
+    if len(ids):
+        ds.check_ids(ids)                                 # before they index the host lengths
+    windows = list(iter_windows(ids, ds.lengths, ds.shape[1], batch_size, piece_size))
+    real = [w[0] for w in windows if w is not None]
+    ids_dev, at = ds.upload_ids(np.concatenate(real)) if real else None, 0
+    for w in windows:
+        if w is None:
+            yield None
+            continue
+        yield w + (ids_dev[at:at + len(w[0])],)
+        at += len(w[0])
+
+
+class LossRing:
+    """The losses of consecutive steps, kept on the device and read back in batches: `put` copies a loss TENSOR into the next slot of a small
+    ring (no synchronisation: the host runs ahead of the device) and `drain` hands the slots to `sink(value, note)` in step order -- when the
+    ring is full, every `drain_every` puts if given, and at `flush` (the end of an epoch).  A loss that already is a host number goes to the
+    sink at once, behind whatever the ring still holds, so the sink sees every loss in step order and ends in the state that per-step
+    `float(loss)` reads would have left.  The slots are float64: every float dtype a step returns converts to it exactly, like float() does."""
+
+    def __init__(self, sink, slots=1024, drain_every=None):
+        if drain_every is not None and drain_every < 1:
+            raise ValueError(f"drain_every must be a positive number of steps, got {drain_every}")
+        self.sink, self.slots = sink, slots if drain_every is None else min(slots, drain_every)
+        self._ring, self._notes = None, []
+
+    def put(self, loss, note=None):
+        import torch
+        if not isinstance(loss, torch.Tensor):
+            self.flush()
+            self.sink(float(loss), note)
+            return
+        if self._ring is None or self._ring.device != loss.device:
+            self.flush()
+            self._ring = torch.empty(self.slots, dtype=torch.float64, device=loss.device)
+        self._ring[len(self._notes)].copy_(loss.detach().reshape(()))
+        self._notes.append(note)
+        if len(self._notes) == self.slots:
+            self.drain()
+
+    def flush(self):
+        if self._notes:
+            self.drain()
+
+    def drain(self):
+        """One device synchronisation and one copy for all the losses held."""
+        notes, self._notes = self._notes, []
+        for value, note in zip(self._ring[:len(notes)].tolist(), notes):
+            self.sink(value, note)
+
+
+def _train_epoch_dataset(generator, ds, lengths, ids, batch_size, piece_size, optimizer, loss_accum, stats, lr, drain_every):
+    """train_epoch over a DeviceDataset: the same windows in the same order, cut out of the dataset on its device; the same step."""
+    ring = LossRing(lambda value, _: loss_accum.update(value), drain_every=drain_every)
+    for w in _dataset_windows(ds, lengths, ids, batch_size, piece_size):
+        if w is None:
+            stats.new_step()
+            continue
+        song_ids, j, max_len, len_batch, ids_dev = w
+        xb, lb = ds.window(song_ids, j, max_len, ids_dev=ids_dev)
+        xb = xb.view(xb.shape[0], max_len, *ds.shape[2:])             # [B, Tw, P, M], what the NumPy path feeds
+        full = bool((len_batch == max_len).all())
+        lb = None if full else lb
+        run = _captured_step(generator, xb, optimizer, lr, lengths=lb)
+        if run is not None:
+            loss = run(xb) if full else run(xb, lb)
+        else:
+            loss = generator.train_step(xb, lb, optimizer, lr)
+        ring.put(loss)
+    ring.flush()
+    return loss_accum.loss()
+
+
+def train_epoch(generator, X, lengths, ids, batch_size, piece_size, optimizer, loss_accum, stats, lr=None, device=None, drain_every=None):
+    """One epoch of train.py:164-194.  X uint8 [S,T,P,M] (numpy); every window starts from a ZERO rnn state.
+    X may be a DeviceDataset instead (lengths: None or its own; `device` is the dataset's): the windows are cut out of it on the device and
+    the losses are read back in one batch at the end of the epoch (LossRing), or every `drain_every` steps."""
     import torch
+    if _dataset(X) is not None:
+        return _train_epoch_dataset(generator, X, lengths, ids, batch_size, piece_size, optimizer, loss_accum, stats, lr, drain_every)
+    _host_only(drain_every)
     for w in iter_windows(ids, lengths, X.shape[1], batch_size, piece_size):
         if w is None:
             stats.new_step()
@@ -158,7 +254,7 @@ def _captured_step(generator, xb, optimizer, lr, max_graphs=8, lengths=None):
     return graphs[key]
 
 
-def evaluate(generator, X, lengths, batch_size, piece_size, device=None, nll="loss", ais=None, given_mask=None, partial="refuse"):
+def evaluate(generator, X, lengths, batch_size, piece_size, device=None, nll="loss", ais=None, given_mask=None, partial="refuse", drain_every=None):
     """utils/training.py:180-213 collect_metrics: mean generator NLL per valid row over all windows.
     nll="loss" (default): the training loss (an RBM generator's is the CD cost, a difference of free energies, not a likelihood).
     nll="ais": the model's estimate_nll(x, lengths, **ais) -- exact for NADE generators, annealed importance sampling for RBM generators
@@ -169,7 +265,9 @@ def evaluate(generator, X, lengths, batch_size, piece_size, device=None, nll="lo
     given_mask (optional, with nll "ais" / "raise" / "bracket"): a batch-independent bool mask, [M] or [P, M], passed to every window's
     estimate_nll -- the mean CONDITIONAL NLL per valid step of the cells outside the mask given those under it (and the past).
     partial ("refuse" or "importance", with given_mask): estimate_nll's -- "importance" estimates a NADE that the mask leaves partly given
-    by importance sampling (ais: num_chains particles per row) where "refuse" raises; nll "bracket" then reports its two sides and their gap."""
+    by importance sampling (ais: num_chains particles per row) where "refuse" raises; nll "bracket" then reports its two sides and their gap.
+    X may be a DeviceDataset (lengths: None or its own): every window is cut out of it on its device, and nll="loss" reads its losses back
+    in one batch (LossRing; every `drain_every` windows if given) -- the estimator modes take the gathered window and are otherwise unchanged."""
     import torch
     methods = {"ais": "ais", "raise": "raise", "bracket": "both"}
     if nll != "loss" and nll not in methods:
@@ -186,24 +284,46 @@ def evaluate(generator, X, lengths, batch_size, piece_size, device=None, nll="lo
         cond = dict(given_mask=given_mask) if partial == "refuse" else dict(given_mask=given_mask, partial=partial)
     tot, cnt, tot_upper = 0.0, 0, 0.0
     ids = np.arange(X.shape[0])
-    for w in iter_windows(ids, lengths, X.shape[1], batch_size, piece_size):
+    ds = _dataset(X)
+    if ds is None:
+        _host_only(drain_every)
+        windows = iter_windows(ids, lengths, X.shape[1], batch_size, piece_size)
+    else:
+        windows = _dataset_windows(ds, lengths, ids, batch_size, piece_size)
+        weighted = [0.0]
+
+        def add_weighted(value, n):
+            weighted[0] += value * n
+        ring = LossRing(add_weighted, drain_every=drain_every)
+    for w in windows:
         if w is None:
             continue
-        song_ids, j, max_len, len_batch = w
-        xb = torch.from_numpy(np.ascontiguousarray(X[song_ids, j:j + max_len])).to(device or "cuda")
+        song_ids, j, max_len, len_batch = w[:4]
         full = bool((len_batch == max_len).all())
+        if ds is None:
+            xb = torch.from_numpy(np.ascontiguousarray(X[song_ids, j:j + max_len])).to(device or "cuda")
+            lb = None if full else torch.from_numpy(len_batch).to(xb.device)
+        else:
+            xb, lb = ds.window(song_ids, j, max_len, ids_dev=w[4])
+            xb, lb = xb.view(xb.shape[0], max_len, *ds.shape[2:]), None if full else lb
         if nll != "loss":
             n = int(len_batch.sum())
-            est = generator.estimate_nll(xb, None if full else torch.from_numpy(len_batch).to(xb.device), **dict(ais or {}, method=methods[nll]), **cond)
+            est = generator.estimate_nll(xb, lb, **dict(ais or {}, method=methods[nll]), **cond)
             tot += (est.lower if nll == "bracket" else est).mean * n
             tot_upper += est.upper.mean * n if nll == "bracket" else 0.0
             cnt += n
             continue
-        generator.build_pianoroll(xb, None if full else torch.from_numpy(len_batch).to(xb.device), is_train=False, mode="eval")
+        generator.build_pianoroll(xb, lb, is_train=False, mode="eval")
         n = int(len_batch.sum())
         loss = generator.generator_loss() if hasattr(generator, "generator_loss") else generator.metrics["batch/loss"]
-        tot += float(loss) * n
+        if ds is None:
+            tot += float(loss) * n
+        else:
+            ring.put(loss, n)
         cnt += n
+    if ds is not None:
+        ring.flush()
+        tot += weighted[0]
     if nll == "bracket":
         lower, upper = tot / max(cnt, 1), tot_upper / max(cnt, 1)
         return {"lower": lower, "upper": upper, "gap": upper - lower}
@@ -263,12 +383,14 @@ def pretrain_encoders(encoders, X_train, len_train, training_config, beat_size=4
     `epochs` epochs, every shuffled song batch and every piece of `piece_size` beats: the encoder is built on the window of its
     track (`x[..., i]` for track i, all tracks flattened for a single joint encoder) and `encoder.train(None, lr, layer)` runs one
     CD-k update of that layer's RBM fed with the sampled codes of the layers below (dbn_encoder.py:192-240).
-    X_train uint8 [songs, T, P, M] (numpy).  Returns {(encoder index, layer): [mean reconstruction cost per epoch]}."""
+    X_train uint8 [songs, T, P, M] (numpy), or a DeviceDataset (len_train: None or its own): track i's windows are then gathered on its device.
+    Returns {(encoder index, layer): [mean reconstruction cost per epoch]}."""
     import torch
     batch_size = training_config['batch_size']
     piece_size = int(training_config['piece_size'] * beat_size)
     lr = training_config['learning_rate'] if lr is None else lr
     ids = np.arange(X_train.shape[0])
+    ds = _dataset(X_train)
     history = {}
     for e_i, enc in enumerate(encoders):
         for layer in range(enc.num_layers):
@@ -277,16 +399,29 @@ def pretrain_encoders(encoders, X_train, len_train, training_config, beat_size=4
                 np.random.seed(epoch)                           # train_encoders.py:134-135
                 np.random.shuffle(ids)
                 acc = LossAccumulator()
-                for w in iter_windows(ids, len_train, X_train.shape[1], batch_size, piece_size):
+                if ds is None:
+                    windows = iter_windows(ids, len_train, X_train.shape[1], batch_size, piece_size)
+                else:
+                    windows = _dataset_windows(ds, len_train, ids, batch_size, piece_size)
+                    ring = LossRing(lambda value, _, acc=acc: acc.update(value))
+                for w in windows:
                     if w is None:
                         continue
-                    song_ids, j, max_len, _ = w
-                    xb = X_train[song_ids, j:j + max_len]
-                    xb = xb[..., e_i] if len(encoders) > 1 else xb.reshape(xb.shape[0], xb.shape[1], -1)
-                    xt = torch.from_numpy(np.ascontiguousarray(xb)).to(device or "cuda")
+                    song_ids, j, max_len = w[:3]
+                    if ds is None:
+                        xb = X_train[song_ids, j:j + max_len]
+                        xb = xb[..., e_i] if len(encoders) > 1 else xb.reshape(xb.shape[0], xb.shape[1], -1)
+                        xt = torch.from_numpy(np.ascontiguousarray(xb)).to(device or "cuda")
+                    else:
+                        xt, _ = ds.window(song_ids, j, max_len, track=e_i if len(encoders) > 1 else None, ids_dev=w[4])
                     enc.build(x=xt, is_train=True, mode="train")
                     _, _, metrics, _, _ = enc.train(None, lr, layer=layer)
-                    acc.update(float(metrics["batch/loss"]) if metrics else 0.0)
+                    if ds is None:
+                        acc.update(float(metrics["batch/loss"]) if metrics else 0.0)
+                    else:
+                        ring.put(metrics["batch/loss"] if metrics else 0.0)
+                if ds is not None:
+                    ring.flush()
                 costs.append(acc.loss())
                 if log is not None:
                     log(f"[PRETRAIN] encoder {e_i} layer {layer} epoch {epoch}: reconstruction cost {costs[-1]:.4f}")
@@ -331,6 +466,8 @@ def main(argv=None):
     ap.add_argument("--reuse-config", action="store_true")
     ap.add_argument("--precision", default="fp16", choices=["fp16", "bf16", "fp32"],
                     help="fp16: IEEE-half operands, the mode that meets the 1e-4 parity gate at full speed; bf16; fp32: v_mfma_f32 GEMMs, launch-per-step recurrence")
+    ap.add_argument("--device-data", action="store_true",
+                    help="keep the train and validation splits on the device (DeviceDataset): windows are cut out of them there, losses read back per epoch")
     a = ap.parse_args(argv)
     from .training import AdamOptimizer
     root = os.path.join("..", "results", a.model_name)                  # utils/setup.py:50
@@ -366,7 +503,11 @@ def main(argv=None):
         src = dirs["model_last_dir"] if a.from_last else dirs["model_dir"]
         if gen.load(None, src):
             stats.load(os.path.join(src, "steps"))
-    fit(gen, AdamOptimizer(tr["learning_rate"]), X[:nt], lengths[:nt], X[nt:nt + nv], lengths[nt:nt + nv], tr, config["logs"], dirs, stats,
+    X_train, X_valid = X[:nt], X[nt:nt + nv]
+    if a.device_data:
+        from .device_data import DeviceDataset
+        X_train, X_valid = DeviceDataset(X_train, lengths[:nt]), DeviceDataset(X_valid, lengths[nt:nt + nv])
+    fit(gen, AdamOptimizer(tr["learning_rate"]), X_train, lengths[:nt], X_valid, lengths[nt:nt + nv], tr, config["logs"], dirs, stats,
         beat_size=d["beat_resolution"] / npx, save_best_only=a.save_best_only)
 
 

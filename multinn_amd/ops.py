@@ -171,6 +171,27 @@ def pianoroll_split_tracks(x, out):
     return out
 
 
+def window_gather(X, ids, j, Tw, out, lengths=None, out_len=None, track=None, tracks=1):
+    """out[b, t, :] = X[ids[b], j + t, :] (mnn_window_gather): X u8 [S, T, D] on the device, ids int32 [B] on the device, out u8 [B, Tw, D].
+    track = m with tracks = M: feature p * M + m of every p instead, out u8 [B, Tw, D / M].  lengths int32 [S] with out_len int32 [B]:
+    out_len[b] = clamp(lengths[ids[b]] - j, 0, Tw)."""
+    _req(X.dtype == torch.uint8 and X.dim() == 3 and X.is_contiguous(), "window_gather: X must be contiguous u8 [S,T,D]")
+    S, T, D = X.shape
+    _req(ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous() and ids.numel() > 0, "window_gather: ids int32 [B]")
+    B = ids.numel()
+    if track is None:
+        e0, es, Dout = 0, 1, D
+    else:
+        _req(tracks >= 1 and D % tracks == 0 and 0 <= track < tracks, f"window_gather: track {track} of {tracks} tracks over D = {D}")
+        e0, es, Dout = int(track), int(tracks), D // tracks
+    _req(out.dtype == torch.uint8 and tuple(out.shape) == (B, Tw, Dout) and out.is_contiguous(), f"window_gather: out must be contiguous u8 [{B},{Tw},{Dout}]")
+    _req(lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == S and lengths.is_contiguous()), "window_gather: lengths int32 [S]")
+    _req(out_len is None or (lengths is not None and out_len.dtype == torch.int32 and out_len.numel() == B and out_len.is_contiguous()),
+         "window_gather: out_len int32 [B], with lengths")
+    call("mnn_window_gather", _stream(), _ptr(X), S, T, D, _ptr(ids), B, int(j), int(Tw), e0, es, Dout, _ptr(lengths), _ptr(out), _ptr(out_len))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 def lstm_pack_weights(W, b, n_in, units, wx_t, wh_t, wh_p, wx_p, bias_p):
     _req(W.dtype == torch.float32 and W.shape == (n_in + units, 4 * units) and W.is_contiguous(), "pack: W f32 [(in+u),4u]")
