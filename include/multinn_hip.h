@@ -138,6 +138,21 @@ int mnn_window_gather(mnn_stream_t s, const uint8_t* X /* u8 [S, T, D], D = P * 
                       int e0, int es, int Dout, const int32_t* lengths /* device [S] or NULL */, uint8_t* out /* [B, Tw, Dout] contiguous */,
                       int32_t* out_len /* [B] or NULL: clamp(lengths[ids[b]] - j, 0, Tw) */);
 
+/* Transposition inside the gather (additions without a version bump).  With D = P * M, feature f is cell (p, m) = (f / M, f % M).
+ * mnn_window_gather_shift is mnn_window_gather with a pitch shift per output row: an element that reads feature f of a MOVING track (bit m
+ * of `moving` set) reads cell (p - shifts[b], m) instead, and is 0 where p - shifts[b] leaves 0..P-1 (formed in 64 bits: any int32 is a
+ * valid shift, |shift| >= P gives zeros on the moving tracks); an element of a track that stays is the plain gather's byte.  Both forms
+ * of the plain gather are served (the joint row; e0 = m, es = M for one track) by one byte-per-lane kernel.  All shifts 0, or moving = 0,
+ * give mnn_window_gather's output bit for bit; out_len and the zero row of an id outside [0, S) are the plain gather's.  Refused beyond
+ * what mnn_window_gather refuses: shifts == NULL; M < 1, M > 32 or D % M != 0; a row of 2^31 bytes or more.
+ * mnn_pitch_extent: per song the smallest (lo) and largest (hi) p at which a moving track has a non-zero cell in a step t < lengths[song]
+ * (every step when lengths is NULL); lo = P, hi = -1 for a song without one.  One workgroup per song; meant to run once per dataset. */
+int mnn_window_gather_shift(mnn_stream_t s, const uint8_t* X, long S, int T, int D, const int32_t* ids, int B, int j, int Tw, int e0, int es, int Dout,
+                            const int32_t* lengths, uint8_t* out, int32_t* out_len, const int32_t* shifts /* device [B] */, int M /* tracks */,
+                            uint32_t moving /* bit m: track m is transposed */);
+int mnn_pitch_extent(mnn_stream_t s, const uint8_t* X /* u8 [S, T, D] */, long S, int T, int D, int M, uint32_t moving,
+                     const int32_t* lengths /* device int32 [S] or NULL */, int32_t* lo /* device [S] */, int32_t* hi /* device [S] */);
+
 /* ------------------------------------------------------------------------------------------
  * LSTM (tf.contrib.cudnn_rnn.CudnnCompatibleLSTMCell == LSTMBlockCell, gate order i,ci,f,o,
  * forget_bias 0; rnn.py:104-145).  Internal pre-activation layout is gate-interleaved:

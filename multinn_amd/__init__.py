@@ -5,7 +5,7 @@ behind the C ABI in include/multinn_hip.h (libmultinn_hip.so).  No CPU fallback.
 """
 __all__ = ["RnnNade", "RnnMultiNADE", "RnnMultiRBM", "RnnRBM", "PassEncoder", "DBNEncoder", "NADE", "RBM", "RNN", "DBN",
            "AdamOptimizer", "GradientDescentOptimizer", "MultINN", "MultINNJoint", "MultINNComposer", "MultINNJamming",
-           "MultINNFeedback", "MultINNFeedbackRnn", "GeneratorSession", "ModeSession", "DeviceDataset"]
+           "MultINNFeedback", "MultINNFeedbackRnn", "GeneratorSession", "ModeSession", "DeviceDataset", "Transpose"]
 
 
 def __getattr__(name):
@@ -31,6 +31,9 @@ def __getattr__(name):
     if name == "DeviceDataset":
         from . import device_data
         return device_data.DeviceDataset
+    if name == "Transpose":
+        from . import data
+        return data.Transpose
     if name in ("AdamOptimizer", "GradientDescentOptimizer", "compute_gradients"):
         from . import training
         return getattr(training, name)

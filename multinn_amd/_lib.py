@@ -230,6 +230,9 @@ SIGNATURES["mnn_generate_scan_ragged"] = (_i, SIGNATURES["mnn_generate_scan_sir"
 SIGNATURES["mnn_generate_scan_chunk_ragged"] = (_i, SIGNATURES["mnn_generate_scan_chunk_sir"][1] + [_p])
 # device-resident dataset (an addition without a version bump): a window [B, Tw, Dout] cut out of u8 [S, T, D] by song id
 SIGNATURES["mnn_window_gather"] = (_i, [_p, _p, _l, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p])
+# transposition inside the gather (additions without a version bump): the gather with (shifts, M, moving) behind; the songs' pitch extents
+SIGNATURES["mnn_window_gather_shift"] = (_i, SIGNATURES["mnn_window_gather"][1] + [_p, _i, _u32])
+SIGNATURES["mnn_pitch_extent"] = (_i, [_p, _p, _l, _i, _i, _i, _u32, _p, _p, _p])
 PARTICLES_MAX = 1024      # mnn_sir.particles
 TEMPS_MAX = 8              # MNN_TEMPS_MAX
 REDRAWS_MAX = 255          # mnn_redraw.tries

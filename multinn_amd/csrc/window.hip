@@ -106,3 +106,90 @@ extern "C" int mnn_window_gather(mnn_stream_t s, const uint8_t* X, long S, int T
     MNN_LAUNCH_CHECK();
     return MNN_OK;
 }
+
+// ---- transposition (pitch shift) inside the gather ------------------------------------------------------------------------------------
+// Feature f of a [P, M] step is cell (p, m) = (f / M, f % M).  An output byte that reads feature f of a MOVING track (bit m of `moving`)
+// reads cell (p - shifts[b], m) instead, or nothing (0) where p - shifts[b] leaves 0..P-1; a byte of a track that stays is the plain
+// gather's.  One output byte per lane, like window_gather_kernel, for the joint row (e0 = 0, es = 1, Dout = D) and the single track
+// (e0 = m, es = M, Dout = P) alike.  p - shifts[b] is formed in 64 bits and compared with [0, P) BEFORE it is used, so no int32 shift
+// indexes outside the time step it belongs to: every read is X[id, j + t, q * M + m] with 0 <= q < P, m < M, q * M + m < D.
+__global__ void __launch_bounds__(WIN_THREADS) window_gather_shift_kernel(const uint8_t* __restrict__ X, long S, long row_pitch, int D,
+                                                                          const int32_t* __restrict__ ids, const int32_t* __restrict__ shifts, int B,
+                                                                          int j, int Tw, int e0, int es, int Dout, int M, uint32_t moving,
+                                                                          const int32_t* __restrict__ lengths, uint8_t* __restrict__ out,
+                                                                          int32_t* __restrict__ out_len) {
+    const unsigned n = (unsigned)Tw * (unsigned)Dout;                     // < 2^31 (checked on the host)
+    const unsigned e = blockIdx.x * WIN_THREADS + threadIdx.x;
+    const unsigned t = e / (unsigned)Dout, d = e - t * (unsigned)Dout;
+    const unsigned f = (unsigned)e0 + d * (unsigned)es;                   // < D for e < n
+    const unsigned p = f / (unsigned)M, m = f - p * (unsigned)M;
+    const bool moves = (moving >> m) & 1u;
+    const long P = D / M;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        const long id = window_song(ids, b, S);
+        window_length(lengths, id, j, Tw, out_len, b);
+        if (e >= n) continue;
+        const long q = moves ? (long)p - (long)shifts[b] : (long)p;
+        uint8_t v = 0;
+        if (id >= 0 && q >= 0 && q < P) v = X[id * row_pitch + (long)(j + t) * D + q * M + m];
+        out[(long)b * n + e] = v;
+    }
+}
+
+extern "C" int mnn_window_gather_shift(mnn_stream_t s, const uint8_t* X, long S, int T, int D, const int32_t* ids, int B, int j, int Tw, int e0, int es,
+                                       int Dout, const int32_t* lengths, uint8_t* out, int32_t* out_len, const int32_t* shifts, int M, uint32_t moving) {
+    MNN_REQUIRE(S > 0 && T > 0 && D > 0 && B > 0 && Tw > 0 && Dout > 0,
+                "mnn_window_gather_shift: S, T, D, B, Tw and Dout must be positive (got %ld, %d, %d, %d, %d, %d)", S, T, D, B, Tw, Dout);
+    MNN_REQUIRE(j >= 0 && (long)j + Tw <= T, "mnn_window_gather_shift: the window j = %d, Tw = %d leaves the %d steps of the dataset", j, Tw, T);
+    MNN_REQUIRE(es >= 1 && e0 >= 0 && (long)e0 + (long)(Dout - 1) * es < D,
+                "mnn_window_gather_shift: features e0 = %d, es = %d, Dout = %d leave the D = %d of the dataset", e0, es, Dout, D);
+    MNN_REQUIRE(X && ids && out, "mnn_window_gather_shift: X, ids and out must not be NULL");
+    MNN_REQUIRE(shifts != nullptr, "mnn_window_gather_shift: shifts must not be NULL (mnn_window_gather is the gather without shifts)");
+    MNN_REQUIRE(M >= 1 && M <= 32 && D % M == 0, "mnn_window_gather_shift: tracks M = %d must lie in 1..32 and divide D = %d", M, D);
+    MNN_REQUIRE(out_len == nullptr || lengths != nullptr, "mnn_window_gather_shift: out_len needs lengths");
+    MNN_REQUIRE((long)Tw * Dout < (1L << 31), "mnn_window_gather_shift: a window row of %ld bytes is too long", (long)Tw * Dout);
+    const dim3 grid(cdiv((long)Tw * Dout, WIN_THREADS), std::min(B, 65535));
+    hipLaunchKernelGGL(window_gather_shift_kernel, grid, dim3(WIN_THREADS), 0, (hipStream_t)s, X, S, (long)T * D, D, ids, shifts, B, j, Tw, e0, es, Dout, M,
+                       moving, lengths, out, out_len);
+    MNN_LAUNCH_CHECK();
+    return MNN_OK;
+}
+
+// The pitch range a song's moving tracks occupy: lo[s] / hi[s] = the smallest / largest p with X[s, t, p, m] != 0 for some t < lengths[s]
+// (all T steps without lengths) and some moving m; lo = P, hi = -1 where there is none.  Runs once per dataset and set of tracks: one
+// workgroup per song, each lane walks the steps of its features (p and m fixed per lane: consecutive lanes read consecutive bytes), then
+// a min / max over the wave by shuffles and over the workgroup through LDS.
+__global__ void __launch_bounds__(WIN_THREADS) pitch_extent_kernel(const uint8_t* __restrict__ X, int T, int D, int M, uint32_t moving,
+                                                                   const int32_t* __restrict__ lengths, int32_t* __restrict__ lo,
+                                                                   int32_t* __restrict__ hi) {
+    __shared__ int32_t s_lo[WIN_THREADS / 64], s_hi[WIN_THREADS / 64];
+    const long song = blockIdx.x;
+    const int len = lengths == nullptr ? T : min(max(lengths[song], 0), T);
+    const uint8_t* __restrict__ x = X + song * (long)T * D;
+    int32_t l = D / M, h = -1;
+    for (int f = threadIdx.x; f < D; f += WIN_THREADS) {
+        const int p = f / M, m = f - p * M;
+        if (!((moving >> m) & 1u)) continue;
+        uint32_t any = 0;
+        for (int t = 0; t < len; ++t) any |= x[(long)t * D + f];
+        if (any) l = min(l, p), h = max(h, p);
+    }
+    for (int o = 32; o > 0; o >>= 1) l = min(l, __shfl_down(l, o, 64)), h = max(h, __shfl_down(h, o, 64));
+    if ((threadIdx.x & 63) == 0) s_lo[threadIdx.x >> 6] = l, s_hi[threadIdx.x >> 6] = h;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < WIN_THREADS / 64; ++w) l = min(l, s_lo[w]), h = max(h, s_hi[w]);
+        lo[song] = l;
+        hi[song] = h;
+    }
+}
+
+extern "C" int mnn_pitch_extent(mnn_stream_t s, const uint8_t* X, long S, int T, int D, int M, uint32_t moving, const int32_t* lengths, int32_t* lo,
+                                int32_t* hi) {
+    MNN_REQUIRE(S > 0 && S < (1L << 31) && T > 0 && D > 0, "mnn_pitch_extent: S, T and D must be positive, S below 2^31 (got %ld, %d, %d)", S, T, D);
+    MNN_REQUIRE(M >= 1 && M <= 32 && D % M == 0, "mnn_pitch_extent: tracks M = %d must lie in 1..32 and divide D = %d", M, D);
+    MNN_REQUIRE(X && lo && hi, "mnn_pitch_extent: X, lo and hi must not be NULL");
+    hipLaunchKernelGGL(pitch_extent_kernel, dim3((unsigned)S), dim3(WIN_THREADS), 0, (hipStream_t)s, X, T, D, M, moving, lengths, lo, hi);
+    MNN_LAUNCH_CHECK();
+    return MNN_OK;
+}

@@ -61,6 +61,114 @@ def prepare_sampling_inputs(X_train, X_valid, sampling_config, beat_size):
     return intro_songs, save_ids, song_labels
 
 
+# ---- transposition augmentation --------------------------------------------------------------------------------------
+# The reference has no augmentation.  This is the host statement of what `mnn_window_gather_shift` / `mnn_pitch_extent` do on the device
+# (device_data.DeviceDataset): the NumPy path of the driver runs it, and the kernels are tested against it.
+def _moving_mask(moving_tracks, M):
+    """bool [M]: True for the tracks that are transposed (`moving_tracks`: distinct integers in 0..M-1)."""
+    tracks = [int(m) for m in moving_tracks]
+    if len(set(tracks)) != len(tracks) or any(not 0 <= m < M for m in tracks):
+        raise ValueError(f"moving_tracks must be distinct integers in 0..{M - 1}, got {list(moving_tracks)}")
+    mask = np.zeros(M, bool)
+    mask[tracks] = True
+    return mask
+
+
+def moving_bits(moving_tracks, M):
+    """The tracks as the bit mask the kernels take (bit m: track m is transposed)."""
+    return sum(1 << m for m in np.nonzero(_moving_mask(moving_tracks, M))[0].tolist())
+
+
+def transpose_rolls(x, shifts, moving_tracks, pitch_stride=1):
+    """x u8 [B, Tw, P, M] -> the same shape with row b's moving tracks shifted along the pitch axis by shifts[b] * pitch_stride positions:
+    out[b, t, p, m] = x[b, t, p - shifts[b] * pitch_stride, m] where that position lies in 0..P-1, 0 elsewhere (nothing wraps around; a
+    shift of P or more either way leaves zeros); the other tracks are x's.  shifts: B integers.  With the default pitch_stride = 1 they
+    are positions of the pitch axis -- what `Transpose.shifts` returns and the kernel takes."""
+    x = np.asarray(x)
+    if x.ndim != 4:
+        raise ValueError(f"transpose_rolls: x must be [B, Tw, P, M], got shape {x.shape}")
+    B, _, P, M = x.shape
+    shifts = np.asarray(shifts)
+    if shifts.shape != (B,) or not np.issubdtype(shifts.dtype, np.integer):
+        raise ValueError(f"transpose_rolls: shifts must be {B} integers (one per row), got {shifts.dtype} {shifts.shape}")
+    mask = _moving_mask(moving_tracks, M)
+    out = x.copy()
+    if not mask.any():
+        return out
+    out[..., mask] = 0
+    for b in range(B):
+        s = int(shifts[b]) * int(pitch_stride)
+        if abs(s) >= P:
+            continue
+        src, dst = (slice(0, P - s), slice(s, P)) if s >= 0 else (slice(-s, P), slice(0, P + s))
+        out[b][:, dst, mask] = x[b][:, src, mask]          # out[b] is a view: one boolean index over the tracks, assigned in place
+    return out
+
+
+def pitch_extents(X, lengths, moving_tracks):
+    """(lo, hi) int64 [S]: per song of X [S, T, P, M] the smallest and largest pitch position at which a moving track has a non-zero cell
+    in a step t < lengths[song] (lengths None: every step); (P, -1) for a song without such a cell."""
+    X = np.asarray(X)
+    S, T, P, M = X.shape
+    mask = _moving_mask(moving_tracks, M)
+    lengths = np.full(S, T, np.int64) if lengths is None else np.asarray(lengths)
+    lo, hi = np.full(S, P, np.int64), np.full(S, -1, np.int64)
+    for s in range(S):
+        used = np.nonzero(X[s, :max(int(lengths[s]), 0)][..., mask].any(axis=(0, 2)))[0]
+        if used.size:
+            lo[s], hi[s] = used[0], used[-1]
+    return lo, hi
+
+
+class Transpose:
+    """Random transposition of the pitched tracks of a training window: every song is shifted by its own number of semitones, drawn anew
+    each epoch from -max_shift..max_shift and clipped so that none of the song's notes leaves the pitch range.
+
+    max_shift: K >= 1 semitones.  fixed_tracks: the tracks that stay where they are (the drums: track 0 in the LPD-5 order; there is no
+    default guess -- with none given every track moves).  pitch_stride: positions of the pitch axis per semitone (`training.num_pixels`
+    folds n time pixels into the pitch axis, position p * n + px: one semitone is then n positions).
+
+    The shift is a function of (seed, epoch, song) alone -- not of the shuffle, the batch size, the window or the rank -- from a generator
+    of its own: the global np.random stream that `fit` seeds and shuffles with is not touched.  Bound to a dataset's [P, M] at first use."""
+
+    def __init__(self, max_shift, fixed_tracks=(), seed=23, pitch_stride=1):
+        for name, v in (("max_shift", max_shift), ("pitch_stride", pitch_stride)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"Transpose: {name} must be a positive integer, got {v!r}")
+        fixed = list(fixed_tracks)
+        if any(isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) or m < 0 for m in fixed) or len(set(fixed)) != len(fixed):
+            raise ValueError(f"Transpose: fixed_tracks must be distinct track numbers, got {fixed!r}")
+        self.max_shift, self.fixed_tracks, self.seed, self.pitch_stride = int(max_shift), tuple(int(m) for m in fixed), int(seed), int(pitch_stride)
+        self.P = None
+
+    def bind(self, P, M):
+        """Check this augmentation against rolls of P pitch positions and M tracks (ValueError where it does not fit, before any work is
+        done with it), remember P for `shifts`, and return the moving tracks."""
+        if M > 32:
+            raise ValueError(f"Transpose: at most 32 tracks, got {M}")
+        if any(m >= M for m in self.fixed_tracks):
+            raise ValueError(f"Transpose: fixed_tracks {self.fixed_tracks} must lie in 0..{M - 1}")
+        if P % self.pitch_stride != 0:
+            raise ValueError(f"Transpose: pitch_stride = {self.pitch_stride} must divide the {P} positions of the pitch axis")
+        if self.max_shift >= P // self.pitch_stride:
+            raise ValueError(f"Transpose: max_shift = {self.max_shift} must be below the {P // self.pitch_stride} semitones of the pitch axis")
+        self.P = int(P)
+        return tuple(m for m in range(M) if m not in self.fixed_tracks)
+
+    def shifts(self, extents, epoch, P=None):
+        """int32 [S], in positions of the pitch axis (semitones * pitch_stride): the epoch's draw per song, clipped to what the song's
+        extent (lo, hi) -- `pitch_extents` of the moving tracks -- leaves free below and above.  A song without a pitched note keeps its
+        draw, which moves nothing.  P: the positions of the pitch axis (default: what `bind` was given)."""
+        P = self.P if P is None else int(P)
+        if P is None:
+            raise ValueError("Transpose.shifts: the pitch axis is unknown (call bind(P, M) first, or pass P)")
+        lo, hi = (np.asarray(a, np.int64) for a in extents)
+        n = self.pitch_stride
+        raw = np.random.Generator(np.random.PCG64([self.seed, int(epoch)])).integers(-self.max_shift, self.max_shift + 1, size=lo.shape[0])
+        clipped = np.clip(raw, -(lo // n), (P - 1 - hi) // n)
+        return (np.where(hi < 0, raw, clipped) * n).astype(np.int32)
+
+
 # ---- Standard MIDI File writer ---------------------------------------------------------------------------------------
 def _vlq(n):
     out = [n & 0x7F]

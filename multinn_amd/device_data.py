@@ -1,12 +1,14 @@
 """A dataset that lives on the device: the `[songs, steps, pitches, tracks]` piano-rolls of utils/data.py:38-100 uploaded ONCE, and the windows
 of train.py:164-173 cut out of them by one HIP kernel (`ops.window_gather`) instead of a NumPy fancy index + a pageable host-to-device copy
 per step.  Opt-in: `driver.train_epoch` / `evaluate` / `pretrain_encoders` / `fit` take a `DeviceDataset` wherever they take the NumPy array,
-and feed the step the same bytes in the same order.
+and feed the step the same bytes in the same order.  A window may be transposed while it is cut (`data.Transpose` through the driver's
+`augment=`: per-row pitch shifts of the moving tracks, `ops.window_gather_shift`), with `data.transpose_rolls` as the host statement of it.
 """
 import numpy as np
 import torch
 
 from . import ops
+from .data import moving_bits, pitch_extents, transpose_rolls
 
 
 class DeviceDataset:
@@ -59,6 +61,7 @@ class DeviceDataset:
         self._len_dev = torch.from_numpy(lengths.astype(np.int32)).to(device)
         self._x_buf = torch.empty(0, dtype=torch.uint8, device=self.device)
         self._len_buf = torch.empty(0, dtype=torch.int32, device=self.device)
+        self._extents = {}
 
     def _upload(self, X, slab_bytes):
         S, T, P, M = self.shape
@@ -91,12 +94,27 @@ class DeviceDataset:
             raise ValueError(f"DeviceDataset: song_ids must lie in 0..{self.shape[0] - 1}, got {int(ids.min())}..{int(ids.max())}")
         return ids
 
-    def window(self, song_ids, j, Tw, track=None, ids_dev=None):
+    def extents(self, moving_tracks):
+        """Host (lo, hi) int64 [S]: `data.pitch_extents` of every song over its own length and the given tracks (what `data.Transpose`
+        clips its shifts with).  Computed once per set of tracks -- on a ROCm device by `ops.pitch_extent` with one read-back -- and kept."""
+        S, T, P, M = self.shape
+        bits = moving_bits(moving_tracks, M)
+        if bits not in self._extents:
+            if self.device.type == "cuda":
+                lo, hi = ops.pitch_extent(self._X, M, bits, lengths=self._len_dev)
+                both = torch.stack([lo, hi]).cpu().numpy().astype(np.int64)
+                self._extents[bits] = (both[0], both[1])
+            else:
+                self._extents[bits] = pitch_extents(self._X.numpy().reshape(S, T, P, M), self.lengths, moving_tracks)
+        return self._extents[bits]
+
+    def window(self, song_ids, j, Tw, track=None, ids_dev=None, shifts_dev=None, moving=None):
         """(x u8 [B, Tw, P*M] -- or [B, Tw, P], track `track` -- , len int32 [B]) = (X[song_ids, j:j+Tw], clamp(lengths[song_ids] - j, 0, Tw)) on the
         device, written into ONE pair of buffers the dataset owns, grows to the largest window asked for and REUSES for every window:
         consume (or clone) a window before asking for the next one (work already queued on the stream has consumed it).  song_ids: host
         integers, range-checked here; ids_dev: the same ids already on the device as int32 [B] (a slice of one upload per epoch), uploaded
-        here when None."""
+        here when None.  shifts_dev (int32 [B] on the device, with moving = the bit mask of the transposed tracks): row b's moving tracks are
+        shifted by shifts_dev[b] positions along the pitch axis, zeros moving in (`data.transpose_rolls`); None: the plain window."""
         S, T, P, M = self.shape
         ids = self.check_ids(song_ids)
         B, j, Tw = ids.size, int(j), int(Tw)
@@ -109,17 +127,31 @@ class DeviceDataset:
             ids_dev = torch.from_numpy(ids.astype(np.int32)).to(self.device)
         elif ids_dev.dtype != torch.int32 or ids_dev.device != self._X.device or tuple(ids_dev.shape) != (B,) or not ids_dev.is_contiguous():
             raise ValueError(f"DeviceDataset: ids_dev must be the {B} song ids as contiguous int32 on {self._X.device}")
+        if shifts_dev is None:
+            if moving is not None:
+                raise ValueError("DeviceDataset: moving comes with shifts_dev")
+        else:
+            if not isinstance(shifts_dev, torch.Tensor) or shifts_dev.dtype != torch.int32 or shifts_dev.device != self._X.device \
+                    or tuple(shifts_dev.shape) != (B,) or not shifts_dev.is_contiguous():
+                raise ValueError(f"DeviceDataset: shifts_dev must be the {B} rows' shifts as contiguous int32 on {self._X.device}")
+            if M > 32 or isinstance(moving, bool) or not isinstance(moving, int) or not 0 <= moving < (1 << M):
+                raise ValueError(f"DeviceDataset: moving must be a bit mask over the {M} tracks (at most 32), got {moving!r}")
         Dout = P * M if track is None else P
         if self._x_buf.numel() < B * Tw * Dout:
             self._x_buf = torch.empty(B * Tw * Dout, dtype=torch.uint8, device=self.device)
         if self._len_buf.numel() < B:
             self._len_buf = torch.empty(B, dtype=torch.int32, device=self.device)
         x, ln = self._x_buf[:B * Tw * Dout].view(B, Tw, Dout), self._len_buf[:B]
-        if self.device.type == "cuda":
+        if self.device.type == "cuda" and shifts_dev is not None:
+            ops.window_gather_shift(self._X, ids_dev, j, Tw, x, shifts_dev, M, moving, lengths=self._len_dev, out_len=ln, track=track)
+        elif self.device.type == "cuda":
             ops.window_gather(self._X, ids_dev, j, Tw, x, lengths=self._len_dev, out_len=ln, track=track, tracks=M)
         else:
             idx = ids_dev.long()
             w = self._X[idx, j:j + Tw]
+            if shifts_dev is not None:
+                tracks = [m for m in range(M) if moving >> m & 1]
+                w = torch.from_numpy(transpose_rolls(w.numpy().reshape(B, Tw, P, M), shifts_dev.numpy(), tracks)).view(B, Tw, P * M)
             x.copy_(w if track is None else w.view(B, Tw, P, M)[..., track])
             ln.copy_((self._len_dev[idx] - j).clamp(0, Tw))
         return x, ln

@@ -126,22 +126,59 @@ def _host_only(drain_every):
         raise ValueError("drain_every batches the loss read-backs of a DeviceDataset; a NumPy X reads every loss as it is produced")
 
 
-def _dataset_windows(ds, lengths, ids, batch_size, piece_size):
+class _Augment:
+    """A data.Transpose bound to one training set for one epoch: the moving tracks (as a list and as the kernels' bit mask) and the epoch's
+    shift per song (int32 [S], positions of the pitch axis).  The shifts are drawn once, here; nothing of the global np.random is used."""
+
+    def __init__(self, augment, X, lengths, epoch):
+        from .data import Transpose, moving_bits, pitch_extents
+        if not isinstance(augment, Transpose):
+            raise ValueError(f"augment must be a data.Transpose or None, got {type(augment).__name__}")
+        P, M = X.shape[2:]
+        self.tracks = augment.bind(P, M)
+        self.bits = moving_bits(self.tracks, M)
+        ds = _dataset(X)
+        if ds is not None:
+            extents = ds.extents(self.tracks)
+        else:                                             # a NumPy X: computed once per array and lengths, kept on the Transpose
+            kept = getattr(augment, "_host_extents", None)
+            if kept is None or kept[0] is not X or not np.array_equal(kept[1], lengths):
+                kept = augment._host_extents = (X, np.array(lengths), pitch_extents(X, lengths, self.tracks))
+            extents = kept[2]
+        self.shifts = augment.shifts(extents, epoch, P)
+
+    def apply(self, xb, song_ids):
+        """The NumPy path: the fancy-indexed window [B, Tw, P, M], transposed."""
+        from .data import transpose_rolls
+        return transpose_rolls(xb, self.shifts[song_ids], self.tracks)
+
+
+def _dataset_windows(ds, lengths, ids, batch_size, piece_size, shifts=None):
     """iter_windows over a DeviceDataset, with the song ids of the WHOLE epoch uploaded once (int32, the windows' ids back to back) in front
-    of the first step: yields None, or (song_ids, j, max_length, clipped_lengths, ids_dev) with ids_dev the window's slice of that upload."""
+    of the first step: yields None, or (song_ids, j, max_length, clipped_lengths, ids_dev, shifts_dev) with ids_dev the window's slice of
+    that upload.  shifts (int32 [S], a shift per song) ride in the same upload, laid out like the ids behind them, and shifts_dev is the
+    window's slice of those; None without shifts."""
     if lengths is not None and not np.array_equal(np.asarray(lengths), ds.lengths):
         raise ValueError("the lengths passed beside a DeviceDataset differ from the dataset's own (pass None, or the ones it was built with)")
     if len(ids):
         ds.check_ids(ids)                                 # before they index the host lengths
     windows = list(iter_windows(ids, ds.lengths, ds.shape[1], batch_size, piece_size))
     real = [w[0] for w in windows if w is not None]
-    ids_dev, at = ds.upload_ids(np.concatenate(real)) if real else None, 0
+    shifts_dev = None
+    if shifts is None or not real:
+        ids_dev, at = ds.upload_ids(np.concatenate(real)) if real else None, 0
+    else:
+        import torch
+        row_ids = np.concatenate(real)
+        both = torch.from_numpy(np.stack([row_ids, shifts[row_ids]]).astype(np.int32)).to(ds.device)
+        (ids_dev, shifts_dev), at = both, 0
     for w in windows:
         if w is None:
             yield None
             continue
-        yield w + (ids_dev[at:at + len(w[0])],)
-        at += len(w[0])
+        n = len(w[0])
+        yield w + (ids_dev[at:at + n], None if shifts_dev is None else shifts_dev[at:at + n])
+        at += n
 
 
 class LossRing:
@@ -182,15 +219,18 @@ class LossRing:
             self.sink(value, note)
 
 
-def _train_epoch_dataset(generator, ds, lengths, ids, batch_size, piece_size, optimizer, loss_accum, stats, lr, drain_every):
+def _train_epoch_dataset(generator, ds, lengths, ids, batch_size, piece_size, optimizer, loss_accum, stats, lr, drain_every, aug=None):
     """train_epoch over a DeviceDataset: the same windows in the same order, cut out of the dataset on its device; the same step."""
     ring = LossRing(lambda value, _: loss_accum.update(value), drain_every=drain_every)
-    for w in _dataset_windows(ds, lengths, ids, batch_size, piece_size):
+    for w in _dataset_windows(ds, lengths, ids, batch_size, piece_size, None if aug is None else aug.shifts):
         if w is None:
             stats.new_step()
             continue
-        song_ids, j, max_len, len_batch, ids_dev = w
-        xb, lb = ds.window(song_ids, j, max_len, ids_dev=ids_dev)
+        song_ids, j, max_len, len_batch, ids_dev, shifts_dev = w
+        if aug is None:
+            xb, lb = ds.window(song_ids, j, max_len, ids_dev=ids_dev)
+        else:
+            xb, lb = ds.window(song_ids, j, max_len, ids_dev=ids_dev, shifts_dev=shifts_dev, moving=aug.bits)
         xb = xb.view(xb.shape[0], max_len, *ds.shape[2:])             # [B, Tw, P, M], what the NumPy path feeds
         full = bool((len_batch == max_len).all())
         lb = None if full else lb
@@ -204,20 +244,25 @@ def _train_epoch_dataset(generator, ds, lengths, ids, batch_size, piece_size, op
     return loss_accum.loss()
 
 
-def train_epoch(generator, X, lengths, ids, batch_size, piece_size, optimizer, loss_accum, stats, lr=None, device=None, drain_every=None):
+def train_epoch(generator, X, lengths, ids, batch_size, piece_size, optimizer, loss_accum, stats, lr=None, device=None, drain_every=None,
+                augment=None):
     """One epoch of train.py:164-194.  X uint8 [S,T,P,M] (numpy); every window starts from a ZERO rnn state.
     X may be a DeviceDataset instead (lengths: None or its own; `device` is the dataset's): the windows are cut out of it on the device and
-    the losses are read back in one batch at the end of the epoch (LossRing), or every `drain_every` steps."""
+    the losses are read back in one batch at the end of the epoch (LossRing), or every `drain_every` steps.
+    augment (a data.Transpose, or None): every song's moving tracks are transposed by the shift it draws for (its seed, stats.epoch, song)
+    -- inside the gather of a DeviceDataset, by data.transpose_rolls on the NumPy path; both feed the step the same bytes."""
     import torch
+    aug = None if augment is None else _Augment(augment, X, lengths, stats.epoch)
     if _dataset(X) is not None:
-        return _train_epoch_dataset(generator, X, lengths, ids, batch_size, piece_size, optimizer, loss_accum, stats, lr, drain_every)
+        return _train_epoch_dataset(generator, X, lengths, ids, batch_size, piece_size, optimizer, loss_accum, stats, lr, drain_every, aug)
     _host_only(drain_every)
     for w in iter_windows(ids, lengths, X.shape[1], batch_size, piece_size):
         if w is None:
             stats.new_step()
             continue
         song_ids, j, max_len, len_batch = w
-        xb = torch.from_numpy(np.ascontiguousarray(X[song_ids, j:j + max_len])).to(device or "cuda")
+        xw = X[song_ids, j:j + max_len]
+        xb = torch.from_numpy(np.ascontiguousarray(xw if aug is None else aug.apply(xw, song_ids))).to(device or "cuda")
         full = bool((len_batch == max_len).all())
         lb = None if full else torch.from_numpy(len_batch).to(xb.device)
         run = _captured_step(generator, xb, optimizer, lr, lengths=lb)
@@ -341,10 +386,20 @@ def check_recurrences(model):
 
 
 def fit(generator, optimizer, X_train, len_train, X_valid, len_valid, training_config, logs_config, dirs, stats=None, beat_size=4,
-        save_best_only=False, log=print):
+        save_best_only=False, log=print, pitch_stride=1):
     """train.py:150-282: epochs, shuffling (np.random.seed(epoch)), evaluation, best / last checkpoints,
-    early stopping after ``early_stopping`` idle epochs."""
+    early stopping after ``early_stopping`` idle epochs.
+    training_config["transpose"] (optional, a mapping {max_shift, fixed_tracks}): the TRAINING windows are transposed (data.Transpose,
+    seeded with random_seed; pitch_stride: positions of the pitch axis per semitone, `num_pixels` in `main`); validation never is."""
     stats = stats or TrainingStats()
+    augment = None
+    if training_config.get("transpose") is not None:
+        from .data import Transpose
+        tp = training_config["transpose"]
+        if not isinstance(tp, dict) or "max_shift" not in tp or set(tp) - {"max_shift", "fixed_tracks"}:
+            raise ValueError(f"training.transpose must be a mapping {{max_shift, fixed_tracks}}, got {tp!r}")
+        augment = Transpose(tp["max_shift"], tuple(tp.get("fixed_tracks") or ()), seed=training_config["random_seed"], pitch_stride=pitch_stride)
+        augment.bind(*X_train.shape[2:])
     batch_size = training_config["batch_size"]
     piece_size = int(training_config["piece_size"] * beat_size)
     ids = np.arange(X_train.shape[0])
@@ -356,7 +411,11 @@ def fit(generator, optimizer, X_train, len_train, X_valid, len_valid, training_c
         t0 = time.time()
         np.random.shuffle(ids)
         acc.clear()
-        train_epoch(generator, X_train, len_train, ids, batch_size, piece_size, optimizer, acc, stats, training_config.get("learning_rate"))
+        if augment is None:
+            train_epoch(generator, X_train, len_train, ids, batch_size, piece_size, optimizer, acc, stats, training_config.get("learning_rate"))
+        else:
+            train_epoch(generator, X_train, len_train, ids, batch_size, piece_size, optimizer, acc, stats, training_config.get("learning_rate"),
+                        augment=augment)
         check_recurrences(generator)            # a persistent launch that gave up would have trained on garbage: raise before validating / saving
         loglik_val = evaluate(generator, X_valid, len_valid, batch_size, piece_size) if logs_config.get("evaluate_epochs", 1) else acc.loss()
         log(f" epoch: {epoch:3d} (steps: {stats.steps:5d}) time: {time.time() - t0:.2f}s{acc} valid nll: {loglik_val:.4f}")
@@ -378,12 +437,13 @@ def fit(generator, optimizer, X_train, len_train, X_valid, len_valid, training_c
     return stats
 
 
-def pretrain_encoders(encoders, X_train, len_train, training_config, beat_size=4, lr=None, device=None, log=None):
+def pretrain_encoders(encoders, X_train, len_train, training_config, beat_size=4, lr=None, device=None, log=None, augment=None):
     """train_encoders.py:118-200: greedy layer-wise pre-training of the per-track (or joint) DBN encoders.  For every layer, for
     `epochs` epochs, every shuffled song batch and every piece of `piece_size` beats: the encoder is built on the window of its
     track (`x[..., i]` for track i, all tracks flattened for a single joint encoder) and `encoder.train(None, lr, layer)` runs one
     CD-k update of that layer's RBM fed with the sampled codes of the layers below (dbn_encoder.py:192-240).
     X_train uint8 [songs, T, P, M] (numpy), or a DeviceDataset (len_train: None or its own): track i's windows are then gathered on its device.
+    augment (a data.Transpose, or None): train_epoch's, with the loop's own `epoch`; a per-track encoder gets its track's single-track form.
     Returns {(encoder index, layer): [mean reconstruction cost per epoch]}."""
     import torch
     batch_size = training_config['batch_size']
@@ -399,10 +459,11 @@ def pretrain_encoders(encoders, X_train, len_train, training_config, beat_size=4
                 np.random.seed(epoch)                           # train_encoders.py:134-135
                 np.random.shuffle(ids)
                 acc = LossAccumulator()
+                aug = None if augment is None else _Augment(augment, X_train, len_train, epoch)
                 if ds is None:
                     windows = iter_windows(ids, len_train, X_train.shape[1], batch_size, piece_size)
                 else:
-                    windows = _dataset_windows(ds, len_train, ids, batch_size, piece_size)
+                    windows = _dataset_windows(ds, len_train, ids, batch_size, piece_size, None if aug is None else aug.shifts)
                     ring = LossRing(lambda value, _, acc=acc: acc.update(value))
                 for w in windows:
                     if w is None:
@@ -410,10 +471,12 @@ def pretrain_encoders(encoders, X_train, len_train, training_config, beat_size=4
                     song_ids, j, max_len = w[:3]
                     if ds is None:
                         xb = X_train[song_ids, j:j + max_len]
+                        xb = xb if aug is None else aug.apply(xb, song_ids)
                         xb = xb[..., e_i] if len(encoders) > 1 else xb.reshape(xb.shape[0], xb.shape[1], -1)
                         xt = torch.from_numpy(np.ascontiguousarray(xb)).to(device or "cuda")
                     else:
-                        xt, _ = ds.window(song_ids, j, max_len, track=e_i if len(encoders) > 1 else None, ids_dev=w[4])
+                        shifted = {} if aug is None else dict(shifts_dev=w[5], moving=aug.bits)
+                        xt, _ = ds.window(song_ids, j, max_len, track=e_i if len(encoders) > 1 else None, ids_dev=w[4], **shifted)
                     enc.build(x=xt, is_train=True, mode="train")
                     _, _, metrics, _, _ = enc.train(None, lr, layer=layer)
                     if ds is None:
@@ -508,7 +571,7 @@ def main(argv=None):
         from .device_data import DeviceDataset
         X_train, X_valid = DeviceDataset(X_train, lengths[:nt]), DeviceDataset(X_valid, lengths[nt:nt + nv])
     fit(gen, AdamOptimizer(tr["learning_rate"]), X_train, lengths[:nt], X_valid, lengths[nt:nt + nv], tr, config["logs"], dirs, stats,
-        beat_size=d["beat_resolution"] / npx, save_best_only=a.save_best_only)
+        beat_size=d["beat_resolution"] / npx, save_best_only=a.save_best_only, pitch_stride=npx)
 
 
 if __name__ == "__main__":

@@ -192,6 +192,51 @@ def window_gather(X, ids, j, Tw, out, lengths=None, out_len=None, track=None, tr
     return out
 
 
+def _moving_mask(moving, tracks, D, what):
+    _req(isinstance(tracks, int) and 1 <= tracks <= 32 and D % tracks == 0, f"{what}: tracks = {tracks} must lie in 1..32 and divide D = {D}")
+    _req(isinstance(moving, int) and not isinstance(moving, bool) and 0 <= moving < (1 << tracks), f"{what}: moving must be a bit mask over {tracks} tracks, got {moving!r}")
+    return moving
+
+
+def window_gather_shift(X, ids, j, Tw, out, shifts, tracks, moving, lengths=None, out_len=None, track=None):
+    """window_gather with a pitch shift per output row (mnn_window_gather_shift): X u8 [S, T, P * tracks], shifts int32 [B] on X's device,
+    moving a bit mask (bit m: track m is transposed).  An element of a moving track reads pitch p - shifts[b] of its track, 0 where that
+    leaves 0..P-1; the other tracks are the plain gather's.  track = m: that track alone, out u8 [B, Tw, P]."""
+    _req(X.dtype == torch.uint8 and X.dim() == 3 and X.is_contiguous(), "window_gather_shift: X must be contiguous u8 [S,T,D]")
+    S, T, D = X.shape
+    _req(ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous() and ids.numel() > 0, "window_gather_shift: ids int32 [B]")
+    B = ids.numel()
+    moving = _moving_mask(moving, tracks, D, "window_gather_shift")
+    _req(isinstance(shifts, torch.Tensor) and shifts.dtype == torch.int32 and tuple(shifts.shape) == (B,) and shifts.is_contiguous()
+         and shifts.device == X.device, f"window_gather_shift: shifts must be contiguous int32 [{B}] on {X.device}")
+    if track is None:
+        e0, es, Dout = 0, 1, D
+    else:
+        _req(0 <= track < tracks, f"window_gather_shift: track {track} of {tracks} tracks over D = {D}")
+        e0, es, Dout = int(track), int(tracks), D // tracks
+    _req(out.dtype == torch.uint8 and tuple(out.shape) == (B, Tw, Dout) and out.is_contiguous(), f"window_gather_shift: out must be contiguous u8 [{B},{Tw},{Dout}]")
+    _req(lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == S and lengths.is_contiguous()), "window_gather_shift: lengths int32 [S]")
+    _req(out_len is None or (lengths is not None and out_len.dtype == torch.int32 and out_len.numel() == B and out_len.is_contiguous()),
+         "window_gather_shift: out_len int32 [B], with lengths")
+    call("mnn_window_gather_shift", _stream(), _ptr(X), S, T, D, _ptr(ids), B, int(j), int(Tw), e0, es, Dout, _ptr(lengths), _ptr(out), _ptr(out_len),
+         _ptr(shifts), tracks, moving)
+    return out
+
+
+def pitch_extent(X, tracks, moving, lengths=None):
+    """(lo, hi) int32 [S] on X's device (mnn_pitch_extent): per song of X u8 [S, T, P * tracks] the smallest and largest pitch at which a moving
+    track (bit mask `moving`) has a non-zero cell in a step t < lengths[song] (every step without lengths); (P, -1) for a song with none."""
+    _req(X.dtype == torch.uint8 and X.dim() == 3 and X.is_contiguous(), "pitch_extent: X must be contiguous u8 [S,T,D]")
+    S, T, D = X.shape
+    moving = _moving_mask(moving, tracks, D, "pitch_extent")
+    _req(lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == S and lengths.is_contiguous() and lengths.device == X.device),
+         "pitch_extent: lengths int32 [S] on X's device")
+    lo = torch.empty(S, dtype=torch.int32, device=X.device)
+    hi = torch.empty(S, dtype=torch.int32, device=X.device)
+    call("mnn_pitch_extent", _stream(), _ptr(X), S, T, D, tracks, moving, _ptr(lengths), _ptr(lo), _ptr(hi))
+    return lo, hi
+
+
 # ------------------------------------------------------------------------------------------------
 def lstm_pack_weights(W, b, n_in, units, wx_t, wh_t, wh_p, wx_p, bias_p):
     _req(W.dtype == torch.float32 and W.shape == (n_in + units, 4 * units) and W.is_contiguous(), "pack: W f32 [(in+u),4u]")
