@@ -734,6 +734,26 @@ int mnn_step_increment(mnn_stream_t s, int32_t* step_dev, const float* sumsq, fl
                                         `grow_after` applied steps in a row; the owner of the backward pass multiplies its gradient seed by m and the
                                         finished gradient by 1 / m (both read on the device: a captured step follows it) */,
                        int32_t* ls_good /* [1]: applied steps since the last change */, int grow_after);
+/* Grouped forms (additions without a version bump; csrc/opt_multi.hip): the three launches above for 1..16 flat stores behind ONE global
+ * norm in one launch each -- the optimiser step of a mode that trains several generators on one loss.  The job table is copied into the
+ * kernel's argument block by the call (the host array may be freed afterwards).  step_dev is required: the step count is *step_dev + 1, read
+ * on the device.  For the same *sumsq every job's theta / m / v / skipped are bit for bit what mnn_clip_adam_step leaves, and step_dev /
+ * ls_dyn / ls_good what mnn_step_increment leaves.  16-byte accesses per job whose own theta / grad / m / v are 16-byte aligned.
+ *   mnn_sumsq_multi: out[0] += sum over the jobs of sum(grad^2) (reads grad and n only).
+ *   mnn_clip_adam_step_multi: m, v may be NULL when sgd != 0; skipped may be NULL.
+ *   mnn_step_increment_multi: ls_dyn and ls_good come together or not at all, per job; grow_after > 0 where a job has them.
+ * mnn_segments_copy: dst[0, n) = src[0, n) for 1..16 segments of f32 words in one launch (the pack and the unpack of a gradient arena that
+ *   several stores exchange in ONE all-reduce); segments must not overlap one another. */
+typedef struct {
+    float* theta; float* grad; float* m; float* v; long n;
+    int32_t* step_dev; int32_t* skipped; float* ls_dyn; int32_t* ls_good;
+} mnn_opt_job;
+int mnn_sumsq_multi(mnn_stream_t s, int njobs, const mnn_opt_job* jobs, float* out);
+int mnn_clip_adam_step_multi(mnn_stream_t s, int njobs, const mnn_opt_job* jobs, const float* sumsq, float clip_norm, float lr, float beta1,
+                             float beta2, float eps, int sgd);
+int mnn_step_increment_multi(mnn_stream_t s, int njobs, const mnn_opt_job* jobs, const float* sumsq, float clip_norm, int grow_after);
+typedef struct { const float* src; float* dst; long n; } mnn_copy_seg;
+int mnn_segments_copy(mnn_stream_t s, int nsegs, const mnn_copy_seg* segs);
 int mnn_bias_grad(mnn_stream_t s, const float* dY, int rows, int cols, int ld, float* db, int accumulate);
 int mnn_fill_f32(mnn_stream_t s, float* x, long n, float value);
 /* One pass over the f32 gradient block dY[rows, cols_c] of the dense layer (rnn_estimator.py:205-215's tf.gradients through the

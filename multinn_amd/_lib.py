@@ -113,6 +113,16 @@ class RbmFreeEnergyJob(C.Structure):
     _fields_ = [("v", _p), ("W", _p), ("bh", _p), ("bv", _p), ("F", _p), ("p_h", _p)]
 
 
+class OptJob(C.Structure):
+    """mnn_opt_job (include/multinn_hip.h)."""
+    _fields_ = [("theta", _p), ("grad", _p), ("m", _p), ("v", _p), ("n", _l), ("step_dev", _p), ("skipped", _p), ("ls_dyn", _p), ("ls_good", _p)]
+
+
+class CopySeg(C.Structure):
+    """mnn_copy_seg (include/multinn_hip.h)."""
+    _fields_ = [("src", _p), ("dst", _p), ("n", _l)]
+
+
 class ScanLstmLayer(C.Structure):
     """mnn_scan_lstm_layer (include/multinn_hip.h)."""
     _fields_ = [("W", _p), ("bias", _p), ("units", _i)]
@@ -233,6 +243,12 @@ SIGNATURES["mnn_window_gather"] = (_i, [_p, _p, _l, _i, _i, _p, _i, _i, _i, _i, 
 # transposition inside the gather (additions without a version bump): the gather with (shifts, M, moving) behind; the songs' pitch extents
 SIGNATURES["mnn_window_gather_shift"] = (_i, SIGNATURES["mnn_window_gather"][1] + [_p, _i, _u32])
 SIGNATURES["mnn_pitch_extent"] = (_i, [_p, _p, _l, _i, _i, _i, _u32, _p, _p, _p])
+# grouped optimiser launches and the gradient arena's segment copy (additions without a version bump): const mnn_opt_job* / mnn_copy_seg* tables
+SIGNATURES["mnn_sumsq_multi"] = (_i, [_p, _i, _p, _p])
+SIGNATURES["mnn_clip_adam_step_multi"] = (_i, [_p, _i, _p, _p, _f, _f, _f, _f, _f, _i])
+SIGNATURES["mnn_step_increment_multi"] = (_i, [_p, _i, _p, _p, _f, _i])
+SIGNATURES["mnn_segments_copy"] = (_i, [_p, _i, _p])
+OPT_MULTI_MAX_JOBS = 16    # jobs / segments per launch of the four entries above
 PARTICLES_MAX = 1024      # mnn_sir.particles
 TEMPS_MAX = 8              # MNN_TEMPS_MAX
 REDRAWS_MAX = 255          # mnn_redraw.tries

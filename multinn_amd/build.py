@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmultinn_hip.so")
-SOURCES = ["gemm.hip", "gemm_bres.hip", "lstm_seq.hip", "lstm_persist.hip", "lstm_rowpar.hip", "lstm_resident.hip", "lstm_cluster.hip", "elementwise.hip", "window.hip", "nade.hip", "nade_mfma.hip", "nade_is.hip", "nade_sir.hip", "rbm.hip", "rbm_multi.hip", "rbm_ais.hip", "musical.hip", "det_step.hip", "comm.hip"]
+SOURCES = ["gemm.hip", "gemm_bres.hip", "lstm_seq.hip", "lstm_persist.hip", "lstm_rowpar.hip", "lstm_resident.hip", "lstm_cluster.hip", "elementwise.hip", "opt_multi.hip", "window.hip", "nade.hip", "nade_mfma.hip", "nade_is.hip", "nade_sir.hip", "rbm.hip", "rbm_multi.hip", "rbm_ais.hip", "musical.hip", "det_step.hip", "comm.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wno-unused-result"]
 # per-source additions.  lstm_resident.hip: MFMA results in VGPRs (the pointwise reads them there: no v_accvgpr_read per accumulator register),
 # which leaves the AGPRs to the recurrent weights the matrix cores read in place

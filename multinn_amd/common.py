@@ -60,13 +60,15 @@ def _warm_up(fn, n=1):
     cur.wait_stream(side)
 
 
-def capture_train_step(feed, step, warmup, models, stores, split=False, fwd_bwd=None, opt=None, error_mode="global"):
+def capture_train_step(feed, step, warmup, models, stores, split=False, fwd_bwd=None, opt=None, error_mode="global", reduce=None):
     """The captured optimiser step of every graphed_* train entry: `warmup` eager step()s on a side stream, then hipGraph(s) of the step.
     Returns run(*a, **kw) -> loss: feed(*a, **kw) copies new inputs into the static ones, then the replay.  One rank: ONE graph of step()
     (capture_error_mode=error_mode).  split (data parallel): a graph of fwd_bwd() -> loss and one of opt() (clip + Adam, no all-reduce) in its
     pool (run.opt_graph); each replay all-reduces the flat gradients eagerly between them, so nothing of RCCL is captured (thread_local: the
     process group's watchdog thread may touch the runtime while this thread captures).  The 16-bit packed weights of `models` are marked
     stale before the capture (the graph packs them itself, whatever ran before) and after it (the packed copies live in the graph's pool).
+    reduce (split only, optional): the eager work of a replay between the two graphs, in place of the all-reduce of every store's gradient
+    -- a mode with several stores exchanges them in ONE collective of its gradient arena.
     stores() (asked after the warm-up, which may create some): the ParamStores whose host mirror store.step follows the device counter.
     run holds no model: one cached on its model (driver._captured_step) would make it cyclic garbage (graph_capture)."""
     from .training import allreduce_flat, setup_cabi_comm
@@ -92,8 +94,11 @@ def capture_train_step(feed, step, warmup, models, stores, split=False, fwd_bwd=
         feed(*a, **kw)
         graph.replay()
         if opt_graph is not None:
-            for st in mirror:
-                allreduce_flat(st.grad)
+            if reduce is not None:
+                reduce()
+            else:
+                for st in mirror:
+                    allreduce_flat(st.grad)
             opt_graph.replay()
         for st in mirror:
             st.step += 1

@@ -26,7 +26,7 @@ import weakref
 
 import torch
 
-from .common import Model, capture_train_step, given_codes, given_tracks, prompt_lengths, refuse_particles, sampling_max_notes, sampling_particles, sampling_redraws, sampling_temperature
+from .common import Model, _warm_up, capture_train_step, given_codes, given_tracks, prompt_lengths, refuse_particles, sampling_max_notes, sampling_particles, sampling_redraws, sampling_temperature
 from .encoders import PassEncoder, DBNEncoder
 from .generators import RnnNade, RnnRBM, RnnMultiNADE, RnnMultiRBM
 from . import ops
@@ -697,12 +697,21 @@ class MultINNCore(Model):
         values (dropout / Gibbs seeds, Adam's step) are read from each store's device-side counter, so every replay is the next step.
         lengths (int32 [B], optional): capture the RAGGED step; the graph holds a static copy of the lengths and everything derived from them
         (row weights, valid-row counts, f16 loss scales, the compaction of the NADE generators' rows) is computed on the device inside the graph
-        (`RnnEstimator.ragged_on_device`), so one capture serves every later `run(x, lengths)`.  Returns run(x=None, lengths=None) -> loss."""
-        from .training import dp_active
-        if dp_active():
-            raise NotImplementedError("graphed_train_step of a mode is single-rank (the generators' own captured steps handle data parallelism)")
-        sx = x.clone()
+        (`RnnEstimator.ragged_on_device`), so one capture serves every later `run(x, lengths)`.  Returns run(x=None, lengths=None) -> loss.
+        Data parallel (training.dp_active(); the caller shards the batch and sets model.row0 = rank * B_local, as for RnnNade): TWO graphs,
+        as the single generators' steps -- build + backward passes + the pack of the gradient arena | clip + Adam over all stores -- with
+        ONE eager allreduce_flat of the arena between them per replay (common.capture_train_step(split=True); run.opt_graph).  Full-length
+        windows only: a ragged window weighs its rows by 1 / (valid rows of ALL ranks), so that total would have to be all-reduced in front
+        of the replay and fed to every generator's row weights and compaction header -- not built; ragged windows train eagerly there.
+        The joint, jamming and composer modes only: the feedback modes' captured step is not verified under data parallelism and is refused."""
+        from . import training
+        from .training import dp_active, GradArena
         ragged = lengths is not None
+        if dp_active() and ragged:
+            raise NotImplementedError("graphed_train_step(lengths=) of a mode is single-rank: under data parallelism the valid-row total of all "
+                                      "ranks would have to be all-reduced in front of every replay and fed to each generator's row weights "
+                                      "and compaction header; train ragged windows with train_step there")
+        sx = x.clone()
         sl = lengths.to(device=x.device, dtype=torch.int32).clone() if ragged else None
         if ragged:
             for g in self._generators:
@@ -721,15 +730,56 @@ class MultINNCore(Model):
 
         # warm-up steps are REAL optimiser steps: variables, persistent-kernel attributes and workspaces must exist before the capture.
         # warmup = 0 is for a caller that has just run this very step eagerly (driver._captured_step: the capture then executes nothing)
-        run = capture_train_step(feed, lambda: self.train_step(sx, sl, optimizer, lr), warmup, self._generators, self._all_stores)
-        run.ragged = ragged
+        step = lambda: self.train_step(sx, sl, optimizer, lr)
+        if not dp_active():
+            run = capture_train_step(feed, step, warmup, self._generators, self._all_stores)
+            run.ragged = ragged
+            return run
+        if self._mode not in ("joint", "jamming", "composer"):
+            raise NotImplementedError(f"graphed_train_step of the {self._mode} mode under data parallelism is not verified (its eager "
+                                      "data-parallel step is): train with train_step there")
+        # the warm-up runs HERE, in front of the arena: the arena needs every store's variables, and it must not be laid out (allocated and
+        # zero-filled) inside the capture -- it is cached on the model and later eager steps exchange through it
+        training.setup_cabi_comm()
+        _warm_up(step, warmup)
+        arena = GradArena.cached(self, self._step_stores())         # (run holds the arena, not the model)
+
+        def fwd_bwd():
+            self.build(sx, lengths=None, is_train=True, mode="train")
+            self._backward_pass(optimizer, lr)
+            arena.pack()
+            return self.generator_loss()
+
+        def opt():
+            arena.unpack()
+            self._optimizer_pass(optimizer, lr)
+
+        run = capture_train_step(feed, step, 0, self._generators, self._all_stores, split=True, fwd_bwd=fwd_bwd, opt=opt,
+                                 reduce=lambda: training.allreduce_flat(arena.flat))
+        run.ragged = False
         return run
+
+    def _step_stores(self):
+        """The stores the mode's optimiser step updates, in the order of its gradient arena."""
+        return [self._generators[0].store]
+
+    def _backward_pass(self, optimizer, lr):
+        """What train_generators runs in front of its optimiser step (joint, composer: the one generator's backward pass)."""
+        self._generators[0].backward()
+
+    def _optimizer_pass(self, optimizer, lr):
+        """train_generators' optimiser step on gradients that have been exchanged already (joint, composer: Generator.train's)."""
+        from .training import compute_gradients
+        g = self._generators[0]
+        g._grad_sumsq = compute_gradients(optimizer, g.store, g.clip_norm, lr, reduce=False)
+        g._packed_step = -1
 
     def capturable(self, shape, ragged):
         """Whether the driver may train windows of this shape as replays of graphed_train_step (driver._captured_step), full-length or ragged:
-        the modes whose captured step is tested (joint, jamming, composer), on one rank, once every generator's variables exist."""
+        the modes whose captured step is tested (joint, jamming, composer), once every generator's variables exist.  Under data parallelism
+        full-length windows only (the two-graph step of graphed_train_step); ragged windows train eagerly there."""
         from .training import dp_active
-        if not (self._mode in ("joint", "jamming", "composer") and not dp_active() and
+        if not (self._mode in ("joint", "jamming", "composer") and not (ragged and dp_active()) and
                 all(getattr(g, "store", None) is not None and g.store.theta is not None for g in self._generators)):
             return False
         # a learned initial state off the resident / cluster kernels trains on the launch-per-timestep path, eagerly (RnnNade.capturable)
@@ -1003,7 +1053,41 @@ class MultINNJamming(MultIEncoderNN):
         pre-training call without separate losses is the visible-bias init ops plus an ordinary step on the mean track loss) -- ONE clipped
         step on the mean track loss over all generators' (and the feedback module's) variables.  The per-track weight of that mean (1/M) is
         applied to the gradient seed at build time from `self.separate_losses`; an argument that differs from the attribute is honoured by
-        rescaling the finished gradients (everything downstream of the seed is linear in it)."""
+        rescaling the finished gradients (everything downstream of the seed is linear in it).
+        The two halves are methods of their own (_backward_generators, _joint_step): the captured data-parallel step puts the one
+        all-reduce of the step between them (graphed_train_step).  The separate_losses=True step -- one clipped step and one all-reduce per
+        generator -- stays eager under data parallelism."""
+        init_ops, update_ops, metrics, metrics_upd, summaries = self._backward_generators(optimizer, lr, pretrain, separate_losses)
+        if not separate_losses:
+            self._joint_step(optimizer, lr)
+            update_ops = []                         # multinn_jamming.py:237: the joint step REPLACES the collected update ops (it has run)
+        return init_ops, update_ops, metrics, metrics_upd, summaries
+
+    def _joint_stores(self):
+        return [g.store for g in self.generators] + self._extra_stores()
+
+    def _step_stores(self):
+        return self._joint_stores()
+
+    def _backward_pass(self, optimizer, lr):
+        self._backward_generators(optimizer, lr)
+
+    def _optimizer_pass(self, optimizer, lr):
+        self._joint_step(optimizer, lr, reduce=False)
+
+    def _joint_step(self, optimizer, lr, reduce=True):
+        """ONE clipped step over all generators' (and the feedback module's) stores: under data parallelism one all-reduce of their gradient
+        arena (reduce=False: the caller has exchanged the gradients), then three grouped launches."""
+        from .training import GradArena, dp_active
+        stores = self._joint_stores()
+        arena = GradArena.cached(self, stores) if reduce and dp_active() else None      # (one rank: no exchange, no arena)
+        self._grad_sumsq = compute_gradients_multi(optimizer, stores, self.clip_norm, lr, reduce=reduce, arena=arena)
+        for g in self.generators:
+            g._packed_step = -1
+
+    def _backward_generators(self, optimizer, lr, pretrain=False, separate_losses=False):
+        """The part of _train_generators in front of the joint step: every generator's backward pass (side by side where they were built in
+        lockstep), the per-generator steps of separate_losses, and -- without separate losses -- the feedback module's backward."""
         M = self.num_tracks
         built_scale = 1.0 if self.separate_losses else 1.0 / M
         want_scale = 1.0 if separate_losses else 1.0 / M
@@ -1035,11 +1119,6 @@ class MultINNJamming(MultIEncoderNN):
         metrics, metrics_upd, summaries = self._combine_track_metrics(tm, tu, ts, global_scope=f"metrics/{self.generators[0].name}/global/")
         if not separate_losses:
             self._backward_extra()
-            stores = [g.store for g in self.generators] + self._extra_stores()
-            self._grad_sumsq = compute_gradients_multi(optimizer, stores, self.clip_norm, lr)
-            for g in self.generators:
-                g._packed_step = -1
-            update_ops = []                         # multinn_jamming.py:237: the joint step REPLACES the collected update ops (it has run)
         return init_ops, update_ops, metrics, metrics_upd, summaries
 
 

@@ -1349,6 +1349,88 @@ def step_increment(step_dev, sumsq_buf=None, clip_norm=0.0, ls_dyn=None, ls_good
     call("mnn_step_increment", _stream(), _ptr(step_dev), _ptr(sumsq_buf), float(clip_norm), _ptr(ls_dyn), _ptr(ls_good), int(grow_after))
 
 
+OPT_MULTI_MAX_JOBS = _lib.OPT_MULTI_MAX_JOBS
+
+
+class OptJobTables:
+    """The mnn_opt_job tables of a job list, validated and built ONCE (at most OPT_MULTI_MAX_JOBS jobs per table): what the three grouped
+    optimiser ops launch from.  Holds the jobs, so the tensors behind the pointers live as long as the tables."""
+
+    def __init__(self, jobs, sgd=False, who="opt_job_tables"):
+        _req(isinstance(jobs, (list, tuple)) and len(jobs) >= 1, f"{who}: a non-empty list of jobs")
+        for j in jobs:
+            n = j["theta"].numel()
+            for t in (j["theta"], j["grad"]) + (() if sgd else (j["m"], j["v"])):
+                _req(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and n > 0, f"{who}: flat f32 buffers of equal size per job")
+            _req(j.get("step_dev") is not None, f"{who}: step_dev is required")
+            _step_ok(j["step_dev"])
+            sk, ld, lg = j.get("skipped"), j.get("ls_dyn"), j.get("ls_good")
+            _req(sk is None or (sk.dtype == torch.int32 and sk.numel() == 1), f"{who}: skipped int32[1]")
+            _req((ld is None) == (lg is None), f"{who}: ls_dyn and ls_good come together")
+            _req(ld is None or (ld.dtype == torch.float32 and ld.numel() == 2 and ld.is_contiguous() and lg.dtype == torch.int32 and lg.numel() == 1),
+                 f"{who}: ls_dyn f32[2], ls_good int32[1]")
+        self.jobs, self.sgd, self.tables = list(jobs), bool(sgd), []
+        for c in range(0, len(jobs), OPT_MULTI_MAX_JOBS):
+            chunk = jobs[c:c + OPT_MULTI_MAX_JOBS]
+            arr = (_lib.OptJob * len(chunk))()
+            for a, j in zip(arr, chunk):
+                a.theta, a.grad, a.m, a.v, a.n = _ptr(j["theta"]), _ptr(j["grad"]), _ptr(j.get("m")), _ptr(j.get("v")), j["theta"].numel()
+                a.step_dev, a.skipped, a.ls_dyn, a.ls_good = _ptr(j["step_dev"]), _ptr(j.get("skipped")), _ptr(j.get("ls_dyn")), _ptr(j.get("ls_good"))
+            self.tables.append(arr)
+
+
+def opt_job_tables(jobs, sgd=False):
+    """Prepare a job list for sumsq_multi / clip_adam_step_multi / step_increment_multi, which take the result in place of the list: a step
+    that calls all three validates and builds the tables once.  job = dict(theta, grad, m, v: flat f32 of one size (m, v None with sgd);
+    step_dev int32 [1]; skipped int32 [1] or None; ls_dyn f32 [2] + ls_good int32 [1] or both None).  sgd: m and v are not asked for (the
+    tables then serve clip_adam_step_multi(sgd=True) only)."""
+    return OptJobTables(jobs, sgd)
+
+
+def _opt_tables(jobs, sgd, who):
+    if isinstance(jobs, OptJobTables):
+        _req(sgd or not jobs.sgd, f"{who}: these tables were prepared for sgd (no m, v)")
+        return jobs.tables
+    return OptJobTables(jobs, sgd, who).tables
+
+
+def sumsq_multi(jobs, out):
+    """out[0] += sum over the jobs of sum(grad^2): ops.sumsq of every job's gradient in one launch per 16 jobs (mnn_sumsq_multi).
+    jobs: a list of job dicts, or opt_job_tables(jobs)."""
+    _req(out.dtype == torch.float32 and out.numel() >= 1, "sumsq_multi: out f32")
+    for arr in _opt_tables(jobs, True, "sumsq_multi"):
+        call("mnn_sumsq_multi", _stream(), len(arr), arr, _ptr(out))
+
+
+def clip_adam_step_multi(jobs, sumsq_buf, clip_norm, lr, beta1, beta2, eps, sgd=False):
+    """ops.clip_adam_step (its step_dev form) of every job behind the one norm word sumsq_buf, in one launch per 16 jobs
+    (mnn_clip_adam_step_multi): bit for bit the per-job calls.  jobs: a list of job dicts, or opt_job_tables(jobs)."""
+    for arr in _opt_tables(jobs, sgd, "clip_adam_step_multi"):
+        call("mnn_clip_adam_step_multi", _stream(), len(arr), arr, _ptr(sumsq_buf), float(clip_norm), float(lr), float(beta1), float(beta2),
+             float(eps), int(sgd))
+
+
+def step_increment_multi(jobs, sumsq_buf=None, clip_norm=0.0, grow_after=200):
+    """ops.step_increment of every job's step_dev (and ls_dyn / ls_good where the job has them) in one launch per 16 jobs.
+    jobs: a list of job dicts, or opt_job_tables(jobs)."""
+    for arr in _opt_tables(jobs, True, "step_increment_multi"):
+        call("mnn_step_increment_multi", _stream(), len(arr), arr, _ptr(sumsq_buf), float(clip_norm), int(grow_after))
+
+
+def segments_copy(segs):
+    """dst[:n] = src[:n] for a list of (src, dst, n) over flat f32 tensors, one launch per 16 segments (mnn_segments_copy)."""
+    _req(isinstance(segs, (list, tuple)) and len(segs) >= 1, "segments_copy: a non-empty list of (src, dst, n)")
+    for src, dst, n in segs:
+        for t in (src, dst):
+            _req(t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n > 0, "segments_copy: contiguous f32 buffers of at least n > 0 words")
+    for c in range(0, len(segs), OPT_MULTI_MAX_JOBS):
+        chunk = segs[c:c + OPT_MULTI_MAX_JOBS]
+        arr = (_lib.CopySeg * len(chunk))()
+        for a, (src, dst, n) in zip(arr, chunk):
+            a.src, a.dst, a.n = _ptr(src), _ptr(dst), int(n)
+        call("mnn_segments_copy", _stream(), len(arr), arr)
+
+
 def bias_grad(dY, db, accumulate=False):
     _rowmajor(dY, "bias_grad dY")
     _req(dY.dtype == torch.float32 and db.dtype == torch.float32 and db.numel() == dY.shape[1] and db.is_contiguous(), "bias_grad: shapes")

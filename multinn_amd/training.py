@@ -2,7 +2,8 @@
 
 ``compute_gradients(optimizer, loss_model, store)`` = global-norm clip + apply, on the flat
 buffer of a ParamStore, with ONE all-reduce of that buffer when torch.distributed is initialised
-(backend "nccl" is RCCL over xGMI on ROCm; "gloo" in CPU tests).
+(backend "nccl" is RCCL over xGMI on ROCm; "gloo" in CPU tests).  ``compute_gradients_multi`` is the same step over the several
+stores of a mode: one global norm, and still ONE all-reduce -- of a ``GradArena`` that holds every store's gradient.
 """
 
 import torch
@@ -123,20 +124,85 @@ def compute_gradients(optimizer, store, clip_norm=5.0, lr=None, reduce=True):
     return sumsq
 
 
-def compute_gradients_multi(optimizer, stores, clip_norm=5.0, lr=None, reduce=True):
+class GradArena:
+    """ONE flat f32 tensor holding the gradient segment of every store of a step, so that the step's data-parallel exchange is one
+    all-reduce whatever the number of stores (five generators, or M generators + the feedback module).  Segment i holds stores[i].grad and
+    starts on a multiple of 4 floats (16-byte accesses in the copy kernel and the collective); the gap words are zero, written once here and
+    never again.  pack(): every store.grad -> its segment; unpack(): back -- one mnn_segments_copy launch each, capture-safe.
+    A single store needs no arena: `flat` is its store.grad and pack / unpack do nothing."""
+
+    ALIGN = 4
+
+    @staticmethod
+    def key_of(stores):
+        """What an arena was laid out for: the stores, their gradient buffers (a re-materialised store has a new one) and sizes."""
+        return tuple((id(st), id(st.grad), int(st.grad.numel())) for st in stores)
+
+    def __init__(self, stores):
+        stores = list(stores)
+        if not stores or any(st.grad is None for st in stores):
+            raise ValueError("GradArena: every store must be materialised")
+        self.key = self.key_of(stores)
+        self.grads = [st.grad for st in stores]             # (held: the key's ids stay theirs while this arena lives)
+        self.sizes = [int(g.numel()) for g in self.grads]
+        self.offsets, off = [], 0
+        for n in self.sizes:
+            self.offsets.append(off)
+            off = (off + n + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        self.single = len(stores) == 1
+        self.flat = self.grads[0] if self.single else torch.zeros(off, device=self.grads[0].device, dtype=torch.float32)
+
+    def segment(self, i):
+        return self.flat[self.offsets[i]:self.offsets[i] + self.sizes[i]]
+
+    def pack(self):
+        if not self.single:
+            ops.segments_copy([(g, self.segment(i), n) for i, (g, n) in enumerate(zip(self.grads, self.sizes))])
+
+    def unpack(self):
+        if not self.single:
+            ops.segments_copy([(self.segment(i), g, n) for i, (g, n) in enumerate(zip(self.grads, self.sizes))])
+
+    @classmethod
+    def cached(cls, owner, stores):
+        """The arena of `stores`, kept on `owner` (a mode) as long as the stores and their gradient buffers stay the same."""
+        stores = list(stores)
+        arena = owner.__dict__.get("_grad_arena")
+        if arena is None or arena.key != cls.key_of(stores):
+            arena = owner.__dict__["_grad_arena"] = cls(stores)
+        return arena
+
+
+def _opt_job(st):
+    return dict(theta=st.theta, grad=st.grad, m=st.m, v=st.v, step_dev=st.step_dev, skipped=st.skipped, ls_dyn=st.ls_dyn, ls_good=st.ls_good)
+
+
+def compute_gradients_multi(optimizer, stores, clip_norm=5.0, lr=None, reduce=True, arena=None):
     """The optimiser step of a mode that trains SEVERAL generators on one loss (multinn_jamming.py:235-241: `compute_gradients(optimizer,
     mean track loss, all generators' + feedback variables)`): ONE global norm over every store's gradient (training.py:166 clips the
-    whole variable list together), then the clipped TF-Adam step per store.  Each store's flat gradient is summed over the ranks first
-    (data parallel).  Returns the device scalar holding the global sum of squares."""
-    if reduce:
-        for st in stores:
-            allreduce_flat(st.grad)
+    whole variable list together), then the clipped TF-Adam step of every store -- three grouped launches (mnn_sumsq_multi,
+    mnn_clip_adam_step_multi, mnn_step_increment_multi) whatever the number of stores.  reduce, under data parallelism: the gradients are
+    summed over the ranks first, by ONE allreduce_flat of `arena` (pack -> all-reduce -> unpack), the GradArena laid out for exactly these
+    stores, which the caller keeps (GradArena.cached(owner, stores): the one place an arena is made and cached); a single store is
+    exchanged in place and needs none.  Afterwards every store.grad holds the summed gradient.  reduce=False: the three launches only
+    (the caller has exchanged the gradients).  Returns the device scalar holding the global sum of squares."""
+    stores = list(stores)
+    if reduce and dp_active():
+        if arena is None and len(stores) == 1:
+            allreduce_flat(stores[0].grad)
+        else:
+            if arena is None or len(arena.grads) != len(stores) or any(g is not st.grad for g, st in zip(arena.grads, stores)):
+                raise ValueError("compute_gradients_multi: under data parallelism several stores are exchanged through their gradient "
+                                 "arena: pass arena=GradArena.cached(owner, stores)")
+            arena.pack()
+            allreduce_flat(arena.flat)
+            arena.unpack()
     sumsq = torch.zeros(1, device=stores[0].grad.device)
+    jobs = ops.opt_job_tables([_opt_job(st) for st in stores], optimizer.sgd)        # validated and built once for the three launches
+    ops.sumsq_multi(jobs, sumsq)                        # accumulates (one f32 atomic add per workgroup into the one word)
     for st in stores:
-        ops.sumsq(st.grad, sumsq)                       # accumulates (f32 atomic add into the one word)
-    for st in stores:
-        st.step += 1
-        ops.clip_adam_step(st.theta, st.grad, st.m, st.v, sumsq, clip_norm, optimizer.lr if lr is None else lr,
-                           optimizer.beta1, optimizer.beta2, optimizer.epsilon, st.step, optimizer.sgd, st.step_dev, st.skipped)
-        ops.step_increment(st.step_dev, sumsq, clip_norm, st.ls_dyn, st.ls_good, st.LS_GROW_AFTER)
+        st.step += 1                                    # host mirror; the kernels read the step count from store.step_dev ON DEVICE
+    ops.clip_adam_step_multi(jobs, sumsq, clip_norm, optimizer.lr if lr is None else lr, optimizer.beta1, optimizer.beta2, optimizer.epsilon,
+                             optimizer.sgd)
+    ops.step_increment_multi(jobs, sumsq, clip_norm, stores[0].LS_GROW_AFTER)
     return sumsq
